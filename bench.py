@@ -16,6 +16,14 @@ Multi-GPU: one process per GPU (torch.distributed, backend nccl = RCCL); streams
 there is no data-path collective -- only the closing barrier and a stats all-reduce.  Weak scaling:
 per-GPU work is fixed.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what `value` needs: it generates the
+inputs -- 32 distinct streams per GPU (seeds 1000..1031), each used 8 times, so that its setup stays
+short --, prepares, warms up, times the K steps and prints the line.  `--full` adds everything else as
+before: all 256 streams distinct on one GPU, the parity gate against the generator's reconstruction,
+per-kernel durations and the roofline, the K6 pack, the prepare-inclusive rates, the contract's other
+configurations and the CPU baseline.  `--dump-outputs DIR` writes a fixed, seeded sample of the frames
+the last timed step decoded (float32 .npy files, under 64 MB) for output-for-output comparisons.
+
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -113,6 +121,39 @@ def gen_stream(args):
 
 
 GEN_CORE_SECONDS_1080P_GOP = 29.0  # measured: one 1080p GOP-30 C3 stream on one host core of the GPU node (round 3: 256 streams, 62 threads, 121 s)
+
+
+LEAN_DISTINCT = 32  # distinct streams of a plain N = 1 run: one or two generator rounds on a 16-core host, not the ~70 s that 256 take
+
+
+def default_distinct(streams, world, full):
+    """Distinct streams a rank generates when --distinct is not given: all of them for --full on one GPU, 32 otherwise --
+    a plain run's setup stays short, and N > 1 ranks share one host's cores."""
+    return max(1, min(streams if (world == 1 and full) else (LEAN_DISTINCT if world == 1 else 32), streams))
+
+
+DUMP_SEED = 20260101
+DUMP_WHOLE_BYTES = 40_000_000  # whole float32 frames: at most this many bytes (two cropped 1080p frames: 24.9 MB)
+DUMP_SAMPLED_FRAMES, DUMP_SAMPLES_PER_FRAME = 64, 65536  # 64 x 65536 float32 samples: 16.8 MB
+
+
+def dump_outputs(dec, out_dir, n_streams, n_frames):
+    """What the last executed step handed its caller, as float32 / float64 .npy files under `out_dir` (under 64 MB in all): the cropped
+    I420 frames of the first stream's first picture and the last stream's last picture whole, 65536 seeded sample positions of 64 seeded
+    (stream, frame) pairs, and every stream's status.  The choices depend on the seed and the batch shape only."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    n = dec.read_frame_tight(0, 0, crop=True).size
+    whole = [(0, 0), (n_streams - 1, n_frames - 1)][:max(0, min(2, DUMP_WHOLE_BYTES // (4 * n)))]
+    frames = np.stack([dec.read_frame_tight(s, f, crop=True).astype(np.float32) for s, f in whole]) if whole else np.zeros((0, n), np.float32)
+    picks = rng.choice(n_streams * n_frames, size=min(DUMP_SAMPLED_FRAMES, n_streams * n_frames), replace=False)
+    pairs = [(int(p) // n_frames, int(p) % n_frames) for p in picks]
+    samples = np.stack([dec.read_frame_tight(s, f, crop=True)[rng.integers(0, n, DUMP_SAMPLES_PER_FRAME)].astype(np.float32) for s, f in pairs])
+    np.save(os.path.join(out_dir, "frames.npy"), frames)
+    np.save(os.path.join(out_dir, "frame_index.npy"), np.asarray(whole, np.float64).reshape(-1, 2))
+    np.save(os.path.join(out_dir, "samples.npy"), samples)
+    np.save(os.path.join(out_dir, "sample_index.npy"), np.asarray(pairs, np.float64).reshape(-1, 2))
+    np.save(os.path.join(out_dir, "stream_status.npy"), np.asarray([dec.stream_status(s) for s in range(n_streams)], np.float64))
 
 
 def generation_threads(n_distinct, world):
@@ -423,6 +464,8 @@ def run_strong(args, H, torch, dist, rank, world, local_rank):
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs and rank == 0 and S > 0:
+        dump_outputs(dec, args.dump_outputs, S, F * D)
     red = allreduce_stats({"ranks": 1, "frames": S * G * F * args.steps, "pixels": S * G * F * args.steps * args.width * args.height,
                            "bytes_in": sum(len(x) for bt in batches for x in bt) * args.steps, "seconds": elapsed}, device="cuda" if (dist and dist.get_backend() == "nccl") else None)
     dec.close()
@@ -451,13 +494,18 @@ def main():
     ap.add_argument("--frames", type=int, default=30, help="frames per stream per step (one GOP)")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--distinct", type=int, default=0, help="distinct synthetic streams generated per GPU (0 = all of them, SURVEY 8d C5: seeds 1000 + global stream index); fewer are replicated")
+    ap.add_argument("--distinct", type=int, default=0, help="distinct synthetic streams generated per GPU (0 = the default: %d in a plain run, with --full all of them on one GPU, "
+                                                            "SURVEY 8d C5: seeds 1000 + global stream index; 32 per rank on N > 1); fewer are replicated" % LEAN_DISTINCT)
+    ap.add_argument("--full", action="store_true", help="everything beside `value`: all streams distinct on one GPU, the parity gate, per-kernel durations and the roofline, K6 pack, "
+                                                        "end-to-end and pipelined-ingest rates, the contract's other configurations, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write a fixed, seeded sample of the frames the last step decoded to DIR/*.npy "
+                                                                        "(float32 / float64, under 64 MB in all)")
     ap.add_argument("--total-streams", type=int, default=0, help="STRONG scaling: this many streams in total, sharded over the GPUs (LPT on stream bytes); "
                                                                   "each stream is --gops GOPs long and a step decodes all of it, in batches deep enough to fill a GPU")
     ap.add_argument("--gops", type=int, default=8, help="GOPs per stream and step in the strong-scaling mode")
-    ap.add_argument("--no-extra", action="store_true", help="skip the c5_share (32 streams per GPU) and single_stream (C3: 1 stream x 300 frames) measurements")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the c5_share (32 streams per GPU) and single_stream (C3: 1 stream x 300 frames) measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity gate")
     ap.add_argument("--serialized", action="store_true", help="profiling aid: the timed passes run in the library's profiling mode (stages back to back on one stream), so that "
                                                               "a kernel trace of this command shows uncontended kernel durations -- the quantity `roofline.launch_ms` is; `value` is then not the contract's")
     ap.add_argument("--max-ref-frames", type=int, default=0, help="h264mi_config.max_ref_frames of the bench decoder (0 = the default of 16 reference slots per stream; "
@@ -494,7 +542,7 @@ def main():
             dist.init_process_group(os.environ.get("H264MI_BENCH_BACKEND", "nccl" if torch.cuda.is_available() else "gloo"))
         red = allreduce_stats({"frames": 1.0, "ranks": 1.0, "seconds": float(rank)})
         if rank == 0:
-            nd_plan = max(1, min(args.distinct or (args.streams if world == 1 else 32), args.streams))
+            nd_plan = max(1, min(args.distinct or default_distinct(args.streams, world, args.full), args.streams))
             print(json.dumps({"dry_run": True, "n_gpus": world, "ranks_seen": int(red["ranks"]), "slowest_rank_seconds": red["seconds"],
                               "distinct_streams_per_rank": nd_plan, "generator_threads_per_rank": generation_threads(nd_plan, world),
                               "planned_generation_s": round(planned_generation_seconds(nd_plan, world, frames=args.frames), 1)}))
@@ -519,16 +567,17 @@ def main():
     if args.total_streams > 0:
         return run_strong(args, H, torch, dist, rank, world, local_rank)
     S, F = args.streams, args.frames
-    # Distinct streams per rank: all of them on one GPU.  With N > 1 every rank generates its own inputs on the SAME host: 8 x 256
+    # Distinct streams per rank: all of them on one GPU with --full.  With N > 1 every rank generates its own inputs on the SAME host: 8 x 256
     # distinct 1080p GOPs are ~16 core-hours of generator time, more than the bench's time limit on any host -- so a rank generates 32 distinct
     # streams by default (each used 8 times; --distinct overrides) with its share of the host's cores, and the line says so (config.workload).
-    nd = max(1, min(args.distinct or (S if world == 1 else 32), S))
+    # A plain run on one GPU does the same: 256 distinct GOPs are ~70 s of generation on 16 cores, 32 take one or two generator rounds.
+    nd = max(1, min(args.distinct or default_distinct(S, world, args.full), S))
     gen_threads = generation_threads(nd, world)
     # ---- synthetic inputs (not timed) ----
     t0 = time.time()
     seeds = [1000 + rank * S + i for i in range(nd)]
     # (the inputs of the contract's other configurations -- extra_configs: C2, C4 -- are generated by the same pool, longest jobs first)
-    jobs_x = [] if (args.no_extra or world > 1) else [(4000 + i, 30, 3840, 2160, {"recipe": "C4", "idr_period": 30}) for i in range(2)] + \
+    jobs_x = [] if (not args.full or args.no_extra or world > 1) else [(4000 + i, 30, 3840, 2160, {"recipe": "C4", "idr_period": 30}) for i in range(2)] + \
         [(2000 + i, 60, 1280, 720, {"recipe": "C2", "idr_period": 1}) for i in range(8)]
     with ThreadPoolExecutor(max_workers=gen_threads) as ex:
         fx = [ex.submit(gen_stream, j) for j in jobs_x]
@@ -552,8 +601,8 @@ def main():
     assert info.n_frames == S * F, (info.n_frames, S * F)
 
     # ---- parity gate before any timing: GPU output == generator reconstruction, bit for bit ----
-    parity = "skipped"
-    if not args.no_parity:
+    parity = "skipped" if args.full else "not checked in a plain run (--full checks it)"
+    if args.full and not args.no_parity:
         dec.execute()
         dec.sync()
         import hashlib
@@ -593,6 +642,25 @@ def main():
     ranks_seen = int(red.get("ranks", 1))
     fps = total_frames / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(dec, args.dump_outputs, S, F)
+    workload = "%dx%d Main CABAC IPPP GOP-%d, %d independent streams per GPU (%d distinct%s), QP 28, 1 slice/frame, 1 ref" % (
+        args.width, args.height, F, S, nd, "" if nd == S else ", each used %d times%s" % (-(-S // nd), ": %d ranks generate their inputs on one host" % world if world > 1 else ""))
+    config = {"workload": workload, "frames_per_step_per_gpu": S * F, "bytes_per_frame": round(bytes_per_frame, 1), "parallelism": "streams sharded, no collective"}
+    if not args.full:
+        # a plain run ends here: the line carries `value` and what describes it; everything else is --full's
+        dec.close()
+        del dec
+        if rank == 0:
+            print(json.dumps({
+                "metric": "1080p Main CABAC frames/sec", "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+                "data": "synthetic", "full": False, "config": config, "mpixels_per_s": round(fps * args.width * args.height / 1e6, 1), "roofline": None,
+                "cpu_baseline": None, "parity": parity, "host_prepare_ms": round(prepare_s * 1e3, 2), "stream_gen_s": round(gen_s, 1),
+                "stream_gen_note": "slowest rank; %d distinct streams per rank on %d generator threads" % (nd, gen_threads)}))
+        if dist:
+            dist.destroy_process_group()
+        return
 
     # ---- per-kernel durations: HIP events on the launch stream around every launch of 2 more passes
     # (profiling mode runs the stages back to back on one stream so that intervals are per kernel) ----
@@ -755,12 +823,11 @@ def main():
         "vs_baseline": None,
         "dtype": "u8",
         "data": "synthetic",
+        "full": True,
         "value_with_pack": (k_pack or {}).get("value_with_pack"),
         "value_note": "`value`: K passes of h264mi_batch_execute over a batch resident in HBM (entropy decode -> reconstruction -> deblocked frames in the frame pool); "
                       "`value_with_pack` adds the K6 crop + pack launch of the whole batch to every step; host parse + H2D are in `end_to_end_fps` / `pipelined_ingest_fps`",
-        "config": {"workload": "%dx%d Main CABAC IPPP GOP-%d, %d independent streams per GPU (%d distinct%s), QP 28, 1 slice/frame, 1 ref"
-                               % (args.width, args.height, F, S, nd, "" if nd == S else ", each used %d times: %d ranks generate their inputs on one host" % (-(-S // nd), world)),
-                   "frames_per_step_per_gpu": S * F, "bytes_per_frame": round(bytes_per_frame, 1), "parallelism": "streams sharded, no collective"},
+        "config": config,
         "mpixels_per_s": round(fps * args.width * args.height / 1e6, 1),
         "roofline": roofline,
         "cpu_baseline": cpu_baseline,

@@ -55,13 +55,12 @@ def H():
     return h264decode_amd
 
 
-REAL_MP4 = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/realshort.mp4"
+# imageio's public sample clip realshort.mp4 (x264, High profile, 320x240), stored under tests/golden/
+REAL_MP4 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "realshort.mp4")
 
 
 @pytest.fixture(scope="session")
 def real_stream():
-    if not os.path.exists(REAL_MP4):
-        pytest.skip("third-party sample MP4 not present on this machine")
     from mp4util import mp4_to_annexb
     return mp4_to_annexb(open(REAL_MP4, "rb").read())
 

@@ -1,6 +1,6 @@
-"""Minimal MP4 (ISO BMFF) -> Annex-B rewrap for the optional third-party real-stream tests.
+"""Minimal MP4 (ISO BMFF) -> Annex-B rewrap for the third-party real-stream tests.
 
-Not part of the product; used only to feed local sample MP4s (if present) to the oracle /
+Not part of the product; used only to feed the sample MP4 stored under tests/golden/ to the oracle /
 decoder.  Finds the first 'avc1' track, reads avcC (SPS/PPS, NAL length size) and the sample
 tables (stsz/stco/co64/stsc) and emits start-code delimited NAL units."""
 import struct

@@ -5,6 +5,8 @@ import json
 import os
 import re
 
+import pytest
+
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 
 
@@ -65,3 +67,49 @@ def test_eight_rank_input_generation_fits_the_time_limit():
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 8 and d["ranks_seen"] == 8 and d["distinct_streams_per_rank"] == 32
     assert d["generator_threads_per_rank"] == bench.generation_threads(32, 8)
+
+
+def test_plain_run_generates_few_distinct_streams_and_full_all_of_them():
+    """A plain run's setup is short: 32 distinct 1080p streams per GPU (each used 8 times), not the 256 that --full generates on one GPU."""
+    import subprocess
+    import sys
+    for extra, want in (([], 32), (["--full"], 256)):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run"] + extra, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["n_gpus"] == 1 and d["distinct_streams_per_rank"] == want, (extra, d)
+
+
+@pytest.mark.gpu
+def test_gpu_plain_run_dumps_what_its_last_step_decoded(tmp_path, oracle_mod, sg):
+    """bench.py --dump-outputs DIR: float32 / float64 arrays under 64 MB, the same from run to run, and the whole frames among them are the
+    oracle's decode of the generated streams (stream 0 frame 0, the last stream's last frame).  The line says how many steps it timed."""
+    import subprocess
+    import sys
+    import numpy as np
+    S, F, W, Hh = 8, 4, 320, 240
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--streams", str(S), "--frames", str(F),
+               "--width", str(W), "--height", str(Hh), "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd=ROOT, env=dict(os.environ, H264MI_BENCH_CACHE="off"))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False and line["unit"] == "frames/s" and line["higher_is_better"] is True
+        assert abs(line["value"] - S * F / (line["ms_per_step"] * 1e-3)) / line["value"] < 0.02
+        files = sorted(os.listdir(d))
+        assert files and sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64e6
+        arrs = {f: np.load(os.path.join(d, f), allow_pickle=False) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])
+    a = dumps[0]
+    assert (a["stream_status.npy"] == 0).all() and a["stream_status.npy"].shape == (S,)
+    assert a["frame_index.npy"].tolist() == [[0, 0], [S - 1, F - 1]]
+    for (s, f), got in zip(a["frame_index.npy"].astype(int), a["frames.npy"]):
+        stream = sg.encode(**sg.recipe("C3", frames=F, idr_period=F, seed=1000 + s, width=W, height=Hh))[0]
+        ref, _ = oracle_mod.decode(stream, crop=True)
+        assert np.array_equal(got, ref[f].astype(np.float32)), (s, f)

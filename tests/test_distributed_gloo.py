@@ -120,8 +120,8 @@ def test_gpu_bench_two_ranks_rehearsal():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict({k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}, H264MI_BENCH_DEVICE="0", H264MI_BENCH_BACKEND="gloo")
-    # no launcher: bench.py --gpus 2 starts its two ranks itself
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--streams", "8", "--frames", "4", "--width", "320", "--height", "240"]
+    # no launcher: bench.py --gpus 2 starts its two ranks itself; --full: the parity gate and the measurements after the timed steps run on both ranks too
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--streams", "8", "--frames", "4", "--width", "320", "--height", "240", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -403,11 +403,9 @@ def test_gpu_residual_pool_exhaustion_of_an_older_batch_is_reported_not_repeated
 def test_gpu_rejects_out_of_scope_profile(H):
     """A third-party High 4:4:4 Predictive stream (chroma_format_idc 3) must be refused with a clear status, not mis-decoded."""
     import os
-    from mp4util import mp4_to_annexb
-    path = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/cockatoo.mp4"
-    if not os.path.exists(path):
-        pytest.skip("third-party sample MP4 not present on this machine")
-    stream = mp4_to_annexb(open(path, "rb").read())
+    # the first 400000 bytes of imageio's public sample clip cockatoo.mp4 rewrapped as Annex B (tests/mp4util.py), stored under tests/golden/
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cockatoo_head.h264")
+    stream = open(path, "rb").read()
     dec = H.Decoder(max_streams=1, max_width=1280, max_height=720, max_frames_per_batch=8, max_slices_per_frame=4)
     with pytest.raises(H.H264MIError) as ei:
         dec.decode([stream[:400000]])

@@ -7,7 +7,7 @@ for lib in "$@"; do
   name=$(basename "${lib:-default}" .so)
   out=$R/gpurun_out/$tag/$name
   mkdir -p $out
-  H264MI_LIB=${lib:+$R/$lib} timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 $R/bench.py --distinct 32 --no-extra --no-cpu-baseline --no-parity --steps 3 > $out.json 2> $out.err || tail -3 $out.err
+  H264MI_LIB=${lib:+$R/$lib} timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 $R/bench.py --full --distinct 32 --no-extra --no-cpu-baseline --no-parity --steps 3 > $out.json 2> $out.err || tail -3 $out.err
   echo "== $name"
   python3 - $out <<'PY'
 import csv, glob, sys

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for g in "$@"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $g --output-format csv -d $out/g$i -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-parity --no-extra $bargs > $out/g$i.json 2> $out/g$i.err || { echo "group $i ($g) failed:"; tail -2 $out/g$i.err; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $g --output-format csv -d $out/g$i -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-parity --no-extra $bargs > $out/g$i.json 2> $out/g$i.err || { echo "group $i ($g) failed:"; tail -2 $out/g$i.err; }
 done
 python3 - $out <<'PY'
 import collections, csv, glob, os, sys

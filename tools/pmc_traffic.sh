@@ -9,6 +9,6 @@ out=$R/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 500 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/$c -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-parity "$@" > $out/$c.json 2> $out/$c.err || tail -3 $out/$c.err
+  timeout -k 10 500 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/$c -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-parity "$@" > $out/$c.json 2> $out/$c.err || tail -3 $out/$c.err
 done
 python3 $R/tools/pmc_traffic_summary.py $out "$@"

@@ -7,10 +7,10 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$R/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o $tag -- python3 $R/bench.py --steps 3 --no-cpu-baseline --no-extra > $out/stats_bench.json 2> $out/stats.err; echo "stats rc=$?"
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o $tag -- python3 $R/bench.py --full --steps 3 --no-cpu-baseline --no-extra > $out/stats_bench.json 2> $out/stats.err; echo "stats rc=$?"
 find $out/stats -name "*kernel_stats.csv" -exec cp {} $out/${tag}_kernel_stats.csv \;
 echo "--- kernel stats"; head -12 $out/${tag}_kernel_stats.csv
 cd $R && bash tools/pmc_traffic.sh ${tag}_traffic --distinct 8 --no-extra > $out/${tag}_pmc_traffic.txt 2>&1; echo "traffic rc=$?"; tail -12 $out/${tag}_pmc_traffic.txt
-cd $R && bash tools/pmc_run.sh ${tag}_mix bench.py --distinct 8 --no-extra --no-cpu-baseline --no-parity --steps 2 > $out/${tag}_pmc_instruction_mix.txt 2>&1; echo "mix rc=$?"; grep -A8 "^k_inter\|^k_deblock\|^k_dbprep" $out/${tag}_pmc_instruction_mix.txt | head -60
+cd $R && bash tools/pmc_run.sh ${tag}_mix bench.py --full --distinct 8 --no-extra --no-cpu-baseline --no-parity --steps 2 > $out/${tag}_pmc_instruction_mix.txt 2>&1; echo "mix rc=$?"; grep -A8 "^k_inter\|^k_deblock\|^k_dbprep" $out/${tag}_pmc_instruction_mix.txt | head -60
 cp $R/profiles/pmc_traffic.json $out/pmc_traffic.json
 rm -rf $out/stats $R/gpurun_out/${tag}_traffic/FETCH_SIZE $R/gpurun_out/${tag}_traffic/WRITE_SIZE $R/gpurun_out/${tag}_mix/p1 $R/gpurun_out/${tag}_mix/p2
