@@ -392,11 +392,45 @@ FI uint32_t cabac_decide(Ent &e, uint32_t &reg, int idx_) {
     cabac_refill(e); // RenormD: the scaled range stays as it is, only the scale moves
     return vst ^ diff; // the bin is the complement of the sign: valMPS on the MPS path (diff negative), !valMPS otherwise
 }
+// DecodeDecision + RenormD on lane `idx_` of the residual working set WITHOUT the state transition: the significance map of a ctxBlockCat 0..4 block
+// decodes each of its contexts at most once (ctxIdxInc = the scan position), so no successor state is read before the block ends, and wk_advance()
+// moves all the lanes the map used in one lane-parallel step.  Saves the v_trans read, the two candidate successors and the two selects per bin.
+// And as the states stand still during the map, their rangeTabLPS rows are gathered for all lanes before it (wk_lane_table(v_rlps) -> rlw): the
+// state and its row are then two independent lane reads, not a lane read whose result selects the lane of the next one.
+FI uint32_t cabac_decide_once(Ent &e, uint32_t rlw, int idx_) {
+    MI_COUNT_BIN(e);
+    const int idx = RFL(idx_);
+    const uint32_t st = RDL(e.wk, idx);
+    const uint32_t rl4 = RDL(rlw, idx);
+    const uint32_t rlps = __builtin_amdgcn_perm(rl4, 0u, e.range >> (e.avail + 6)) << e.avail;
+    const uint32_t rmps = e.range - rlps;
+    const bool lps = e.value >= rmps;
+    const uint32_t diff = e.value - rmps;
+    e.value = min(e.value, diff);
+    e.range = lps ? rlps : rmps;
+    cabac_refill(e);
+    return st ^ diff;
+}
+// The deferred transition of cabac_decide_once(): every lane of wk in `used` goes to its successor for the bin in `ones` (lanes 0..31 only).  The same
+// state arithmetic as cabac_decide(), per lane, with the v_trans entry fetched through ds_bpermute (the state selects its lane modulo 64, as there).
+// `tr` is fetched apart from the update so that the caller can issue it early and let the LDS latency pass under other work.
+FI uint32_t wk_lane_table(const Ent &e, uint32_t table) { return static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(static_cast<int>((e.wk & 63u) << 2), static_cast<int>(table))); }
+FI void wk_advance(Ent &e, uint32_t tr, uint64_t used, uint64_t ones) {
+    const uint32_t st = e.wk;
+    uint32_t next_mps;
+    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "=v"(next_mps) : "v"(tr), "v"(st));
+    const uint32_t next_lps = tr ^ st;
+    uint32_t bin = 0; // bit 6: this lane's bin, lined up with valMPS in the state
+    asm("v_cndmask_b32_e64 %0, %0, 64, %1" : "+v"(bin) : "s"(ones));
+    const uint32_t next = ((bin ^ st) & 64u) ? next_lps : next_mps;
+    asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(e.wk) : "v"(next), "s"(used));
+}
 // a bin as a branch condition (v_cmp + s_cbranch_vcc) / as a scalar integer
 #define BIN_A(e, ctx) UNI(static_cast<int>(cabac_decide(e, (e).ca, (ctx))) >= 0)          /* ctxIdx 0..63 */
 #define BIN_B(e, ctx) UNI(static_cast<int>(cabac_decide(e, (e).cb, (ctx) - 64)) >= 0)     /* ctxIdx 64..124 */
 #define BIN_T8(e, inc) UNI(static_cast<int>(cabac_decide(e, (e).cb, 61 + (inc))) >= 0)    /* ctxIdx 399..401 */
 #define BIN_W(e, lane) UNI(static_cast<int>(cabac_decide<true>(e, (e).wk, (lane))) >= 0)        /* residual working set */
+#define BIN_1(e, rlw, lane) UNI(static_cast<int>(cabac_decide_once(e, (rlw), (lane))) >= 0)      /* residual working set, transition deferred */
 #define BINI_A(e, ctx) static_cast<int>(RFL(~cabac_decide(e, (e).ca, (ctx)) >> 31))
 #define BINI_B(e, ctx) static_cast<int>(RFL(~cabac_decide(e, (e).cb, (ctx) - 64) >> 31))
 #define BINI_T8(e, inc) static_cast<int>(RFL(~cabac_decide(e, (e).cb, 61 + (inc)) >> 31))
@@ -483,6 +517,9 @@ FI int cabac_residual(Ent &e, int16_t *dst, int cat_, int cbf_inc) {
         e.wk_cat = cat, e.wk_c0 = c0n;
     }
     const uint32_t c0 = e.wk_c0;
+    // the lane tables of the deferred significance map (cabac_decide_once, wk_advance), gathered while coded_block_flag is decoded: that bin reads cb, and the
+    // wk states stand still until the map is over
+    const uint32_t rlw = wk_lane_table(e, e.v_rlps), tr = wk_lane_table(e, e.v_trans);
     if (cat != 5 && !BIN_B(e, 64 + ((c0 >> 8) & 255) + cbf_inc)) {
         MI_R(e, 2);
         return 0;
@@ -497,7 +534,8 @@ FI int cabac_residual(Ent &e, int16_t *dst, int cat_, int cbf_inc) {
     // significance map; a set last_significant_coeff_flag ends the loop through the index itself (a jump out of the loop costs the compiler's
     // structurizer more than the select), running off the end means the final coefficient is significant by inference.
     // (ctxIdxInc of a 4x4 / 2x2 block is the scan position itself: Min(numDecod / NumC8x8, 2) only bites with 4:2:2 chroma DC blocks.)
-    if (is8) {
+    uint64_t used = 0, ones = 0;
+    if (is8) { // (Table 9-43 maps several scan positions to one context: the transition stays immediate)
         for (i = 0; i < last; i++) {
             const uint32_t m = RDL(e.v_maps, i);
             if (BIN_W(e, m & 255)) {
@@ -507,11 +545,18 @@ FI int cabac_residual(Ent &e, int16_t *dst, int cat_, int cbf_inc) {
         }
     } else {
         for (i = 0; i < last; i++) {
-            if (BIN_W(e, i)) {
+            if (BIN_1(e, rlw, i)) {
                 sig |= 0x8000000000000000ull >> i;
-                if (BIN_W(e, 16 + i)) i = 64;
+                if (BIN_1(e, rlw, 16 + i)) i = 64;
             }
         }
+        // which lanes the map decoded, and their bins, follow from the map itself: significant_coeff_flag at scan positions 0 .. reach - 1 (bin =
+        // significance), last_significant_coeff_flag at every significant one (bin 1 only where the loop ended on it, at reach - 1)
+        const uint32_t s0 = static_cast<uint32_t>(__builtin_bitreverse64(sig)); // bit j: scan position j is significant (before the inference below)
+        const bool ran_off = i == last;
+        const int reach = ran_off ? last : 32 - __builtin_clz(s0 | 1u); // (s0 != 0 when a last flag ended the loop)
+        used = ((1u << reach) - 1u) | s0 << 16;
+        ones = s0 | (ran_off ? 0u : 1u << (15 + reach));
     }
     if (i == last) sig |= 0x8000000000000000ull >> last;
     MI_R(e, 0);
@@ -537,6 +582,7 @@ FI int cabac_residual(Ent &e, int16_t *dst, int cat_, int cbf_inc) {
         lv = lrev == k ? v : lv;
     }
     MI_R(e, 1);
+    if (!is8) wk_advance(e, tr, used, ones); // (after the levels, which touch lanes 32..41 only) before the block ends: the next block, or a category switch, reads these lanes
     {
         const uint32_t pos = __builtin_amdgcn_ubfe(e.v_pos, (c0 >> 17) & 0x18u, 8); // the byte of the category's position mode: one bit-field extract, no branch
         if (lv != 0) dst[pos] = static_cast<int16_t>(lv);
