@@ -24,9 +24,11 @@ static int fail(const char *what, int code) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch]\n", argv[0]);
+        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal]\n", argv[0]);
         return 2;
     }
+    int conceal = 0; /* --conceal (last argument): h264mi_config.conceal_errors */
+    if (argc > 3 && !strcmp(argv[argc - 1], "--conceal")) conceal = 1, argc--;
     const int per_batch = argc > 3 ? atoi(argv[3]) : 30;
     FILE *f = fopen(argv[1], "rb");
     if (!f) return fail("fopen", -1);
@@ -62,6 +64,7 @@ int main(int argc, char **argv) {
     h264mi_config cfg = H264MI_CONFIG_INIT; /* zero-initialised, struct_size = this build's sizeof */
     cfg.max_streams = 1, cfg.max_width = sps.width, cfg.max_height = sps.height;
     cfg.max_frames_per_batch = per_batch, cfg.max_slices_per_frame = 32, cfg.max_bitstream_bytes = len + (1 << 20);
+    cfg.conceal_errors = conceal;
     h264mi_decoder *dec = NULL;
     if ((r = h264mi_decoder_create(&cfg, &dec)) != H264MI_OK) return fail("h264mi_decoder_create", r);
 
@@ -148,6 +151,10 @@ int main(int argc, char **argv) {
         if (i < n && (nals[i].type == 1 || nals[i].type == 5)) seen_vcl = 1;
     }
     fclose(out);
+    if (conceal) { /* the totals live in the decoder: ask before it is destroyed */
+        int64_t cs = 0, cm = 0;
+        if (h264mi_decoder_concealed(dec, &cs, &cm) == H264MI_OK) fprintf(stderr, "concealed: %lld slices, %lld macroblocks\n", (long long)cs, (long long)cm);
+    }
     h264mi_decoder_destroy(dec);
     fprintf(stderr, "%s: %ld frames %dx%d -> %s\n", h264mi_version(), total, sps.width, sps.height, argv[2]);
     return 0;

@@ -334,6 +334,7 @@ type Config struct {
 	MaxRefFrames, CoefBlocksPerMb                                                  int // 0 = defaults (16 reference slots per stream, 8 residual blocks per macroblock)
 	BPictures                                                                      int // 1 = the buffers only B pictures need exist from the start (h264mi_config.b_pictures)
 	AllowUnpinnedFieldCabac                                                        int // 1 = CABAC field pictures are decoded with the unpinned context tables (h264mi_config.allow_unpinned_field_cabac)
+	ConcealErrors                                                                  int // 1 = lost macroblocks of non-IDR frame pictures are copied from a reference picture (h264mi_config.conceal_errors)
 }
 type Decoder struct{ h *C.h264mi_decoder }
 type BatchInfo struct {
@@ -346,7 +347,8 @@ func NewDecoder(cfg Config) (*Decoder, error) {
 	c := C.h264mi_config{struct_size: C.uint32_t(C.sizeof_h264mi_config), device: C.int32_t(cfg.Device), max_streams: C.int32_t(cfg.MaxStreams), max_width: C.int32_t(cfg.MaxWidth),
 		max_height: C.int32_t(cfg.MaxHeight), max_frames_per_batch: C.int32_t(cfg.MaxFramesPerBatch),
 		max_slices_per_frame: C.int32_t(cfg.MaxSlicesPerFrame), max_bitstream_bytes: C.int64_t(cfg.MaxBitstreamBytes),
-		max_ref_frames: C.int32_t(cfg.MaxRefFrames), coef_blocks_per_mb: C.int32_t(cfg.CoefBlocksPerMb), b_pictures: C.int32_t(cfg.BPictures), allow_unpinned_field_cabac: C.int32_t(cfg.AllowUnpinnedFieldCabac)}
+		max_ref_frames: C.int32_t(cfg.MaxRefFrames), coef_blocks_per_mb: C.int32_t(cfg.CoefBlocksPerMb), b_pictures: C.int32_t(cfg.BPictures), allow_unpinned_field_cabac: C.int32_t(cfg.AllowUnpinnedFieldCabac),
+		conceal_errors: C.int32_t(cfg.ConcealErrors)}
 	d := &Decoder{}
 	if err := status(C.h264mi_decoder_create(&c, &d.h)); err != nil {
 		return nil, err
@@ -374,6 +376,24 @@ func (d *Decoder) DecodeBatch(chunks [][]byte) (BatchInfo, error) {
 	}
 	return BatchInfo{Frames: int(info.n_frames), Slices: int(info.n_slices), Width: int(info.width), Height: int(info.height),
 		CodedWidth: int(info.coded_width), CodedHeight: int(info.coded_height)}, nil
+}
+
+// FrameConcealed: macroblocks of a frame of the last batch that error concealment filled in (h264mi_frame_concealed).
+func (d *Decoder) FrameConcealed(stream, frame int) (int, error) {
+	var n C.int32_t
+	if err := status(C.h264mi_frame_concealed(d.h, C.int32_t(stream), C.int32_t(frame), &n)); err != nil {
+		return 0, err
+	}
+	return int(n), nil
+}
+
+// Concealed: slices and macroblocks concealed since the decoder was created (h264mi_decoder_concealed).
+func (d *Decoder) Concealed() (slices, macroblocks int64, err error) {
+	var s, m C.int64_t
+	if err = status(C.h264mi_decoder_concealed(d.h, &s, &m)); err != nil {
+		return 0, 0, err
+	}
+	return int64(s), int64(m), nil
 }
 
 // FrameRead returns tight I420 (Y, Cb, Cr back to back).

@@ -228,6 +228,9 @@ struct StreamState {
     int status = H264MI_OK; // of this stream in the current batch (h264mi_stream_status)
     const void *status_batch = nullptr; // the batch whose entropy kernels set `status` (harvest_status)
     bool need_idr = false;  // after an error: nothing is decodable before the next IDR picture
+    // error concealment: slice NAL units with an unparsable header that arrived while no picture was under construction -- they belong to the picture
+    // the next slice starts, and are tolerated only if that picture turns out to be concealable (add_slice); that slice may come with a later chunk
+    int pending_drops = 0, pending_drop_err = H264MI_OK;
 };
 
 // Everything one prepared batch owns: the pinned staging buffers and their device mirrors, the descriptors, the launch
@@ -254,6 +257,9 @@ struct Stage {
     // n - 1 or older than the batch (k_entropy_b) -- and the slice table is ordered by level.
     std::vector<int> pic_level, slice_level; // per picture / per slice of the batch (slice_level in parse order, until the table is sorted)
     std::vector<uint8_t> pic_save_col;       // the picture's motion is kept for later direct prediction (k_dbprep writes its ColRec array)
+    std::vector<uint8_t> pic_init_qp;        // error concealment: 26 + pic_init_qp_minus26 of the picture's PPS (QP_Y of its concealment SliceDesc)
+    uint32_t *d_cmap = nullptr, *h_cmap = nullptr; // error concealment: per picture where its slices are in the sorted slice table (k_conceal)
+    std::vector<uint16_t> pic_dropped;       // error concealment: per picture, slice NAL units whose header did not parse and that were dropped as lost (add_slice)
     std::vector<int> pic_wave;               // reconstruction wave of the picture: 0 for a picture that reads no picture of this batch, else 1 + the latest wave among its references
     std::vector<int> level_first;            // first slice of each level in the sorted table (+ end marker)
     std::vector<uint32_t> colsave_n;            // per level: pictures whose ColRec array k_dbprep writes (what the cross-pass fence looks at)
@@ -314,6 +320,8 @@ struct h264mi_decoder {
     int n_scaling = 0;
     bool tables_dirty = true;
     size_t ent_lds_pad = 0; // dynamic LDS requested (and not used) by k_entropy: caps its wavefronts per CU, see h264mi_decoder_create
+    bool conceal = false; // h264mi_config.conceal_errors: lost macroblocks of concealable pictures are copied from a reference picture (k_conceal)
+    int64_t concealed_slices = 0, concealed_mbs = 0; // totals since create (h264mi_decoder_concealed)
     bool isolate = false; // h264mi_decoder_set_isolation: a broken stream does not fail the batch
     // profiling
     bool profiling = false;
@@ -423,6 +431,8 @@ static void free_all(h264mi_decoder *d) {
         if (g.h_lists) hipHostFree(g.h_lists);
         if (g.d_bext) hipFree(g.d_bext);
         if (g.h_bext) hipHostFree(g.h_bext);
+        if (g.d_cmap) hipFree(g.d_cmap);
+        if (g.h_cmap) hipHostFree(g.h_cmap);
         if (g.ev_upload) hipEventDestroy(g.ev_upload);
         if (g.ev_done) hipEventDestroy(g.ev_done);
     }
@@ -479,6 +489,7 @@ extern "C" int32_t h264mi_decoder_create(const h264mi_config *cfg_, h264mi_decod
     if (r != H264MI_OK) return r;
     h264mi_decoder *d = new h264mi_decoder();
     d->cfg = *cfg;
+    d->conceal = cfg->conceal_errors != 0;
     if (d->cfg.max_slices_per_frame < 1) d->cfg.max_slices_per_frame = 1;
     d->Wmax = (cfg->max_width + 15) & ~15;
     d->Hmax = (cfg->max_height + 15) & ~15;
@@ -530,15 +541,23 @@ extern "C" int32_t h264mi_decoder_create(const h264mi_config *cfg_, h264mi_decod
         TRY_ALLOC(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
         d->own_stream = true;
     }
+    // error concealment: one more SliceDesc per picture (what concealed macroblocks point at; it takes no entropy wavefront and does not count
+    // against max_slices_per_frame), and behind the status words one counter per picture (k_conceal)
+    const size_t slices_alloc = static_cast<size_t>(d->slices_cap) + (d->conceal ? d->pics_cap : 0);
+    const size_t status_alloc = static_cast<size_t>(8) * d->slices_cap + (d->conceal ? static_cast<size_t>(d->pics_cap) : 0);
     for (Stage &g : d->stage) {
         DEV_ALLOC(g.d_bits, d->bits_cap);
         TRY_ALLOC(hipHostMalloc(&g.h_bits, d->bits_cap));
-        DEV_ALLOC(g.d_slices, sizeof(SliceDesc) * d->slices_cap);
-        TRY_ALLOC(hipHostMalloc(&g.h_slices, sizeof(SliceDesc) * d->slices_cap));
+        DEV_ALLOC(g.d_slices, sizeof(SliceDesc) * slices_alloc);
+        TRY_ALLOC(hipHostMalloc(&g.h_slices, sizeof(SliceDesc) * slices_alloc));
         DEV_ALLOC(g.d_pics, sizeof(PicDesc) * d->pics_cap);
         TRY_ALLOC(hipHostMalloc(&g.h_pics, sizeof(PicDesc) * d->pics_cap));
-        DEV_ALLOC(g.d_status, sizeof(uint32_t) * 8 * d->slices_cap);
-        TRY_ALLOC(hipHostMalloc(&g.h_status, sizeof(uint32_t) * 8 * d->slices_cap));
+        DEV_ALLOC(g.d_status, sizeof(uint32_t) * status_alloc);
+        TRY_ALLOC(hipHostMalloc(&g.h_status, sizeof(uint32_t) * status_alloc));
+        if (d->conceal) {
+            DEV_ALLOC(g.d_cmap, sizeof(uint32_t) * (static_cast<size_t>(d->pics_cap) + d->slices_cap));
+            TRY_ALLOC(hipHostMalloc(&g.h_cmap, sizeof(uint32_t) * (static_cast<size_t>(d->pics_cap) + d->slices_cap)));
+        }
         DEV_ALLOC(g.d_lists, sizeof(uint32_t) * 6 * d->pics_cap);
         TRY_ALLOC(hipHostMalloc(&g.h_lists, sizeof(uint32_t) * 6 * d->pics_cap));
         DEV_ALLOC(g.d_bext, sizeof(BSliceExt) * d->slices_cap);
@@ -687,6 +706,7 @@ static void reset_stream(StreamState &s, bool keep_parameter_sets) {
     s.cur_slot = s.cur_pic = -1, s.cur_slices = 0;
     s.cur_field = 0, s.cur_second = false, s.pend_slot = -1;
     s.n_pics_in_batch = 0;
+    s.pending_drops = 0;
     s.prev_poc_msb = s.prev_poc_lsb = s.prev_frame_num = s.prev_frame_num_offset = s.prev_ref_frame_num = 0;
     if (!keep_parameter_sets) {
         memset(s.sps_ok, 0, sizeof(s.sps_ok));
@@ -729,6 +749,23 @@ extern "C" int32_t h264mi_decoder_unpinned_failures(h264mi_decoder *d, int64_t *
     if (!d || !n) return H264MI_EINVAL;
     GUARD(d);
     *n = d->unpinned_failures;
+    return H264MI_OK;
+}
+
+extern "C" int32_t h264mi_decoder_concealed(h264mi_decoder *d, int64_t *slices, int64_t *macroblocks) {
+    if (!d || !slices || !macroblocks) return H264MI_EINVAL;
+    *slices = d->concealed_slices, *macroblocks = d->concealed_mbs;
+    return H264MI_OK;
+}
+extern "C" int32_t h264mi_frame_concealed(h264mi_decoder *d, int32_t stream, int32_t frame, int32_t *n_macroblocks) {
+    if (!d || !n_macroblocks || stream < 0 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    const Stage &g = d->stage[d->exec];
+    if (frame < 0 || frame >= static_cast<int>(g.out[stream].size())) return H264MI_EINVAL;
+    int32_t n = 0;
+    if (d->conceal && g.executed && g.harvested)
+        for (int pic : {g.out[stream][frame].pic, g.out[stream][frame].pic2})
+            if (pic >= 0 && pic < g.n_pics) n += static_cast<int32_t>(g.h_status[8 * g.n_slices + pic]);
+    *n_macroblocks = n;
     return H264MI_OK;
 }
 
@@ -1336,7 +1373,23 @@ static int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref
     const h264mi_sps &sps = s.sps[pps.sps_id];
     h264mi_slice_header sh;
     int r = parse_slice_header(&sps, &pps, ref_idc, type, rbsp, rlen, &sh);
-    if (r != H264MI_OK) return r;
+    if (r != H264MI_OK) {
+        // error concealment: a damaged slice header is a lost slice -- its macroblocks stay undelivered and k_conceal fills them in -- but only in a
+        // picture that is concealable; anywhere else it fails the stream as without the mode.  Which picture a slice without a header belongs to is not
+        // known: it is taken for a slice of the picture under construction, or, if there is none or that one is an IDR picture (whose slices are
+        // NAL units of type 5, and only type 1 is tolerated), of the picture the next slice starts (decided there).
+        if (d->conceal && type == 1 && !s.need_idr && (r == H264MI_EBITSTREAM || r == H264MI_EINVAL)) {
+            if (s.cur_slot < 0 || s.first_sh.nal_unit_type == 5) {
+                s.pending_drops++, s.pending_drop_err = r;
+                return H264MI_OK;
+            }
+            if (g.h_pics[s.cur_pic].conceal_ref >= 0) {
+                g.pic_dropped[s.cur_pic]++;
+                return H264MI_OK;
+            }
+        }
+        return r;
+    }
     if (sh.redundant_pic_cnt > 0) return H264MI_OK; // redundant pictures are dropped
     if (s.need_idr) { // after an error nothing can be trusted before the next IDR picture
         if (type != 5) return H264MI_OK;
@@ -1466,8 +1519,42 @@ static int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref
         pd.pitch = static_cast<uint32_t>(wmb * 16 * (sh.field_pic ? 2 : 1)), pd.plane = static_cast<uint32_t>(wmb * 16) * static_cast<uint32_t>(hmb * 16);
         pd.inv_wmb = static_cast<uint32_t>((1ull << 32) / static_cast<uint32_t>(wmb)) + 1u;
         pd.pool_base = d->h_pools[si].base, pd.slot_bytes = d->slot_bytes, pd.n_slots = static_cast<uint32_t>(d->n_slots);
-        g.pic_level.resize(g.n_pics, 0), g.pic_save_col.resize(g.n_pics, 0), g.pic_wave.resize(g.n_pics, 0);
+        g.pic_level.resize(g.n_pics, 0), g.pic_save_col.resize(g.n_pics, 0), g.pic_wave.resize(g.n_pics, 0), g.pic_init_qp.resize(g.n_pics, 26);
+        g.pic_dropped.resize(g.n_pics, 0), g.pic_dropped[s.cur_pic] = 0;
         g.pic_level[s.cur_pic] = 0, g.pic_save_col[s.cur_pic] = 0, g.pic_wave[s.cur_pic] = 0;
+        g.pic_init_qp[s.cur_pic] = static_cast<uint8_t>(std::min(std::max(26 + pps.pic_init_qp_minus26, 0), 51));
+        pd.conceal_ref = -1;
+        if (d->conceal && !sh.field_pic && type != 5) {
+            // Error concealment: the picture is concealable when the initial P list of 8.2.4.2.1, built for THIS picture whatever the types of its
+            // slices, is not empty; its entry 0 -- the short-term frame with the highest PicNum, else the long-term frame with the lowest
+            // LongTermPicNum -- is what lost macroblocks are copied from.  (A frame inferred by the frame_num gap process holds no samples: not concealable.)
+            const int max_fn = 1 << (sps.log2_max_frame_num_minus4 + 4);
+            int best = -1, best_num = 0;
+            for (int pass = 1; pass <= 2 && best < 0; pass++) // short-term, then long-term
+                for (int i = 0; i < static_cast<int>(s.slots.size()); i++) {
+                    const Slot &c = s.slots[i];
+                    if (i == slot || c.ref != pass || c.fields != 3 || c.funref) continue;
+                    const int num = pass == 1 ? (c.frame_num > sh.frame_num ? c.frame_num - max_fn : c.frame_num) : -c.long_idx;
+                    if (best < 0 || num > best_num) best = i, best_num = num;
+                }
+            if (best >= 0 && !s.slots[best].nonexisting) {
+                pd.conceal_ref = static_cast<int16_t>(best);
+                // ... and the picture is reconstructed behind it when this batch decodes it: a non-IDR I picture would otherwise be in wave 0, and the
+                // MODIFIED lists of a P picture's slices need not hold this entry
+                const Slot &rs = s.slots[best];
+                for (int pic : {rs.pic, rs.fpic[0], rs.fpic[1]})
+                    if (pic >= 0 && pic != s.cur_pic && pic < static_cast<int>(g.pic_wave.size())) g.pic_wave[s.cur_pic] = std::max(g.pic_wave[s.cur_pic], g.pic_wave[pic] + 1);
+            }
+        }
+        if (s.pending_drops) { // slices without a readable header in front of this picture's first good one: lost slices of it, if it can be concealed
+            const int n = s.pending_drops, e = s.pending_drop_err;
+            s.pending_drops = 0;
+            if (pd.conceal_ref < 0) {
+                set_error("stream %d: a slice header does not parse, in a picture that cannot be concealed", si);
+                return e;
+            }
+            g.pic_dropped[s.cur_pic] = static_cast<uint16_t>(std::min(n, 65535));
+        }
         pd.mb_base = g.mb_used;
         g.mb_used += static_cast<uint64_t>(wmb) * hmb_pic;
         pd.first_slice = g.n_slices;
@@ -1667,6 +1754,12 @@ static int harvest_status(h264mi_decoder *d, Stage &g) {
             // the stream was reset (h264mi_decoder_reset / h264mi_stream_reset: a new connection took the slot, or the caller started over) after this
             // batch was prepared: what failed in it is not a property of what the slot decodes now
             if (g.h_pics[sd.pic_idx].stream < g.epochs.size() && g.epochs[g.h_pics[sd.pic_idx].stream] != s.epoch) continue;
+            // error concealment: k_conceal has rewritten every macroblock of the slice as a copy from the picture's concealment reference; the picture
+            // is a reference like any other, the stream goes on
+            if (d->conceal && g.h_pics[sd.pic_idx].conceal_ref >= 0) {
+                d->concealed_slices++;
+                continue;
+            }
             const bool field_cabac = g.h_pics[sd.pic_idx].field != 0 && g.h_pics[sd.pic_idx].cabac != 0;
             if (field_cabac) d->unpinned_failures++; // what a wrong value in the unpinned context tables looks like: the slice does not end on end_of_slice_flag where it should
             if (result == H264MI_OK)
@@ -1680,6 +1773,10 @@ static int harvest_status(h264mi_decoder *d, Stage &g) {
             }
             result = H264MI_EDECODE;
         }
+    if (d->conceal) // the counter k_conceal left behind the status words: concealed macroblocks per picture; and the slices dropped for their header
+        for (int p = 0; p < g.n_pics; p++)
+            if (g.h_pics[p].stream >= g.epochs.size() || g.epochs[g.h_pics[p].stream] == d->st[g.h_pics[p].stream].epoch)
+                d->concealed_mbs += g.h_status[8 * g.n_slices + p], d->concealed_slices += g.pic_dropped[p];
     return result;
 }
 
@@ -1705,7 +1802,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
     g.epochs.resize(d->st.size());
     for (size_t si = 0; si < d->st.size(); si++) g.epochs[si] = d->st[si].epoch;
     g.n_bext = 0;
-    g.pic_level.clear(), g.slice_level.clear(), g.pic_save_col.clear(), g.pic_wave.clear();
+    g.pic_level.clear(), g.slice_level.clear(), g.pic_save_col.clear(), g.pic_wave.clear(), g.pic_init_qp.clear(), g.pic_dropped.clear();
     memset(&g.info, 0, sizeof(g.info));
     for (size_t si = 0; si < d->st.size(); si++) {
         StreamState &s = d->st[si];
@@ -1853,7 +1950,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
             // (nothing is decodable before its next IDR picture); the other streams are not affected.
             g.n_pics = pics0, g.n_slices = slices0, g.mb_used = mb0, g.info.n_macroblocks = info_mb0;
             g.n_bext = bext0;
-            g.pic_level.resize(pics0), g.pic_save_col.resize(pics0), g.pic_wave.resize(pics0), g.slice_level.resize(slices0);
+            g.pic_level.resize(pics0), g.pic_save_col.resize(pics0), g.pic_wave.resize(pics0), g.slice_level.resize(slices0), g.pic_init_qp.resize(pics0), g.pic_dropped.resize(pics0);
             while (!g.fmo_pics.empty() && static_cast<int>(g.fmo_pics.back()) >= pics0) g.fmo_pics.pop_back();
             g.grey.erase(std::remove_if(g.grey.begin(), g.grey.end(), [&](const Stage::GreyFill &f) { return static_cast<int>(f.stream) == si; }), g.grey.end());
             reset_stream(s, true);
@@ -1869,6 +1966,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
     // A reference picture that outlives the batch may become the co-located picture of a B picture of a later batch: its
     // motion is kept too (8.4.1.2.1).
     g.pic_level.resize(g.n_pics, 0), g.pic_save_col.resize(g.n_pics, 0), g.pic_wave.resize(g.n_pics, 0), g.slice_level.resize(g.n_slices, 0);
+    g.pic_init_qp.resize(g.n_pics, 26), g.pic_dropped.resize(g.n_pics, 0);
     for (int si = 0; si < n_streams; si++)
         for (const Slot &sl : d->st[si].slots)
             if (sl.ref)
@@ -1892,6 +1990,28 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
         for (int i = g.n_slices - 1; i >= 0; i--) g.level_first[g.slice_level[i]] = i;
         for (int l = n_levels - 1; l >= 0; l--) g.level_first[l] = std::min(g.level_first[l], g.level_first[l + 1]);
     }
+    if (d->conceal) {
+        // Error concealment.  Behind the slices of the batch one SliceDesc per picture -- what MbRec::slice_idx of a concealed macroblock names, so that
+        // K4 finds neither the explicit weights of the slice that failed nor those of the slice whose wavefront blanked a gap: type P, wp_flag 0 and
+        // identity weights (the one-list K4 chooses explicit weighting per picture: denominators 0, weight 1, offset 0 give the default prediction
+        // exactly; the two-list K4 sees a slice that is not a B slice and has no wp_flag: default), QP_Y from the PPS, all edges filtered, and a
+        // slice_in_pic no real slice has.  And the picture -> slices map of the sorted table (k_conceal).
+        for (int p = 0; p < g.n_pics; p++) {
+            SliceDesc &cd = g.h_slices[g.n_slices + p];
+            memset(&cd, 0, sizeof(cd));
+            cd.pic_idx = static_cast<uint32_t>(p);
+            cd.slice_type = 0, cd.slice_qp = g.pic_init_qp[p], cd.num_ref_idx_active = 1;
+            cd.slice_in_pic = 0xFFFF;
+            for (int i = 0; i < MI_MAX_REFS; i++) {
+                cd.ref_slot[i] = static_cast<int16_t>(i == 0 ? g.h_pics[p].conceal_ref : -1);
+                cd.wp_lw[i] = 1, cd.wp_cw[i][0] = cd.wp_cw[i][1] = 1;
+            }
+        }
+        uint32_t at = static_cast<uint32_t>(g.n_pics);
+        for (int p = 0; p < g.n_pics; p++) g.h_cmap[p] = at, at += g.h_pics[p].n_slices;
+        std::vector<uint32_t> fill(g.h_cmap, g.h_cmap + g.n_pics);
+        for (int i = 0; i < g.n_slices; i++) g.h_cmap[fill[g.h_slices[i].pic_idx]++] = static_cast<uint32_t>(i);
+    }
     // picture "waves": pictures that do not predict from one another are reconstructed side by side -- wave 0 holds the pictures that read no
     // picture of this batch (intra pictures wherever they stand in their stream; pictures whose references an earlier batch decoded), wave n + 1
     // the pictures whose latest reference is of wave n (Stage::pic_wave; with I P P P ... that is the k-th picture of every stream, with
@@ -1903,7 +2023,8 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
     g.waves_inter.assign(nw, {});
     for (int i = 0; i < g.n_pics; i++) {
         g.waves[g.pic_wave[i]].push_back(i);
-        if (!g.h_pics[i].is_intra_only) g.waves_inter[g.pic_wave[i]].push_back(i);
+        // (error concealment: the concealed macroblocks of a picture whose delivered slices are all I slices are inter macroblocks -- K4 must see it)
+        if (!g.h_pics[i].is_intra_only || g.h_pics[i].conceal_ref >= 0) g.waves_inter[g.pic_wave[i]].push_back(i);
     }
     g.wave_off.clear();
     g.wave_inter_off.clear();
@@ -1953,7 +2074,8 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
         size_t nbytes = std::min(d->bits_cap, ((end + 15) & ~static_cast<size_t>(15)) + 4096);
         memset(g.h_bits + end, 0, nbytes - end);
         HIP_TRY(hipMemcpyAsync(g.d_bits, g.h_bits, nbytes, hipMemcpyHostToDevice, up));
-        HIP_TRY(hipMemcpyAsync(g.d_slices, g.h_slices, sizeof(SliceDesc) * g.n_slices, hipMemcpyHostToDevice, up));
+        HIP_TRY(hipMemcpyAsync(g.d_slices, g.h_slices, sizeof(SliceDesc) * (g.n_slices + (d->conceal ? g.n_pics : 0)), hipMemcpyHostToDevice, up));
+        if (d->conceal) HIP_TRY(hipMemcpyAsync(g.d_cmap, g.h_cmap, sizeof(uint32_t) * (g.n_pics + g.n_slices), hipMemcpyHostToDevice, up));
         HIP_TRY(hipMemcpyAsync(g.d_pics, g.h_pics, sizeof(PicDesc) * g.n_pics, hipMemcpyHostToDevice, up));
         HIP_TRY(hipMemcpyAsync(g.d_lists, g.h_lists, sizeof(uint32_t) * pos, hipMemcpyHostToDevice, up));
         if (g.n_bext) HIP_TRY(hipMemcpyAsync(g.d_bext, g.h_bext, sizeof(BSliceExt) * g.n_bext, hipMemcpyHostToDevice, up));
@@ -2068,6 +2190,10 @@ static int execute_stage(h264mi_decoder *d, int stage_idx, bool exclusive) {
             // the pictures complete with this level: K5's strengths and filter parameters, and the motion later B slices (the next
             // level's, or a later batch's) take their direct prediction from
             if (g.colsave_n[lv]) fence();
+            // error concealment: the lost macroblocks of these pictures become decodable records before anything downstream reads them
+            if (d->conceal && g.prep_n[lv])
+                hipLaunchKernelGGL(k_conceal, dim3(g.prep_n[lv]), dim3(256), 0, st, g.d_lists + g.prep_off[lv], g.d_pics, g.d_slices, g.d_cmap, static_cast<uint32_t>(g.n_slices),
+                                   g.d_status, g.d_bits, d->d_tables, mbrec, d->d_mv1[set], g.d_status + 8 * static_cast<size_t>(g.n_slices));
             if (g.prep_n[lv])
                 hipLaunchKernelGGL(k_dbprep, dim3((g.mbs_max + MI_DBPREP_MBS - 1) / MI_DBPREP_MBS, (g.prep_n[lv] + 7u) & ~7u), dim3(256), 0, st, g.d_lists + g.prep_off[lv], g.d_pics,
                                    d->d_tables, mbrec, d->d_mv1[set], d->d_dbprm[set], 0, d->d_imask[set], static_cast<int>(g.prep_n[lv]));
@@ -2157,7 +2283,8 @@ static int execute_stage(h264mi_decoder *d, int stage_idx, bool exclusive) {
     if (!prof) HIP_TRY(hipStreamWaitEvent(d->stream, d->ev_rec[set], 0)); // the caller's stream sees the finished pass
     d->pass++;
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(g.h_status, g.d_status, sizeof(uint32_t) * 8 * g.n_slices, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipMemcpyAsync(g.h_status, g.d_status, sizeof(uint32_t) * (8 * static_cast<size_t>(g.n_slices) + (d->conceal ? static_cast<size_t>(g.n_pics) : 0)), hipMemcpyDeviceToHost,
+                           d->stream)); // (error concealment: k_conceal's counters travel with the status words)
     HIP_TRY(hipMemcpyAsync(d->h_xstatus, d->d_xctl + 64, sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipEventRecord(g.ev_done, d->stream)); // d->stream has waited for the reconstruction kernels: the batch's buffers are idle after this
     g.executed = true, g.harvested = false;

@@ -40,6 +40,12 @@ extern "C" __global__ void k_intra_x(const uint32_t *pic_list, const PicDesc *pi
 #define MI_DBPREP_MBS 64
 #endif
 extern "C" __global__ void k_dbprep(const uint32_t *pic_list, const PicDesc *pics, const DevTables *tab, const MbRec *mbrec, const MbMv1 *mbmv1, DbPrm *out, int col_only, unsigned long long *intramask, int n_pics);
+// k_conceal (k_conceal.hip): error concealment -- between a level's entropy launch and its k_dbprep, the lost macroblocks of the concealable pictures of
+// the list (MBT_NONE records; every macroblock of a slice with a non-zero status) become zero-vector P_Skip records that point at PicDesc::conceal_ref
+// and at the picture's concealment SliceDesc (slices[conceal_base + picture]).  grid = pictures of the list, block = 256.
+// cmap: [picture] -> start, within cmap, of the picture's slice indices; cstat: [p] concealed macroblocks of picture p
+extern "C" __global__ void k_conceal(const uint32_t *pic_list, const PicDesc *pics, const SliceDesc *slices, const uint32_t *cmap, uint32_t conceal_base,
+                                     const uint32_t *status, const uint8_t *bitstream, const DevTables *tab, MbRec *mbrec, MbMv1 *mbmv1, uint32_t *cstat);
 // K5 (k_deblock.hip): in-loop deblocking, one workgroup per picture, one wavefront per group of 8 macroblock rows, 8 lanes per macroblock
 // (two lines per lane, packed 16-bit arithmetic).  block = 64 * nwaves, dynamic LDS = mi_deblock8_lds_bytes(nwaves, ring, ring_last, last_bufs);
 // (nwaves, ring, ring_last, last_bufs) from mi_deblock8_plan()

@@ -164,7 +164,10 @@ typedef struct {
     uint32_t pitch;        /* luma bytes from one row of the picture to the next (chroma: half) */
     uint32_t plane;        /* offset of the Cb plane from the slot's first byte = luma bytes of the frame (Cr: plane * 5 / 4) */
     uint8_t field;         /* 0 frame picture, 1 top field, 2 bottom field */
-    uint8_t pad2[7];
+    uint8_t pad2;
+    int16_t conceal_ref;   /* error concealment (h264mi_config.conceal_errors): frame-pool slot of entry 0 of the initial P list built for this picture
+                            * (8.2.4.2.1) -- what k_conceal copies lost macroblocks from; -1: the picture is not concealable, or the mode is off */
+    uint8_t pad3[4];
 } PicDesc;
 /* In field pictures a reference "slot" (SliceDesc::ref_slot, BSliceExt::ref_slot1, MbRec::refslot / refslot1, ColRec::refslot) names a FIELD:
  * the frame slot in the low bits and the field's parity in bit 14 (frame pictures never set it: they predict from whole frames). */

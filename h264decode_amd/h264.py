@@ -201,12 +201,15 @@ class Decoder:
     """Batched GPU decoder: N independent Annex-B streams side by side on one MI355X."""
 
     def __init__(self, max_streams=1, max_width=1920, max_height=1088, max_frames_per_batch=32, max_slices_per_frame=8, device=0,
-                 max_bitstream_bytes=0, hip_stream=None, max_ref_frames=0, coef_blocks_per_mb=0, b_pictures=0, allow_unpinned_field_cabac=0):
+                 max_bitstream_bytes=0, hip_stream=None, max_ref_frames=0, coef_blocks_per_mb=0, b_pictures=0, allow_unpinned_field_cabac=0,
+                 conceal_errors=False):
         L = _lib.load()
         cfg = _lib.Config()
         cfg.struct_size = ctypes.sizeof(cfg)
         cfg.b_pictures = b_pictures  # 1: the B-only buffers exist from the start (default: from the first B slice on)
         cfg.allow_unpinned_field_cabac = allow_unpinned_field_cabac  # 1: CABAC field pictures are decoded with the unpinned context tables of field-coded blocks (default: refused)
+        # 1: lost macroblocks of non-IDR frame pictures are copied from a reference picture and the stream goes on (default: the stream waits for an IDR picture)
+        cfg.conceal_errors = int(bool(conceal_errors))
         cfg.device, cfg.max_streams, cfg.max_width, cfg.max_height = device, max_streams, max_width, max_height
         cfg.max_frames_per_batch, cfg.max_slices_per_frame, cfg.max_bitstream_bytes = max_frames_per_batch, max_slices_per_frame, max_bitstream_bytes
         cfg.hip_stream = hip_stream
@@ -264,6 +267,18 @@ class Decoder:
         n = ctypes.c_int64()
         check(self._L.h264mi_decoder_unpinned_failures(self._h, ctypes.byref(n)))
         return n.value
+
+    def frame_concealed(self, stream, frame):
+        """Concealed macroblocks of a frame of the last batch (h264mi_frame_concealed); call after sync()."""
+        n = ctypes.c_int32()
+        check(self._L.h264mi_frame_concealed(self._h, stream, frame, ctypes.byref(n)))
+        return int(n.value)
+
+    def concealed(self):
+        """(slices, macroblocks) concealed since the decoder was created (h264mi_decoder_concealed)."""
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        check(self._L.h264mi_decoder_concealed(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
 
     def coef_pool(self):
         """(used, capacity) of the residual-coefficient pool in 32-byte blocks (h264mi_decoder_coef_pool); call after sync()."""
@@ -578,11 +593,12 @@ class H264Reader:
     `on_frames(frames)` receives uint8[n, width*height*3/2] arrays (cropped I420) in decoding order, or -- with
     display_order=N -- in display order through a DisplayOrder buffer of depth N (streams with B pictures)."""
 
-    def __init__(self, connection, decoder=None, on_frames=None, max_width=1920, max_height=1088, frames_per_batch=30, read_size=1 << 16, display_order=0):
+    def __init__(self, connection, decoder=None, on_frames=None, max_width=1920, max_height=1088, frames_per_batch=30, read_size=1 << 16, display_order=0,
+                 conceal_errors=False):
         self.Stream = connection
         self.frames_per_batch = frames_per_batch
         self.decoder = decoder or Decoder(max_streams=1, max_width=(max_width + 15) // 16 * 16, max_height=(max_height + 15) // 16 * 16,
-                                          max_frames_per_batch=frames_per_batch, max_slices_per_frame=16)
+                                          max_frames_per_batch=frames_per_batch, max_slices_per_frame=16, conceal_errors=conceal_errors)
         self.on_frames = on_frames
         self.read_size = read_size
         self.splitter = AccessUnitSplitter(frames_per_batch)
@@ -651,9 +667,9 @@ class BatchServer:
     batch scheduler the reference's per-connection goroutine (main.go:12-21) lacks.  `on_frames(slot, frames)` receives
     the cropped I420 frames of a connection in decoding order; `on_close(slot, n_frames)` when its peer is done."""
 
-    def __init__(self, max_connections=8, max_width=1920, max_height=1088, frames_per_batch=30, on_frames=None, on_close=None, read_size=1 << 16):
+    def __init__(self, max_connections=8, max_width=1920, max_height=1088, frames_per_batch=30, on_frames=None, on_close=None, read_size=1 << 16, conceal_errors=False):
         self.decoder = Decoder(max_streams=max_connections, max_width=(max_width + 15) // 16 * 16, max_height=(max_height + 15) // 16 * 16,
-                               max_frames_per_batch=frames_per_batch, max_slices_per_frame=16)
+                               max_frames_per_batch=frames_per_batch, max_slices_per_frame=16, conceal_errors=conceal_errors)
         self.decoder.set_isolation(True)  # one bad client must not take the other connections' chunks down with it
         self.errors = [0] * max_connections
         self.n = max_connections

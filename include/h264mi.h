@@ -42,7 +42,8 @@ extern "C" {
 #define H264MI_ENOMEM (-5)
 #define H264MI_EDEVICE (-6)     /* HIP runtime error */
 #define H264MI_ECAPACITY (-7)   /* caller buffer or decoder configuration too small */
-#define H264MI_EDECODE (-8)     /* a GPU entropy kernel reported a slice error */
+#define H264MI_EDECODE (-8)     /* a GPU entropy kernel reported a slice error.  With h264mi_config.conceal_errors a failed slice of a concealable picture
+                                 * (a non-IDR frame picture that has a reference picture) is not an error: it is concealed and counted (h264mi_decoder_concealed) */
 
 /* ---- NAL unit: h264/nalUnit.go:3-30 (NalUnit), :75-131 (NewNalUnit) ---- */
 typedef struct {
@@ -205,6 +206,17 @@ typedef struct {
      * build machine.  With a wrong value a slice loses synchronisation and does not end on end_of_slice_flag at the picture's last macroblock: such
      * slices fail (H264MI_EDECODE, the stream waits for its next IDR picture) and are counted: h264mi_decoder_unpinned_failures. */
     int32_t allow_unpinned_field_cabac;
+    /* conceal_errors: 0 (default) = a slice that fails in the entropy kernel takes its stream out until the next IDR picture, and macroblocks no slice
+     * delivered are mid-grey.  1 = error concealment: in a frame picture that is not an IDR picture and for which the initial P reference list
+     * (8.2.4.2.1) is not empty, the LOST macroblocks -- the ones no slice delivered, and ALL macroblocks of a slice the entropy kernel failed on -- are
+     * reconstructed as a zero-motion copy of entry 0 of that list; the result is bit for bit what a conforming decoder produces for the stream in
+     * which those macroblocks are coded as P slices of P_Skip macroblocks (one active reference, slice_qp_delta 0, deblocking on, default weights).
+     * The picture is kept and used as a reference, the stream's status stays H264MI_OK, nothing waits for an IDR picture.  The repair happens on the
+     * device inside the pass, so pipelined callers get it for the batch prepared before the failure was known as well.  A slice NAL unit of
+     * type 1 whose header does not parse is dropped and counted as a lost slice of the picture under construction (of the next picture, if there is none
+     * or it is an IDR picture) when that picture is concealable; otherwise it fails the stream as with 0.  IDR pictures, field pictures, pictures
+     * without any reference picture, wholly missing pictures and parameter-set errors are handled as with 0. */
+    int32_t conceal_errors;
 } h264mi_config;
 #define H264MI_CONFIG_INIT {(uint32_t)sizeof(h264mi_config)} /* h264mi_config cfg = H264MI_CONFIG_INIT; then set the fields */
 
@@ -229,7 +241,8 @@ int32_t h264mi_stream_reset(h264mi_decoder *dec, int32_t stream);
 /* Error isolation for batches of unrelated streams (one connection each).  Off (default): the first stream error fails
  * h264mi_batch_prepare / h264mi_batch_sync.  On: a stream whose chunk cannot be parsed, or whose slices fail in the
  * entropy kernel, is dropped from the batch and marked; the calls return H264MI_OK and the other streams decode
- * normally.  A marked stream resumes at its next IDR picture. */
+ * normally.  A marked stream resumes at its next IDR picture.  (With h264mi_config.conceal_errors a failed slice of a concealable picture
+ * marks nothing: only what cannot be concealed takes a stream out.) */
 int32_t h264mi_decoder_set_isolation(h264mi_decoder *dec, int32_t on);
 /* Status of a stream in the current batch: H264MI_OK or the H264MI_E* that took it out (valid after prepare; entropy
  * kernel failures appear after sync).  Pipelined callers (execute(k); prepare(k + 1); execute(k + 1); ... one sync for
@@ -237,7 +250,8 @@ int32_t h264mi_decoder_set_isolation(h264mi_decoder *dec, int32_t on);
  * batch whose staging set it takes back, so a failure in batch k marks its stream (references dropped, nothing decoded
  * before its next IDR picture) before batch k + 2 is parsed at the latest; batch k + 1 of that stream, prepared before the
  * failure was known, is decoded from the damaged pictures.  The status VALUE is reset by every prepare: read it after
- * the sync that follows an execute if it matters. */
+ * the sync that follows an execute if it matters.  With h264mi_config.conceal_errors failed slices of concealable pictures leave the
+ * status at H264MI_OK (batch k + 1 is then decoded from the concealed pictures, which is what a decoder of the repaired stream does). */
 int32_t h264mi_stream_status(h264mi_decoder *dec, int32_t stream, int32_t *status);
 
 /* Stage 1 (host + H2D): scan and parse each stream's Annex-B chunk (whole access units), run
@@ -314,6 +328,12 @@ int32_t h264mi_decoder_coef_pool(h264mi_decoder *dec, int64_t *used_blocks, int6
 /* Slices of CABAC field pictures (h264mi_config.allow_unpinned_field_cabac) that failed in the entropy kernels since the decoder was created: what a wrong
  * value in the unpinned context tables of field-coded blocks looks like (a damaged stream looks the same). */
 int32_t h264mi_decoder_unpinned_failures(h264mi_decoder *dec, int64_t *n);
+
+/* Error concealment (h264mi_config.conceal_errors).  h264mi_frame_concealed: macroblocks of a frame of the last batch that were concealed (valid after
+ * h264mi_batch_sync; 0 without the mode).  h264mi_decoder_concealed: totals since the decoder was created -- slices that failed in the entropy kernels or
+ * were dropped for an unparsable header and were concealed, and concealed macroblocks (lost NAL units the decoder never saw count as macroblocks only). */
+int32_t h264mi_frame_concealed(h264mi_decoder *dec, int32_t stream, int32_t frame, int32_t *n_macroblocks);
+int32_t h264mi_decoder_concealed(h264mi_decoder *dec, int64_t *slices, int64_t *macroblocks);
 
 const char *h264mi_last_error_string(void);
 const char *h264mi_version(void);

@@ -3,6 +3,7 @@
 #include <string.h>
 #include "sg_int.h"
 
+size_t sg_bw_sizeof(void) { return sizeof(sg_bw); }
 void sg_bw_init(sg_bw *w, uint8_t *buf, size_t cap) {
     memset(w, 0, sizeof(*w));
     w->buf = buf;

@@ -17,6 +17,7 @@ typedef struct {
     uint8_t ctx[SG_NCTX]; /* (pStateIdx<<1)|valMPS */
 } sg_bw;
 
+size_t sg_bw_sizeof(void); /* for callers that hold an sg_bw as an opaque buffer (tests/concealutil.py through ctypes) */
 void sg_bw_init(sg_bw *w, uint8_t *buf, size_t cap);
 void sg_put(sg_bw *w, uint32_t v, int n);
 void sg_put_ue(sg_bw *w, uint32_t v);

@@ -26,6 +26,7 @@ def main():
                     help="deliver frames in display order through a reorder buffer of this depth (streams with B pictures; single-connection mode)")
     ap.add_argument("--out", default=None, help="append decoded frames (tight I420) to this file")
     ap.add_argument("--once", action="store_true", help="serve one connection and exit")
+    ap.add_argument("--conceal", action="store_true", help="error concealment: lost or damaged slices are filled from a reference picture, the stream goes on")
     ap.add_argument("--batch", type=int, default=0, help="decode up to N concurrent connections side by side in one batched decoder (H.BatchServer)")
     args = ap.parse_args()
     srv = socket.socket()
@@ -36,7 +37,7 @@ def main():
     out = open(args.out, "ab") if args.out else None
     if args.batch > 0:  # several connections, one batched GPU decoder
         import select
-        bs = H.BatchServer(max_connections=args.batch, max_width=args.max_width, max_height=args.max_height, frames_per_batch=args.frames_per_batch,
+        bs = H.BatchServer(max_connections=args.batch, max_width=args.max_width, max_height=args.max_height, frames_per_batch=args.frames_per_batch, conceal_errors=args.conceal,
                            on_frames=lambda i, f: print("slot %d: %d frames md5 %s" % (i, len(f), hashlib.md5(f.tobytes()).hexdigest()), flush=True),
                            on_close=lambda i, n: print("slot %d closed after %d frames" % (i, n), flush=True))
         srv.setblocking(False)
@@ -58,7 +59,7 @@ def main():
 
         try:
             H.ByteStreamReader(conn, on_frames=on_frames, max_width=args.max_width, max_height=args.max_height, frames_per_batch=args.frames_per_batch,
-                               display_order=args.display_order)
+                               display_order=args.display_order, conceal_errors=args.conceal)
         except H.H264MIError as e:
             print("%s: decode error: %s" % (peer[0], e), flush=True)
         if args.once:
