@@ -24,11 +24,13 @@ static int fail(const char *what, int code) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal]\n", argv[0]);
+        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all]\n", argv[0]);
         return 2;
     }
     int conceal = 0; /* --conceal (last argument): h264mi_config.conceal_errors */
-    if (argc > 3 && !strcmp(argv[argc - 1], "--conceal")) conceal = 1, argc--;
+    if (argc > 3 && !strcmp(argv[argc - 1], "--conceal")) conceal = H264MI_CONCEAL_SLICES, argc--;
+    /* --conceal-all: wholly lost reference frames and slices of field pictures are concealed too */
+    else if (argc > 3 && !strcmp(argv[argc - 1], "--conceal-all")) conceal = H264MI_CONCEAL_SLICES | H264MI_CONCEAL_PICTURES | H264MI_CONCEAL_FIELDS, argc--;
     const int per_batch = argc > 3 ? atoi(argv[3]) : 30;
     FILE *f = fopen(argv[1], "rb");
     if (!f) return fail("fopen", -1);
@@ -63,7 +65,8 @@ int main(int argc, char **argv) {
 
     h264mi_config cfg = H264MI_CONFIG_INIT; /* zero-initialised, struct_size = this build's sizeof */
     cfg.max_streams = 1, cfg.max_width = sps.width, cfg.max_height = sps.height;
-    cfg.max_frames_per_batch = per_batch, cfg.max_slices_per_frame = 32, cfg.max_bitstream_bytes = len + (1 << 20);
+    /* (frames inserted for lost pictures count against max_frames_per_batch: headroom for the longest gap that is concealed) */
+    cfg.max_frames_per_batch = per_batch + (conceal & H264MI_CONCEAL_PICTURES ? H264MI_CONCEAL_MAX_GAP : 0), cfg.max_slices_per_frame = 32, cfg.max_bitstream_bytes = len + (1 << 20);
     cfg.conceal_errors = conceal;
     h264mi_decoder *dec = NULL;
     if ((r = h264mi_decoder_create(&cfg, &dec)) != H264MI_OK) return fail("h264mi_decoder_create", r);
@@ -154,6 +157,7 @@ int main(int argc, char **argv) {
     if (conceal) { /* the totals live in the decoder: ask before it is destroyed */
         int64_t cs = 0, cm = 0;
         if (h264mi_decoder_concealed(dec, &cs, &cm) == H264MI_OK) fprintf(stderr, "concealed: %lld slices, %lld macroblocks\n", (long long)cs, (long long)cm);
+        if ((conceal & H264MI_CONCEAL_PICTURES) && h264mi_decoder_concealed_pictures(dec, &cs) == H264MI_OK) fprintf(stderr, "concealed: %lld pictures\n", (long long)cs);
     }
     h264mi_decoder_destroy(dec);
     fprintf(stderr, "%s: %ld frames %dx%d -> %s\n", h264mi_version(), total, sps.width, sps.height, argv[2]);

@@ -334,8 +334,17 @@ type Config struct {
 	MaxRefFrames, CoefBlocksPerMb                                                  int // 0 = defaults (16 reference slots per stream, 8 residual blocks per macroblock)
 	BPictures                                                                      int // 1 = the buffers only B pictures need exist from the start (h264mi_config.b_pictures)
 	AllowUnpinnedFieldCabac                                                        int // 1 = CABAC field pictures are decoded with the unpinned context tables (h264mi_config.allow_unpinned_field_cabac)
-	ConcealErrors                                                                  int // 1 = lost macroblocks of non-IDR frame pictures are copied from a reference picture (h264mi_config.conceal_errors)
+	ConcealErrors                                                                  int // ConcealSlices = lost macroblocks of non-IDR frame pictures are copied from a reference picture; | ConcealPictures = wholly lost reference frames too; | ConcealFields = field pictures too (h264mi_config.conceal_errors)
 }
+
+// Bits of Config.ConcealErrors (H264MI_CONCEAL_*); ConcealPictures and ConcealFields only together with ConcealSlices.  ConcealMaxGap: the longest run of lost
+// frames that is concealed -- MaxFramesPerBatch needs that much headroom over the pictures of a chunk.
+const (
+	ConcealSlices   = C.H264MI_CONCEAL_SLICES
+	ConcealPictures = C.H264MI_CONCEAL_PICTURES
+	ConcealFields   = C.H264MI_CONCEAL_FIELDS
+	ConcealMaxGap   = C.H264MI_CONCEAL_MAX_GAP
+)
 type Decoder struct{ h *C.h264mi_decoder }
 type BatchInfo struct {
 	Frames, Slices             int
@@ -394,6 +403,15 @@ func (d *Decoder) Concealed() (slices, macroblocks int64, err error) {
 		return 0, 0, err
 	}
 	return int64(s), int64(m), nil
+}
+
+// ConcealedPictures: frames inserted for wholly lost pictures since the decoder was created (h264mi_decoder_concealed_pictures).
+func (d *Decoder) ConcealedPictures() (int64, error) {
+	var n C.int64_t
+	if err := status(C.h264mi_decoder_concealed_pictures(d.h, &n)); err != nil {
+		return 0, err
+	}
+	return int64(n), nil
 }
 
 // FrameRead returns tight I420 (Y, Cb, Cr back to back).

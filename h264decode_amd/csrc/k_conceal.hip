@@ -18,10 +18,15 @@
 // slice_idx names the picture's concealment descriptor (slices[conceal_base + picture]: type P, wp_flag 0, identity weights), never the slice
 // that failed or whose wavefront blanked a gap: K4 takes its weights from there.  Intact slices are untouched.
 // Pictures that are not concealable keep their records as they are (MBT_NONE is painted mid-grey by K3, the host marks the stream).
+// A FIELD picture (H264MI_CONCEAL_FIELDS) needs nothing of its own here: PicDesc::hmb is the field's, and conceal_ref carries the parity of the reference
+// field the way every entry of a field list does (slot | MI_REF_PARITY) -- exactly the refslot words the entropy kernel writes for a P_Skip of a field P slice.
+// A picture WITHOUT SLICES (PicDesc::n_slices 0) is a frame the host inserted for a wholly lost reference frame (H264MI_CONCEAL_PICTURES): every
+// macroblock is lost, no slice status is read, nothing was written to its records before.  All of its boundary strengths come out 0 (one reference
+// picture, zero vectors, no coefficients, no intra macroblock), so K5 filters nothing and the picture is an exact copy of its concealment reference.
 //
 // Cost when nothing is lost: per picture one workgroup that reads two status words and three SliceDesc words per slice and leaves
 // (err == 0 && fill_from == first_mb && first_mb + n_mbs == end_mb for every slice).  Pictures with slice groups start from zeroed records and
-// are walked.
+// are walked, pictures without slices are written whole.
 #include <hip/hip_runtime.h>
 #include "mi_kernels.h"
 
@@ -55,7 +60,7 @@ extern "C" __global__ void __launch_bounds__(256) k_conceal(const uint32_t *pic_
     const bool fmo = pd->fmo != 0;
     int todo = 0;
     if (ref >= 0) {
-        todo = fmo ? 1 : 0;
+        todo = fmo || nsl == 0 ? 1 : 0;
         for (int i = tid; i < nsl; i += 256) {
             const uint32_t s = sl[i];
             const SliceDesc *sd = &slices[s];
@@ -96,7 +101,9 @@ extern "C" __global__ void __launch_bounds__(256) k_conceal(const uint32_t *pic_
                 if (recs[mb].type == MBT_NONE) conceal_write(recs + mb, recs1 ? recs1 + mb : nullptr, w0, w1, slots, cidx), mine++;
         }
     }
-    if (fmo) { // (a) with slice groups: whatever is still as the memset before the entropy launch left it
+    if (nsl == 0) { // an inserted picture: all of it
+        for (int mb = tid; mb < total; mb += 256) conceal_write(recs + mb, recs1 ? recs1 + mb : nullptr, w0, w1, slots, cidx), mine++;
+    } else if (fmo) { // (a) with slice groups: whatever is still as the memset before the entropy launch left it
         __syncthreads();
         for (int mb = tid; mb < total; mb += 256)
             if (recs[mb].type == MBT_NONE) conceal_write(recs + mb, recs1 ? recs1 + mb : nullptr, w0, w1, slots, cidx), mine++;

@@ -321,7 +321,10 @@ struct h264mi_decoder {
     bool tables_dirty = true;
     size_t ent_lds_pad = 0; // dynamic LDS requested (and not used) by k_entropy: caps its wavefronts per CU, see h264mi_decoder_create
     bool conceal = false; // h264mi_config.conceal_errors: lost macroblocks of concealable pictures are copied from a reference picture (k_conceal)
+    bool conceal_pics = false; // ... bit H264MI_CONCEAL_PICTURES: wholly lost reference frames are inserted as pictures without slices (conceal_frame_num_gap)
+    bool conceal_fields = false; // ... bit H264MI_CONCEAL_FIELDS: field pictures are concealable too
     int64_t concealed_slices = 0, concealed_mbs = 0; // totals since create (h264mi_decoder_concealed)
+    int64_t concealed_pics = 0;                      // (h264mi_decoder_concealed_pictures)
     bool isolate = false; // h264mi_decoder_set_isolation: a broken stream does not fail the batch
     // profiling
     bool profiling = false;
@@ -485,11 +488,17 @@ extern "C" int32_t h264mi_decoder_create(const h264mi_config *cfg_, h264mi_decod
     memcpy(&cfg_copy, cfg_, std::min<size_t>(cfg_->struct_size, sizeof(cfg_copy)));
     const h264mi_config *cfg = &cfg_copy;
     if (cfg->max_streams < 1 || cfg->max_width < 16 || cfg->max_height < 16 || cfg->max_frames_per_batch < 1) return H264MI_EINVAL;
+    if ((cfg->conceal_errors & ~(H264MI_CONCEAL_SLICES | H264MI_CONCEAL_PICTURES | H264MI_CONCEAL_FIELDS)) || (cfg->conceal_errors && !(cfg->conceal_errors & H264MI_CONCEAL_SLICES))) {
+        set_error("h264mi_decoder_create: h264mi_config.conceal_errors = %d (0, or H264MI_CONCEAL_SLICES with or without H264MI_CONCEAL_PICTURES and H264MI_CONCEAL_FIELDS)",
+                  cfg->conceal_errors);
+        return H264MI_EINVAL;
+    }
     int r = h264mi_init(cfg->device);
     if (r != H264MI_OK) return r;
     h264mi_decoder *d = new h264mi_decoder();
     d->cfg = *cfg;
-    d->conceal = cfg->conceal_errors != 0;
+    d->conceal = (cfg->conceal_errors & H264MI_CONCEAL_SLICES) != 0, d->conceal_pics = (cfg->conceal_errors & H264MI_CONCEAL_PICTURES) != 0;
+    d->conceal_fields = (cfg->conceal_errors & H264MI_CONCEAL_FIELDS) != 0;
     if (d->cfg.max_slices_per_frame < 1) d->cfg.max_slices_per_frame = 1;
     d->Wmax = (cfg->max_width + 15) & ~15;
     d->Hmax = (cfg->max_height + 15) & ~15;
@@ -755,6 +764,11 @@ extern "C" int32_t h264mi_decoder_unpinned_failures(h264mi_decoder *d, int64_t *
 extern "C" int32_t h264mi_decoder_concealed(h264mi_decoder *d, int64_t *slices, int64_t *macroblocks) {
     if (!d || !slices || !macroblocks) return H264MI_EINVAL;
     *slices = d->concealed_slices, *macroblocks = d->concealed_mbs;
+    return H264MI_OK;
+}
+extern "C" int32_t h264mi_decoder_concealed_pictures(h264mi_decoder *d, int64_t *pictures) {
+    if (!d || !pictures) return H264MI_EINVAL;
+    *pictures = d->concealed_pics;
     return H264MI_OK;
 }
 extern "C" int32_t h264mi_frame_concealed(h264mi_decoder *d, int32_t stream, int32_t frame, int32_t *n_macroblocks) {
@@ -1346,6 +1360,213 @@ static int ensure_b_buffers(h264mi_decoder *d) {
     return H264MI_OK;
 }
 
+// Entry 0 of the initial P list of 8.2.4.2.1 for a frame picture with frame_num `frame_num` that lives in slot `cur` (-1: not placed yet): the short-term
+// frame with the highest PicNum, else the long-term frame with the lowest LongTermPicNum; -1 if the list is empty
+static int initial_p_entry0(const StreamState &s, int cur, int frame_num, int max_fn) {
+    int best = -1, best_num = 0;
+    for (int pass = 1; pass <= 2 && best < 0; pass++) // short-term, then long-term
+        for (int i = 0; i < static_cast<int>(s.slots.size()); i++) {
+            const Slot &c = s.slots[i];
+            if (i == cur || c.ref != pass || c.fields != 3 || c.funref) continue;
+            const int num = pass == 1 ? (c.frame_num > frame_num ? c.frame_num - max_fn : c.frame_num) : -c.long_idx;
+            if (best < 0 || num > best_num) best = i, best_num = num;
+        }
+    return best;
+}
+
+// The first slice of a new picture (`sh`, of NAL unit type `type`; second: the second field of the frame in StreamState::pend_slot): its frame slot, its place
+// in the batch's tables, its PicDesc and the frame it goes out as.  The picture is then under construction (StreamState::cur_*) until finish_picture.
+static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const h264mi_pps &pps, uint32_t pps_id, const h264mi_slice_header &sh, int type, bool second) {
+    StreamState &s = d->st[si];
+    Stage &g = d->stage[d->prep];
+    const int wmb = sps.pic_width_in_mbs, hmb = sps.pic_height_in_mbs, hmb_pic = sh.field_pic ? hmb / 2 : hmb;
+    // (a field counts as a picture of its own against max_frames_per_batch: include/h264mi.h)
+    if (s.n_pics_in_batch >= d->cfg.max_frames_per_batch || g.n_pics >= d->pics_cap) {
+        set_error("stream %d: more than %d pictures in one batch", si, d->cfg.max_frames_per_batch);
+        return H264MI_ECAPACITY;
+    }
+    int r, slot = second ? s.pend_slot : -1;
+    for (int i = 0; i < static_cast<int>(s.slots.size()) && slot < 0; i++)
+        if (!s.slots[i].ref && !s.slots[i].held) slot = i;
+    if (slot < 0) {
+        set_error("stream %d: frame pool exhausted", si);
+        return H264MI_ECAPACITY;
+    }
+    if (g.mb_used + static_cast<uint64_t>(wmb) * hmb_pic > d->mb_cap) {
+        set_error("macroblock record pool exhausted");
+        return H264MI_ECAPACITY;
+    }
+    s.cur_slot = slot;
+    s.cur_pic = g.n_pics++;
+    s.cur_slices = 0;
+    s.cur_first_mbs.clear();
+    s.first_sh = sh;
+    s.cur_field = sh.field_pic ? 1 + (sh.bottom_field ? 1 : 0) : 0;
+    s.cur_second = second;
+    if (second) s.pend_slot = -1; // (it is the current picture's frame now; back in pend_slot only if it still lacks a field when this picture ends)
+    Slot &sl = s.slots[slot];
+    if (!second) {
+        sl = Slot();
+        sl.held = true;
+        sl.frame_num = sh.frame_num;
+        sl.field_coded = sh.field_pic != 0;
+    }
+    const int pic_poc = compute_poc(s, sps, sh);
+    if (sh.field_pic) {
+        sl.fpoc[sh.bottom_field ? 1 : 0] = pic_poc;
+        sl.fpic[sh.bottom_field ? 1 : 0] = s.cur_pic;
+        if (!second) sl.poc = pic_poc;
+    } else {
+        sl.poc = pic_poc, sl.fpoc[0] = s.poc_top, sl.fpoc[1] = s.poc_bot;
+        sl.fields = 3; // (a frame picture delivers both fields; it is not in its own reference lists)
+        sl.pic = s.cur_pic;
+    }
+    PicDesc &pd = g.h_pics[s.cur_pic];
+    memset(&pd, 0, sizeof(pd));
+    pd.stream = si, pd.slot = slot, pd.wmb = wmb, pd.hmb = hmb_pic;
+    // where the picture lives in its frame slot: a field picture in the rows of its parity (PicDesc)
+    pd.field = static_cast<uint8_t>(s.cur_field);
+    pd.pitch = static_cast<uint32_t>(wmb * 16 * (sh.field_pic ? 2 : 1)), pd.plane = static_cast<uint32_t>(wmb * 16) * static_cast<uint32_t>(hmb * 16);
+    pd.inv_wmb = static_cast<uint32_t>((1ull << 32) / static_cast<uint32_t>(wmb)) + 1u;
+    pd.pool_base = d->h_pools[si].base, pd.slot_bytes = d->slot_bytes, pd.n_slots = static_cast<uint32_t>(d->n_slots);
+    g.pic_level.resize(g.n_pics, 0), g.pic_save_col.resize(g.n_pics, 0), g.pic_wave.resize(g.n_pics, 0), g.pic_init_qp.resize(g.n_pics, 26);
+    g.pic_dropped.resize(g.n_pics, 0), g.pic_dropped[s.cur_pic] = 0;
+    g.pic_level[s.cur_pic] = 0, g.pic_save_col[s.cur_pic] = 0, g.pic_wave[s.cur_pic] = 0;
+    g.pic_init_qp[s.cur_pic] = static_cast<uint8_t>(std::min(std::max(26 + pps.pic_init_qp_minus26, 0), 51));
+    pd.conceal_ref = -1;
+    if (d->conceal && type != 5 && (!sh.field_pic || d->conceal_fields)) {
+        // Error concealment: the picture is concealable when the initial P list, built for THIS picture whatever the types of its slices, is not
+        // empty; its entry 0 is what lost macroblocks are copied from.  A frame picture (8.2.4.2.1): the short-term frame with the highest PicNum, else
+        // the long-term frame with the lowest LongTermPicNum.  A field picture (H264MI_CONCEAL_FIELDS; 8.2.4.2.5): the first field of the alternation
+        // that starts with this field's parity -- the first field of the same frame, if this is its second field and that one is a short-term
+        // reference --, written like every entry of a field list as slot | parity (MI_REF_PARITY).  (A frame inferred by the frame_num gap process
+        // holds no samples: not concealable.)
+        int best = -1;
+        if (sh.field_pic) {
+            h264mi_slice_header p = sh; // a P slice with one active reference and no list modification
+            p.slice_type = 0, p.num_ref_idx_l0_active_minus1 = 0, p.ref_pic_list_modification_flag_l0 = 0, p.n_ref_pic_list_modifications = 0;
+            int16_t l0[MI_MAX_REFS], l1[MI_MAX_REFS];
+            if (build_ref_lists_field(s, sps, p, false, l0, l1) == H264MI_OK) best = l0[0];
+        } else
+            best = initial_p_entry0(s, slot, sh.frame_num, 1 << (sps.log2_max_frame_num_minus4 + 4));
+        if (best >= 0 && !s.slots[sh.field_pic ? MI_REF_SLOT(best) : best].nonexisting) {
+            pd.conceal_ref = static_cast<int16_t>(best);
+            // ... and the picture is reconstructed behind it when this batch decodes it: a non-IDR I picture would otherwise be in wave 0, and the
+            // MODIFIED lists of a P picture's slices need not hold this entry
+            const Slot &rs = s.slots[sh.field_pic ? MI_REF_SLOT(best) : best];
+            for (int pic : {rs.pic, rs.fpic[0], rs.fpic[1]})
+                if (pic >= 0 && pic != s.cur_pic && pic < static_cast<int>(g.pic_wave.size())) g.pic_wave[s.cur_pic] = std::max(g.pic_wave[s.cur_pic], g.pic_wave[pic] + 1);
+        }
+    }
+    if (s.pending_drops) { // slices without a readable header in front of this picture's first good one: lost slices of it, if it can be concealed
+        const int n = s.pending_drops, e = s.pending_drop_err;
+        s.pending_drops = 0;
+        if (pd.conceal_ref < 0) {
+            set_error("stream %d: a slice header does not parse, in a picture that cannot be concealed", si);
+            return e;
+        }
+        g.pic_dropped[s.cur_pic] = static_cast<uint16_t>(std::min(n, 65535));
+    }
+    pd.mb_base = g.mb_used;
+    g.mb_used += static_cast<uint64_t>(wmb) * hmb_pic;
+    pd.first_slice = g.n_slices;
+    pd.cabac = pps.entropy_coding_mode, pd.t8x8_mode = pps.transform_8x8_mode, pd.cip = pps.constrained_intra_pred;
+    pd.mono = sps.chroma_format == 0;
+    pd.weighted_pred = pps.weighted_pred;
+    pd.cqp_off[0] = static_cast<int8_t>(pps.chroma_qp_index_offset), pd.cqp_off[1] = static_cast<int8_t>(pps.second_chroma_qp_index_offset);
+    pd.is_intra_only = 1;
+    int ss = scaling_set_for(d, pps);
+    if (ss < 0) {
+        set_error("more than %d distinct scaling matrices in flight", MI_MAX_SCALING_SETS);
+        return H264MI_ECAPACITY;
+    }
+    pd.scaling_set = static_cast<uint8_t>(ss);
+    pd.order = s.n_pics_in_batch++;
+    if (pps.num_slice_groups_minus1 > 0) { // FMO: this picture's macroblock-to-slice-group map travels with the bitstream (8.2.2; h264/slice.go:134-158)
+        const size_t n_mbs = static_cast<size_t>(wmb) * hmb_pic, moff = (g.map_cursor + 15) & ~static_cast<size_t>(15);
+        if (moff + n_mbs + 4096 > d->bits_cap) {
+            set_error("bitstream staging buffer too small for the slice group maps (%zu bytes)", d->bits_cap);
+            return H264MI_ECAPACITY;
+        }
+        r = mb_to_slice_group_map(&sps, &pps, s.sg_ids[pps_id].data(), s.sg_ids[pps_id].size(), sh.slice_group_change_cycle, sh.field_pic ? 1 : 0, g.h_bits + moff, n_mbs, nullptr);
+        if (r != H264MI_OK) return r;
+        pd.fmo = 1, pd.sgmap_off = static_cast<uint32_t>(moff);
+        g.map_cursor = moff + n_mbs;
+        g.bits_end = std::max(g.bits_end, g.map_cursor);
+    }
+    if (!second) { // the frame this picture belongs to, as it will be shown: pushed now (frame picture), or when its fields are through (finish_picture / flush_pending_field)
+        OutFrame of{slot, wmb, hmb, 2 * sps.frame_crop_left_offset, 2 * (2 - sps.frame_mbs_only) * sps.frame_crop_top_offset, sps.width, sps.height, sl.poc, sh.frame_num,
+                    sh.nal_ref_idc, sh.nal_unit_type == 5, s.cur_pic, sh.nal_unit_type == 5};
+        if (sh.nal_ref_idc && sh.adaptive_ref_pic_marking_mode_flag)
+            for (int k = 0; k < sh.n_memory_management_control_operations; k++)
+                if (sh.memory_management_control_operation[k] == 5) of.new_sequence = 1;
+        if (sh.field_pic)
+            s.pend_out = of;
+        else
+            g.out[si].push_back(of);
+    }
+    g.wmb_max = std::max(g.wmb_max, wmb);
+    g.hmb_max = std::max(g.hmb_max, hmb_pic);
+    g.mbs_max = std::max(g.mbs_max, wmb * hmb_pic);
+    g.info.n_macroblocks += static_cast<int64_t>(wmb) * hmb_pic;
+    if (si == 0) g.info.width = sps.width, g.info.height = sps.height, g.info.coded_width = wmb * 16, g.info.coded_height = hmb * 16;
+    return H264MI_OK;
+}
+
+// Error concealment of wholly lost reference frames (H264MI_CONCEAL_PICTURES; the rule: include/h264mi.h).  `sh` is the first slice of a picture that is
+// not the second field of the frame before it.  Where fill_frame_num_gap would refuse the stream -- frame_num skips values and the SPS does not allow
+// gaps -- and the gap is concealable, one frame picture WITHOUT SLICES per missing frame_num is put in front of the revealing picture: a picture of the
+// batch like any other (slot, PicDesc, records, output frame, POC, sliding window), all of whose macroblocks k_conceal writes as P_Skip copies of
+// PicDesc::conceal_ref -- which of the second inserted picture on is the inserted picture before it.  Returns H264MI_OK (inserted), 1 (no gap, or not
+// concealable: the caller goes on as without the bit) or an error.
+static int conceal_frame_num_gap(h264mi_decoder *d, int si, const h264mi_sps &sps, const h264mi_pps &pps, uint32_t pps_id, const h264mi_slice_header &sh) {
+    StreamState &s = d->st[si];
+    Stage &g = d->stage[d->prep];
+    if (sh.nal_unit_type == 5 || sps.gaps_in_frame_num_value_allowed) return 1;
+    const int max_fn = 1 << (sps.log2_max_frame_num_minus4 + 4), first = (s.prev_ref_frame_num + 1) % max_fn;
+    if (sh.frame_num == s.prev_ref_frame_num || sh.frame_num == first) return 1;
+    const int m = (sh.frame_num - first + max_fn) % max_fn;
+    if (m > H264MI_CONCEAL_MAX_GAP) return 1;
+    const int ref0 = initial_p_entry0(s, -1, first, max_fn);
+    if (ref0 < 0 || s.slots[ref0].nonexisting) return 1;
+    // the m pictures and the revealing one must fit into what the batch has left (a slot taken by a picture of this batch stays taken until the next
+    // prepare, so counting the free ones now is exact)
+    const uint64_t frame_mbs = static_cast<uint64_t>(sps.pic_width_in_mbs) * sps.pic_height_in_mbs;
+    int free_slots = 0;
+    for (const Slot &sl : s.slots) free_slots += !sl.ref && !sl.held;
+    if (s.n_pics_in_batch + m + 1 > d->cfg.max_frames_per_batch || g.n_pics + m + 1 > d->pics_cap || free_slots < m + 1) return 1;
+    if (g.mb_used + frame_mbs * m + (sh.field_pic ? frame_mbs / 2 : frame_mbs) > d->mb_cap) return 1;
+    if (pps.num_slice_groups_minus1 > 0) { // every picture's slice group map goes into the staging buffer (start_picture)
+        size_t cursor = g.map_cursor;
+        for (int k = 0; k <= m; k++) {
+            const size_t moff = (cursor + 15) & ~static_cast<size_t>(15);
+            if (moff + frame_mbs + 4096 > d->bits_cap) return 1;
+            cursor = moff + frame_mbs;
+        }
+    }
+    if (scaling_set_for(d, pps) < 0) return 1;
+    const int drops = s.pending_drops; // slices with an unreadable header in front of `sh` belong to ITS picture, not to an inserted one
+    s.pending_drops = 0;
+    for (int k = 0; k < m; k++) {
+        h264mi_slice_header f; // what the repaired stream's slices of this frame say, as far as picture management looks
+        memset(&f, 0, sizeof(f));
+        f.pps_id = static_cast<int32_t>(pps_id), f.frame_num = (first + k) % max_fn, f.nal_ref_idc = 1, f.nal_unit_type = 1;
+        f.slice_group_change_cycle = sh.slice_group_change_cycle;
+        if (sps.pic_order_count_type == 0) f.pic_order_cnt_lsb = (s.prev_poc_lsb + 2) % (1 << (sps.log2_max_pic_order_cnt_lsb_min4 + 4));
+        f.num_ref_idx_active_override = 1;
+        f.slice_qp_y = 26 + pps.pic_init_qp_minus26;
+        int r = start_picture(d, si, sps, pps, pps_id, f, 1, false);
+        if (r != H264MI_OK) return r;
+        if (g.h_pics[s.cur_pic].conceal_ref < 0) { // (cannot happen: entry 0 was looked up above, and from then on it is the picture inserted before)
+            set_error("stream %d: frame_num %d after %d: reference pictures are missing", si, sh.frame_num, s.prev_ref_frame_num);
+            return H264MI_EBITSTREAM;
+        }
+        finish_picture(d, si);
+    }
+    s.pending_drops = drops;
+    return H264MI_OK;
+}
+
 // one slice NAL of stream `si`
 // `off` / `rlen`: where batch_prepare's parallel pass put the slice's RBSP in the pinned staging buffer (16-byte aligned)
 static int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref_idc, int type) {
@@ -1467,137 +1688,12 @@ static int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref
                 flush_pending_field(d, si);
         }
         if (!second) {
-            r = fill_frame_num_gap(d, si, sps, sh);
+            r = d->conceal_pics ? conceal_frame_num_gap(d, si, sps, pps, pps_id, sh) : 1;
+            if (r == 1) r = fill_frame_num_gap(d, si, sps, sh);
             if (r != H264MI_OK) return r;
         }
-        // (a field counts as a picture of its own against max_frames_per_batch: include/h264mi.h)
-        if (s.n_pics_in_batch >= d->cfg.max_frames_per_batch || g.n_pics >= d->pics_cap) {
-            set_error("stream %d: more than %d pictures in one batch", si, d->cfg.max_frames_per_batch);
-            return H264MI_ECAPACITY;
-        }
-        int slot = second ? s.pend_slot : -1;
-        for (int i = 0; i < static_cast<int>(s.slots.size()) && slot < 0; i++)
-            if (!s.slots[i].ref && !s.slots[i].held) slot = i;
-        if (slot < 0) {
-            set_error("stream %d: frame pool exhausted", si);
-            return H264MI_ECAPACITY;
-        }
-        if (g.mb_used + static_cast<uint64_t>(wmb) * hmb_pic > d->mb_cap) {
-            set_error("macroblock record pool exhausted");
-            return H264MI_ECAPACITY;
-        }
-        s.cur_slot = slot;
-        s.cur_pic = g.n_pics++;
-        s.cur_slices = 0;
-        s.cur_first_mbs.clear();
-        s.first_sh = sh;
-        s.cur_field = sh.field_pic ? 1 + (sh.bottom_field ? 1 : 0) : 0;
-        s.cur_second = second;
-        if (second) s.pend_slot = -1; // (it is the current picture's frame now; back in pend_slot only if it still lacks a field when this picture ends)
-        Slot &sl = s.slots[slot];
-        if (!second) {
-            sl = Slot();
-            sl.held = true;
-            sl.frame_num = sh.frame_num;
-            sl.field_coded = sh.field_pic != 0;
-        }
-        const int pic_poc = compute_poc(s, sps, sh);
-        if (sh.field_pic) {
-            sl.fpoc[sh.bottom_field ? 1 : 0] = pic_poc;
-            sl.fpic[sh.bottom_field ? 1 : 0] = s.cur_pic;
-            if (!second) sl.poc = pic_poc;
-        } else {
-            sl.poc = pic_poc, sl.fpoc[0] = s.poc_top, sl.fpoc[1] = s.poc_bot;
-            sl.fields = 3; // (a frame picture delivers both fields; it is not in its own reference lists)
-            sl.pic = s.cur_pic;
-        }
-        PicDesc &pd = g.h_pics[s.cur_pic];
-        memset(&pd, 0, sizeof(pd));
-        pd.stream = si, pd.slot = slot, pd.wmb = wmb, pd.hmb = hmb_pic;
-        // where the picture lives in its frame slot: a field picture in the rows of its parity (PicDesc)
-        pd.field = static_cast<uint8_t>(s.cur_field);
-        pd.pitch = static_cast<uint32_t>(wmb * 16 * (sh.field_pic ? 2 : 1)), pd.plane = static_cast<uint32_t>(wmb * 16) * static_cast<uint32_t>(hmb * 16);
-        pd.inv_wmb = static_cast<uint32_t>((1ull << 32) / static_cast<uint32_t>(wmb)) + 1u;
-        pd.pool_base = d->h_pools[si].base, pd.slot_bytes = d->slot_bytes, pd.n_slots = static_cast<uint32_t>(d->n_slots);
-        g.pic_level.resize(g.n_pics, 0), g.pic_save_col.resize(g.n_pics, 0), g.pic_wave.resize(g.n_pics, 0), g.pic_init_qp.resize(g.n_pics, 26);
-        g.pic_dropped.resize(g.n_pics, 0), g.pic_dropped[s.cur_pic] = 0;
-        g.pic_level[s.cur_pic] = 0, g.pic_save_col[s.cur_pic] = 0, g.pic_wave[s.cur_pic] = 0;
-        g.pic_init_qp[s.cur_pic] = static_cast<uint8_t>(std::min(std::max(26 + pps.pic_init_qp_minus26, 0), 51));
-        pd.conceal_ref = -1;
-        if (d->conceal && !sh.field_pic && type != 5) {
-            // Error concealment: the picture is concealable when the initial P list of 8.2.4.2.1, built for THIS picture whatever the types of its
-            // slices, is not empty; its entry 0 -- the short-term frame with the highest PicNum, else the long-term frame with the lowest
-            // LongTermPicNum -- is what lost macroblocks are copied from.  (A frame inferred by the frame_num gap process holds no samples: not concealable.)
-            const int max_fn = 1 << (sps.log2_max_frame_num_minus4 + 4);
-            int best = -1, best_num = 0;
-            for (int pass = 1; pass <= 2 && best < 0; pass++) // short-term, then long-term
-                for (int i = 0; i < static_cast<int>(s.slots.size()); i++) {
-                    const Slot &c = s.slots[i];
-                    if (i == slot || c.ref != pass || c.fields != 3 || c.funref) continue;
-                    const int num = pass == 1 ? (c.frame_num > sh.frame_num ? c.frame_num - max_fn : c.frame_num) : -c.long_idx;
-                    if (best < 0 || num > best_num) best = i, best_num = num;
-                }
-            if (best >= 0 && !s.slots[best].nonexisting) {
-                pd.conceal_ref = static_cast<int16_t>(best);
-                // ... and the picture is reconstructed behind it when this batch decodes it: a non-IDR I picture would otherwise be in wave 0, and the
-                // MODIFIED lists of a P picture's slices need not hold this entry
-                const Slot &rs = s.slots[best];
-                for (int pic : {rs.pic, rs.fpic[0], rs.fpic[1]})
-                    if (pic >= 0 && pic != s.cur_pic && pic < static_cast<int>(g.pic_wave.size())) g.pic_wave[s.cur_pic] = std::max(g.pic_wave[s.cur_pic], g.pic_wave[pic] + 1);
-            }
-        }
-        if (s.pending_drops) { // slices without a readable header in front of this picture's first good one: lost slices of it, if it can be concealed
-            const int n = s.pending_drops, e = s.pending_drop_err;
-            s.pending_drops = 0;
-            if (pd.conceal_ref < 0) {
-                set_error("stream %d: a slice header does not parse, in a picture that cannot be concealed", si);
-                return e;
-            }
-            g.pic_dropped[s.cur_pic] = static_cast<uint16_t>(std::min(n, 65535));
-        }
-        pd.mb_base = g.mb_used;
-        g.mb_used += static_cast<uint64_t>(wmb) * hmb_pic;
-        pd.first_slice = g.n_slices;
-        pd.cabac = pps.entropy_coding_mode, pd.t8x8_mode = pps.transform_8x8_mode, pd.cip = pps.constrained_intra_pred;
-        pd.mono = sps.chroma_format == 0;
-        pd.weighted_pred = pps.weighted_pred;
-        pd.cqp_off[0] = static_cast<int8_t>(pps.chroma_qp_index_offset), pd.cqp_off[1] = static_cast<int8_t>(pps.second_chroma_qp_index_offset);
-        pd.is_intra_only = 1;
-        int ss = scaling_set_for(d, pps);
-        if (ss < 0) {
-            set_error("more than %d distinct scaling matrices in flight", MI_MAX_SCALING_SETS);
-            return H264MI_ECAPACITY;
-        }
-        pd.scaling_set = static_cast<uint8_t>(ss);
-        pd.order = s.n_pics_in_batch++;
-        if (pps.num_slice_groups_minus1 > 0) { // FMO: this picture's macroblock-to-slice-group map travels with the bitstream (8.2.2; h264/slice.go:134-158)
-            const size_t n_mbs = static_cast<size_t>(wmb) * hmb_pic, moff = (g.map_cursor + 15) & ~static_cast<size_t>(15);
-            if (moff + n_mbs + 4096 > d->bits_cap) {
-                set_error("bitstream staging buffer too small for the slice group maps (%zu bytes)", d->bits_cap);
-                return H264MI_ECAPACITY;
-            }
-            r = mb_to_slice_group_map(&sps, &pps, s.sg_ids[pps_id].data(), s.sg_ids[pps_id].size(), sh.slice_group_change_cycle, sh.field_pic ? 1 : 0, g.h_bits + moff, n_mbs, nullptr);
-            if (r != H264MI_OK) return r;
-            pd.fmo = 1, pd.sgmap_off = static_cast<uint32_t>(moff);
-            g.map_cursor = moff + n_mbs;
-            g.bits_end = std::max(g.bits_end, g.map_cursor);
-        }
-        if (!second) { // the frame this picture belongs to, as it will be shown: pushed now (frame picture), or when its fields are through (finish_picture / flush_pending_field)
-            OutFrame of{slot, wmb, hmb, 2 * sps.frame_crop_left_offset, 2 * (2 - sps.frame_mbs_only) * sps.frame_crop_top_offset, sps.width, sps.height, sl.poc, sh.frame_num,
-                        sh.nal_ref_idc, sh.nal_unit_type == 5, s.cur_pic, sh.nal_unit_type == 5};
-            if (sh.nal_ref_idc && sh.adaptive_ref_pic_marking_mode_flag)
-                for (int k = 0; k < sh.n_memory_management_control_operations; k++)
-                    if (sh.memory_management_control_operation[k] == 5) of.new_sequence = 1;
-            if (sh.field_pic)
-                s.pend_out = of;
-            else
-                g.out[si].push_back(of);
-        }
-        g.wmb_max = std::max(g.wmb_max, wmb);
-        g.hmb_max = std::max(g.hmb_max, hmb_pic);
-        g.mbs_max = std::max(g.mbs_max, wmb * hmb_pic);
-        g.info.n_macroblocks += static_cast<int64_t>(wmb) * hmb_pic;
-        if (si == 0) g.info.width = sps.width, g.info.height = sps.height, g.info.coded_width = wmb * 16, g.info.coded_height = hmb * 16;
+        r = start_picture(d, si, sps, pps, pps_id, sh, type, second);
+        if (r != H264MI_OK) return r;
     }
     if (s.cur_slices >= d->cfg.max_slices_per_frame) {
         set_error("stream %d: more than %d slices in a frame", si, d->cfg.max_slices_per_frame);
@@ -1756,12 +1852,12 @@ static int harvest_status(h264mi_decoder *d, Stage &g) {
             if (g.h_pics[sd.pic_idx].stream < g.epochs.size() && g.epochs[g.h_pics[sd.pic_idx].stream] != s.epoch) continue;
             // error concealment: k_conceal has rewritten every macroblock of the slice as a copy from the picture's concealment reference; the picture
             // is a reference like any other, the stream goes on
+            const bool field_cabac = g.h_pics[sd.pic_idx].field != 0 && g.h_pics[sd.pic_idx].cabac != 0;
+            if (field_cabac) d->unpinned_failures++; // what a wrong value in the unpinned context tables looks like: the slice does not end on end_of_slice_flag where it should
             if (d->conceal && g.h_pics[sd.pic_idx].conceal_ref >= 0) {
                 d->concealed_slices++;
                 continue;
             }
-            const bool field_cabac = g.h_pics[sd.pic_idx].field != 0 && g.h_pics[sd.pic_idx].cabac != 0;
-            if (field_cabac) d->unpinned_failures++; // what a wrong value in the unpinned context tables looks like: the slice does not end on end_of_slice_flag where it should
             if (result == H264MI_OK)
                 set_error("entropy kernel: slice %d (picture %u, stream %u) failed with code %u after %u macroblocks%s", i, sd.pic_idx, g.h_pics[sd.pic_idx].stream,
                           g.h_status[8 * i], g.h_status[8 * i + 1],
@@ -1776,7 +1872,8 @@ static int harvest_status(h264mi_decoder *d, Stage &g) {
     if (d->conceal) // the counter k_conceal left behind the status words: concealed macroblocks per picture; and the slices dropped for their header
         for (int p = 0; p < g.n_pics; p++)
             if (g.h_pics[p].stream >= g.epochs.size() || g.epochs[g.h_pics[p].stream] == d->st[g.h_pics[p].stream].epoch)
-                d->concealed_mbs += g.h_status[8 * g.n_slices + p], d->concealed_slices += g.pic_dropped[p];
+                d->concealed_mbs += g.h_status[8 * g.n_slices + p], d->concealed_slices += g.pic_dropped[p],
+                    d->concealed_pics += g.h_pics[p].n_slices == 0 && g.h_pics[p].conceal_ref >= 0; // (only an inserted picture has no slice: conceal_frame_num_gap)
     return result;
 }
 

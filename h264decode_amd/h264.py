@@ -197,6 +197,15 @@ def read_nal_units(stream: bytes):
     return out
 
 
+CONCEAL_SLICES, CONCEAL_PICTURES, CONCEAL_FIELDS = 1, 2, 4  # bits of h264mi_config.conceal_errors (H264MI_CONCEAL_*): 2 and 4 only together with CONCEAL_SLICES
+CONCEAL_MAX_GAP = 16                     # H264MI_CONCEAL_MAX_GAP: the longest run of lost frames that is concealed
+
+
+def _frames_with_headroom(frames_per_batch, conceal_errors):
+    """max_frames_per_batch of a decoder fed chunks of `frames_per_batch` pictures: frames inserted for lost pictures need room in a full chunk too."""
+    return frames_per_batch + (CONCEAL_MAX_GAP if int(conceal_errors) & CONCEAL_PICTURES else 0)
+
+
 class Decoder:
     """Batched GPU decoder: N independent Annex-B streams side by side on one MI355X."""
 
@@ -208,8 +217,9 @@ class Decoder:
         cfg.struct_size = ctypes.sizeof(cfg)
         cfg.b_pictures = b_pictures  # 1: the B-only buffers exist from the start (default: from the first B slice on)
         cfg.allow_unpinned_field_cabac = allow_unpinned_field_cabac  # 1: CABAC field pictures are decoded with the unpinned context tables of field-coded blocks (default: refused)
-        # 1: lost macroblocks of non-IDR frame pictures are copied from a reference picture and the stream goes on (default: the stream waits for an IDR picture)
-        cfg.conceal_errors = int(bool(conceal_errors))
+        # True / CONCEAL_SLICES: lost macroblocks of non-IDR frame pictures are copied from a reference picture and the stream goes on (default: the
+        # stream waits for an IDR picture); | CONCEAL_PICTURES: wholly lost reference frames are inserted as copies too; | CONCEAL_FIELDS: field pictures too
+        cfg.conceal_errors = int(conceal_errors)
         cfg.device, cfg.max_streams, cfg.max_width, cfg.max_height = device, max_streams, max_width, max_height
         cfg.max_frames_per_batch, cfg.max_slices_per_frame, cfg.max_bitstream_bytes = max_frames_per_batch, max_slices_per_frame, max_bitstream_bytes
         cfg.hip_stream = hip_stream
@@ -279,6 +289,12 @@ class Decoder:
         a, b = ctypes.c_int64(), ctypes.c_int64()
         check(self._L.h264mi_decoder_concealed(self._h, ctypes.byref(a), ctypes.byref(b)))
         return int(a.value), int(b.value)
+
+    def concealed_pictures(self):
+        """Frames inserted for wholly lost pictures since the decoder was created (h264mi_decoder_concealed_pictures)."""
+        n = ctypes.c_int64()
+        check(self._L.h264mi_decoder_concealed_pictures(self._h, ctypes.byref(n)))
+        return int(n.value)
 
     def coef_pool(self):
         """(used, capacity) of the residual-coefficient pool in 32-byte blocks (h264mi_decoder_coef_pool); call after sync()."""
@@ -598,7 +614,8 @@ class H264Reader:
         self.Stream = connection
         self.frames_per_batch = frames_per_batch
         self.decoder = decoder or Decoder(max_streams=1, max_width=(max_width + 15) // 16 * 16, max_height=(max_height + 15) // 16 * 16,
-                                          max_frames_per_batch=frames_per_batch, max_slices_per_frame=16, conceal_errors=conceal_errors)
+                                          max_frames_per_batch=_frames_with_headroom(frames_per_batch, conceal_errors), max_slices_per_frame=16,
+                                          conceal_errors=conceal_errors)
         self.on_frames = on_frames
         self.read_size = read_size
         self.splitter = AccessUnitSplitter(frames_per_batch)
@@ -669,7 +686,7 @@ class BatchServer:
 
     def __init__(self, max_connections=8, max_width=1920, max_height=1088, frames_per_batch=30, on_frames=None, on_close=None, read_size=1 << 16, conceal_errors=False):
         self.decoder = Decoder(max_streams=max_connections, max_width=(max_width + 15) // 16 * 16, max_height=(max_height + 15) // 16 * 16,
-                               max_frames_per_batch=frames_per_batch, max_slices_per_frame=16, conceal_errors=conceal_errors)
+                               max_frames_per_batch=_frames_with_headroom(frames_per_batch, conceal_errors), max_slices_per_frame=16, conceal_errors=conceal_errors)
         self.decoder.set_isolation(True)  # one bad client must not take the other connections' chunks down with it
         self.errors = [0] * max_connections
         self.n = max_connections

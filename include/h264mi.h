@@ -43,7 +43,7 @@ extern "C" {
 #define H264MI_EDEVICE (-6)     /* HIP runtime error */
 #define H264MI_ECAPACITY (-7)   /* caller buffer or decoder configuration too small */
 #define H264MI_EDECODE (-8)     /* a GPU entropy kernel reported a slice error.  With h264mi_config.conceal_errors a failed slice of a concealable picture
-                                 * (a non-IDR frame picture that has a reference picture) is not an error: it is concealed and counted (h264mi_decoder_concealed) */
+                                 * (a non-IDR frame picture -- with H264MI_CONCEAL_FIELDS: or field picture -- that has a reference picture) is not an error: it is concealed and counted (h264mi_decoder_concealed) */
 
 /* ---- NAL unit: h264/nalUnit.go:3-30 (NalUnit), :75-131 (NewNalUnit) ---- */
 typedef struct {
@@ -214,10 +214,45 @@ typedef struct {
      * The picture is kept and used as a reference, the stream's status stays H264MI_OK, nothing waits for an IDR picture.  The repair happens on the
      * device inside the pass, so pipelined callers get it for the batch prepared before the failure was known as well.  A slice NAL unit of
      * type 1 whose header does not parse is dropped and counted as a lost slice of the picture under construction (of the next picture, if there is none
-     * or it is an IDR picture) when that picture is concealable; otherwise it fails the stream as with 0.  IDR pictures, field pictures, pictures
-     * without any reference picture, wholly missing pictures and parameter-set errors are handled as with 0. */
+     * or it is an IDR picture) when that picture is concealable; otherwise it fails the stream as with 0.
+     * The field is a bit set; 0 and 1 mean what they always meant.  H264MI_CONCEAL_PICTURES (2, together with bit 1: value 3) = wholly lost REFERENCE FRAMES
+     * are concealed too.  They show as a gap in frame_num (the first slice of a picture that is not an IDR picture and not the second field of the frame
+     * before it, in a stream with gaps_in_frame_num_value_allowed_flag 0, carries a frame_num that is neither PrevRefFrameNum nor its successor):
+     * m = (frame_num - PrevRefFrameNum - 1) mod MaxFrameNum frames are missing.  If m <= H264MI_CONCEAL_MAX_GAP, entry 0 of the initial P list (8.2.4.2.1)
+     * of a frame with the first missing frame_num exists and holds samples, and the m pictures plus the revealing one fit into what the batch has left
+     * (max_frames_per_batch -- leave H264MI_CONCEAL_MAX_GAP of headroom --, frame slots, macroblock records), the decoder inserts one frame picture per
+     * missing value, in increasing frame_num order, in front of the revealing picture; otherwise everything is as with the bit clear ("reference pictures
+     * are missing", the stream waits for its IDR picture).  The result is bit for bit what a conforming decoder produces for the stream in which each
+     * missing frame is coded as: nal_unit_type 1, nal_ref_idc 1; one P slice of P_Skip macroblocks per slice group (first_mb_in_slice the lowest address
+     * of the group); pic_parameter_set_id and slice_group_change_cycle of the first slice seen of the revealing picture; the missing frame_num;
+     * field_pic_flag 0; pic_order_cnt_lsb = (prevPicOrderCntLsb + 2) mod MaxPicOrderCntLsb (8.2.1.1, inserted pictures included) and
+     * delta_pic_order_cnt_bottom 0 / delta_pic_order_cnt[0] = [1] = 0 / nothing for picture order count types 0 / 1 / 2; redundant_pic_cnt 0; one active
+     * reference, no list modification, a pred_weight_table() with all flags 0, sliding-window marking, cabac_init_idc 0, slice_qp_delta 0,
+     * disable_deblocking_filter_idc 0 with zero offsets.  Every boundary strength of such a picture is 0, so an inserted picture is an exact copy of
+     * entry 0 of its initial P list.  It is output in decoding order like any frame (h264mi_frame_get_info: its frame_num and PicOrderCnt, nal_ref_idc 1,
+     * idr 0), stays a reference and goes through the sliding window, updates PrevRefFrameNum and the picture order count state, and
+     * h264mi_frame_concealed reports all of its macroblocks (h264mi_decoder_concealed_pictures counts it).
+     * As with 0, whatever the bits: a lost NON-reference picture leaves no gap and is not noticed; pictures lost in front of an IDR picture are not
+     * inserted; a gap of a multiple of MaxFrameNum pictures is invisible; what the lost pictures carried is lost (a memory management operation, a
+     * long-term assignment, operation 5), and a later slice that depends on it fails as it always did ("ref_pic_list_modification names a missing
+     * picture", ...); in streams with B pictures the chosen PicOrderCnt can equal that of a B picture nearby, and the outcome is whatever the repaired
+     * stream decodes to.
+     * H264MI_CONCEAL_FIELDS (4, together with bit 1) = the rule of value 1 holds for FIELD pictures too: a field picture that is not an IDR picture and
+     * whose initial P list for fields (8.2.4.2.5, built for this field: it includes the first field of the same frame when that is a reference) is not
+     * empty and has an entry 0 that holds samples.  The lost macroblocks are a zero-motion copy of that entry 0 -- for the second field of an IDR frame
+     * the frame's own first field --; in the repaired stream the replacement P slices carry field_pic_flag 1 and the picture's bottom_field_flag, and
+     * delta_pic_order_cnt_bottom / delta_pic_order_cnt[1] are absent (7.3.3).  The tolerance for type-1 slices whose header does not parse extends to
+     * such pictures.  CABAC field pictures still need allow_unpinned_field_cabac, and h264mi_decoder_unpinned_failures counts their failed slices
+     * whether they are concealed or not.
+     * With every value: IDR pictures, a wholly missing field (its rows stay mid-grey), MBAFF (out of scope altogether), pictures without any reference
+     * picture and parameter-set errors are handled as with 0.  A value with bit 2 or 4 set and bit 1 clear, or with any bit above 4, is refused by
+     * h264mi_decoder_create (H264MI_EINVAL). */
     int32_t conceal_errors;
 } h264mi_config;
+#define H264MI_CONCEAL_SLICES 1    /* h264mi_config.conceal_errors: lost and damaged slices of non-IDR frame pictures */
+#define H264MI_CONCEAL_PICTURES 2  /* ... and wholly lost reference frames (only together with H264MI_CONCEAL_SLICES) */
+#define H264MI_CONCEAL_FIELDS 4    /* ... and lost and damaged slices of field pictures (only together with H264MI_CONCEAL_SLICES) */
+#define H264MI_CONCEAL_MAX_GAP 16  /* the longest run of lost frames that is concealed: the largest DPB -- older frames would have left the sliding window anyway */
 #define H264MI_CONFIG_INIT {(uint32_t)sizeof(h264mi_config)} /* h264mi_config cfg = H264MI_CONFIG_INIT; then set the fields */
 
 typedef struct {
@@ -334,6 +369,9 @@ int32_t h264mi_decoder_unpinned_failures(h264mi_decoder *dec, int64_t *n);
  * were dropped for an unparsable header and were concealed, and concealed macroblocks (lost NAL units the decoder never saw count as macroblocks only). */
 int32_t h264mi_frame_concealed(h264mi_decoder *dec, int32_t stream, int32_t frame, int32_t *n_macroblocks);
 int32_t h264mi_decoder_concealed(h264mi_decoder *dec, int64_t *slices, int64_t *macroblocks);
+/* Frames inserted for wholly lost pictures (H264MI_CONCEAL_PICTURES) since the decoder was created, counted like the totals above when their batch is
+ * synchronised.  Their macroblocks are part of the macroblock total of h264mi_decoder_concealed; the slice total does not count them. */
+int32_t h264mi_decoder_concealed_pictures(h264mi_decoder *dec, int64_t *pictures);
 
 const char *h264mi_last_error_string(void);
 const char *h264mi_version(void);

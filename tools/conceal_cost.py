@@ -6,6 +6,8 @@
     clean    with the switch on, intact streams       (k_conceal launched, nothing to do)
     damaged  with the switch on, the slice data of about --permille of the P slices zeroed
              (the streams have one slice per picture: a failed slice conceals the whole picture)
+    lost     with H264MI_CONCEAL_PICTURES on top, about --permille of the non-IDR reference pictures REMOVED: every one of them is a frame_num gap
+             that the decoder fills with an inserted frame (frames/s counts output frames, so the inserted ones are included)
 
 and prints one JSON line with frames/s of each.  For the duration of k_conceal per pass run one mode under the profiler:
 
@@ -36,6 +38,19 @@ def damage(stream, permille, rnd):
     return b"".join(units), n
 
 
+def lose(stream, permille, rnd):
+    """The stream without about `permille` of its non-IDR reference pictures (never the last picture: something has to reveal the gap)."""
+    import concealutil as cu
+    units, _, pics = cu.parse(stream)
+    n = 0
+    for p in pics[1:-1]:
+        if p[0].type == 1 and p[0].ref_idc and rnd.random() * 1000 < permille:
+            for s in p:
+                units[s.unit] = b""
+            n += 1
+    return b"".join(units), n
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=256)
@@ -46,7 +61,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--permille", type=float, default=10.0, help="share of the P slices that are damaged")
-    ap.add_argument("--modes", default="off,clean,damaged")
+    ap.add_argument("--modes", default="off,clean,damaged,lost")
     ap.add_argument("--seed", type=int, default=1)
     args = ap.parse_args()
     import torch
@@ -65,15 +80,19 @@ def main():
             dm = [damage(g[0], args.permille, rnd) for g in gen]
             streams = [dm[i % nd][0] for i in range(S)]
             n_damaged = sum(dm[i % nd][1] for i in range(S))
+        if mode == "lost":
+            dm = [lose(g[0], args.permille, rnd) for g in gen]
+            streams = [dm[i % nd][0] for i in range(S)]
+            n_damaged = sum(dm[i % nd][1] for i in range(S))
         dec = H.Decoder(max_streams=S, max_width=W, max_height=Hc, max_frames_per_batch=F, max_slices_per_frame=1, max_bitstream_bytes=int(sum(len(s) for s in streams) * 1.1) + (1 << 20),
-                        hip_stream=torch.cuda.current_stream().cuda_stream, conceal_errors=mode != "off")
+                        hip_stream=torch.cuda.current_stream().cuda_stream, conceal_errors=0 if mode == "off" else (H.CONCEAL_SLICES | H.CONCEAL_PICTURES if mode == "lost" else H.CONCEAL_SLICES))
         info = dec.prepare(streams)
         assert info.n_frames == S * F
         for _ in range(args.warmup):
             dec.execute()
         dec.sync()
         torch.cuda.synchronize()
-        before = dec.concealed()
+        before, pics_before = dec.concealed(), dec.concealed_pictures()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             dec.execute()
@@ -81,7 +100,8 @@ def main():
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         after = dec.concealed()
-        out["modes"][mode] = {"frames_per_s": round(S * F * args.steps / dt, 1), "ms_per_step": round(dt / args.steps * 1e3, 3), "damaged_slices_in_batch": n_damaged,
+        out["modes"][mode] = {"frames_per_s": round(S * F * args.steps / dt, 1), "ms_per_step": round(dt / args.steps * 1e3, 3), ("lost_pictures_in_batch" if mode == "lost" else "damaged_slices_in_batch"): n_damaged,
+                              "inserted_pictures_last_pass": dec.concealed_pictures() - pics_before,
                               "concealed_slices_last_pass": after[0] - before[0], "concealed_macroblocks_last_pass": after[1] - before[1],
                               "stream_status_errors": sum(1 for i in range(S) if dec.stream_status(i) != 0)}
         dec.close()

@@ -9,7 +9,7 @@
 #include <vector>
 
 int main(int argc, char **argv) {
-    if (argc < 5) { fprintf(stderr, "usage: host_pocs stream.h264 max_width max_height max_frames [max_slices]\n"); return 2; }
+    if (argc < 5) { fprintf(stderr, "usage: host_pocs stream.h264 max_width max_height max_frames [max_slices [conceal_errors [allow_unpinned_field_cabac]]]\n"); return 2; }
     FILE *f = fopen(argv[1], "rb");
     if (!f) return 2;
     fseek(f, 0, SEEK_END);
@@ -23,6 +23,7 @@ int main(int argc, char **argv) {
     cfg.struct_size = sizeof cfg;
     cfg.max_streams = 1, cfg.max_width = atoi(argv[2]), cfg.max_height = atoi(argv[3]), cfg.max_frames_per_batch = atoi(argv[4]);
     cfg.max_slices_per_frame = argc > 5 ? atoi(argv[5]) : 64, cfg.max_bitstream_bytes = len + 4096;
+    cfg.conceal_errors = argc > 6 ? atoi(argv[6]) : 0, cfg.allow_unpinned_field_cabac = argc > 7 ? atoi(argv[7]) : 0;
     h264mi_decoder *dec = nullptr;
     if (h264mi_decoder_create(&cfg, &dec) != 0) { fprintf(stderr, "create: %s\n", h264mi_last_error_string()); return 1; }
     const uint8_t *bufs[1] = {buf.data()};

@@ -27,8 +27,12 @@ def main():
     ap.add_argument("--out", default=None, help="append decoded frames (tight I420) to this file")
     ap.add_argument("--once", action="store_true", help="serve one connection and exit")
     ap.add_argument("--conceal", action="store_true", help="error concealment: lost or damaged slices are filled from a reference picture, the stream goes on")
+    ap.add_argument("--conceal-pictures", action="store_true", help="... and wholly lost reference pictures are replaced by a copy of the picture before them (implies --conceal)")
+    ap.add_argument("--conceal-fields", action="store_true", help="... and lost or damaged slices of field pictures are concealed too (implies --conceal)")
     ap.add_argument("--batch", type=int, default=0, help="decode up to N concurrent connections side by side in one batched decoder (H.BatchServer)")
     args = ap.parse_args()
+    conceal = (H.CONCEAL_PICTURES if args.conceal_pictures else 0) | (H.CONCEAL_FIELDS if args.conceal_fields else 0)
+    conceal = conceal | H.CONCEAL_SLICES if conceal else int(args.conceal)
     srv = socket.socket()
     srv.setsockopt(socket.SOL_SOCKET, socket.SO_REUSEADDR, 1)
     srv.bind((args.host, args.port))
@@ -37,7 +41,7 @@ def main():
     out = open(args.out, "ab") if args.out else None
     if args.batch > 0:  # several connections, one batched GPU decoder
         import select
-        bs = H.BatchServer(max_connections=args.batch, max_width=args.max_width, max_height=args.max_height, frames_per_batch=args.frames_per_batch, conceal_errors=args.conceal,
+        bs = H.BatchServer(max_connections=args.batch, max_width=args.max_width, max_height=args.max_height, frames_per_batch=args.frames_per_batch, conceal_errors=conceal,
                            on_frames=lambda i, f: print("slot %d: %d frames md5 %s" % (i, len(f), hashlib.md5(f.tobytes()).hexdigest()), flush=True),
                            on_close=lambda i, n: print("slot %d closed after %d frames" % (i, n), flush=True))
         srv.setblocking(False)
@@ -59,7 +63,7 @@ def main():
 
         try:
             H.ByteStreamReader(conn, on_frames=on_frames, max_width=args.max_width, max_height=args.max_height, frames_per_batch=args.frames_per_batch,
-                               display_order=args.display_order, conceal_errors=args.conceal)
+                               display_order=args.display_order, conceal_errors=conceal)
         except H.H264MIError as e:
             print("%s: decode error: %s" % (peer[0], e), flush=True)
         if args.once:
