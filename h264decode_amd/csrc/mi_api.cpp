@@ -1,5 +1,6 @@
 // h264decode_amd/csrc/mi_api.cpp -- the C ABI of libh264mi.so (include/h264mi.h): host-side
-// front end (NAL dispatch h264/server.go:113-166, picture management 8.2) and GPU launch sequence.
+// front end (NAL dispatch h264/server.go:113-166; where pictures go in a batch's tables, asking mi_dpb.cpp -- picture management 8.2 -- for
+// slots, counts and lists) and GPU launch sequence.
 //
 // There is deliberately NO CPU pixel path in this library: every sample is produced by the HIP
 // kernels in k_entropy.hip / k_recon.hip / k_deblock.hip.  If no device is usable the create call
@@ -17,6 +18,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/h264mi.h"
+#include "mi_dpb.hpp"
 #include "mi_kernels.h"
 #include "mi_parse.hpp"
 #include "mi_tables.h"
@@ -175,24 +177,6 @@ static void build_scaling(const uint8_t s4[6][16], const uint8_t s8[2][64], Scal
 }
 
 // ---------------------------------------------------------------- per-stream host state
-struct Slot {
-    int ref = 0; // 0 unused, 1 short-term, 2 long-term
-    int frame_num = 0, frame_num_wrap = 0, pic_num = 0, long_idx = 0, poc = 0;
-    // Output of the current batch, or a reference picture at the start of the batch: not reused before the next prepare.
-    // (The second half keeps h264mi_batch_execute repeatable: a slot freed by a marking operation in the middle of the
-    // batch still holds the samples earlier pictures of the batch predict from.)
-    bool held = false;
-    bool nonexisting = false; // a frame inferred by the gaps-in-frame_num process (8.2.5.2): a place in the window, no picture
-    int pic = -1; // index into the PicDesc table of the batch being prepared, -1: decoded by an earlier batch (field-coded frames: fpic[])
-    // Fields (h264/slice.go:867-872 field_pic_flag / bottom_field_flag; h264/sps.go:316-322).  A frame slot holds both fields of a frame, however
-    // they were coded: a frame picture fills both at once (fields = 3), a field picture the rows of its parity.
-    int fields = 0;          // decoded fields: bit 0 top, bit 1 bottom
-    int funref = 0;          // fields taken out of the reference set one by one (memory_management_control_operation 1 in a field picture, 8.2.5.4.1)
-    int fpoc[2] = {0, 0};    // PicOrderCnt of the top / bottom field (8.2.1); `poc` is the frame's: the smaller one, or that of the only field there is
-    int fpic[2] = {-1, -1};  // PicDesc of the field pictures decoded by the batch being prepared
-    bool field_coded = false;          // coded as field pictures (direct prediction needs a co-located picture of the same structure as the current one)
-    bool col_valid[2] = {false, false}; // the ColRec array of the frame / top field [0], the bottom field [1] holds this picture's motion
-};
 struct OutFrame { // a decoded picture of the current batch, with the geometry it was coded with
     int slot, wmb, hmb, crop_x, crop_y, width, height;
     int poc, frame_num, nal_ref_idc, idr, pic;
@@ -208,22 +192,11 @@ struct StreamState {
     bool sps_ok[32] = {}, pps_ok[256] = {};
     int active_sps = -1;
     int wmb = 0, hmb = 0;
-    std::vector<Slot> slots;
-    int prev_poc_msb = 0, prev_poc_lsb = 0, prev_frame_num = 0, prev_frame_num_offset = 0;
-    int top_above_poc = 0; // TopFieldOrderCnt - PicOrderCnt of the picture compute_poc() was last asked about (> 0: its bottom field comes first)
-    int poc_top = 0, poc_bot = 0; // TopFieldOrderCnt / BottomFieldOrderCnt of that picture (a field picture: both its one count)
-    int prev_ref_frame_num = 0; // PrevRefFrameNum (7.4.3): frame_num of the previous reference picture; 0 after an IDR picture or operation 5
-    // picture under construction
-    int cur_slot = -1, cur_pic = -1, cur_slices = 0;
-    int cur_field = 0;        // the picture under construction is 0 a frame, 1 a top field, 2 a bottom field
-    bool cur_second = false;  // ... and the second field of its frame (it may predict from the first one)
-    // A frame whose first field has been decoded waits here for its second field (the next picture, if it is a field of the other parity
-    // with the same frame_num, 7.4.1.2.4 / 3.30); it goes out -- once -- when that field is complete, or with one field decoded (the rows of
-    // the other one mid-grey) when something else follows: another picture, an end-of-sequence / end-of-stream NAL unit, a reset.  The wait
-    // may span a batch boundary.
-    int pend_slot = -1;
+    Dpb dpb; // frame slots, POC / frame_num history, the picture under construction (dpb.cur_slot >= 0) and its frame slot: mi_dpb.hpp
+    int cur_pic = -1, cur_slices = 0; // the picture under construction: its PicDesc, slices so far
+    // The frame that waits in dpb.pend_slot for its second field goes out -- once -- when that field is complete, or with one field decoded (the
+    // rows of the other one mid-grey) when something else follows: another picture, an end-of-sequence / end-of-stream NAL unit, a reset.
     OutFrame pend_out;
-    h264mi_slice_header first_sh;
     int n_pics_in_batch = 0;
     int status = H264MI_OK; // of this stream in the current batch (h264mi_stream_status)
     const void *status_batch = nullptr; // the batch whose entropy kernels set `status` (harvest_status)
@@ -519,7 +492,7 @@ extern "C" int32_t h264mi_decoder_create(const h264mi_config *cfg_, h264mi_decod
     d->slot_bytes = (static_cast<size_t>(d->Wmax) * d->Hmax * 3 / 2 + 255) & ~static_cast<size_t>(255);
     const int S = cfg->max_streams;
     d->st.resize(S);
-    for (auto &s : d->st) s.slots.resize(d->n_slots);
+    for (auto &s : d->st) s.dpb.slots.resize(d->n_slots);
     d->pics_cap = S * cfg->max_frames_per_batch;
     d->slices_cap = d->pics_cap * d->cfg.max_slices_per_frame;
     d->mb_cap = static_cast<uint64_t>(d->pics_cap) * (d->Wmax / 16) * (d->Hmax / 16);
@@ -710,13 +683,11 @@ extern "C" int32_t h264mi_decoder_set_stream(h264mi_decoder *d, void *s) {
 }
 // Forget everything about a stream: parameter sets, reference pictures, POC / frame_num history, outputs.
 static void reset_stream(StreamState &s, bool keep_parameter_sets) {
-    for (auto &sl : s.slots) sl = Slot();
+    s.dpb.reset();
     s.epoch++;
-    s.cur_slot = s.cur_pic = -1, s.cur_slices = 0;
-    s.cur_field = 0, s.cur_second = false, s.pend_slot = -1;
+    s.cur_pic = -1, s.cur_slices = 0;
     s.n_pics_in_batch = 0;
     s.pending_drops = 0;
-    s.prev_poc_msb = s.prev_poc_lsb = s.prev_frame_num = s.prev_frame_num_offset = s.prev_ref_frame_num = 0;
     if (!keep_parameter_sets) {
         memset(s.sps_ok, 0, sizeof(s.sps_ok));
         memset(s.pps_ok, 0, sizeof(s.pps_ok));
@@ -798,377 +769,24 @@ extern "C" int32_t h264mi_decoder_set_profiling(h264mi_decoder *d, int32_t on) {
     return H264MI_OK;
 }
 
-// ---------------------------------------------------------------- picture management (8.2)
-static int compute_poc(StreamState &s, const h264mi_sps &sps, const h264mi_slice_header &sh) { // 8.2.1
-    const bool idr = sh.nal_unit_type == 5;
-    const int max_fn = 1 << (sps.log2_max_frame_num_minus4 + 4);
-    int poc = 0;
-    if (sps.pic_order_count_type == 0) {
-        const int max_lsb = 1 << (sps.log2_max_pic_order_cnt_lsb_min4 + 4);
-        int prev_msb = idr ? 0 : s.prev_poc_msb, prev_lsb = idr ? 0 : s.prev_poc_lsb, msb;
-        if (sh.pic_order_cnt_lsb < prev_lsb && prev_lsb - sh.pic_order_cnt_lsb >= max_lsb / 2)
-            msb = prev_msb + max_lsb;
-        else if (sh.pic_order_cnt_lsb > prev_lsb && sh.pic_order_cnt_lsb - prev_lsb > max_lsb / 2)
-            msb = prev_msb - max_lsb;
-        else
-            msb = prev_msb;
-        const int top = msb + sh.pic_order_cnt_lsb, bot = top + sh.delta_pic_order_cnt_bottom; // (8-4 / 8-5: a field picture has the one count, delta is 0)
-        poc = std::min(top, bot);
-        s.top_above_poc = top - poc;
-        s.poc_top = top, s.poc_bot = bot;
-        if (sh.nal_ref_idc) s.prev_poc_msb = msb, s.prev_poc_lsb = sh.pic_order_cnt_lsb;
-    } else {
-        int fno = idr ? 0 : (s.prev_frame_num > sh.frame_num ? s.prev_frame_num_offset + max_fn : s.prev_frame_num_offset);
-        if (sps.pic_order_count_type == 1) {
-            int n = sps.num_ref_frames_in_pic_order_cnt_cycle;
-            int abs_fn = n ? fno + sh.frame_num : 0;
-            if (!sh.nal_ref_idc && abs_fn > 0) abs_fn--;
-            int expected = 0;
-            if (abs_fn > 0) {
-                int cyc = (abs_fn - 1) / n, in_cyc = (abs_fn - 1) % n, delta = 0;
-                for (int i = 0; i < n; i++) delta += sps.offset_for_ref_frame_list[i];
-                expected = cyc * delta;
-                for (int i = 0; i <= in_cyc; i++) expected += sps.offset_for_ref_frame_list[i];
-            }
-            if (!sh.nal_ref_idc) expected += sps.offset_for_non_ref_pic;
-            const int top = expected + sh.delta_pic_order_cnt[0], bot = top + sps.offset_for_top_to_bottom_field + sh.delta_pic_order_cnt[1];
-            if (sh.field_pic) // 8-10: a bottom field is at expected + offset_for_top_to_bottom_field + delta_pic_order_cnt[0]
-                poc = sh.bottom_field ? expected + sps.offset_for_top_to_bottom_field + sh.delta_pic_order_cnt[0] : top, s.poc_top = s.poc_bot = poc;
-            else
-                poc = std::min(top, bot), s.poc_top = top, s.poc_bot = bot;
-        } else {
-            poc = idr ? 0 : (sh.nal_ref_idc ? 2 * (fno + sh.frame_num) : 2 * (fno + sh.frame_num) - 1);
-            s.poc_top = s.poc_bot = poc;
-        }
-        s.prev_frame_num_offset = fno;
-    }
-    s.prev_frame_num = sh.frame_num;
-    return poc;
-}
-
-// 8.2.4 for a field picture (8.2.4.2.2 / 8.2.4.2.4 + 8.2.4.2.5, modification 8.2.4.3 with the field picture numbers of 8.2.4.1): the lists hold
-// FIELDS, written as frame slot | parity << 14 (MI_REF_PARITY).  The reference frames are put in order first -- P: by FrameNumWrap, the frame
-// of the current field included when this is its second field and the first one is a reference; B: by PicOrderCnt around the current field,
-// list 0 the earlier ones nearest first and then the later ones, list 1 the other way round; long-term frames by LongTermFrameIdx --, then
-// their fields are taken alternately, the parity of the current field first; a frame that lacks the wanted field is passed over, and when one
-// parity is used up the rest of the other one follows in order.
-static int build_ref_lists_field(StreamState &s, const h264mi_sps &sps, const h264mi_slice_header &sh, bool bslice, int16_t *out0, int16_t *out1) {
-    const int max_fn = 1 << (sps.log2_max_frame_num_minus4 + 4);
-    const int bottom = sh.bottom_field ? 1 : 0;
-    auto usable = [&](int slot, int par) { return ((s.slots[slot].fields & ~s.slots[slot].funref) >> par) & 1; };
-    std::vector<int> st, lt;
-    for (int i = 0; i < static_cast<int>(s.slots.size()); i++) {
-        Slot &sl = s.slots[i];
-        if (i == s.cur_slot && !(s.cur_second && sl.ref == 1)) continue; // (a second field may predict from the first field of its frame)
-        if (sl.ref == 1) {
-            sl.frame_num_wrap = sl.frame_num > sh.frame_num ? sl.frame_num - max_fn : sl.frame_num;
-            st.push_back(i);
-        } else if (sl.ref == 2)
-            lt.push_back(i);
-    }
-    std::sort(lt.begin(), lt.end(), [&](int a, int b) { return s.slots[a].long_idx < s.slots[b].long_idx; });
-    if (st.empty() && lt.empty()) {
-        set_error("P/B slice without reference pictures");
-        return H264MI_EBITSTREAM;
-    }
-    std::vector<int> ord[2];
-    if (!bslice) {
-        std::sort(st.begin(), st.end(), [&](int a, int b) { return s.slots[a].frame_num_wrap > s.slots[b].frame_num_wrap; });
-        ord[0] = st;
-    } else {
-        // PicOrderCnt of a reference frame here: the smaller of its fields' (Slot::poc); of the current frame (second field): its first field's
-        const int cur_poc = s.slots[s.cur_slot].fpoc[bottom];
-        std::vector<std::pair<int, int>> before, after; // (PicOrderCnt, slot)
-        for (int i : st) {
-            if (s.slots[i].nonexisting) continue;
-            const int fp = i == s.cur_slot ? s.slots[i].fpoc[!bottom] : s.slots[i].poc;
-            (fp <= cur_poc ? before : after).push_back({fp, i});
-        }
-        std::stable_sort(before.begin(), before.end(), [](const std::pair<int, int> &a, const std::pair<int, int> &b) { return a.first > b.first; });
-        std::stable_sort(after.begin(), after.end(), [](const std::pair<int, int> &a, const std::pair<int, int> &b) { return a.first < b.first; });
-        for (auto &e : before) ord[0].push_back(e.second);
-        for (auto &e : after) ord[0].push_back(e.second), ord[1].push_back(e.second);
-        for (auto &e : before) ord[1].push_back(e.second);
-    }
-    std::vector<int> lists[2];
-    for (int l = 0; l < (bslice ? 2 : 1); l++)
-        for (int grp = 0; grp < 2; grp++) { // short-term frames, then long-term frames: each group alternates on its own
-            const std::vector<int> &fr = grp ? lt : ord[l];
-            const int nfr = static_cast<int>(fr.size());
-            int a = 0, b = 0; // next frame to look at for the same / the opposite parity
-            for (int want_same = 1;; want_same ^= 1) {
-                int &cursor = want_same ? a : b;
-                const int par = want_same ? bottom : !bottom;
-                while (cursor < nfr && !usable(fr[cursor], par)) cursor++;
-                if (cursor == nfr) { // this parity is used up: the rest of the other one
-                    int &other = want_same ? b : a;
-                    for (; other < nfr; other++)
-                        if (usable(fr[other], !par)) lists[l].push_back(fr[other] | (!par ? MI_REF_PARITY : 0));
-                    break;
-                }
-                lists[l].push_back(fr[cursor] | (par ? MI_REF_PARITY : 0));
-                cursor++;
-            }
-        }
-    if (bslice && lists[1].size() > 1 && lists[1] == lists[0]) std::swap(lists[1][0], lists[1][1]);
-    const int max_pic_num = 2 * max_fn, cur_pic_num = 2 * sh.frame_num + 1; // 8.2.4.1: MaxPicNum, CurrPicNum of a field
-    for (int l = 0; l < (bslice ? 2 : 1); l++) {
-        std::vector<int> &list = lists[l];
-        const int nact = (l ? sh.num_ref_idx_l1_active_minus1 : sh.num_ref_idx_l0_active_minus1) + 1;
-        if (nact > MI_MAX_REFS) {
-            set_error("num_ref_idx_l%d_active %d > %d reference fields is out of scope", l, nact, MI_MAX_REFS);
-            return H264MI_EUNSUPPORTED;
-        }
-        list.resize(nact, -1);
-        list.resize(nact + 1, -1);
-        const int32_t *idcs = l ? sh.modification_of_pic_nums_l1 : sh.modification_of_pic_nums, *vals = l ? sh.modification_value_l1 : sh.modification_value;
-        const int nmod = l ? sh.n_ref_pic_list_modifications_l1 : sh.n_ref_pic_list_modifications;
-        if (l ? sh.ref_pic_list_modification_flag_l1 : sh.ref_pic_list_modification_flag_l0) { // 8.2.4.3 on field picture numbers
-            int pred = cur_pic_num, idx = 0;
-            for (int k = 0; k < nmod && idx < nact; k++) {
-                int target = -1;
-                if (idcs[k] < 2) {
-                    const int diff = vals[k] + 1;
-                    if (idcs[k] == 0) {
-                        pred -= diff;
-                        if (pred < 0) pred += max_pic_num;
-                    } else {
-                        pred += diff;
-                        if (pred >= max_pic_num) pred -= max_pic_num;
-                    }
-                    const int picnum = pred > cur_pic_num ? pred - max_pic_num : pred;
-                    for (int i : st)
-                        for (int par = 0; par < 2; par++) // picNumF: 2 * FrameNumWrap + 1 for a field of the current parity, 2 * FrameNumWrap for the other
-                            if (usable(i, par) && 2 * s.slots[i].frame_num_wrap + (par == bottom) == picnum) target = i | (par ? MI_REF_PARITY : 0);
-                } else
-                    for (int i : lt)
-                        for (int par = 0; par < 2; par++)
-                            if (usable(i, par) && 2 * s.slots[i].long_idx + (par == bottom) == vals[k]) target = i | (par ? MI_REF_PARITY : 0);
-                if (target < 0) {
-                    set_error("ref_pic_list_modification names a missing field");
-                    return H264MI_EBITSTREAM;
-                }
-                for (int c = nact; c > idx; c--) list[c] = list[c - 1];
-                list[idx++] = target;
-                int nidx = idx;
-                for (int c = idx; c <= nact; c++)
-                    if (list[c] != target) list[nidx++] = list[c];
-            }
-        }
-        int16_t *out = l ? out1 : out0;
-        for (int i = 0; i < MI_MAX_REFS; i++) out[i] = static_cast<int16_t>(i < nact ? list[i] : -1);
-    }
-    return H264MI_OK;
-}
-
-// 8.2.4: RefPicList0 (P and B slices) and RefPicList1 (B slices) as frame-pool slots
-static int build_ref_lists(StreamState &s, const h264mi_sps &sps, const h264mi_slice_header &sh, bool bslice, int16_t *out0 /*MI_MAX_REFS*/, int16_t *out1) {
-    if (sh.field_pic) return build_ref_lists_field(s, sps, sh, bslice, out0, out1);
-    const int max_fn = 1 << (sps.log2_max_frame_num_minus4 + 4);
-    std::vector<int> st, lt;
-    for (int i = 0; i < static_cast<int>(s.slots.size()); i++) {
-        Slot &sl = s.slots[i];
-        if (i == s.cur_slot) continue;
-        // 8.2.4.2.1: a frame picture predicts from frames (or complementary field pairs) of which BOTH fields are reference fields
-        if (sl.ref && (sl.fields != 3 || sl.funref)) continue;
-        if (sl.ref == 1) {
-            sl.frame_num_wrap = sl.frame_num > sh.frame_num ? sl.frame_num - max_fn : sl.frame_num;
-            sl.pic_num = sl.frame_num_wrap;
-            st.push_back(i);
-        } else if (sl.ref == 2) {
-            sl.pic_num = sl.long_idx;
-            lt.push_back(i);
-        }
-    }
-    std::sort(lt.begin(), lt.end(), [&](int a, int b) { return s.slots[a].long_idx < s.slots[b].long_idx; });
-    if (st.empty() && lt.empty()) {
-        set_error("P/B slice without reference pictures");
-        return H264MI_EBITSTREAM;
-    }
-    std::vector<int> lists[2];
-    if (!bslice) { // 8.2.4.2.1: PicNum descending, then LongTermPicNum ascending
-        std::sort(st.begin(), st.end(), [&](int a, int b) { return s.slots[a].pic_num > s.slots[b].pic_num; });
-        lists[0] = st;
-    } else { // 8.2.4.2.3: by PicOrderCnt relative to the current picture
-        const int cur_poc = s.slots[s.cur_slot].poc;
-        std::vector<int> before, after;
-        for (int i : st) {
-            if (s.slots[i].nonexisting && sps.pic_order_count_type == 0) continue; // 8.2.4.2.3: no PicOrderCnt, not in the lists of B slices
-            (s.slots[i].poc < cur_poc ? before : after).push_back(i);
-        }
-        std::sort(before.begin(), before.end(), [&](int a, int b) { return s.slots[a].poc > s.slots[b].poc; });
-        std::sort(after.begin(), after.end(), [&](int a, int b) { return s.slots[a].poc < s.slots[b].poc; });
-        lists[0] = before;
-        lists[0].insert(lists[0].end(), after.begin(), after.end());
-        lists[1] = after;
-        lists[1].insert(lists[1].end(), before.begin(), before.end());
-        lists[1].insert(lists[1].end(), lt.begin(), lt.end());
-    }
-    lists[0].insert(lists[0].end(), lt.begin(), lt.end());
-    if (bslice && lists[1].size() > 1 && lists[1] == lists[0]) std::swap(lists[1][0], lists[1][1]);
-    for (int l = 0; l < (bslice ? 2 : 1); l++) {
-        std::vector<int> &list = lists[l];
-        const int nact = (l ? sh.num_ref_idx_l1_active_minus1 : sh.num_ref_idx_l0_active_minus1) + 1;
-        if (nact > MI_MAX_REFS) {
-            set_error("num_ref_idx_l%d_active %d > %d (field refs are out of scope)", l, nact, MI_MAX_REFS);
-            return H264MI_EUNSUPPORTED;
-        }
-        list.resize(nact, -1); // the initial list is cut (or padded with "no reference picture") to the active size
-        list.resize(nact + 1, -1);
-        const int32_t *idcs = l ? sh.modification_of_pic_nums_l1 : sh.modification_of_pic_nums, *vals = l ? sh.modification_value_l1 : sh.modification_value;
-        const int nmod = l ? sh.n_ref_pic_list_modifications_l1 : sh.n_ref_pic_list_modifications;
-        if (l ? sh.ref_pic_list_modification_flag_l1 : sh.ref_pic_list_modification_flag_l0) { // 8.2.4.3
-            int pred = sh.frame_num, idx = 0;
-            for (int k = 0; k < nmod && idx < nact; k++) {
-                int target = -1;
-                if (idcs[k] < 2) {
-                    int diff = vals[k] + 1;
-                    if (idcs[k] == 0) {
-                        pred -= diff;
-                        if (pred < 0) pred += max_fn;
-                    } else {
-                        pred += diff;
-                        if (pred >= max_fn) pred -= max_fn;
-                    }
-                    int picnum = pred > sh.frame_num ? pred - max_fn : pred;
-                    for (int i : st)
-                        if (s.slots[i].pic_num == picnum) target = i;
-                } else
-                    for (int i : lt)
-                        if (s.slots[i].long_idx == vals[k]) target = i;
-                if (target < 0) {
-                    set_error("ref_pic_list_modification names a missing picture");
-                    return H264MI_EBITSTREAM;
-                }
-                for (int c = nact; c > idx; c--) list[c] = list[c - 1];
-                list[idx++] = target;
-                int nidx = idx;
-                for (int c = idx; c <= nact; c++)
-                    if (list[c] != target) list[nidx++] = list[c];
-            }
-        }
-        int16_t *out = l ? out1 : out0;
-        for (int i = 0; i < MI_MAX_REFS; i++) out[i] = static_cast<int16_t>(i < nact ? list[i] : -1);
-    }
-    return H264MI_OK;
-}
-
-// 8.2.5: marking after the current picture is complete
-static void mark_reference(StreamState &s, const h264mi_sps &sps) {
-    const h264mi_slice_header &sh = s.first_sh;
-    Slot &cur = s.slots[s.cur_slot];
-    const int max_fn = 1 << (sps.log2_max_frame_num_minus4 + 4);
-    if (sh.nal_ref_idc) s.prev_ref_frame_num = sh.frame_num; // (operation 5 below: 0)
-    if (s.cur_field && sh.nal_ref_idc && sh.nal_unit_type != 5 && sh.adaptive_ref_pic_marking_mode_flag) {
-        // 8.2.5.4.1 in a field picture: picNumX names a FIELD (8.2.4.1); the frame stays in the window while its other field is a reference.
-        // (operations 2..6 on fields were refused when the picture started)
-        const int bottom = s.cur_field == 2, cur_pic_num = 2 * sh.frame_num + 1;
-        for (int k = 0; k < sh.n_memory_management_control_operations; k++) {
-            const int picnum = cur_pic_num - (sh.mmco_arg1[k] + 1);
-            for (auto &sl : s.slots) {
-                if (sl.ref != 1) continue;
-                const int wrap = sl.frame_num > sh.frame_num ? sl.frame_num - max_fn : sl.frame_num;
-                for (int par = 0; par < 2; par++)
-                    if ((((sl.fields & ~sl.funref) >> par) & 1) && 2 * wrap + (par == bottom) == picnum) {
-                        sl.funref |= 1 << par;
-                        if (!(sl.fields & ~sl.funref)) sl.ref = 0; // (the current frame, whose other field is being decoded, is marked just below)
-                    }
-            }
-        }
-        cur.ref = 1;
-        return;
-    }
-    // 8.2.5.3: the second field of a frame whose first field is a reference joins it; nothing leaves the window
-    if (s.cur_field && s.cur_second && cur.ref) return;
-    if (!sh.nal_ref_idc) {
-        cur.ref = 0;
-        return;
-    }
-    if (sh.nal_unit_type == 5) {
-        for (auto &sl : s.slots) sl.ref = 0;
-        cur.ref = sh.long_term_reference_flag ? 2 : 1;
-        cur.long_idx = 0;
-        return;
-    }
-    cur.ref = 1;
-    if (sh.adaptive_ref_pic_marking_mode_flag) {
-        for (int k = 0; k < sh.n_memory_management_control_operations; k++) {
-            int op = sh.memory_management_control_operation[k];
-            for (auto &sl : s.slots)
-                if (sl.ref == 1) sl.pic_num = sl.frame_num > sh.frame_num ? sl.frame_num - max_fn : sl.frame_num;
-            if (op == 1 || op == 3) {
-                int picnum = sh.frame_num - (sh.mmco_arg1[k] + 1);
-                for (auto &sl : s.slots)
-                    if (&sl != &cur && sl.ref == 1 && sl.pic_num == picnum) {
-                        if (op == 1)
-                            sl.ref = 0;
-                        else {
-                            for (auto &o : s.slots)
-                                if (o.ref == 2 && o.long_idx == sh.mmco_arg2[k]) o.ref = 0;
-                            sl.ref = 2, sl.long_idx = sh.mmco_arg2[k];
-                        }
-                    }
-            } else if (op == 2) {
-                for (auto &sl : s.slots)
-                    if (sl.ref == 2 && sl.long_idx == sh.mmco_arg1[k]) sl.ref = 0;
-            } else if (op == 4) {
-                for (auto &sl : s.slots)
-                    if (sl.ref == 2 && sl.long_idx >= sh.mmco_arg1[k]) sl.ref = 0;
-            } else if (op == 5) {
-                for (auto &sl : s.slots)
-                    if (&sl != &cur) sl.ref = 0;
-                cur.frame_num = 0, cur.poc = 0; // 8.2.1: tempPicOrderCnt is subtracted, the picture ends up at PicOrderCnt 0
-                {
-                    const int m = std::min(cur.fpoc[0], cur.fpoc[1]);
-                    cur.fpoc[0] -= m, cur.fpoc[1] -= m;
-                }
-                s.prev_frame_num = s.prev_frame_num_offset = s.prev_poc_msb = s.prev_ref_frame_num = 0;
-                // 8.2.1.1: prevPicOrderCntLsb = TopFieldOrderCnt after tempPicOrderCnt was subtracted -- 0 unless the bottom field is the earlier one
-                s.prev_poc_lsb = sps.pic_order_count_type == 0 ? s.top_above_poc : 0;
-            } else if (op == 6) {
-                for (auto &o : s.slots)
-                    if (o.ref == 2 && o.long_idx == sh.mmco_arg2[k]) o.ref = 0;
-                cur.ref = 2, cur.long_idx = sh.mmco_arg2[k];
-            }
-        }
-    } else { // sliding window 8.2.5.3
-        int nref = 0, maxref = std::max(sps.max_num_ref_frames, 1);
-        Slot *oldest = nullptr;
-        for (auto &sl : s.slots) {
-            if (&sl == &cur || !sl.ref) continue;
-            nref++;
-            if (sl.ref == 1) {
-                sl.frame_num_wrap = sl.frame_num > sh.frame_num ? sl.frame_num - max_fn : sl.frame_num;
-                if (!oldest || sl.frame_num_wrap < oldest->frame_num_wrap) oldest = &sl;
-            }
-        }
-        if (nref >= maxref && oldest) oldest->ref = 0;
-    }
-}
-
+// ---------------------------------------------------------------- the pictures of a batch (picture management, 8.2: mi_dpb.cpp)
 static void finish_picture(h264mi_decoder *d, int si) {
     StreamState &s = d->st[si];
     Stage &g = d->stage[d->prep];
-    if (s.cur_slot < 0) return;
-    mark_reference(s, s.sps[s.active_sps]);
+    Dpb &dpb = s.dpb;
+    if (dpb.cur_slot < 0) return;
+    dpb.finish_picture(s.sps[s.active_sps]);
     PicDesc &pd = g.h_pics[s.cur_pic];
     pd.n_slices = static_cast<uint32_t>(s.cur_slices);
-    if (s.cur_field) {
+    if (dpb.cur_field) {
         // a field: the frame goes out when its second field is complete -- or, if that never comes, when the next picture starts (flush_pending_field)
-        Slot &cur = s.slots[s.cur_slot];
-        cur.fields |= 1 << (s.cur_field - 1);
-        if (cur.fields == 3) {
-            cur.poc = std::min(cur.fpoc[0], cur.fpoc[1]);
-            s.pend_out.poc = cur.poc;
-            if (s.cur_second) s.pend_out.pic2 = s.cur_pic;
+        if (dpb.pend_slot < 0) {
+            s.pend_out.poc = dpb.slots[dpb.cur_slot].poc;
+            if (dpb.cur_second) s.pend_out.pic2 = s.cur_pic;
             g.out[si].push_back(s.pend_out);
-            s.pend_slot = -1;
-        } else {
-            cur.poc = cur.fpoc[s.cur_field - 1];
-            s.pend_slot = s.cur_slot;
         }
     } else if (!g.out[si].empty())
-        g.out[si].back().poc = s.slots[s.cur_slot].poc; // operation 5 rewrites it
+        g.out[si].back().poc = dpb.slots[dpb.cur_slot].poc; // operation 5 rewrites it
     // Every macroblock of the picture belongs to exactly one slice wavefront (SliceDesc::fill_from / end_mb): order the
     // slices by first_mb (arbitrary slice order is legal in Baseline); a slice's range ends where the next one starts.
     std::vector<uint32_t> idx(pd.n_slices);
@@ -1195,39 +813,21 @@ static void finish_picture(h264mi_decoder *d, int si) {
             sd.fill_from = i == 0 ? 0 : sd.first_mb;
             sd.end_mb = i + 1 < pd.n_slices ? std::max(g.h_slices[idx[i + 1]].first_mb, sd.first_mb) : total;
         }
-    s.cur_slot = s.cur_pic = -1;
+    dpb.cur_slot = s.cur_pic = -1;
 }
 
 // A first field whose second field did not come: the frame goes out with one field decoded, the rows of the other parity painted mid-grey
 // (at the start of the batch's reconstruction: whatever the slot held before must not show)
 static void flush_pending_field(h264mi_decoder *d, int si) {
     StreamState &s = d->st[si];
-    if (s.pend_slot < 0) return;
+    if (s.dpb.pend_slot < 0) return;
     Stage &g = d->stage[d->prep];
-    const Slot &f = s.slots[s.pend_slot];
+    const Slot &f = s.dpb.slots[s.dpb.pend_slot];
     OutFrame o = s.pend_out;
     o.poc = f.poc;
     g.out[si].push_back(o);
-    g.grey.push_back({static_cast<uint32_t>(si), static_cast<uint32_t>(s.pend_slot), f.fields == 1 ? 1u : 0u, static_cast<uint32_t>(o.wmb * 16), static_cast<uint32_t>(o.hmb * 16)});
-    s.pend_slot = -1;
-}
-
-static bool new_picture(const h264mi_sps &sps, const h264mi_slice_header &a, const h264mi_slice_header &b) { // 7.4.1.2.4
-    if (a.frame_num != b.frame_num || a.pps_id != b.pps_id) return true;
-    if (a.field_pic != b.field_pic || a.bottom_field != b.bottom_field) return true; // (the two fields of a frame are two pictures)
-    if ((a.nal_ref_idc == 0) != (b.nal_ref_idc == 0)) return true;
-    if ((a.nal_unit_type == 5) != (b.nal_unit_type == 5)) return true;
-    if (a.nal_unit_type == 5 && a.idr_pic_id != b.idr_pic_id) return true;
-    if (sps.pic_order_count_type == 0 && (a.pic_order_cnt_lsb != b.pic_order_cnt_lsb || a.delta_pic_order_cnt_bottom != b.delta_pic_order_cnt_bottom)) return true;
-    if (sps.pic_order_count_type == 1 && (a.delta_pic_order_cnt[0] != b.delta_pic_order_cnt[0] || a.delta_pic_order_cnt[1] != b.delta_pic_order_cnt[1])) return true;
-    // not in the list of 7.4.1.2.4, but a consequence of 7.4.3: all slices of a picture carry the same slice_group_change_cycle (the map is the
-    // picture's), the same marking script and the same long_term_reference_flag -- a difference means another picture even when frame_num and the
-    // picture order count agree (they do after memory management operation 5 resets both)
-    if (a.slice_group_change_cycle != b.slice_group_change_cycle) return true;
-    if (a.adaptive_ref_pic_marking_mode_flag != b.adaptive_ref_pic_marking_mode_flag || a.n_memory_management_control_operations != b.n_memory_management_control_operations) return true;
-    for (int k = 0; k < a.n_memory_management_control_operations; k++)
-        if (a.memory_management_control_operation[k] != b.memory_management_control_operation[k] || a.mmco_arg1[k] != b.mmco_arg1[k] || a.mmco_arg2[k] != b.mmco_arg2[k]) return true;
-    return false;
+    g.grey.push_back({static_cast<uint32_t>(si), static_cast<uint32_t>(s.dpb.pend_slot), f.fields == 1 ? 1u : 0u, static_cast<uint32_t>(o.wmb * 16), static_cast<uint32_t>(o.hmb * 16)});
+    s.dpb.pend_slot = -1;
 }
 
 extern "C" int32_t h264mi_slice_starts_picture(const h264mi_sps *sps, const h264mi_slice_header *prev, const h264mi_slice_header *cur) {
@@ -1254,44 +854,18 @@ static int scaling_set_for(h264mi_decoder *d, const h264mi_pps &p) {
 // refused (H264MI_EBITSTREAM; with isolation it alone leaves the batch and waits for its next IDR picture) rather than
 // predicted from the wrong pictures.
 static int fill_frame_num_gap(h264mi_decoder *d, int si, const h264mi_sps &sps, const h264mi_slice_header &sh) {
-    StreamState &s = d->st[si];
-    if (sh.nal_unit_type == 5) return H264MI_OK;
-    const int max_fn = 1 << (sps.log2_max_frame_num_minus4 + 4), cur_fn = sh.frame_num;
-    const int expect = (s.prev_ref_frame_num + 1) % max_fn;
-    if (cur_fn == s.prev_ref_frame_num || cur_fn == expect) return H264MI_OK;
+    Dpb &dpb = d->st[si].dpb;
+    const int m = dpb.missing_frames(sps, sh), max_fn = 1 << (sps.log2_max_frame_num_minus4 + 4);
+    if (!m) return H264MI_OK;
     if (!sps.gaps_in_frame_num_value_allowed) {
-        set_error("stream %d: frame_num %d after %d: reference pictures are missing", si, cur_fn, s.prev_ref_frame_num);
+        set_error("stream %d: frame_num %d after %d: reference pictures are missing", si, sh.frame_num, dpb.prev_ref_frame_num);
         return H264MI_EBITSTREAM;
     }
-    const int maxref = std::max(sps.max_num_ref_frames, 1);
-    for (int fn = expect; fn != cur_fn; fn = (fn + 1) % max_fn) {
-        int nref = 0;
-        Slot *oldest = nullptr, *slot = nullptr;
-        for (auto &sl : s.slots) { // 8.2.5.3 with this frame as the current one
-            if (!sl.ref) continue;
-            nref++;
-            if (sl.ref == 1) {
-                sl.frame_num_wrap = sl.frame_num > fn ? sl.frame_num - max_fn : sl.frame_num;
-                if (!oldest || sl.frame_num_wrap < oldest->frame_num_wrap) oldest = &sl;
-            }
-        }
-        if (nref >= maxref && oldest) oldest->ref = 0;
-        for (auto &sl : s.slots)
-            if (!sl.ref && !sl.held && !slot) slot = &sl;
-        if (!slot) {
+    for (int k = 0; k < m; k++)
+        if (!dpb.add_nonexisting_frame(sps, (dpb.prev_ref_frame_num + 1) % max_fn)) {
             set_error("stream %d: frame pool exhausted", si);
             return H264MI_ECAPACITY;
         }
-        *slot = Slot();
-        slot->ref = 1, slot->nonexisting = true, slot->frame_num = fn, slot->fields = 3;
-        if (sps.pic_order_count_type != 0) { // 8.2.1: as a reference frame with this frame_num (keeps FrameNumOffset right across a wrap)
-            h264mi_slice_header f;
-            memset(&f, 0, sizeof(f));
-            f.frame_num = fn, f.nal_ref_idc = 1, f.nal_unit_type = 1;
-            slot->poc = compute_poc(s, sps, f);
-        }
-        s.prev_ref_frame_num = fn;
-    }
     return H264MI_OK;
 }
 
@@ -1336,7 +910,7 @@ static int ensure_b_buffers(h264mi_decoder *d) {
         std::vector<uint32_t> list;
         auto want = [&](size_t si, const OutFrame &o, int pic, int par) {
             if (pic < 0 || pic >= pv.n_pics) return;
-            Slot &sl = d->st[si].slots[o.slot];
+            Slot &sl = d->st[si].dpb.slots[o.slot];
             pv.h_pics[pic].save_col = 1;
             pv.h_pics[pic].col_out = reinterpret_cast<uint64_t>(d->d_colrec + (si * d->n_slots + o.slot) * d->colrec_per_slot + (par ? d->colrec_per_slot / 2 : 0));
             sl.col_valid[par] = true;
@@ -1344,7 +918,7 @@ static int ensure_b_buffers(h264mi_decoder *d) {
         };
         for (size_t si = 0; si < S; si++)
             for (const OutFrame &o : pv.out[si])
-                if (d->st[si].slots[o.slot].ref) { // still a reference picture: a B picture may point at it
+                if (d->st[si].dpb.slots[o.slot].ref) { // still a reference picture: a B picture may point at it
                     for (int pic : {o.pic, o.pic2})
                         if (pic >= 0 && pic < pv.n_pics) want(si, o, pic, pv.h_pics[pic].field == 2 ? 1 : 0);
                 }
@@ -1360,22 +934,17 @@ static int ensure_b_buffers(h264mi_decoder *d) {
     return H264MI_OK;
 }
 
-// Entry 0 of the initial P list of 8.2.4.2.1 for a frame picture with frame_num `frame_num` that lives in slot `cur` (-1: not placed yet): the short-term
-// frame with the highest PicNum, else the long-term frame with the lowest LongTermPicNum; -1 if the list is empty
-static int initial_p_entry0(const StreamState &s, int cur, int frame_num, int max_fn) {
-    int best = -1, best_num = 0;
-    for (int pass = 1; pass <= 2 && best < 0; pass++) // short-term, then long-term
-        for (int i = 0; i < static_cast<int>(s.slots.size()); i++) {
-            const Slot &c = s.slots[i];
-            if (i == cur || c.ref != pass || c.fields != 3 || c.funref) continue;
-            const int num = pass == 1 ? (c.frame_num > frame_num ? c.frame_num - max_fn : c.frame_num) : -c.long_idx;
-            if (best < 0 || num > best_num) best = i, best_num = num;
-        }
-    return best;
+// The pictures of this batch that live in the frame slot a list entry names (a frame, or either field: whichever of them this batch decodes) have to
+// be reconstructed (deblocked) before picture `pic`, which predicts from it: Stage::pic_wave
+static void wave_after(Stage &g, const Dpb &dpb, int pic, int entry) {
+    if (entry < 0) return;
+    const Slot &rs = dpb.slots[MI_REF_SLOT(entry)]; // (frame pictures never set the parity bit)
+    for (int p : {rs.pic, rs.fpic[0], rs.fpic[1]})
+        if (p >= 0 && p != pic && p < static_cast<int>(g.pic_wave.size())) g.pic_wave[pic] = std::max(g.pic_wave[pic], g.pic_wave[p] + 1);
 }
 
-// The first slice of a new picture (`sh`, of NAL unit type `type`; second: the second field of the frame in StreamState::pend_slot): its frame slot, its place
-// in the batch's tables, its PicDesc and the frame it goes out as.  The picture is then under construction (StreamState::cur_*) until finish_picture.
+// The first slice of a new picture (`sh`, of NAL unit type `type`; second: the second field of the frame in Dpb::pend_slot): its frame slot, its place
+// in the batch's tables, its PicDesc and the frame it goes out as.  The picture is then under construction (Dpb::cur_slot, StreamState::cur_*) until finish_picture.
 static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const h264mi_pps &pps, uint32_t pps_id, const h264mi_slice_header &sh, int type, bool second) {
     StreamState &s = d->st[si];
     Stage &g = d->stage[d->prep];
@@ -1385,9 +954,7 @@ static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const
         set_error("stream %d: more than %d pictures in one batch", si, d->cfg.max_frames_per_batch);
         return H264MI_ECAPACITY;
     }
-    int r, slot = second ? s.pend_slot : -1;
-    for (int i = 0; i < static_cast<int>(s.slots.size()) && slot < 0; i++)
-        if (!s.slots[i].ref && !s.slots[i].held) slot = i;
+    int r, slot = second ? s.dpb.pend_slot : s.dpb.first_free_slot();
     if (slot < 0) {
         set_error("stream %d: frame pool exhausted", si);
         return H264MI_ECAPACITY;
@@ -1396,36 +963,16 @@ static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const
         set_error("macroblock record pool exhausted");
         return H264MI_ECAPACITY;
     }
-    s.cur_slot = slot;
     s.cur_pic = g.n_pics++;
     s.cur_slices = 0;
     s.cur_first_mbs.clear();
-    s.first_sh = sh;
-    s.cur_field = sh.field_pic ? 1 + (sh.bottom_field ? 1 : 0) : 0;
-    s.cur_second = second;
-    if (second) s.pend_slot = -1; // (it is the current picture's frame now; back in pend_slot only if it still lacks a field when this picture ends)
-    Slot &sl = s.slots[slot];
-    if (!second) {
-        sl = Slot();
-        sl.held = true;
-        sl.frame_num = sh.frame_num;
-        sl.field_coded = sh.field_pic != 0;
-    }
-    const int pic_poc = compute_poc(s, sps, sh);
-    if (sh.field_pic) {
-        sl.fpoc[sh.bottom_field ? 1 : 0] = pic_poc;
-        sl.fpic[sh.bottom_field ? 1 : 0] = s.cur_pic;
-        if (!second) sl.poc = pic_poc;
-    } else {
-        sl.poc = pic_poc, sl.fpoc[0] = s.poc_top, sl.fpoc[1] = s.poc_bot;
-        sl.fields = 3; // (a frame picture delivers both fields; it is not in its own reference lists)
-        sl.pic = s.cur_pic;
-    }
+    s.dpb.begin_picture(sps, sh, slot, second, s.cur_pic);
+    const Slot &sl = s.dpb.slots[slot];
     PicDesc &pd = g.h_pics[s.cur_pic];
     memset(&pd, 0, sizeof(pd));
     pd.stream = si, pd.slot = slot, pd.wmb = wmb, pd.hmb = hmb_pic;
     // where the picture lives in its frame slot: a field picture in the rows of its parity (PicDesc)
-    pd.field = static_cast<uint8_t>(s.cur_field);
+    pd.field = static_cast<uint8_t>(s.dpb.cur_field);
     pd.pitch = static_cast<uint32_t>(wmb * 16 * (sh.field_pic ? 2 : 1)), pd.plane = static_cast<uint32_t>(wmb * 16) * static_cast<uint32_t>(hmb * 16);
     pd.inv_wmb = static_cast<uint32_t>((1ull << 32) / static_cast<uint32_t>(wmb)) + 1u;
     pd.pool_base = d->h_pools[si].base, pd.slot_bytes = d->slot_bytes, pd.n_slots = static_cast<uint32_t>(d->n_slots);
@@ -1436,26 +983,15 @@ static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const
     pd.conceal_ref = -1;
     if (d->conceal && type != 5 && (!sh.field_pic || d->conceal_fields)) {
         // Error concealment: the picture is concealable when the initial P list, built for THIS picture whatever the types of its slices, is not
-        // empty; its entry 0 is what lost macroblocks are copied from.  A frame picture (8.2.4.2.1): the short-term frame with the highest PicNum, else
-        // the long-term frame with the lowest LongTermPicNum.  A field picture (H264MI_CONCEAL_FIELDS; 8.2.4.2.5): the first field of the alternation
-        // that starts with this field's parity -- the first field of the same frame, if this is its second field and that one is a short-term
-        // reference --, written like every entry of a field list as slot | parity (MI_REF_PARITY).  (A frame inferred by the frame_num gap process
-        // holds no samples: not concealable.)
-        int best = -1;
-        if (sh.field_pic) {
-            h264mi_slice_header p = sh; // a P slice with one active reference and no list modification
-            p.slice_type = 0, p.num_ref_idx_l0_active_minus1 = 0, p.ref_pic_list_modification_flag_l0 = 0, p.n_ref_pic_list_modifications = 0;
-            int16_t l0[MI_MAX_REFS], l1[MI_MAX_REFS];
-            if (build_ref_lists_field(s, sps, p, false, l0, l1) == H264MI_OK) best = l0[0];
-        } else
-            best = initial_p_entry0(s, slot, sh.frame_num, 1 << (sps.log2_max_frame_num_minus4 + 4));
-        if (best >= 0 && !s.slots[sh.field_pic ? MI_REF_SLOT(best) : best].nonexisting) {
+        // empty; its entry 0 is what lost macroblocks are copied from.  A field picture's (H264MI_CONCEAL_FIELDS) is a field -- the first field of the
+        // same frame, if this is its second field and that one is a short-term reference --, written like every entry of a field list as
+        // slot | parity (MI_REF_PARITY).  (A frame inferred by the frame_num gap process holds no samples: not concealable.)
+        const int best = s.dpb.initial_p_entry0(sps, sh.frame_num, s.dpb.cur_field);
+        if (best >= 0 && !s.dpb.slots[MI_REF_SLOT(best)].nonexisting) {
             pd.conceal_ref = static_cast<int16_t>(best);
             // ... and the picture is reconstructed behind it when this batch decodes it: a non-IDR I picture would otherwise be in wave 0, and the
             // MODIFIED lists of a P picture's slices need not hold this entry
-            const Slot &rs = s.slots[sh.field_pic ? MI_REF_SLOT(best) : best];
-            for (int pic : {rs.pic, rs.fpic[0], rs.fpic[1]})
-                if (pic >= 0 && pic != s.cur_pic && pic < static_cast<int>(g.pic_wave.size())) g.pic_wave[s.cur_pic] = std::max(g.pic_wave[s.cur_pic], g.pic_wave[pic] + 1);
+            wave_after(g, s.dpb, s.cur_pic, best);
         }
     }
     if (s.pending_drops) { // slices without a readable header in front of this picture's first good one: lost slices of it, if it can be concealed
@@ -1522,19 +1058,15 @@ static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const
 static int conceal_frame_num_gap(h264mi_decoder *d, int si, const h264mi_sps &sps, const h264mi_pps &pps, uint32_t pps_id, const h264mi_slice_header &sh) {
     StreamState &s = d->st[si];
     Stage &g = d->stage[d->prep];
-    if (sh.nal_unit_type == 5 || sps.gaps_in_frame_num_value_allowed) return 1;
-    const int max_fn = 1 << (sps.log2_max_frame_num_minus4 + 4), first = (s.prev_ref_frame_num + 1) % max_fn;
-    if (sh.frame_num == s.prev_ref_frame_num || sh.frame_num == first) return 1;
-    const int m = (sh.frame_num - first + max_fn) % max_fn;
-    if (m > H264MI_CONCEAL_MAX_GAP) return 1;
-    const int ref0 = initial_p_entry0(s, -1, first, max_fn);
-    if (ref0 < 0 || s.slots[ref0].nonexisting) return 1;
+    const int m = s.dpb.missing_frames(sps, sh);
+    if (!m || sps.gaps_in_frame_num_value_allowed || m > H264MI_CONCEAL_MAX_GAP) return 1;
+    const int max_fn = 1 << (sps.log2_max_frame_num_minus4 + 4), first = (s.dpb.prev_ref_frame_num + 1) % max_fn;
+    const int ref0 = s.dpb.initial_p_entry0(sps, first, 0);
+    if (ref0 < 0 || s.dpb.slots[ref0].nonexisting) return 1;
     // the m pictures and the revealing one must fit into what the batch has left (a slot taken by a picture of this batch stays taken until the next
     // prepare, so counting the free ones now is exact)
     const uint64_t frame_mbs = static_cast<uint64_t>(sps.pic_width_in_mbs) * sps.pic_height_in_mbs;
-    int free_slots = 0;
-    for (const Slot &sl : s.slots) free_slots += !sl.ref && !sl.held;
-    if (s.n_pics_in_batch + m + 1 > d->cfg.max_frames_per_batch || g.n_pics + m + 1 > d->pics_cap || free_slots < m + 1) return 1;
+    if (s.n_pics_in_batch + m + 1 > d->cfg.max_frames_per_batch || g.n_pics + m + 1 > d->pics_cap || s.dpb.free_slots() < m + 1) return 1;
     if (g.mb_used + frame_mbs * m + (sh.field_pic ? frame_mbs / 2 : frame_mbs) > d->mb_cap) return 1;
     if (pps.num_slice_groups_minus1 > 0) { // every picture's slice group map goes into the staging buffer (start_picture)
         size_t cursor = g.map_cursor;
@@ -1552,13 +1084,13 @@ static int conceal_frame_num_gap(h264mi_decoder *d, int si, const h264mi_sps &sp
         memset(&f, 0, sizeof(f));
         f.pps_id = static_cast<int32_t>(pps_id), f.frame_num = (first + k) % max_fn, f.nal_ref_idc = 1, f.nal_unit_type = 1;
         f.slice_group_change_cycle = sh.slice_group_change_cycle;
-        if (sps.pic_order_count_type == 0) f.pic_order_cnt_lsb = (s.prev_poc_lsb + 2) % (1 << (sps.log2_max_pic_order_cnt_lsb_min4 + 4));
+        if (sps.pic_order_count_type == 0) f.pic_order_cnt_lsb = (s.dpb.prev_poc_lsb + 2) % (1 << (sps.log2_max_pic_order_cnt_lsb_min4 + 4));
         f.num_ref_idx_active_override = 1;
         f.slice_qp_y = 26 + pps.pic_init_qp_minus26;
         int r = start_picture(d, si, sps, pps, pps_id, f, 1, false);
         if (r != H264MI_OK) return r;
         if (g.h_pics[s.cur_pic].conceal_ref < 0) { // (cannot happen: entry 0 was looked up above, and from then on it is the picture inserted before)
-            set_error("stream %d: frame_num %d after %d: reference pictures are missing", si, sh.frame_num, s.prev_ref_frame_num);
+            set_error("stream %d: frame_num %d after %d: reference pictures are missing", si, sh.frame_num, s.dpb.prev_ref_frame_num);
             return H264MI_EBITSTREAM;
         }
         finish_picture(d, si);
@@ -1600,7 +1132,7 @@ static int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref
         // known: it is taken for a slice of the picture under construction, or, if there is none or that one is an IDR picture (whose slices are
         // NAL units of type 5, and only type 1 is tolerated), of the picture the next slice starts (decided there).
         if (d->conceal && type == 1 && !s.need_idr && (r == H264MI_EBITSTREAM || r == H264MI_EINVAL)) {
-            if (s.cur_slot < 0 || s.first_sh.nal_unit_type == 5) {
+            if (s.dpb.cur_slot < 0 || s.dpb.first_sh.nal_unit_type == 5) {
                 s.pending_drops++, s.pending_drop_err = r;
                 return H264MI_OK;
             }
@@ -1667,7 +1199,7 @@ static int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref
     // started begins a new picture whatever the headers say.  Not "first_mb_in_slice == 0": with slice groups or arbitrary slice
     // order that slice may come late.)
     const bool restarts = std::find(s.cur_first_mbs.begin(), s.cur_first_mbs.end(), sh.first_mb_in_slice) != s.cur_first_mbs.end();
-    if (s.cur_slot >= 0 && (restarts || new_picture(sps, s.first_sh, sh))) finish_picture(d, si);
+    if (s.dpb.cur_slot >= 0 && (restarts || new_picture(sps, s.dpb.first_sh, sh))) finish_picture(d, si);
     if (s.active_sps != pps.sps_id || s.wmb != wmb || s.hmb != hmb) { // (re)activate: new sequence geometry
         if (sh.nal_unit_type != 5 && s.active_sps >= 0 && (s.wmb != wmb || s.hmb != hmb)) {
             set_error("stream %d: picture size changes without an IDR", si);
@@ -1676,12 +1208,12 @@ static int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref
         flush_pending_field(d, si); // (a lone first field of the old sequence goes out before anything of the new one)
         s.active_sps = pps.sps_id, s.wmb = wmb, s.hmb = hmb;
     }
-    if (s.cur_slot < 0) { // first slice of a new picture
+    if (s.dpb.cur_slot < 0) { // first slice of a new picture
         // the second field of the frame whose first field was the previous picture (7.4.1.2.4, 3.30 / 3.31): opposite parity, same frame_num, not
         // an IDR picture, reference or not like the first one
         bool second = false;
-        if (s.pend_slot >= 0) {
-            const Slot &f = s.slots[s.pend_slot];
+        if (s.dpb.pend_slot >= 0) {
+            const Slot &f = s.dpb.slots[s.dpb.pend_slot];
             if (sh.field_pic && type != 5 && f.fields == (sh.bottom_field ? 1 : 2) && f.frame_num == sh.frame_num && (f.ref != 0) == (ref_idc != 0))
                 second = true;
             else
@@ -1726,21 +1258,11 @@ static int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref
         const bool explicit_wp = bslice ? pps.weighted_bipred == 1 : pps.weighted_pred != 0;
         BSliceExt bx;
         memset(&bx, 0, sizeof(bx));
-        r = build_ref_lists(s, sps, sh, bslice, sd.ref_slot, bx.ref_slot1);
+        r = s.dpb.build_ref_lists(sps, sh, bslice, sd.ref_slot, bx.ref_slot1);
         if (r != H264MI_OK) return r;
-        { // the pictures of this batch the slice predicts from have to be reconstructed (deblocked) first: Stage::pic_wave
-            int wave = g.pic_wave[s.cur_pic];
-            auto after = [&](int entry) {
-                if (entry < 0) return;
-                const Slot &rs = s.slots[sh.field_pic ? MI_REF_SLOT(entry) : entry];
-                for (int pic : {rs.pic, rs.fpic[0], rs.fpic[1]}) // (a frame, or either field: whichever of them this batch decodes)
-                    if (pic >= 0 && pic != s.cur_pic && pic < static_cast<int>(g.pic_wave.size())) wave = std::max(wave, g.pic_wave[pic] + 1);
-            };
-            for (int i = 0; i <= sh.num_ref_idx_l0_active_minus1 && i < MI_MAX_REFS; i++) after(sd.ref_slot[i]);
-            if (bslice)
-                for (int i = 0; i <= sh.num_ref_idx_l1_active_minus1 && i < MI_MAX_REFS; i++) after(bx.ref_slot1[i]);
-            g.pic_wave[s.cur_pic] = wave;
-        }
+        for (int i = 0; i <= sh.num_ref_idx_l0_active_minus1 && i < MI_MAX_REFS; i++) wave_after(g, s.dpb, s.cur_pic, sd.ref_slot[i]);
+        if (bslice)
+            for (int i = 0; i <= sh.num_ref_idx_l1_active_minus1 && i < MI_MAX_REFS; i++) wave_after(g, s.dpb, s.cur_pic, bx.ref_slot1[i]);
         sd.wp_flag = static_cast<uint8_t>(explicit_wp);
         sd.luma_log2_denom = static_cast<uint8_t>(sh.luma_log2_weight_denom), sd.chroma_log2_denom = static_cast<uint8_t>(sh.chroma_log2_weight_denom);
         for (int i = 0; i < MI_MAX_REFS; i++) {
@@ -1754,8 +1276,9 @@ static int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref
             pd.has_b = 1;
             // PicOrderCnt of the current picture and of a list entry: a field's own count in a field picture (entries name fields), the frame's otherwise
             const bool fieldpic = sh.field_pic != 0;
-            const int cur_poc = fieldpic ? s.slots[s.cur_slot].fpoc[sh.bottom_field ? 1 : 0] : s.slots[s.cur_slot].poc;
-            auto entry_slot = [&](int e) -> const Slot & { return s.slots[fieldpic ? MI_REF_SLOT(e) : e]; };
+            const Slot &cur = s.dpb.slots[s.dpb.cur_slot];
+            const int cur_poc = fieldpic ? cur.fpoc[sh.bottom_field ? 1 : 0] : cur.poc;
+            auto entry_slot = [&](int e) -> const Slot & { return s.dpb.slots[fieldpic ? MI_REF_SLOT(e) : e]; };
             auto entry_poc = [&](int e) { return fieldpic ? entry_slot(e).fpoc[(e & MI_REF_PARITY) ? 1 : 0] : entry_slot(e).poc; };
             const int n0 = sh.num_ref_idx_l0_active_minus1 + 1, n1 = sh.num_ref_idx_l1_active_minus1 + 1;
             bx.num_ref_idx_l1_active = static_cast<uint8_t>(n1);
@@ -1864,7 +1387,7 @@ static int harvest_status(h264mi_decoder *d, Stage &g) {
                           field_cabac ? " -- a CABAC field picture: the context values of field-coded blocks are unpinned (h264mi_config.allow_unpinned_field_cabac)" : "");
             if (s.status == H264MI_OK || s.status_batch != &g) { // first failure of the stream in this batch
                 s.status = H264MI_EDECODE, s.status_batch = &g;
-                for (auto &sl : s.slots) sl.ref = 0;
+                s.dpb.drop_references();
                 s.need_idr = true;
             }
             result = H264MI_EDECODE;
@@ -1903,14 +1426,14 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
     memset(&g.info, 0, sizeof(g.info));
     for (size_t si = 0; si < d->st.size(); si++) {
         StreamState &s = d->st[si];
-        for (auto &sl : s.slots) sl.held = sl.ref != 0, sl.pic = sl.fpic[0] = sl.fpic[1] = -1; // reference pictures at batch start stay put for the whole batch
-        if (s.pend_slot >= 0) s.slots[s.pend_slot].held = true, s.pend_out.pic = -1; // a first field waiting for its second one (decoded by an earlier batch now)
+        s.dpb.begin_batch(); // reference pictures at batch start, and a first field waiting for its second one, stay put for the whole batch
+        if (s.dpb.pend_slot >= 0) s.pend_out.pic = -1; // (that field was decoded by an earlier batch now)
         // the frames of the batch prepared before this one stay readable (and, if it is still executing, writable)
         if (MI_STAGES > 1)
-            for (const OutFrame &o : d->stage[prev_stage].out[si]) s.slots[o.slot].held = true;
+            for (const OutFrame &o : d->stage[prev_stage].out[si]) s.dpb.slots[o.slot].held = true;
         g.out[si].clear();
         s.n_pics_in_batch = 0;
-        s.cur_slot = s.cur_pic = -1;
+        s.cur_pic = -1;
         s.status = H264MI_OK;
     }
     // ---- pass 1 (parallel over streams): Annex-B scan ----
@@ -1993,7 +1516,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
                 h264mi_sps sps;
                 r = parse_sps(tmp.data(), rl, &sps);
                 if (r == H264MI_OK) {
-                    if (s.cur_slot >= 0) finish_picture(d, si);
+                    if (s.dpb.cur_slot >= 0) finish_picture(d, si);
                     s.sps[sps.id] = sps, s.sps_ok[sps.id] = true;
                 }
                 break;
@@ -2014,7 +1537,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
                 size_t n_ids = 0;
                 r = parse_pps_ids(&s.sps[sid], tmp.data(), rl, &pps, ids.data(), ids.size(), &n_ids);
                 if (r == H264MI_OK) {
-                    if (s.cur_slot >= 0) finish_picture(d, si);
+                    if (s.dpb.cur_slot >= 0) finish_picture(d, si);
                     s.pps[pps.id] = pps, s.pps_ok[pps.id] = true;
                     ids.resize(n_ids);
                     s.sg_ids[pps.id] = std::move(ids);
@@ -2030,7 +1553,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
             case 9:
             case 10:
             case 11:
-                if (s.cur_slot >= 0) finish_picture(d, si);
+                if (s.dpb.cur_slot >= 0) finish_picture(d, si);
                 if (nal.type != 9) flush_pending_field(d, si); // end of sequence / end of stream: no second field will follow a lone first one
                 break;
             case 2:
@@ -2058,14 +1581,14 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
             if (!d->isolate) return r;
             continue;
         }
-        if (s.cur_slot >= 0) finish_picture(d, si);
+        if (s.dpb.cur_slot >= 0) finish_picture(d, si);
     }
     // A reference picture that outlives the batch may become the co-located picture of a B picture of a later batch: its
     // motion is kept too (8.4.1.2.1).
     g.pic_level.resize(g.n_pics, 0), g.pic_save_col.resize(g.n_pics, 0), g.pic_wave.resize(g.n_pics, 0), g.slice_level.resize(g.n_slices, 0);
     g.pic_init_qp.resize(g.n_pics, 26), g.pic_dropped.resize(g.n_pics, 0);
     for (int si = 0; si < n_streams; si++)
-        for (const Slot &sl : d->st[si].slots)
+        for (const Slot &sl : d->st[si].dpb.slots)
             if (sl.ref)
                 for (int pic : {sl.pic, sl.fpic[0], sl.fpic[1]})
                     if (pic >= 0 && pic < g.n_pics) g.pic_save_col[pic] = 1;
@@ -2156,7 +1679,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
                 pd.col_out = d->d_colrec ? reinterpret_cast<uint64_t>(d->d_colrec + (static_cast<size_t>(pd.stream) * d->n_slots + pd.slot) * d->colrec_per_slot +
                                                                       (par ? d->colrec_per_slot / 2 : 0))
                                          : 0;
-                if (pd.save_col) d->st[pd.stream].slots[pd.slot].col_valid[par] = true; // (the slot is this picture's until the next prepare at least: held)
+                if (pd.save_col) d->st[pd.stream].dpb.slots[pd.slot].col_valid[par] = true; // (the slot is this picture's until the next prepare at least: held)
                 g.colsave_n[l] += pd.save_col;
             }
         g.prep_n[l] = pos - g.prep_off[l];
@@ -2771,6 +2294,60 @@ extern "C" int32_t h264mi_internal_set_epoch(h264mi_decoder *d, uint32_t v) {
     // the device-side ticket counters stand where the host's bases do
     HIP_TRY(hipMemcpy(d->d_xctl, &d->x_tk5, sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d->d_xctl + 32, &d->x_tk3, sizeof(uint32_t), hipMemcpyHostToDevice));
+    return H264MI_OK;
+}
+
+// Not part of the public ABI: what picture management (8.2) made of the batch prepared last, for one stream, as text -- its pictures, slices
+// (reference lists as raw entries, parity bit included) and output frames, then the frame slots that are references or held and the stream's
+// POC / frame_num history (tools/host_dpb_trace.cpp; tests/test_host_dpb_trace.py pins the text).  Reads plain data only: it calls nothing of
+// picture management, so a change of that code cannot change what it prints about the same state.  `len`: bytes the whole text needs (without
+// the terminating 0); H264MI_ECAPACITY if that is more than cap - 1.
+extern "C" int32_t h264mi_internal_dpb_trace(h264mi_decoder *d, int32_t stream, char *buf, size_t cap, size_t *len) {
+    if (!d || !buf || !len || !cap || stream < 0 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    const Stage &g = d->stage[d->prep];
+    const StreamState &s = d->st[stream];
+    size_t n = 0;
+    auto put = [&](const char *fmt, auto... args) {
+        const int k = snprintf(n < cap ? buf + n : nullptr, n < cap ? cap - n : 0, fmt, args...);
+        if (k > 0) n += static_cast<size_t>(k);
+    };
+    auto put_list = [&](const char *name, const int16_t *v, int count) {
+        put(" %s=", name);
+        for (int i = 0; i < count && i < MI_MAX_REFS; i++) put(i ? ",%d" : "%d", v[i]);
+    };
+    for (int p = 0; p < g.n_pics; p++) {
+        const PicDesc &pd = g.h_pics[p];
+        if (static_cast<int>(pd.stream) != stream) continue;
+        const Slot &sl = s.dpb.slots[pd.slot];
+        put("pic %d slot=%u field=%d poc=%d fpoc=%d,%d frame_num=%d wave=%d level=%d conceal_ref=%d n_slices=%u dropped=%d\n", p, pd.slot, pd.field, sl.poc, sl.fpoc[0], sl.fpoc[1],
+            sl.frame_num, g.pic_wave[p], g.pic_level[p], pd.conceal_ref, pd.n_slices, g.pic_dropped[p]);
+    }
+    for (int i = 0; i < g.n_slices; i++) {
+        const SliceDesc &sd = g.h_slices[i];
+        if (static_cast<int>(g.h_pics[sd.pic_idx].stream) != stream) continue;
+        put("slice pic=%u first_mb=%u type=%d fill_from=%u end_mb=%u", sd.pic_idx, sd.first_mb, sd.slice_type, sd.fill_from, sd.end_mb);
+        put_list("l0", sd.ref_slot, sd.num_ref_idx_active);
+        if (sd.slice_type == 1) {
+            const BSliceExt &bx = g.h_bext[sd.bext];
+            put_list("l1", bx.ref_slot1, bx.num_ref_idx_l1_active);
+            put_list("dist_scale", bx.dist_scale, sd.num_ref_idx_active);
+            put(" col_short=%d", bx.col_short);
+        }
+        put("%s", "\n");
+    }
+    for (const OutFrame &o : g.out[stream])
+        put("out slot=%d wmb=%d hmb=%d crop=%d,%d size=%dx%d poc=%d frame_num=%d nal_ref_idc=%d idr=%d pic=%d new_sequence=%d pic2=%d\n", o.slot, o.wmb, o.hmb, o.crop_x, o.crop_y,
+            o.width, o.height, o.poc, o.frame_num, o.nal_ref_idc, o.idr, o.pic, o.new_sequence, o.pic2);
+    for (size_t i = 0; i < s.dpb.slots.size(); i++) {
+        const Slot &sl = s.dpb.slots[i];
+        if (sl.ref || sl.held)
+            put("slot %zu ref=%d long_idx=%d frame_num=%d fields=%d funref=%d nonexisting=%d field_coded=%d poc=%d held=%d\n", i, sl.ref, sl.long_idx, sl.frame_num, sl.fields,
+                sl.funref, sl.nonexisting, sl.field_coded, sl.poc, sl.held);
+    }
+    put("state prev_ref_frame_num=%d prev_poc_msb=%d prev_poc_lsb=%d prev_frame_num=%d prev_frame_num_offset=%d pend_slot=%d need_idr=%d\n", s.dpb.prev_ref_frame_num, s.dpb.prev_poc_msb,
+        s.dpb.prev_poc_lsb, s.dpb.prev_frame_num, s.dpb.prev_frame_num_offset, s.dpb.pend_slot, s.need_idr);
+    *len = n;
+    if (n >= cap) return H264MI_ECAPACITY;
     return H264MI_OK;
 }
 #endif /* H264MI_TEST_HOOKS */

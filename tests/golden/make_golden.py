@@ -53,3 +53,16 @@ for name in sorted(POC_MATRIX):
                  "pocs": [int(x) for x in streamgen.last_pocs()]}
 json.dump(out, open(os.path.join(HERE, "poc_md5.json"), "w"), indent=1, sort_keys=True)
 print("wrote", len(out), "POC vectors")
+
+# the characterisation trace of the product's picture management (tests/dpbtrace.py; CPU, null device): MD5 of the trace text of every case.  It
+# pins what the code DOES, so it is written once and not again for a change that is meant to keep behaviour.  Only with --dpb-trace.
+if "--dpb-trace" in sys.argv[1:]:
+    import tempfile
+
+    import dpbtrace  # noqa: E402
+    streamgen.build()
+    with tempfile.TemporaryDirectory() as tmp:
+        prog = dpbtrace.build(tmp)
+        out = {name: hashlib.md5(dpbtrace.trace(prog, tmp, *case).encode()).hexdigest() for name, case in dpbtrace.cases(streamgen).items()}
+    json.dump(out, open(os.path.join(HERE, "dpb_trace_md5.json"), "w"), indent=1, sort_keys=True)
+    print("wrote", len(out), "picture management traces")

@@ -8,6 +8,7 @@ import pytest
 
 import concealutil as cu
 import concealutil2 as c2
+import hostprog
 from concealutil2 import FIELD_CASES
 from conftest import pictures_of
 
@@ -76,14 +77,10 @@ def test_second_field_of_the_idr_frame_is_copied_from_its_first_field(sg, oracle
 @pytest.fixture(scope="module")
 def host_pocs(tmp_path_factory):
     import shutil
-    import subprocess
     if not shutil.which("g++"):
         pytest.skip("g++ not available")
     tmp = tmp_path_factory.mktemp("host_pocs_fields")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run(["bash", os.path.join(root, "tools", "host_pocs.sh")], env=dict(os.environ, TMPDIR=str(tmp)), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stdout.strip().splitlines()[-1], tmp
+    return hostprog.build("host_pocs.sh", tmp), tmp
 
 
 @pytest.mark.parametrize("name", sorted(FIELD_CASES))

@@ -12,6 +12,7 @@ import pytest
 
 import concealutil as cu
 import concealutil2 as c2
+import hostprog
 from concealutil2 import CASES, MATRIX_CASES
 from conftest import FULL_MATRIX, pictures_of
 
@@ -66,9 +67,7 @@ def host_pocs(tmp_path_factory):
     if not shutil.which("g++"):
         pytest.skip("g++ not available")
     tmp = tmp_path_factory.mktemp("host_pocs_conceal")
-    r = subprocess.run(["bash", os.path.join(ROOT, "tools", "host_pocs.sh")], env=dict(os.environ, TMPDIR=str(tmp)), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stdout.strip().splitlines()[-1], tmp
+    return hostprog.build("host_pocs.sh", tmp), tmp
 
 
 def _host(prog, tmp, stream, kw, conceal, frames=None):

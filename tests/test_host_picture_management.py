@@ -1,4 +1,4 @@
-"""The product's picture management on the CPU: mi_api.cpp + mi_parse.cpp built against the null device of tools/hoststub (kernels are
+"""The product's picture management on the CPU: mi_dpb.cpp with mi_api.cpp + mi_parse.cpp around it, built against the null device of tools/hoststub (kernels are
 not run) prepare every matrix stream, and the PicOrderCnt / frame_num / IDR flag they report per picture (h264mi_frame_get_info) must
 be the generator's -- 8.2.1 for all three pic_order_cnt_types, memory management operation 5, frame_num gaps, B pictures in coding
 order, non-reference pictures, and a bottom field that is not at the top field's count (POC_MATRIX).  The oracle is held to the same
@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import hostprog
 from conftest import FULL_MATRIX, MATRIX, POC_MATRIX, pictures_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,9 +20,7 @@ pytestmark = pytest.mark.skipif(not shutil.which("g++"), reason="g++ not availab
 @pytest.fixture(scope="module")
 def host_pocs(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("host_pocs")
-    r = subprocess.run(["bash", os.path.join(ROOT, "tools", "host_pocs.sh")], env=dict(os.environ, TMPDIR=str(tmp)), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stdout.strip().splitlines()[-1], tmp
+    return hostprog.build("host_pocs.sh", tmp), tmp
 
 
 def _host(prog, tmp, stream, kw):
