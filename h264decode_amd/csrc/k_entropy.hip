@@ -46,12 +46,30 @@
 #ifndef MI_ENT_FMO
 #define MI_ENT_FMO MI_ENT_B
 #endif
+// Fourth build (k_entropy_c.hip: MI_ENT_CABAC = 1): the I/P kernel for launches whose slices are all CABAC-coded (Main / High) -- the
+// entropy coding mode is the constant "CABAC" instead of PicDesc::cabac.  The CAVLC parser is not compiled at all (IF_CAVLC), its tables
+// leave Shared, and the dozen uniform `if (cabac)` of a macroblock fold; what that frees in scalar registers is what the bit reader and the
+// arithmetic decoder otherwise spill into VGPR lanes.  Unset: the mode is read per slice, as the general kernel must.  (Independent of
+// MI_ENT_B / MI_ENT_FMO, so that the B build can be given a CABAC-only twin the same way.)
+#ifndef MI_ENT_CABAC
+#define MI_ENT_CABAC 0
+#endif
+#if MI_ENT_CABAC
+#define ENT_CABAC(e) 1
+#define IF_CAVLC(x) 0 /* a CAVLC-only expression: not even instantiated in the CABAC build (always the dead arm of an ENT_CABAC test) */
+#else
+#define ENT_CABAC(e) ((e).cabac)
+#define IF_CAVLC(x) (x)
+#endif
 #if MI_ENT_B
 #define NL 2
 #define MI_ENT_KERNEL k_entropy_b
 #elif MI_ENT_FMO
 #define NL 1
 #define MI_ENT_KERNEL k_entropy_f
+#elif MI_ENT_CABAC
+#define NL 1
+#define MI_ENT_KERNEL k_entropy_c
 #else
 #define NL 1
 #define MI_ENT_KERNEL k_entropy
@@ -88,7 +106,9 @@ static_assert(sizeof(TopInfo) == (MI_ENT_B ? 72 : 48), "TopInfo layout");
 
 struct Shared {
     uint8_t ctx[464];      // home of the residual-block context states (ctxIdx >= 105); see Ent::wk
+#if !MI_ENT_CABAC
     uint8_t posmap[4][64]; // CAVLC: scan index -> position: [0] zig-zag 4x4, [1] zig-zag 4x4 of AC index (k+1), [2] zig-zag 8x8, [3] identity
+#endif
     int16_t coef[MI_COEF_PER_MB];
     MbRec rec;
     // The neighbour entries as ONE array, so that a lane picks its neighbour by index (an LDS offset) and not by a select of
@@ -112,7 +132,9 @@ struct Shared {
     int16_t ref_slot[NL][MI_MAX_REFS]; // frame-pool slot per ref_idx of this slice
     uint32_t skip_tmpl[32];            // the MbRec of a P_Skip macroblock as far as it is the same for the whole slice (pskip_fast)
     uint32_t role[64];                 // what each lane does in fill_caches (build_role)
+#if !MI_ENT_CABAC
     uint16_t vlc[MI_VLC_N];            // CAVLC slices: the code tables in compact form (mi_types.h: MI_VLC_*), copied in at the start of the slice
+#endif
     uint8_t coded[64];                 // CABAC neighbourhood, one entry per bit position of parse_residual_cabac's layout: 1 coded, 2 unavailable (fill_caches)
 #if MI_ENT_B
     uint32_t col[20];          // ColRec of the co-located macroblock (8.4.1.2.1)
@@ -244,6 +266,8 @@ FI uint32_t cat_word1(int c, int field) {
     return (field ? sigf[c] : sig[c]) | (field ? lastf[c] : last[c]) << 10 | ab[c] << 20;
 }
 
+// (the `@region` lines name the source regions of tools/ent_spills.py: a region runs to the next such line)
+// @region bit reader
 // ------------------------------------------------------------------ bit reader
 FI uint32_t load_win(const Ent &e, uint32_t base) {
     const uint32_t i = base + LANE;
@@ -314,6 +338,7 @@ FI int get_se(Ent &e) {
     return (k & 1) ? m : -m;
 }
 
+// @region CABAC engine
 // ------------------------------------------------------------------ CABAC engine (9.3.1.2, 9.3.3.2)
 // codIOffset is kept scaled: value = (codIOffset << avail) | next `avail` stream bits, and so is codIRange: range = codIRange << avail.
 //
@@ -468,6 +493,7 @@ FI int cabac_egk(Ent &e, int k) {
     return v;
 }
 
+// @region other
 FI void set_qp(Ent &e, int qp) { // QP_Y and the two chroma QPs it maps to (8.5.8: Table 8-15 on qP_I = Clip3(0, 51, QP_Y + chroma_qp_index_offset))
     e.qp = qp;
     e.qpw0 = static_cast<uint32_t>(qp) << 16 | RDL(e.v_qpc, min(max(qp + e.cqp_off0, 0), 51)) << 24;
@@ -489,6 +515,7 @@ FI uint32_t top_load(const Ent &e, int col, int dw) {
     return col < e.wmb ? __hip_atomic_load(reinterpret_cast<const uint32_t *>(e.top + col) + dw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
 }
 
+// @region cabac_residual
 // ------------------------------------------------------------------ residual blocks
 // residual_block_cabac 7.3.5.3.3 for ctxBlockCat `cat`; coefficients are written de-zig-zagged.
 // The block's context states are gathered into e.wk (lanes 0..15 significant_coeff_flag, 16..31
@@ -591,6 +618,8 @@ FI int cabac_residual(Ent &e, int16_t *dst, int cat_, int cbf_inc) {
     return n;
 }
 
+// @region CAVLC
+#if !MI_ENT_CABAC
 // residual_block_cavlc 9.2.  kind: 0 = 16 coefficients, 1 = 15 (AC), 2 = chroma DC (4),
 // 3 = 16 coefficients that are every fourth one of an 8x8 block's scan (CAVLC + 8x8 transform interleave: scan index pmul * i + padd)
 FI int cavlc_residual(Ent &e, int16_t *dst, int kind, int nC, int pmul, int padd) {
@@ -708,6 +737,8 @@ FI int nc_of(uint8_t a, uint8_t b) { // 9.2.1
     if (av && bv) return (a + b + 1) >> 1;
     return av ? a : (bv ? b : 0);
 }
+#endif
+// @region parse_residual_cabac
 FI int cbf_inc_of(const Ent &e, uint8_t a, uint8_t b) { // 9.3.3.1.1.9
     int ci = MB_IS_INTRA(e.cur_type);
     int ca = (a & 0x80) ? ci : (a != 0), cb = (b & 0x80) ? ci : (b != 0);
@@ -791,6 +822,8 @@ FI void parse_residual_cabac(Ent &e, int cbp_luma, int cbp_chroma, int t8x8) {
     }
 }
 
+// @region CAVLC
+#if !MI_ENT_CABAC
 FI void parse_residual_cavlc(Ent &e, int cbp_luma, int cbp_chroma, int t8x8) {
     Shared *s = e.s;
     const int i16 = e.cur_type == MBT_I16x16;
@@ -866,7 +899,9 @@ FI void parse_residual_cavlc(Ent &e, int cbp_luma, int cbp_chroma, int t8x8) {
         if (g < 9 && gx >= 0 && gy >= 0) (&s->nnzc_c[0][0])[nl - 32] = static_cast<uint8_t>(vnn);
     }
 }
+#endif
 
+// @region vector prediction and caches
 FI int median3(int a, int b, int c) {
     int mn = a < b ? a : b, mx = a < b ? b : a;
     return c < mn ? mn : (c > mx ? mx : c);
@@ -1124,7 +1159,7 @@ FI void read_ref_idx(Ent &e, const int L, int bx, int by, int w, int h, int nref
     Shared *s = e.s;
     int ref = 0;
     if (nref > 1) {
-        if (e.cabac) {
+        if (ENT_CABAC(e)) {
             int ctx = (s->refi_c[L][GI(bx - 1, by)] > 0) + 2 * (s->refi_c[L][GI(bx, by - 1)] > 0);
             while (BIN_A(e, 54 + ctx)) {
                 ctx = (ctx >> 2) + 4;
@@ -1134,7 +1169,7 @@ FI void read_ref_idx(Ent &e, const int L, int bx, int by, int w, int h, int nref
                 }
             }
         } else
-            ref = nref == 2 ? !get_bit(e) : static_cast<int>(get_ue(e));
+            ref = IF_CAVLC(nref == 2 ? !get_bit(e) : static_cast<int>(get_ue(e)));
         if (ref >= nref || ref >= MI_MAX_REFS) e.err = 13, ref = 0;
     }
     { // one 4x4 block per lane: ref_idx cache for the ctxIdxInc of later partitions, and the per-8x8 list
@@ -1154,7 +1189,7 @@ FI void read_mv(Ent &e, const int L, int p) {
     int d[2];
     for (int comp = 0; comp < 2; comp++) {
         int v;
-        if (e.cabac) { // UEG3, uCoff 9, signed (9.3.2.3, 9.3.3.1.1.7)
+        if (ENT_CABAC(e)) { // UEG3, uCoff 9, signed (9.3.2.3, 9.3.3.1.1.7)
             const int sum = s->mvd_c[L][GI(bx - 1, by)][comp] + s->mvd_c[L][GI(bx, by - 1)][comp];
             const int base = comp ? 47 : 40;
             v = 0;
@@ -1169,7 +1204,7 @@ FI void read_mv(Ent &e, const int L, int p) {
                 if (cabac_bypass(e)) v = -v;
             }
         } else
-            v = get_se(e);
+            v = IF_CAVLC(get_se(e));
         d[comp] = v;
     }
     int px, py;
@@ -1177,6 +1212,7 @@ FI void read_mv(Ent &e, const int L, int p) {
     set_part(e, L, bx, by, w, h, ref, px + d[0], py + d[1], d[0], d[1]);
 }
 
+// @region pskip_fast
 // ------------------------------------------------------------------ P_Skip without the general machinery
 // A skipped macroblock of a P slice has no syntax: its vector comes from the neighbours A, B, C / D (8.4.1.1, 8.4.1.3 with refIdx 0), its
 // record and its edge entry are that vector sixteen / four times over next to constants.  Everything is taken straight from the four
@@ -1239,11 +1275,12 @@ FI void pskip_fast(Ent &e) {
 }
 #endif
 
+// @region decode_mb
 // ------------------------------------------------------------------ macroblock_layer() 7.3.5
 FI void decode_mb(Ent &e, int skipped) {
     Shared *s = e.s;
     MbRec &r = s->rec;
-    const int cabac = e.cabac, islice = e.islice;
+    const int cabac = ENT_CABAC(e), islice = e.islice;
     int cbp_luma = 0, cbp_chroma = 0, t8x8 = 0, i16mode = 0, chroma_mode = 0, has_coef = 0;
     int type, raw = 0, nparts = 0;
     const Nb a{e.aw}, b{e.bw};
@@ -1328,7 +1365,7 @@ FI void decode_mb(Ent &e, int skipped) {
                 raw = islice ? it : it + (MI_ENT_B ? 23 : 5);
             }
         } else
-            raw = static_cast<int>(get_ue(e));
+            raw = IF_CAVLC(static_cast<int>(get_ue(e)));
         const int it = islice ? raw : raw - (MI_ENT_B ? 23 : 5);
 #if MI_ENT_B
         if (raw < 23)
@@ -1416,7 +1453,7 @@ FI void decode_mb(Ent &e, int skipped) {
                                     }
                                 }
                             } else
-                                st = static_cast<int>(get_ue(e));
+                                st = IF_CAVLC(static_cast<int>(get_ue(e)));
                             if (st > 12) e.err = 21, st = 1;
                             s->sub_type[i] = static_cast<int8_t>(st);
                             const int md = b_sub_mode(st), shp = b_sub_shape(st);
@@ -1479,7 +1516,7 @@ FI void decode_mb(Ent &e, int skipped) {
                         if (cabac) // Table 9-38
                             st = BIN_A(e, 21) ? 0 : (!BIN_A(e, 22) ? 1 : (BIN_A(e, 23) ? 2 : 3));
                         else
-                            st = static_cast<int>(get_ue(e));
+                            st = IF_CAVLC(static_cast<int>(get_ue(e)));
                         if (st > 3) e.err = 21, st = 0;
                         s->sub_type[i] = static_cast<int8_t>(st);
                         const int bx = (i & 1) * 2, by = (i >> 1) * 2;
@@ -1505,7 +1542,7 @@ FI void decode_mb(Ent &e, int skipped) {
             } else {
                 // ---- intra: transform_size_8x8_flag, prediction modes, intra_chroma_pred_mode ----
                 if (type == MBT_I4x4 && e.t8x8_mode) {
-                    t8x8 = cabac ? BINI_T8(e, (a.ok() && a.t8x8()) + (b.ok() && b.t8x8())) : static_cast<int>(get_bit(e));
+                    t8x8 = cabac ? BINI_T8(e, (a.ok() && a.t8x8()) + (b.ok() && b.t8x8())) : IF_CAVLC(static_cast<int>(get_bit(e)));
                     if (t8x8) type = MBT_I8x8, e.cur_type = type;
                 }
                 if (type == MBT_I4x4 || type == MBT_I8x8) {
@@ -1525,8 +1562,8 @@ FI void decode_mb(Ent &e, int skipped) {
                                 for (int k = 0; k < 3; k++) rem |= BINI_B(e, 69) << k;
                                 mode = rem < pred ? rem : rem + 1;
                             }
-                        } else if (!get_bit(e)) {
-                            int rem = static_cast<int>(get_bits(e, 3));
+                        } else if (IF_CAVLC(!get_bit(e))) {
+                            int rem = IF_CAVLC(static_cast<int>(get_bits(e, 3)));
                             mode = rem < pred ? rem : rem + 1;
                         }
                         const int g = GI(bx, by), d = LANE - g;
@@ -1545,7 +1582,7 @@ FI void decode_mb(Ent &e, int skipped) {
                         while (chroma_mode < 3 && BIN_B(e, 67)) chroma_mode++;
                     }
                 } else {
-                    chroma_mode = static_cast<int>(get_ue(e));
+                    chroma_mode = IF_CAVLC(static_cast<int>(get_ue(e)));
                     if (chroma_mode > 3) e.err = 22, chroma_mode = 0;
                 }
                 if (LANE < 16) {
@@ -1573,10 +1610,10 @@ FI void decode_mb(Ent &e, int skipped) {
                         cbp |= (1 + BINI_B(e, 77 + 4 + ca + 2 * cb)) << 4;
                     }
                 } else {
-                    uint32_t k = get_ue(e);
+                    uint32_t k = IF_CAVLC(get_ue(e));
                     if (k > (e.mono ? 15u : 47u)) e.err = 23, k = 0;
                     if (e.mono) k += 48; // the ChromaArrayType 0 column of Table 9-4 (h264/bit_reader.go:118-135) sits behind the 48 entries of the other
-                    cbp = RFL(static_cast<int>(MB_IS_INTRA(type) ? e.tab->me_intra[k] : e.tab->me_inter[k]));
+                    cbp = IF_CAVLC(RFL(static_cast<int>(MB_IS_INTRA(type) ? e.tab->me_intra[k] : e.tab->me_inter[k])));
                 }
                 cbp_luma = cbp & 15, cbp_chroma = cbp >> 4;
                 if (cbp_luma && e.t8x8_mode && MB_IS_INTER(type)) {
@@ -1587,7 +1624,7 @@ FI void decode_mb(Ent &e, int skipped) {
                     if (type == MBT_P8x8)
                         for (int i = 0; i < 4; i++) all8 &= s->sub_type[i] == 0;
 #endif
-                    if (all8) t8x8 = cabac ? BINI_T8(e, (a.ok() && a.t8x8()) + (b.ok() && b.t8x8())) : static_cast<int>(get_bit(e));
+                    if (all8) t8x8 = cabac ? BINI_T8(e, (a.ok() && a.t8x8()) + (b.ok() && b.t8x8())) : IF_CAVLC(static_cast<int>(get_bit(e)));
                 }
             }
             // ---- mb_qp_delta + residual ----
@@ -1604,7 +1641,7 @@ FI void decode_mb(Ent &e, int skipped) {
                     }
                     dqp = (val & 1) ? (val + 1) >> 1 : -((val + 1) >> 1);
                 } else
-                    dqp = get_se(e);
+                    dqp = IF_CAVLC(get_se(e));
                 if (dqp < -26 || dqp > 25) e.err = 24, dqp = 0;
                 e.prev_dqp_nz = dqp != 0;
                 if (dqp) set_qp(e, (e.qp + dqp + 52) % 52);
@@ -1614,7 +1651,7 @@ FI void decode_mb(Ent &e, int skipped) {
                 if (cabac)
                     parse_residual_cabac(e, cbp_luma, cbp_chroma, t8x8);
                 else
-                    parse_residual_cavlc(e, cbp_luma, cbp_chroma, t8x8);
+                    IF_CAVLC((parse_residual_cavlc(e, cbp_luma, cbp_chroma, t8x8), 0));
                 MI_R(e, 3);
                 MI_T(e, 2);
                 has_coef = 1;
@@ -1767,6 +1804,7 @@ FI void fill_none(const Ent &e, int from, int to) {
     for (int a = from + (l >> 5); a < to; a += 2) reinterpret_cast<uint32_t *>(e.mbrec + e.mb_base + static_cast<uint64_t>(a))[l & 31] = 0u;
 }
 
+// @region kernel body
 // ------------------------------------------------------------------ kernel: slice_data() 7.3.4
 // grid = number of slices of the launch; `slice_base` = index of its first slice (the host orders the slices by launch)
 #if MI_ENT_B
@@ -1803,7 +1841,7 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
     e.pool_head = pool_head, e.pool_blocks = pool_blocks;
     e.coef_cur = e.coef_end = 0;
     e.err = 0;
-    e.cabac = RFL(static_cast<int>(pd->cabac));
+    e.cabac = MI_ENT_CABAC ? 1 : RFL(static_cast<int>(pd->cabac));
     e.islice = RFL(static_cast<int>(sd->slice_type == 2));
 #if MI_ENT_ISLICE_PRIO
     // the I slice of a GOP is the longest wavefront of the launch by far: let it win the instruction arbitration
@@ -1836,10 +1874,12 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
     e.v_step = step_word(l);
     e.aw = e.bw = 0;
     e.v_ipm = 0;
+#if !MI_ENT_CABAC
     sh.posmap[0][l] = scan4[l & 15];
     sh.posmap[1][l] = scan4[(l + 1) & 15];
     sh.posmap[2][l] = scan8[l];
     sh.posmap[3][l] = static_cast<uint8_t>(l);
+#endif
     if (l < MI_MAX_REFS) sh.ref_slot[0][l] = sd->ref_slot[l];
 #if MI_ENT_B
     {
@@ -1862,11 +1902,15 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
         e.wk_cat = -1, e.wk_c0 = 0, e.wk_home = 0, e.wk_valid = 0;
         for (int i = l; i < 464; i += 64) sh.ctx[i] = src[i];
     }
+#if !MI_ENT_CABAC
     if (!pd->cabac) // CAVLC: the code tables move into LDS (2.2 KB; a lookup in HBM-resident direct tables was most of a CAVLC slice's time)
         for (int i = l; i < MI_VLC_N / 2; i += 64) reinterpret_cast<uint32_t *>(sh.vlc)[i] = reinterpret_cast<const uint32_t *>(tab->vlc_c)[i];
+#endif
     if (l < 32) reinterpret_cast<uint32_t *>(&sh.rec)[l] = 0;
     LDS_SYNC();
+#if !MI_ENT_CABAC
     if (!pd->cabac) e.v_cat0 = l < 48 ? sh.vlc[MI_VLC_RUN + l] : 0u; // run_before for zerosLeft 1..6: 6 x 8 entries, read with v_readlane
+#endif
     if (l == 0) { // slice constants of every MbRec
         sh.rec.dbf_idc = sd->dbf_idc;
         sh.rec.alpha_off = sd->alpha_off, sh.rec.beta_off = sd->beta_off;
@@ -1889,13 +1933,15 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
     LDS_SYNC();
     {
         uint32_t pos = RFL(sd->data_bit_off);
-        if (e.cabac) pos = (pos + 7) & ~7u; // cabac_alignment_one_bit
+        if (ENT_CABAC(e)) pos = (pos + 7) & ~7u; // cabac_alignment_one_bit
         e.wbase = 0x80000000u; // force the window load
         seek(e, pos);
-        if (e.cabac) cabac_start(e);
+        if (ENT_CABAC(e)) cabac_start(e);
     }
     const int total = min(e.wmb * e.hmb, RFL(static_cast<int>(sd->end_mb))); // the next slice's territory is out of bounds
+#if !MI_ENT_CABAC
     const uint32_t stop_bit = RFL(sd->stop_bit);
+#endif
     int addr = RFL(static_cast<int>(sd->first_mb));
     // Slice groups (FMO, 8.2.2; h264/slice.go:134-158, :530-552): the picture's mbToSliceGroupMap follows the slices in the
     // bitstream buffer; the slice walks the macroblocks of its group (nextMbAddress), the host has zeroed all records.
@@ -1904,7 +1950,11 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
     bool consecutive = false; // FMO: the previous macroblock of the slice is (mbx - 1, mby)
     if (!fmo) fill_none(e, RFL(static_cast<int>(sd->fill_from)), min(addr, total)); // a gap in front of the first slice of the picture
     e.mbx = addr % e.wmb, e.mby = addr / e.wmb;
+#if MI_ENT_CABAC
+    int more = 1;
+#else
     int more = 1, skip_state = 0 /* 0: read mb_skip_run, 1: inside a run, 2: coded MB follows a run */, pending = 0;
+#endif
     int n_mbs = 0;
     while (more && !e.err) {
         if (addr >= total) {
@@ -1941,11 +1991,13 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
         e.aw = RFL(*reinterpret_cast<const uint32_t *>(&sh.nb[NB_LEFT])), e.bw = RFL(*reinterpret_cast<const uint32_t *>(&sh.nb[NB_TOP]));
         int skipped = 0;
         if (!e.islice) {
-            if (e.cabac) {
+            if (ENT_CABAC(e)) {
                 const Nb a{e.aw}, b{e.bw};
                 const int skip_type = MI_ENT_B ? MBT_BSKIP : MBT_PSKIP; // ctxIdxOffset 11 in P slices, 24 in B slices (Table 9-34)
                 skipped = BINI_A(e, (MI_ENT_B ? 24 : 11) + (a.ok() && a.type() != skip_type) + (b.ok() && b.type() != skip_type));
-            } else {
+            }
+#if !MI_ENT_CABAC
+            else {
                 if (skip_state == 0) {
                     pending = static_cast<int>(get_ue(e));
                     if (pending > total - addr) e.err = 31, pending = 0;
@@ -1956,6 +2008,7 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
                     pending--;
                 }
             }
+#endif
         }
 #if !MI_ENT_B
         if (skipped) {
@@ -1972,8 +2025,9 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
         MI_T(e, 3);
         if (e.err) break; // the record of this macroblock cannot be trusted: it is blanked with the rest of the range
         n_mbs++;
-        if (e.cabac)
+        if (ENT_CABAC(e))
             more = !cabac_terminate(e);
+#if !MI_ENT_CABAC
         else if (skipped) {
             if (pending == 0) {
                 more = bitpos(e) < stop_bit;
@@ -1983,6 +2037,7 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
             more = bitpos(e) < stop_bit;
             skip_state = 0;
         }
+#endif
         if (fmo) { // nextMbAddress (8-17): 64 candidates at a time
             const uint8_t *sgmap = bitstream + RFL(e.pd->sgmap_off);
             const int sgroup = RFL(static_cast<int>(sgmap[RFL(static_cast<int>(e.sd->first_mb))]));

@@ -235,6 +235,7 @@ struct Stage {
     std::vector<uint16_t> pic_dropped;       // error concealment: per picture, slice NAL units whose header did not parse and that were dropped as lost (add_slice)
     std::vector<int> pic_wave;               // reconstruction wave of the picture: 0 for a picture that reads no picture of this batch, else 1 + the latest wave among its references
     std::vector<int> level_first;            // first slice of each level in the sorted table (+ end marker)
+    int ent_kernel = MI_ENT_K_GENERAL;       // the I/P entropy kernel of level 0 (mi_entropy_kernel_choice), decided when the batch is prepared
     std::vector<uint32_t> colsave_n;            // per level: pictures whose ColRec array k_dbprep writes (what the cross-pass fence looks at)
     std::vector<uint32_t> prep_off, prep_n;     // per level: the pictures whose last slice is of that level (k_dbprep runs on them after the level), as a range of d_lists
     std::vector<uint32_t> wave_b_off, wave_b_n, wave_p_off, wave_p_n, wave_nb_off, wave_nb_n; // per wave: B pictures / inter non-B / non-B
@@ -1609,6 +1610,13 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
         g.level_first.assign(n_levels + 1, g.n_slices);
         for (int i = g.n_slices - 1; i >= 0; i--) g.level_first[g.slice_level[i]] = i;
         for (int l = n_levels - 1; l >= 0; l--) g.level_first[l] = std::min(g.level_first[l], g.level_first[l + 1]);
+        int n_mode[2] = {0, 0}; // level 0 by entropy coding mode: CAVLC, CABAC slices
+        for (int i = g.level_first[0]; i < g.level_first[1]; i++) n_mode[g.h_pics[g.h_slices[i].pic_idx].cabac != 0]++;
+        g.ent_kernel = mi_entropy_kernel_choice(n_mode[1], n_mode[0], !g.fmo_pics.empty());
+#if defined(H264MI_TEST_HOOKS) /* measurement: the general kernel for CABAC launches too, as before there was a CABAC-only build */
+        if (const char *e = getenv("H264MI_ENT_GENERIC"))
+            if (atoi(e) && g.ent_kernel == MI_ENT_K_CABAC) g.ent_kernel = MI_ENT_K_GENERAL;
+#endif
     }
     if (d->conceal) {
         // Error concealment.  Behind the slices of the batch one SliceDesc per picture -- what MbRec::slice_idx of a concealed macroblock names, so that
@@ -1778,7 +1786,7 @@ static int execute_stage(h264mi_decoder *d, int stage_idx, bool exclusive) {
     hipStream_t es = d->ent_stream[d->pass & 1];
     MbRec *mbrec = d->d_mbrec[set];
     int16_t *coef = d->d_coef[set];
-    // Entropy decoding, level by level (Stage::level_first): k_entropy for the I / P slices, k_entropy_b for each level of B
+    // Entropy decoding, level by level (Stage::level_first): k_entropy or one of its builds (Stage::ent_kernel) for the I / P slices, k_entropy_b for each level of B
     // slices, and after each level k_dbprep for the pictures complete with it (K5's parameters; the ColRec arrays later B slices ask for).
     // `done`: recorded after the last level's k_dbprep -- what the reconstruction kernels wait for.
     auto launch_entropy = [&](hipStream_t st, size_t lds_pad, bool fence_prev_pass, hipEvent_t done) {
@@ -1801,7 +1809,7 @@ static int execute_stage(h264mi_decoder *d, int stage_idx, bool exclusive) {
             if (lv > 0) fence();
             if (n > 0) {
                 if (lv == 0)
-                    hipLaunchKernelGGL(g.fmo_pics.empty() ? k_entropy : k_entropy_f, dim3(n), dim3(64), lds_pad, st, g.d_slices, g.d_pics, g.d_bits, d->d_tables, mbrec, coef, d->d_pool_head + set,
+                    hipLaunchKernelGGL(g.ent_kernel == MI_ENT_K_FMO ? k_entropy_f : (g.ent_kernel == MI_ENT_K_CABAC ? k_entropy_c : k_entropy), dim3(n), dim3(64), lds_pad, st, g.d_slices, g.d_pics, g.d_bits, d->d_tables, mbrec, coef, d->d_pool_head + set,
                                        pool_blocks, g.d_status, d->d_toprows[set], g.wmb_max, static_cast<uint32_t>(first));
                 else
                     hipLaunchKernelGGL(k_entropy_b, dim3(n), dim3(64), 0, st, g.d_slices, g.d_pics, g.d_bits, d->d_tables, mbrec, coef, d->d_pool_head + set,
@@ -2248,6 +2256,11 @@ extern "C" int32_t h264mi_internal_deblock_plan(int32_t wmb, int32_t hmb, int32_
     return H264MI_OK;
 }
 
+// Not part of the public ABI: which I/P entropy kernel a level 0 of n_cabac CABAC and n_cavlc CAVLC slices runs on (mi_entropy_kernel_choice):
+// 0 k_entropy, 1 k_entropy_f, 2 k_entropy_c.
+extern "C" int32_t h264mi_internal_entropy_kernel_choice(int32_t n_cabac, int32_t n_cavlc, int32_t slice_groups) {
+    return mi_entropy_kernel_choice(n_cabac, n_cavlc, slice_groups != 0);
+}
 
 // Not part of the public ABI: the phase clocks a -DMI_DB_STATS build of the banded deblocking kernels leaves (zero otherwise); reading clears them
 extern "C" int32_t h264mi_internal_deblock_phase_clocks(h264mi_decoder *d, uint32_t out[12]) {

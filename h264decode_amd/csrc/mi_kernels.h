@@ -9,6 +9,9 @@ extern "C" __global__ void k_entropy(const SliceDesc *slices, const PicDesc *pic
 // the same with the slice-group walk of 8.2.2 (k_entropy_f.hip): for launches that hold a picture with more than one slice group
 extern "C" __global__ void k_entropy_f(const SliceDesc *slices, const PicDesc *pics, const uint8_t *bitstream, const DevTables *tab, MbRec *mbrec, int16_t *coefs,
                                        uint32_t *pool_head, uint32_t pool_blocks, uint32_t *status, uint32_t *toprows, int wmb_max, uint32_t slice_base);
+// the same with the entropy coding mode fixed to CABAC (k_entropy_c.hip): for launches whose slices are all CABAC-coded
+extern "C" __global__ void k_entropy_c(const SliceDesc *slices, const PicDesc *pics, const uint8_t *bitstream, const DevTables *tab, MbRec *mbrec, int16_t *coefs,
+                                       uint32_t *pool_head, uint32_t pool_blocks, uint32_t *status, uint32_t *toprows, int wmb_max, uint32_t slice_base);
 // the same for B slices (k_entropy_b.hip): two reference lists, direct prediction from the ColRec array of RefPicList1[0]; toprows = 18 dwords per column
 extern "C" __global__ void k_entropy_b(const SliceDesc *slices, const PicDesc *pics, const uint8_t *bitstream, const DevTables *tab, MbRec *mbrec, int16_t *coefs,
                                        uint32_t *pool_head, uint32_t pool_blocks, uint32_t *status, uint32_t *toprows, int wmb_max, uint32_t slice_base,
@@ -115,6 +118,14 @@ static inline void mi_deblock8_plan(int wmb, int hmb, int *nwaves, int *ring, in
         }
     }
     *nwaves = 1, *ring = 1, *ring_last = w1, *last_bufs = 2; // 2 x 512 columns x 96 bytes + one wavefront always fit
+}
+// Which build of the I/P entropy kernel level 0 of a batch runs on: the slice-group build if a picture of the batch has slice groups (it reads the
+// mode per slice); else the CABAC-only build if every slice of the level is CABAC-coded; else -- one CAVLC slice is enough -- the general one.
+// (An empty level 0, a batch of B slices only, launches nothing: any id will do.)
+enum { MI_ENT_K_GENERAL = 0, MI_ENT_K_FMO = 1, MI_ENT_K_CABAC = 2 };
+static inline int mi_entropy_kernel_choice(int n_cabac, int n_cavlc, bool slice_groups) {
+    if (slice_groups) return MI_ENT_K_FMO;
+    return (n_cavlc == 0 && n_cabac > 0) ? MI_ENT_K_CABAC : MI_ENT_K_GENERAL;
 }
 // K6: crop + tight pack of a list of frames into I420; grid = (frames, ceil(2 * h_max / rows_per_block)), block = 256
 typedef struct {
