@@ -24,13 +24,16 @@ static int fail(const char *what, int code) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all]\n", argv[0]);
+        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr]\n", argv[0]);
         return 2;
     }
     int conceal = 0; /* --conceal (last argument): h264mi_config.conceal_errors */
     if (argc > 3 && !strcmp(argv[argc - 1], "--conceal")) conceal = H264MI_CONCEAL_SLICES, argc--;
     /* --conceal-all: wholly lost reference frames and slices of field pictures are concealed too */
     else if (argc > 3 && !strcmp(argv[argc - 1], "--conceal-all")) conceal = H264MI_CONCEAL_SLICES | H264MI_CONCEAL_PICTURES | H264MI_CONCEAL_FIELDS, argc--;
+    /* --conceal-idr: all of that, and slices of IDR frame pictures that still have a reference frame */
+    else if (argc > 3 && !strcmp(argv[argc - 1], "--conceal-idr"))
+        conceal = H264MI_CONCEAL_SLICES | H264MI_CONCEAL_PICTURES | H264MI_CONCEAL_FIELDS | H264MI_CONCEAL_IDR, argc--;
     const int per_batch = argc > 3 ? atoi(argv[3]) : 30;
     FILE *f = fopen(argv[1], "rb");
     if (!f) return fail("fopen", -1);

@@ -334,15 +334,16 @@ type Config struct {
 	MaxRefFrames, CoefBlocksPerMb                                                  int // 0 = defaults (16 reference slots per stream, 8 residual blocks per macroblock)
 	BPictures                                                                      int // 1 = the buffers only B pictures need exist from the start (h264mi_config.b_pictures)
 	AllowUnpinnedFieldCabac                                                        int // 1 = CABAC field pictures are decoded with the unpinned context tables (h264mi_config.allow_unpinned_field_cabac)
-	ConcealErrors                                                                  int // ConcealSlices = lost macroblocks of non-IDR frame pictures are copied from a reference picture; | ConcealPictures = wholly lost reference frames too; | ConcealFields = field pictures too (h264mi_config.conceal_errors)
+	ConcealErrors                                                                  int // ConcealSlices = lost macroblocks of non-IDR frame pictures are copied from a reference picture; | ConcealPictures = wholly lost reference frames too; | ConcealFields = field pictures too; | ConcealIDR = IDR frame pictures that still have a reference frame too (h264mi_config.conceal_errors)
 }
 
-// Bits of Config.ConcealErrors (H264MI_CONCEAL_*); ConcealPictures and ConcealFields only together with ConcealSlices.  ConcealMaxGap: the longest run of lost
+// Bits of Config.ConcealErrors (H264MI_CONCEAL_*); ConcealPictures, ConcealFields and ConcealIDR only together with ConcealSlices.  ConcealMaxGap: the longest run of lost
 // frames that is concealed -- MaxFramesPerBatch needs that much headroom over the pictures of a chunk.
 const (
 	ConcealSlices   = C.H264MI_CONCEAL_SLICES
 	ConcealPictures = C.H264MI_CONCEAL_PICTURES
 	ConcealFields   = C.H264MI_CONCEAL_FIELDS
+	ConcealIDR      = C.H264MI_CONCEAL_IDR
 	ConcealMaxGap   = C.H264MI_CONCEAL_MAX_GAP
 )
 type Decoder struct{ h *C.h264mi_decoder }

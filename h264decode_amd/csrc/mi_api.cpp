@@ -204,6 +204,15 @@ struct StreamState {
     // error concealment: slice NAL units with an unparsable header that arrived while no picture was under construction -- they belong to the picture
     // the next slice starts, and are tolerated only if that picture turns out to be concealable (add_slice); that slice may come with a later chunk
     int pending_drops = 0, pending_drop_err = H264MI_OK;
+    int pending_drop_type = 0; // ... their nal_unit_type (1 or 5; -1: both kinds): tolerated only in a picture of that kind (H264MI_CONCEAL_IDR)
+    // error concealment of IDR pictures (H264MI_CONCEAL_IDR): what of the SPS the stream's reference frames were decoded under must still hold for an
+    // IDR picture to predict from them -- picture size in macroblocks, chroma_format_idc, frame_mbs_only_flag, log2_max_frame_num_minus4 (start_picture)
+    struct RefSeq {
+        int wmb = -1, hmb = 0, chroma_format = 0, frame_mbs_only = 0, log2_max_frame_num_minus4 = 0;
+        bool operator==(const RefSeq &o) const {
+            return wmb == o.wmb && hmb == o.hmb && chroma_format == o.chroma_format && frame_mbs_only == o.frame_mbs_only && log2_max_frame_num_minus4 == o.log2_max_frame_num_minus4;
+        }
+    } ref_seq;
 };
 
 // Everything one prepared batch owns: the pinned staging buffers and their device mirrors, the descriptors, the launch
@@ -297,6 +306,7 @@ struct h264mi_decoder {
     bool conceal = false; // h264mi_config.conceal_errors: lost macroblocks of concealable pictures are copied from a reference picture (k_conceal)
     bool conceal_pics = false; // ... bit H264MI_CONCEAL_PICTURES: wholly lost reference frames are inserted as pictures without slices (conceal_frame_num_gap)
     bool conceal_fields = false; // ... bit H264MI_CONCEAL_FIELDS: field pictures are concealable too
+    bool conceal_idr = false; // ... bit H264MI_CONCEAL_IDR: IDR frame pictures that still have a reference frame are concealable too
     int64_t concealed_slices = 0, concealed_mbs = 0; // totals since create (h264mi_decoder_concealed)
     int64_t concealed_pics = 0;                      // (h264mi_decoder_concealed_pictures)
     bool isolate = false; // h264mi_decoder_set_isolation: a broken stream does not fail the batch
@@ -462,8 +472,10 @@ extern "C" int32_t h264mi_decoder_create(const h264mi_config *cfg_, h264mi_decod
     memcpy(&cfg_copy, cfg_, std::min<size_t>(cfg_->struct_size, sizeof(cfg_copy)));
     const h264mi_config *cfg = &cfg_copy;
     if (cfg->max_streams < 1 || cfg->max_width < 16 || cfg->max_height < 16 || cfg->max_frames_per_batch < 1) return H264MI_EINVAL;
-    if ((cfg->conceal_errors & ~(H264MI_CONCEAL_SLICES | H264MI_CONCEAL_PICTURES | H264MI_CONCEAL_FIELDS)) || (cfg->conceal_errors && !(cfg->conceal_errors & H264MI_CONCEAL_SLICES))) {
-        set_error("h264mi_decoder_create: h264mi_config.conceal_errors = %d (0, or H264MI_CONCEAL_SLICES with or without H264MI_CONCEAL_PICTURES and H264MI_CONCEAL_FIELDS)",
+    if ((cfg->conceal_errors & ~(H264MI_CONCEAL_SLICES | H264MI_CONCEAL_PICTURES | H264MI_CONCEAL_FIELDS | H264MI_CONCEAL_IDR)) ||
+        (cfg->conceal_errors && !(cfg->conceal_errors & H264MI_CONCEAL_SLICES))) {
+        set_error("h264mi_decoder_create: h264mi_config.conceal_errors = %d (0, or H264MI_CONCEAL_SLICES with or without H264MI_CONCEAL_PICTURES, H264MI_CONCEAL_FIELDS and "
+                  "H264MI_CONCEAL_IDR: 0, 1, 3, 5, 7, 17, 19, 21, 23)",
                   cfg->conceal_errors);
         return H264MI_EINVAL;
     }
@@ -472,7 +484,7 @@ extern "C" int32_t h264mi_decoder_create(const h264mi_config *cfg_, h264mi_decod
     h264mi_decoder *d = new h264mi_decoder();
     d->cfg = *cfg;
     d->conceal = (cfg->conceal_errors & H264MI_CONCEAL_SLICES) != 0, d->conceal_pics = (cfg->conceal_errors & H264MI_CONCEAL_PICTURES) != 0;
-    d->conceal_fields = (cfg->conceal_errors & H264MI_CONCEAL_FIELDS) != 0;
+    d->conceal_fields = (cfg->conceal_errors & H264MI_CONCEAL_FIELDS) != 0, d->conceal_idr = (cfg->conceal_errors & H264MI_CONCEAL_IDR) != 0;
     if (d->cfg.max_slices_per_frame < 1) d->cfg.max_slices_per_frame = 1;
     d->Wmax = (cfg->max_width + 15) & ~15;
     d->Hmax = (cfg->max_height + 15) & ~15;
@@ -689,6 +701,7 @@ static void reset_stream(StreamState &s, bool keep_parameter_sets) {
     s.cur_pic = -1, s.cur_slices = 0;
     s.n_pics_in_batch = 0;
     s.pending_drops = 0;
+    s.ref_seq = StreamState::RefSeq();
     if (!keep_parameter_sets) {
         memset(s.sps_ok, 0, sizeof(s.sps_ok));
         memset(s.pps_ok, 0, sizeof(s.pps_ok));
@@ -964,6 +977,19 @@ static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const
         set_error("macroblock record pool exhausted");
         return H264MI_ECAPACITY;
     }
+    // Error concealment of an IDR frame picture (H264MI_CONCEAL_IDR; the rule: include/h264mi.h): its concealment reference is entry 0 of the initial P
+    // list of a frame picture with frame_num (PrevRefFrameNum + 1) mod MaxFrameNum -- what the picture predicts from in the repaired stream, where it is
+    // a non-IDR picture that ends in memory management operation 5 --, looked up now: before the picture takes its slot and long before its marking
+    // drops the references (Dpb::finish_picture).  The slot named stays put for the batch: it is held, or a picture of this batch.  The references
+    // must have been decoded under an SPS this picture could still predict under (MaxFrameNum: the previous sequence's, which is then this one's).
+    StreamState::RefSeq seq;
+    seq.wmb = wmb, seq.hmb = hmb, seq.chroma_format = sps.chroma_format, seq.frame_mbs_only = sps.frame_mbs_only, seq.log2_max_frame_num_minus4 = sps.log2_max_frame_num_minus4;
+    int idr_ref = -1;
+    if (d->conceal_idr && type == 5 && !sh.field_pic && !second && seq == s.ref_seq) {
+        const int best = s.dpb.initial_p_entry0(sps, (s.dpb.prev_ref_frame_num + 1) % (1 << (sps.log2_max_frame_num_minus4 + 4)), 0);
+        if (best >= 0 && !s.dpb.slots[best].nonexisting) idr_ref = best;
+    }
+    s.ref_seq = seq;
     s.cur_pic = g.n_pics++;
     s.cur_slices = 0;
     s.cur_first_mbs.clear();
@@ -995,10 +1021,14 @@ static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const
             wave_after(g, s.dpb, s.cur_pic, best);
         }
     }
+    if (idr_ref >= 0) { // ... and like a non-IDR I picture that is concealable, the IDR picture is reconstructed behind its concealment reference, damaged or not
+        pd.conceal_ref = static_cast<int16_t>(idr_ref);
+        wave_after(g, s.dpb, s.cur_pic, idr_ref);
+    }
     if (s.pending_drops) { // slices without a readable header in front of this picture's first good one: lost slices of it, if it can be concealed
         const int n = s.pending_drops, e = s.pending_drop_err;
         s.pending_drops = 0;
-        if (pd.conceal_ref < 0) {
+        if (pd.conceal_ref < 0 || s.pending_drop_type != (type == 5 ? 5 : 1)) { // (a dropped unit of the other kind was no slice of this picture)
             set_error("stream %d: a slice header does not parse, in a picture that cannot be concealed", si);
             return e;
         }
@@ -1130,10 +1160,11 @@ static int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref
     if (r != H264MI_OK) {
         // error concealment: a damaged slice header is a lost slice -- its macroblocks stay undelivered and k_conceal fills them in -- but only in a
         // picture that is concealable; anywhere else it fails the stream as without the mode.  Which picture a slice without a header belongs to is not
-        // known: it is taken for a slice of the picture under construction, or, if there is none or that one is an IDR picture (whose slices are
-        // NAL units of type 5, and only type 1 is tolerated), of the picture the next slice starts (decided there).
-        if (d->conceal && type == 1 && !s.need_idr && (r == H264MI_EBITSTREAM || r == H264MI_EINVAL)) {
-            if (s.dpb.cur_slot < 0 || s.dpb.first_sh.nal_unit_type == 5) {
+        // known: it is taken for a slice of the picture under construction if that one is of its kind -- a unit of type 1: a non-IDR picture, a unit of
+        // type 5 (tolerated with H264MI_CONCEAL_IDR only): an IDR picture --, else, or if there is none, of the picture the next slice starts (decided there).
+        if (d->conceal && (type == 1 || (type == 5 && d->conceal_idr)) && !s.need_idr && (r == H264MI_EBITSTREAM || r == H264MI_EINVAL)) {
+            if (s.dpb.cur_slot < 0 || (s.dpb.first_sh.nal_unit_type == 5) != (type == 5)) {
+                s.pending_drop_type = s.pending_drops && s.pending_drop_type != type ? -1 : type;
                 s.pending_drops++, s.pending_drop_err = r;
                 return H264MI_OK;
             }

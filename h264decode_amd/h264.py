@@ -197,7 +197,8 @@ def read_nal_units(stream: bytes):
     return out
 
 
-CONCEAL_SLICES, CONCEAL_PICTURES, CONCEAL_FIELDS = 1, 2, 4  # bits of h264mi_config.conceal_errors (H264MI_CONCEAL_*): 2 and 4 only together with CONCEAL_SLICES
+CONCEAL_SLICES, CONCEAL_PICTURES, CONCEAL_FIELDS = 1, 2, 4  # bits of h264mi_config.conceal_errors (H264MI_CONCEAL_*): 2, 4 and 16 only together with CONCEAL_SLICES
+CONCEAL_IDR = 16                         # H264MI_CONCEAL_IDR (bit 8 is unassigned)
 CONCEAL_MAX_GAP = 16                     # H264MI_CONCEAL_MAX_GAP: the longest run of lost frames that is concealed
 
 
@@ -218,7 +219,8 @@ class Decoder:
         cfg.b_pictures = b_pictures  # 1: the B-only buffers exist from the start (default: from the first B slice on)
         cfg.allow_unpinned_field_cabac = allow_unpinned_field_cabac  # 1: CABAC field pictures are decoded with the unpinned context tables of field-coded blocks (default: refused)
         # True / CONCEAL_SLICES: lost macroblocks of non-IDR frame pictures are copied from a reference picture and the stream goes on (default: the
-        # stream waits for an IDR picture); | CONCEAL_PICTURES: wholly lost reference frames are inserted as copies too; | CONCEAL_FIELDS: field pictures too
+        # stream waits for an IDR picture); | CONCEAL_PICTURES: wholly lost reference frames are inserted as copies too; | CONCEAL_FIELDS: field pictures too;
+        # | CONCEAL_IDR: IDR frame pictures that still have a reference frame too (they are then reconstructed behind that frame when one batch holds both)
         cfg.conceal_errors = int(conceal_errors)
         cfg.device, cfg.max_streams, cfg.max_width, cfg.max_height = device, max_streams, max_width, max_height
         cfg.max_frames_per_batch, cfg.max_slices_per_frame, cfg.max_bitstream_bytes = max_frames_per_batch, max_slices_per_frame, max_bitstream_bytes

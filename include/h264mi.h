@@ -43,7 +43,7 @@ extern "C" {
 #define H264MI_EDEVICE (-6)     /* HIP runtime error */
 #define H264MI_ECAPACITY (-7)   /* caller buffer or decoder configuration too small */
 #define H264MI_EDECODE (-8)     /* a GPU entropy kernel reported a slice error.  With h264mi_config.conceal_errors a failed slice of a concealable picture
-                                 * (a non-IDR frame picture -- with H264MI_CONCEAL_FIELDS: or field picture -- that has a reference picture) is not an error: it is concealed and counted (h264mi_decoder_concealed) */
+                                 * (a non-IDR frame picture -- with H264MI_CONCEAL_FIELDS: or field picture; with H264MI_CONCEAL_IDR: or IDR frame picture -- that has a reference picture) is not an error: it is concealed and counted (h264mi_decoder_concealed) */
 
 /* ---- NAL unit: h264/nalUnit.go:3-30 (NalUnit), :75-131 (NewNalUnit) ---- */
 typedef struct {
@@ -213,8 +213,8 @@ typedef struct {
      * which those macroblocks are coded as P slices of P_Skip macroblocks (one active reference, slice_qp_delta 0, deblocking on, default weights).
      * The picture is kept and used as a reference, the stream's status stays H264MI_OK, nothing waits for an IDR picture.  The repair happens on the
      * device inside the pass, so pipelined callers get it for the batch prepared before the failure was known as well.  A slice NAL unit of
-     * type 1 whose header does not parse is dropped and counted as a lost slice of the picture under construction (of the next picture, if there is none
-     * or it is an IDR picture) when that picture is concealable; otherwise it fails the stream as with 0.
+     * type 1 whose header does not parse is dropped and counted as a lost slice of the non-IDR picture under construction (of the next picture, if there is
+     * none or it is an IDR picture) when that picture is concealable; otherwise it fails the stream as with 0.
      * The field is a bit set; 0 and 1 mean what they always meant.  H264MI_CONCEAL_PICTURES (2, together with bit 1: value 3) = wholly lost REFERENCE FRAMES
      * are concealed too.  They show as a gap in frame_num (the first slice of a picture that is not an IDR picture and not the second field of the frame
      * before it, in a stream with gaps_in_frame_num_value_allowed_flag 0, carries a frame_num that is neither PrevRefFrameNum nor its successor):
@@ -244,14 +244,38 @@ typedef struct {
      * delta_pic_order_cnt_bottom / delta_pic_order_cnt[1] are absent (7.3.3).  The tolerance for type-1 slices whose header does not parse extends to
      * such pictures.  CABAC field pictures still need allow_unpinned_field_cabac, and h264mi_decoder_unpinned_failures counts their failed slices
      * whether they are concealed or not.
-     * With every value: IDR pictures, a wholly missing field (its rows stay mid-grey), MBAFF (out of scope altogether), pictures without any reference
-     * picture and parameter-set errors are handled as with 0.  A value with bit 2 or 4 set and bit 1 clear, or with any bit above 4, is refused by
-     * h264mi_decoder_create (H264MI_EINVAL). */
+     * H264MI_CONCEAL_IDR (16, together with bit 1) = lost and damaged slices of IDR FRAME pictures are concealed too.  An IDR picture X (all its slices
+     * nal_unit_type 5, field_pic_flag 0) is concealable when the SPS active for X gives the same picture size in macroblocks, chroma_format_idc,
+     * frame_mbs_only_flag and log2_max_frame_num_minus4 as the one the stream's reference frames were decoded under (a re-sent identical SPS is fine),
+     * and the initial P list (8.2.4.2.1) -- built when X's first slice arrives, BEFORE X's marking drops the references, for a frame picture with
+     * frame_num F' = (PrevRefFrameNum + 1) mod MaxFrameNum -- is not empty and its entry 0 holds samples.  That entry is X's concealment reference.  So
+     * the first picture of a stream, and an IDR picture after a reset or after an error that dropped the references, are not concealable; what is not
+     * concealable behaves exactly as with the bit clear.  The lost macroblocks of a concealable X (same definition as for bit 1) come out bit for bit
+     * as a conforming decoder reconstructs X in the stream in which: every slice NAL unit of X has nal_unit_type 1 with nal_ref_idc unchanged; every
+     * slice header of X carries frame_num F', no idr_pic_id, and a dec_ref_pic_marking() of adaptive_ref_pic_marking_mode_flag 1 with memory management
+     * operation 5 and the end code 0 (operation 5 takes effect after the picture is decoded: X predicts from the old references and leaves behind
+     * exactly the state an IDR picture leaves); the intact I slices keep every other header field and their slice data (slice_type 7 is written as 2:
+     * the picture holds P slices now); each lost slice is a P slice of P_Skip macroblocks over the same macroblocks, written as for bit 1 (one active
+     * reference, no list modification, an all-zero pred_weight_table() where the PPS asks for one, slice_qp_delta 0, disable_deblocking_filter_idc 0 with
+     * zero offsets, cabac_init_idc 0) with the same rewritten frame_num and marking.  The rule defines X's samples only: what is REPORTED for X stays an
+     * IDR picture's (h264mi_frame_get_info: idr 1, its own frame_num and PicOrderCnt), its marking is the real IDR marking, and later pictures predict
+     * from the concealed X as from any picture.  (A later B picture that uses TEMPORAL direct prediction with a concealed macroblock of X as co-located
+     * block refers to a picture that is no longer a reference: the outcome is whatever the repaired stream decodes to.)  A slice NAL unit of type 5 whose
+     * header does not parse is counted as a lost slice of the IDR picture under construction -- of the next picture, if there is none or it is not an IDR
+     * picture -- and tolerated only if that picture turns out to be a concealable IDR picture; a dropped unit whose type does not match the picture it
+     * falls to fails the stream as with 0.  Cost: with the bit set a concealable IDR picture is reconstructed behind its concealment reference when one
+     * batch decodes both, damaged or not (the device learns about damage only after the entropy launch), so a batch that holds several GOPs of one
+     * stream loses the overlap between them; a reference decoded by an earlier batch costs nothing.
+     * With every value: IDR FIELD pictures, wholly lost IDR pictures, a wholly missing field (its rows stay mid-grey), MBAFF (out of scope altogether),
+     * pictures without any reference picture and parameter-set errors are handled as with 0; so are IDR frame pictures without H264MI_CONCEAL_IDR.  The
+     * legal values are 0, 1, 3, 5, 7, 17, 19, 21 and 23: any other (bit 2, 4 or 16 without bit 1; bit 8, which is unassigned; anything above 23) is
+     * refused by h264mi_decoder_create (H264MI_EINVAL). */
     int32_t conceal_errors;
 } h264mi_config;
 #define H264MI_CONCEAL_SLICES 1    /* h264mi_config.conceal_errors: lost and damaged slices of non-IDR frame pictures */
 #define H264MI_CONCEAL_PICTURES 2  /* ... and wholly lost reference frames (only together with H264MI_CONCEAL_SLICES) */
 #define H264MI_CONCEAL_FIELDS 4    /* ... and lost and damaged slices of field pictures (only together with H264MI_CONCEAL_SLICES) */
+#define H264MI_CONCEAL_IDR 16      /* ... and lost and damaged slices of IDR frame pictures that still have a reference frame (only together with H264MI_CONCEAL_SLICES) */
 #define H264MI_CONCEAL_MAX_GAP 16  /* the longest run of lost frames that is concealed: the largest DPB -- older frames would have left the sliding window anyway */
 #define H264MI_CONFIG_INIT {(uint32_t)sizeof(h264mi_config)} /* h264mi_config cfg = H264MI_CONFIG_INIT; then set the fields */
 

@@ -51,12 +51,14 @@ static std::vector<size_t> au_cuts(const std::vector<uint8_t> &s) {
 }
 
 static std::vector<std::vector<uint8_t>> streams;
-static std::atomic<long> batches{0}, ok_streams{0}, failed_streams{0}, frames{0}, refused{0};
+static std::atomic<long> batches{0}, ok_streams{0}, failed_streams{0}, frames{0}, refused{0}, concealing{0};
 static std::atomic<long> codes[64];
 
 // one client: `iters` decoders one after the other, each fed its own random mix of streams
 static void client(int iters, unsigned seed) {
     std::mt19937 rng(seed);
+    std::mt19937 crng(seed ^ 0x5bd1e995u); // error concealment is drawn from a generator of its own: everything else a seed draws stays what it was
+    static const int conceal_values[] = {0, 0, 0, 1, 3, 5, 7, 17, 19, 21, 23}; // every legal value of h264mi_config.conceal_errors
     std::vector<uint8_t> pix(4 << 20);
     for (int it = 0; it < iters; it++) {
         const int ns = 1 + rng() % 4;
@@ -73,8 +75,11 @@ static void client(int iters, unsigned seed) {
         cfg.max_bitstream_bytes = tight ? 4096 << (rng() % 9) : 4 << 20;
         if (rng() % 4 == 0) cfg.max_ref_frames = 1 + rng() % 16;
         if (rng() % 4 == 0) cfg.coef_blocks_per_mb = 1 + rng() % 26;
+        const int conceal = conceal_values[crng() % (sizeof conceal_values / sizeof conceal_values[0])];
+        if (cfg.struct_size == sizeof cfg) cfg.conceal_errors = conceal; // (the short struct of an older caller ends in front of the field)
         h264mi_decoder *dec = nullptr;
         if (h264mi_decoder_create(&cfg, &dec) != 0 || !dec) { refused++; continue; }
+        if (cfg.conceal_errors) concealing++;
         if (rng() % 3 == 0) h264mi_decoder_set_isolation(dec, rng() & 1);
         // per stream: a (possibly damaged) copy and its cut list
         std::vector<std::vector<uint8_t>> data(ns);
@@ -158,6 +163,7 @@ int main(int argc, char **argv) {
     }
     printf("host asan: %d decoders (%ld refused), %ld batches, stream results %ld ok / %ld failed, %ld frames\n", iters, refused.load(), batches.load(), ok_streams.load(),
            failed_streams.load(), frames.load());
+    printf("decoders with error concealment: %ld\n", concealing.load());
     printf("stream status histogram:");
     for (int i = 0; i < 64; i++) if (codes[i].load()) printf(" %d:%ld", -i, codes[i].load());
     printf("\n");
