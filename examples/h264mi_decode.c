@@ -75,7 +75,7 @@ int main(int argc, char **argv) {
     if ((r = h264mi_decoder_create(&cfg, &dec)) != H264MI_OK) return fail("h264mi_decoder_create", r);
 
     FILE *out = fopen(argv[2], "wb");
-    const size_t fsz = (size_t)sps.width * sps.height * 3 / 2;
+    const size_t fsz = H264MI_I420_SIZE(sps.width, sps.height);
     uint8_t *frame = NULL;
     size_t frame_cap = 0;
     long total = 0;
@@ -144,7 +144,7 @@ int main(int argc, char **argv) {
                 if ((r = h264mi_decode_batch(dec, 1, &ptr, &l, &info)) != H264MI_OK) return fail("h264mi_decode_batch", r);
                 int32_t k = 0;
                 h264mi_stream_frame_count(dec, 0, &k);
-                const size_t need = (size_t)info.coded_width * info.coded_height * 3 / 2;
+                const size_t need = H264MI_I420_SIZE(info.coded_width, info.coded_height);
                 if (need > frame_cap) frame = (uint8_t *)realloc(frame, frame_cap = need);
                 for (int fidx = 0; fidx < k; fidx++) {
                     if ((r = h264mi_frame_read(dec, 0, fidx, 1, frame, frame_cap)) != H264MI_OK) return fail("h264mi_frame_read", r);

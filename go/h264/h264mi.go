@@ -415,9 +415,13 @@ func (d *Decoder) ConcealedPictures() (int64, error) {
 	return int64(n), nil
 }
 
+// I420Size is H264MI_I420_SIZE of include/h264mi.h: w*h luma bytes and two chroma planes of ceil(w/2) x ceil(h/2)
+// (w*h*3/2 for even sizes; monochrome streams may have odd display sizes).
+func I420Size(w, h int) int { return w*h + 2*((w+1)/2)*((h+1)/2) }
+
 // FrameRead returns tight I420 (Y, Cb, Cr back to back).
 func (d *Decoder) FrameRead(stream, frame int, crop bool, w, h int) ([]byte, error) {
-	buf := make([]byte, w*h*3/2)
+	buf := make([]byte, I420Size(w, h))
 	cr := 0
 	if crop {
 		cr = 1

@@ -92,7 +92,7 @@ extern "C" __global__ void __launch_bounds__(256) k_dbprep(const uint32_t *pic_l
     for (int it = wave; it < MI_DBPREP_MBS / 4; it += 4) {
         const int mb = mb_first + it * 4 + sub;
         const bool valid = mb < nmb;
-        const int mby = static_cast<int>(__umulhi(static_cast<uint32_t>(valid ? mb : 0), pd->inv_wmb)), mbx = (valid ? mb : 0) - mby * wmb;
+        const int mby = static_cast<int>(MI_MB_ROW(static_cast<uint32_t>(valid ? mb : 0), pd->inv_wmb)), mbx = (valid ? mb : 0) - mby * wmb;
         const bool has_left = valid && mbx > 0, has_top = valid && mby > 0;
         if (valid) { // lanes 0-7: the record, lanes 8-15: the record above; then lanes 0-7: the record to the left
             const v4u z = v4u{0u, 0u, 0u, 0u};

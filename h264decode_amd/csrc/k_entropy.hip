@@ -2053,7 +2053,7 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
             }
             consecutive = next == addr + 1 && e.mbx + 1 < e.wmb;
             addr = next;
-            e.mby = static_cast<int>(__umulhi(static_cast<uint32_t>(addr), inv_wmb)), e.mbx = addr - e.mby * e.wmb;
+            e.mby = static_cast<int>(MI_MB_ROW(static_cast<uint32_t>(addr), inv_wmb)), e.mbx = addr - e.mby * e.wmb;
         } else {
             addr++;
             if (++e.mbx == e.wmb) e.mbx = 0, e.mby++;

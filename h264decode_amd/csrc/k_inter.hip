@@ -331,7 +331,7 @@ __device__ __forceinline__ void inter4(InterLds *lds, const uint32_t *pic_list, 
     const int t8x8 = static_cast<int>((h0 >> 8) & 255u), qp = static_cast<int>((h0 >> 16) & 255u), cbp = static_cast<int>((h1 >> 8) & 255u);
     const uint32_t cmask = inter ? rw[29] : 0u, coef_off = rw[28];
     const int W = wmb * 16, H = hmb * 16;
-    const int mby = static_cast<int>(__umulhi(static_cast<uint32_t>(valid ? mb : 0), pd->inv_wmb)), mbx = (valid ? mb : 0) - mby * wmb;
+    const int mby = static_cast<int>(MI_MB_ROW(static_cast<uint32_t>(valid ? mb : 0), pd->inv_wmb)), mbx = (valid ? mb : 0) - mby * wmb;
     const int px = mbx * 16 + bx * 4, py = mby * 16 + by * 4;
     const g8 *pool = (const g8 *)pd->pool_base;
     const uint32_t slot_bytes = static_cast<uint32_t>(pd->slot_bytes);

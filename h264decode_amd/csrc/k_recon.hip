@@ -770,7 +770,8 @@ extern "C" __global__ void __launch_bounds__(MI_INTRA_WAVES * 64) k_intra_x(cons
 extern "C" __global__ void __launch_bounds__(256) k_pack(const PackDesc *descs, uint8_t *dst, int rows_per_block) {
     const PackDesc pd = descs[blockIdx.x];
     const int w = static_cast<int>(pd.w), h = static_cast<int>(pd.h), W = static_cast<int>(pd.W), H = static_cast<int>(pd.H);
-    const int nrows = 2 * h; // h luma rows + h/2 + h/2 chroma rows
+    const int wc = (w + 1) / 2, hc = (h + 1) / 2; // chroma plane of the packed frame (H264MI_I420_SIZE; odd w or h: monochrome streams only)
+    const int nrows = h + 2 * hc; // h luma rows + hc Cb rows + hc Cr rows
     const uint8_t *src = reinterpret_cast<const uint8_t *>(pd.src);
     uint8_t *out = dst + pd.dst_off;
     const int r0 = static_cast<int>(blockIdx.y) * rows_per_block, r1 = min(r0 + rows_per_block, nrows);
@@ -781,9 +782,9 @@ extern "C" __global__ void __launch_bounds__(256) k_pack(const PackDesc *descs, 
         if (r < h) {
             s = src + static_cast<size_t>(r + pd.y0) * W + pd.x0, d = out + static_cast<size_t>(r) * w, n = w;
         } else {
-            const int c = r - h >= h / 2, rc = r - h - c * (h / 2);
+            const int c = r - h >= hc, rc = r - h - c * hc;
             s = src + static_cast<size_t>(W) * H + static_cast<size_t>(c) * (W / 2) * (H / 2) + static_cast<size_t>(rc + pd.y0 / 2) * (W / 2) + pd.x0 / 2;
-            d = out + static_cast<size_t>(w) * h + static_cast<size_t>(c) * (w / 2) * (h / 2) + static_cast<size_t>(rc) * (w / 2), n = w / 2;
+            d = out + static_cast<size_t>(w) * h + static_cast<size_t>(c) * wc * hc + static_cast<size_t>(rc) * wc, n = wc;
         }
         if ((((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d)) & 15) == 0) && (n & 15) == 0) {
             for (int i = static_cast<int>(threadIdx.x) * 16; i < n; i += 256 * 16) *reinterpret_cast<uint4 *>(d + i) = *reinterpret_cast<const uint4 *>(s + i);

@@ -1001,7 +1001,7 @@ static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const
     // where the picture lives in its frame slot: a field picture in the rows of its parity (PicDesc)
     pd.field = static_cast<uint8_t>(s.dpb.cur_field);
     pd.pitch = static_cast<uint32_t>(wmb * 16 * (sh.field_pic ? 2 : 1)), pd.plane = static_cast<uint32_t>(wmb * 16) * static_cast<uint32_t>(hmb * 16);
-    pd.inv_wmb = static_cast<uint32_t>((1ull << 32) / static_cast<uint32_t>(wmb)) + 1u;
+    pd.inv_wmb = wmb > 1 ? static_cast<uint32_t>((1ull << 32) / static_cast<uint32_t>(wmb)) + 1u : 0u; // (one macroblock column: mi_types.h)
     pd.pool_base = d->h_pools[si].base, pd.slot_bytes = d->slot_bytes, pd.n_slots = static_cast<uint32_t>(d->n_slots);
     g.pic_level.resize(g.n_pics, 0), g.pic_save_col.resize(g.n_pics, 0), g.pic_wave.resize(g.n_pics, 0), g.pic_init_qp.resize(g.n_pics, 26);
     g.pic_dropped.resize(g.n_pics, 0), g.pic_dropped[s.cur_pic] = 0;
@@ -1062,7 +1062,7 @@ static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const
         g.bits_end = std::max(g.bits_end, g.map_cursor);
     }
     if (!second) { // the frame this picture belongs to, as it will be shown: pushed now (frame picture), or when its fields are through (finish_picture / flush_pending_field)
-        OutFrame of{slot, wmb, hmb, 2 * sps.frame_crop_left_offset, 2 * (2 - sps.frame_mbs_only) * sps.frame_crop_top_offset, sps.width, sps.height, sl.poc, sh.frame_num,
+        OutFrame of{slot, wmb, hmb, crop_unit_x(&sps) * sps.frame_crop_left_offset, crop_unit_y(&sps) * sps.frame_crop_top_offset, sps.width, sps.height, sl.poc, sh.frame_num,
                     sh.nal_ref_idc, sh.nal_unit_type == 5, s.cur_pic, sh.nal_unit_type == 5};
         if (sh.nal_ref_idc && sh.adaptive_ref_pic_marking_mode_flag)
             for (int k = 0; k < sh.n_memory_management_control_operations; k++)
@@ -2148,14 +2148,15 @@ extern "C" int32_t h264mi_frame_read(h264mi_decoder *d, int32_t stream, int32_t 
     GUARD(d);
     const int W = of->wmb * 16, H = of->hmb * 16;
     crop_rect(of, crop, &x0, &y0, &w, &h);
-    if (cap < static_cast<size_t>(w) * h * 3 / 2) return H264MI_ECAPACITY;
+    if (cap < H264MI_I420_SIZE(w, h)) return H264MI_ECAPACITY;
     HIP_TRY(hipStreamSynchronize(d->stream));
     HIP_TRY(hipMemcpy2D(dst, w, p + static_cast<size_t>(y0) * W + x0, W, w, h, hipMemcpyDeviceToHost));
     const uint8_t *cb = p + static_cast<size_t>(W) * H, *cr = cb + static_cast<size_t>(W) * H / 4;
+    const int wc = (w + 1) / 2, hc = (h + 1) / 2; // (odd only for monochrome streams: x0 + w <= W, so x0 / 2 + wc <= W / 2)
     uint8_t *o = dst + static_cast<size_t>(w) * h;
-    HIP_TRY(hipMemcpy2D(o, w / 2, cb + static_cast<size_t>(y0 / 2) * (W / 2) + x0 / 2, W / 2, w / 2, h / 2, hipMemcpyDeviceToHost));
-    o += static_cast<size_t>(w / 2) * (h / 2);
-    HIP_TRY(hipMemcpy2D(o, w / 2, cr + static_cast<size_t>(y0 / 2) * (W / 2) + x0 / 2, W / 2, w / 2, h / 2, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(o, wc, cb + static_cast<size_t>(y0 / 2) * (W / 2) + x0 / 2, W / 2, wc, hc, hipMemcpyDeviceToHost));
+    o += static_cast<size_t>(wc) * hc;
+    HIP_TRY(hipMemcpy2D(o, wc, cr + static_cast<size_t>(y0 / 2) * (W / 2) + x0 / 2, W / 2, wc, hc, hipMemcpyDeviceToHost));
     return H264MI_OK;
 }
 
@@ -2185,7 +2186,7 @@ static int pack_frames(h264mi_decoder *d, const std::vector<std::pair<int, int>>
         PackDesc &pk = d->h_pack[ps][i];
         pk.src = reinterpret_cast<uint64_t>(p), pk.dst_off = off;
         pk.W = of->wmb * 16, pk.H = of->hmb * 16, pk.x0 = x0, pk.y0 = y0, pk.w = w, pk.h = h;
-        off += static_cast<size_t>(w) * h * 3 / 2;
+        off += H264MI_I420_SIZE(w, h);
         hmax = std::max(hmax, h);
     }
     if (bytes) *bytes = off;
@@ -2194,7 +2195,7 @@ static int pack_frames(h264mi_decoder *d, const std::vector<std::pair<int, int>>
     // (in order on the decoder's stream, which has waited for the reconstruction of the last executed pass: h264mi_batch_execute)
     HIP_TRY(hipMemcpyAsync(d->d_pack[ps], d->h_pack[ps], sizeof(PackDesc) * frames.size(), hipMemcpyHostToDevice, d->stream));
     const int rows_per_block = 32;
-    hipLaunchKernelGGL(k_pack, dim3(static_cast<uint32_t>(frames.size()), (2 * hmax + rows_per_block - 1) / rows_per_block), dim3(256), 0, d->stream, d->d_pack[ps],
+    hipLaunchKernelGGL(k_pack, dim3(static_cast<uint32_t>(frames.size()), (hmax + 2 * ((hmax + 1) / 2) + rows_per_block - 1) / rows_per_block), dim3(256), 0, d->stream, d->d_pack[ps],
                        static_cast<uint8_t *>(dst), rows_per_block);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(d->ev_pack[ps], d->stream));

@@ -127,7 +127,7 @@ static inline int mi_entropy_kernel_choice(int n_cabac, int n_cavlc, bool slice_
     if (slice_groups) return MI_ENT_K_FMO;
     return (n_cavlc == 0 && n_cabac > 0) ? MI_ENT_K_CABAC : MI_ENT_K_GENERAL;
 }
-// K6: crop + tight pack of a list of frames into I420; grid = (frames, ceil(2 * h_max / rows_per_block)), block = 256
+// K6: crop + tight pack of a list of frames into I420; grid = (frames, ceil((h_max + 2 * ceil(h_max / 2)) / rows_per_block)), block = 256
 typedef struct {
     uint64_t src;     // Y plane of the frame (coded size W x H; Cb at + W*H, Cr at + W*H*5/4)
     uint64_t dst_off; // byte offset of the packed frame in the destination buffer

@@ -327,11 +327,13 @@ int parse_sps(const uint8_t *rbsp, size_t len, h264mi_sps *s) {
         else if (static_cast<uint32_t>(s->chroma_format) > 3) bad = "chroma_format_idc > 3";
         else if (static_cast<uint32_t>(s->bit_depth_luma_minus8) > 6 || static_cast<uint32_t>(s->bit_depth_chroma_minus8) > 6) bad = "bit depth > 14";
         else {
-            // cropping (7-18 .. 7-21) in 4:2:0 frame units of 2 luma samples: what remains must be a non-empty part of the coded picture
+            // cropping (7-18 .. 7-21) in units of CropUnitX x CropUnitY luma samples (7.4.2.1.1: SubWidthC x SubHeightC * (2 - frame_mbs_only_flag),
+            // 1 x (2 - frame_mbs_only_flag) for monochrome): what remains must be a non-empty part of the coded picture
             const uint32_t cl = static_cast<uint32_t>(s->frame_crop_left_offset), cr = static_cast<uint32_t>(s->frame_crop_right_offset);
             const uint32_t ct = static_cast<uint32_t>(s->frame_crop_top_offset), cb = static_cast<uint32_t>(s->frame_crop_bottom_offset);
-            const uint32_t W = (wmb1 + 1) * 16, H = (hmu1 + 1) * (2 - s->frame_mbs_only) * 16, vy = 2 * (2 - s->frame_mbs_only);
-            if (cl > W || cr > W || 2 * (static_cast<uint64_t>(cl) + cr) >= W) bad = "horizontal cropping leaves no picture";
+            const uint32_t W = (wmb1 + 1) * 16, H = (hmu1 + 1) * (2 - s->frame_mbs_only) * 16;
+            const uint32_t ux = crop_unit_x(s), vy = crop_unit_y(s);
+            if (cl > W || cr > W || ux * (static_cast<uint64_t>(cl) + cr) >= W) bad = "horizontal cropping leaves no picture";
             else if (ct > H || cb > H || vy * (static_cast<uint64_t>(ct) + cb) >= H) bad = "vertical cropping leaves no picture";
         }
         if (bad) {
@@ -339,11 +341,11 @@ int parse_sps(const uint8_t *rbsp, size_t len, h264mi_sps *s) {
             return H264MI_EBITSTREAM;
         }
     }
-    // PicWidthInMbs / PicHeightInMbs (h264/slice.go:159-176), cropped size (7-18..7-21, 4:2:0 frame)
+    // PicWidthInMbs / PicHeightInMbs (h264/slice.go:159-176), cropped size (7-18..7-21)
     s->pic_width_in_mbs = s->pic_width_in_mbs_minus1 + 1;
     s->pic_height_in_mbs = (s->pic_height_in_map_units_minus1 + 1) * (2 - s->frame_mbs_only);
-    s->width = s->pic_width_in_mbs * 16 - 2 * (s->frame_crop_left_offset + s->frame_crop_right_offset);
-    s->height = s->pic_height_in_mbs * 16 - 2 * (2 - s->frame_mbs_only) * (s->frame_crop_top_offset + s->frame_crop_bottom_offset);
+    s->width = s->pic_width_in_mbs * 16 - crop_unit_x(s) * (s->frame_crop_left_offset + s->frame_crop_right_offset);
+    s->height = s->pic_height_in_mbs * 16 - crop_unit_y(s) * (s->frame_crop_top_offset + s->frame_crop_bottom_offset);
     return H264MI_OK;
 }
 

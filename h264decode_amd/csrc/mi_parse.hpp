@@ -33,6 +33,10 @@ int nal_parse(const uint8_t *nal, size_t len, h264mi_nal *hdr, uint8_t *rbsp, si
 // RBSP extraction only (header byte(s) skipped by the caller via `skip`)
 size_t unescape(const uint8_t *src, size_t n, uint8_t *dst);
 int parse_sps(const uint8_t *rbsp, size_t len, h264mi_sps *s);
+// CropUnitX / CropUnitY (7.4.2.1.1) in luma samples: 1 x (2 - frame_mbs_only_flag) for ChromaArrayType 0, else SubWidthC x SubHeightC * (2 - frame_mbs_only_flag)
+// (4:2:0 values; 4:2:2 / 4:4:4 streams parse but are refused before anything is cropped)
+inline int crop_unit_x(const h264mi_sps *s) { return s->chroma_format == 0 ? 1 : 2; }
+inline int crop_unit_y(const h264mi_sps *s) { return (s->chroma_format == 0 ? 1 : 2) * (2 - s->frame_mbs_only); }
 int parse_pps(const h264mi_sps *sps, const uint8_t *rbsp, size_t len, h264mi_pps *p);
 int parse_pps_ids(const h264mi_sps *sps, const uint8_t *rbsp, size_t len, h264mi_pps *p, uint8_t *ids, size_t cap, size_t *n_ids);
 // 8.2.2 (h264/slice.go:134-158, :457-552)

@@ -156,7 +156,8 @@ typedef struct {
     uint8_t fmo;           /* more than one slice group: sgmap_off is valid, the records are zeroed before the entropy kernels run */
     uint8_t mono;          /* chroma_format_idc 0: the entropy kernels parse no chroma syntax (h264/sps.go:226-243) */
     uint32_t sgmap_off;    /* byte offset of the picture's mbToSliceGroupMap (8.2.2.8, one byte per macroblock) in the bitstream buffer */
-    uint32_t inv_wmb;      /* floor(2^32 / wmb) + 1: mby = mulhi(mb, inv_wmb) is exact for mb < 2^32 / wmb / wmb (wmb <= 512, hmb <= 320) */
+    uint32_t inv_wmb;      /* floor(2^32 / wmb) + 1: mby = mulhi(mb, inv_wmb) is exact for mb < 2^32 / wmb / wmb (wmb <= 512, hmb <= 320); 0 for wmb = 1, whose
+                            * reciprocal 2^32 + 1 has no 32 bits: mby = mb (MI_MB_ROW) */
     /* Where the picture's samples are in its frame slot.  A frame: pitch = 16 wmb, plane = 16 wmb x 16 hmb.  A field picture
      * (h264/slice.go:867-872 field_pic_flag / bottom_field_flag) is reconstructed IN PLACE into the rows of its parity of the frame's slot:
      * hmb counts the field's macroblock rows, pitch is twice the frame's, plane the FRAME's plane size, and the first row starts
@@ -169,6 +170,8 @@ typedef struct {
                             * (8.2.4.2.1) -- what k_conceal copies lost macroblocks from; -1: the picture is not concealable, or the mode is off */
     uint8_t pad3[4];
 } PicDesc;
+/* macroblock row of macroblock address mb in a picture whose PicDesc::inv_wmb is inv (device code) */
+#define MI_MB_ROW(mb, inv) ((inv) ? __umulhi((mb), (inv)) : (mb))
 /* In field pictures a reference "slot" (SliceDesc::ref_slot, BSliceExt::ref_slot1, MbRec::refslot / refslot1, ColRec::refslot) names a FIELD:
  * the frame slot in the low bits and the field's parity in bit 14 (frame pictures never set it: they predict from whole frames). */
 #define MI_REF_PARITY 0x4000

@@ -367,6 +367,12 @@ class Decoder:
                                                  ctypes.byref(pc), ctypes.byref(w), ctypes.byref(h)))
         return dict(y=y.value, cb=cb.value, cr=cr.value, pitch_y=py.value, pitch_c=pc.value, coded_width=w.value, coded_height=h.value)
 
+    @staticmethod
+    def i420_size(w, h):
+        """H264MI_I420_SIZE of include/h264mi.h: w*h luma bytes, then two chroma planes of ceil(w/2) x ceil(h/2) (w*h*3/2 for even sizes;
+        the display size of a monochrome stream may be odd)."""
+        return w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)
+
     def read_frame(self, stream, frame, crop=True):
         p = self.frame_planes(stream, frame)
         buf = np.zeros(p["coded_width"] * p["coded_height"] * 3 // 2, dtype=np.uint8)
@@ -374,10 +380,10 @@ class Decoder:
         return buf
 
     def read_frame_tight(self, stream, frame, crop=True):
-        """The frame as exactly w*h*3/2 bytes of its own geometry (display size when cropped)."""
+        """The frame as exactly i420_size(w, h) bytes of its own geometry (display size when cropped)."""
         fi = self.frame_info(stream, frame)
         w, h = (fi.width, fi.height) if crop else (fi.coded_width, fi.coded_height)
-        return self.read_frame(stream, frame, crop)[:w * h * 3 // 2]
+        return self.read_frame(stream, frame, crop)[:self.i420_size(w, h)]
 
     def read_frames(self, stream=0, crop=False, size=None):
         """All frames of `stream` from the last batch as uint8[n, w*h*3/2] (tight I420)."""
@@ -649,7 +655,7 @@ class H264Reader:
         info = self.decoder.info
         if info.width and info.height:
             self._dims = (info.width, info.height)
-        return self._dims[0] * self._dims[1] * 3 // 2
+        return Decoder.i420_size(*self._dims)
 
     def run(self):
         """Read until the peer closes the connection; returns the number of decoded frames."""

@@ -350,7 +350,11 @@ int32_t h264mi_frame_get_info(h264mi_decoder *dec, int32_t stream, int32_t frame
  * of a group of B pictures merges the tail of one batch with the head of the next by pic_order_cnt.  (The reference has no
  * output process at all: h264/server.go:113-166 stops at the parsed slice.) */
 int32_t h264mi_stream_output_order(h264mi_decoder *dec, int32_t stream, int32_t *order, int32_t cap, int32_t *n);
-/* Copy a frame to host memory as tight I420 (crop != 0: display size, else coded size). */
+/* Tight I420 layout of a w x h frame, the one every output call below writes: w * h luma bytes, then the Cb and the Cr plane of
+ * ceil(w / 2) x ceil(h / 2) bytes each -- w * h * 3 / 2 for even sizes.  The display size is odd only for monochrome streams (crop
+ * units of one luma sample, 7.4.2.1.1); a chroma plane then starts at (crop_x / 2, crop_y / 2) of the coded plane like any other. */
+#define H264MI_I420_SIZE(w, h) ((size_t)(w) * (size_t)(h) + 2 * (((size_t)(w) + 1) / 2) * (((size_t)(h) + 1) / 2))
+/* Copy a frame to host memory as tight I420 (crop != 0: display size, else coded size); cap >= H264MI_I420_SIZE of that size. */
 int32_t h264mi_frame_read(h264mi_decoder *dec, int32_t stream, int32_t frame, int32_t crop, uint8_t *dst, size_t cap);
 /* Cropped, tightly packed I420 copy on the device (K6): dst is a DEVICE pointer. */
 int32_t h264mi_frame_pack_device(h264mi_decoder *dec, int32_t stream, int32_t frame, void *dst_device, size_t cap);

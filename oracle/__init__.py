@@ -69,7 +69,7 @@ def probe(stream: bytes) -> "StreamInfo":
 
 
 def decode(stream: bytes, crop=True, trace=False, info=None):
-    """Decode an Annex-B stream.  Returns (frames uint8[n, w*h*3/2], info[, trace int32[nmb,8]]).
+    """Decode an Annex-B stream.  Returns (frames uint8[n, w*h + 2*ceil(w/2)*ceil(h/2)], info[, trace int32[nmb,8]]).
     With `info` (from probe()) the sizing pass is skipped: exactly one decode runs (used for timing)."""
     L = lib()
     d = L.h264o_decoder_create()
@@ -82,7 +82,8 @@ def decode(stream: bytes, crop=True, trace=False, info=None):
             L.h264o_decoder_destroy(d)
             d = L.h264o_decoder_create()
         w, h = (info.width, info.height) if crop else (info.coded_width, info.coded_height)
-        out = np.zeros((info.n_frames, w * h * 3 // 2), dtype=np.uint8)
+        # (luma, then two chroma planes of ceil(w/2) x ceil(h/2): the display size of a monochrome stream may be odd)
+        out = np.zeros((info.n_frames, w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)), dtype=np.uint8)
         tr = None
         if trace:
             tr = np.zeros((int(info.n_mbs), 8), dtype=np.int32)

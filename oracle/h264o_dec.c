@@ -45,6 +45,11 @@ void h264o_set_mb_trace(h264o_decoder *d, int32_t *trace, size_t cap) {
     d->trace_pos = 0;
 }
 
+/* CropUnitX / CropUnitY of 7.4.2.1.1 in luma samples: SubWidthC x SubHeightC * (2 - frame_mbs_only_flag), and 1 x (2 - frame_mbs_only_flag)
+ * for ChromaArrayType 0 (4:2:0 and monochrome are all that activate() lets through) */
+static int crop_unit_x(const h264o_sps *s) { return s->chroma_format_idc == 0 ? 1 : 2; }
+static int crop_unit_y(const h264o_sps *s) { return (s->chroma_format_idc == 0 ? 1 : 2) * (2 - s->frame_mbs_only_flag); }
+
 static int activate(h264o_decoder *d, const h264o_pps *pps) {
     const h264o_sps *s = &d->sps[pps->seq_parameter_set_id];
     if (!s->valid) return h264o_fail(d, "PPS %d refers to missing SPS %d", pps->pic_parameter_set_id, pps->seq_parameter_set_id);
@@ -79,8 +84,8 @@ static int activate(h264o_decoder *d, const h264o_pps *pps) {
     }
     d->info.coded_width = wmb * 16;
     d->info.coded_height = hmb * 16;
-    d->info.width = wmb * 16 - 2 * (s->frame_crop_left_offset + s->frame_crop_right_offset);
-    d->info.height = hmb * 16 - 2 * (2 - s->frame_mbs_only_flag) * (s->frame_crop_top_offset + s->frame_crop_bottom_offset); /* CropUnitY = SubHeightC * (2 - frame_mbs_only_flag) */
+    d->info.width = wmb * 16 - crop_unit_x(s) * (s->frame_crop_left_offset + s->frame_crop_right_offset);
+    d->info.height = hmb * 16 - crop_unit_y(s) * (s->frame_crop_top_offset + s->frame_crop_bottom_offset);
     d->asps = s;
     d->apps = pps;
     h264o_build_level_scale(d);
@@ -489,15 +494,16 @@ static void emit_frame(h264o_decoder *d, h264o_pic *p) {
     const h264o_sps *s = d->asps;
     int cw = d->info.coded_width, ch = d->info.coded_height;
     int w = d->crop ? d->info.width : cw, h = d->crop ? d->info.height : ch;
-    int x0 = d->crop ? 2 * s->frame_crop_left_offset : 0, y0 = d->crop ? 2 * (2 - s->frame_mbs_only_flag) * s->frame_crop_top_offset : 0;
-    size_t need = (size_t)w * h * 3 / 2;
+    int x0 = d->crop ? crop_unit_x(s) * s->frame_crop_left_offset : 0, y0 = d->crop ? crop_unit_y(s) * s->frame_crop_top_offset : 0;
+    int wc = (w + 1) / 2, hc = (h + 1) / 2; /* odd display sizes (monochrome only): chroma planes of ceil(w / 2) x ceil(h / 2) */
+    size_t need = (size_t)w * h + 2 * (size_t)wc * hc;
     if (d->out && d->out_pos + need <= d->out_cap) {
         uint8_t *o = d->out + d->out_pos;
         for (int y = 0; y < h; y++) memcpy(o + (size_t)y * w, p->plane[0] + (size_t)(y + y0) * p->stride[0] + x0, w);
         o += (size_t)w * h;
         for (int pl = 1; pl < 3; pl++) {
-            for (int y = 0; y < h / 2; y++) memcpy(o + (size_t)y * (w / 2), p->plane[pl] + (size_t)(y + y0 / 2) * p->stride[pl] + x0 / 2, w / 2);
-            o += (size_t)(w / 2) * (h / 2);
+            for (int y = 0; y < hc; y++) memcpy(o + (size_t)y * wc, p->plane[pl] + (size_t)(y + y0 / 2) * p->stride[pl] + x0 / 2, wc);
+            o += (size_t)wc * hc;
         }
     }
     d->out_pos += need;

@@ -1776,7 +1776,9 @@ static size_t write_sps(enc *e, uint8_t *dst, size_t cap) {
         sg_put(&w, 1, 1); /* frame_mbs_only */
     }
     sg_put(&w, 1, 1); /* direct_8x8_inference */
-    int cr = (e->W - p->width) / 2, cb = (e->fH - p->height) / (p->interlace_sps ? 4 : 2);
+    /* CropUnitX x CropUnitY (7.4.2.1.1): SubWidthC x SubHeightC * (2 - frame_mbs_only_flag); monochrome: 1 x (2 - frame_mbs_only_flag) */
+    int ux = p->mono ? 1 : 2, uy = (p->mono ? 1 : 2) * (p->interlace_sps ? 2 : 1);
+    int cr = (e->W - p->width) / ux, cb = (e->fH - p->height) / uy;
     sg_put(&w, cr || cb, 1);
     if (cr || cb) {
         sg_put_ue(&w, 0);
@@ -2512,8 +2514,8 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
     }
     e->W = (p->width + 15) & ~15, e->H = (p->height + 15) & ~15;
     e->wmb = e->W / 16, e->hmb = e->H / 16;
-    if (p->interlace_sps && ((e->hmb & 1) || ((e->H - p->height) & 3))) {
-        snprintf(g_err, sizeof(g_err), "interlace_sps needs an even number of macroblock rows and a height whose padding is a multiple of 4");
+    if (p->interlace_sps && ((e->hmb & 1) || ((e->H - p->height) & (p->mono ? 1 : 3)))) {
+        snprintf(g_err, sizeof(g_err), "interlace_sps needs an even number of macroblock rows and a height whose padding is a multiple of 4 (monochrome: of 2)");
         free(e);
         return 0;
     }
