@@ -24,7 +24,7 @@ static int fail(const char *what, int code) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr]\n", argv[0]);
+        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields]\n", argv[0]);
         return 2;
     }
     int conceal = 0; /* --conceal (last argument): h264mi_config.conceal_errors */
@@ -34,6 +34,9 @@ int main(int argc, char **argv) {
     /* --conceal-idr: all of that, and slices of IDR frame pictures that still have a reference frame */
     else if (argc > 3 && !strcmp(argv[argc - 1], "--conceal-idr"))
         conceal = H264MI_CONCEAL_SLICES | H264MI_CONCEAL_PICTURES | H264MI_CONCEAL_FIELDS | H264MI_CONCEAL_IDR, argc--;
+    /* --conceal-lone-fields: what --conceal-all conceals, and the wholly lost field of a frame coded as two field pictures */
+    else if (argc > 3 && !strcmp(argv[argc - 1], "--conceal-lone-fields"))
+        conceal = H264MI_CONCEAL_SLICES | H264MI_CONCEAL_PICTURES | H264MI_CONCEAL_FIELDS | H264MI_CONCEAL_LONE_FIELDS, argc--;
     const int per_batch = argc > 3 ? atoi(argv[3]) : 30;
     FILE *f = fopen(argv[1], "rb");
     if (!f) return fail("fopen", -1);
@@ -161,6 +164,7 @@ int main(int argc, char **argv) {
         int64_t cs = 0, cm = 0;
         if (h264mi_decoder_concealed(dec, &cs, &cm) == H264MI_OK) fprintf(stderr, "concealed: %lld slices, %lld macroblocks\n", (long long)cs, (long long)cm);
         if ((conceal & H264MI_CONCEAL_PICTURES) && h264mi_decoder_concealed_pictures(dec, &cs) == H264MI_OK) fprintf(stderr, "concealed: %lld pictures\n", (long long)cs);
+        if ((conceal & H264MI_CONCEAL_LONE_FIELDS) && h264mi_decoder_concealed_fields(dec, &cs) == H264MI_OK) fprintf(stderr, "concealed: %lld fields\n", (long long)cs);
     }
     h264mi_decoder_destroy(dec);
     fprintf(stderr, "%s: %ld frames %dx%d -> %s\n", h264mi_version(), total, sps.width, sps.height, argv[2]);

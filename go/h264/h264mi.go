@@ -334,17 +334,18 @@ type Config struct {
 	MaxRefFrames, CoefBlocksPerMb                                                  int // 0 = defaults (16 reference slots per stream, 8 residual blocks per macroblock)
 	BPictures                                                                      int // 1 = the buffers only B pictures need exist from the start (h264mi_config.b_pictures)
 	AllowUnpinnedFieldCabac                                                        int // 1 = CABAC field pictures are decoded with the unpinned context tables (h264mi_config.allow_unpinned_field_cabac)
-	ConcealErrors                                                                  int // ConcealSlices = lost macroblocks of non-IDR frame pictures are copied from a reference picture; | ConcealPictures = wholly lost reference frames too; | ConcealFields = field pictures too; | ConcealIDR = IDR frame pictures that still have a reference frame too (h264mi_config.conceal_errors)
+	ConcealErrors                                                                  int // ConcealSlices = lost macroblocks of non-IDR frame pictures are copied from a reference picture; | ConcealPictures = wholly lost reference frames too; | ConcealFields = field pictures too; | ConcealIDR = IDR frame pictures that still have a reference frame too; | ConcealLoneFields (with ConcealFields) = the wholly lost field of a frame coded as two field pictures too (h264mi_config.conceal_errors)
 }
 
-// Bits of Config.ConcealErrors (H264MI_CONCEAL_*); ConcealPictures, ConcealFields and ConcealIDR only together with ConcealSlices.  ConcealMaxGap: the longest run of lost
+// Bits of Config.ConcealErrors (H264MI_CONCEAL_*); ConcealPictures, ConcealFields and ConcealIDR only together with ConcealSlices, ConcealLoneFields only together with ConcealSlices and ConcealFields.  ConcealMaxGap: the longest run of lost
 // frames that is concealed -- MaxFramesPerBatch needs that much headroom over the pictures of a chunk.
 const (
-	ConcealSlices   = C.H264MI_CONCEAL_SLICES
-	ConcealPictures = C.H264MI_CONCEAL_PICTURES
-	ConcealFields   = C.H264MI_CONCEAL_FIELDS
-	ConcealIDR      = C.H264MI_CONCEAL_IDR
-	ConcealMaxGap   = C.H264MI_CONCEAL_MAX_GAP
+	ConcealSlices     = C.H264MI_CONCEAL_SLICES
+	ConcealPictures   = C.H264MI_CONCEAL_PICTURES
+	ConcealFields     = C.H264MI_CONCEAL_FIELDS
+	ConcealIDR        = C.H264MI_CONCEAL_IDR
+	ConcealLoneFields = C.H264MI_CONCEAL_LONE_FIELDS
+	ConcealMaxGap     = C.H264MI_CONCEAL_MAX_GAP
 )
 type Decoder struct{ h *C.h264mi_decoder }
 type BatchInfo struct {
@@ -410,6 +411,15 @@ func (d *Decoder) Concealed() (slices, macroblocks int64, err error) {
 func (d *Decoder) ConcealedPictures() (int64, error) {
 	var n C.int64_t
 	if err := status(C.h264mi_decoder_concealed_pictures(d.h, &n)); err != nil {
+		return 0, err
+	}
+	return int64(n), nil
+}
+
+// ConcealedFields: fields inserted for wholly lost fields since the decoder was created (h264mi_decoder_concealed_fields).
+func (d *Decoder) ConcealedFields() (int64, error) {
+	var n C.int64_t
+	if err := status(C.h264mi_decoder_concealed_fields(d.h, &n)); err != nil {
 		return 0, err
 	}
 	return int64(n), nil

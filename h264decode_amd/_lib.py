@@ -125,6 +125,7 @@ def load():
         "h264mi_frame_concealed": [vp, I32, I32, P(I32)],
         "h264mi_decoder_concealed": [vp, P(ctypes.c_int64), P(ctypes.c_int64)],
         "h264mi_decoder_concealed_pictures": [vp, P(ctypes.c_int64)],
+        "h264mi_decoder_concealed_fields": [vp, P(ctypes.c_int64)],
         "h264mi_last_kernel_times": [vp, P(ctypes.c_double)],
         "h264mi_last_launch_times": [vp, I32, P(ctypes.c_float), I32, P(I32)],
     }
@@ -154,4 +155,4 @@ EXPORTS = ["h264mi_annexb_scan", "h264mi_nal_parse", "h264mi_sps_parse", "h264mi
            "h264mi_decoder_set_profiling", "h264mi_last_kernel_times", "h264mi_last_error_string", "h264mi_version",
            "h264mi_last_launch_times", "h264mi_batch_pack_device", "h264mi_stream_reset", "h264mi_stream_status", "h264mi_decoder_set_isolation", "h264mi_frame_get_info", "h264mi_stream_output_order", "h264mi_decoder_memory", "h264mi_frame_read_mbmv1", "h264mi_decoder_coef_pool", "h264mi_decoder_unpinned_failures",
            "h264mi_slice_starts_picture", "h264mi_pps_slice_group_ids", "h264mi_map_unit_to_slice_group_map", "h264mi_mb_to_slice_group_map", "h264mi_next_mb_address",
-           "h264mi_frame_concealed", "h264mi_decoder_concealed", "h264mi_decoder_concealed_pictures"]
+           "h264mi_frame_concealed", "h264mi_decoder_concealed", "h264mi_decoder_concealed_pictures", "h264mi_decoder_concealed_fields"]

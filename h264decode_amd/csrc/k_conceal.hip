@@ -23,6 +23,9 @@
 // A picture WITHOUT SLICES (PicDesc::n_slices 0) is a frame the host inserted for a wholly lost reference frame (H264MI_CONCEAL_PICTURES): every
 // macroblock is lost, no slice status is read, nothing was written to its records before.  All of its boundary strengths come out 0 (one reference
 // picture, zero vectors, no coefficients, no intra macroblock), so K5 filters nothing and the picture is an exact copy of its concealment reference.
+// The same holds for a FIELD without slices, the complement the host inserts for a lone field (H264MI_CONCEAL_LONE_FIELDS): nothing of its own here
+// either -- hmb is the field's, conceal_ref carries the parity, and K4 derives the chroma vector of a reference field of the other parity as for any
+// field P_Skip.
 //
 // Cost when nothing is lost: per picture one workgroup that reads two status words and three SliceDesc words per slice and leaves
 // (err == 0 && fill_from == first_mb && first_mb + n_mbs == end_mb for every slice).  Pictures with slice groups start from zeroed records and

@@ -205,6 +205,10 @@ struct StreamState {
     // the next slice starts, and are tolerated only if that picture turns out to be concealable (add_slice); that slice may come with a later chunk
     int pending_drops = 0, pending_drop_err = H264MI_OK;
     int pending_drop_type = 0; // ... their nal_unit_type (1 or 5; -1: both kinds): tolerated only in a picture of that kind (H264MI_CONCEAL_IDR)
+    // error concealment of lone fields (H264MI_CONCEAL_LONE_FIELDS): the parameter sets the first field in dpb.pend_slot was decoded under, and whether
+    // the stream has stored other content under one of those ids since (the inserted field needs the ones its frame was decoded with)
+    int pend_sps_id = -1, pend_pps_id = -1;
+    bool pend_stale = false;
     // error concealment of IDR pictures (H264MI_CONCEAL_IDR): what of the SPS the stream's reference frames were decoded under must still hold for an
     // IDR picture to predict from them -- picture size in macroblocks, chroma_format_idc, frame_mbs_only_flag, log2_max_frame_num_minus4 (start_picture)
     struct RefSeq {
@@ -307,8 +311,10 @@ struct h264mi_decoder {
     bool conceal_pics = false; // ... bit H264MI_CONCEAL_PICTURES: wholly lost reference frames are inserted as pictures without slices (conceal_frame_num_gap)
     bool conceal_fields = false; // ... bit H264MI_CONCEAL_FIELDS: field pictures are concealable too
     bool conceal_idr = false; // ... bit H264MI_CONCEAL_IDR: IDR frame pictures that still have a reference frame are concealable too
+    bool conceal_lone = false; // ... bit H264MI_CONCEAL_LONE_FIELDS: the missing field of a frame is inserted as a picture without slices (flush_pending_field)
     int64_t concealed_slices = 0, concealed_mbs = 0; // totals since create (h264mi_decoder_concealed)
     int64_t concealed_pics = 0;                      // (h264mi_decoder_concealed_pictures)
+    int64_t concealed_fields = 0;                    // (h264mi_decoder_concealed_fields)
     bool isolate = false; // h264mi_decoder_set_isolation: a broken stream does not fail the batch
     // profiling
     bool profiling = false;
@@ -472,10 +478,11 @@ extern "C" int32_t h264mi_decoder_create(const h264mi_config *cfg_, h264mi_decod
     memcpy(&cfg_copy, cfg_, std::min<size_t>(cfg_->struct_size, sizeof(cfg_copy)));
     const h264mi_config *cfg = &cfg_copy;
     if (cfg->max_streams < 1 || cfg->max_width < 16 || cfg->max_height < 16 || cfg->max_frames_per_batch < 1) return H264MI_EINVAL;
-    if ((cfg->conceal_errors & ~(H264MI_CONCEAL_SLICES | H264MI_CONCEAL_PICTURES | H264MI_CONCEAL_FIELDS | H264MI_CONCEAL_IDR)) ||
-        (cfg->conceal_errors && !(cfg->conceal_errors & H264MI_CONCEAL_SLICES))) {
+    if ((cfg->conceal_errors & ~(H264MI_CONCEAL_SLICES | H264MI_CONCEAL_PICTURES | H264MI_CONCEAL_FIELDS | H264MI_CONCEAL_IDR | H264MI_CONCEAL_LONE_FIELDS)) ||
+        (cfg->conceal_errors && !(cfg->conceal_errors & H264MI_CONCEAL_SLICES)) ||
+        ((cfg->conceal_errors & H264MI_CONCEAL_LONE_FIELDS) && !(cfg->conceal_errors & H264MI_CONCEAL_FIELDS))) {
         set_error("h264mi_decoder_create: h264mi_config.conceal_errors = %d (0, or H264MI_CONCEAL_SLICES with or without H264MI_CONCEAL_PICTURES, H264MI_CONCEAL_FIELDS and "
-                  "H264MI_CONCEAL_IDR: 0, 1, 3, 5, 7, 17, 19, 21, 23)",
+                  "H264MI_CONCEAL_IDR: 0, 1, 3, 5, 7, 17, 19, 21, 23; H264MI_CONCEAL_LONE_FIELDS only together with H264MI_CONCEAL_FIELDS: 69, 71, 85, 87)",
                   cfg->conceal_errors);
         return H264MI_EINVAL;
     }
@@ -485,6 +492,7 @@ extern "C" int32_t h264mi_decoder_create(const h264mi_config *cfg_, h264mi_decod
     d->cfg = *cfg;
     d->conceal = (cfg->conceal_errors & H264MI_CONCEAL_SLICES) != 0, d->conceal_pics = (cfg->conceal_errors & H264MI_CONCEAL_PICTURES) != 0;
     d->conceal_fields = (cfg->conceal_errors & H264MI_CONCEAL_FIELDS) != 0, d->conceal_idr = (cfg->conceal_errors & H264MI_CONCEAL_IDR) != 0;
+    d->conceal_lone = (cfg->conceal_errors & H264MI_CONCEAL_LONE_FIELDS) != 0;
     if (d->cfg.max_slices_per_frame < 1) d->cfg.max_slices_per_frame = 1;
     d->Wmax = (cfg->max_width + 15) & ~15;
     d->Hmax = (cfg->max_height + 15) & ~15;
@@ -756,6 +764,11 @@ extern "C" int32_t h264mi_decoder_concealed_pictures(h264mi_decoder *d, int64_t 
     *pictures = d->concealed_pics;
     return H264MI_OK;
 }
+extern "C" int32_t h264mi_decoder_concealed_fields(h264mi_decoder *d, int64_t *fields) {
+    if (!d || !fields) return H264MI_EINVAL;
+    *fields = d->concealed_fields;
+    return H264MI_OK;
+}
 extern "C" int32_t h264mi_frame_concealed(h264mi_decoder *d, int32_t stream, int32_t frame, int32_t *n_macroblocks) {
     if (!d || !n_macroblocks || stream < 0 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
     const Stage &g = d->stage[d->exec];
@@ -830,11 +843,84 @@ static void finish_picture(h264mi_decoder *d, int si) {
     dpb.cur_slot = s.cur_pic = -1;
 }
 
-// A first field whose second field did not come: the frame goes out with one field decoded, the rows of the other parity painted mid-grey
-// (at the start of the batch's reconstruction: whatever the slot held before must not show)
-static void flush_pending_field(h264mi_decoder *d, int si) {
+static int scaling_set_for(h264mi_decoder *d, const h264mi_pps &p);
+static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const h264mi_pps &pps, uint32_t pps_id, const h264mi_slice_header &sh, int type, bool second);
+
+// Error concealment of a lone field (H264MI_CONCEAL_LONE_FIELDS; the rule: include/h264mi.h).  The frame in Dpb::pend_slot holds one field F and the
+// other one is not coming: the field F' of the opposite parity is put in front of whatever revealed that (`next`: the picture, with the parameter
+// sets it is decoded under; nullptr: an end-of-sequence / end-of-stream unit) as a picture WITHOUT SLICES -- the second field of F's frame, a picture
+// of the batch like any other (PicDesc, records, PicOrderCnt, marking), all of whose macroblocks k_conceal writes as P_Skip copies of
+// PicDesc::conceal_ref: entry 0 of the initial P list for fields built for F' (the field of F''s parity of the nearest reference frame that has one;
+// F itself when there is none).  The header made up here is what the repaired stream's slices of F' say, as far as picture management looks.  Returns H264MI_OK (inserted: the frame went out
+// complete), 1 (not concealable: the caller paints the rows grey as without the bit) or an error.
+static int conceal_lone_field(h264mi_decoder *d, int si, const h264mi_sps *nsps, const h264mi_pps *npps, const h264mi_slice_header *next) {
     StreamState &s = d->st[si];
-    if (s.dpb.pend_slot < 0) return;
+    Stage &g = d->stage[d->prep];
+    // the parameter sets F was decoded under must still be the ones the stream stores
+    if (s.pend_stale || s.pend_sps_id < 0 || s.pend_pps_id < 0 || !s.sps_ok[s.pend_sps_id] || !s.pps_ok[s.pend_pps_id] || s.pps[s.pend_pps_id].sps_id != s.pend_sps_id) return 1;
+    const h264mi_sps &sps = s.sps[s.pend_sps_id];
+    const h264mi_pps &pps = s.pps[s.pend_pps_id];
+    const h264mi_slice_header &fh = s.dpb.first_sh; // F's first slice: F is the picture that was completed last
+    const Slot &fs = s.dpb.slots[s.dpb.pend_slot];
+    if (!fh.field_pic || fs.fields != (fh.bottom_field ? 2 : 1) || fs.frame_num != fh.frame_num) return 1;
+    if (pps.entropy_coding_mode && !d->cfg.allow_unpinned_field_cabac) return 1;
+    const int parity = fh.bottom_field ? 1 : 2; // of F' (Dpb::cur_field: 1 top, 2 bottom)
+    const int ref0 = s.dpb.second_field_p_entry0(sps, fs.frame_num, parity);
+    if (ref0 < 0 || s.dpb.slots[MI_REF_SLOT(ref0)].nonexisting) return 1;
+    // F' -- and the revealing picture, which has to fit with the bit set wherever it fits with the bit clear -- in what the batch has left
+    // (with H264MI_CONCEAL_PICTURES the revealing picture may open a frame_num gap as well: the frames conceal_frame_num_gap would insert with this bit
+    // clear must still fit with it set, or the inserted field would turn a concealed gap into a refused stream)
+    int gap = 0;
+    if (next && d->conceal_pics && next->nal_unit_type != 5 && !nsps->gaps_in_frame_num_value_allowed) {
+        const int max_fn = 1 << (nsps->log2_max_frame_num_minus4 + 4);
+        const int prev_ref = fh.nal_ref_idc ? fs.frame_num : s.dpb.prev_ref_frame_num; // PrevRefFrameNum once F' is through
+        if (next->frame_num != prev_ref) gap = (next->frame_num - (prev_ref + 1) % max_fn + max_fn) % max_fn;
+        if (gap > H264MI_CONCEAL_MAX_GAP) gap = 0; // (not concealed either way)
+    }
+    const int need = (next ? 2 : 1) + gap;
+    const uint64_t field_mbs = static_cast<uint64_t>(sps.pic_width_in_mbs) * (sps.pic_height_in_mbs / 2);
+    const uint64_t next_mbs = next ? static_cast<uint64_t>(nsps->pic_width_in_mbs) * (next->field_pic ? nsps->pic_height_in_mbs / 2 : nsps->pic_height_in_mbs) : 0;
+    if (s.n_pics_in_batch + need > d->cfg.max_frames_per_batch || g.n_pics + need > d->pics_cap) return 1;
+    const uint64_t gap_mbs = gap ? static_cast<uint64_t>(gap) * nsps->pic_width_in_mbs * nsps->pic_height_in_mbs : 0;
+    if (g.mb_used + field_mbs + next_mbs + gap_mbs > d->mb_cap) return 1;
+    size_t cursor = g.map_cursor; // every picture's slice group map goes into the staging buffer (start_picture)
+    for (int k = 0; k < need; k++) // F', the revealing picture, the frames of its gap
+        if ((k ? npps : &pps)->num_slice_groups_minus1 > 0) {
+            const size_t moff = (cursor + 15) & ~static_cast<size_t>(15), n_mbs = static_cast<size_t>(k == 0 ? field_mbs : (k == 1 ? next_mbs : gap_mbs / gap));
+            if (moff + n_mbs + 4096 > d->bits_cap) return 1;
+            cursor = moff + n_mbs;
+        }
+    if (scaling_set_for(d, pps) < 0) return 1;
+    h264mi_slice_header f;
+    memset(&f, 0, sizeof(f));
+    f.pps_id = s.pend_pps_id, f.frame_num = fs.frame_num, f.nal_ref_idc = fh.nal_ref_idc, f.nal_unit_type = 1;
+    f.field_pic = 1, f.bottom_field = fh.bottom_field ? 0 : 1;
+    f.slice_group_change_cycle = fh.slice_group_change_cycle;
+    if (sps.pic_order_count_type == 0) f.pic_order_cnt_lsb = (fh.pic_order_cnt_lsb + 1) % (1 << (sps.log2_max_pic_order_cnt_lsb_min4 + 4));
+    f.num_ref_idx_active_override = 1;
+    f.slice_qp_y = 26 + pps.pic_init_qp_minus26;
+    const int drops = s.pending_drops; // slices with an unreadable header in front of the revealing picture belong to IT, not to the inserted field
+    s.pending_drops = 0;
+    int r = start_picture(d, si, sps, pps, static_cast<uint32_t>(s.pend_pps_id), f, 1, true);
+    if (r == H264MI_OK && g.h_pics[s.cur_pic].conceal_ref != ref0) { // (cannot happen: the same list was built above)
+        set_error("stream %d: the field inserted for a lone field has no reference", si);
+        r = H264MI_EBITSTREAM;
+    }
+    if (r == H264MI_OK) finish_picture(d, si); // (both fields are through: the frame goes out there)
+    s.pending_drops = drops;
+    return r;
+}
+
+// A first field whose second field did not come: the frame goes out with one field decoded, the rows of the other parity painted mid-grey
+// (at the start of the batch's reconstruction: whatever the slot held before must not show) -- or, with H264MI_CONCEAL_LONE_FIELDS and where
+// that is possible, complete: conceal_lone_field.  `next`: the picture that follows, nullptr: none (an end-of-sequence / end-of-stream unit).
+static int flush_pending_field(h264mi_decoder *d, int si, const h264mi_sps *nsps = nullptr, const h264mi_pps *npps = nullptr, const h264mi_slice_header *next = nullptr) {
+    StreamState &s = d->st[si];
+    if (s.dpb.pend_slot < 0) return H264MI_OK;
+    if (d->conceal_lone) {
+        const int r = conceal_lone_field(d, si, nsps, npps, next);
+        if (r != 1) return r;
+    }
     Stage &g = d->stage[d->prep];
     const Slot &f = s.dpb.slots[s.dpb.pend_slot];
     OutFrame o = s.pend_out;
@@ -842,6 +928,7 @@ static void flush_pending_field(h264mi_decoder *d, int si) {
     g.out[si].push_back(o);
     g.grey.push_back({static_cast<uint32_t>(si), static_cast<uint32_t>(s.dpb.pend_slot), f.fields == 1 ? 1u : 0u, static_cast<uint32_t>(o.wmb * 16), static_cast<uint32_t>(o.hmb * 16)});
     s.dpb.pend_slot = -1;
+    return H264MI_OK;
 }
 
 extern "C" int32_t h264mi_slice_starts_picture(const h264mi_sps *sps, const h264mi_slice_header *prev, const h264mi_slice_header *cur) {
@@ -1068,7 +1155,7 @@ static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const
             for (int k = 0; k < sh.n_memory_management_control_operations; k++)
                 if (sh.memory_management_control_operation[k] == 5) of.new_sequence = 1;
         if (sh.field_pic)
-            s.pend_out = of;
+            s.pend_out = of, s.pend_sps_id = pps.sps_id, s.pend_pps_id = static_cast<int>(pps_id), s.pend_stale = false;
         else
             g.out[si].push_back(of);
     }
@@ -1237,7 +1324,8 @@ static int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref
             set_error("stream %d: picture size changes without an IDR", si);
             return H264MI_EBITSTREAM;
         }
-        flush_pending_field(d, si); // (a lone first field of the old sequence goes out before anything of the new one)
+        r = flush_pending_field(d, si, &sps, &pps, &sh); // (a lone first field of the old sequence goes out before anything of the new one)
+        if (r != H264MI_OK) return r;
         s.active_sps = pps.sps_id, s.wmb = wmb, s.hmb = hmb;
     }
     if (s.dpb.cur_slot < 0) { // first slice of a new picture
@@ -1248,8 +1336,8 @@ static int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref
             const Slot &f = s.dpb.slots[s.dpb.pend_slot];
             if (sh.field_pic && type != 5 && f.fields == (sh.bottom_field ? 1 : 2) && f.frame_num == sh.frame_num && (f.ref != 0) == (ref_idc != 0))
                 second = true;
-            else
-                flush_pending_field(d, si);
+            else if ((r = flush_pending_field(d, si, &sps, &pps, &sh)) != H264MI_OK)
+                return r;
         }
         if (!second) {
             r = d->conceal_pics ? conceal_frame_num_gap(d, si, sps, pps, pps_id, sh) : 1;
@@ -1428,7 +1516,9 @@ static int harvest_status(h264mi_decoder *d, Stage &g) {
         for (int p = 0; p < g.n_pics; p++)
             if (g.h_pics[p].stream >= g.epochs.size() || g.epochs[g.h_pics[p].stream] == d->st[g.h_pics[p].stream].epoch)
                 d->concealed_mbs += g.h_status[8 * g.n_slices + p], d->concealed_slices += g.pic_dropped[p],
-                    d->concealed_pics += g.h_pics[p].n_slices == 0 && g.h_pics[p].conceal_ref >= 0; // (only an inserted picture has no slice: conceal_frame_num_gap)
+                    // (only an inserted picture has no slice -- a frame: conceal_frame_num_gap, a field: flush_pending_field)
+                    d->concealed_pics += g.h_pics[p].n_slices == 0 && g.h_pics[p].conceal_ref >= 0 && g.h_pics[p].field == 0,
+                    d->concealed_fields += g.h_pics[p].n_slices == 0 && g.h_pics[p].conceal_ref >= 0 && g.h_pics[p].field != 0;
     return result;
 }
 
@@ -1549,6 +1639,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
                 r = parse_sps(tmp.data(), rl, &sps);
                 if (r == H264MI_OK) {
                     if (s.dpb.cur_slot >= 0) finish_picture(d, si);
+                    if (d->conceal_lone && s.dpb.pend_slot >= 0 && sps.id == s.pend_sps_id && memcmp(&s.sps[sps.id], &sps, sizeof(sps))) s.pend_stale = true;
                     s.sps[sps.id] = sps, s.sps_ok[sps.id] = true;
                 }
                 break;
@@ -1570,8 +1661,9 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
                 r = parse_pps_ids(&s.sps[sid], tmp.data(), rl, &pps, ids.data(), ids.size(), &n_ids);
                 if (r == H264MI_OK) {
                     if (s.dpb.cur_slot >= 0) finish_picture(d, si);
-                    s.pps[pps.id] = pps, s.pps_ok[pps.id] = true;
                     ids.resize(n_ids);
+                    if (d->conceal_lone && s.dpb.pend_slot >= 0 && pps.id == s.pend_pps_id && (memcmp(&s.pps[pps.id], &pps, sizeof(pps)) || s.sg_ids[pps.id] != ids)) s.pend_stale = true;
+                    s.pps[pps.id] = pps, s.pps_ok[pps.id] = true;
                     s.sg_ids[pps.id] = std::move(ids);
                 }
                 break;
@@ -1586,7 +1678,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
             case 10:
             case 11:
                 if (s.dpb.cur_slot >= 0) finish_picture(d, si);
-                if (nal.type != 9) flush_pending_field(d, si); // end of sequence / end of stream: no second field will follow a lone first one
+                if (nal.type != 9) r = flush_pending_field(d, si); // end of sequence / end of stream: no second field will follow a lone first one
                 break;
             case 2:
             case 3:
@@ -1728,7 +1820,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
     // runtime multiplexes streams onto 4 hardware queues by default, and a fifth stream ended up sharing a queue with one of
     // the kernel streams, which serialised entropy decoding and reconstruction of consecutive passes.
     hipStream_t up = d->ent_stream[d->pass & 1];
-    if (g.n_slices) {
+    if (g.n_slices || g.n_pics) {
         const size_t end = std::max(g.bits_used, g.bits_end); // (bits_end: behind the slice group maps of FMO pictures, if any)
         size_t nbytes = std::min(d->bits_cap, ((end + 15) & ~static_cast<size_t>(15)) + 4096);
         memset(g.h_bits + end, 0, nbytes - end);
@@ -1785,7 +1877,7 @@ static int execute_stage(h264mi_decoder *d, int stage_idx, bool exclusive) {
     if (exclusive) d->pass += (MI_SETS - d->pass % MI_SETS) % MI_SETS; // record set 0
     d->last_exec_stage = stage_idx, d->last_exec_set = static_cast<int>(d->pass % MI_SETS);
     Stage &g = d->stage[stage_idx];
-    if (!g.n_slices && g.grey.empty()) return H264MI_OK;
+    if (!g.n_slices && !g.n_pics && g.grey.empty()) return H264MI_OK; // (pictures without slices: inserted for a lone field that an end-of-sequence unit revealed)
     GUARD(d);
     // frames that went out with one field decoded (flush_pending_field): the rows of the field that never came are painted mid-grey
     auto grey_fills = [&](hipStream_t st) -> hipError_t { // the first error, if any: a frame that was not painted must not go out as if it were
@@ -1799,7 +1891,7 @@ static int execute_stage(h264mi_decoder *d, int stage_idx, bool exclusive) {
         }
         return hipSuccess;
     };
-    if (!g.n_slices) { // nothing to decode: a chunk that only ended a sequence and thereby sent a lone first field out
+    if (!g.n_slices && !g.n_pics) { // nothing to decode: a chunk that only ended a sequence and thereby sent a lone first field out
         HIP_TRY(grey_fills(d->stream));
         HIP_TRY(hipEventRecord(g.ev_done, d->stream));
         g.executed = true, g.harvested = true;

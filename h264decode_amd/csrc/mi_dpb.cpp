@@ -185,6 +185,15 @@ int Dpb::initial_p_entry0(const h264mi_sps &sps, int frame_num, int field) const
     return initial_lists(sps, frame_num, field, false, st, lt, lists) && !lists[0].empty() ? lists[0][0] : -1;
 }
 
+int Dpb::second_field_p_entry0(const h264mi_sps &sps, int frame_num, int field) {
+    if (pend_slot < 0 || cur_slot >= 0) return -1;
+    const bool was_second = cur_second;
+    cur_slot = pend_slot, cur_second = true; // (what the list looks at of the picture under construction)
+    const int e = initial_p_entry0(sps, frame_num, field);
+    cur_slot = -1, cur_second = was_second;
+    return e;
+}
+
 int Dpb::build_ref_lists(const h264mi_sps &sps, const h264mi_slice_header &sh, bool bslice, int16_t *out0 /*MI_MAX_REFS*/, int16_t *out1) const {
     const bool field = sh.field_pic != 0;
     const int max_fn = max_frame_num(sps), bottom = sh.bottom_field ? 1 : 0;

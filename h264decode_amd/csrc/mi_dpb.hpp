@@ -61,6 +61,9 @@ struct Dpb {
     // Entry 0 of the initial P list (8.2.4.2.1 / 8.2.4.2.2 + 8.2.4.2.5) of a picture with this frame_num and structure (0 frame, 1 top field, 2 bottom
     // field) -- the picture under construction, or, with none, the next one --, written like a list entry; -1: the list is empty
     int initial_p_entry0(const h264mi_sps &sps, int frame_num, int field) const;
+    // The same for the SECOND field (structure `field`: the parity the frame in pend_slot lacks) of the frame that waits in pend_slot, before that
+    // field is under construction: what initial_p_entry0 returns once begin_picture(..., second = true) has run; -1 also when no frame waits
+    int second_field_p_entry0(const h264mi_sps &sps, int frame_num, int field);
     // The picture under construction is complete: marking (8.2.5), and the field it adds to its frame -- which then waits in pend_slot for the other one
     void finish_picture(const h264mi_sps &sps);
 

@@ -199,6 +199,7 @@ def read_nal_units(stream: bytes):
 
 CONCEAL_SLICES, CONCEAL_PICTURES, CONCEAL_FIELDS = 1, 2, 4  # bits of h264mi_config.conceal_errors (H264MI_CONCEAL_*): 2, 4 and 16 only together with CONCEAL_SLICES
 CONCEAL_IDR = 16                         # H264MI_CONCEAL_IDR (bit 8 is unassigned)
+CONCEAL_LONE_FIELDS = 64                 # H264MI_CONCEAL_LONE_FIELDS (only together with CONCEAL_SLICES | CONCEAL_FIELDS; bit 32 is unassigned)
 CONCEAL_MAX_GAP = 16                     # H264MI_CONCEAL_MAX_GAP: the longest run of lost frames that is concealed
 
 
@@ -220,7 +221,8 @@ class Decoder:
         cfg.allow_unpinned_field_cabac = allow_unpinned_field_cabac  # 1: CABAC field pictures are decoded with the unpinned context tables of field-coded blocks (default: refused)
         # True / CONCEAL_SLICES: lost macroblocks of non-IDR frame pictures are copied from a reference picture and the stream goes on (default: the
         # stream waits for an IDR picture); | CONCEAL_PICTURES: wholly lost reference frames are inserted as copies too; | CONCEAL_FIELDS: field pictures too;
-        # | CONCEAL_IDR: IDR frame pictures that still have a reference frame too (they are then reconstructed behind that frame when one batch holds both)
+        # | CONCEAL_IDR: IDR frame pictures that still have a reference frame too (they are then reconstructed behind that frame when one batch holds both);
+        # | CONCEAL_LONE_FIELDS (with CONCEAL_FIELDS): the wholly lost field of a frame coded as two field pictures is inserted as a copy too
         cfg.conceal_errors = int(conceal_errors)
         cfg.device, cfg.max_streams, cfg.max_width, cfg.max_height = device, max_streams, max_width, max_height
         cfg.max_frames_per_batch, cfg.max_slices_per_frame, cfg.max_bitstream_bytes = max_frames_per_batch, max_slices_per_frame, max_bitstream_bytes
@@ -296,6 +298,12 @@ class Decoder:
         """Frames inserted for wholly lost pictures since the decoder was created (h264mi_decoder_concealed_pictures)."""
         n = ctypes.c_int64()
         check(self._L.h264mi_decoder_concealed_pictures(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def concealed_fields(self):
+        """Fields inserted for wholly lost fields since the decoder was created (h264mi_decoder_concealed_fields)."""
+        n = ctypes.c_int64()
+        check(self._L.h264mi_decoder_concealed_fields(self._h, ctypes.byref(n)))
         return int(n.value)
 
     def coef_pool(self):

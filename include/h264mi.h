@@ -266,16 +266,40 @@ typedef struct {
      * falls to fails the stream as with 0.  Cost: with the bit set a concealable IDR picture is reconstructed behind its concealment reference when one
      * batch decodes both, damaged or not (the device learns about damage only after the entropy launch), so a batch that holds several GOPs of one
      * stream loses the overlap between them; a reference decoded by an earlier batch costs nothing.
-     * With every value: IDR FIELD pictures, wholly lost IDR pictures, a wholly missing field (its rows stay mid-grey), MBAFF (out of scope altogether),
-     * pictures without any reference picture and parameter-set errors are handled as with 0; so are IDR frame pictures without H264MI_CONCEAL_IDR.  The
-     * legal values are 0, 1, 3, 5, 7, 17, 19, 21 and 23: any other (bit 2, 4 or 16 without bit 1; bit 8, which is unassigned; anything above 23) is
-     * refused by h264mi_decoder_create (H264MI_EINVAL). */
+     * H264MI_CONCEAL_LONE_FIELDS (64, together with bits 1 and 4) = a wholly lost FIELD of a frame coded as two field pictures is concealed too.  A first
+     * field F is lone when what the decoder meets next for the stream is not its second field: another picture (one that is not a non-IDR field of the
+     * opposite parity with F's frame_num and the same zero-ness of nal_ref_idc), an end-of-sequence or end-of-stream NAL unit, or a change of the active
+     * sequence.  At that point, in front of the revealing picture, the decoder inserts the field picture F': opposite parity, F's frame_num, reference
+     * or not like F, no slices.  The result is bit for bit what a conforming decoder produces for the stream in which F' is coded as: nal_unit_type 1,
+     * nal_ref_idc equal to F's; one P slice of P_Skip macroblocks per slice group (first_mb_in_slice the lowest address of the group); F's
+     * pic_parameter_set_id and slice_group_change_cycle; F's frame_num; field_pic_flag 1 and bottom_field_flag the opposite of F's; pic_order_cnt_lsb =
+     * (F's + 1) mod MaxPicOrderCntLsb / delta_pic_order_cnt[0] = 0 / nothing for picture order count types 0 / 1 / 2 (delta_pic_order_cnt_bottom and
+     * delta_pic_order_cnt[1] are absent in a field, 7.3.3); one active reference (num_ref_idx_active_override_flag 1), no list modification, a
+     * pred_weight_table() with all flags 0 where the PPS asks for one, adaptive_ref_pic_marking_mode_flag 0 if F' is a reference, cabac_init_idc 0,
+     * slice_qp_delta 0, disable_deblocking_filter_idc 0 with zero offsets.  So F' is a zero-motion copy of entry 0 of the initial P list for fields
+     * (8.2.4.2.5) built for F', used exactly as H264MI_CONCEAL_FIELDS uses it -- the field of F''s own parity of the first reference frame in FrameNumWrap
+     * order that has one; F itself when there is none, as in the IDR frame (a zero luma vector into a field of the other parity is a chroma vector of
+     * a quarter sample, 8.4.1.4) --, nothing of it is filtered, h264mi_frame_concealed reports its macroblocks with its frame and
+     * h264mi_decoder_concealed_fields counts it.  A lost FIRST
+     * field needs no rule of its own: the surviving second field is taken for a first field, as it always was, and gets its complement by the rule above
+     * (the survivor's reference lists lack the lost field: the outcome is whatever the repaired stream decodes to).  F' is NOT inserted, and everything is
+     * as with the bit clear (the rows mid-grey, no error), when entry 0 does not exist or holds no samples; when the SPS or PPS F was decoded under has
+     * been replaced by other content since; when allow_unpinned_field_cabac is off for a CABAC stream; or when F' and the revealing picture do not fit into
+     * what the batch has left (max_frames_per_batch, macroblock records, staging room for a slice group map).  A field always counted as a picture against
+     * max_frames_per_batch: a caller who sized it for two pictures per frame needs NO extra headroom for this bit.  A lone field at the very end of
+     * input, with nothing behind it, waits for its second field as it always did.
+     * With every value: IDR FIELD pictures whose own slices are lost, wholly lost IDR pictures, a wholly missing field without H264MI_CONCEAL_LONE_FIELDS
+     * (its rows stay mid-grey), MBAFF (out of scope altogether), pictures without any reference picture and parameter-set errors are handled as with 0; so
+     * are IDR frame pictures without H264MI_CONCEAL_IDR.  The legal values are 0, 1, 3, 5, 7, 17, 19, 21 and 23, and with H264MI_CONCEAL_LONE_FIELDS 69, 71,
+     * 85 and 87: any other (bit 2, 4 or 16 without bit 1; bit 64 without bits 1 and 4; bits 8 and 32, which are unassigned; anything above 87) is refused
+     * by h264mi_decoder_create (H264MI_EINVAL). */
     int32_t conceal_errors;
 } h264mi_config;
 #define H264MI_CONCEAL_SLICES 1    /* h264mi_config.conceal_errors: lost and damaged slices of non-IDR frame pictures */
 #define H264MI_CONCEAL_PICTURES 2  /* ... and wholly lost reference frames (only together with H264MI_CONCEAL_SLICES) */
 #define H264MI_CONCEAL_FIELDS 4    /* ... and lost and damaged slices of field pictures (only together with H264MI_CONCEAL_SLICES) */
 #define H264MI_CONCEAL_IDR 16      /* ... and lost and damaged slices of IDR frame pictures that still have a reference frame (only together with H264MI_CONCEAL_SLICES) */
+#define H264MI_CONCEAL_LONE_FIELDS 64 /* ... and the wholly lost field of a frame coded as two field pictures (only together with H264MI_CONCEAL_SLICES and H264MI_CONCEAL_FIELDS) */
 #define H264MI_CONCEAL_MAX_GAP 16  /* the longest run of lost frames that is concealed: the largest DPB -- older frames would have left the sliding window anyway */
 #define H264MI_CONFIG_INIT {(uint32_t)sizeof(h264mi_config)} /* h264mi_config cfg = H264MI_CONFIG_INIT; then set the fields */
 
@@ -330,7 +354,7 @@ int32_t h264mi_decode_batch(h264mi_decoder *dec, int32_t n_streams, const uint8_
 /* Frames of the last batch, in decoding order (== output order unless the stream has B pictures: h264mi_stream_output_order).  A frame coded as two
  * field pictures (h264/slice.go:867-872) is ONE frame here: it is reported with the batch that holds its second field -- the first field's batch
  * reports nothing for it --, or, if the second field never comes, with the batch in which something else follows it (another picture, an
- * end-of-sequence / end-of-stream NAL unit), the rows of the missing field mid-grey. */
+ * end-of-sequence / end-of-stream NAL unit), the rows of the missing field mid-grey (with H264MI_CONCEAL_LONE_FIELDS: concealed). */
 int32_t h264mi_stream_frame_count(h264mi_decoder *dec, int32_t stream, int32_t *n);
 /* Device pointers + pitches of a decoded frame (coded size; planes are resident in HBM until the
  * next h264mi_batch_prepare). */
@@ -400,6 +424,9 @@ int32_t h264mi_decoder_concealed(h264mi_decoder *dec, int64_t *slices, int64_t *
 /* Frames inserted for wholly lost pictures (H264MI_CONCEAL_PICTURES) since the decoder was created, counted like the totals above when their batch is
  * synchronised.  Their macroblocks are part of the macroblock total of h264mi_decoder_concealed; the slice total does not count them. */
 int32_t h264mi_decoder_concealed_pictures(h264mi_decoder *dec, int64_t *pictures);
+/* Fields inserted for wholly lost fields (H264MI_CONCEAL_LONE_FIELDS) since the decoder was created, counted the same way (h264mi_decoder_concealed_pictures
+ * does not count them).  Their macroblocks are part of h264mi_frame_concealed of their frame and of the macroblock total of h264mi_decoder_concealed. */
+int32_t h264mi_decoder_concealed_fields(h264mi_decoder *dec, int64_t *fields);
 
 const char *h264mi_last_error_string(void);
 const char *h264mi_version(void);

@@ -30,9 +30,11 @@ def main():
     ap.add_argument("--conceal-pictures", action="store_true", help="... and wholly lost reference pictures are replaced by a copy of the picture before them (implies --conceal)")
     ap.add_argument("--conceal-idr", action="store_true", help="... and lost or damaged slices of IDR pictures that still have a reference frame are concealed too (implies --conceal)")
     ap.add_argument("--conceal-fields", action="store_true", help="... and lost or damaged slices of field pictures are concealed too (implies --conceal)")
+    ap.add_argument("--conceal-lone-fields", action="store_true", help="... and the wholly lost field of a frame coded as two field pictures is concealed too (implies --conceal-fields)")
     ap.add_argument("--batch", type=int, default=0, help="decode up to N concurrent connections side by side in one batched decoder (H.BatchServer)")
     args = ap.parse_args()
     conceal = (H.CONCEAL_PICTURES if args.conceal_pictures else 0) | (H.CONCEAL_FIELDS if args.conceal_fields else 0) | (H.CONCEAL_IDR if args.conceal_idr else 0)
+    conceal |= H.CONCEAL_FIELDS | H.CONCEAL_LONE_FIELDS if args.conceal_lone_fields else 0
     conceal = conceal | H.CONCEAL_SLICES if conceal else int(args.conceal)
     srv = socket.socket()
     srv.setsockopt(socket.SOL_SOCKET, socket.SO_REUSEADDR, 1)
