@@ -1,7 +1,13 @@
 /*
  * examples/h264mi_decode.c -- the C ABI from plain C: decode an Annex-B file to raw I420 on the GPU.
  *
- *   h264mi_decode in.h264 out.yuv [frames_per_batch]
+ *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--conceal...] [--nv12 | --rgb]
+ *
+ * --nv12 / --rgb write NV12 / tight R, G, B bytes instead of I420: the frames are converted on the device (h264mi_batch_convert_device into a
+ * device buffer, matrix and range from each frame's own SPS) and copied to the host from there.  Those two calls are the only HIP this file
+ * needs; they are declared below, so it still builds without the HIP headers.
+ *
+ * The file includes nothing but include/h264mi.h and the C library.
  *
  * What a Go/cgo (or any FFI) caller does is exactly this sequence: cut the byte
  * stream at access units, hand whole access units to h264mi_decode_batch, read the frames back.
@@ -17,6 +23,13 @@
 #include <string.h>
 #include "h264mi.h"
 
+/* The three HIP runtime calls of --nv12 / --rgb, declared by hand so that the file builds with gcc and without the HIP headers
+ * (hip/hip_runtime_api.h: hipError_t and hipMemcpyKind are enums, int-sized in the C ABI; 0 = hipSuccess, hipMemcpyDeviceToHost = 2).  The program
+ * therefore links the HIP runtime itself (examples/Makefile), which the I420 path alone would not need: libh264mi.so brings it along anyway. */
+extern int hipMalloc(void **ptr, size_t size);
+extern int hipMemcpy(void *dst, const void *src, size_t size, int kind);
+extern int hipFree(void *ptr);
+
 static int fail(const char *what, int code) {
     fprintf(stderr, "%s failed: %d (%s)\n", what, code, h264mi_last_error_string());
     return 1;
@@ -24,10 +37,13 @@ static int fail(const char *what, int code) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields]\n", argv[0]);
+        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb]\n", argv[0]);
         return 2;
     }
-    int conceal = 0; /* --conceal (last argument): h264mi_config.conceal_errors */
+    int format = H264MI_FMT_I420; /* --nv12 / --rgb (last argument): the output format */
+    if (argc > 3 && !strcmp(argv[argc - 1], "--nv12")) format = H264MI_FMT_NV12, argc--;
+    else if (argc > 3 && !strcmp(argv[argc - 1], "--rgb")) format = H264MI_FMT_RGB24, argc--;
+    int conceal = 0; /* --conceal (last argument but for the format): h264mi_config.conceal_errors */
     if (argc > 3 && !strcmp(argv[argc - 1], "--conceal")) conceal = H264MI_CONCEAL_SLICES, argc--;
     /* --conceal-all: wholly lost reference frames and slices of field pictures are concealed too */
     else if (argc > 3 && !strcmp(argv[argc - 1], "--conceal-all")) conceal = H264MI_CONCEAL_SLICES | H264MI_CONCEAL_PICTURES | H264MI_CONCEAL_FIELDS, argc--;
@@ -81,6 +97,8 @@ int main(int argc, char **argv) {
     const size_t fsz = H264MI_I420_SIZE(sps.width, sps.height);
     uint8_t *frame = NULL;
     size_t frame_cap = 0;
+    void *dev = NULL; /* --nv12 / --rgb: the converted frames of a batch on the device */
+    size_t dev_cap = 0;
     long total = 0;
     int start = 0, pics = 0, seen_vcl = 0;
     /* parameter sets by id and the slices of the current picture, for the picture-boundary test */
@@ -149,10 +167,28 @@ int main(int argc, char **argv) {
                 h264mi_stream_frame_count(dec, 0, &k);
                 const size_t need = H264MI_I420_SIZE(info.coded_width, info.coded_height);
                 if (need > frame_cap) frame = (uint8_t *)realloc(frame, frame_cap = need);
-                for (int fidx = 0; fidx < k; fidx++) {
-                    if ((r = h264mi_frame_read(dec, 0, fidx, 1, frame, frame_cap)) != H264MI_OK) return fail("h264mi_frame_read", r);
-                    fwrite(frame, 1, fsz, out);
-                }
+                if (format != H264MI_FMT_I420) { /* one launch converts the batch; csc 0: matrix and range of each frame's own SPS, nearest chroma */
+                    size_t bytes = 0;
+                    /* the size query: with cap 0 the call resolves and sizes every frame, sets bytes, launches nothing and returns H264MI_ECAPACITY (or
+                     * H264MI_OK for an empty batch) -- the destination is never touched, it only has to be non-NULL, so before the device buffer exists
+                     * the host buffer's address stands in for it */
+                    r = h264mi_batch_convert_device(dec, 0, format, H264MI_CSC_AUTO, dev ? dev : (void *)frame, 0, &bytes);
+                    if (r != H264MI_OK && r != H264MI_ECAPACITY) return fail("h264mi_batch_convert_device", r);
+                    if (bytes > dev_cap) {
+                        if (dev) hipFree(dev);
+                        if (hipMalloc(&dev, dev_cap = bytes) != 0) return fail("hipMalloc", H264MI_ENOMEM);
+                    }
+                    if (bytes > frame_cap) frame = (uint8_t *)realloc(frame, frame_cap = bytes);
+                    if (bytes && (r = h264mi_batch_convert_device(dec, 0, format, H264MI_CSC_AUTO, dev, dev_cap, &bytes)) != H264MI_OK)
+                        return fail("h264mi_batch_convert_device", r);
+                    if ((r = h264mi_batch_sync(dec)) != H264MI_OK) return fail("h264mi_batch_sync", r); /* the conversion is asynchronous on the decoder's stream */
+                    if (bytes && hipMemcpy(frame, dev, bytes, 2 /* hipMemcpyDeviceToHost */) != 0) return fail("hipMemcpy", H264MI_EDEVICE);
+                    fwrite(frame, 1, bytes, out);
+                } else
+                    for (int fidx = 0; fidx < k; fidx++) {
+                        if ((r = h264mi_frame_read(dec, 0, fidx, 1, frame, frame_cap)) != H264MI_OK) return fail("h264mi_frame_read", r);
+                        fwrite(frame, 1, fsz, out);
+                    }
                 total += k;
                 start = i, pics = 0;
             }
@@ -166,6 +202,7 @@ int main(int argc, char **argv) {
         if ((conceal & H264MI_CONCEAL_PICTURES) && h264mi_decoder_concealed_pictures(dec, &cs) == H264MI_OK) fprintf(stderr, "concealed: %lld pictures\n", (long long)cs);
         if ((conceal & H264MI_CONCEAL_LONE_FIELDS) && h264mi_decoder_concealed_fields(dec, &cs) == H264MI_OK) fprintf(stderr, "concealed: %lld fields\n", (long long)cs);
     }
+    if (dev) hipFree(dev);
     h264mi_decoder_destroy(dec);
     fprintf(stderr, "%s: %ld frames %dx%d -> %s\n", h264mi_version(), total, sps.width, sps.height, argv[2]);
     return 0;

@@ -519,3 +519,53 @@ func (d *Decoder) PackBatch(stream int, dst unsafe.Pointer, capBytes int) (int, 
 	err := status(C.h264mi_batch_pack_device(d.h, C.int32_t(stream), dst, C.size_t(capBytes), &n))
 	return int(n), err
 }
+
+// Output formats and colour conversion (K7; include/h264mi.h "Output formats").  Like the rest of this file these wrappers were written
+// blind: no Go toolchain was at hand to compile them.
+const (
+	FmtI420  = 0 // H264MI_FMT_I420: what PackBatch writes; only OutputSize accepts it
+	FmtNV12  = 1 // H264MI_FMT_NV12
+	FmtRGB24 = 2 // H264MI_FMT_RGB24: h x w x 3 bytes R, G, B
+	FmtRGBP  = 3 // H264MI_FMT_RGBP: three planes R, G, B
+
+	CscAuto           = 0  // H264MI_CSC_AUTO: matrix and range of each frame's own SPS
+	CscBT601          = 1  // H264MI_CSC_BT601
+	CscBT709          = 2  // H264MI_CSC_BT709
+	CscFullRange      = 16 // H264MI_CSC_FULL_RANGE (with an explicit matrix only)
+	CscChromaBilinear = 32 // H264MI_CSC_CHROMA_BILINEAR (default: nearest)
+)
+
+// OutputSize: bytes of a w x h frame in `format`.
+func OutputSize(format, w, h int) (int, error) {
+	var n C.size_t
+	err := status(C.h264mi_output_size(C.int32_t(format), C.int32_t(w), C.int32_t(h), &n))
+	return int(n), err
+}
+
+// CscResolve: what `csc` stands for (matrix | CscFullRange | CscChromaBilinear) for a frame of width x height whose SPS carries
+// matrixCoefficients (2 when absent) and videoFullRange.
+func CscResolve(csc, matrixCoefficients, videoFullRange, width, height int) (int, error) {
+	var r C.int32_t
+	err := status(C.h264mi_csc_resolve(C.int32_t(csc), C.int32_t(matrixCoefficients), C.int32_t(videoFullRange), C.int32_t(width), C.int32_t(height), &r))
+	return int(r), err
+}
+
+// FrameColour: matrix_coefficients and video_full_range_flag of the SPS the frame was decoded under (2 and 0 where it carries none).
+func (d *Decoder) FrameColour(stream, frame int) (matrixCoefficients int, videoFullRange bool, err error) {
+	var m, f C.int32_t
+	err = status(C.h264mi_frame_colour(d.h, C.int32_t(stream), C.int32_t(frame), &m, &f))
+	return int(m), f != 0, err
+}
+
+// ConvertFrame converts one frame of the last batch into device memory `dst` (asynchronous on the decoder's stream).
+func (d *Decoder) ConvertFrame(stream, frame, format, csc int, dst unsafe.Pointer, capBytes int) error {
+	return status(C.h264mi_frame_convert_device(d.h, C.int32_t(stream), C.int32_t(frame), C.int32_t(format), C.int32_t(csc), dst, C.size_t(capBytes)))
+}
+
+// ConvertBatch is PackBatch for NV12 / RGB24 / planar RGB: every frame of the last batch (stream < 0: all streams, stream-major) cropped
+// and converted into device memory `dst` with one kernel launch; returns the byte count (also when capBytes is too small).
+func (d *Decoder) ConvertBatch(stream, format, csc int, dst unsafe.Pointer, capBytes int) (int, error) {
+	var n C.size_t
+	err := status(C.h264mi_batch_convert_device(d.h, C.int32_t(stream), C.int32_t(format), C.int32_t(csc), dst, C.size_t(capBytes), &n))
+	return int(n), err
+}

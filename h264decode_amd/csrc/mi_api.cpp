@@ -182,6 +182,7 @@ struct OutFrame { // a decoded picture of the current batch, with the geometry i
     int poc, frame_num, nal_ref_idc, idr, pic;
     int new_sequence; // IDR picture or memory_management_control_operation 5: picture order counts start over
     int pic2 = -1;    // a frame coded as two field pictures: `pic` / `pic2` are the first / second field's PicDesc (-1: decoded by an earlier batch, or never)
+    int matrix_coefficients = 2, video_full_range = 0; // of the picture's own SPS (E.2.1: "unspecified" / 0 where it does not carry them): h264mi_frame_colour
 };
 struct StreamState {
     h264mi_sps sps[32];
@@ -337,7 +338,12 @@ struct h264mi_decoder {
     size_t pack_cap[2] = {0, 0};
     hipEvent_t ev_pack[2] = {nullptr, nullptr};
     int pack_slot = 0;
-    hipEvent_t last_pack = nullptr; // the most recent pack launch: the reconstruction of a later pass may rewrite the frames it reads
+    hipEvent_t last_pack = nullptr; // the most recent pack or convert launch: the reconstruction of a later pass may rewrite the frames it reads
+    // K7 descriptor tables: the same discipline
+    ConvDesc *h_conv[2] = {nullptr, nullptr}, *d_conv[2] = {nullptr, nullptr};
+    size_t conv_cap[2] = {0, 0};
+    hipEvent_t ev_conv[2] = {nullptr, nullptr};
+    int conv_slot = 0;
     std::vector<float> launch_ms[4]; // duration of every launch of the last profiled pass, per kernel
 };
 
@@ -456,6 +462,9 @@ static void free_all(h264mi_decoder *d) {
         if (d->h_pack[i]) hipHostFree(d->h_pack[i]);
         if (d->d_pack[i]) hipFree(d->d_pack[i]);
         if (d->ev_pack[i]) hipEventDestroy(d->ev_pack[i]);
+        if (d->h_conv[i]) hipHostFree(d->h_conv[i]);
+        if (d->d_conv[i]) hipFree(d->d_conv[i]);
+        if (d->ev_conv[i]) hipEventDestroy(d->ev_conv[i]);
     }
     if (d->d_frames) hipFree(d->d_frames);
     if (d->d_tables) hipFree(d->d_tables);
@@ -1154,6 +1163,10 @@ static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const
         if (sh.nal_ref_idc && sh.adaptive_ref_pic_marking_mode_flag)
             for (int k = 0; k < sh.n_memory_management_control_operations; k++)
                 if (sh.memory_management_control_operation[k] == 5) of.new_sequence = 1;
+        if (sps.vui_parameters_present && sps.video_signal_type_present) {
+            of.video_full_range = sps.video_full_range;
+            if (sps.color_description_present) of.matrix_coefficients = sps.matrix_coefficients;
+        }
         if (sh.field_pic)
             s.pend_out = of, s.pend_sps_id = pps.sps_id, s.pend_pps_id = static_cast<int>(pps_id), s.pend_stale = false;
         else
@@ -2310,6 +2323,144 @@ extern "C" int32_t h264mi_batch_pack_device(h264mi_decoder *d, int32_t stream, v
     return pack_frames(d, frames, dst, cap, bytes);
 }
 
+// ---------------------------------------------------------------- output formats (K7): the rule of include/h264mi.h
+// (the reference has no output process: h264/server.go:113-166 stops at the parsed slice)
+extern "C" int32_t h264mi_output_size(int32_t format, int32_t w, int32_t h, size_t *bytes) {
+    if (!bytes || w <= 0 || h <= 0) return H264MI_EINVAL;
+    switch (format) {
+    case H264MI_FMT_I420:
+    case H264MI_FMT_NV12: *bytes = H264MI_I420_SIZE(w, h); return H264MI_OK;
+    case H264MI_FMT_RGB24:
+    case H264MI_FMT_RGBP: *bytes = static_cast<size_t>(3) * w * h; return H264MI_OK;
+    }
+    set_error("unknown output format %d", format);
+    return H264MI_EINVAL;
+}
+
+extern "C" int32_t h264mi_csc_resolve(int32_t csc, int32_t matrix_coefficients, int32_t video_full_range, int32_t width, int32_t height, int32_t *resolved) {
+    if (!resolved) return H264MI_EINVAL;
+    int matrix = csc & 15;
+    if (csc < 0 || (csc & ~(15 | H264MI_CSC_FULL_RANGE | H264MI_CSC_CHROMA_BILINEAR)) || matrix > H264MI_CSC_BT709) {
+        set_error("csc %d: not a matrix (0 auto, 1 BT.601, 2 BT.709) with H264MI_CSC_FULL_RANGE / H264MI_CSC_CHROMA_BILINEAR", csc);
+        return H264MI_EINVAL;
+    }
+    int full = csc & H264MI_CSC_FULL_RANGE;
+    if (matrix == H264MI_CSC_AUTO) {
+        if (full) {
+            set_error("H264MI_CSC_FULL_RANGE needs an explicit matrix: with H264MI_CSC_AUTO the range comes from the stream");
+            return H264MI_EINVAL;
+        }
+        switch (matrix_coefficients) {
+        case 1: matrix = H264MI_CSC_BT709; break;
+        case 5:
+        case 6: matrix = H264MI_CSC_BT601; break;
+        case 2: matrix = (width >= 1280 || height > 576) ? H264MI_CSC_BT709 : H264MI_CSC_BT601; break;
+        default:
+            set_error("matrix_coefficients %d of the stream is not BT.601 / BT.709 (1, 2, 5, 6): pass an explicit matrix (H264MI_CSC_BT601 / H264MI_CSC_BT709)", matrix_coefficients);
+            return H264MI_EUNSUPPORTED;
+        }
+        full = video_full_range ? H264MI_CSC_FULL_RANGE : 0;
+    }
+    *resolved = matrix | full | (csc & H264MI_CSC_CHROMA_BILINEAR);
+    return H264MI_OK;
+}
+
+extern "C" int32_t h264mi_frame_colour(h264mi_decoder *d, int32_t stream, int32_t frame, int32_t *matrix_coefficients, int32_t *video_full_range) {
+    uint8_t *p;
+    const OutFrame *of;
+    int r = frame_ptrs(d, stream, frame, &p, &of);
+    if (r != H264MI_OK) return r;
+    if (matrix_coefficients) *matrix_coefficients = of->matrix_coefficients;
+    if (video_full_range) *video_full_range = of->video_full_range;
+    return H264MI_OK;
+}
+
+// K7 over a list of frames: pack_frames' discipline (two pinned descriptor tables fenced by events, one launch on the decoder's stream, last_pack).
+// Every frame is resolved and sized before anything is launched.
+static int convert_frames(h264mi_decoder *d, const std::vector<std::pair<int, int>> &frames /* (stream, frame) */, int format, int csc, void *dst, size_t cap, size_t *bytes) {
+    if (format != H264MI_FMT_NV12 && format != H264MI_FMT_RGB24 && format != H264MI_FMT_RGBP) {
+        set_error("output format %d: not H264MI_FMT_NV12, _RGB24 or _RGBP", format);
+        return H264MI_EINVAL;
+    }
+    if (format == H264MI_FMT_NV12 && csc != 0) {
+        set_error("H264MI_FMT_NV12 converts nothing: csc must be 0, not %d", csc);
+        return H264MI_EINVAL;
+    }
+    int probe;
+    int r = h264mi_csc_resolve(csc, 1, 0, 16, 16, &probe); // is csc legal at all (whatever the frames are, and if there are none)
+    if (r != H264MI_OK) return r;
+    GUARD(d);
+    // every frame is resolved and sized before a descriptor table is taken: a call that fails launches nothing and waits for nothing
+    std::vector<ConvDesc> descs(frames.size());
+    size_t off = 0;
+    int hmax = 0;
+    for (size_t i = 0; i < frames.size(); i++) {
+        uint8_t *p;
+        const OutFrame *of;
+        int x0, y0, w, h, res = 0;
+        r = frame_ptrs(d, frames[i].first, frames[i].second, &p, &of);
+        if (r != H264MI_OK) return r;
+        crop_rect(of, 1, &x0, &y0, &w, &h);
+        if (format != H264MI_FMT_NV12) {
+            r = h264mi_csc_resolve(csc, of->matrix_coefficients, of->video_full_range, w, h, &res);
+            if (r != H264MI_OK) return r;
+        }
+        ConvDesc &cv = descs[i];
+        cv.src = reinterpret_cast<uint64_t>(p), cv.dst_off = off;
+        cv.W = of->wmb * 16, cv.H = of->hmb * 16, cv.x0 = x0, cv.y0 = y0, cv.w = w, cv.h = h;
+        cv.format = format, cv.pad = 0;
+        cv.cset = format == H264MI_FMT_NV12 ? 0 : 2 * ((res & 15) - 1) + ((res & H264MI_CSC_FULL_RANGE) ? 1 : 0);
+        cv.bilinear = (res & H264MI_CSC_CHROMA_BILINEAR) ? 1 : 0;
+        size_t sz = 0;
+        h264mi_output_size(format, w, h, &sz);
+        off += sz;
+        hmax = std::max(hmax, h);
+    }
+    if (bytes) *bytes = off;
+    if (off > cap) return H264MI_ECAPACITY;
+    if (frames.empty()) return H264MI_OK;
+    const int ps = d->conv_slot ^= 1;
+    if (!d->ev_conv[ps]) HIP_TRY(hipEventCreateWithFlags(&d->ev_conv[ps], hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(d->ev_conv[ps])); // the launch that used this table (two calls ago) has read it
+    if (frames.size() > d->conv_cap[ps]) {
+        if (d->h_conv[ps]) hipHostFree(d->h_conv[ps]);
+        if (d->d_conv[ps]) hipFree(d->d_conv[ps]);
+        d->h_conv[ps] = nullptr, d->d_conv[ps] = nullptr, d->conv_cap[ps] = 0;
+        const size_t n = std::max<size_t>(frames.size(), 64);
+        HIP_TRY(hipHostMalloc(&d->h_conv[ps], sizeof(ConvDesc) * n));
+        HIP_TRY(hipMalloc(&d->d_conv[ps], sizeof(ConvDesc) * n));
+        d->conv_cap[ps] = n;
+    }
+    memcpy(d->h_conv[ps], descs.data(), sizeof(ConvDesc) * frames.size());
+    if (bytes) *bytes = off;
+    if (off > cap) return H264MI_ECAPACITY;
+    if (frames.empty()) return H264MI_OK;
+    // (in order on the decoder's stream, which has waited for the reconstruction of the last executed pass: h264mi_batch_execute)
+    HIP_TRY(hipMemcpyAsync(d->d_conv[ps], d->h_conv[ps], sizeof(ConvDesc) * frames.size(), hipMemcpyHostToDevice, d->stream));
+    const int pairs_per_block = 8; // 1080p: 8 x 120 items of 2 x 16 pixels for 256 threads, 68 blocks per frame
+    hipLaunchKernelGGL(k_convert, dim3(static_cast<uint32_t>(frames.size()), ((hmax + 1) / 2 + pairs_per_block - 1) / pairs_per_block), dim3(256), 0, d->stream, d->d_conv[ps],
+                       static_cast<uint8_t *>(dst), pairs_per_block);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(d->ev_conv[ps], d->stream));
+    d->last_pack = d->ev_conv[ps];
+    return H264MI_OK;
+}
+
+extern "C" int32_t h264mi_frame_convert_device(h264mi_decoder *d, int32_t stream, int32_t frame, int32_t format, int32_t csc, void *dst, size_t cap) {
+    if (!d || !dst) return H264MI_EINVAL;
+    return convert_frames(d, {{stream, frame}}, format, csc, dst, cap, nullptr);
+}
+
+extern "C" int32_t h264mi_batch_convert_device(h264mi_decoder *d, int32_t stream, int32_t format, int32_t csc, void *dst, size_t cap, size_t *bytes) {
+    if (!d || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    std::vector<std::pair<int, int>> frames;
+    const Stage &g = d->stage[d->exec];
+    for (int si = 0; si < static_cast<int>(g.out.size()); si++)
+        if (stream < 0 || stream == si)
+            for (int f = 0; f < static_cast<int>(g.out[si].size()); f++) frames.push_back({si, f});
+    return convert_frames(d, frames, format, csc, dst, cap, bytes);
+}
+
 extern "C" int32_t h264mi_frame_read_mbrecs(h264mi_decoder *d, int32_t stream, int32_t frame, uint8_t *rec, size_t cap) {
     if (!d || !rec || stream < 0 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
     GUARD(d);
@@ -2351,6 +2502,13 @@ extern "C" int32_t h264mi_frame_read_mbmv1(h264mi_decoder *d, int32_t stream, in
 
 #if defined(H264MI_TEST_HOOKS)
 // ---- test and measurement hooks: built into libh264mi_hooks.so only (csrc/Makefile); the product library exports the ABI of include/h264mi.h and nothing else ----
+// 1 while a pack / convert launch is recorded that the next pass has to wait for before it rewrites frames (last_pack), else 0
+extern "C" int32_t h264mi_internal_pack_pending(h264mi_decoder *d, int32_t *pending) {
+    if (!d || !pending) return H264MI_EINVAL;
+    *pending = d->last_pack ? 1 : 0;
+    return H264MI_OK;
+}
+
 // Not part of the public ABI: fills every intermediate buffer (macroblock records, coefficient blocks, row state) with
 // 0xFF so that a test can prove that no kernel depends on what an earlier batch -- or the allocator -- left there.
 extern "C" int32_t h264mi_internal_poison(h264mi_decoder *d) {

@@ -134,6 +134,18 @@ typedef struct {
     uint32_t W, H, x0, y0, w, h;
 } PackDesc;
 extern "C" __global__ void k_pack(const PackDesc *descs, uint8_t *dst, int rows_per_block);
+// K7 (k_convert.hip): crop + convert a list of frames to NV12 / RGB24 / planar RGB by the integer rule of include/h264mi.h;
+// grid = (frames, ceil(ceil(h_max / 2) / pairs_per_block)), block = 256; a thread owns two luma rows x 16 columns
+typedef struct {
+    uint64_t src;     // as PackDesc
+    uint64_t dst_off; // byte offset of the converted frame in the destination buffer
+    uint32_t W, H, x0, y0, w, h;
+    uint32_t format;   // H264MI_FMT_NV12 / _RGB24 / _RGBP
+    uint32_t cset;     // row of the coefficient table: 2 * (matrix - 1) + full range (unused for NV12)
+    uint32_t bilinear; // chroma upsampling: 0 nearest, 1 bilinear (unused for NV12)
+    uint32_t pad;
+} ConvDesc;
+extern "C" __global__ void k_convert(const ConvDesc *descs, uint8_t *dst, int pairs_per_block);
 
 #ifndef MI_INTRA_WAVES
 #define MI_INTRA_WAVES 16 /* 1024 threads, 128 VGPRs per wavefront: the kernels need 120 once nothing lane-dependent is hoisted out of the macroblock loop */

@@ -201,6 +201,18 @@ CONCEAL_SLICES, CONCEAL_PICTURES, CONCEAL_FIELDS = 1, 2, 4  # bits of h264mi_con
 CONCEAL_IDR = 16                         # H264MI_CONCEAL_IDR (bit 8 is unassigned)
 CONCEAL_LONE_FIELDS = 64                 # H264MI_CONCEAL_LONE_FIELDS (only together with CONCEAL_SLICES | CONCEAL_FIELDS; bit 32 is unassigned)
 CONCEAL_MAX_GAP = 16                     # H264MI_CONCEAL_MAX_GAP: the longest run of lost frames that is concealed
+FMT_I420, FMT_NV12, FMT_RGB24, FMT_RGBP = 0, 1, 2, 3  # H264MI_FMT_*: output formats of convert_frame / convert_batch / frames_tensor
+CSC_AUTO, CSC_BT601, CSC_BT709 = 0, 1, 2              # H264MI_CSC_*: the matrix (AUTO: from each frame's own SPS) ...
+CSC_FULL_RANGE, CSC_CHROMA_BILINEAR = 16, 32          # ... | full range (explicit matrix only) | bilinear chroma upsampling (default: nearest)
+_FMT_NAMES = {"i420": FMT_I420, "nv12": FMT_NV12, "rgb24": FMT_RGB24, "rgbp": FMT_RGBP}
+
+
+def _fmt(fmt):
+    if isinstance(fmt, str):
+        if fmt.lower() not in _FMT_NAMES:
+            raise H264MIError(-1, "unknown output format %r (i420, nv12, rgb24, rgbp)" % (fmt,))
+        return _FMT_NAMES[fmt.lower()]
+    return int(fmt)
 
 
 def _frames_with_headroom(frames_per_batch, conceal_errors):
@@ -232,6 +244,7 @@ class Decoder:
         check(L.h264mi_decoder_create(ctypes.byref(cfg), ctypes.byref(self._h)))
         self._L = L
         self.max_streams = max_streams
+        self.device = device
         self._keep = None
 
     def close(self):
@@ -408,6 +421,57 @@ class Decoder:
         n = ctypes.c_size_t(0)
         check(self._L.h264mi_batch_pack_device(self._h, stream, dst_ptr, cap, ctypes.byref(n)))
         return n.value
+
+    @staticmethod
+    def output_size(fmt, w, h):
+        """Bytes of a w x h frame in `fmt` ("i420", "nv12", "rgb24", "rgbp" or an H264MI_FMT_* value): h264mi_output_size."""
+        n = ctypes.c_size_t(0)
+        check(_lib.load().h264mi_output_size(_fmt(fmt), w, h, ctypes.byref(n)))
+        return n.value
+
+    def frame_colour(self, stream, frame):
+        """(matrix_coefficients, video_full_range) of the SPS the frame was decoded under -- (2, 0) where it carries none: what CSC_AUTO resolves from."""
+        m, f = ctypes.c_int32(0), ctypes.c_int32(0)
+        check(self._L.h264mi_frame_colour(self._h, stream, frame, ctypes.byref(m), ctypes.byref(f)))
+        return m.value, f.value
+
+    def convert_frame(self, stream, frame, dst_ptr, cap, fmt, csc=0):
+        """K7 for one frame of the last executed batch: cropped and converted to `fmt` into the DEVICE buffer at dst_ptr (asynchronous on the
+        decoder's stream).  csc: CSC_AUTO / CSC_BT601 / CSC_BT709, | CSC_FULL_RANGE (explicit matrix only), | CSC_CHROMA_BILINEAR; 0 for "nv12"."""
+        check(self._L.h264mi_frame_convert_device(self._h, stream, frame, _fmt(fmt), csc, dst_ptr, cap))
+
+    def convert_batch(self, dst_ptr, cap, fmt, csc=0, stream=-1):
+        """K7 in one launch: every frame of the last executed batch (of one stream, or of all streams, stream-major) cropped and converted to
+        `fmt`, back to back in the DEVICE buffer at dst_ptr -- pack_batch's contract.  Returns the number of bytes."""
+        n = ctypes.c_size_t(0)
+        check(self._L.h264mi_batch_convert_device(self._h, stream, _fmt(fmt), csc, dst_ptr, cap, ctypes.byref(n)))
+        return n.value
+
+    def frames_tensor(self, stream, fmt="rgbp", csc=0):
+        """The frames of `stream` of the last executed batch as one torch uint8 tensor on the decoder's device: [n, 3, h, w] ("rgbp"), [n, h, w, 3]
+        ("rgb24") or [n, H264MI_I420_SIZE(w, h)] ("nv12"), converted by one K7 launch.  Raises ValueError if the stream's frames differ in display size.
+        Ordering, both ways, by synchronising (no event is involved): the tensor comes from torch's caching allocator on torch's current stream, which may
+        hand back a block that work still queued on that stream reads, and the conversion writes it on the decoder's stream -- so torch's current
+        stream is SYNCHRONISED after the allocation and before the launch; and the decoder's stream is SYNCHRONISED (sync()) before the method returns,
+        so the tensor is complete for any torch stream.  A caller who cannot afford the two waits allocates for themselves and calls convert_batch."""
+        import torch
+        f = _fmt(fmt)
+        n = self.frame_count(stream)
+        infos = [self.frame_info(stream, i) for i in range(n)]
+        sizes = {(fi.width, fi.height) for fi in infos}
+        if len(sizes) > 1:
+            raise ValueError("the frames of stream %d differ in display size (%s): convert them with convert_frame / convert_batch" % (stream, sorted(sizes)))
+        w, h = sizes.pop() if sizes else (0, 0)
+        shape = {FMT_NV12: (n, self.i420_size(w, h)), FMT_RGB24: (n, h, w, 3), FMT_RGBP: (n, 3, h, w)}.get(f)
+        if shape is None:
+            raise H264MIError(-1, "frames_tensor: format %r is not nv12, rgb24 or rgbp" % (fmt,))
+        out = torch.empty(shape, dtype=torch.uint8, device="cuda:%d" % self.device)
+        if n:
+            torch.cuda.current_stream(out.device).synchronize()  # whatever still uses a recycled block has finished before K7 writes it
+            got = self.convert_batch(out.data_ptr(), out.numel(), f, csc, stream)
+            assert got == out.numel()
+            self.sync()
+        return out
 
     def output_order(self, stream=0):
         """Indices (decoding order) of the stream's frames of the last batch in display order: ascending PicOrderCnt per

@@ -386,6 +386,64 @@ int32_t h264mi_frame_pack_device(h264mi_decoder *dec, int32_t stream, int32_t fr
  * stream = -1, stream-major) in decoding order, back to back.  *bytes receives the total size (also on H264MI_ECAPACITY). */
 int32_t h264mi_batch_pack_device(h264mi_decoder *dec, int32_t stream, void *dst_device, size_t cap, size_t *bytes);
 
+/* ---- Output formats (K7): NV12 and RGB on the device.  The reference has no output process (h264/server.go:113-166 stops at the parsed slice) ----
+ * A converted frame is a function of the tight I420 frame h264mi_frame_read(crop = 1) returns, and of nothing else: Y[h][w], Cb[hc][wc], Cr[hc][wc] with
+ * wc = ceil(w / 2), hc = ceil(h / 2) (chroma from (crop_x / 2, crop_y / 2) of the coded plane, as K6 takes it; 128 in monochrome streams, so RGB comes
+ * out grey and the NV12 chroma plane is 128).  Everything below is integer arithmetic; this comment is the contract.
+ *   H264MI_FMT_NV12   w * h luma bytes, then hc rows of wc (Cb, Cr) byte pairs                  H264MI_I420_SIZE(w, h) bytes
+ *   H264MI_FMT_RGB24  h x w x 3 bytes R, G, B, tight                                           3 * w * h bytes
+ *   H264MI_FMT_RGBP   three tight h x w planes R, G, B (torch's CHW)                            3 * w * h bytes
+ * Any other format is H264MI_EINVAL (H264MI_FMT_I420 is what the pack calls above write; only h264mi_output_size accepts it).
+ * csc, a small bit set: the matrix in the low four bits (H264MI_CSC_AUTO, _BT601, _BT709), H264MI_CSC_FULL_RANGE (only with an explicit matrix: with AUTO
+ * the range comes from the stream), H264MI_CSC_CHROMA_BILINEAR (default: nearest).  For NV12 csc must be 0 -- nothing is converted.  Anything else is
+ * H264MI_EINVAL.
+ * AUTO is resolved per frame from the SPS that frame was decoded under: video_full_range_flag is the range (0 when the VUI or video_signal_type is absent,
+ * E.2.1); matrix_coefficients (2, "unspecified", when absent) 1 gives BT.709, 5 and 6 give BT.601, 2 gives BT.709 when the display width is >= 1280 or the
+ * display height is > 576 and BT.601 otherwise; every other value (0 GBR, 4, 7, 8 YCgCo, 9 ...) is H264MI_EUNSUPPORTED, and the message names the value and
+ * says that an explicit matrix can be passed.  An explicit matrix never looks at the stream.
+ * Coefficients: with (Kr, Kb) = (0.299, 0.114) for BT.601 and (0.2126, 0.0722) for BT.709, Kg = 1 - Kr - Kb, sy = 255 / 219 and sc = 255 / 224 for limited
+ * range (both 1 for full range):  cy = round(8192 sy), crv = round(8192 * 2 (1 - Kr) sc), cgu = round(8192 * 2 Kb (1 - Kb) / Kg * sc),
+ * cgv = round(8192 * 2 Kr (1 - Kr) / Kg * sc), cbu = round(8192 * 2 (1 - Kb) sc) -- the four sets are H264MI_CSC_COEFFS below.
+ * Arithmetic: y' = Y - 16 for limited range, Y for full range; u = cb - 128, v = cr - 128 with cb, cr the upsampled 8-bit chroma samples of the pixel;
+ * 32-bit integers, >> is an arithmetic shift (floor), clip is to 0 .. 255:
+ *   R = clip((cy y' + crv v + 4096) >> 13)    G = clip((cy y' - cgu u - cgv v + 4096) >> 13)    B = clip((cy y' + cbu u + 4096) >> 13)
+ * Chroma of luma position (x, y), k = x >> 1, j = y >> 1.  Nearest: cb = Cb[j][k].  Bilinear: the 4:2:0 siting of chroma_sample_loc_type 0 (co-sited with
+ * even luma columns, midway between luma rows 2j and 2j + 1): Hrow(r) = 2 C[r][k] for even x, C[r][k] + C[r][min(k + 1, wc - 1)] for odd x;
+ * j' = max(j - 1, 0) for even y, min(j + 1, hc - 1) for odd y; c = (3 Hrow(j) + Hrow(j') + 4) >> 3 (weights sum to 8, one rounding).  The clamps are at the
+ * edges of the DISPLAY chroma plane: coded samples outside the crop rectangle are never read.  The rule is applied to frames as they are, whether they
+ * were coded as frame or field pictures: interlace-aware upsampling, and chroma_sample_loc_type other than 0, are out of scope. */
+#define H264MI_FMT_I420 0
+#define H264MI_FMT_NV12 1
+#define H264MI_FMT_RGB24 2
+#define H264MI_FMT_RGBP 3
+#define H264MI_CSC_AUTO 0
+#define H264MI_CSC_BT601 1
+#define H264MI_CSC_BT709 2
+#define H264MI_CSC_FULL_RANGE 16
+#define H264MI_CSC_CHROMA_BILINEAR 32
+/* {cy, crv, cgu, cgv, cbu}: BT.601 limited, BT.601 full, BT.709 limited, BT.709 full */
+#define H264MI_CSC_COEFFS { \
+    {9539, 13075, 3209, 6660, 16525}, \
+    {8192, 11485, 2819, 5850, 14516}, \
+    {9539, 14686, 1747, 4366, 17305}, \
+    {8192, 12901, 1535, 3835, 15201}}
+/* Bytes of a w x h frame in `format` (H264MI_FMT_I420 too).  Pure: no decoder, no device. */
+int32_t h264mi_output_size(int32_t format, int32_t w, int32_t h, size_t *bytes);
+/* The AUTO rule above as a pure function: *resolved = the matrix (H264MI_CSC_BT601 / _BT709) | H264MI_CSC_FULL_RANGE or 0 | the chroma bit of csc, for a
+ * frame of width x height display samples whose SPS carries matrix_coefficients (2 when absent) and video_full_range (0 when absent).  H264MI_EINVAL for a
+ * csc that is not legal, H264MI_EUNSUPPORTED for AUTO over a matrix_coefficients value outside 1, 2, 5, 6. */
+int32_t h264mi_csc_resolve(int32_t csc, int32_t matrix_coefficients, int32_t video_full_range, int32_t width, int32_t height, int32_t *resolved);
+/* matrix_coefficients and video_full_range_flag a frame of the last batch was coded under (its own SPS: a batch may span a change of them); 2 and 0
+ * where the SPS does not carry them.  What AUTO resolves from. */
+int32_t h264mi_frame_colour(h264mi_decoder *dec, int32_t stream, int32_t frame, int32_t *matrix_coefficients, int32_t *video_full_range);
+/* One frame of the last executed batch, cropped and converted on the device (K7) into the DEVICE buffer dst_device; cap >= h264mi_output_size of its
+ * display size.  Asynchronous on the decoder's stream, like h264mi_frame_pack_device. */
+int32_t h264mi_frame_convert_device(h264mi_decoder *dec, int32_t stream, int32_t frame, int32_t format, int32_t csc, void *dst_device, size_t cap);
+/* The same for every frame of the last executed batch in ONE launch -- h264mi_batch_pack_device's contract: frames of stream `stream` (or of all streams
+ * when stream = -1, stream-major) in decoding order, back to back; *bytes receives the total size (also on H264MI_ECAPACITY).  All frames are resolved
+ * before anything is launched: one frame AUTO cannot resolve fails the call (H264MI_EUNSUPPORTED) with nothing written. */
+int32_t h264mi_batch_convert_device(h264mi_decoder *dec, int32_t stream, int32_t format, int32_t csc, void *dst_device, size_t cap, size_t *bytes);
+
 /* Debug / test access to the intermediate macroblock records of a frame (host copy).
  * rec: 128 bytes per MB (layout: h264decode_amd/csrc/mi_types.h struct MbRec). */
 int32_t h264mi_frame_read_mbrecs(h264mi_decoder *dec, int32_t stream, int32_t frame, uint8_t *rec, size_t cap);
@@ -432,7 +490,7 @@ const char *h264mi_last_error_string(void);
 const char *h264mi_version(void);
 
 /* Exported but NOT part of the ABI (test hooks of this repository's own suite, may change or vanish): h264mi_internal_poison,
- * h264mi_internal_deblock_plan, h264mi_internal_band_plan, h264mi_internal_deblock_phase_clocks, h264mi_internal_vlc_selftest. */
+ * h264mi_internal_deblock_plan, h264mi_internal_band_plan, h264mi_internal_pack_pending, h264mi_internal_deblock_phase_clocks, h264mi_internal_vlc_selftest. */
 
 #ifdef __cplusplus
 }

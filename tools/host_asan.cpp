@@ -137,6 +137,12 @@ static void client(int iters, unsigned seed) {
                     if (h264mi_frame_get_info(dec, s, f, &fi) != 0) continue;
                     if (rng() % 4 == 0) h264mi_frame_read(dec, s, f, rng() & 1, pix.data(), rng() % 5 ? pix.size() : 1000);
                 }
+                // K7's host side (descriptor tables, AUTO per frame, sizes, capacity); the choices come from nf, not from rng(): the sequence above stays what it was
+                size_t conv = 0;
+                int32_t mc = 0, fr = 0;
+                h264mi_frame_colour(dec, s, nf / 2, &mc, &fr);
+                h264mi_batch_convert_device(dec, (nf & 1) ? s : -1, 1 + nf % 3, nf % 3 ? (nf & 2) * 16 : 0, pix.data(), (nf & 4) ? pix.size() : 1000, &conv);
+                h264mi_frame_convert_device(dec, s, nf - 1, 3, H264MI_CSC_BT601 | H264MI_CSC_FULL_RANGE, pix.data(), pix.size());
                 if (rng() % 13 == 0) h264mi_stream_reset(dec, s);
             }
             if (rng() % 29 == 0) h264mi_decoder_reset(dec);
