@@ -306,6 +306,7 @@ struct h264mi_decoder {
     uint8_t *d_frames = nullptr;
     DevTables *d_tables = nullptr, *h_tables = nullptr;
     int n_scaling = 0;
+    uint32_t scaling_used[MI_STAGES] = {}; // bit i: the batch of that staging set refers to DevTables::scaling[i]
     bool tables_dirty = true;
     size_t ent_lds_pad = 0; // dynamic LDS requested (and not used) by k_entropy: caps its wavefronts per CU, see h264mi_decoder_create
     bool conceal = false; // h264mi_config.conceal_errors: lost macroblocks of concealable pictures are copied from a reference picture (k_conceal)
@@ -948,12 +949,27 @@ extern "C" int32_t h264mi_slice_starts_picture(const h264mi_sps *sps, const h264
 static int scaling_set_for(h264mi_decoder *d, const h264mi_pps &p) {
     ScalingSet tmp;
     build_scaling(p.scaling_list_4x4, p.scaling_list_8x8, &tmp);
+    uint32_t &mine = d->scaling_used[d->prep];
     for (int i = 0; i < d->n_scaling; i++)
-        if (!memcmp(&d->h_tables->scaling[i], &tmp, sizeof(tmp))) return i;
-    if (d->n_scaling >= MI_MAX_SCALING_SETS) return -1;
-    d->h_tables->scaling[d->n_scaling] = tmp;
+        if (!memcmp(&d->h_tables->scaling[i], &tmp, sizeof(tmp))) {
+            mine |= 1u << i;
+            return i;
+        }
+    // a new matrix: the next free entry, or one that only batches which have finished referred to (the batch of the other staging set
+    // may still be executing: its entries stay as they are -- the upload rewrites them with the bytes they hold)
+    int at = d->n_scaling < MI_MAX_SCALING_SETS ? d->n_scaling : -1;
+    if (at < 0) {
+        uint32_t busy = 0;
+        for (int st = 0; st < MI_STAGES; st++) busy |= d->scaling_used[st];
+        for (int i = 0; i < MI_MAX_SCALING_SETS && at < 0; i++)
+            if (!(busy >> i & 1)) at = i;
+        if (at < 0) return -1;
+    } else
+        d->n_scaling++;
+    d->h_tables->scaling[at] = tmp;
     d->tables_dirty = true;
-    return d->n_scaling++;
+    mine |= 1u << at;
+    return at;
 }
 
 // 8.2.5.2 decoding process for gaps in frame_num (h264/sps.go:311-312 parses the flag, nothing in the reference uses it): a
@@ -1549,6 +1565,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
         (void)harvest_status(d, g); // a batch nobody synchronised on: its failures still mark their streams (need_idr) before this parse
     }
     g.prepared = false, g.executed = false;
+    d->scaling_used[d->prep] = 0; // (the batch that filled this staging set before has finished: its LevelScale sets may go to new matrices)
     g.n_slices = g.n_pics = 0;
     g.bits_used = 0, g.mb_used = 0, g.wmb_max = 0, g.hmb_max = 0, g.mbs_max = 0;
     g.map_cursor = g.bits_end = 0;

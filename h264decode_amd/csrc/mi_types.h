@@ -191,7 +191,9 @@ typedef struct {
     uint16_t ls8[2][6][64];
 } ScalingSet;
 
-#define MI_MAX_SCALING_SETS 8
+/* distinct LevelScale sets the batches in flight may use between them (a set no batch in flight uses is given to the next new matrix:
+ * mi_api.cpp scaling_set_for); at most 32: one bit each in h264mi_decoder::scaling_used */
+#define MI_MAX_SCALING_SETS 32
 /* CAVLC code tables in compact form (they live in LDS while a CAVLC slice is decoded): a code word is looked up by the number of its leading
  * zeros -- capped at the longest code of the table, L -- and the S bits behind its first one: entry [min(clz, L) << S | next S bits] =
  * len << 8 | value (value: total_coeff << 2 | trailing_ones for coeff_token), 0: no such code.  mi_api.cpp derives the tables from direct-indexed

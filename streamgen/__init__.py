@@ -21,7 +21,8 @@ class Params(ctypes.Structure):
         ("idr_long_term", ctypes.c_int), ("nonref_period", ctypes.c_int), ("slice_qp_delta", ctypes.c_int), ("bframes", ctypes.c_int),
         ("direct_temporal", ctypes.c_int), ("weighted_bipred", ctypes.c_int), ("bskip_permille", ctypes.c_int),
         ("motion_x4", ctypes.c_int), ("motion_y4", ctypes.c_int), ("interlace_sps", ctypes.c_int), ("fn_gap_period", ctypes.c_int), ("fn_gap_declared", ctypes.c_int),
-        ("b_pyramid", ctypes.c_int), ("slice_groups", ctypes.c_int), ("fmo_type", ctypes.c_int), ("aso", ctypes.c_int), ("field_pics", ctypes.c_int), ("poc_bottom_delta", ctypes.c_int), ("mono", ctypes.c_int)]
+        ("b_pyramid", ctypes.c_int), ("slice_groups", ctypes.c_int), ("fmo_type", ctypes.c_int), ("aso", ctypes.c_int), ("field_pics", ctypes.c_int), ("poc_bottom_delta", ctypes.c_int), ("mono", ctypes.c_int),
+        ("wp_range", ctypes.c_int), ("poc_step", ctypes.c_int), ("mv_reach", ctypes.c_int), ("mv_margin", ctypes.c_int), ("contrast", ctypes.c_int)]
 
 
 def build(force=False):
@@ -47,6 +48,7 @@ def lib():
         _lib.sg_source_frame.argtypes = [ctypes.POINTER(Params), ctypes.c_int, ctypes.c_void_p]
         _lib.sg_last_pocs.argtypes = [ctypes.c_void_p, ctypes.c_int]
         _lib.sg_last_features.restype = ctypes.c_uint32
+        _lib.sg_last_ranges.argtypes = [ctypes.c_void_p, ctypes.c_int]
     return _lib
 
 
@@ -88,6 +90,26 @@ def last_features():
     """Bit set of the picture-management syntax the last encode() call emitted (see sg.h)."""
     return int(lib().sg_last_features())
 
+
+RANGE_NAMES = (
+    "mvd_max_x", "mvd_max_y", "outside_left", "outside_right", "outside_top", "outside_bottom",
+    "half1_clip0", "half1_clip255", "halfj_clip0", "halfj_clip255",
+    "w1_clip0", "w1_clip255", "w2_clip0", "w2_clip255", "denom_mask",
+    "w_min", "w_max", "o_min", "o_max", "neg_weight", "odd_neg_offsets",
+    "tbtd_clipped", "dsf_clipped", "implicit_fallback", "implicit_pairs", "implicit_w1_min", "implicit_w1_max", "scaling_forms", "guard_zeroed", "ref_twice")
+
+
+def last_ranges():
+    """What the last encode() call really reached (the SG_R_* counters of sg.h), as a dict."""
+    n = lib().sg_last_ranges(None, 0)
+    assert n == len(RANGE_NAMES), (n, len(RANGE_NAMES))
+    out = np.zeros(n, dtype=np.int32)
+    lib().sg_last_ranges(out.ctypes.data, n)
+    return {k: int(v) for k, v in zip(RANGE_NAMES, out)}
+
+
+SCALING_FORMS = dict(absent_first=1, absent_next=2, use_default=4, cut_short=8, wrap=16, entry_1=32, entry_255=64, full=128,
+                     sps_matrix=256, pps_rule_a=512, pps_rule_b=1024, pps_six_lists=2048)
 
 # Named recipes (SURVEY.md 8d).  Sizes may be overridden for small test cases.
 RECIPES = {

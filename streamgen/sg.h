@@ -39,7 +39,9 @@ typedef struct {
     int skip_permille;      /* probability of P_Skip */
     int sub8x8_permille;    /* probability of P_8x8 (with random sub-partitions) / 16x8 / 8x16 */
     int weighted_pred;      /* explicit weighted prediction in P slices */
-    int scaling_matrix;     /* 0 flat, 1 = send default (non-flat) scaling lists in the SPS (High) */
+    int scaling_matrix;     /* 0 flat, 1 = send default (non-flat) scaling lists in the SPS (High), 2 = coded lists in the SPS, 3 = every
+                             * parameter-set pair (one per IDR picture) has a new matrix in the PPS, in turn after an SPS with a matrix (fall-back rule B
+                             * of Table 7-2) and after one without (rule A); under every third PPS the 8x8 transform is off and the matrix has six lists */
     int noise;              /* amplitude of the uniform source noise */
     uint32_t seed;
     int long_start_code;    /* 1: 4-byte start codes everywhere; 0: 3-byte for non-parameter-set NALs */
@@ -93,6 +95,24 @@ typedef struct {
      * ChromaArrayType 0 column of Table 9-4 (CABAC: no chroma bins), no chroma residual, 256 samples per I_PCM macroblock, no chroma weights.  The
      * reconstruction carries chroma planes of 128 (what a decoder puts out for a 4:2:0 display). */
     int mono;
+    /* value-range stimulus: all 0 = the streams of before, byte for byte.
+     * wp_range 1: every slice with a pred_weight_table() draws its own two denominators from 0..7 and, per list entry and
+     * separately for luma and chroma, a flag, a weight from -128..127 and an offset from -128..127, biased to the ends
+     * (-128, -1, 0, 1, 127, 2^denom and its neighbours); weights of two lists keep -128 <= w0 + w1 <= (denom == 7 ? 127 : 128)
+     * for every pair of entries (7.4.3.2).  Needs weighted_pred (P slices) / weighted_bipred 1 (B slices) to show.
+     * 2: the same, and list modification puts one reference picture at two indices of RefPicList0 (P frame pictures with two or more active entries). */
+    int wp_range;
+    /* N > 1 (pic_order_cnt_type 0 / 1): PicOrderCnt advances by 2 * N per frame; the SPS then carries a 16-bit pic_order_cnt_lsb,
+     * so that an anchor several B pictures ahead stays within MaxPicOrderCntLsb / 2 of the picture before it */
+    int poc_step;
+    /* mv_reach r > 0: the random candidate of the motion search comes from -r..r quarter samples (default 64), is drawn at the
+     * ends of that range one time in four per component and is taken without a search one time in five; mv_margin m > 0: a block
+     * may lie up to m samples outside the picture (default 24).  Vectors stay within -8192..8191 horizontally and -2048..2047
+     * vertically (field pictures: -1024..1023), the range of levels 3.1 to 5.1 (Table A-1) */
+    int mv_reach, mv_margin;
+    /* 1: the source is a hard 0 / 255 pattern: per 16x16 region of the (moving) scene flat, stripes or checks of period 1..3 samples,
+     * in luma and in both chroma planes */
+    int contrast;
 } sg_params;
 
 void sg_default_params(sg_params *p);
@@ -110,6 +130,34 @@ int sg_last_pocs(int32_t *dst, int cap);
  * modification_of_pic_nums_idc 0/1/2, bit 11 = a long-term picture in an active reference list, bit 12 = non-reference
  * picture, bit 13 = slice_qp_delta != 0, bit 14 = pic_order_cnt_type 1 with delta_pic_order_cnt[0] != 0 */
 uint32_t sg_last_features(void);
+/* what the last sg_encode() call really reached, counted where the generator builds the prediction that goes into its
+ * reconstruction (never in the motion search).  Returns the number of counters; dst receives up to cap of them. */
+enum {
+    SG_R_MVD_X, SG_R_MVD_Y,                       /* largest |mvd| per component (quarter samples) */
+    SG_R_OUT_LEFT, SG_R_OUT_RIGHT, SG_R_OUT_TOP, SG_R_OUT_BOTTOM, /* predicted blocks whose whole (w + 5) x (h + 5) luma window lies outside the picture */
+    SG_R_HALF1_CLIP0, SG_R_HALF1_CLIP255,         /* luma half samples b / h (one 6-tap filter) clipped at 0 / at 255 */
+    SG_R_HALFJ_CLIP0, SG_R_HALFJ_CLIP255,         /* the centre half sample j (two filters) clipped */
+    SG_R_W1_CLIP0, SG_R_W1_CLIP255,               /* explicitly weighted samples clipped, blocks with one list */
+    SG_R_W2_CLIP0, SG_R_W2_CLIP255,               /* ... blocks with two lists */
+    SG_R_DENOM_MASK,                              /* bit d: a block was predicted with log2 denominator d (luma or chroma) */
+    SG_R_W_MIN, SG_R_W_MAX, SG_R_O_MIN, SG_R_O_MAX, /* smallest / largest explicit weight and offset of a block actually predicted */
+    SG_R_NEG_WEIGHT,                              /* blocks predicted with a negative explicit weight */
+    SG_R_ODD_NEG_OFFSETS,                         /* two-list blocks with o0 + o1 odd and negative */
+    SG_R_TBTD_CLIPPED, SG_R_DSF_CLIPPED,          /* 8.4.1.2.3: tb or td clipped; DistScaleFactor clipped */
+    SG_R_IMPLICIT_FALLBACK, SG_R_IMPLICIT_PAIRS,  /* implicit two-list blocks that fell back to 32 / 32, and those that did not */
+    SG_R_IMPLICIT_W1_MIN, SG_R_IMPLICIT_W1_MAX,   /* ... smallest and largest w1 of the latter */
+    SG_R_SCALING_FORMS,                           /* scaling-list forms written: the SG_SF_* bits */
+    SG_R_GUARD_ZEROED,                            /* levels set to 0 because they would have left the 16-bit range of 8.5.12 */
+    SG_R_REF_TWICE,                               /* wp_range 2: slices' lists with one picture at two indices */
+    SG_R_COUNT
+};
+enum {
+    SG_SF_ABSENT_FIRST = 1,   /* list 0, 3, 6 or 7 absent (falls back to a Default list or to the SPS) */
+    SG_SF_ABSENT_NEXT = 2,    /* list 1, 2, 4 or 5 absent (takes the list before it) */
+    SG_SF_USE_DEFAULT = 4, SG_SF_CUT_SHORT = 8, SG_SF_WRAP = 16, SG_SF_ENTRY_1 = 32, SG_SF_ENTRY_255 = 64, SG_SF_FULL = 128,
+    SG_SF_SPS_MATRIX = 256, SG_SF_PPS_RULE_A = 512, SG_SF_PPS_RULE_B = 1024, SG_SF_PPS_SIX_LISTS = 2048
+};
+int sg_last_ranges(int32_t *dst, int cap);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,10 @@ typedef struct {
     int qp, prev_dqp_nz, slice_id, slice_type, skip_run, init_idc, nref_active;
     int ls4[6][6][16], ls8[2][6][64];
     uint8_t s4[6][16], s8[2][64]; /* scaling lists, zig-zag */
+    /* scaling_matrix 2 / 3: the lists in force after the SPS (flat without a matrix), whether it had a matrix, parameter sets sent so far,
+     * transform8x8 as asked for (scaling_matrix 3 switches it off for the pictures under one PPS) */
+    uint8_t sps4[6][16], sps8[2][64];
+    int sps_matrix, n_param_sets, t8_req;
     int wp_w[4], wp_o[4], wp_cw[4][2], wp_co[4][2], wp_ld, wp_cd;
     /* picture management of the current picture (8.2.4.3 / 8.2.5.4), planned before its slice headers are written */
     int nal_ref_idc, cur_frame_num, n_rplm, n_mmco, max_lt, idr_lt, slice_qp, delta_poc0;
@@ -73,6 +77,26 @@ typedef struct {
 } enc;
 
 static char g_err[256];
+/* sg_last_ranges(): per thread (callers generate streams in parallel threads: counters shared between them would be wrong, and a cache line
+ * that every thread writes slows all of them down), read back by the thread that called sg_encode() */
+static _Thread_local int32_t g_rng[SG_R_COUNT];
+static void rng_minmax(int lo, int hi, int v) {
+    if (v < g_rng[lo]) g_rng[lo] = v;
+    if (v > g_rng[hi]) g_rng[hi] = v;
+}
+/* one explicitly weighted block: denominator, weight and offset as used; returns nothing, counts into g_rng */
+static void rng_weight(int ld, int w, int o) {
+    g_rng[SG_R_DENOM_MASK] |= 1 << ld;
+    rng_minmax(SG_R_W_MIN, SG_R_W_MAX, w), rng_minmax(SG_R_O_MIN, SG_R_O_MAX, o);
+    if (w < 0) g_rng[SG_R_NEG_WEIGHT]++;
+}
+/* a predicted block of w x h luma samples at (ix, iy) of the reference picture: is its whole 6-tap window outside? */
+static void rng_window(const sg_pic *ref, int ix, int iy, int w, int h) {
+    if (ix + w + 2 < 0) g_rng[SG_R_OUT_LEFT]++;
+    if (ix - 2 > ref->w - 1) g_rng[SG_R_OUT_RIGHT]++;
+    if (iy + h + 2 < 0) g_rng[SG_R_OUT_TOP]++;
+    if (iy - 2 > ref->h - 1) g_rng[SG_R_OUT_BOTTOM]++;
+}
 const char *sg_last_error(void) { return g_err; }
 
 void sg_default_params(sg_params *p) {
@@ -113,6 +137,26 @@ void sg_source_frame(const sg_params *p, int t, uint8_t *dst) {
     int W = (p->width + 15) & ~15, H = (p->height + 15) & ~15;
     uint8_t *y = dst, *cb = dst + W * H, *cr = cb + W * H / 4;
     const double mx = p->motion_x4 * t / 4.0, my = p->motion_y4 * t / 4.0;
+    if (p->contrast) {
+        /* hard 0 / 255 pattern: every 16x16 luma region of the scene (8x8 in chroma) is flat, vertical stripes, horizontal stripes or
+         * checks of period 1..3 samples, by a hash of its position; the scene moves by whole samples (the floor of the motion) */
+        const int ox = (int)floor(mx), oy = (int)floor(my);
+        for (int pl = 0; pl < 3; pl++) {
+            const int pw = pl ? W / 2 : W, ph = pl ? H / 2 : H, rs = pl ? 3 : 4;
+            uint8_t *d = pl == 0 ? y : (pl == 1 ? cb : cr);
+            for (int j = 0; j < ph; j++)
+                for (int i = 0; i < pw; i++) {
+                    const int xi = i + (pl ? ox >> 1 : ox) + (1 << 20), yi = j + (pl ? oy >> 1 : oy) + (1 << 20);
+                    const uint32_t hh = hash32(((uint32_t)(xi >> rs) * 7919u + (uint32_t)(yi >> rs) * 104729u + (uint32_t)pl * 31337u) ^ p->seed);
+                    const int kind = (int)(hh & 3), per = 1 + (int)((hh >> 2) % 3u), inv = (int)(hh >> 8 & 1);
+                    const int a = (xi / per) & 1, b = (yi / per) & 1;
+                    const int on = kind == 0 ? 0 : (kind == 1 ? a : (kind == 2 ? b : a ^ b));
+                    d[j * pw + i] = (on ^ inv) ? 255 : 0;
+                }
+        }
+        if (p->mono) memset(cb, 128, (size_t)(W * H / 2));
+        return;
+    }
     for (int j = 0; j < H; j++)
         for (int i = 0; i < W; i++) {
             double xs = i + mx, ys = j + my;
@@ -1087,9 +1131,18 @@ static void pick_mv(enc *e, int x, int y, int w, int h, sg_pic *ref, const int m
     cand[n][0] = tmx, cand[n++][1] = tmy; /* true motion of the synthetic scene per frame */
     cand[n][0] = tmx + rnd_range(e, -6, 6), cand[n++][1] = tmy + rnd_range(e, -6, 6);
     cand[n][0] = tmx + rnd_range(e, -3, 3), cand[n++][1] = tmy + rnd_range(e, -3, 3);
-    cand[n][0] = rnd_range(e, -64, 64), cand[n++][1] = rnd_range(e, -64, 64);
+    const int reach = e->p.mv_reach > 0 ? e->p.mv_reach : 64, margin = e->p.mv_margin > 0 ? e->p.mv_margin : 24;
+    cand[n][0] = rnd_range(e, -reach, reach), cand[n++][1] = rnd_range(e, -reach, reach);
     cand[n][0] = 0, cand[n++][1] = 0;
-    if (rnd(e) % 100 < 25)
+    int far = 0;
+    if (e->p.mv_reach > 0) { /* the far candidate: at an end of its range one time in four per component, taken as it is one time in five */
+        for (int c = 0; c < 2; c++)
+            if (rnd(e) % 4 == 0) cand[4][c] = rnd(e) % 2 ? reach : -reach;
+        far = rnd(e) % 5 == 0;
+    }
+    if (far)
+        best = 4;
+    else if (rnd(e) % 100 < 25)
         best = (int)(rnd(e) % (uint32_t)n);
     else
         for (int i = 0; i < n; i++) {
@@ -1099,36 +1152,52 @@ static void pick_mv(enc *e, int x, int y, int w, int h, sg_pic *ref, const int m
         }
     out[0] = cand[best][0], out[1] = cand[best][1];
     /* keep the displaced block within 32 samples of the picture so that streams stay level-conformant */
-    int minx = -4 * (x + 24), maxx = 4 * (e->W - x - w + 24), miny = -4 * (y + 24), maxy = 4 * (e->H - y - h + 24);
+    int minx = -4 * (x + margin), maxx = 4 * (e->W - x - w + margin), miny = -4 * (y + margin), maxy = 4 * (e->H - y - h + margin);
     out[0] = out[0] < minx ? minx : (out[0] > maxx ? maxx : out[0]);
     out[1] = out[1] < miny ? miny : (out[1] > maxy ? maxy : out[1]);
+    if (e->p.mv_reach > 0 || e->p.mv_margin > 0) { /* Table A-1, levels 3.1 to 5.1: -2048..2047.75 samples across, -512..511.75 down (field pictures: half of that) */
+        const int vlim = e->field ? 1024 : 2048;
+        out[0] = out[0] < -8192 ? -8192 : (out[0] > 8191 ? 8191 : out[0]);
+        out[1] = out[1] < -vlim ? -vlim : (out[1] > vlim - 1 ? vlim - 1 : out[1]);
+    }
+    if (abs(out[0] - mvp[0]) > g_rng[SG_R_MVD_X]) g_rng[SG_R_MVD_X] = abs(out[0] - mvp[0]);
+    if (abs(out[1] - mvp[1]) > g_rng[SG_R_MVD_Y]) g_rng[SG_R_MVD_Y] = abs(out[1] - mvp[1]);
 }
 static void mc_part(enc *e, int bx, int by, int w, int h, uint8_t *py, uint8_t pc[2][64]) {
     emb *m = CURMB(e);
     int ref = m->ref[(by >> 1) * 2 + (bx >> 1)];
     sg_pic *rp = e->refs[ref];
     int mvx = m->mv[by * 4 + bx][0], mvy = m->mv[by * 4 + bx][1];
+    sg_mc_clip_count = &g_rng[SG_R_HALF1_CLIP0];
     sg_mc_luma(rp, e->mbx * 16 + bx * 4, e->mby * 16 + by * 4, w * 4, h * 4, mvx, mvy, py + by * 4 * 16 + bx * 4, 16);
+    sg_mc_clip_count = NULL;
+    rng_window(rp, e->mbx * 16 + bx * 4 + (mvx >> 2), e->mby * 16 + by * 4 + (mvy >> 2), w * 4, h * 4);
     /* Table 8-9: predicting from a field of the other parity shifts the chroma vector by a quarter chroma sample */
     const int cofs = !e->field || rp->parity == e->bottom ? 0 : (e->bottom ? 2 : -2);
     for (int c = 0; c < 2; c++) sg_mc_chroma(rp, 1 + c, e->mbx * 8 + bx * 2, e->mby * 8 + by * 2, w * 2, h * 2, mvx, mvy + cofs, pc[c] + by * 2 * 8 + bx * 2, 8);
     if (e->p.weighted_pred) {
         int ld = e->wp_ld, w0 = e->wp_w[ref], o0 = e->wp_o[ref];
+        int lo_clips = 0, hi_clips = 0;
+        rng_weight(ld, w0, o0);
         for (int y = by * 4; y < (by + h) * 4; y++)
             for (int x = bx * 4; x < (bx + w) * 4; x++) {
                 int v = py[y * 16 + x];
                 v = ld >= 1 ? ((v * w0 + (1 << (ld - 1))) >> ld) + o0 : v * w0 + o0;
+                lo_clips += v < 0, hi_clips += v > 255;
                 py[y * 16 + x] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
             }
         for (int c = 0; c < 2; c++) {
             int cd = e->wp_cd, cw = e->wp_cw[ref][c], co = e->wp_co[ref][c];
+            if (!e->p.mono) rng_weight(cd, cw, co);
             for (int y = by * 2; y < (by + h) * 2; y++)
                 for (int x = bx * 2; x < (bx + w) * 2; x++) {
                     int v = pc[c][y * 8 + x];
                     v = cd >= 1 ? ((v * cw + (1 << (cd - 1))) >> cd) + co : v * cw + co;
+                    lo_clips += v < 0, hi_clips += v > 255;
                     pc[c][y * 8 + x] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
                 }
         }
+        g_rng[SG_R_W1_CLIP0] += lo_clips, g_rng[SG_R_W1_CLIP255] += hi_clips;
     }
 }
 typedef struct {
@@ -1425,6 +1494,7 @@ static int dist_scale(int cur, int p0, int p1, int lt, int *dsf) {
     if (lt || td == 0) return 0;
     int tx = (16384 + abs(td / 2)) / td, v = (tb * tx + 32) >> 6;
     *dsf = v < -1024 ? -1024 : (v > 1023 ? 1023 : v);
+    g_rng[SG_R_TBTD_CLIPPED] += tb != cur - p0 || td != p1 - p0, g_rng[SG_R_DSF_CLIPPED] += *dsf != v;
     return 1;
 }
 /* motion of the quadrants in mask8, predicted in direct mode */
@@ -1494,7 +1564,10 @@ static void b_predict(enc *e, uint8_t *py, uint8_t pc[2][64]) {
         for (int l = 0; l < 2; l++) {
             if (!use[l]) continue;
             int mvx = EMV(m, l)[blk][0], mvy = EMV(m, l)[blk][1];
+            sg_mc_clip_count = &g_rng[SG_R_HALF1_CLIP0];
             sg_mc_luma(rp[l], e->mbx * 16 + bx * 4, e->mby * 16 + by * 4, 4, 4, mvx, mvy, ty[l], 4);
+            sg_mc_clip_count = NULL;
+            rng_window(rp[l], e->mbx * 16 + bx * 4 + (mvx >> 2), e->mby * 16 + by * 4 + (mvy >> 2), 4, 4);
             const int cofs = !e->field || rp[l]->parity == e->bottom ? 0 : (e->bottom ? 2 : -2); /* Table 8-9, as in mc_part() */
             for (int c = 0; c < 2; c++) sg_mc_chroma(rp[l], 1 + c, e->mbx * 8 + bx * 2, e->mby * 8 + by * 2, 2, 2, mvx, mvy + cofs, tc[l][c], 2);
         }
@@ -1502,13 +1575,21 @@ static void b_predict(enc *e, uint8_t *py, uint8_t pc[2][64]) {
         if (idc == 2 && use[0] && use[1]) {
             int dsf = 0;
             if (rp[1]->is_ref != 2 && dist_scale(e->cur_poc, rp[0]->poc, rp[1]->poc, rp[0]->is_ref == 2, &dsf) && (dsf >> 2) >= -64 && (dsf >> 2) <= 128)
-                iw[0] = 64 - (dsf >> 2), iw[1] = dsf >> 2;
+                iw[0] = 64 - (dsf >> 2), iw[1] = dsf >> 2, g_rng[SG_R_IMPLICIT_PAIRS]++, rng_minmax(SG_R_IMPLICIT_W1_MIN, SG_R_IMPLICIT_W1_MAX, iw[1]);
+            else
+                g_rng[SG_R_IMPLICIT_FALLBACK]++;
         }
         for (int comp = 0; comp < 3; comp++) {
             int n = comp ? 4 : 16, wd = comp ? 2 : 4;
             int ld = comp ? e->wp_cd : e->wp_ld;
             int w0 = use[0] ? (comp ? e->wp_cw[m->ref[q]][comp - 1] : e->wp_w[m->ref[q]]) : 0, o0 = use[0] ? (comp ? e->wp_co[m->ref[q]][comp - 1] : e->wp_o[m->ref[q]]) : 0;
             int w1 = use[1] ? (comp ? e->wb_cw1[m->ref1[q]][comp - 1] : e->wb_w1[m->ref1[q]]) : 0, o1 = use[1] ? (comp ? e->wb_co1[m->ref1[q]][comp - 1] : e->wb_o1[m->ref1[q]]) : 0;
+            if (idc == 1 && !(comp && e->p.mono)) {
+                if (use[0]) rng_weight(ld, w0, o0);
+                if (use[1]) rng_weight(ld, w1, o1);
+                if (use[0] && use[1] && o0 + o1 < 0 && ((o0 + o1) & 1)) g_rng[SG_R_ODD_NEG_OFFSETS]++;
+            }
+            int lo_clips = 0, hi_clips = 0;
             for (int i = 0; i < n; i++) {
                 int a = comp ? tc[0][comp - 1][i] : ty[0][i], b = comp ? tc[1][comp - 1][i] : ty[1][i], v;
                 if (use[0] && use[1]) {
@@ -1525,12 +1606,14 @@ static void b_predict(enc *e, uint8_t *py, uint8_t pc[2][64]) {
                         v = ld >= 1 ? ((v * ww + (1 << (ld - 1))) >> ld) + oo : v * ww + oo;
                     }
                 }
+                lo_clips += v < 0, hi_clips += v > 255;
                 v = v < 0 ? 0 : (v > 255 ? 255 : v);
                 if (comp == 0)
                     py[(by * 4 + i / wd) * 16 + bx * 4 + i % wd] = (uint8_t)v;
                 else
                     pc[comp - 1][(by * 2 + i / wd) * 8 + bx * 2 + i % wd] = (uint8_t)v;
             }
+            if (idc == 1) g_rng[use[0] && use[1] ? SG_R_W2_CLIP0 : SG_R_W1_CLIP0] += lo_clips, g_rng[use[0] && use[1] ? SG_R_W2_CLIP255 : SG_R_W1_CLIP255] += hi_clips;
         }
     }
 }
@@ -1729,8 +1812,65 @@ static void encode_b(enc *e, int kind) {
  * partition -- impossible, since A (left) and B (above) always precede in decoding order. */
 
 /* ------------------------------------------------------------------ headers */
+/* ------------------------------------------------------------------ coded scaling lists (7.3.2.1.1.1, Table 7-2)
+ * scaling_matrix 2 / 3.  Every list of a matrix is absent (fall-back rule A or B), sends useDefault, is coded in full or is cut short
+ * after entry k > 0 (nextScale = 0: the last value repeats).  Values wander between 1 and 255 in zig-zag order -- nothing symmetric about
+ * the diagonal, every list drawn on its own -- with jumps to 1, to 255 and across the ends of the range, which delta_scale (-128..127)
+ * can only reach modulo 256. */
+static void scaling_matrix_syntax(enc *e, sg_bw *w, int nlists, int rule_b, uint8_t out4[6][16], uint8_t out8[2][64]) {
+    for (int i = 0; i < nlists; i++) {
+        const int n = i < 6 ? 16 : 64;
+        uint8_t *dst = i < 6 ? out4[i] : out8[i - 6];
+        const uint8_t *def = i < 6 ? (i < 3 ? sg_default4x4_intra : sg_default4x4_inter) : (i == 6 ? sg_default8x8_intra : sg_default8x8_inter);
+        const int form = (int)(rnd(e) % 8); /* 0, 1: absent, 2: useDefault, 3, 4: cut short, 5..7: in full */
+        sg_put(w, form >= 2, 1); /* scaling_list_present_flag */
+        if (form < 2) {
+            const int first = i == 0 || i == 3 || i >= 6;
+            g_rng[SG_R_SCALING_FORMS] |= first ? SG_SF_ABSENT_FIRST : SG_SF_ABSENT_NEXT;
+            if (!first)
+                memcpy(dst, out4[i - 1], 16);
+            else if (!rule_b)
+                memcpy(dst, def, (size_t)n);
+            else
+                memcpy(dst, i < 6 ? e->sps4[i] : e->sps8[i - 6], (size_t)n);
+            continue;
+        }
+        uint8_t val[64];
+        int v = 4 + (int)(rnd(e) % 40), ncoded = form == 2 ? 0 : (form < 5 ? 2 + (int)(rnd(e) % (uint32_t)(n - 2)) : n);
+        for (int j = 0; j < n; j++) {
+            const int r = (int)(rnd(e) % 24);
+            if (r == 0) v = 1;
+            else if (r == 1) v = 255;
+            else if (r == 2) v = v < 128 ? 250 - (int)(rnd(e) % 8) : 2 + (int)(rnd(e) % 8); /* across an end of the range */
+            else v += rnd_range(e, -7, 9);
+            v = v < 1 ? 1 : (v > 255 ? 255 : v);
+            val[j] = (uint8_t)v;
+        }
+        int last = 8, next = 8;
+        for (int j = 0; j < n; j++) {
+            if (next != 0) {
+                const int target = j < ncoded ? val[j] : 0, delta = ((target - last + 128) & 255) - 128;
+                sg_put_se(w, delta);
+                if (target && (last + delta < 0 || last + delta > 255)) g_rng[SG_R_SCALING_FORMS] |= SG_SF_WRAP;
+                next = (last + delta + 256) % 256;
+                if (j == 0 && next == 0) { /* useDefaultScalingMatrixFlag */
+                    memcpy(dst, def, (size_t)n);
+                    g_rng[SG_R_SCALING_FORMS] |= SG_SF_USE_DEFAULT;
+                    break;
+                }
+                if (next == 0) g_rng[SG_R_SCALING_FORMS] |= SG_SF_CUT_SHORT;
+            }
+            dst[j] = (uint8_t)(next == 0 ? last : next);
+            last = dst[j];
+            if (dst[j] == 1) g_rng[SG_R_SCALING_FORMS] |= SG_SF_ENTRY_1;
+            if (dst[j] == 255) g_rng[SG_R_SCALING_FORMS] |= SG_SF_ENTRY_255;
+        }
+        if (ncoded == n) g_rng[SG_R_SCALING_FORMS] |= SG_SF_FULL;
+    }
+}
+
 static size_t write_sps(enc *e, uint8_t *dst, size_t cap) {
-    uint8_t buf[512];
+    uint8_t buf[1024];
     sg_bw w;
     const sg_params *p = &e->p;
     sg_bw_init(&w, buf, sizeof(buf));
@@ -1743,8 +1883,13 @@ static size_t write_sps(enc *e, uint8_t *dst, size_t cap) {
         sg_put_ue(&w, 0);
         sg_put_ue(&w, 0);
         sg_put(&w, 0, 1); /* qpprime_y_zero_transform_bypass */
-        sg_put(&w, p->scaling_matrix ? 1 : 0, 1);
-        if (p->scaling_matrix) {
+        memset(e->sps4, 16, sizeof(e->sps4)), memset(e->sps8, 16, sizeof(e->sps8));
+        e->sps_matrix = p->scaling_matrix == 1 || p->scaling_matrix == 2 || (p->scaling_matrix == 3 && e->n_param_sets % 2 == 0);
+        sg_put(&w, (uint32_t)e->sps_matrix, 1);
+        if (e->sps_matrix && p->scaling_matrix >= 2) {
+            scaling_matrix_syntax(e, &w, 8, 0, e->sps4, e->sps8);
+            g_rng[SG_R_SCALING_FORMS] |= SG_SF_SPS_MATRIX;
+        } else if (e->sps_matrix) {
             /* lists 0 and 3 and 6,7: useDefault (delta_scale -8 at j=0 -> nextScale 0); others fall back */
             for (int i = 0; i < 8; i++) {
                 int send = (i == 0 || i == 3 || i == 6 || i == 7);
@@ -1755,7 +1900,7 @@ static size_t write_sps(enc *e, uint8_t *dst, size_t cap) {
     }
     sg_put_ue(&w, 4); /* log2_max_frame_num_minus4 -> 8 bits */
     sg_put_ue(&w, (uint32_t)p->poc_type);
-    if (p->poc_type == 0) sg_put_ue(&w, 4); /* log2_max_poc_lsb_minus4 -> 8 bits */
+    if (p->poc_type == 0) sg_put_ue(&w, p->poc_step > 1 ? 12 : 4); /* log2_max_poc_lsb_minus4 -> 8 bits (poc_step: 16) */
     if (p->poc_type == 1) {
         sg_put(&w, 0, 1);   /* delta_pic_order_always_zero_flag */
         sg_put_se(&w, -1);  /* offset_for_non_ref_pic */
@@ -1880,7 +2025,7 @@ static int sg_next_mb(const enc *e, int addr) {
 
 static size_t write_pps(enc *e, uint8_t *dst, size_t cap) {
     const sg_params *p = &e->p;
-    size_t bcap = 64 + (p->slice_groups > 1 ? (size_t)sg_map_units(e) : 0);
+    size_t bcap = 64 + (p->slice_groups > 1 ? (size_t)sg_map_units(e) : 0) + (p->scaling_matrix >= 2 ? 1024 : 0);
     uint8_t *buf = (uint8_t *)malloc(bcap);
     sg_bw w;
     sg_bw_init(&w, buf, bcap);
@@ -1917,7 +2062,14 @@ static size_t write_pps(enc *e, uint8_t *dst, size_t cap) {
     sg_put(&w, 0, 1);
     if (p->profile_idc == 100) {
         sg_put(&w, (uint32_t)p->transform8x8, 1);
-        sg_put(&w, 0, 1); /* pic_scaling_matrix_present */
+        sg_put(&w, p->scaling_matrix == 3, 1); /* pic_scaling_matrix_present */
+        if (p->scaling_matrix == 2) memcpy(e->s4, e->sps4, sizeof(e->s4)), memcpy(e->s8, e->sps8, sizeof(e->s8));
+        if (p->scaling_matrix == 3) { /* fall-back rule B after an SPS with a matrix, rule A after one without; six lists without the 8x8 transform */
+            memcpy(e->s8, e->sps8, sizeof(e->s8));
+            scaling_matrix_syntax(e, &w, p->transform8x8 ? 8 : 6, e->sps_matrix, e->s4, e->s8);
+            g_rng[SG_R_SCALING_FORMS] |= (e->sps_matrix ? SG_SF_PPS_RULE_B : SG_SF_PPS_RULE_A) | (p->transform8x8 ? 0 : SG_SF_PPS_SIX_LISTS);
+        }
+        if (p->scaling_matrix >= 2) build_scale(e);
         sg_put_se(&w, p->chroma_qp_offset + (p->transform8x8 && p->chroma_qp_offset < 12 ? 1 : 0));
     }
     sg_trailing(&w);
@@ -1938,7 +2090,7 @@ static void write_slice_header(enc *e, int first_mb, int idr, int frame_num, int
     if (e->field) sg_put(w, (uint32_t)e->bottom, 1);    /* bottom_field_flag */
     if (idr) sg_put_ue(w, (uint32_t)idr_id);
     const int bottom_delta = e->field || p->poc_type == 2 ? 0 : (idr && p->poc_bottom_delta < 0 ? 0 : p->poc_bottom_delta); /* (sent in frame pictures only) */
-    if (p->poc_type == 0) sg_put(w, (uint32_t)poc_lsb, 8);
+    if (p->poc_type == 0) sg_put(w, (uint32_t)poc_lsb, p->poc_step > 1 ? 16 : 8);
     if (p->poc_type == 0 && p->poc_bottom_delta != 0 && !e->field) sg_put_se(w, bottom_delta); /* delta_pic_order_cnt_bottom */
     if (p->poc_type == 1) sg_put_se(w, e->delta_poc0); /* delta_pic_order_cnt[0] (delta_pic_order_always_zero_flag = 0) */
     if (p->poc_type == 1 && p->poc_bottom_delta != 0 && !e->field) sg_put_se(w, bottom_delta - 1); /* delta_pic_order_cnt[1]: on top of offset_for_top_to_bottom_field = 1 */
@@ -2021,6 +2173,10 @@ static uint32_t g_feat;
 static int32_t g_pocs[8192];
 static int g_npocs;
 uint32_t sg_last_features(void) { return g_feat; }
+int sg_last_ranges(int32_t *dst, int cap) {
+    for (int i = 0; i < SG_R_COUNT && i < cap && dst; i++) dst[i] = g_rng[i];
+    return SG_R_COUNT;
+}
 int sg_last_pocs(int32_t *dst, int cap) {
     for (int i = 0; i < g_npocs && i < cap && dst; i++) dst[i] = g_pocs[i];
     return g_npocs;
@@ -2071,7 +2227,37 @@ static void plan_ref_list(enc *e) {
         else if (i < e->nref_active) force_real = 1;
     }
     if (force_real) e->nref_active = nreal < e->nref_active ? nreal : e->nref_active;
-    if (force_real || (e->p.rplm && !(e->p.bframes > 0 && e->p.direct_temporal) && n >= 2 && rnd(e) % 100 < 75)) { /* (temporal direct: see above) */
+    /* wp_range 2: one picture at two indices, so that it is predicted from under two sets of weights (what x264 does in fades).  The
+     * commands name picture A, with three or more entries a second picture B, and A again; with two entries the second command repeats the
+     * first picture number, which only abs_diff_pic_num_minus1 = MaxPicNum - 1 can say */
+    int twice = 0;
+    if (e->p.wp_range == 2 && e->p.weighted_pred && !e->p.field_pics && !force_real && !(e->p.bframes > 0 && e->p.direct_temporal) && e->nref_active >= 2) {
+        sg_pic *a = NULL, *b = NULL;
+        for (int tries = 0; tries < 16 && !a; tries++) {
+            sg_pic *t = init[rnd(e) % (uint32_t)n];
+            if (t->is_ref == 1 && !t->nonexist) a = t;
+        }
+        for (int tries = 0; tries < 16 && a && !b && e->nref_active >= 3; tries++) {
+            sg_pic *t = init[rnd(e) % (uint32_t)n];
+            if (t->is_ref == 1 && !t->nonexist && t != a) b = t;
+        }
+        if (a && (b || e->nref_active == 2)) {
+            sg_pic *seq[3] = {a, b ? b : a, a};
+            int pred = cur_fn;
+            twice = 1;
+            for (int c = 0; c < (b ? 3 : 2); c++) {
+                const int fn = seq[c]->frame_num, down = (pred - fn + SG_MAX_FN) % SG_MAX_FN;
+                final[nf++] = seq[c];
+                e->rplm[e->n_rplm].idc = 0, e->rplm[e->n_rplm++].val = (down ? down : SG_MAX_FN) - 1;
+                g_feat |= 1u << 8;
+                pred = fn;
+            }
+            g_rng[SG_R_REF_TWICE]++;
+        }
+    }
+    if (twice)
+        ;
+    else if (force_real || (e->p.rplm && !(e->p.bframes > 0 && e->p.direct_temporal) && n >= 2 && rnd(e) % 100 < 75)) { /* (temporal direct: see above) */
         /* the first k entries become k distinct pictures picked from the WHOLE set of reference pictures */
         int k = force_real ? e->nref_active : 1 + (int)(rnd(e) % (uint32_t)(e->nref_active < 3 ? e->nref_active : 3));
         int pred = cur_fn; /* picNumL0Pred */
@@ -2471,6 +2657,59 @@ static void weave_or_split(enc *e, int slot, int from_fields) {
 }
 
 /* ------------------------------------------------------------------ top level */
+/* wp_range: the pred_weight_table() of one slice (see sg.h).  A weight without a flag is 2^denom with offset 0; weights of
+ * list 1 are drawn from what -128 <= w0 + w1 <= (denom == 7 ? 127 : 128) leaves them against EVERY entry of list 0. */
+static int draw_end(enc *e, int ld, int lo, int hi, int is_weight) {
+    const int ends[8] = {-128, -1, 0, 1, 127, 1 << ld, (1 << ld) - 1, (1 << ld) + 1};
+    if (rnd(e) % 2) {
+        int v = ends[rnd(e) % (is_weight ? 8u : 5u)];
+        if (v >= lo && v <= hi) return v;
+    }
+    return rnd_range(e, lo, hi);
+}
+static void draw_weights(enc *e, int is_b) {
+    for (int attempt = 0;; attempt++) {
+        const int tame = attempt >= 64; /* (never seen: weights of 1 always fit) */
+        int ok = 1, lo1[3], hi1[3];
+        e->wp_ld = rnd_range(e, 0, 7), e->wp_cd = rnd_range(e, 0, 7);
+        for (int i = 0; i < 4; i++) /* list 0: luma under one flag, Cb and Cr under another */
+            for (int k = 0; k < 2; k++) {
+                const int ld = k ? e->wp_cd : e->wp_ld, flag = tame || rnd(e) % 4 != 0;
+                for (int c = 0; c < (k ? 2 : 1); c++) {
+                    const int wv = tame ? 1 : (flag ? draw_end(e, ld, -128, 127, 1) : 1 << ld), ov = flag && !tame ? draw_end(e, ld, -128, 127, 0) : 0;
+                    if (k == 0) e->wp_w[i] = wv, e->wp_o[i] = ov;
+                    else e->wp_cw[i][c] = wv, e->wp_co[i][c] = ov;
+                }
+            }
+        for (int comp = 0; comp < 3; comp++) { /* what the sum leaves to an entry of list 1 */
+            int mn = 1 << 20, mx = -(1 << 20);
+            for (int i = 0; i < e->nref_active; i++) {
+                const int wv = comp ? e->wp_cw[i][comp - 1] : e->wp_w[i];
+                mn = wv < mn ? wv : mn, mx = wv > mx ? wv : mx;
+            }
+            lo1[comp] = -128 - mn, hi1[comp] = ((comp ? e->wp_cd : e->wp_ld) == 7 ? 127 : 128) - mx;
+        }
+        for (int i = 0; i < 4 && is_b; i++)
+            for (int k = 0; k < 2; k++) {
+                const int ld = k ? e->wp_cd : e->wp_ld, def = 1 << ld;
+                int flag = tame || rnd(e) % 4 != 0;
+                for (int c = 0; c < (k ? 2 : 1); c++)
+                    if (def < lo1[k + c] || def > hi1[k + c]) flag = 1; /* the default weight does not fit: code one */
+                for (int c = 0; c < (k ? 2 : 1); c++) {
+                    const int lo = lo1[k + c] < -128 ? -128 : lo1[k + c], hi = hi1[k + c] > 127 ? 127 : hi1[k + c];
+                    if (flag && lo > hi) ok = 0;
+                    const int wv = tame ? 1 : (flag ? (lo > hi ? 0 : draw_end(e, ld, lo, hi, 1)) : def), ov = flag && !tame ? draw_end(e, ld, -128, 127, 0) : 0;
+                    if (k == 0) e->wb_w1[i] = wv, e->wb_o1[i] = ov;
+                    else e->wb_cw1[i][c] = wv, e->wb_co1[i][c] = ov;
+                }
+            }
+        if (ok || tame) break;
+    }
+    if (e->p.mono)
+        for (int i = 0; i < 4; i++)
+            for (int c = 0; c < 2; c++) e->wp_cw[i][c] = e->wb_cw1[i][c] = 1 << e->wp_cd, e->wp_co[i][c] = e->wb_co1[i][c] = 0;
+}
+
 size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *recon, size_t recon_cap, uint32_t *frame_sizes) {
     enc *e = (enc *)calloc(1, sizeof(enc));
     size_t out = 0;
@@ -2553,7 +2792,10 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
     /* scaling lists: flat, or the spec's Default_* lists when scaling_matrix is set */
     memset(e->s4, 16, sizeof(e->s4));
     memset(e->s8, 16, sizeof(e->s8));
-    if (p->scaling_matrix) {
+    if (p->scaling_matrix < 0 || p->scaling_matrix > 3) p->scaling_matrix = 1;
+    e->t8_req = p->transform8x8;
+    sg_set_range_guard(p->scaling_matrix >= 2);
+    if (p->scaling_matrix == 1) {
         for (int l = 0; l < 6; l++) memcpy(e->s4[l], l < 3 ? sg_default4x4_intra : sg_default4x4_inter, 16);
         memcpy(e->s8[0], sg_default8x8_intra, 64);
         memcpy(e->s8[1], sg_default8x8_inter, 64);
@@ -2562,6 +2804,9 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
     int frame_num = 0, idr_id = 0, poc = 0, refs_since_reset = 0, since_idr = 0;
     static const int poc1_offsets[2] = {2, 6}; /* offset_for_ref_frame[] of write_sps() */
     g_feat = 0, g_npocs = 0;
+    memset(g_rng, 0, sizeof(g_rng));
+    g_rng[SG_R_W_MIN] = g_rng[SG_R_O_MIN] = g_rng[SG_R_IMPLICIT_W1_MIN] = 1 << 20, g_rng[SG_R_W_MAX] = g_rng[SG_R_O_MAX] = g_rng[SG_R_IMPLICIT_W1_MAX] = -(1 << 20);
+    const int pstep = p->poc_step > 1 && p->poc_type != 2 ? (p->poc_step > 31 ? 31 : p->poc_step) : 1;
     /* coding order.  Without B pictures it is the display order.  With them every (bframes + 1)-th picture is an anchor
      * (I or P) and the pictures between two anchors are B pictures coded right after the later anchor -- unless that anchor
      * is an IDR picture or does not exist any more: then they are P pictures in display order (a closed group). */
@@ -2619,13 +2864,16 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
                 fs += (size_t)pw * ph;
             }
         }
-        if (p->bframes > 0) poc = 2 * (dsp - idr_disp);
+        if (p->bframes > 0) poc = 2 * pstep * (dsp - idr_disp);
         if (idr) {
             frame_num = 0, poc = 0, e->nrefs = 0, refs_since_reset = 0, since_idr = 0;
+            /* scaling_matrix 3: the pictures under every third PPS do without the 8x8 transform (a matrix of six lists) */
+            if (p->scaling_matrix == 3) p->transform8x8 = e->t8_req && (e->n_param_sets + (int)(p->seed % 3u)) % 3 != 2;
             size_t n = write_sps(e, stream + out, cap - out);
             out += n;
             n = write_pps(e, stream + out, cap - out);
             out += n;
+            e->n_param_sets++;
             for (int i = 0; i < 6; i++) e->pics[i].is_ref = 0;
         }
         /* frame_num gap (8.2.5.2): the skipped values enter the window as non-existing frames, oldest pictures leave */
@@ -2776,7 +3024,8 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
             e->slice_qp = e->slice_qp < 0 ? 0 : (e->slice_qp > 51 ? 51 : e->slice_qp);
             if (e->slice_qp != p->qp) g_feat |= 1u << 13;
             sg_bw_init(&e->bw, rbsp, slice_cap);
-            write_slice_header(e, first, idr, frame_num, idr_id, pic_poc & 255);
+            if (p->wp_range && !intra_pic && (bpic ? p->weighted_bipred == 1 : p->weighted_pred != 0)) draw_weights(e, bpic);
+            write_slice_header(e, first, idr, frame_num, idr_id, pic_poc & (p->poc_step > 1 ? 65535 : 255));
             e->qp = e->slice_qp, e->prev_dqp_nz = 0, e->skip_run = 0;
             if (p->cabac) {
                 while (!sg_bw_aligned(&e->bw)) sg_put(&e->bw, 1, 1);
@@ -2891,14 +3140,14 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
         }
       } /* fld */
         since_idr++;
-        poc += 2;
+        poc += 2 * pstep;
         if (e->nal_ref_idc) {
             frame_num = (frame_num + 1) & (SG_MAX_FN - 1);
             refs_since_reset++;
         }
         if (ms.clear_all) { /* after operation 5 the picture counts as frame_num 0 / POC 0 (7.4.3, 8.2.1) */
             e->cur->frame_num = 0;
-            frame_num = 1, refs_since_reset = 1, poc = 2;
+            frame_num = 1, refs_since_reset = 1, poc = 2 * pstep;
             if (p->poc_bottom_delta < 0 && p->poc_type != 2) poc -= p->poc_bottom_delta; /* the next frame's bottom field (top + d) comes 2 after this picture's 0 */
             g_pocs[g_npocs - 1] = 0;
         }
@@ -2906,6 +3155,8 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
         if (frame_sizes) frame_sizes[t] = (uint32_t)(out - au_start);
     }
 done:
+    g_rng[SG_R_GUARD_ZEROED] = sg_guard_zeroed;
+    sg_set_range_guard(0);
     free(disp);
     free(is_b);
     free(b_ref);

@@ -59,6 +59,9 @@ void sg_pred_i8(const sg_pic *p, int x, int y, int mode, const sg_avail *a, uint
 void sg_pred_i16(const sg_pic *p, int x, int y, int mode, const sg_avail *a, uint8_t *pred /*16x16*/);
 void sg_pred_chroma(const sg_pic *p, int plane, int x, int y, int mode, const sg_avail *a, uint8_t *pred /*8x8*/);
 void sg_mc_luma(const sg_pic *ref, int x, int y, int w, int h, int mvx, int mvy, uint8_t *dst, int dstride);
+/* while set, sg_mc_luma() counts the half samples that its result is made of and that the clip changed: [0] / [1] = b, h, s, m
+ * (one 6-tap filter) below 0 / above 255, [2] / [3] = j (two filters).  The motion search leaves it NULL.  Per thread. */
+extern _Thread_local int32_t *sg_mc_clip_count;
 void sg_mc_chroma(const sg_pic *ref, int plane, int x, int y, int w, int h, int mvx, int mvy, uint8_t *dst, int dstride);
 
 /* levels in scan order -> residual samples (raster).  ls = LevelScale for qP%6, raster order. */
@@ -85,5 +88,9 @@ void sg_deblock(sg_pic *p, const sg_dbmb *mbs, int wmb, int hmb);
 /* field pictures: coefficients in field scan order (8.5.6, 8.5.7); deblocking with the rules for field macroblocks (8.7.2.1:
  * horizontal edges of intra macroblocks get bS 3, vertical vector differences count from 4 quarter FRAME samples = 2 field ones) */
 void sg_set_field_mode(int on);
+/* on: the quantisers drop levels that would take a scaled coefficient or a transform intermediate out of the 16-bit range of 8.5.12
+ * (scaling lists with large entries); sg_guard_zeroed counts them since the call */
+void sg_set_range_guard(int on);
+extern _Thread_local int32_t sg_guard_zeroed;
 
 #endif

@@ -223,9 +223,19 @@ void sg_pred_chroma(const sg_pic *p, int plane, int x, int y, int mode, const sg
 }
 
 /* ------------------------------------------------------------------ inter prediction (separable) */
+_Thread_local int32_t *sg_mc_clip_count;
+/* which half samples a fractional position (fy * 4 + fx) reads: bit 0 b, 1 h, 2 s, 3 m, 4 j */
+static const uint8_t half_used[16] = {0, 1, 1, 1, 2, 3, 17, 9, 2, 18, 16, 24, 2, 6, 20, 12};
+static void count_half(int32_t *count, int used, int kind, int raw, int shift) {
+    if (!(used >> kind & 1)) return;
+    const int v = raw >> shift;
+    if (v < 0) count[kind == 4 ? 2 : 0]++;
+    if (v > 255) count[kind == 4 ? 3 : 1]++;
+}
 void sg_mc_luma(const sg_pic *ref, int x, int y, int w, int h, int mvx, int mvy, uint8_t *dst, int dstride) {
     /* clamped integer window covering [-2, +3] around the block */
     int win[21 + 5][21 + 5];
+    int32_t *const count = sg_mc_clip_count;
     int fx = mvx & 3, fy = mvy & 3, ix = x + (mvx >> 2), iy = y + (mvy >> 2);
     int ww = w + 5, wh = h + 5;
     for (int j = 0; j < wh; j++) {
@@ -251,6 +261,11 @@ void sg_mc_luma(const sg_pic *ref, int x, int y, int w, int h, int mvx, int mvy,
             int jj = hb[j][i] - 5 * hb[j + 1][i] + 20 * hb[j + 2][i] + 20 * hb[j + 3][i] - 5 * hb[j + 4][i] + hb[j + 5][i];
             int c = clip255((jj + 512) >> 10);
             int v;
+            if (count) {
+                const int used = half_used[fy * 4 + fx];
+                count_half(count, used, 0, hb[j + 2][i] + 16, 5), count_half(count, used, 1, vb[j][i + 2] + 16, 5), count_half(count, used, 2, hb[j + 3][i] + 16, 5);
+                count_half(count, used, 3, vb[j][i + 3] + 16, 5), count_half(count, used, 4, jj + 512, 10);
+            }
             switch (fy * 4 + fx) {
             case 0: v = G; break;
             case 1: v = (G + b + 1) >> 1; break;
@@ -358,6 +373,75 @@ void sg_residual8(const int16_t *lev, const int *ls, int qp, int *res) {
     }
     inv8(res);
 }
+/* ------------------------------------------------------------------ 16-bit range guard (8.5.10 - 8.5.13)
+ * A conforming stream keeps every scaled coefficient and every intermediate of the inverse transforms within -2^15 .. 2^15 - 1.  With
+ * scaling-list entries of 255 one level can leave that range where the quantiser still prefers it to 0; the generator then drops
+ * levels, largest scaled coefficient first, until the block is inside.  AC blocks whose DC arrives separately stay within GUARD_AC and
+ * the DC values within GUARD_DC: the DC coefficient adds to every intermediate exactly (it passes no shift), and the two bounds add up
+ * to less than 2^15. */
+#define GUARD_ALL 32700
+#define GUARD_AC 12000
+#define GUARD_DC 20000
+static _Thread_local int g_guard; /* (per thread, like the counters of sg_enc.c: streams are generated in parallel threads) */
+_Thread_local int32_t sg_guard_zeroed;
+void sg_set_range_guard(int on) { g_guard = on != 0, sg_guard_zeroed = 0; }
+static int amax(int m, int v) { return abs(v) > m ? abs(v) : m; }
+static int peak4(const int *d) { /* largest magnitude among the coefficients and the intermediates of inv4() */
+    int m[16], pk = 0;
+    memcpy(m, d, sizeof(m));
+    for (int i = 0; i < 16; i++) pk = amax(pk, m[i]);
+    for (int pass = 0; pass < 2; pass++) {
+        int step = pass ? 4 : 1, line = pass ? 1 : 4;
+        for (int k = 0; k < 4; k++) {
+            int *p = m + k * line;
+            int a = p[0], b = p[step], c = p[2 * step], dd = p[3 * step];
+            int s0 = a + c, s1 = a - c, s2 = (b >> 1) - dd, s3 = b + (dd >> 1);
+            pk = amax(amax(amax(amax(pk, s0), s1), s2), s3);
+            p[0] = s0 + s3, p[step] = s1 + s2, p[2 * step] = s1 - s2, p[3 * step] = s0 - s3;
+            for (int i = 0; i < 4; i++) pk = amax(pk, p[i * step]);
+        }
+    }
+    return pk + 32;
+}
+static int peak8(const int *d) {
+    int m[64], pk = 0;
+    memcpy(m, d, sizeof(m));
+    for (int i = 0; i < 64; i++) pk = amax(pk, m[i]);
+    for (int pass = 0; pass < 2; pass++) {
+        int step = pass ? 8 : 1, line = pass ? 1 : 8;
+        for (int k = 0; k < 8; k++) {
+            int *p = m + k * line;
+            int d0 = p[0], d1 = p[step], d2 = p[2 * step], d3 = p[3 * step], d4 = p[4 * step], d5 = p[5 * step], d6 = p[6 * step], d7 = p[7 * step];
+            int a[8] = {d0 + d4, d5 - d3 - d7 - (d7 >> 1), d0 - d4, d1 + d7 - d3 - (d3 >> 1), (d2 >> 1) - d6, d7 - d1 + d5 + (d5 >> 1), d2 + (d6 >> 1), d3 + d5 + d1 + (d1 >> 1)};
+            int b[8] = {a[0] + a[6], a[1] + (a[7] >> 2), a[2] + a[4], a[3] + (a[5] >> 2), a[2] - a[4], (a[3] >> 2) - a[5], a[0] - a[6], a[7] - (a[1] >> 2)};
+            p[0] = b[0] + b[7], p[step] = b[2] + b[5], p[2 * step] = b[4] + b[3], p[3 * step] = b[6] + b[1];
+            p[4 * step] = b[6] - b[1], p[5 * step] = b[4] - b[3], p[6 * step] = b[2] - b[5], p[7 * step] = b[0] - b[7];
+            for (int i = 0; i < 8; i++) pk = amax(amax(amax(pk, a[i]), b[i]), p[i * step]);
+        }
+    }
+    return pk + 32;
+}
+/* drop levels of lev[first..n) until peak(scaled coefficients) <= limit; scale() fills d[] (raster) from the levels */
+static void guard_block(int16_t *lev, int n, int first, const int *ls, int qp, int limit) {
+    for (;;) {
+        int d[64], big = -1, bigv = 0;
+        memset(d, 0, sizeof(d));
+        for (int k = first; k < n; k++) {
+            if (!lev[k]) continue;
+            const int per = qp / 6, pos = n == 16 ? g_scan4[k] : g_scan8[k];
+            const long long v = (long long)lev[k] * ls[pos];
+            const long long c = n == 16 ? (per >= 4 ? v * (1 << (per - 4)) : (v + (1 << (3 - per))) >> (4 - per)) : (per >= 6 ? v * (1 << (per - 6)) : (v + (1 << (5 - per))) >> (6 - per));
+            if (c < -limit || c > limit) { /* (also keeps the int arithmetic below from overflowing) */
+                lev[k] = 0, sg_guard_zeroed++;
+                continue;
+            }
+            d[pos] = (int)c;
+            if (llabs(c) > bigv) bigv = (int)llabs(c), big = k;
+        }
+        if (big < 0 || (n == 16 ? peak4(d) : peak8(d)) <= limit) return;
+        lev[big] = 0, sg_guard_zeroed++;
+    }
+}
 static void hadamard4(const int *in, int *out) {
     int t[16];
     for (int r = 0; r < 4; r++) {
@@ -445,6 +529,7 @@ void sg_quant4(const int *resid, const int *ls, int qp, double dead, int skip_dc
         /* resid ~= lev * ls * scale * B / 64 */
         lev[k] = dead_round(64.0 * acc / (norm4[u] * norm4[v] * ls[pos] * scale), dead);
     }
+    if (g_guard) guard_block(lev, 16, skip_dc ? 1 : 0, ls, qp, skip_dc ? GUARD_AC : GUARD_ALL);
 }
 void sg_quant8(const int *resid, const int *ls, int qp, double dead, int16_t *lev) {
     init_basis();
@@ -456,6 +541,7 @@ void sg_quant8(const int *resid, const int *ls, int qp, double dead, int16_t *le
             for (int x = 0; x < 8; x++) acc += resid[y * 8 + x] * basis8[v][y] * basis8[u][x];
         lev[k] = dead_round(64.0 * acc / (norm8[u] * norm8[v] * ls[pos] * scale), dead);
     }
+    if (g_guard) guard_block(lev, 64, 0, ls, qp, GUARD_ALL);
 }
 void sg_quant_luma_dc(const int *sums, int ls00, int qp, double dead, int16_t *lev) {
     /* wanted DC coefficient of block i: d_i = 64 * sum_i / 16; d = (H c H) * ls00 * 2^(qp/6-6)  =>  c = H d H / 16 / (...) */
@@ -464,11 +550,36 @@ void sg_quant_luma_dc(const int *sums, int ls00, int qp, double dead, int16_t *l
     hadamard4(d4, f);
     double scale = ls00 * ldexp(1.0, qp / 6 - 6);
     for (int k = 0; k < 16; k++) lev[k] = dead_round(4.0 * f[g_scan4[k]] / 16.0 / scale, dead);
+    while (g_guard) { /* the transformed levels and the scaled DC values (8.5.10) */
+        int c[16], pk = 0, big = 0;
+        for (int k = 0; k < 16; k++) c[g_scan4[k]] = lev[k], big = abs(lev[k]) > abs(lev[big]) ? k : big;
+        hadamard4(c, f);
+        long long worst = 0;
+        for (int i = 0; i < 16; i++) {
+            const long long v = (long long)f[i] * ls00, q = qp / 6 >= 6 ? v * (1 << (qp / 6 - 6)) : (v + (1 << (5 - qp / 6))) >> (6 - qp / 6);
+            worst = llabs(q) > worst ? llabs(q) : worst;
+            pk = abs(f[i]) > pk ? abs(f[i]) : pk;
+        }
+        if ((pk <= GUARD_ALL && worst <= GUARD_DC) || !lev[big]) break;
+        lev[big] = 0, sg_guard_zeroed++;
+    }
 }
 void sg_quant_chroma_dc(const int *s, int ls00, int qpc, double dead, int16_t *lev) {
     int f[4] = {s[0] + s[1] + s[2] + s[3], s[0] - s[1] + s[2] - s[3], s[0] + s[1] - s[2] - s[3], s[0] - s[1] - s[2] + s[3]};
     double scale = ls00 * ldexp(1.0, qpc / 6) / 32.0;
     for (int i = 0; i < 4; i++) lev[i] = dead_round(4.0 * f[i] / 4.0 / scale, dead);
+    while (g_guard) { /* 8.5.11 */
+        int big = 0;
+        long long worst = 0;
+        const int t[4] = {lev[0] + lev[1] + lev[2] + lev[3], lev[0] - lev[1] + lev[2] - lev[3], lev[0] + lev[1] - lev[2] - lev[3], lev[0] - lev[1] - lev[2] + lev[3]};
+        for (int i = 0; i < 4; i++) {
+            const long long q = ((long long)t[i] * ls00 * (1 << (qpc / 6))) >> 5;
+            worst = llabs(q) > worst ? llabs(q) : worst;
+            big = abs(lev[i]) > abs(lev[big]) ? i : big;
+        }
+        if (worst <= GUARD_DC || !lev[big]) break;
+        lev[big] = 0, sg_guard_zeroed++;
+    }
 }
 
 /* ------------------------------------------------------------------ deblocking 8.7 */

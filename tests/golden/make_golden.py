@@ -54,6 +54,24 @@ for name in sorted(POC_MATRIX):
 json.dump(out, open(os.path.join(HERE, "poc_md5.json"), "w"), indent=1, sort_keys=True)
 print("wrote", len(out), "POC vectors")
 
+
+
+def value_range_vectors():
+    """tests/rangeutil.py: the recipes at the ends of the value ranges of inter prediction, the vector syntax and the scaling lists."""
+    import rangeutil
+    out = {}
+    for name in sorted(rangeutil.RECIPES):
+        s, rec, _ = streamgen.encode(**rangeutil.RECIPES[name])
+        pocs = [int(x) for x in streamgen.last_pocs()]
+        frames, _ = oracle.decode(s, crop=False)
+        assert (frames == rec).all(), name
+        out[name] = {"stream_md5": hashlib.md5(s).hexdigest(), "frames_md5": hashlib.md5(rec.tobytes()).hexdigest(), "stream_bytes": len(s), "pocs": pocs}
+    json.dump(out, open(os.path.join(HERE, "value_range_md5.json"), "w"), indent=1, sort_keys=True)
+    print("wrote", len(out), "value range vectors")
+
+
+value_range_vectors()
+
 # the characterisation trace of the product's picture management (tests/dpbtrace.py; CPU, null device): MD5 of the trace text of every case.  It
 # pins what the code DOES, so it is written once and not again for a change that is meant to keep behaviour.  Only with --dpb-trace.
 if "--dpb-trace" in sys.argv[1:]:

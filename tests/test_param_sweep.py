@@ -21,6 +21,8 @@ def test_sweep_oracle_equals_generator():
     _sweep("150", "--seed", "5", "--concat")
     _sweep("300", "--seed", "61", "--extreme")
     _sweep("400", "--seed", "21", "--fields")  # field pictures (PAFF)
+    _sweep("300", "--seed", "71", "--ranges")  # weights, picture order count distances, vectors, 0 / 255 content and scaling lists at the ends of their ranges
+    _sweep("150", "--seed", "72", "--ranges", "--fields")
 
 
 @pytest.mark.gpu
@@ -28,6 +30,7 @@ def test_sweep_oracle_equals_generator():
                                   ("150", "--seed", "5", "--concat"), ("150", "--seed", "13", "--concat", "--split"), ("40", "--seed", "9", "--big"),
                                   ("250", "--seed", "41", "--xwgs"), ("300", "--seed", "61", "--extreme"),
                                   ("250", "--seed", "21", "--fields"), ("200", "--seed", "22", "--fields", "--split"), ("100", "--seed", "23", "--fields", "--xwgs"),
-                                  ("60", "--seed", "24", "--fields", "--big")])
+                                  ("60", "--seed", "24", "--fields", "--big"),
+                                  ("300", "--seed", "71", "--ranges"), ("150", "--seed", "72", "--ranges", "--fields"), ("150", "--seed", "73", "--ranges", "--split")])
 def test_gpu_sweep_equals_generator(args):
     _sweep(*args, "--gpu")

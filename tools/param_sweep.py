@@ -6,6 +6,8 @@ generator's reconstruction bit for bit.  Usage: param_sweep.py [trials] [--gpu] 
   --batch B (GPU): B streams of different recipes and sizes side by side in one decoder per trial;
   --fields: field-picture (PAFF) recipes -- every frame as two field pictures, or picture-adaptively a frame or two fields; with --split the
   pieces are whole PICTURES, so the two fields of a frame may arrive in different calls;  --pocdelta: frame pictures whose bottom field has its own picture order count;
+  --ranges: on top of the recipe, explicit weights over their whole coded range, picture order counts 2 * N apart, vectors out to the limits of
+  Table A-1, a 0 / 255 source, coded scaling lists in SPS and PPS (composes with --fields, --split, --xwgs, --extreme);
   --split (GPU): every stream is fed in several calls, a random number of access units at a time (state that must survive a batch boundary:
   reference pictures and their marking, picture order counts, co-located motion, frame_num gap bookkeeping, parameter sets)."""
 import os, sys, time
@@ -24,6 +26,7 @@ EXTREME = "--extreme" in sys.argv  # the corners of the value ranges: QP 0..51, 
 BIG = "--big" in sys.argv  # pictures wider than 64 macroblocks (rows of more than one 64-macroblock chunk), more slices
 FIELDS = "--fields" in sys.argv  # PAFF recipes: every frame as two field pictures, or a frame / two fields picture by picture
 POCD = "--pocdelta" in sys.argv  # bottom_field_pic_order_in_frame_present_flag = 1: the bottom field of every frame picture at its own count (before or after the top field)
+RANGES = "--ranges" in sys.argv  # the ends of the value ranges of inter prediction and dequantisation: wp_range, poc_step, mv_reach / mv_margin, contrast, coded scaling lists
 CONCAT = "--concat" in sys.argv  # two recipes back to back in one stream: new parameter sets, entropy coder, slice groups, picture size at the second IDR picture
 args = [a for a in args if a not in (str(seed0), str(BATCH))] or args[:1]
 rng = np.random.default_rng(seed0)
@@ -86,6 +89,17 @@ def draw():
         kw["weighted_pred"] = pick(0, 0, 1, 2)
     if POCD:
         kw["poc_bottom_delta"] = pick(-1, -1, 1, 2, 4)
+    if RANGES:  # (drawn last: the recipes of the other modes stay what they were)
+        if kw["profile_idc"] != 66:
+            kw["weighted_pred"] = pick(0, 1, 1, 2)
+            kw["wp_range"] = pick(0, 1, 1, 2)
+        kw["poc_step"] = pick(0, 0, 2, 15, 20, 31)
+        # (temporal direct under a B pyramid scales co-located vectors by more than 1: only vectors of ordinary length keep the result inside Table A-1)
+        if rng.random() < 0.5 and not (kw.get("direct_temporal") and kw.get("b_pyramid")):
+            kw.update(mv_reach=pick(300, 2000, 8000), mv_margin=pick(24, 100, 500, 2000))
+        kw["contrast"] = pick(0, 0, 1)
+        if kw["profile_idc"] == 100:
+            kw["scaling_matrix"] = pick(0, 1, 2, 3, 3)
     return kw
 
 
