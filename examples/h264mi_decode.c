@@ -1,11 +1,12 @@
 /*
  * examples/h264mi_decode.c -- the C ABI from plain C: decode an Annex-B file to raw I420 on the GPU.
  *
- *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--conceal...] [--nv12 | --rgb]
+ *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--conceal...] [--nv12 | --rgb] [--scale WxH[:area]]
  *
  * --nv12 / --rgb write NV12 / tight R, G, B bytes instead of I420: the frames are converted on the device (h264mi_batch_convert_device into a
- * device buffer, matrix and range from each frame's own SPS) and copied to the host from there.  Those two calls are the only HIP this file
- * needs; they are declared below, so it still builds without the HIP headers.
+ * device buffer, matrix and range from each frame's own SPS) and copied to the host from there.  --scale WxH writes every frame at W x H instead of
+ * its display size (h264mi_batch_scale_device: bilinear, or the area filter with ":area"; I420 unless --nv12 / --rgb is given).  The HIP calls of these
+ * paths are the only HIP this file needs; they are declared below, so it still builds without the HIP headers.
  *
  * The file includes nothing but include/h264mi.h and the C library.
  *
@@ -37,10 +38,21 @@ static int fail(const char *what, int code) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb]\n", argv[0]);
+        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb] [--scale WxH[:area]]\n", argv[0]);
         return 2;
     }
-    int format = H264MI_FMT_I420; /* --nv12 / --rgb (last argument): the output format */
+    int scale_w = 0, scale_h = 0, scale_filter = H264MI_SCALE_BILINEAR; /* --scale WxH[:area] (the last two arguments): every frame at W x H */
+    if (argc > 4 && !strcmp(argv[argc - 2], "--scale")) {
+        char tail[8] = "";
+        const int got = sscanf(argv[argc - 1], "%dx%d%7s", &scale_w, &scale_h, tail);
+        if (got < 2 || scale_w < 1 || scale_h < 1 || (got == 3 && strcmp(tail, ":area"))) {
+            fprintf(stderr, "--scale %s: expected WxH or WxH:area\n", argv[argc - 1]);
+            return 2;
+        }
+        if (got == 3) scale_filter = H264MI_SCALE_AREA;
+        argc -= 2;
+    }
+    int format = H264MI_FMT_I420; /* --nv12 / --rgb (last argument but for --scale): the output format */
     if (argc > 3 && !strcmp(argv[argc - 1], "--nv12")) format = H264MI_FMT_NV12, argc--;
     else if (argc > 3 && !strcmp(argv[argc - 1], "--rgb")) format = H264MI_FMT_RGB24, argc--;
     int conceal = 0; /* --conceal (last argument but for the format): h264mi_config.conceal_errors */
@@ -167,21 +179,26 @@ int main(int argc, char **argv) {
                 h264mi_stream_frame_count(dec, 0, &k);
                 const size_t need = H264MI_I420_SIZE(info.coded_width, info.coded_height);
                 if (need > frame_cap) frame = (uint8_t *)realloc(frame, frame_cap = need);
-                if (format != H264MI_FMT_I420) { /* one launch converts the batch; csc 0: matrix and range of each frame's own SPS, nearest chroma */
+                if (format != H264MI_FMT_I420 || scale_w) { /* one launch converts (and scales) the batch; csc 0: matrix and range of each frame's own SPS, nearest chroma */
                     size_t bytes = 0;
                     /* the size query: with cap 0 the call resolves and sizes every frame, sets bytes, launches nothing and returns H264MI_ECAPACITY (or
                      * H264MI_OK for an empty batch) -- the destination is never touched, it only has to be non-NULL, so before the device buffer exists
                      * the host buffer's address stands in for it */
-                    r = h264mi_batch_convert_device(dec, 0, format, H264MI_CSC_AUTO, dev ? dev : (void *)frame, 0, &bytes);
-                    if (r != H264MI_OK && r != H264MI_ECAPACITY) return fail("h264mi_batch_convert_device", r);
+                    const char *what = scale_w ? "h264mi_batch_scale_device" : "h264mi_batch_convert_device";
+                    r = scale_w ? h264mi_batch_scale_device(dec, 0, format, H264MI_CSC_AUTO, scale_w, scale_h, scale_filter, dev ? dev : (void *)frame, 0, &bytes)
+                                : h264mi_batch_convert_device(dec, 0, format, H264MI_CSC_AUTO, dev ? dev : (void *)frame, 0, &bytes);
+                    if (r != H264MI_OK && r != H264MI_ECAPACITY) return fail(what, r);
                     if (bytes > dev_cap) {
                         if (dev) hipFree(dev);
                         if (hipMalloc(&dev, dev_cap = bytes) != 0) return fail("hipMalloc", H264MI_ENOMEM);
                     }
                     if (bytes > frame_cap) frame = (uint8_t *)realloc(frame, frame_cap = bytes);
-                    if (bytes && (r = h264mi_batch_convert_device(dec, 0, format, H264MI_CSC_AUTO, dev, dev_cap, &bytes)) != H264MI_OK)
-                        return fail("h264mi_batch_convert_device", r);
-                    if ((r = h264mi_batch_sync(dec)) != H264MI_OK) return fail("h264mi_batch_sync", r); /* the conversion is asynchronous on the decoder's stream */
+                    if (bytes) {
+                        r = scale_w ? h264mi_batch_scale_device(dec, 0, format, H264MI_CSC_AUTO, scale_w, scale_h, scale_filter, dev, dev_cap, &bytes)
+                                    : h264mi_batch_convert_device(dec, 0, format, H264MI_CSC_AUTO, dev, dev_cap, &bytes);
+                        if (r != H264MI_OK) return fail(what, r);
+                    }
+                    if ((r = h264mi_batch_sync(dec)) != H264MI_OK) return fail("h264mi_batch_sync", r); /* the launch is asynchronous on the decoder's stream */
                     if (bytes && hipMemcpy(frame, dev, bytes, 2 /* hipMemcpyDeviceToHost */) != 0) return fail("hipMemcpy", H264MI_EDEVICE);
                     fwrite(frame, 1, bytes, out);
                 } else

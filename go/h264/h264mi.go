@@ -523,7 +523,7 @@ func (d *Decoder) PackBatch(stream int, dst unsafe.Pointer, capBytes int) (int, 
 // Output formats and colour conversion (K7; include/h264mi.h "Output formats").  Like the rest of this file these wrappers were written
 // blind: no Go toolchain was at hand to compile them.
 const (
-	FmtI420  = 0 // H264MI_FMT_I420: what PackBatch writes; only OutputSize accepts it
+	FmtI420  = 0 // H264MI_FMT_I420: what PackBatch writes; OutputSize, ScaleFrame and ScaleBatch accept it
 	FmtNV12  = 1 // H264MI_FMT_NV12
 	FmtRGB24 = 2 // H264MI_FMT_RGB24: h x w x 3 bytes R, G, B
 	FmtRGBP  = 3 // H264MI_FMT_RGBP: three planes R, G, B
@@ -567,5 +567,48 @@ func (d *Decoder) ConvertFrame(stream, frame, format, csc int, dst unsafe.Pointe
 func (d *Decoder) ConvertBatch(stream, format, csc int, dst unsafe.Pointer, capBytes int) (int, error) {
 	var n C.size_t
 	err := status(C.h264mi_batch_convert_device(d.h, C.int32_t(stream), C.int32_t(format), C.int32_t(csc), dst, C.size_t(capBytes), &n))
+	return int(n), err
+}
+
+// Scaled output (K8; include/h264mi.h "Scaled output").  Written blind like the wrappers above: no Go toolchain was at hand to compile them.
+const (
+	ScaleBilinear = 0 // H264MI_SCALE_BILINEAR
+	ScaleArea     = 1 // H264MI_SCALE_AREA: downscaling only
+)
+
+// ScaleTaps: the scaling rule for output index i of an axis of nIn samples scaled to nOut -- tap t reads source sample
+// min(first + t, nIn - 1) with weights[t] -- from the library, without a decoder or a device.
+func ScaleTaps(filter, nIn, nOut, i int) (first int, weights []int32, err error) {
+	var f, n C.int32_t
+	var two [2]C.int32_t
+	r := C.h264mi_scale_taps(C.int32_t(filter), C.int32_t(nIn), C.int32_t(nOut), C.int32_t(i), &f, &n, &two[0], 2)
+	buf := two[:]
+	if r == C.H264MI_ECAPACITY { // n says how many there are
+		buf = make([]C.int32_t, int(n))
+		r = C.h264mi_scale_taps(C.int32_t(filter), C.int32_t(nIn), C.int32_t(nOut), C.int32_t(i), &f, &n, &buf[0], n)
+	}
+	if err = status(r); err != nil {
+		return 0, nil, err
+	}
+	weights = make([]int32, int(n))
+	for t := range weights {
+		weights[t] = int32(buf[t])
+	}
+	return int(f), weights, nil
+}
+
+// ScaleFrame scales one frame of the last batch to outW x outH and converts it into device memory `dst` (asynchronous on the decoder's stream).
+func (d *Decoder) ScaleFrame(stream, frame, format, csc, outW, outH, filter int, dst unsafe.Pointer, capBytes int) error {
+	return status(C.h264mi_frame_scale_device(d.h, C.int32_t(stream), C.int32_t(frame), C.int32_t(format), C.int32_t(csc), C.int32_t(outW), C.int32_t(outH),
+		C.int32_t(filter), dst, C.size_t(capBytes)))
+}
+
+// ScaleBatch is ConvertBatch with an output size: every frame of the last batch (stream < 0: all streams, stream-major) cropped, scaled to
+// outW x outH whatever its display size, and converted (FmtI420 too) into device memory `dst` with one kernel launch; returns the byte count
+// (also when capBytes is too small): frames x OutputSize(format, outW, outH).
+func (d *Decoder) ScaleBatch(stream, format, csc, outW, outH, filter int, dst unsafe.Pointer, capBytes int) (int, error) {
+	var n C.size_t
+	err := status(C.h264mi_batch_scale_device(d.h, C.int32_t(stream), C.int32_t(format), C.int32_t(csc), C.int32_t(outW), C.int32_t(outH), C.int32_t(filter),
+		dst, C.size_t(capBytes), &n))
 	return int(n), err
 }

@@ -8,7 +8,8 @@ from .h264 import (  # noqa: F401
     NALU_TYPE_NAMES, PPS, SPS, Decoder, NalUnit, NewNalUnit, NewPPS, NewSPS, NewSliceContext, SliceContext, SliceHeader,
     VideoStream, read_nal_units, MapUnitToSliceGroupMap, MbToSliceGroupMap, nextMbAddress, AccessUnitSplitter, DisplayOrder, H264Reader, handleConnection, ByteStreamReader, BatchServer,
     CONCEAL_SLICES, CONCEAL_PICTURES, CONCEAL_FIELDS, CONCEAL_IDR, CONCEAL_LONE_FIELDS, CONCEAL_MAX_GAP,
-    FMT_I420, FMT_NV12, FMT_RGB24, FMT_RGBP, CSC_AUTO, CSC_BT601, CSC_BT709, CSC_FULL_RANGE, CSC_CHROMA_BILINEAR)
+    FMT_I420, FMT_NV12, FMT_RGB24, FMT_RGBP, CSC_AUTO, CSC_BT601, CSC_BT709, CSC_FULL_RANGE, CSC_CHROMA_BILINEAR,
+    SCALE_BILINEAR, SCALE_AREA, scale_taps)
 from .mbtype import (  # noqa: F401
     MB_TYPE_INFERRED, ISliceMbType, SISliceMbType, PSliceMbType, BSliceMbType, MbTypeName, MbPartPredMode, NumMbPart, PicWidthInMbs,
     PicHeightInMapUnits, PicSizeInMapUnits, FrameHeightInMbs, PicHeightInMbs, PicSizeInMbs, SubWidthC, SubHeightC, MbWidthC, MbHeightC,

@@ -121,6 +121,9 @@ def load():
         "h264mi_frame_colour": [vp, I32, I32, P(I32), P(I32)],
         "h264mi_frame_convert_device": [vp, I32, I32, I32, I32, vp, SZ],
         "h264mi_batch_convert_device": [vp, I32, I32, I32, vp, SZ, P(SZ)],
+        "h264mi_scale_taps": [I32, I32, I32, I32, P(I32), P(I32), P(I32), I32],
+        "h264mi_frame_scale_device": [vp, I32, I32, I32, I32, I32, I32, I32, vp, SZ],
+        "h264mi_batch_scale_device": [vp, I32, I32, I32, I32, I32, I32, vp, SZ, P(SZ)],
         "h264mi_frame_read_mbrecs": [vp, I32, I32, vp, SZ],
         "h264mi_frame_read_mbmv1": [vp, I32, I32, vp, SZ],
         "h264mi_decoder_set_profiling": [vp, I32],
@@ -161,4 +164,5 @@ EXPORTS = ["h264mi_annexb_scan", "h264mi_nal_parse", "h264mi_sps_parse", "h264mi
            "h264mi_last_launch_times", "h264mi_batch_pack_device", "h264mi_stream_reset", "h264mi_stream_status", "h264mi_decoder_set_isolation", "h264mi_frame_get_info", "h264mi_stream_output_order", "h264mi_decoder_memory", "h264mi_frame_read_mbmv1", "h264mi_decoder_coef_pool", "h264mi_decoder_unpinned_failures",
            "h264mi_slice_starts_picture", "h264mi_pps_slice_group_ids", "h264mi_map_unit_to_slice_group_map", "h264mi_mb_to_slice_group_map", "h264mi_next_mb_address",
            "h264mi_frame_concealed", "h264mi_decoder_concealed", "h264mi_decoder_concealed_pictures", "h264mi_decoder_concealed_fields",
-           "h264mi_output_size", "h264mi_csc_resolve", "h264mi_frame_colour", "h264mi_frame_convert_device", "h264mi_batch_convert_device"]
+           "h264mi_output_size", "h264mi_csc_resolve", "h264mi_frame_colour", "h264mi_frame_convert_device", "h264mi_batch_convert_device",
+           "h264mi_scale_taps", "h264mi_frame_scale_device", "h264mi_batch_scale_device"]

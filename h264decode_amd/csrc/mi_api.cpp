@@ -345,6 +345,11 @@ struct h264mi_decoder {
     size_t conv_cap[2] = {0, 0};
     hipEvent_t ev_conv[2] = {nullptr, nullptr};
     int conv_slot = 0;
+    // K8 descriptor tables: the same discipline
+    ScaleDesc *h_scale[2] = {nullptr, nullptr}, *d_scale[2] = {nullptr, nullptr};
+    size_t scale_cap[2] = {0, 0};
+    hipEvent_t ev_scale[2] = {nullptr, nullptr};
+    int scale_slot = 0;
     std::vector<float> launch_ms[4]; // duration of every launch of the last profiled pass, per kernel
 };
 
@@ -466,6 +471,9 @@ static void free_all(h264mi_decoder *d) {
         if (d->h_conv[i]) hipHostFree(d->h_conv[i]);
         if (d->d_conv[i]) hipFree(d->d_conv[i]);
         if (d->ev_conv[i]) hipEventDestroy(d->ev_conv[i]);
+        if (d->h_scale[i]) hipHostFree(d->h_scale[i]);
+        if (d->d_scale[i]) hipFree(d->d_scale[i]);
+        if (d->ev_scale[i]) hipEventDestroy(d->ev_scale[i]);
     }
     if (d->d_frames) hipFree(d->d_frames);
     if (d->d_tables) hipFree(d->d_tables);
@@ -2476,6 +2484,154 @@ extern "C" int32_t h264mi_batch_convert_device(h264mi_decoder *d, int32_t stream
         if (stream < 0 || stream == si)
             for (int f = 0; f < static_cast<int>(g.out[si].size()); f++) frames.push_back({si, f});
     return convert_frames(d, frames, format, csc, dst, cap, bytes);
+}
+
+// ---------------------------------------------------------------- scaled output (K8): the rule of include/h264mi.h, "Scaled output"
+// bilinear: position of output index i on an axis of n_in samples scaled to n_out -- a in the high bits, f in bits 8 .. 15
+static inline void bilinear_axis(int n_in, int n_out, uint32_t *step, int32_t *half) {
+    *step = (static_cast<uint32_t>(n_in) << 16) / static_cast<uint32_t>(n_out); // n_in <= 16384: fits
+    *half = static_cast<int32_t>(*step >> 1) - 32768;
+}
+
+extern "C" int32_t h264mi_scale_taps(int32_t filter, int32_t n_in, int32_t n_out, int32_t i, int32_t *first, int32_t *count, int32_t *weights, int32_t cap) {
+    if (!first || !count || !weights || cap < 0) return H264MI_EINVAL;
+    if (filter != H264MI_SCALE_BILINEAR && filter != H264MI_SCALE_AREA) {
+        set_error("scale filter %d: not H264MI_SCALE_BILINEAR or H264MI_SCALE_AREA", filter);
+        return H264MI_EINVAL;
+    }
+    if (n_in < 1 || n_in > H264MI_SCALE_MAX || n_out < 1 || n_out > H264MI_SCALE_MAX || i < 0 || i >= n_out) {
+        set_error("scale taps: n_in %d, n_out %d must be 1 .. %d and 0 <= i (%d) < n_out", n_in, n_out, H264MI_SCALE_MAX, i);
+        return H264MI_EINVAL;
+    }
+    if (filter == H264MI_SCALE_BILINEAR) {
+        uint32_t step;
+        int32_t half;
+        bilinear_axis(n_in, n_out, &step, &half);
+        const int32_t P = std::min(std::max(static_cast<int32_t>(i * step) + half, 0), (n_in - 1) << 16);
+        *first = P >> 16, *count = 2;
+        if (cap < 2) return H264MI_ECAPACITY;
+        const int32_t f = (P >> 8) & 255;
+        weights[0] = 256 - f, weights[1] = f;
+        return H264MI_OK;
+    }
+    if (n_out > n_in) {
+        set_error("H264MI_SCALE_AREA only scales down: %d -> %d", n_in, n_out);
+        return H264MI_EINVAL;
+    }
+    const int32_t lo = i * n_in, hi = lo + n_in; // <= 2^28
+    const int32_t k0 = lo / n_out, k1 = (hi - 1) / n_out;
+    *first = k0, *count = k1 - k0 + 1;
+    if (cap < *count) return H264MI_ECAPACITY;
+    for (int32_t k = k0; k <= k1; k++) weights[k - k0] = std::min(hi, (k + 1) * n_out) - std::max(lo, k * n_out);
+    return H264MI_OK;
+}
+
+// K8 over a list of frames: convert_frames' discipline.  Every frame is checked, resolved and sized before anything is launched.
+static int scale_frames(h264mi_decoder *d, const std::vector<std::pair<int, int>> &frames /* (stream, frame) */, int format, int csc, int ow, int oh, int filter, void *dst,
+                        size_t cap, size_t *bytes) {
+    if (format != H264MI_FMT_I420 && format != H264MI_FMT_NV12 && format != H264MI_FMT_RGB24 && format != H264MI_FMT_RGBP) {
+        set_error("output format %d: not H264MI_FMT_I420, _NV12, _RGB24 or _RGBP", format);
+        return H264MI_EINVAL;
+    }
+    const bool plain = format == H264MI_FMT_I420 || format == H264MI_FMT_NV12;
+    if (plain && csc != 0) {
+        set_error("H264MI_FMT_I420 and H264MI_FMT_NV12 convert nothing: csc must be 0, not %d", csc);
+        return H264MI_EINVAL;
+    }
+    if (filter != H264MI_SCALE_BILINEAR && filter != H264MI_SCALE_AREA) {
+        set_error("scale filter %d: not H264MI_SCALE_BILINEAR or H264MI_SCALE_AREA", filter);
+        return H264MI_EINVAL;
+    }
+    if (ow < 1 || ow > H264MI_SCALE_MAX || oh < 1 || oh > H264MI_SCALE_MAX) {
+        set_error("output size %d x %d: both must be 1 .. %d", ow, oh, H264MI_SCALE_MAX);
+        return H264MI_EINVAL;
+    }
+    int probe;
+    int r = h264mi_csc_resolve(csc, 1, 0, 16, 16, &probe); // is csc legal at all (whatever the frames are, and if there are none)
+    if (r != H264MI_OK) return r;
+    GUARD(d);
+    std::vector<ScaleDesc> descs(frames.size());
+    size_t one = 0, off = 0;
+    h264mi_output_size(format, ow, oh, &one);
+    for (size_t i = 0; i < frames.size(); i++) {
+        uint8_t *p;
+        const OutFrame *of;
+        int x0, y0, w, h, res = 0;
+        r = frame_ptrs(d, frames[i].first, frames[i].second, &p, &of);
+        if (r != H264MI_OK) return r;
+        crop_rect(of, 1, &x0, &y0, &w, &h);
+        if (filter == H264MI_SCALE_AREA) {
+            if (ow > w || oh > h) {
+                set_error("H264MI_SCALE_AREA only scales down: frame %d of stream %d is %d x %d, the output %d x %d", frames[i].second, frames[i].first, w, h, ow, oh);
+                return H264MI_EINVAL;
+            }
+            const uint64_t px = static_cast<uint64_t>(w) * h;
+            if (255 * px + (px >> 1) >= (static_cast<uint64_t>(1) << 32)) { // the largest weighted sum and its rounding term
+                set_error("H264MI_SCALE_AREA sums in 32 bits and needs 255 * w * h + ((w * h) >> 1) < 2^32: frame %d of stream %d is %d x %d", frames[i].second, frames[i].first, w, h);
+                return H264MI_EUNSUPPORTED;
+            }
+        }
+        if (!plain) { // from the frame's SPS and its display (source) size, never from the output size
+            r = h264mi_csc_resolve(csc, of->matrix_coefficients, of->video_full_range, w, h, &res);
+            if (r != H264MI_OK) return r;
+        }
+        ScaleDesc &sc = descs[i];
+        sc.src = reinterpret_cast<uint64_t>(p), sc.dst_off = off;
+        sc.W = of->wmb * 16, sc.H = of->hmb * 16, sc.x0 = x0, sc.y0 = y0, sc.w = w, sc.h = h;
+        sc.format = format, sc.filter = filter;
+        sc.cset = plain ? 0 : 2 * ((res & 15) - 1) + ((res & H264MI_CSC_FULL_RANGE) ? 1 : 0);
+        sc.bilinear = (res & H264MI_CSC_CHROMA_BILINEAR) ? 1 : 0;
+        bilinear_axis(w, ow, &sc.step[0], &sc.half[0]);
+        bilinear_axis(h, oh, &sc.step[1], &sc.half[1]);
+        bilinear_axis((w + 1) / 2, (ow + 1) / 2, &sc.step[2], &sc.half[2]);
+        bilinear_axis((h + 1) / 2, (oh + 1) / 2, &sc.step[3], &sc.half[3]);
+        off += one;
+    }
+    if (bytes) *bytes = off;
+    if (off > cap) return H264MI_ECAPACITY;
+    if (frames.empty()) return H264MI_OK;
+    const int ps = d->scale_slot ^= 1;
+    if (!d->ev_scale[ps]) HIP_TRY(hipEventCreateWithFlags(&d->ev_scale[ps], hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(d->ev_scale[ps])); // the launch that used this table (two calls ago) has read it
+    if (frames.size() > d->scale_cap[ps]) {
+        if (d->h_scale[ps]) hipHostFree(d->h_scale[ps]);
+        if (d->d_scale[ps]) hipFree(d->d_scale[ps]);
+        d->h_scale[ps] = nullptr, d->d_scale[ps] = nullptr, d->scale_cap[ps] = 0;
+        const size_t n = std::max<size_t>(frames.size(), 64);
+        HIP_TRY(hipHostMalloc(&d->h_scale[ps], sizeof(ScaleDesc) * n));
+        HIP_TRY(hipMalloc(&d->d_scale[ps], sizeof(ScaleDesc) * n));
+        d->scale_cap[ps] = n;
+    }
+    memcpy(d->h_scale[ps], descs.data(), sizeof(ScaleDesc) * frames.size());
+    // (in order on the decoder's stream, which has waited for the reconstruction of the last executed pass: h264mi_batch_execute)
+    HIP_TRY(hipMemcpyAsync(d->d_scale[ps], d->h_scale[ps], sizeof(ScaleDesc) * frames.size(), hipMemcpyHostToDevice, d->stream));
+    // about 256 items of 2 x 16 output pixels per block: 640 wide: 6 row pairs x 40 groups; 224 wide: 18 x 14
+    const int ngroups = (ow + 15) / 16, npairs = (oh + 1) / 2;
+    const int pairs_per_block = std::max(1, std::min(256 / ngroups, npairs));
+    const dim3 grid(static_cast<uint32_t>(frames.size()), (npairs + pairs_per_block - 1) / pairs_per_block);
+    if (filter == H264MI_SCALE_AREA) hipLaunchKernelGGL(k_scale_area, grid, dim3(256), 0, d->stream, d->d_scale[ps], static_cast<uint8_t *>(dst), ow, oh, pairs_per_block);
+    else hipLaunchKernelGGL(k_scale, grid, dim3(256), 0, d->stream, d->d_scale[ps], static_cast<uint8_t *>(dst), ow, oh, pairs_per_block);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(d->ev_scale[ps], d->stream));
+    d->last_pack = d->ev_scale[ps];
+    return H264MI_OK;
+}
+
+extern "C" int32_t h264mi_frame_scale_device(h264mi_decoder *d, int32_t stream, int32_t frame, int32_t format, int32_t csc, int32_t out_w, int32_t out_h, int32_t filter,
+                                             void *dst, size_t cap) {
+    if (!d || !dst) return H264MI_EINVAL;
+    return scale_frames(d, {{stream, frame}}, format, csc, out_w, out_h, filter, dst, cap, nullptr);
+}
+
+extern "C" int32_t h264mi_batch_scale_device(h264mi_decoder *d, int32_t stream, int32_t format, int32_t csc, int32_t out_w, int32_t out_h, int32_t filter, void *dst,
+                                             size_t cap, size_t *bytes) {
+    if (!d || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    std::vector<std::pair<int, int>> frames;
+    const Stage &g = d->stage[d->exec];
+    for (int si = 0; si < static_cast<int>(g.out.size()); si++)
+        if (stream < 0 || stream == si)
+            for (int f = 0; f < static_cast<int>(g.out[si].size()); f++) frames.push_back({si, f});
+    return scale_frames(d, frames, format, csc, out_w, out_h, filter, dst, cap, bytes);
 }
 
 extern "C" int32_t h264mi_frame_read_mbrecs(h264mi_decoder *d, int32_t stream, int32_t frame, uint8_t *rec, size_t cap) {

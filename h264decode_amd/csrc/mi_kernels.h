@@ -146,6 +146,23 @@ typedef struct {
     uint32_t pad;
 } ConvDesc;
 extern "C" __global__ void k_convert(const ConvDesc *descs, uint8_t *dst, int pairs_per_block);
+// K8 (k_scale.hip): crop + scale a list of frames to ONE output size ow x oh + convert, by the integer rule of include/h264mi.h ("Scaled output");
+// grid = (frames, ceil(ceil(oh / 2) / pairs_per_block)), block = 256; a thread owns two OUTPUT luma rows x 16 columns and the chroma under them
+typedef struct {
+    uint64_t src;     // as PackDesc
+    uint64_t dst_off; // byte offset of the scaled frame in the destination buffer
+    uint32_t W, H, x0, y0, w, h; // the source: coded size, crop origin, display size
+    uint32_t format;   // H264MI_FMT_I420 / _NV12 / _RGB24 / _RGBP
+    uint32_t cset;     // as ConvDesc (unused for I420 and NV12)
+    uint32_t bilinear; // chroma upsampling of the SCALED chroma planes, as ConvDesc
+    uint32_t filter;   // H264MI_SCALE_BILINEAR / _AREA (uniform per launch: it selects the kernel)
+    // bilinear, per axis (luma x, luma y, chroma x, chroma y): step = (n_in << 16) / n_out and the half-step offset (step >> 1) - 32768,
+    // computed once per frame on the host: the kernel divides nothing in this mode
+    uint32_t step[4];
+    int32_t half[4];
+} ScaleDesc;
+extern "C" __global__ void k_scale(const ScaleDesc *descs, uint8_t *dst, int ow, int oh, int pairs_per_block);      // H264MI_SCALE_BILINEAR
+extern "C" __global__ void k_scale_area(const ScaleDesc *descs, uint8_t *dst, int ow, int oh, int pairs_per_block); // H264MI_SCALE_AREA
 
 #ifndef MI_INTRA_WAVES
 #define MI_INTRA_WAVES 16 /* 1024 threads, 128 VGPRs per wavefront: the kernels need 120 once nothing lane-dependent is hoisted out of the macroblock loop */

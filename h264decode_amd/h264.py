@@ -205,6 +205,8 @@ FMT_I420, FMT_NV12, FMT_RGB24, FMT_RGBP = 0, 1, 2, 3  # H264MI_FMT_*: output for
 CSC_AUTO, CSC_BT601, CSC_BT709 = 0, 1, 2              # H264MI_CSC_*: the matrix (AUTO: from each frame's own SPS) ...
 CSC_FULL_RANGE, CSC_CHROMA_BILINEAR = 16, 32          # ... | full range (explicit matrix only) | bilinear chroma upsampling (default: nearest)
 _FMT_NAMES = {"i420": FMT_I420, "nv12": FMT_NV12, "rgb24": FMT_RGB24, "rgbp": FMT_RGBP}
+SCALE_BILINEAR, SCALE_AREA = 0, 1                     # H264MI_SCALE_*: filters of scale_frame / scale_batch / frames_tensor(size=...)
+_FILTER_NAMES = {"bilinear": SCALE_BILINEAR, "area": SCALE_AREA}
 
 
 def _fmt(fmt):
@@ -213,6 +215,29 @@ def _fmt(fmt):
             raise H264MIError(-1, "unknown output format %r (i420, nv12, rgb24, rgbp)" % (fmt,))
         return _FMT_NAMES[fmt.lower()]
     return int(fmt)
+
+
+def _filter(filter):
+    if isinstance(filter, str):
+        if filter.lower() not in _FILTER_NAMES:
+            raise H264MIError(-1, "unknown scale filter %r (bilinear, area)" % (filter,))
+        return _FILTER_NAMES[filter.lower()]
+    return int(filter)
+
+
+def scale_taps(filter, n_in, n_out, i):
+    """The scaling rule of include/h264mi.h for output index i of an axis of n_in samples scaled to n_out, from the library (h264mi_scale_taps; no
+    GPU): ([source indices], [weights]).  Bilinear: two taps with weights (256 - f, f); area: the overlapping source samples and their overlaps."""
+    L = _lib.load()
+    first, count = ctypes.c_int32(0), ctypes.c_int32(0)
+    one = (ctypes.c_int32 * 2)()
+    code = L.h264mi_scale_taps(_filter(filter), n_in, n_out, i, ctypes.byref(first), ctypes.byref(count), one, 2)
+    w = one
+    if code == -7:  # H264MI_ECAPACITY: *count says how many there are
+        w = (ctypes.c_int32 * count.value)()
+        code = L.h264mi_scale_taps(_filter(filter), n_in, n_out, i, ctypes.byref(first), ctypes.byref(count), w, count.value)
+    check(code)
+    return [min(first.value + t, n_in - 1) for t in range(count.value)], [w[t] for t in range(count.value)]
 
 
 def _frames_with_headroom(frames_per_batch, conceal_errors):
@@ -447,15 +472,45 @@ class Decoder:
         check(self._L.h264mi_batch_convert_device(self._h, stream, _fmt(fmt), csc, dst_ptr, cap, ctypes.byref(n)))
         return n.value
 
-    def frames_tensor(self, stream, fmt="rgbp", csc=0):
+    def scale_frame(self, stream, frame, dst_ptr, cap, fmt, size, csc=0, filter="bilinear"):
+        """K8 for one frame of the last executed batch: cropped, scaled to size = (ow, oh) and converted to `fmt` ("i420" too) into the DEVICE buffer
+        at dst_ptr (asynchronous on the decoder's stream).  filter: "bilinear" or "area" (downscaling only); csc as for convert_frame."""
+        check(self._L.h264mi_frame_scale_device(self._h, stream, frame, _fmt(fmt), csc, int(size[0]), int(size[1]), _filter(filter), dst_ptr, cap))
+
+    def scale_batch(self, dst_ptr, cap, fmt, size, csc=0, filter="bilinear", stream=-1):
+        """K8 in one launch: every frame of the last executed batch (of one stream, or of all streams, stream-major) cropped, scaled to
+        size = (ow, oh) whatever its display size, and converted to `fmt`, back to back in the DEVICE buffer at dst_ptr -- convert_batch's contract.
+        Returns the number of bytes: frames x output_size(fmt, ow, oh)."""
+        n = ctypes.c_size_t(0)
+        check(self._L.h264mi_batch_scale_device(self._h, stream, _fmt(fmt), csc, int(size[0]), int(size[1]), _filter(filter), dst_ptr, cap, ctypes.byref(n)))
+        return n.value
+
+    def frames_tensor(self, stream, fmt="rgbp", csc=0, size=None, filter="bilinear"):
         """The frames of `stream` of the last executed batch as one torch uint8 tensor on the decoder's device: [n, 3, h, w] ("rgbp"), [n, h, w, 3]
         ("rgb24") or [n, H264MI_I420_SIZE(w, h)] ("nv12"), converted by one K7 launch.  Raises ValueError if the stream's frames differ in display size.
+        With size = (ow, oh) the frames are scaled to that size by one K8 launch (`filter`: "bilinear" or "area"): the shapes are those with (ow, oh) for
+        (w, h), "i420" is a format too ([n, H264MI_I420_SIZE(ow, oh)]), frames of unlike display size are fine, and stream = -1 takes the frames of all
+        streams, stream-major.
         Ordering, both ways, by synchronising (no event is involved): the tensor comes from torch's caching allocator on torch's current stream, which may
         hand back a block that work still queued on that stream reads, and the conversion writes it on the decoder's stream -- so torch's current
         stream is SYNCHRONISED after the allocation and before the launch; and the decoder's stream is SYNCHRONISED (sync()) before the method returns,
-        so the tensor is complete for any torch stream.  A caller who cannot afford the two waits allocates for themselves and calls convert_batch."""
+        so the tensor is complete for any torch stream.  A caller who cannot afford the two waits allocates for themselves and calls convert_batch
+        or scale_batch."""
         import torch
         f = _fmt(fmt)
+        if size is not None:
+            ow, oh = int(size[0]), int(size[1])
+            n = sum(self.frame_count(s) for s in (range(self.max_streams) if stream < 0 else (stream,)))
+            shape = {FMT_I420: (n, self.i420_size(ow, oh)), FMT_NV12: (n, self.i420_size(ow, oh)), FMT_RGB24: (n, oh, ow, 3), FMT_RGBP: (n, 3, oh, ow)}.get(f)
+            if shape is None:
+                raise H264MIError(-1, "frames_tensor: format %r is not i420, nv12, rgb24 or rgbp" % (fmt,))
+            out = torch.empty(shape, dtype=torch.uint8, device="cuda:%d" % self.device)
+            if n:
+                torch.cuda.current_stream(out.device).synchronize()  # whatever still uses a recycled block has finished before K8 writes it
+                got = self.scale_batch(out.data_ptr(), out.numel(), f, (ow, oh), csc, filter, stream)
+                assert got == out.numel()
+                self.sync()
+            return out
         n = self.frame_count(stream)
         infos = [self.frame_info(stream, i) for i in range(n)]
         sizes = {(fi.width, fi.height) for fi in infos}

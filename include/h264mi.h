@@ -393,7 +393,7 @@ int32_t h264mi_batch_pack_device(h264mi_decoder *dec, int32_t stream, void *dst_
  *   H264MI_FMT_NV12   w * h luma bytes, then hc rows of wc (Cb, Cr) byte pairs                  H264MI_I420_SIZE(w, h) bytes
  *   H264MI_FMT_RGB24  h x w x 3 bytes R, G, B, tight                                           3 * w * h bytes
  *   H264MI_FMT_RGBP   three tight h x w planes R, G, B (torch's CHW)                            3 * w * h bytes
- * Any other format is H264MI_EINVAL (H264MI_FMT_I420 is what the pack calls above write; only h264mi_output_size accepts it).
+ * Any other format is H264MI_EINVAL (H264MI_FMT_I420 is what the pack calls above write; of the calls of this section only h264mi_output_size accepts it, the scale calls below do too).
  * csc, a small bit set: the matrix in the low four bits (H264MI_CSC_AUTO, _BT601, _BT709), H264MI_CSC_FULL_RANGE (only with an explicit matrix: with AUTO
  * the range comes from the stream), H264MI_CSC_CHROMA_BILINEAR (default: nearest).  For NV12 csc must be 0 -- nothing is converted.  Anything else is
  * H264MI_EINVAL.
@@ -443,6 +443,49 @@ int32_t h264mi_frame_convert_device(h264mi_decoder *dec, int32_t stream, int32_t
  * when stream = -1, stream-major) in decoding order, back to back; *bytes receives the total size (also on H264MI_ECAPACITY).  All frames are resolved
  * before anything is launched: one frame AUTO cannot resolve fails the call (H264MI_EUNSUPPORTED) with nothing written. */
 int32_t h264mi_batch_convert_device(h264mi_decoder *dec, int32_t stream, int32_t format, int32_t csc, void *dst_device, size_t cap, size_t *bytes);
+
+/* ---- Scaled output (K8): resize while converting, on the device ----
+ * A scaled frame is a function of the tight I420 frame, the output size ow x oh and the filter; a scaled and converted frame is the function of
+ * "Output formats" above applied to the scaled I420 frame of size ow x oh.  All arithmetic is integer, >> is a floor shift; this comment is the contract.
+ * Sizes: luma is scaled from w x h to ow x oh, each chroma plane from ceil(w / 2) x ceil(h / 2) to ceil(ow / 2) x ceil(oh / 2), per plane and per axis
+ * independently.  Source samples are those of the tight I420 frame: every clamp is at the edges of the display planes, coded samples outside the crop
+ * rectangle are never read.  Chroma planes are scaled as planes, centre-aligned: the siting of chroma_sample_loc_type is not modelled in the scaler
+ * (as for the upsampling above, only type 0 is, and only there).  In a monochrome stream the chroma is 128 and stays 128.  Frames are scaled as they are,
+ * whether coded as frame or field pictures.
+ * H264MI_SCALE_BILINEAR, for an axis of n_in samples scaled to n_out, output index i:
+ *   step = (n_in << 16) / n_out (floor);  P = i step + (step >> 1) - 32768, clamped to 0 .. (n_in - 1) << 16;  a = P >> 16;  f = (P >> 8) & 255;
+ *   b = min(a + 1, n_in - 1);  with (ax, bx, fx) of the column and (ay, by, fy) of the row the sample is
+ *   ((256 - fy) ((256 - fx) S[ay][ax] + fx S[ay][bx]) + fy ((256 - fx) S[by][ax] + fx S[by][bx]) + 32768) >> 16
+ *   -- one rounding; everything fits 32 bits for n_in, n_out <= 16384 (i step < n_in << 16 <= 2^30, the sum is below 2^24); n_out == n_in gives f = 0,
+ *   a = i: the identity.
+ * H264MI_SCALE_AREA, downscaling only (ow <= w and oh <= h for every frame of the call, else H264MI_EINVAL): output sample i of an axis weighs source
+ *   sample k by the overlap of [i n_in, (i + 1) n_in) with [k n_out, (k + 1) n_out): max(0, min((i + 1) n_in, (k + 1) n_out) - max(i n_in, k n_out)); the
+ *   weights of one output sample sum to n_in.  The sample is (sum_y wy sum_x wx S + ((w_p h_p) >> 1)) / (w_p h_p) with w_p x h_p the source plane: unsigned
+ *   32-bit arithmetic and one floor division per output sample.  That needs 255 w h + ((w h) >> 1) < 2^32 (the largest sum and its rounding term: about
+ *   16.8 million samples): a larger display size is H264MI_EUNSUPPORTED with the reason.  n_out == n_in is the identity.
+ * Formats: H264MI_FMT_I420 -- the scaled planes, tight, H264MI_I420_SIZE(ow, oh) bytes -- and _NV12, _RGB24, _RGBP: exactly the rule of "Output formats"
+ * applied to the scaled frame (the same coefficient sets; nearest or H264MI_CSC_CHROMA_BILINEAR upsampling of the SCALED chroma planes; csc must be 0 for
+ * I420 and NV12).  H264MI_CSC_AUTO resolves per frame from that frame's SPS and its display (source) size, never from the output size. */
+#define H264MI_SCALE_BILINEAR 0
+#define H264MI_SCALE_AREA 1
+#define H264MI_SCALE_MAX 16384 /* the largest out_w, out_h (and axis of h264mi_scale_taps) */
+/* The rule above for one output index of one axis, as a pure function (no decoder, no device): tap t (0 <= t < *count) reads source sample
+ * min(*first + t, n_in - 1) with weights[t].  Bilinear: two taps, a and b, with weights {256 - f, f} as they come out -- at the far clamp b is a again.
+ * Area: the overlapping source samples with their overlaps (they sum to n_in; at most ceil(n_in / n_out) + 1 of them).  *first and *count are also set
+ * on H264MI_ECAPACITY (cap < *count: nothing is written to weights).  H264MI_EINVAL: an unknown filter, n_in or n_out outside 1 .. H264MI_SCALE_MAX,
+ * i outside 0 .. n_out - 1, area with n_out > n_in. */
+int32_t h264mi_scale_taps(int32_t filter, int32_t n_in, int32_t n_out, int32_t i, int32_t *first, int32_t *count, int32_t *weights, int32_t cap);
+/* One frame of the last executed batch, cropped, scaled to out_w x out_h and converted on the device (K8) into the DEVICE buffer dst_device;
+ * cap >= h264mi_output_size(format, out_w, out_h).  Asynchronous on the decoder's stream, like h264mi_frame_convert_device. */
+int32_t h264mi_frame_scale_device(h264mi_decoder *dec, int32_t stream, int32_t frame, int32_t format, int32_t csc, int32_t out_w, int32_t out_h,
+                                  int32_t filter, void *dst_device, size_t cap);
+/* The same for every frame of the last executed batch in ONE launch -- h264mi_batch_convert_device's contract: frames of stream `stream` (or of all
+ * streams when stream = -1, stream-major) in decoding order, back to back; *bytes receives the total size (also on H264MI_ECAPACITY); nothing is written
+ * on failure.  Every frame comes out at out_w x out_h whatever its display size, so a batch of unlike streams is one uniform array of
+ * n * h264mi_output_size(format, out_w, out_h) bytes.  H264MI_EINVAL: out_w or out_h outside 1 .. H264MI_SCALE_MAX, an unknown filter, area upscaling in
+ * either axis of any frame of the call, an illegal format / csc pair.  All frames are checked and resolved before anything is launched. */
+int32_t h264mi_batch_scale_device(h264mi_decoder *dec, int32_t stream, int32_t format, int32_t csc, int32_t out_w, int32_t out_h, int32_t filter,
+                                  void *dst_device, size_t cap, size_t *bytes);
 
 /* Debug / test access to the intermediate macroblock records of a frame (host copy).
  * rec: 128 bytes per MB (layout: h264decode_amd/csrc/mi_types.h struct MbRec). */

@@ -143,6 +143,11 @@ static void client(int iters, unsigned seed) {
                 h264mi_frame_colour(dec, s, nf / 2, &mc, &fr);
                 h264mi_batch_convert_device(dec, (nf & 1) ? s : -1, 1 + nf % 3, nf % 3 ? (nf & 2) * 16 : 0, pix.data(), (nf & 4) ? pix.size() : 1000, &conv);
                 h264mi_frame_convert_device(dec, s, nf - 1, 3, H264MI_CSC_BT601 | H264MI_CSC_FULL_RANGE, pix.data(), pix.size());
+                // K8's host side (sizes, filters, area's downscale-only and 32-bit checks, AUTO per frame, capacity), chosen from nf in the same way
+                h264mi_batch_scale_device(dec, (nf & 1) ? s : -1, nf % 4, nf % 4 >= 2 ? (nf & 2) * 16 : 0, 1 + (nf * 37) % 300, 1 + (nf * 53) % 200, nf & 1, pix.data(),
+                                          (nf & 4) ? pix.size() : 1000, &conv);
+                h264mi_frame_scale_device(dec, s, nf - 1, 0, 0, 16384, 1, H264MI_SCALE_BILINEAR, pix.data(), pix.size());
+                h264mi_frame_scale_device(dec, s, 0, 3, H264MI_CSC_BT709, 8, 8, 2 - (nf & 3), pix.data(), pix.size());
                 if (rng() % 13 == 0) h264mi_stream_reset(dec, s);
             }
             if (rng() % 29 == 0) h264mi_decoder_reset(dec);
