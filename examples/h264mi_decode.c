@@ -1,11 +1,13 @@
 /*
  * examples/h264mi_decode.c -- the C ABI from plain C: decode an Annex-B file to raw I420 on the GPU.
  *
- *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--conceal...] [--nv12 | --rgb] [--scale WxH[:area]]
+ *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--conceal...] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH]
  *
  * --nv12 / --rgb write NV12 / tight R, G, B bytes instead of I420: the frames are converted on the device (h264mi_batch_convert_device into a
  * device buffer, matrix and range from each frame's own SPS) and copied to the host from there.  --scale WxH writes every frame at W x H instead of
- * its display size (h264mi_batch_scale_device: bilinear, or the area filter with ":area"; I420 unless --nv12 / --rgb is given).  The HIP calls of these
+ * its display size (h264mi_batch_scale_device: bilinear, or the area filter with ":area"; I420 unless --nv12 / --rgb is given).  --tensor WxH writes
+ * every frame as a model-input item instead (h264mi_batch_tensor_device): letterboxed into a W x H canvas on grey (114, 114, 114), float32 in three
+ * planes R, G, B, each value v / 255 (scale 1 / 255, bias 0), bilinear, matrix and range from each frame's own SPS.  The HIP calls of these
  * paths are the only HIP this file needs; they are declared below, so it still builds without the HIP headers.
  *
  * The file includes nothing but include/h264mi.h and the C library.
@@ -38,7 +40,7 @@ static int fail(const char *what, int code) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb] [--scale WxH[:area]]\n", argv[0]);
+        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH]\n", argv[0]);
         return 2;
     }
     int scale_w = 0, scale_h = 0, scale_filter = H264MI_SCALE_BILINEAR; /* --scale WxH[:area] (the last two arguments): every frame at W x H */
@@ -50,6 +52,19 @@ int main(int argc, char **argv) {
             return 2;
         }
         if (got == 3) scale_filter = H264MI_SCALE_AREA;
+        argc -= 2;
+    }
+    h264mi_tensor_spec tensor; /* --tensor WxH (the last two arguments, instead of --scale): every frame as a letterboxed float32 CHW item */
+    memset(&tensor, 0, sizeof(tensor));
+    if (!scale_w && argc > 4 && !strcmp(argv[argc - 2], "--tensor")) {
+        char tail[2] = "";
+        if (sscanf(argv[argc - 1], "%dx%d%1s", &tensor.out_w, &tensor.out_h, tail) != 2 || tensor.out_w < 1 || tensor.out_h < 1) {
+            fprintf(stderr, "--tensor %s: expected WxH\n", argv[argc - 1]);
+            return 2;
+        }
+        tensor.format = H264MI_FMT_RGBP, tensor.dtype = H264MI_DT_F32, tensor.csc = H264MI_CSC_AUTO;
+        tensor.filter = H264MI_SCALE_BILINEAR, tensor.fit = H264MI_FIT_LETTERBOX;
+        for (int c = 0; c < 3; c++) tensor.pad[c] = 114, tensor.scale[c] = 1.0f / 255.0f, tensor.bias[c] = 0.0f;
         argc -= 2;
     }
     int format = H264MI_FMT_I420; /* --nv12 / --rgb (last argument but for --scale): the output format */
@@ -179,7 +194,20 @@ int main(int argc, char **argv) {
                 h264mi_stream_frame_count(dec, 0, &k);
                 const size_t need = H264MI_I420_SIZE(info.coded_width, info.coded_height);
                 if (need > frame_cap) frame = (uint8_t *)realloc(frame, frame_cap = need);
-                if (format != H264MI_FMT_I420 || scale_w) { /* one launch converts (and scales) the batch; csc 0: matrix and range of each frame's own SPS, nearest chroma */
+                if (tensor.out_w) { /* one launch makes the items of the batch; the size query as below */
+                    size_t bytes = 0;
+                    r = h264mi_batch_tensor_device(dec, 0, &tensor, dev ? dev : (void *)frame, 0, &bytes);
+                    if (r != H264MI_OK && r != H264MI_ECAPACITY) return fail("h264mi_batch_tensor_device", r);
+                    if (bytes > dev_cap) {
+                        if (dev) hipFree(dev);
+                        if (hipMalloc(&dev, dev_cap = bytes) != 0) return fail("hipMalloc", H264MI_ENOMEM);
+                    }
+                    if (bytes > frame_cap) frame = (uint8_t *)realloc(frame, frame_cap = bytes);
+                    if (bytes && (r = h264mi_batch_tensor_device(dec, 0, &tensor, dev, dev_cap, &bytes)) != H264MI_OK) return fail("h264mi_batch_tensor_device", r);
+                    if ((r = h264mi_batch_sync(dec)) != H264MI_OK) return fail("h264mi_batch_sync", r);
+                    if (bytes && hipMemcpy(frame, dev, bytes, 2 /* hipMemcpyDeviceToHost */) != 0) return fail("hipMemcpy", H264MI_EDEVICE);
+                    fwrite(frame, 1, bytes, out);
+                } else if (format != H264MI_FMT_I420 || scale_w) { /* one launch converts (and scales) the batch; csc 0: matrix and range of each frame's own SPS, nearest chroma */
                     size_t bytes = 0;
                     /* the size query: with cap 0 the call resolves and sizes every frame, sets bytes, launches nothing and returns H264MI_ECAPACITY (or
                      * H264MI_OK for an empty batch) -- the destination is never touched, it only has to be non-NULL, so before the device buffer exists

@@ -612,3 +612,72 @@ func (d *Decoder) ScaleBatch(stream, format, csc, outW, outH, filter int, dst un
 		dst, C.size_t(capBytes), &n))
 	return int(n), err
 }
+
+// Model input (K9; include/h264mi.h "Model input").  Written blind like the wrappers above: no Go toolchain was at hand to compile them.
+const (
+	DtU8         = 0 // H264MI_DT_U8
+	DtF16        = 1 // H264MI_DT_F16
+	DtBF16       = 2 // H264MI_DT_BF16
+	DtF32        = 3 // H264MI_DT_F32
+	FitStretch   = 0 // H264MI_FIT_STRETCH
+	FitLetterbox = 1 // H264MI_FIT_LETTERBOX
+	TensorBGR    = 1 // H264MI_TENSOR_BGR
+)
+
+// TensorSpec mirrors h264mi_tensor_spec: layout (FmtRGBP / FmtRGB24), element type, csc, canvas size, filter, fit, flags, the padding colour and
+// scale / bias per colour R, G, B: an 8-bit value v becomes float32(float32(v * Scale) + Bias), then the element type.
+type TensorSpec struct {
+	Format, Dtype, Csc, OutW, OutH, Filter, Fit, Flags int
+	Pad                                                [3]uint8
+	Scale, Bias                                        [3]float32
+}
+
+// TensorItem mirrors h264mi_tensor_item: a frame of the last batch and a region of it in display coordinates (W = H = 0: the whole frame).
+type TensorItem struct{ Stream, Frame, X, Y, W, H int }
+
+func (s *TensorSpec) c() C.h264mi_tensor_spec {
+	var c C.h264mi_tensor_spec
+	c.format, c.dtype, c.csc = C.int32_t(s.Format), C.int32_t(s.Dtype), C.int32_t(s.Csc)
+	c.out_w, c.out_h, c.filter, c.fit, c.flags = C.int32_t(s.OutW), C.int32_t(s.OutH), C.int32_t(s.Filter), C.int32_t(s.Fit), C.int32_t(s.Flags)
+	for i := 0; i < 3; i++ {
+		c.pad[i], c.scale[i], c.bias[i] = C.uint8_t(s.Pad[i]), C.float(s.Scale[i]), C.float(s.Bias[i])
+	}
+	return c
+}
+
+// FitRect: where a w x h source goes in an outW x outH canvas -- the picture's place and size -- from the library, without a decoder or a device.
+func FitRect(fit, w, h, outW, outH int) (px, py, sw, sh int, err error) {
+	var a, b, c, d C.int32_t
+	err = status(C.h264mi_fit_rect(C.int32_t(fit), C.int32_t(w), C.int32_t(h), C.int32_t(outW), C.int32_t(outH), &a, &b, &c, &d))
+	return int(a), int(b), int(c), int(d), err
+}
+
+// TensorSize: bytes of one tensor item of the spec; validates the spec.
+func TensorSize(spec *TensorSpec) (int, error) {
+	var n C.size_t
+	c := spec.c()
+	err := status(C.h264mi_tensor_size(&c, &n))
+	return int(n), err
+}
+
+// TensorBatch writes the whole of every frame of the last batch (stream < 0: all streams, stream-major) as a tensor item into device memory `dst`
+// with one kernel launch; returns the byte count (also when capBytes is too small).
+func (d *Decoder) TensorBatch(stream int, spec *TensorSpec, dst unsafe.Pointer, capBytes int) (int, error) {
+	var n C.size_t
+	c := spec.c()
+	err := status(C.h264mi_batch_tensor_device(d.h, C.int32_t(stream), &c, dst, C.size_t(capBytes), &n))
+	return int(n), err
+}
+
+// TensorItems writes one tensor item per entry of `items`, in order, back to back, with one kernel launch.
+func (d *Decoder) TensorItems(spec *TensorSpec, items []TensorItem, dst unsafe.Pointer, capBytes int) (int, error) {
+	var n C.size_t
+	c := spec.c()
+	ci := make([]C.h264mi_tensor_item, len(items)+1)
+	for i, it := range items {
+		ci[i].stream, ci[i].frame = C.int32_t(it.Stream), C.int32_t(it.Frame)
+		ci[i].x, ci[i].y, ci[i].w, ci[i].h = C.int32_t(it.X), C.int32_t(it.Y), C.int32_t(it.W), C.int32_t(it.H)
+	}
+	err := status(C.h264mi_items_tensor_device(d.h, &c, &ci[0], C.int32_t(len(items)), dst, C.size_t(capBytes), &n))
+	return int(n), err
+}

@@ -12,7 +12,7 @@ _HEADER = os.path.join(_HERE, "..", "include", "h264mi.h")
 _LIBPATH = os.environ.get("H264MI_LIB") or os.path.join(_HERE, "libh264mi.so")  # H264MI_LIB: a diagnostic build of the same library (csrc/Makefile)
 
 _CT = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64, "uint8_t": ctypes.c_uint8,
-       "double": ctypes.c_double, "void": None}
+       "double": ctypes.c_double, "float": ctypes.c_float, "void": None}
 
 
 class H264MIError(RuntimeError):
@@ -48,6 +48,7 @@ def _parse_structs():
 _S = _parse_structs()
 Nal, Sps, Pps, SliceHdr, Config, BatchInfo, FrameInfo = (_S["h264mi_nal"], _S["h264mi_sps"], _S["h264mi_pps"], _S["h264mi_slice_header"],
                                                          _S["h264mi_config"], _S["h264mi_batch_info"], _S["h264mi_frame_info"])
+TensorSpec, TensorItem = _S["h264mi_tensor_spec"], _S["h264mi_tensor_item"]
 
 
 def build(force=False):
@@ -124,6 +125,10 @@ def load():
         "h264mi_scale_taps": [I32, I32, I32, I32, P(I32), P(I32), P(I32), I32],
         "h264mi_frame_scale_device": [vp, I32, I32, I32, I32, I32, I32, I32, vp, SZ],
         "h264mi_batch_scale_device": [vp, I32, I32, I32, I32, I32, I32, vp, SZ, P(SZ)],
+        "h264mi_fit_rect": [I32, I32, I32, I32, I32, P(I32), P(I32), P(I32), P(I32)],
+        "h264mi_tensor_size": [P(TensorSpec), P(SZ)],
+        "h264mi_items_tensor_device": [vp, P(TensorSpec), P(TensorItem), I32, vp, SZ, P(SZ)],
+        "h264mi_batch_tensor_device": [vp, I32, P(TensorSpec), vp, SZ, P(SZ)],
         "h264mi_frame_read_mbrecs": [vp, I32, I32, vp, SZ],
         "h264mi_frame_read_mbmv1": [vp, I32, I32, vp, SZ],
         "h264mi_decoder_set_profiling": [vp, I32],
@@ -165,4 +170,5 @@ EXPORTS = ["h264mi_annexb_scan", "h264mi_nal_parse", "h264mi_sps_parse", "h264mi
            "h264mi_slice_starts_picture", "h264mi_pps_slice_group_ids", "h264mi_map_unit_to_slice_group_map", "h264mi_mb_to_slice_group_map", "h264mi_next_mb_address",
            "h264mi_frame_concealed", "h264mi_decoder_concealed", "h264mi_decoder_concealed_pictures", "h264mi_decoder_concealed_fields",
            "h264mi_output_size", "h264mi_csc_resolve", "h264mi_frame_colour", "h264mi_frame_convert_device", "h264mi_batch_convert_device",
-           "h264mi_scale_taps", "h264mi_frame_scale_device", "h264mi_batch_scale_device"]
+           "h264mi_scale_taps", "h264mi_frame_scale_device", "h264mi_batch_scale_device",
+           "h264mi_fit_rect", "h264mi_tensor_size", "h264mi_items_tensor_device", "h264mi_batch_tensor_device"]

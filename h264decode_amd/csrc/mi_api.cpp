@@ -11,6 +11,7 @@
 #include <functional>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
@@ -350,6 +351,11 @@ struct h264mi_decoder {
     size_t scale_cap[2] = {0, 0};
     hipEvent_t ev_scale[2] = {nullptr, nullptr};
     int scale_slot = 0;
+    // K9 descriptor tables: the same discipline
+    TensorDesc *h_tensor[2] = {nullptr, nullptr}, *d_tensor[2] = {nullptr, nullptr};
+    size_t tensor_cap[2] = {0, 0};
+    hipEvent_t ev_tensor[2] = {nullptr, nullptr};
+    int tensor_slot = 0;
     std::vector<float> launch_ms[4]; // duration of every launch of the last profiled pass, per kernel
 };
 
@@ -474,6 +480,9 @@ static void free_all(h264mi_decoder *d) {
         if (d->h_scale[i]) hipHostFree(d->h_scale[i]);
         if (d->d_scale[i]) hipFree(d->d_scale[i]);
         if (d->ev_scale[i]) hipEventDestroy(d->ev_scale[i]);
+        if (d->h_tensor[i]) hipHostFree(d->h_tensor[i]);
+        if (d->d_tensor[i]) hipFree(d->d_tensor[i]);
+        if (d->ev_tensor[i]) hipEventDestroy(d->ev_tensor[i]);
     }
     if (d->d_frames) hipFree(d->d_frames);
     if (d->d_tables) hipFree(d->d_tables);
@@ -2632,6 +2641,188 @@ extern "C" int32_t h264mi_batch_scale_device(h264mi_decoder *d, int32_t stream, 
         if (stream < 0 || stream == si)
             for (int f = 0; f < static_cast<int>(g.out[si].size()); f++) frames.push_back({si, f});
     return scale_frames(d, frames, format, csc, out_w, out_h, filter, dst, cap, bytes);
+}
+
+// ---------------------------------------------------------------- model input (K9): the rule of include/h264mi.h, "Model input"
+extern "C" int32_t h264mi_fit_rect(int32_t fit, int32_t w, int32_t h, int32_t out_w, int32_t out_h, int32_t *px, int32_t *py, int32_t *sw, int32_t *sh) {
+    if (!px || !py || !sw || !sh) return H264MI_EINVAL;
+    if (fit != H264MI_FIT_STRETCH && fit != H264MI_FIT_LETTERBOX) {
+        set_error("fit %d: not H264MI_FIT_STRETCH or H264MI_FIT_LETTERBOX", fit);
+        return H264MI_EINVAL;
+    }
+    if (w < 1 || w > H264MI_SCALE_MAX || h < 1 || h > H264MI_SCALE_MAX || out_w < 1 || out_w > H264MI_SCALE_MAX || out_h < 1 || out_h > H264MI_SCALE_MAX) {
+        set_error("fit rect: source %d x %d and canvas %d x %d must all be 1 .. %d", w, h, out_w, out_h, H264MI_SCALE_MAX);
+        return H264MI_EINVAL;
+    }
+    if (fit == H264MI_FIT_STRETCH) {
+        *px = 0, *py = 0, *sw = out_w, *sh = out_h;
+        return H264MI_OK;
+    }
+    if (w * out_h >= h * out_w) { // the width fills the canvas; products <= 2^28, the rounded quotient's numerator <= 2 * 2^28 + 2^14
+        *sw = out_w, *sh = std::min(std::max((2 * h * out_w + w) / (2 * w), 1), out_h);
+    } else {
+        *sh = out_h, *sw = std::min(std::max((2 * w * out_h + h) / (2 * h), 1), out_w);
+    }
+    *px = (out_w - *sw) >> 1, *py = (out_h - *sh) >> 1;
+    return H264MI_OK;
+}
+
+static inline int tensor_elem_size(int dtype) { return dtype == H264MI_DT_U8 ? 1 : dtype == H264MI_DT_F32 ? 4 : 2; }
+
+extern "C" int32_t h264mi_tensor_size(const h264mi_tensor_spec *spec, size_t *bytes) {
+    if (!spec || !bytes) return H264MI_EINVAL;
+    if (spec->format != H264MI_FMT_RGBP && spec->format != H264MI_FMT_RGB24) {
+        set_error("tensor format %d: not H264MI_FMT_RGBP or H264MI_FMT_RGB24", spec->format);
+        return H264MI_EINVAL;
+    }
+    if (spec->dtype != H264MI_DT_U8 && spec->dtype != H264MI_DT_F16 && spec->dtype != H264MI_DT_BF16 && spec->dtype != H264MI_DT_F32) {
+        set_error("tensor dtype %d: not H264MI_DT_U8, _F16, _BF16 or _F32", spec->dtype);
+        return H264MI_EINVAL;
+    }
+    int probe;
+    int r = h264mi_csc_resolve(spec->csc, 1, 0, 16, 16, &probe); // is csc legal at all
+    if (r != H264MI_OK) return r;
+    if (spec->out_w < 1 || spec->out_w > H264MI_SCALE_MAX || spec->out_h < 1 || spec->out_h > H264MI_SCALE_MAX) {
+        set_error("tensor size %d x %d: both must be 1 .. %d", spec->out_w, spec->out_h, H264MI_SCALE_MAX);
+        return H264MI_EINVAL;
+    }
+    if (spec->filter != H264MI_SCALE_BILINEAR && spec->filter != H264MI_SCALE_AREA) {
+        set_error("scale filter %d: not H264MI_SCALE_BILINEAR or H264MI_SCALE_AREA", spec->filter);
+        return H264MI_EINVAL;
+    }
+    if (spec->fit != H264MI_FIT_STRETCH && spec->fit != H264MI_FIT_LETTERBOX) {
+        set_error("fit %d: not H264MI_FIT_STRETCH or H264MI_FIT_LETTERBOX", spec->fit);
+        return H264MI_EINVAL;
+    }
+    if (spec->flags & ~H264MI_TENSOR_BGR) {
+        set_error("tensor flags 0x%x: only H264MI_TENSOR_BGR is defined", static_cast<unsigned>(spec->flags));
+        return H264MI_EINVAL;
+    }
+    for (int c = 0; c < 3; c++) {
+        if (!std::isfinite(spec->scale[c]) || !std::isfinite(spec->bias[c])) {
+            set_error("tensor scale[%d] = %g, bias[%d] = %g: both must be finite", c, static_cast<double>(spec->scale[c]), c, static_cast<double>(spec->bias[c]));
+            return H264MI_EINVAL;
+        }
+        if (spec->dtype == H264MI_DT_U8 && (spec->scale[c] != 1.0f || spec->bias[c] != 0.0f)) {
+            set_error("H264MI_DT_U8 maps nothing: scale[%d] must be 1 and bias[%d] 0, not %g and %g", c, c, static_cast<double>(spec->scale[c]), static_cast<double>(spec->bias[c]));
+            return H264MI_EINVAL;
+        }
+    }
+    *bytes = static_cast<size_t>(3) * spec->out_w * spec->out_h * tensor_elem_size(spec->dtype);
+    return H264MI_OK;
+}
+
+// K9 over a list of items: scale_frames' discipline.  Every item is checked, resolved and sized before anything is launched.
+static int tensor_items(h264mi_decoder *d, const h264mi_tensor_spec *spec, const h264mi_tensor_item *items, size_t n, void *dst, size_t cap, size_t *bytes) {
+    size_t one = 0;
+    int r = h264mi_tensor_size(spec, &one);
+    if (r != H264MI_OK) return r;
+    const int es = tensor_elem_size(spec->dtype), ow = spec->out_w, oh = spec->out_h;
+    if (reinterpret_cast<uintptr_t>(dst) % es) {
+        set_error("tensor destination %p: not aligned to the element size %d", dst, es);
+        return H264MI_EINVAL;
+    }
+    GUARD(d);
+    std::vector<TensorDesc> descs(n);
+    size_t off = 0;
+    for (size_t i = 0; i < n; i++) {
+        const h264mi_tensor_item &it = items[i];
+        uint8_t *p;
+        const OutFrame *of;
+        int x0, y0, w, h, res = 0;
+        r = frame_ptrs(d, it.stream, it.frame, &p, &of);
+        if (r != H264MI_OK) {
+            set_error("tensor item %zu: no frame %d of stream %d in the last executed batch", i, it.frame, it.stream);
+            return r;
+        }
+        crop_rect(of, 1, &x0, &y0, &w, &h);
+        int rx = it.x, ry = it.y, rw = it.w, rh = it.h;
+        if (rw == 0 && rh == 0) rw = w, rh = h; // the whole frame (legal from the origin (0, 0) only)
+        if (rx < 0 || ry < 0 || (rx & 1) || (ry & 1) || rw < 1 || rh < 1 || rx > w - rw || ry > h - rh) {
+            set_error("tensor item %zu: region (%d, %d, %d, %d) of frame %d of stream %d (%d x %d): the origin must be even and non-negative, the size at least 1 x 1, all of it inside the frame",
+                      i, it.x, it.y, it.w, it.h, it.frame, it.stream, w, h);
+            return H264MI_EINVAL;
+        }
+        int px, py, sw, sh;
+        r = h264mi_fit_rect(spec->fit, rw, rh, ow, oh, &px, &py, &sw, &sh);
+        if (r != H264MI_OK) return r;
+        if (spec->filter == H264MI_SCALE_AREA) {
+            if (sw > rw || sh > rh) {
+                set_error("H264MI_SCALE_AREA only scales down: item %zu, region %d x %d of frame %d of stream %d, the picture %d x %d", i, rw, rh, it.frame, it.stream, sw, sh);
+                return H264MI_EINVAL;
+            }
+            const uint64_t px64 = static_cast<uint64_t>(rw) * rh;
+            if (255 * px64 + (px64 >> 1) >= (static_cast<uint64_t>(1) << 32)) {
+                set_error("H264MI_SCALE_AREA sums in 32 bits and needs 255 * w * h + ((w * h) >> 1) < 2^32: item %zu, region %d x %d of frame %d of stream %d", i, rw, rh, it.frame, it.stream);
+                return H264MI_EUNSUPPORTED;
+            }
+        }
+        // from the frame's SPS and its DISPLAY size, never from the region or the canvas
+        r = h264mi_csc_resolve(spec->csc, of->matrix_coefficients, of->video_full_range, w, h, &res);
+        if (r != H264MI_OK) return r;
+        TensorDesc &td = descs[i];
+        td.src = reinterpret_cast<uint64_t>(p), td.dst_off = off;
+        td.W = of->wmb * 16, td.H = of->hmb * 16, td.x0 = x0 + rx, td.y0 = y0 + ry, td.w = rw, td.h = rh; // rx, ry even: (x0 + rx) / 2 = x0 / 2 + rx / 2
+        td.sw = sw, td.sh = sh, td.px = px, td.py = py;
+        td.cset = 2 * ((res & 15) - 1) + ((res & H264MI_CSC_FULL_RANGE) ? 1 : 0);
+        td.bilinear = (res & H264MI_CSC_CHROMA_BILINEAR) ? 1 : 0;
+        bilinear_axis(rw, sw, &td.step[0], &td.half[0]);
+        bilinear_axis(rh, sh, &td.step[1], &td.half[1]);
+        bilinear_axis((rw + 1) / 2, (sw + 1) / 2, &td.step[2], &td.half[2]);
+        bilinear_axis((rh + 1) / 2, (sh + 1) / 2, &td.step[3], &td.half[3]);
+        off += one;
+    }
+    if (bytes) *bytes = off;
+    if (off > cap) return H264MI_ECAPACITY;
+    if (n == 0) return H264MI_OK;
+    const int ps = d->tensor_slot ^= 1;
+    if (!d->ev_tensor[ps]) HIP_TRY(hipEventCreateWithFlags(&d->ev_tensor[ps], hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(d->ev_tensor[ps])); // the launch that used this table (two calls ago) has read it
+    if (n > d->tensor_cap[ps]) {
+        if (d->h_tensor[ps]) hipHostFree(d->h_tensor[ps]);
+        if (d->d_tensor[ps]) hipFree(d->d_tensor[ps]);
+        d->h_tensor[ps] = nullptr, d->d_tensor[ps] = nullptr, d->tensor_cap[ps] = 0;
+        const size_t m = std::max<size_t>(n, 64);
+        HIP_TRY(hipHostMalloc(&d->h_tensor[ps], sizeof(TensorDesc) * m));
+        HIP_TRY(hipMalloc(&d->d_tensor[ps], sizeof(TensorDesc) * m));
+        d->tensor_cap[ps] = m;
+    }
+    memcpy(d->h_tensor[ps], descs.data(), sizeof(TensorDesc) * n);
+    // (in order on the decoder's stream, which has waited for the reconstruction of the last executed pass: h264mi_batch_execute)
+    HIP_TRY(hipMemcpyAsync(d->d_tensor[ps], d->h_tensor[ps], sizeof(TensorDesc) * n, hipMemcpyHostToDevice, d->stream));
+    TensorParams P;
+    const bool bgr = (spec->flags & H264MI_TENSOR_BGR) != 0;
+    P.ow = ow, P.oh = oh, P.dtype = spec->dtype, P.hwc = spec->format == H264MI_FMT_RGB24, P.bgr = bgr;
+    for (int p = 0; p < 3; p++) { // by channel position
+        const int c = bgr ? 2 - p : p;
+        P.pad[p] = spec->pad[c], P.scale[p] = spec->scale[c], P.bias[p] = spec->bias[c];
+    }
+    // about 256 thread items of 2 rows x 8 columns per block; a picture that does not start on a thread item's boundary needs one more group and row pair
+    const int ngroups = (ow + 7) / 8 + 1, npairs = (oh + 1) / 2 + 1;
+    P.pairs_per_block = std::max(1, std::min(256 / ngroups, npairs));
+    const dim3 grid(static_cast<uint32_t>(n), (npairs + P.pairs_per_block - 1) / P.pairs_per_block);
+    if (spec->filter == H264MI_SCALE_AREA) hipLaunchKernelGGL(k_tensor_area, grid, dim3(256), 0, d->stream, d->d_tensor[ps], static_cast<uint8_t *>(dst), P);
+    else hipLaunchKernelGGL(k_tensor, grid, dim3(256), 0, d->stream, d->d_tensor[ps], static_cast<uint8_t *>(dst), P);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(d->ev_tensor[ps], d->stream));
+    d->last_pack = d->ev_tensor[ps];
+    return H264MI_OK;
+}
+
+extern "C" int32_t h264mi_items_tensor_device(h264mi_decoder *d, const h264mi_tensor_spec *spec, const h264mi_tensor_item *items, int32_t n, void *dst, size_t cap,
+                                              size_t *bytes) {
+    if (!d || !spec || !dst || n < 0 || (n > 0 && !items)) return H264MI_EINVAL;
+    return tensor_items(d, spec, items, static_cast<size_t>(n), dst, cap, bytes);
+}
+
+extern "C" int32_t h264mi_batch_tensor_device(h264mi_decoder *d, int32_t stream, const h264mi_tensor_spec *spec, void *dst, size_t cap, size_t *bytes) {
+    if (!d || !spec || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    std::vector<h264mi_tensor_item> items;
+    const Stage &g = d->stage[d->exec];
+    for (int si = 0; si < static_cast<int>(g.out.size()); si++)
+        if (stream < 0 || stream == si)
+            for (int f = 0; f < static_cast<int>(g.out[si].size()); f++) items.push_back({si, f, 0, 0, 0, 0});
+    return tensor_items(d, spec, items.data(), items.size(), dst, cap, bytes);
 }
 
 extern "C" int32_t h264mi_frame_read_mbrecs(h264mi_decoder *d, int32_t stream, int32_t frame, uint8_t *rec, size_t cap) {

@@ -163,6 +163,33 @@ typedef struct {
 } ScaleDesc;
 extern "C" __global__ void k_scale(const ScaleDesc *descs, uint8_t *dst, int ow, int oh, int pairs_per_block);      // H264MI_SCALE_BILINEAR
 extern "C" __global__ void k_scale_area(const ScaleDesc *descs, uint8_t *dst, int ow, int oh, int pairs_per_block); // H264MI_SCALE_AREA
+// K9 (k_tensor.hip): a list of (frame, region) items -> model-input tensors of ONE canvas size, by the rule of include/h264mi.h ("Model input"): the
+// region scaled to sw x sh (K8's rule), converted to RGB (K7's rule), placed at (px, py) of the out_w x out_h canvas, the rest of it `pad`; every 8-bit
+// value mapped to u8 / f16 / bf16 / f32.  grid = (items, chunks of pairs_per_block row pairs), block = 256; a thread owns two rows x 8 columns of the
+// canvas, counted from the picture's origin (so that rows 2j, 2j + 1 and columns 2k, 2k + 1 of the SCALED frame stay together, whatever px and py are)
+typedef struct {
+    uint64_t src;     // as PackDesc
+    uint64_t dst_off; // byte offset of the item in the destination buffer
+    uint32_t W, H;    // coded size
+    uint32_t x0, y0;  // origin of the region in the coded planes: the crop origin + the region's (even) origin in the display frame
+    uint32_t w, h;    // size of the region
+    uint32_t sw, sh, px, py; // the picture: size and place in the canvas (h264mi_fit_rect)
+    uint32_t cset;     // as ConvDesc
+    uint32_t bilinear; // chroma upsampling of the SCALED chroma planes, as ConvDesc
+    uint32_t step[4];  // as ScaleDesc, for region size -> picture size
+    int32_t half[4];
+} TensorDesc;
+typedef struct { // uniform per launch; scale, bias and pad by channel POSITION (colour 2 - position under H264MI_TENSOR_BGR)
+    int32_t ow, oh;          // the canvas
+    int32_t dtype;           // H264MI_DT_*
+    int32_t hwc;             // 0: H264MI_FMT_RGBP (three planes), 1: H264MI_FMT_RGB24
+    int32_t bgr;             // swap R and B
+    int32_t pairs_per_block;
+    uint32_t pad[3];
+    float scale[3], bias[3];
+} TensorParams;
+extern "C" __global__ void k_tensor(const TensorDesc *descs, uint8_t *dst, TensorParams P);      // H264MI_SCALE_BILINEAR
+extern "C" __global__ void k_tensor_area(const TensorDesc *descs, uint8_t *dst, TensorParams P); // H264MI_SCALE_AREA
 
 #ifndef MI_INTRA_WAVES
 #define MI_INTRA_WAVES 16 /* 1024 threads, 128 VGPRs per wavefront: the kernels need 120 once nothing lane-dependent is hoisted out of the macroblock loop */

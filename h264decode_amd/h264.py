@@ -207,6 +207,10 @@ CSC_FULL_RANGE, CSC_CHROMA_BILINEAR = 16, 32          # ... | full range (explic
 _FMT_NAMES = {"i420": FMT_I420, "nv12": FMT_NV12, "rgb24": FMT_RGB24, "rgbp": FMT_RGBP}
 SCALE_BILINEAR, SCALE_AREA = 0, 1                     # H264MI_SCALE_*: filters of scale_frame / scale_batch / frames_tensor(size=...)
 _FILTER_NAMES = {"bilinear": SCALE_BILINEAR, "area": SCALE_AREA}
+DT_U8, DT_F16, DT_BF16, DT_F32 = 0, 1, 2, 3           # H264MI_DT_*: element types of tensor_batch / tensor_items / frames_tensor(dtype=...)
+FIT_STRETCH, FIT_LETTERBOX = 0, 1                     # H264MI_FIT_*: how the picture is placed in the canvas
+TENSOR_BGR = 1                                        # H264MI_TENSOR_BGR: colour c at channel position 2 - c
+_DT_NAMES = {"u8": DT_U8, "uint8": DT_U8, "f16": DT_F16, "float16": DT_F16, "bf16": DT_BF16, "bfloat16": DT_BF16, "f32": DT_F32, "float32": DT_F32}
 
 
 def _fmt(fmt):
@@ -223,6 +227,37 @@ def _filter(filter):
             raise H264MIError(-1, "unknown scale filter %r (bilinear, area)" % (filter,))
         return _FILTER_NAMES[filter.lower()]
     return int(filter)
+
+
+def _dtype(dtype):
+    """An H264MI_DT_* value from a name ("u8", "f16", "bf16", "f32", "float16", ...), a torch or numpy dtype, or the value itself."""
+    if isinstance(dtype, int):
+        return dtype
+    name = str(dtype).lower().replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
+    if name not in _DT_NAMES:
+        raise H264MIError(-1, "unknown tensor dtype %r (u8, f16, bf16, f32)" % (dtype,))
+    return _DT_NAMES[name]
+
+
+def fit_rect(fit, w, h, out_w, out_h):
+    """Where a w x h source goes in an out_w x out_h canvas, from the library (h264mi_fit_rect; no GPU): (px, py, sw, sh).  fit: FIT_STRETCH or
+    FIT_LETTERBOX (the aspect ratio kept to the nearest pixel, centred)."""
+    v = [ctypes.c_int32(0) for _ in range(4)]
+    check(_lib.load().h264mi_fit_rect(int(fit), w, h, out_w, out_h, *[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def tensor_spec(size, fmt="rgbp", dtype="f32", csc=0, filter="bilinear", letterbox=False, bgr=False, pad=(114, 114, 114), scale=(1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0)):
+    """An h264mi_tensor_spec: canvas size = (out_w, out_h), layout "rgbp" (CHW) or "rgb24" (HWC), element type, csc and filter as for scale_batch,
+    stretch or letterbox, RGB or BGR channel order, the padding colour (R, G, B bytes), and scale / bias per colour (R, G, B): an 8-bit value v
+    becomes float32(float32(v * scale) + bias), then the element type."""
+    sp = _lib.TensorSpec()
+    sp.format, sp.dtype, sp.csc, sp.filter = _fmt(fmt), _dtype(dtype), int(csc), _filter(filter)
+    sp.out_w, sp.out_h = int(size[0]), int(size[1])
+    sp.fit, sp.flags = (FIT_LETTERBOX if letterbox else FIT_STRETCH), (TENSOR_BGR if bgr else 0)
+    for c in range(3):
+        sp.pad[c], sp.scale[c], sp.bias[c] = int(pad[c]), float(scale[c]), float(bias[c])
+    return sp
 
 
 def scale_taps(filter, n_in, n_out, i):
@@ -485,7 +520,64 @@ class Decoder:
         check(self._L.h264mi_batch_scale_device(self._h, stream, _fmt(fmt), csc, int(size[0]), int(size[1]), _filter(filter), dst_ptr, cap, ctypes.byref(n)))
         return n.value
 
-    def frames_tensor(self, stream, fmt="rgbp", csc=0, size=None, filter="bilinear"):
+    @staticmethod
+    def tensor_size(spec):
+        """Bytes of one tensor item of `spec` (tensor_spec(...)): h264mi_tensor_size, which validates the spec."""
+        n = ctypes.c_size_t(0)
+        check(_lib.load().h264mi_tensor_size(ctypes.byref(spec), ctypes.byref(n)))
+        return n.value
+
+    def tensor_batch(self, dst_ptr, cap, spec, stream=-1):
+        """K9 in one launch: the whole of every frame of the last executed batch (of one stream, or of all streams, stream-major) as a tensor item of
+        `spec`, back to back in the DEVICE buffer at dst_ptr -- scale_batch's contract.  Returns the number of bytes: frames x tensor_size(spec)."""
+        n = ctypes.c_size_t(0)
+        check(self._L.h264mi_batch_tensor_device(self._h, stream, ctypes.byref(spec), dst_ptr, cap, ctypes.byref(n)))
+        return n.value
+
+    def tensor_items(self, dst_ptr, cap, spec, items):
+        """K9 in one launch over a list of items (stream, frame, x, y, w, h): the region (x, y, w, h) of that frame of the last executed batch, in
+        display coordinates with an even origin (w = h = 0: the whole frame), as a tensor item of `spec`; item order, back to back.  The same frame may
+        appear in many items.  Returns the number of bytes."""
+        arr = (_lib.TensorItem * max(len(items), 1))()
+        for a, it in zip(arr, items):
+            a.stream, a.frame, a.x, a.y, a.w, a.h = (int(v) for v in it)
+        n = ctypes.c_size_t(0)
+        check(self._L.h264mi_items_tensor_device(self._h, ctypes.byref(spec), arr, len(items), dst_ptr, cap, ctypes.byref(n)))
+        return n.value
+
+    def _model_tensor(self, stream, fmt, csc, size, filter, dtype, scale, bias, mean, std, letterbox, pad, rois, bgr):
+        """frames_tensor with one of the model-input keywords: one K9 launch."""
+        import torch
+        if size is None:
+            raise ValueError("frames_tensor: dtype, scale, bias, mean, std, letterbox, rois and bgr need a size")
+        dt = _dtype("u8" if dtype is None else dtype)
+        if (mean is not None or std is not None) and (scale is not None or bias is not None):
+            raise ValueError("frames_tensor: give mean / std or scale / bias, not both")
+        if mean is not None or std is not None:
+            if dt == DT_U8:
+                raise ValueError("frames_tensor: mean / std need a float dtype")
+            mean, std = (0.0, 0.0, 0.0) if mean is None else mean, (1.0, 1.0, 1.0) if std is None else std
+            scale = [1.0 / (255.0 * float(std[c])) for c in range(3)]   # Python doubles, rounded to float32 once (by the ctypes field)
+            bias = [-float(mean[c]) / float(std[c]) for c in range(3)]
+        spec = tensor_spec(size, fmt, dt, csc, filter, letterbox, bgr, pad, (1.0, 1.0, 1.0) if scale is None else scale, (0.0, 0.0, 0.0) if bias is None else bias)
+        one = self.tensor_size(spec)
+        if rois is not None:
+            n = len(rois)
+        else:
+            n = sum(self.frame_count(s) for s in (range(self.max_streams) if stream < 0 else (stream,)))
+        ow, oh = spec.out_w, spec.out_h
+        tdt = {DT_U8: torch.uint8, DT_F16: torch.float16, DT_BF16: torch.bfloat16, DT_F32: torch.float32}[dt]
+        out = torch.empty((n, oh, ow, 3) if spec.format == FMT_RGB24 else (n, 3, oh, ow), dtype=tdt, device="cuda:%d" % self.device)
+        if n:
+            torch.cuda.current_stream(out.device).synchronize()  # whatever still uses a recycled block has finished before K9 writes it
+            cap = out.numel() * out.element_size()
+            got = self.tensor_items(out.data_ptr(), cap, spec, rois) if rois is not None else self.tensor_batch(out.data_ptr(), cap, spec, stream)
+            assert got == cap == n * one
+            self.sync()
+        return out
+
+    def frames_tensor(self, stream, fmt="rgbp", csc=0, size=None, filter="bilinear", *, dtype=None, scale=None, bias=None, mean=None, std=None,
+                      letterbox=False, pad=(114, 114, 114), rois=None, bgr=False):
         """The frames of `stream` of the last executed batch as one torch uint8 tensor on the decoder's device: [n, 3, h, w] ("rgbp"), [n, h, w, 3]
         ("rgb24") or [n, H264MI_I420_SIZE(w, h)] ("nv12"), converted by one K7 launch.  Raises ValueError if the stream's frames differ in display size.
         With size = (ow, oh) the frames are scaled to that size by one K8 launch (`filter`: "bilinear" or "area"): the shapes are those with (ow, oh) for
@@ -495,9 +587,19 @@ class Decoder:
         hand back a block that work still queued on that stream reads, and the conversion writes it on the decoder's stream -- so torch's current
         stream is SYNCHRONISED after the allocation and before the launch; and the decoder's stream is SYNCHRONISED (sync()) before the method returns,
         so the tensor is complete for any torch stream.  A caller who cannot afford the two waits allocates for themselves and calls convert_batch
-        or scale_batch."""
+        or scale_batch.
+        Model input (one K9 launch instead; `size` is required; the same two synchronisations): with any of the keyword-only arguments set the result
+        is [n, 3, oh, ow] ("rgbp") or [n, oh, ow, 3] ("rgb24") of torch dtype `dtype` (torch.uint8 / float16 / bfloat16 / float32 or "u8", "f16", "bf16",
+        "f32"; default uint8).  An 8-bit value v of colour c becomes float32(float32(v * scale[c]) + bias[c]) rounded to `dtype`; mean / std (per colour,
+        in 0 .. 1) stand for scale[c] = float32(1.0 / (255.0 * std[c])) and bias[c] = float32(-mean[c] / std[c]), evaluated in Python doubles and
+        rounded once -- giving both forms, or mean / std with uint8, is a ValueError.  letterbox keeps the aspect ratio and fills the rest of the canvas
+        with pad = (R, G, B); bgr writes the channels in the order B, G, R (scale, bias, mean, std and pad stay per colour R, G, B).  rois, a list of
+        (stream, frame, x, y, w, h) regions in display coordinates with even origins (w = h = 0: the whole frame), replaces "all frames of `stream`":
+        n = len(rois), in list order."""
         import torch
         f = _fmt(fmt)
+        if dtype is not None or scale is not None or bias is not None or mean is not None or std is not None or letterbox or rois is not None or bgr:
+            return self._model_tensor(stream, f, csc, size, filter, dtype, scale, bias, mean, std, letterbox, pad, rois, bgr)
         if size is not None:
             ow, oh = int(size[0]), int(size[1])
             n = sum(self.frame_count(s) for s in (range(self.max_streams) if stream < 0 else (stream,)))

@@ -487,6 +487,63 @@ int32_t h264mi_frame_scale_device(h264mi_decoder *dec, int32_t stream, int32_t f
 int32_t h264mi_batch_scale_device(h264mi_decoder *dec, int32_t stream, int32_t format, int32_t csc, int32_t out_w, int32_t out_h, int32_t filter,
                                   void *dst_device, size_t cap, size_t *bytes);
 
+/* ---- Model input (K9): regions of frames as letterboxed, normalised float tensors, on the device ----
+ * One launch takes a list of (frame, region) items and writes one tensor item per entry, all of one canvas size.  A tensor item is a function of the
+ * tight I420 frame, the region, the spec, the rule of "Scaled output" and the rule of "Output formats", and of nothing else; this comment is the contract.
+ * 1. Region.  (x, y, w, h) in display coordinates of the frame; w = h = 0 stands for the whole frame.  Legal: x and y even, w, h >= 1, x + w <= the
+ *    display width, y + h <= the display height; anything else is H264MI_EINVAL.  The region frame is the tight I420 frame with Y = Ydisp[y : y + h, x : x + w]
+ *    and C = Cdisp[y / 2 : y / 2 + ceil(h / 2), x / 2 : x / 2 + ceil(w / 2)] for both chroma planes (always inside the display chroma plane).  Every
+ *    clamp below is at the edges of the region frame: samples outside the region are never read.
+ * 2. Placement.  h264mi_fit_rect gives the picture's place (px, py) and size sw x sh in the out_w x out_h canvas.  H264MI_FIT_STRETCH: (0, 0, out_w, out_h).
+ *    H264MI_FIT_LETTERBOX, 32-bit integers, / is floor: if w out_h >= h out_w: sw = out_w, sh = clamp((2 h out_w + w) / (2 w), 1, out_h); else
+ *    sh = out_h, sw = clamp((2 w out_h + h) / (2 h), 1, out_w); px = (out_w - sw) >> 1, py = (out_h - sh) >> 1.  (The aspect ratio kept to the nearest
+ *    pixel, the picture centred, the odd pixel of padding right / below.)  All sizes are 1 .. H264MI_SCALE_MAX, so the largest intermediate is
+ *    2 * 16384^2 + 16384 < 2^31.
+ * 3. Picture.  The region frame scaled to sw x sh by "Scaled output" (filter: H264MI_SCALE_BILINEAR or _AREA; area needs sw <= w and sh <= h for every
+ *    item of the call, else H264MI_EINVAL, and its 32-bit bound applies to the region: 255 w h + ((w h) >> 1) < 2^32, else H264MI_EUNSUPPORTED), then
+ *    converted to 8-bit R, G, B by "Output formats" applied to the scaled frame: csc as there, H264MI_CSC_CHROMA_BILINEAR upsampling the SCALED chroma
+ *    planes.  H264MI_CSC_AUTO resolves per item from the frame's SPS and its DISPLAY size -- never from the region or the canvas.
+ * 4. Canvas.  out_h x out_w pixels: pixel (px + i, py + j) is picture pixel (i, j); every other pixel is pad[0], pad[1], pad[2] = R, G, B (pad[3] is ignored).
+ * 5. Element.  An 8-bit value v of colour c (R, G, B = 0, 1, 2) becomes
+ *      H264MI_DT_U8    v; scale must be exactly {1, 1, 1} and bias {0, 0, 0}, else H264MI_EINVAL
+ *      H264MI_DT_F32   r = fl32(fl32(float(v) * scale[c]) + bias[c]): two IEEE binary32 operations, each rounded to nearest even -- NOT a fused
+ *                      multiply-add -- subnormals kept
+ *      H264MI_DT_F16   r converted to binary16, round to nearest even; subnormals kept, overflow gives infinity
+ *      H264MI_DT_BF16  r converted to bfloat16, round to nearest even: for finite r with binary32 bit pattern u, (u + 0x7fff + ((u >> 16) & 1)) >> 16
+ *    scale and bias must be finite, else H264MI_EINVAL.  Pad bytes go through the same mapping.
+ * 6. Layout.  H264MI_FMT_RGBP: three out_h x out_w planes (CHW); H264MI_FMT_RGB24: out_h x out_w x 3 (HWC); any other format is H264MI_EINVAL.
+ *    H264MI_TENSOR_BGR in flags writes colour c at channel position 2 - c; scale, bias and pad stay indexed by colour.  Items are written back to back in
+ *    item order, each 3 * out_w * out_h * (1, 2, 2, 4) bytes (h264mi_tensor_size).  dst_device must be aligned to the element size, else H264MI_EINVAL. */
+#define H264MI_DT_U8 0
+#define H264MI_DT_F16 1
+#define H264MI_DT_BF16 2
+#define H264MI_DT_F32 3
+#define H264MI_FIT_STRETCH 0
+#define H264MI_FIT_LETTERBOX 1
+#define H264MI_TENSOR_BGR 1 /* h264mi_tensor_spec.flags */
+typedef struct {
+    int32_t format, dtype, csc, out_w, out_h, filter, fit, flags;
+    uint8_t pad[4];
+    float scale[3], bias[3];
+} h264mi_tensor_spec;
+typedef struct {
+    int32_t stream, frame, x, y, w, h; /* a frame of the last executed batch and a region of it (w = h = 0: the whole frame) */
+} h264mi_tensor_item;
+/* Rule 2 as a pure function (no decoder, no device).  H264MI_EINVAL: an unknown fit, a size outside 1 .. H264MI_SCALE_MAX, a null pointer. */
+int32_t h264mi_fit_rect(int32_t fit, int32_t w, int32_t h, int32_t out_w, int32_t out_h, int32_t *px, int32_t *py, int32_t *sw, int32_t *sh);
+/* Bytes of one tensor item of the spec.  Pure; validates the spec: H264MI_EINVAL for a format other than _RGBP / _RGB24, an unknown dtype, filter, fit
+ * or flag bit, an illegal csc, out_w or out_h outside 1 .. H264MI_SCALE_MAX, a scale or bias that is not finite, H264MI_DT_U8 with scale != 1 or bias != 0. */
+int32_t h264mi_tensor_size(const h264mi_tensor_spec *spec, size_t *bytes);
+/* The items of the list, in ONE launch (K9), back to back into the DEVICE buffer dst_device, asynchronous on the decoder's stream; `stream` and `frame`
+ * of an item refer to the last executed batch, and the same frame may appear in many items.  h264mi_batch_scale_device's discipline: every item is
+ * checked, resolved and sized before anything is launched; *bytes receives n * h264mi_tensor_size (also on H264MI_ECAPACITY); nothing is written on
+ * failure; n = 0 succeeds with *bytes = 0. */
+int32_t h264mi_items_tensor_device(h264mi_decoder *dec, const h264mi_tensor_spec *spec, const h264mi_tensor_item *items, int32_t n, void *dst_device,
+                                   size_t cap, size_t *bytes);
+/* The same for the whole of every frame of the last executed batch: frames of stream `stream` (or of all streams when stream = -1, stream-major) in
+ * decoding order -- h264mi_batch_scale_device's order. */
+int32_t h264mi_batch_tensor_device(h264mi_decoder *dec, int32_t stream, const h264mi_tensor_spec *spec, void *dst_device, size_t cap, size_t *bytes);
+
 /* Debug / test access to the intermediate macroblock records of a frame (host copy).
  * rec: 128 bytes per MB (layout: h264decode_amd/csrc/mi_types.h struct MbRec). */
 int32_t h264mi_frame_read_mbrecs(h264mi_decoder *dec, int32_t stream, int32_t frame, uint8_t *rec, size_t cap);

@@ -3,6 +3,7 @@
 // prepare / execute / sync in chunks of whole access units, several streams side by side, per-stream resets, isolation
 // on and off, frame queries and read-back.  Built and run by tools/host_asan.sh.
 #include "h264mi.h"
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -58,6 +59,7 @@ static std::atomic<long> codes[64];
 static void client(int iters, unsigned seed) {
     std::mt19937 rng(seed);
     std::mt19937 crng(seed ^ 0x5bd1e995u); // error concealment is drawn from a generator of its own: everything else a seed draws stays what it was
+    std::mt19937 trng(seed ^ 0x9e3779b9u); // ... and so are the model-input (K9) calls
     static const int conceal_values[] = {0, 0, 0, 1, 3, 5, 7, 17, 19, 21, 23}; // every legal value of h264mi_config.conceal_errors
     std::vector<uint8_t> pix(4 << 20);
     for (int it = 0; it < iters; it++) {
@@ -148,6 +150,46 @@ static void client(int iters, unsigned seed) {
                                           (nf & 4) ? pix.size() : 1000, &conv);
                 h264mi_frame_scale_device(dec, s, nf - 1, 0, 0, 16384, 1, H264MI_SCALE_BILINEAR, pix.data(), pix.size());
                 h264mi_frame_scale_device(dec, s, 0, 3, H264MI_CSC_BT709, 8, 8, 2 - (nf & 3), pix.data(), pix.size());
+                // K9's host side (spec validation, regions, placement, area's checks per item, AUTO per item, alignment, capacity): random specs, most
+                // of them legal, and items that are legal, one past the frame, at odd origins, of other streams and frames; short and full capacity
+                {
+                    h264mi_tensor_spec sp;
+                    memset(&sp, 0, sizeof sp);
+                    sp.format = trng() % 8 ? 2 + trng() % 2 : static_cast<int32_t>(trng() % 6) - 1;
+                    sp.dtype = trng() % 8 ? trng() % 4 : static_cast<int32_t>(trng() % 7) - 2;
+                    sp.csc = trng() % 8 ? (trng() % 3) | ((trng() & 1) * 32) : static_cast<int32_t>(trng() % 64);
+                    sp.out_w = trng() % 16 ? 1 + trng() % 700 : static_cast<int32_t>(trng() % 16387) - 1;
+                    sp.out_h = trng() % 16 ? 1 + trng() % 700 : static_cast<int32_t>(trng() % 16387) - 1;
+                    sp.filter = trng() % 16 ? trng() % 2 : 2, sp.fit = trng() % 16 ? trng() % 2 : -1, sp.flags = trng() % 16 ? trng() % 2 : 2;
+                    for (int c = 0; c < 3; c++) {
+                        sp.pad[c] = static_cast<uint8_t>(trng());
+                        sp.scale[c] = sp.dtype == H264MI_DT_U8 && trng() % 8 ? 1.0f : trng() % 32 ? 1.0f / (1 + trng() % 255) : INFINITY;
+                        sp.bias[c] = sp.dtype == H264MI_DT_U8 && trng() % 8 ? 0.0f : trng() % 32 ? -0.5f * (trng() % 5) : NAN;
+                    }
+                    size_t one = 0, got = 0;
+                    h264mi_tensor_size(&sp, &one);
+                    h264mi_frame_info fi;
+                    memset(&fi, 0, sizeof fi);
+                    const bool have = nf > 0 && h264mi_frame_get_info(dec, s, 0, &fi) == 0 && fi.width > 0 && fi.height > 0;
+                    std::vector<h264mi_tensor_item> items(trng() % 6);
+                    for (auto &it : items) {
+                        it.stream = trng() % 16 ? s : static_cast<int32_t>(trng() % (ns + 2)) - 1;
+                        it.frame = trng() % 16 ? static_cast<int32_t>(trng() % (nf + 1)) : -1; // nf: one past the end
+                        const int W = have ? fi.width : 16, H = have ? fi.height : 16;
+                        switch (trng() % 6) {
+                        case 0: it.x = it.y = it.w = it.h = 0; break;
+                        case 1: it.x = 2 * (trng() % ((W + 1) / 2)), it.y = 2 * (trng() % ((H + 1) / 2)), it.w = W - it.x + 1, it.h = H - it.y; break; // one past the right edge
+                        case 2: it.x = 1, it.y = 0, it.w = 1, it.h = 1; break;                                                                   // an odd origin
+                        case 3: it.x = 0, it.y = 0, it.w = 0, it.h = 1 + trng() % H; break;
+                        default: it.x = 2 * (trng() % ((W + 1) / 2)), it.y = 2 * (trng() % ((H + 1) / 2)), it.w = 1 + trng() % (W - it.x), it.h = 1 + trng() % (H - it.y); break;
+                        }
+                    }
+                    const size_t cap = trng() % 3 ? pix.size() : (one * items.size() ? one * items.size() - 1 : 0);
+                    h264mi_items_tensor_device(dec, &sp, items.data(), static_cast<int32_t>(items.size()), pix.data() + (trng() % 8 ? 0 : 1 + trng() % 3), cap, &got);
+                    h264mi_batch_tensor_device(dec, trng() % 2 ? s : -1, &sp, pix.data(), trng() % 3 ? pix.size() : 1000, &got);
+                    int32_t px, py, sw, sh;
+                    h264mi_fit_rect(trng() % 3, 1 + trng() % 16384, 1 + trng() % 16384, 1 + trng() % 16384, static_cast<int32_t>(trng() % 16386), &px, &py, &sw, &sh);
+                }
                 if (rng() % 13 == 0) h264mi_stream_reset(dec, s);
             }
             if (rng() % 29 == 0) h264mi_decoder_reset(dec);
