@@ -12,17 +12,8 @@
 // In bilinear mode step and the half-step offset come from the descriptor: nothing is divided.  Stores are 16 bytes (8 for an I420 chroma row) when
 // the destination and ow are 16-byte aligned, single bytes otherwise; the gathers are byte loads (neighbouring lanes read neighbouring cache lines).
 #include "mi_kernels.h"
-#include "k_scale_rule.h" // the sampling rule and the shared pieces of the conversion
+#include "k_output_rule.h" // the sampling rule and K7's conversion
 
-template <bool VEC> __device__ static __forceinline__ void store16(uint8_t *p, int n, const uint32_t v[4]) {
-    if (VEC) {
-        *reinterpret_cast<uint4 *>(p) = make_uint4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 16; i++)
-            if (i < n) p[i] = static_cast<uint8_t>(byte_of(v[i >> 2], i & 3));
-    }
-}
 template <bool VEC> __device__ static __forceinline__ void store8(uint8_t *p, int n, const uint32_t v[8]) {
     if (VEC) {
         *reinterpret_cast<uint2 *>(p) = make_uint2(pack4(v[0], v[1], v[2], v[3]), pack4(v[4], v[5], v[6], v[7]));
@@ -99,8 +90,7 @@ __device__ static __forceinline__ void scale_item(const ScaleDesc &sd, const uin
             V[0][2 * i] = V[0][2 * i + 1] = V[1][2 * i] = V[1][2 * i + 1] = cr;
         }
     } else {
-        // scaled chroma rows j - 1, j, j + 1 and columns k .. k + 8, clamped to the scaled plane, recomputed here (no intermediate buffer);
-        // Hrow = 2 c[k] (even x) or c[k] + c[k + 1] (odd x); (3 Hrow(j) + Hrow(j') + 4) >> 3
+        // scaled chroma rows j - 1, j, j + 1 and columns k .. k + 8, clamped to the scaled plane, recomputed here (no intermediate buffer)
         const Tap tya = tap_of<FILTER>(CY, max(j - 1, 0)), tyb = tap_of<FILTER>(CY, j), tyc = tap_of<FILTER>(CY, min(j + 1, ohc - 1));
         uint32_t a[2][9], b[2][9], c[2][9]; // [Cb, Cr]: both planes of a column together -- they share its taps, which then die with the column
 #pragma unroll
@@ -115,62 +105,9 @@ __device__ static __forceinline__ void scale_item(const ScaleDesc &sd, const uin
             }
         }
 #pragma unroll
-        for (int p = 0; p < 2; p++) {
-#pragma unroll
-            for (int i = 0; i < 16; i++) {
-                const int q = i >> 1, q1 = q + (i & 1);
-                const int ha = static_cast<int>(a[p][q] + a[p][q1]), hb = static_cast<int>(b[p][q] + b[p][q1]), hcc = static_cast<int>(c[p][q] + c[p][q1]);
-                const int top = ((3 * hb + ha + 4) >> 3) - 128, bot = ((3 * hb + hcc + 4) >> 3) - 128;
-                if (p) V[0][i] = top, V[1][i] = bot;
-                else U[0][i] = top, U[1][i] = bot;
-            }
-        }
+        for (int p = 0; p < 2; p++) upsample_chroma<16>(a[p], b[p], c[p], p ? V[0] : U[0], p ? V[1] : U[1]);
     }
-    const int32_t *cf = k_scale_csc[sd.cset & 3];
-    const int cy = cf[0], crv = cf[1], cgu = cf[2], cgv = cf[3], cbu = cf[4];
-    const int yoff = (sd.cset & 1) ? 0 : 16; // odd sets are full range
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-        if (r && !two) break;
-        uint32_t R[16], G[16], B[16];
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-            // every factor fits 24 bits (coefficients < 2^15, samples within +-256): v_mad_i32_i24
-            const int t = __mul24(cy, static_cast<int>(byte_of(Y[r][i >> 2], i & 3)) - yoff) + 4096;
-            R[i] = clip255((t + __mul24(crv, V[r][i])) >> 13);
-            G[i] = clip255((t - __mul24(cgu, U[r][i]) - __mul24(cgv, V[r][i])) >> 13);
-            B[i] = clip255((t + __mul24(cbu, U[r][i])) >> 13);
-        }
-        const size_t row = static_cast<size_t>(2 * j + r) * ow + x;
-        if (FMT == 2) {
-            if (VEC) {
-                uint32_t o[12]; // pixels 4q .. 4q + 3 are 12 bytes, three words; the thread's 48 bytes are three 16-byte stores
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int i = 4 * q;
-                    o[3 * q] = pack4(R[i], G[i], B[i], R[i + 1]);
-                    o[3 * q + 1] = pack4(G[i + 1], B[i + 1], R[i + 2], G[i + 2]);
-                    o[3 * q + 2] = pack4(B[i + 2], R[i + 3], G[i + 3], B[i + 3]);
-                }
-                uint4 *d = reinterpret_cast<uint4 *>(out + row * 3);
-                d[0] = make_uint4(o[0], o[1], o[2], o[3]), d[1] = make_uint4(o[4], o[5], o[6], o[7]), d[2] = make_uint4(o[8], o[9], o[10], o[11]);
-            } else {
-                uint8_t *d = out + row * 3;
-#pragma unroll
-                for (int i = 0; i < 16; i++)
-                    if (i < n) d[3 * i] = static_cast<uint8_t>(R[i]), d[3 * i + 1] = static_cast<uint8_t>(G[i]), d[3 * i + 2] = static_cast<uint8_t>(B[i]);
-            }
-        } else {
-            uint32_t o[4];
-#pragma unroll
-            for (int p = 0; p < 3; p++) {
-                const uint32_t *c = p == 0 ? R : p == 1 ? G : B;
-#pragma unroll
-                for (int q = 0; q < 4; q++) o[q] = pack4(c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]);
-                store16<VEC>(out + p * npix + row, n, o);
-            }
-        }
-    }
+    store_rgb_rows<FMT, VEC>(out, ow, npix, j, x, n, two, sd.cset, Y, U, V);
 }
 
 template <int FILTER, int FMT, bool BILIN, bool VEC>

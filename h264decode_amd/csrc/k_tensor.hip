@@ -1,6 +1,6 @@
 // h264decode_amd/csrc/k_tensor.hip -- K9: a list of (frame, region) items -> model-input tensors (the rule of include/h264mi.h, "Model input").
 // One launch takes any number of items: blockIdx.x = item, blockIdx.y = a chunk of `pairs_per_block` row pairs of the canvas.  An item is the region
-// of a frame scaled to sw x sh (K8's rule, k_scale_rule.h), converted to 8-bit R, G, B (K7's rule on the scaled frame), placed at (px, py) of the
+// of a frame scaled to sw x sh (K8's rule, k_output_rule.h), converted to 8-bit R, G, B (K7's rule on the scaled frame), placed at (px, py) of the
 // out_w x out_h canvas with `pad` everywhere else, every 8-bit value v mapped to u8 (v), or to fl32(fl32(float(v) * scale) + bias) as f32, f16 or bf16,
 // in three planes or interleaved.  The scaled frame and the 8-bit RGB picture exist in registers only.
 // Work: a thread owns two rows x 8 columns, counted from the PICTURE's origin -- rows py + 2j, py + 2j + 1 and columns px + 8g .. px + 8g + 7 of the
@@ -12,7 +12,7 @@
 // The two float operations are compiled with contraction off (elem_bits): hipcc would contract a * b + c into one fused operation by default, and
 // its __fmul_rn / __fadd_rn are a plain * and + that it contracts too; the rule excludes the fused result.
 #include "mi_kernels.h"
-#include "k_scale_rule.h"
+#include "k_output_rule.h"
 #include <hip/hip_fp16.h>
 
 enum { DT_U8 = 0, DT_F16 = 1, DT_BF16 = 2, DT_F32 = 3 }; // H264MI_DT_*
@@ -121,22 +121,11 @@ __device__ static __forceinline__ void tensor_item(const TensorDesc &td, const T
                     c[p][i] = sample<FILTER>(pl, Wc, CX, CY, tx, tyc);
                 }
             }
-#pragma unroll
-            for (int p = 0; p < 2; p++) {
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const int q = i >> 1, q1 = q + (i & 1);
-                    const int ha = static_cast<int>(a[p][q] + a[p][q1]), hb = static_cast<int>(b[p][q] + b[p][q1]), hcc = static_cast<int>(c[p][q] + c[p][q1]);
-                    const int top = ((3 * hb + ha + 4) >> 3) - 128, bot = ((3 * hb + hcc + 4) >> 3) - 128;
-                    if (p) V[0][i] = top, V[1][i] = bot;
-                    else U[0][i] = top, U[1][i] = bot;
-                }
-            }
+            upsample_chroma<8>(a[0], b[0], c[0], U[0], U[1]);
+            upsample_chroma<8>(a[1], b[1], c[1], V[0], V[1]);
         }
     }
-    const int32_t *cf = k_scale_csc[td.cset & 3];
-    const int cy = cf[0], crv = cf[1], cgu = cf[2], cgv = cf[3], cbu = cf[4];
-    const int yoff = (td.cset & 1) ? 0 : 16; // odd sets are full range
+    const Csc csc = csc_of(td.cset);
     const int npic = sw - x;                 // columns i < npic are picture (where the row is)
 #pragma unroll
     for (int r = 0; r < 2; r++) {
@@ -146,11 +135,8 @@ __device__ static __forceinline__ void tensor_item(const TensorDesc &td, const T
         if (inpic && 2 * j + r < sh) {
 #pragma unroll
             for (int i = 0; i < 8; i++) {
-                // every factor fits 24 bits (coefficients < 2^15, samples within +-256): v_mad_i32_i24
-                const int t = __mul24(cy, static_cast<int>(byte_of(Y[r][i >> 2], i & 3)) - yoff) + 4096;
-                uint32_t c0 = clip255((t + __mul24(crv, V[r][i])) >> 13);
-                const uint32_t c1 = clip255((t - __mul24(cgu, U[r][i]) - __mul24(cgv, V[r][i])) >> 13);
-                uint32_t c2 = clip255((t + __mul24(cbu, U[r][i])) >> 13);
+                uint32_t c0, c1, c2;
+                ycc_to_rgb(byte_of(Y[r][i >> 2], i & 3), U[r][i], V[r][i], csc, c0, c1, c2);
                 if (P.bgr) {
                     const uint32_t s = c0;
                     c0 = c2, c2 = s;

@@ -1,6 +1,7 @@
 // h264decode_amd/csrc/mi_api.cpp -- the C ABI of libh264mi.so (include/h264mi.h): host-side
 // front end (NAL dispatch h264/server.go:113-166; where pictures go in a batch's tables, asking mi_dpb.cpp -- picture management 8.2 -- for
-// slots, counts and lists) and GPU launch sequence.
+// slots, counts and lists), GPU launch sequence, and the read-back and query calls.  The output stage (K6 .. K9: pack, convert, scale, model-input
+// tensors, and their device-free rule functions) is mi_output.cpp; the decoder's state, which both files work on, is mi_decoder.hpp.
 //
 // There is deliberately NO CPU pixel path in this library: every sample is produced by the HIP
 // kernels in k_entropy.hip / k_recon.hip / k_deblock.hip.  If no device is usable the create call
@@ -19,25 +20,8 @@
 #include <cstring>
 #include <vector>
 #include "../../include/h264mi.h"
-#include "mi_dpb.hpp"
-#include "mi_kernels.h"
-#include "mi_parse.hpp"
+#include "mi_decoder.hpp"
 #include "mi_tables.h"
-
-using namespace mi;
-
-#ifndef MI_SETS
-#define MI_SETS 3 /* record / coefficient sets: a pass may run two passes ahead of the reconstruction that frees its set (a fourth set bought 1 % for 28 GB) */
-#endif
-
-#define HIP_TRY(x)                                                                          \
-    do {                                                                                    \
-        hipError_t _e = (x);                                                                \
-        if (_e != hipSuccess) {                                                             \
-            set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(_e), __FILE__, __LINE__); \
-            return H264MI_EDEVICE;                                                          \
-        }                                                                                   \
-    } while (0)
 
 // ---------------------------------------------------------------- device tables
 static void put_vlc(uint16_t *lut, int bits, int len, uint32_t code, uint16_t value) {
@@ -177,210 +161,7 @@ static void build_scaling(const uint8_t s4[6][16], const uint8_t s8[2][64], Scal
             }
 }
 
-// ---------------------------------------------------------------- per-stream host state
-struct OutFrame { // a decoded picture of the current batch, with the geometry it was coded with
-    int slot, wmb, hmb, crop_x, crop_y, width, height;
-    int poc, frame_num, nal_ref_idc, idr, pic;
-    int new_sequence; // IDR picture or memory_management_control_operation 5: picture order counts start over
-    int pic2 = -1;    // a frame coded as two field pictures: `pic` / `pic2` are the first / second field's PicDesc (-1: decoded by an earlier batch, or never)
-    int matrix_coefficients = 2, video_full_range = 0; // of the picture's own SPS (E.2.1: "unspecified" / 0 where it does not carry them): h264mi_frame_colour
-};
-struct StreamState {
-    h264mi_sps sps[32];
-    h264mi_pps pps[256];
-    std::vector<uint8_t> sg_ids[256]; // slice_group_id[] of the PPSs with slice_group_map_type 6 (h264/pps.go:23)
-    std::vector<int32_t> cur_first_mbs; // first_mb_in_slice of the slices of the current picture
-    uint32_t epoch = 0;                 // bumped by every reset of the stream: failures of batches prepared before it are nobody's business any more
-    bool sps_ok[32] = {}, pps_ok[256] = {};
-    int active_sps = -1;
-    int wmb = 0, hmb = 0;
-    Dpb dpb; // frame slots, POC / frame_num history, the picture under construction (dpb.cur_slot >= 0) and its frame slot: mi_dpb.hpp
-    int cur_pic = -1, cur_slices = 0; // the picture under construction: its PicDesc, slices so far
-    // The frame that waits in dpb.pend_slot for its second field goes out -- once -- when that field is complete, or with one field decoded (the
-    // rows of the other one mid-grey) when something else follows: another picture, an end-of-sequence / end-of-stream NAL unit, a reset.
-    OutFrame pend_out;
-    int n_pics_in_batch = 0;
-    int status = H264MI_OK; // of this stream in the current batch (h264mi_stream_status)
-    const void *status_batch = nullptr; // the batch whose entropy kernels set `status` (harvest_status)
-    bool need_idr = false;  // after an error: nothing is decodable before the next IDR picture
-    // error concealment: slice NAL units with an unparsable header that arrived while no picture was under construction -- they belong to the picture
-    // the next slice starts, and are tolerated only if that picture turns out to be concealable (add_slice); that slice may come with a later chunk
-    int pending_drops = 0, pending_drop_err = H264MI_OK;
-    int pending_drop_type = 0; // ... their nal_unit_type (1 or 5; -1: both kinds): tolerated only in a picture of that kind (H264MI_CONCEAL_IDR)
-    // error concealment of lone fields (H264MI_CONCEAL_LONE_FIELDS): the parameter sets the first field in dpb.pend_slot was decoded under, and whether
-    // the stream has stored other content under one of those ids since (the inserted field needs the ones its frame was decoded with)
-    int pend_sps_id = -1, pend_pps_id = -1;
-    bool pend_stale = false;
-    // error concealment of IDR pictures (H264MI_CONCEAL_IDR): what of the SPS the stream's reference frames were decoded under must still hold for an
-    // IDR picture to predict from them -- picture size in macroblocks, chroma_format_idc, frame_mbs_only_flag, log2_max_frame_num_minus4 (start_picture)
-    struct RefSeq {
-        int wmb = -1, hmb = 0, chroma_format = 0, frame_mbs_only = 0, log2_max_frame_num_minus4 = 0;
-        bool operator==(const RefSeq &o) const {
-            return wmb == o.wmb && hmb == o.hmb && chroma_format == o.chroma_format && frame_mbs_only == o.frame_mbs_only && log2_max_frame_num_minus4 == o.log2_max_frame_num_minus4;
-        }
-    } ref_seq;
-};
-
-// Everything one prepared batch owns: the pinned staging buffers and their device mirrors, the descriptors, the launch
-// lists and the output frame lists.  There are MI_STAGES of them, so that h264mi_batch_prepare(n + 1) -- host parsing and
-// the H2D copies -- runs while batch n is still executing (h264/server.go:144-145 reads its connection in an endless loop).
-#ifndef MI_STAGES
-#define MI_STAGES 2
-#endif
-struct Stage {
-    uint8_t *d_bits = nullptr, *h_bits = nullptr;
-    size_t bits_used = 0;
-    size_t map_cursor = 0, bits_end = 0; // slice group maps of FMO pictures follow the slices in the staging buffer; bits_end: what must be uploaded
-    std::vector<uint32_t> fmo_pics;      // pictures whose records are zeroed before the entropy kernels run
-    struct GreyFill { uint32_t stream, slot, parity, w, h; }; // a frame that went out with one field decoded: the rows of the other parity are painted mid-grey
-    std::vector<GreyFill> grey;
-    std::vector<uint32_t> epochs;        // StreamState::epoch of every stream when this batch was prepared
-    SliceDesc *d_slices = nullptr, *h_slices = nullptr;
-    PicDesc *d_pics = nullptr, *h_pics = nullptr;
-    uint32_t *d_status = nullptr, *h_status = nullptr, *d_lists = nullptr, *h_lists = nullptr;
-    BSliceExt *d_bext = nullptr, *h_bext = nullptr; // one per B slice
-    int n_bext = 0;
-    // B pictures take their direct-mode motion from RefPicList1[0], so that picture's slices must have been entropy-decoded
-    // first: slices are launched by level -- 0: I and P slices (k_entropy), n: B slices whose co-located picture is of level
-    // n - 1 or older than the batch (k_entropy_b) -- and the slice table is ordered by level.
-    std::vector<int> pic_level, slice_level; // per picture / per slice of the batch (slice_level in parse order, until the table is sorted)
-    std::vector<uint8_t> pic_save_col;       // the picture's motion is kept for later direct prediction (k_dbprep writes its ColRec array)
-    std::vector<uint8_t> pic_init_qp;        // error concealment: 26 + pic_init_qp_minus26 of the picture's PPS (QP_Y of its concealment SliceDesc)
-    uint32_t *d_cmap = nullptr, *h_cmap = nullptr; // error concealment: per picture where its slices are in the sorted slice table (k_conceal)
-    std::vector<uint16_t> pic_dropped;       // error concealment: per picture, slice NAL units whose header did not parse and that were dropped as lost (add_slice)
-    std::vector<int> pic_wave;               // reconstruction wave of the picture: 0 for a picture that reads no picture of this batch, else 1 + the latest wave among its references
-    std::vector<int> level_first;            // first slice of each level in the sorted table (+ end marker)
-    int ent_kernel = MI_ENT_K_GENERAL;       // the I/P entropy kernel of level 0 (mi_entropy_kernel_choice), decided when the batch is prepared
-    std::vector<uint32_t> colsave_n;            // per level: pictures whose ColRec array k_dbprep writes (what the cross-pass fence looks at)
-    std::vector<uint32_t> prep_off, prep_n;     // per level: the pictures whose last slice is of that level (k_dbprep runs on them after the level), as a range of d_lists
-    std::vector<uint32_t> wave_b_off, wave_b_n, wave_p_off, wave_p_n, wave_nb_off, wave_nb_n; // per wave: B pictures / inter non-B / non-B
-    int n_slices = 0, n_pics = 0, wmb_max = 0, hmb_max = 0, mbs_max = 0;
-    uint64_t mb_used = 0;
-    std::vector<std::vector<uint32_t>> waves, waves_inter;
-    std::vector<uint32_t> wave_off, wave_inter_off;
-    std::vector<std::vector<OutFrame>> out; // per stream: frames of this batch in decoding order
-    bool prepared = false, executed = false;
-    bool harvested = true; // the entropy kernels' per-slice status words of the last execute have been looked at (harvest_status)
-    bool retried = false;  // the batch has been repeated with the whole residual pool (retry_exhausted)
-    h264mi_batch_info info;
-    hipEvent_t ev_upload = nullptr; // H2D copies of this batch are complete
-    hipEvent_t ev_done = nullptr;   // the last pass over this batch has finished (nothing reads or writes its buffers any more)
-};
-
-struct h264mi_decoder {
-    h264mi_config cfg;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    std::vector<StreamState> st;
-    int Wmax = 0, Hmax = 0, n_slots = 0;
-    size_t slot_bytes = 0;
-    Stage stage[MI_STAGES];
-    int prep = 0;  // stage of the most recent h264mi_batch_prepare
-    int exec = 0;  // stage of the most recent h264mi_batch_execute: what sync and the frame accessors refer to
-    size_t bits_cap = 0;
-    uint32_t *d_toprows[MI_SETS] = {}; // entropy kernels' row-above neighbour state: 48 B per MB column per slice
-    int slices_cap = 0, pics_cap = 0;
-    // Passes are pipelined: the entropy kernels of passes n+1 / n+2 (two private streams, alternating)
-    // overlap the reconstruction kernels of pass n (on `stream`); each pass owns one of MI_SETS
-    // MbRec / coefficient buffer sets, fenced by events.
-    MbRec *d_mbrec[MI_SETS] = {};
-    DbPrm *d_dbprm[MI_SETS] = {};        // k_dbprep -> K5: boundary strengths and filter parameters, same indexing as d_mbrec
-    unsigned long long *d_imask[MI_SETS] = {}; // k_dbprep -> K3: one bit per macroblock of the batch (same indexing), set for what K3 reconstructs
-    MbMv1 *d_mv1[MI_SETS] = {};          // list-1 vectors, same indexing as d_mbrec; allocated when the first B slice arrives
-    ColRec *d_colrec = nullptr;          // per stream and frame slot: the motion a picture leaves for later direct prediction
-    size_t colrec_per_slot = 0;          // ColRecs per frame slot
-    int16_t *d_coef[MI_SETS] = {};       // coefficient pools: 32-byte blocks, only the blocks that carry anything (MbRec::coef_off / coef_mask)
-    uint32_t *d_pool_head = nullptr;     // MI_SETS counters: next free block of each pool, reset before every entropy launch
-    uint64_t pool_blocks = 0;            // blocks per pool
-    hipStream_t ent_stream[2] = {nullptr, nullptr};
-    hipStream_t rec_stream = nullptr; // K3-K5; the caller's stream only brackets a pass with events
-    hipEvent_t ev_user = nullptr;
-    hipEvent_t ev_ent[MI_SETS] = {}, ev_rec[MI_SETS] = {}, ev_col[MI_SETS] = {};
-    uint64_t pass = 0; // execute() counter
-    int last_exec_stage = -1, last_exec_set = 0; // staging set and record set of the most recent execute (ensure_b_buffers)
-    bool last_pass_had_b = false;
-    uint64_t mb_cap = 0;
-    uint64_t dev_bytes = 0;              // device memory this decoder holds (h264mi_decoder_memory)
-    uint32_t *d_backfill = nullptr;      // picture list of the one-off ColRec back-fill (first B slice of a decoder)
-    FramePool *d_pools = nullptr;
-    std::vector<FramePool> h_pools;
-    uint8_t *d_frames = nullptr;
-    DevTables *d_tables = nullptr, *h_tables = nullptr;
-    int n_scaling = 0;
-    uint32_t scaling_used[MI_STAGES] = {}; // bit i: the batch of that staging set refers to DevTables::scaling[i]
-    bool tables_dirty = true;
-    size_t ent_lds_pad = 0; // dynamic LDS requested (and not used) by k_entropy: caps its wavefronts per CU, see h264mi_decoder_create
-    bool conceal = false; // h264mi_config.conceal_errors: lost macroblocks of concealable pictures are copied from a reference picture (k_conceal)
-    bool conceal_pics = false; // ... bit H264MI_CONCEAL_PICTURES: wholly lost reference frames are inserted as pictures without slices (conceal_frame_num_gap)
-    bool conceal_fields = false; // ... bit H264MI_CONCEAL_FIELDS: field pictures are concealable too
-    bool conceal_idr = false; // ... bit H264MI_CONCEAL_IDR: IDR frame pictures that still have a reference frame are concealable too
-    bool conceal_lone = false; // ... bit H264MI_CONCEAL_LONE_FIELDS: the missing field of a frame is inserted as a picture without slices (flush_pending_field)
-    int64_t concealed_slices = 0, concealed_mbs = 0; // totals since create (h264mi_decoder_concealed)
-    int64_t concealed_pics = 0;                      // (h264mi_decoder_concealed_pictures)
-    int64_t concealed_fields = 0;                    // (h264mi_decoder_concealed_fields)
-    bool isolate = false; // h264mi_decoder_set_isolation: a broken stream does not fail the batch
-    // profiling
-    bool profiling = false;
-    std::vector<hipEvent_t> ev;
-    std::vector<int> ev_kind;
-    size_t ev_used = 0;
-    double k_ms[5] = {0, 0, 0, 0, 0};
-    // Launches with fewer pictures than the chip has CUs spread a picture over several workgroups (k_intra_x, k_deblock_x,
-    // k_deblock_x): hand-off rings / flags in global memory, a ticket counter per kernel family, a give-up word
-    unsigned long long *d_xring = nullptr; // K5: x_cap * (Wmax / 16) * 24 granules
-    uint32_t *d_xdone = nullptr;           // K3: x_cap * (Wmax / 16) flag words
-    int k5_max_waves = MI_DEBLOCK8_MAX_WAVES;
-    int64_t unpinned_failures = 0; // slices of CABAC field pictures that failed in the entropy kernel (h264mi_decoder_unpinned_failures)
-    uint32_t *d_xctl = nullptr, *h_xstatus = nullptr; // [0] K5 tickets, [32] K3 tickets, [64] give-up code (128-byte lines of their own)
-    uint32_t x_epoch = 0, x_tk5 = 0, x_tk3 = 0;
-    int x_max_wgs = 256, x_cap = 512, x_cap3 = 512; // workgroups per launch: default; capacity of the K5 ring; of the K3 flag array
-    // K6 descriptor tables: two of them, used alternately, each fenced by an event -- a pack call does not wait for the stream (the batch it packs
-    // may still be executing, and the next execute may be enqueued right behind it)
-    PackDesc *h_pack[2] = {nullptr, nullptr}, *d_pack[2] = {nullptr, nullptr};
-    size_t pack_cap[2] = {0, 0};
-    hipEvent_t ev_pack[2] = {nullptr, nullptr};
-    int pack_slot = 0;
-    hipEvent_t last_pack = nullptr; // the most recent pack or convert launch: the reconstruction of a later pass may rewrite the frames it reads
-    // K7 descriptor tables: the same discipline
-    ConvDesc *h_conv[2] = {nullptr, nullptr}, *d_conv[2] = {nullptr, nullptr};
-    size_t conv_cap[2] = {0, 0};
-    hipEvent_t ev_conv[2] = {nullptr, nullptr};
-    int conv_slot = 0;
-    // K8 descriptor tables: the same discipline
-    ScaleDesc *h_scale[2] = {nullptr, nullptr}, *d_scale[2] = {nullptr, nullptr};
-    size_t scale_cap[2] = {0, 0};
-    hipEvent_t ev_scale[2] = {nullptr, nullptr};
-    int scale_slot = 0;
-    // K9 descriptor tables: the same discipline
-    TensorDesc *h_tensor[2] = {nullptr, nullptr}, *d_tensor[2] = {nullptr, nullptr};
-    size_t tensor_cap[2] = {0, 0};
-    hipEvent_t ev_tensor[2] = {nullptr, nullptr};
-    int tensor_slot = 0;
-    std::vector<float> launch_ms[4]; // duration of every launch of the last profiled pass, per kernel
-};
-
 static int g_device = -1;
-
-// hipSetDevice is per-thread state: every entry point that takes a decoder selects the decoder's device for the
-// duration of the call and restores the caller's afterwards (callers may be pool threads or migrating goroutines).
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(const h264mi_decoder *d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != d->cfg.device) ok = hipSetDevice(d->cfg.device) == hipSuccess;
-        else prev = -1;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-#define GUARD(d)                                                        \
-    DeviceGuard guard_(d);                                              \
-    if (!guard_.ok) {                                                   \
-        set_error("hipSetDevice(%d) failed", (d)->cfg.device);          \
-        return H264MI_EDEVICE;                                          \
-    }
 
 extern "C" const char *h264mi_last_error_string(void) { return last_error(); }
 extern "C" const char *h264mi_version(void) { return "h264mi 0.1 (gfx950)"; }
@@ -470,20 +251,12 @@ static void free_all(h264mi_decoder *d) {
     if (d->d_xctl) hipFree(d->d_xctl);
     if (d->h_xstatus) hipHostFree(d->h_xstatus);
     if (d->d_pools) hipFree(d->d_pools);
-    for (int i = 0; i < 2; i++) {
-        if (d->h_pack[i]) hipHostFree(d->h_pack[i]);
-        if (d->d_pack[i]) hipFree(d->d_pack[i]);
-        if (d->ev_pack[i]) hipEventDestroy(d->ev_pack[i]);
-        if (d->h_conv[i]) hipHostFree(d->h_conv[i]);
-        if (d->d_conv[i]) hipFree(d->d_conv[i]);
-        if (d->ev_conv[i]) hipEventDestroy(d->ev_conv[i]);
-        if (d->h_scale[i]) hipHostFree(d->h_scale[i]);
-        if (d->d_scale[i]) hipFree(d->d_scale[i]);
-        if (d->ev_scale[i]) hipEventDestroy(d->ev_scale[i]);
-        if (d->h_tensor[i]) hipHostFree(d->h_tensor[i]);
-        if (d->d_tensor[i]) hipFree(d->d_tensor[i]);
-        if (d->ev_tensor[i]) hipEventDestroy(d->ev_tensor[i]);
-    }
+    for (DescTables &t : d->tables)
+        for (int i = 0; i < 2; i++) {
+            if (t.h[i]) hipHostFree(t.h[i]);
+            if (t.d[i]) hipFree(t.d[i]);
+            if (t.ev[i]) hipEventDestroy(t.ev[i]);
+        }
     if (d->d_frames) hipFree(d->d_frames);
     if (d->d_tables) hipFree(d->d_tables);
     if (d->h_tables) hipHostFree(d->h_tables);
@@ -2217,7 +1990,7 @@ extern "C" int32_t h264mi_stream_frame_count(h264mi_decoder *d, int32_t stream, 
     return H264MI_OK;
 }
 
-static int frame_ptrs(h264mi_decoder *d, int stream, int frame, uint8_t **y, const OutFrame **of) {
+int frame_ptrs(h264mi_decoder *d, int stream, int frame, uint8_t **y, const OutFrame **of) {
     if (!d || stream < 0 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
     const std::vector<OutFrame> &out = d->stage[d->exec].out[stream];
     if (frame < 0 || frame >= static_cast<int>(out.size())) return H264MI_EINVAL;
@@ -2271,12 +2044,6 @@ extern "C" int32_t h264mi_stream_output_order(h264mi_decoder *d, int32_t stream,
     return H264MI_OK;
 }
 
-// the picture's own geometry (a new SPS may have activated later in the same batch)
-static void crop_rect(const OutFrame *of, int crop, int *x0, int *y0, int *w, int *h) {
-    *x0 = *y0 = 0, *w = of->wmb * 16, *h = of->hmb * 16;
-    if (crop) *x0 = of->crop_x, *y0 = of->crop_y, *w = of->width, *h = of->height;
-}
-
 extern "C" int32_t h264mi_frame_read(h264mi_decoder *d, int32_t stream, int32_t frame, int32_t crop, uint8_t *dst, size_t cap) {
     uint8_t *p;
     const OutFrame *of;
@@ -2299,106 +2066,6 @@ extern "C" int32_t h264mi_frame_read(h264mi_decoder *d, int32_t stream, int32_t 
     return H264MI_OK;
 }
 
-// K6 over a list of frames: descriptors go through a small pinned table, one launch packs them all.
-static int pack_frames(h264mi_decoder *d, const std::vector<std::pair<int, int>> &frames /* (stream, frame) */, void *dst, size_t cap, size_t *bytes) {
-    GUARD(d);
-    const int ps = d->pack_slot ^= 1;
-    if (!d->ev_pack[ps]) HIP_TRY(hipEventCreateWithFlags(&d->ev_pack[ps], hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(d->ev_pack[ps])); // the launch that used this table (two calls ago) has read it
-    if (frames.size() > d->pack_cap[ps]) {
-        if (d->h_pack[ps]) hipHostFree(d->h_pack[ps]);
-        if (d->d_pack[ps]) hipFree(d->d_pack[ps]);
-        d->h_pack[ps] = nullptr, d->d_pack[ps] = nullptr;
-        d->pack_cap[ps] = std::max<size_t>(frames.size(), 64);
-        HIP_TRY(hipHostMalloc(&d->h_pack[ps], sizeof(PackDesc) * d->pack_cap[ps]));
-        HIP_TRY(hipMalloc(&d->d_pack[ps], sizeof(PackDesc) * d->pack_cap[ps]));
-    }
-    size_t off = 0;
-    int hmax = 0;
-    for (size_t i = 0; i < frames.size(); i++) {
-        uint8_t *p;
-        const OutFrame *of;
-        int x0, y0, w, h;
-        int r = frame_ptrs(d, frames[i].first, frames[i].second, &p, &of);
-        if (r != H264MI_OK) return r;
-        crop_rect(of, 1, &x0, &y0, &w, &h);
-        PackDesc &pk = d->h_pack[ps][i];
-        pk.src = reinterpret_cast<uint64_t>(p), pk.dst_off = off;
-        pk.W = of->wmb * 16, pk.H = of->hmb * 16, pk.x0 = x0, pk.y0 = y0, pk.w = w, pk.h = h;
-        off += H264MI_I420_SIZE(w, h);
-        hmax = std::max(hmax, h);
-    }
-    if (bytes) *bytes = off;
-    if (off > cap) return H264MI_ECAPACITY;
-    if (frames.empty()) return H264MI_OK;
-    // (in order on the decoder's stream, which has waited for the reconstruction of the last executed pass: h264mi_batch_execute)
-    HIP_TRY(hipMemcpyAsync(d->d_pack[ps], d->h_pack[ps], sizeof(PackDesc) * frames.size(), hipMemcpyHostToDevice, d->stream));
-    const int rows_per_block = 32;
-    hipLaunchKernelGGL(k_pack, dim3(static_cast<uint32_t>(frames.size()), (hmax + 2 * ((hmax + 1) / 2) + rows_per_block - 1) / rows_per_block), dim3(256), 0, d->stream, d->d_pack[ps],
-                       static_cast<uint8_t *>(dst), rows_per_block);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(d->ev_pack[ps], d->stream));
-    d->last_pack = d->ev_pack[ps];
-    return H264MI_OK;
-}
-
-extern "C" int32_t h264mi_frame_pack_device(h264mi_decoder *d, int32_t stream, int32_t frame, void *dst, size_t cap) {
-    if (!d || !dst) return H264MI_EINVAL;
-    return pack_frames(d, {{stream, frame}}, dst, cap, nullptr);
-}
-
-extern "C" int32_t h264mi_batch_pack_device(h264mi_decoder *d, int32_t stream, void *dst, size_t cap, size_t *bytes) {
-    if (!d || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
-    std::vector<std::pair<int, int>> frames;
-    const Stage &g = d->stage[d->exec];
-    for (int si = 0; si < static_cast<int>(g.out.size()); si++)
-        if (stream < 0 || stream == si)
-            for (int f = 0; f < static_cast<int>(g.out[si].size()); f++) frames.push_back({si, f});
-    return pack_frames(d, frames, dst, cap, bytes);
-}
-
-// ---------------------------------------------------------------- output formats (K7): the rule of include/h264mi.h
-// (the reference has no output process: h264/server.go:113-166 stops at the parsed slice)
-extern "C" int32_t h264mi_output_size(int32_t format, int32_t w, int32_t h, size_t *bytes) {
-    if (!bytes || w <= 0 || h <= 0) return H264MI_EINVAL;
-    switch (format) {
-    case H264MI_FMT_I420:
-    case H264MI_FMT_NV12: *bytes = H264MI_I420_SIZE(w, h); return H264MI_OK;
-    case H264MI_FMT_RGB24:
-    case H264MI_FMT_RGBP: *bytes = static_cast<size_t>(3) * w * h; return H264MI_OK;
-    }
-    set_error("unknown output format %d", format);
-    return H264MI_EINVAL;
-}
-
-extern "C" int32_t h264mi_csc_resolve(int32_t csc, int32_t matrix_coefficients, int32_t video_full_range, int32_t width, int32_t height, int32_t *resolved) {
-    if (!resolved) return H264MI_EINVAL;
-    int matrix = csc & 15;
-    if (csc < 0 || (csc & ~(15 | H264MI_CSC_FULL_RANGE | H264MI_CSC_CHROMA_BILINEAR)) || matrix > H264MI_CSC_BT709) {
-        set_error("csc %d: not a matrix (0 auto, 1 BT.601, 2 BT.709) with H264MI_CSC_FULL_RANGE / H264MI_CSC_CHROMA_BILINEAR", csc);
-        return H264MI_EINVAL;
-    }
-    int full = csc & H264MI_CSC_FULL_RANGE;
-    if (matrix == H264MI_CSC_AUTO) {
-        if (full) {
-            set_error("H264MI_CSC_FULL_RANGE needs an explicit matrix: with H264MI_CSC_AUTO the range comes from the stream");
-            return H264MI_EINVAL;
-        }
-        switch (matrix_coefficients) {
-        case 1: matrix = H264MI_CSC_BT709; break;
-        case 5:
-        case 6: matrix = H264MI_CSC_BT601; break;
-        case 2: matrix = (width >= 1280 || height > 576) ? H264MI_CSC_BT709 : H264MI_CSC_BT601; break;
-        default:
-            set_error("matrix_coefficients %d of the stream is not BT.601 / BT.709 (1, 2, 5, 6): pass an explicit matrix (H264MI_CSC_BT601 / H264MI_CSC_BT709)", matrix_coefficients);
-            return H264MI_EUNSUPPORTED;
-        }
-        full = video_full_range ? H264MI_CSC_FULL_RANGE : 0;
-    }
-    *resolved = matrix | full | (csc & H264MI_CSC_CHROMA_BILINEAR);
-    return H264MI_OK;
-}
-
 extern "C" int32_t h264mi_frame_colour(h264mi_decoder *d, int32_t stream, int32_t frame, int32_t *matrix_coefficients, int32_t *video_full_range) {
     uint8_t *p;
     const OutFrame *of;
@@ -2407,422 +2074,6 @@ extern "C" int32_t h264mi_frame_colour(h264mi_decoder *d, int32_t stream, int32_
     if (matrix_coefficients) *matrix_coefficients = of->matrix_coefficients;
     if (video_full_range) *video_full_range = of->video_full_range;
     return H264MI_OK;
-}
-
-// K7 over a list of frames: pack_frames' discipline (two pinned descriptor tables fenced by events, one launch on the decoder's stream, last_pack).
-// Every frame is resolved and sized before anything is launched.
-static int convert_frames(h264mi_decoder *d, const std::vector<std::pair<int, int>> &frames /* (stream, frame) */, int format, int csc, void *dst, size_t cap, size_t *bytes) {
-    if (format != H264MI_FMT_NV12 && format != H264MI_FMT_RGB24 && format != H264MI_FMT_RGBP) {
-        set_error("output format %d: not H264MI_FMT_NV12, _RGB24 or _RGBP", format);
-        return H264MI_EINVAL;
-    }
-    if (format == H264MI_FMT_NV12 && csc != 0) {
-        set_error("H264MI_FMT_NV12 converts nothing: csc must be 0, not %d", csc);
-        return H264MI_EINVAL;
-    }
-    int probe;
-    int r = h264mi_csc_resolve(csc, 1, 0, 16, 16, &probe); // is csc legal at all (whatever the frames are, and if there are none)
-    if (r != H264MI_OK) return r;
-    GUARD(d);
-    // every frame is resolved and sized before a descriptor table is taken: a call that fails launches nothing and waits for nothing
-    std::vector<ConvDesc> descs(frames.size());
-    size_t off = 0;
-    int hmax = 0;
-    for (size_t i = 0; i < frames.size(); i++) {
-        uint8_t *p;
-        const OutFrame *of;
-        int x0, y0, w, h, res = 0;
-        r = frame_ptrs(d, frames[i].first, frames[i].second, &p, &of);
-        if (r != H264MI_OK) return r;
-        crop_rect(of, 1, &x0, &y0, &w, &h);
-        if (format != H264MI_FMT_NV12) {
-            r = h264mi_csc_resolve(csc, of->matrix_coefficients, of->video_full_range, w, h, &res);
-            if (r != H264MI_OK) return r;
-        }
-        ConvDesc &cv = descs[i];
-        cv.src = reinterpret_cast<uint64_t>(p), cv.dst_off = off;
-        cv.W = of->wmb * 16, cv.H = of->hmb * 16, cv.x0 = x0, cv.y0 = y0, cv.w = w, cv.h = h;
-        cv.format = format, cv.pad = 0;
-        cv.cset = format == H264MI_FMT_NV12 ? 0 : 2 * ((res & 15) - 1) + ((res & H264MI_CSC_FULL_RANGE) ? 1 : 0);
-        cv.bilinear = (res & H264MI_CSC_CHROMA_BILINEAR) ? 1 : 0;
-        size_t sz = 0;
-        h264mi_output_size(format, w, h, &sz);
-        off += sz;
-        hmax = std::max(hmax, h);
-    }
-    if (bytes) *bytes = off;
-    if (off > cap) return H264MI_ECAPACITY;
-    if (frames.empty()) return H264MI_OK;
-    const int ps = d->conv_slot ^= 1;
-    if (!d->ev_conv[ps]) HIP_TRY(hipEventCreateWithFlags(&d->ev_conv[ps], hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(d->ev_conv[ps])); // the launch that used this table (two calls ago) has read it
-    if (frames.size() > d->conv_cap[ps]) {
-        if (d->h_conv[ps]) hipHostFree(d->h_conv[ps]);
-        if (d->d_conv[ps]) hipFree(d->d_conv[ps]);
-        d->h_conv[ps] = nullptr, d->d_conv[ps] = nullptr, d->conv_cap[ps] = 0;
-        const size_t n = std::max<size_t>(frames.size(), 64);
-        HIP_TRY(hipHostMalloc(&d->h_conv[ps], sizeof(ConvDesc) * n));
-        HIP_TRY(hipMalloc(&d->d_conv[ps], sizeof(ConvDesc) * n));
-        d->conv_cap[ps] = n;
-    }
-    memcpy(d->h_conv[ps], descs.data(), sizeof(ConvDesc) * frames.size());
-    if (bytes) *bytes = off;
-    if (off > cap) return H264MI_ECAPACITY;
-    if (frames.empty()) return H264MI_OK;
-    // (in order on the decoder's stream, which has waited for the reconstruction of the last executed pass: h264mi_batch_execute)
-    HIP_TRY(hipMemcpyAsync(d->d_conv[ps], d->h_conv[ps], sizeof(ConvDesc) * frames.size(), hipMemcpyHostToDevice, d->stream));
-    const int pairs_per_block = 8; // 1080p: 8 x 120 items of 2 x 16 pixels for 256 threads, 68 blocks per frame
-    hipLaunchKernelGGL(k_convert, dim3(static_cast<uint32_t>(frames.size()), ((hmax + 1) / 2 + pairs_per_block - 1) / pairs_per_block), dim3(256), 0, d->stream, d->d_conv[ps],
-                       static_cast<uint8_t *>(dst), pairs_per_block);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(d->ev_conv[ps], d->stream));
-    d->last_pack = d->ev_conv[ps];
-    return H264MI_OK;
-}
-
-extern "C" int32_t h264mi_frame_convert_device(h264mi_decoder *d, int32_t stream, int32_t frame, int32_t format, int32_t csc, void *dst, size_t cap) {
-    if (!d || !dst) return H264MI_EINVAL;
-    return convert_frames(d, {{stream, frame}}, format, csc, dst, cap, nullptr);
-}
-
-extern "C" int32_t h264mi_batch_convert_device(h264mi_decoder *d, int32_t stream, int32_t format, int32_t csc, void *dst, size_t cap, size_t *bytes) {
-    if (!d || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
-    std::vector<std::pair<int, int>> frames;
-    const Stage &g = d->stage[d->exec];
-    for (int si = 0; si < static_cast<int>(g.out.size()); si++)
-        if (stream < 0 || stream == si)
-            for (int f = 0; f < static_cast<int>(g.out[si].size()); f++) frames.push_back({si, f});
-    return convert_frames(d, frames, format, csc, dst, cap, bytes);
-}
-
-// ---------------------------------------------------------------- scaled output (K8): the rule of include/h264mi.h, "Scaled output"
-// bilinear: position of output index i on an axis of n_in samples scaled to n_out -- a in the high bits, f in bits 8 .. 15
-static inline void bilinear_axis(int n_in, int n_out, uint32_t *step, int32_t *half) {
-    *step = (static_cast<uint32_t>(n_in) << 16) / static_cast<uint32_t>(n_out); // n_in <= 16384: fits
-    *half = static_cast<int32_t>(*step >> 1) - 32768;
-}
-
-extern "C" int32_t h264mi_scale_taps(int32_t filter, int32_t n_in, int32_t n_out, int32_t i, int32_t *first, int32_t *count, int32_t *weights, int32_t cap) {
-    if (!first || !count || !weights || cap < 0) return H264MI_EINVAL;
-    if (filter != H264MI_SCALE_BILINEAR && filter != H264MI_SCALE_AREA) {
-        set_error("scale filter %d: not H264MI_SCALE_BILINEAR or H264MI_SCALE_AREA", filter);
-        return H264MI_EINVAL;
-    }
-    if (n_in < 1 || n_in > H264MI_SCALE_MAX || n_out < 1 || n_out > H264MI_SCALE_MAX || i < 0 || i >= n_out) {
-        set_error("scale taps: n_in %d, n_out %d must be 1 .. %d and 0 <= i (%d) < n_out", n_in, n_out, H264MI_SCALE_MAX, i);
-        return H264MI_EINVAL;
-    }
-    if (filter == H264MI_SCALE_BILINEAR) {
-        uint32_t step;
-        int32_t half;
-        bilinear_axis(n_in, n_out, &step, &half);
-        const int32_t P = std::min(std::max(static_cast<int32_t>(i * step) + half, 0), (n_in - 1) << 16);
-        *first = P >> 16, *count = 2;
-        if (cap < 2) return H264MI_ECAPACITY;
-        const int32_t f = (P >> 8) & 255;
-        weights[0] = 256 - f, weights[1] = f;
-        return H264MI_OK;
-    }
-    if (n_out > n_in) {
-        set_error("H264MI_SCALE_AREA only scales down: %d -> %d", n_in, n_out);
-        return H264MI_EINVAL;
-    }
-    const int32_t lo = i * n_in, hi = lo + n_in; // <= 2^28
-    const int32_t k0 = lo / n_out, k1 = (hi - 1) / n_out;
-    *first = k0, *count = k1 - k0 + 1;
-    if (cap < *count) return H264MI_ECAPACITY;
-    for (int32_t k = k0; k <= k1; k++) weights[k - k0] = std::min(hi, (k + 1) * n_out) - std::max(lo, k * n_out);
-    return H264MI_OK;
-}
-
-// K8 over a list of frames: convert_frames' discipline.  Every frame is checked, resolved and sized before anything is launched.
-static int scale_frames(h264mi_decoder *d, const std::vector<std::pair<int, int>> &frames /* (stream, frame) */, int format, int csc, int ow, int oh, int filter, void *dst,
-                        size_t cap, size_t *bytes) {
-    if (format != H264MI_FMT_I420 && format != H264MI_FMT_NV12 && format != H264MI_FMT_RGB24 && format != H264MI_FMT_RGBP) {
-        set_error("output format %d: not H264MI_FMT_I420, _NV12, _RGB24 or _RGBP", format);
-        return H264MI_EINVAL;
-    }
-    const bool plain = format == H264MI_FMT_I420 || format == H264MI_FMT_NV12;
-    if (plain && csc != 0) {
-        set_error("H264MI_FMT_I420 and H264MI_FMT_NV12 convert nothing: csc must be 0, not %d", csc);
-        return H264MI_EINVAL;
-    }
-    if (filter != H264MI_SCALE_BILINEAR && filter != H264MI_SCALE_AREA) {
-        set_error("scale filter %d: not H264MI_SCALE_BILINEAR or H264MI_SCALE_AREA", filter);
-        return H264MI_EINVAL;
-    }
-    if (ow < 1 || ow > H264MI_SCALE_MAX || oh < 1 || oh > H264MI_SCALE_MAX) {
-        set_error("output size %d x %d: both must be 1 .. %d", ow, oh, H264MI_SCALE_MAX);
-        return H264MI_EINVAL;
-    }
-    int probe;
-    int r = h264mi_csc_resolve(csc, 1, 0, 16, 16, &probe); // is csc legal at all (whatever the frames are, and if there are none)
-    if (r != H264MI_OK) return r;
-    GUARD(d);
-    std::vector<ScaleDesc> descs(frames.size());
-    size_t one = 0, off = 0;
-    h264mi_output_size(format, ow, oh, &one);
-    for (size_t i = 0; i < frames.size(); i++) {
-        uint8_t *p;
-        const OutFrame *of;
-        int x0, y0, w, h, res = 0;
-        r = frame_ptrs(d, frames[i].first, frames[i].second, &p, &of);
-        if (r != H264MI_OK) return r;
-        crop_rect(of, 1, &x0, &y0, &w, &h);
-        if (filter == H264MI_SCALE_AREA) {
-            if (ow > w || oh > h) {
-                set_error("H264MI_SCALE_AREA only scales down: frame %d of stream %d is %d x %d, the output %d x %d", frames[i].second, frames[i].first, w, h, ow, oh);
-                return H264MI_EINVAL;
-            }
-            const uint64_t px = static_cast<uint64_t>(w) * h;
-            if (255 * px + (px >> 1) >= (static_cast<uint64_t>(1) << 32)) { // the largest weighted sum and its rounding term
-                set_error("H264MI_SCALE_AREA sums in 32 bits and needs 255 * w * h + ((w * h) >> 1) < 2^32: frame %d of stream %d is %d x %d", frames[i].second, frames[i].first, w, h);
-                return H264MI_EUNSUPPORTED;
-            }
-        }
-        if (!plain) { // from the frame's SPS and its display (source) size, never from the output size
-            r = h264mi_csc_resolve(csc, of->matrix_coefficients, of->video_full_range, w, h, &res);
-            if (r != H264MI_OK) return r;
-        }
-        ScaleDesc &sc = descs[i];
-        sc.src = reinterpret_cast<uint64_t>(p), sc.dst_off = off;
-        sc.W = of->wmb * 16, sc.H = of->hmb * 16, sc.x0 = x0, sc.y0 = y0, sc.w = w, sc.h = h;
-        sc.format = format, sc.filter = filter;
-        sc.cset = plain ? 0 : 2 * ((res & 15) - 1) + ((res & H264MI_CSC_FULL_RANGE) ? 1 : 0);
-        sc.bilinear = (res & H264MI_CSC_CHROMA_BILINEAR) ? 1 : 0;
-        bilinear_axis(w, ow, &sc.step[0], &sc.half[0]);
-        bilinear_axis(h, oh, &sc.step[1], &sc.half[1]);
-        bilinear_axis((w + 1) / 2, (ow + 1) / 2, &sc.step[2], &sc.half[2]);
-        bilinear_axis((h + 1) / 2, (oh + 1) / 2, &sc.step[3], &sc.half[3]);
-        off += one;
-    }
-    if (bytes) *bytes = off;
-    if (off > cap) return H264MI_ECAPACITY;
-    if (frames.empty()) return H264MI_OK;
-    const int ps = d->scale_slot ^= 1;
-    if (!d->ev_scale[ps]) HIP_TRY(hipEventCreateWithFlags(&d->ev_scale[ps], hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(d->ev_scale[ps])); // the launch that used this table (two calls ago) has read it
-    if (frames.size() > d->scale_cap[ps]) {
-        if (d->h_scale[ps]) hipHostFree(d->h_scale[ps]);
-        if (d->d_scale[ps]) hipFree(d->d_scale[ps]);
-        d->h_scale[ps] = nullptr, d->d_scale[ps] = nullptr, d->scale_cap[ps] = 0;
-        const size_t n = std::max<size_t>(frames.size(), 64);
-        HIP_TRY(hipHostMalloc(&d->h_scale[ps], sizeof(ScaleDesc) * n));
-        HIP_TRY(hipMalloc(&d->d_scale[ps], sizeof(ScaleDesc) * n));
-        d->scale_cap[ps] = n;
-    }
-    memcpy(d->h_scale[ps], descs.data(), sizeof(ScaleDesc) * frames.size());
-    // (in order on the decoder's stream, which has waited for the reconstruction of the last executed pass: h264mi_batch_execute)
-    HIP_TRY(hipMemcpyAsync(d->d_scale[ps], d->h_scale[ps], sizeof(ScaleDesc) * frames.size(), hipMemcpyHostToDevice, d->stream));
-    // about 256 items of 2 x 16 output pixels per block: 640 wide: 6 row pairs x 40 groups; 224 wide: 18 x 14
-    const int ngroups = (ow + 15) / 16, npairs = (oh + 1) / 2;
-    const int pairs_per_block = std::max(1, std::min(256 / ngroups, npairs));
-    const dim3 grid(static_cast<uint32_t>(frames.size()), (npairs + pairs_per_block - 1) / pairs_per_block);
-    if (filter == H264MI_SCALE_AREA) hipLaunchKernelGGL(k_scale_area, grid, dim3(256), 0, d->stream, d->d_scale[ps], static_cast<uint8_t *>(dst), ow, oh, pairs_per_block);
-    else hipLaunchKernelGGL(k_scale, grid, dim3(256), 0, d->stream, d->d_scale[ps], static_cast<uint8_t *>(dst), ow, oh, pairs_per_block);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(d->ev_scale[ps], d->stream));
-    d->last_pack = d->ev_scale[ps];
-    return H264MI_OK;
-}
-
-extern "C" int32_t h264mi_frame_scale_device(h264mi_decoder *d, int32_t stream, int32_t frame, int32_t format, int32_t csc, int32_t out_w, int32_t out_h, int32_t filter,
-                                             void *dst, size_t cap) {
-    if (!d || !dst) return H264MI_EINVAL;
-    return scale_frames(d, {{stream, frame}}, format, csc, out_w, out_h, filter, dst, cap, nullptr);
-}
-
-extern "C" int32_t h264mi_batch_scale_device(h264mi_decoder *d, int32_t stream, int32_t format, int32_t csc, int32_t out_w, int32_t out_h, int32_t filter, void *dst,
-                                             size_t cap, size_t *bytes) {
-    if (!d || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
-    std::vector<std::pair<int, int>> frames;
-    const Stage &g = d->stage[d->exec];
-    for (int si = 0; si < static_cast<int>(g.out.size()); si++)
-        if (stream < 0 || stream == si)
-            for (int f = 0; f < static_cast<int>(g.out[si].size()); f++) frames.push_back({si, f});
-    return scale_frames(d, frames, format, csc, out_w, out_h, filter, dst, cap, bytes);
-}
-
-// ---------------------------------------------------------------- model input (K9): the rule of include/h264mi.h, "Model input"
-extern "C" int32_t h264mi_fit_rect(int32_t fit, int32_t w, int32_t h, int32_t out_w, int32_t out_h, int32_t *px, int32_t *py, int32_t *sw, int32_t *sh) {
-    if (!px || !py || !sw || !sh) return H264MI_EINVAL;
-    if (fit != H264MI_FIT_STRETCH && fit != H264MI_FIT_LETTERBOX) {
-        set_error("fit %d: not H264MI_FIT_STRETCH or H264MI_FIT_LETTERBOX", fit);
-        return H264MI_EINVAL;
-    }
-    if (w < 1 || w > H264MI_SCALE_MAX || h < 1 || h > H264MI_SCALE_MAX || out_w < 1 || out_w > H264MI_SCALE_MAX || out_h < 1 || out_h > H264MI_SCALE_MAX) {
-        set_error("fit rect: source %d x %d and canvas %d x %d must all be 1 .. %d", w, h, out_w, out_h, H264MI_SCALE_MAX);
-        return H264MI_EINVAL;
-    }
-    if (fit == H264MI_FIT_STRETCH) {
-        *px = 0, *py = 0, *sw = out_w, *sh = out_h;
-        return H264MI_OK;
-    }
-    if (w * out_h >= h * out_w) { // the width fills the canvas; products <= 2^28, the rounded quotient's numerator <= 2 * 2^28 + 2^14
-        *sw = out_w, *sh = std::min(std::max((2 * h * out_w + w) / (2 * w), 1), out_h);
-    } else {
-        *sh = out_h, *sw = std::min(std::max((2 * w * out_h + h) / (2 * h), 1), out_w);
-    }
-    *px = (out_w - *sw) >> 1, *py = (out_h - *sh) >> 1;
-    return H264MI_OK;
-}
-
-static inline int tensor_elem_size(int dtype) { return dtype == H264MI_DT_U8 ? 1 : dtype == H264MI_DT_F32 ? 4 : 2; }
-
-extern "C" int32_t h264mi_tensor_size(const h264mi_tensor_spec *spec, size_t *bytes) {
-    if (!spec || !bytes) return H264MI_EINVAL;
-    if (spec->format != H264MI_FMT_RGBP && spec->format != H264MI_FMT_RGB24) {
-        set_error("tensor format %d: not H264MI_FMT_RGBP or H264MI_FMT_RGB24", spec->format);
-        return H264MI_EINVAL;
-    }
-    if (spec->dtype != H264MI_DT_U8 && spec->dtype != H264MI_DT_F16 && spec->dtype != H264MI_DT_BF16 && spec->dtype != H264MI_DT_F32) {
-        set_error("tensor dtype %d: not H264MI_DT_U8, _F16, _BF16 or _F32", spec->dtype);
-        return H264MI_EINVAL;
-    }
-    int probe;
-    int r = h264mi_csc_resolve(spec->csc, 1, 0, 16, 16, &probe); // is csc legal at all
-    if (r != H264MI_OK) return r;
-    if (spec->out_w < 1 || spec->out_w > H264MI_SCALE_MAX || spec->out_h < 1 || spec->out_h > H264MI_SCALE_MAX) {
-        set_error("tensor size %d x %d: both must be 1 .. %d", spec->out_w, spec->out_h, H264MI_SCALE_MAX);
-        return H264MI_EINVAL;
-    }
-    if (spec->filter != H264MI_SCALE_BILINEAR && spec->filter != H264MI_SCALE_AREA) {
-        set_error("scale filter %d: not H264MI_SCALE_BILINEAR or H264MI_SCALE_AREA", spec->filter);
-        return H264MI_EINVAL;
-    }
-    if (spec->fit != H264MI_FIT_STRETCH && spec->fit != H264MI_FIT_LETTERBOX) {
-        set_error("fit %d: not H264MI_FIT_STRETCH or H264MI_FIT_LETTERBOX", spec->fit);
-        return H264MI_EINVAL;
-    }
-    if (spec->flags & ~H264MI_TENSOR_BGR) {
-        set_error("tensor flags 0x%x: only H264MI_TENSOR_BGR is defined", static_cast<unsigned>(spec->flags));
-        return H264MI_EINVAL;
-    }
-    for (int c = 0; c < 3; c++) {
-        if (!std::isfinite(spec->scale[c]) || !std::isfinite(spec->bias[c])) {
-            set_error("tensor scale[%d] = %g, bias[%d] = %g: both must be finite", c, static_cast<double>(spec->scale[c]), c, static_cast<double>(spec->bias[c]));
-            return H264MI_EINVAL;
-        }
-        if (spec->dtype == H264MI_DT_U8 && (spec->scale[c] != 1.0f || spec->bias[c] != 0.0f)) {
-            set_error("H264MI_DT_U8 maps nothing: scale[%d] must be 1 and bias[%d] 0, not %g and %g", c, c, static_cast<double>(spec->scale[c]), static_cast<double>(spec->bias[c]));
-            return H264MI_EINVAL;
-        }
-    }
-    *bytes = static_cast<size_t>(3) * spec->out_w * spec->out_h * tensor_elem_size(spec->dtype);
-    return H264MI_OK;
-}
-
-// K9 over a list of items: scale_frames' discipline.  Every item is checked, resolved and sized before anything is launched.
-static int tensor_items(h264mi_decoder *d, const h264mi_tensor_spec *spec, const h264mi_tensor_item *items, size_t n, void *dst, size_t cap, size_t *bytes) {
-    size_t one = 0;
-    int r = h264mi_tensor_size(spec, &one);
-    if (r != H264MI_OK) return r;
-    const int es = tensor_elem_size(spec->dtype), ow = spec->out_w, oh = spec->out_h;
-    if (reinterpret_cast<uintptr_t>(dst) % es) {
-        set_error("tensor destination %p: not aligned to the element size %d", dst, es);
-        return H264MI_EINVAL;
-    }
-    GUARD(d);
-    std::vector<TensorDesc> descs(n);
-    size_t off = 0;
-    for (size_t i = 0; i < n; i++) {
-        const h264mi_tensor_item &it = items[i];
-        uint8_t *p;
-        const OutFrame *of;
-        int x0, y0, w, h, res = 0;
-        r = frame_ptrs(d, it.stream, it.frame, &p, &of);
-        if (r != H264MI_OK) {
-            set_error("tensor item %zu: no frame %d of stream %d in the last executed batch", i, it.frame, it.stream);
-            return r;
-        }
-        crop_rect(of, 1, &x0, &y0, &w, &h);
-        int rx = it.x, ry = it.y, rw = it.w, rh = it.h;
-        if (rw == 0 && rh == 0) rw = w, rh = h; // the whole frame (legal from the origin (0, 0) only)
-        if (rx < 0 || ry < 0 || (rx & 1) || (ry & 1) || rw < 1 || rh < 1 || rx > w - rw || ry > h - rh) {
-            set_error("tensor item %zu: region (%d, %d, %d, %d) of frame %d of stream %d (%d x %d): the origin must be even and non-negative, the size at least 1 x 1, all of it inside the frame",
-                      i, it.x, it.y, it.w, it.h, it.frame, it.stream, w, h);
-            return H264MI_EINVAL;
-        }
-        int px, py, sw, sh;
-        r = h264mi_fit_rect(spec->fit, rw, rh, ow, oh, &px, &py, &sw, &sh);
-        if (r != H264MI_OK) return r;
-        if (spec->filter == H264MI_SCALE_AREA) {
-            if (sw > rw || sh > rh) {
-                set_error("H264MI_SCALE_AREA only scales down: item %zu, region %d x %d of frame %d of stream %d, the picture %d x %d", i, rw, rh, it.frame, it.stream, sw, sh);
-                return H264MI_EINVAL;
-            }
-            const uint64_t px64 = static_cast<uint64_t>(rw) * rh;
-            if (255 * px64 + (px64 >> 1) >= (static_cast<uint64_t>(1) << 32)) {
-                set_error("H264MI_SCALE_AREA sums in 32 bits and needs 255 * w * h + ((w * h) >> 1) < 2^32: item %zu, region %d x %d of frame %d of stream %d", i, rw, rh, it.frame, it.stream);
-                return H264MI_EUNSUPPORTED;
-            }
-        }
-        // from the frame's SPS and its DISPLAY size, never from the region or the canvas
-        r = h264mi_csc_resolve(spec->csc, of->matrix_coefficients, of->video_full_range, w, h, &res);
-        if (r != H264MI_OK) return r;
-        TensorDesc &td = descs[i];
-        td.src = reinterpret_cast<uint64_t>(p), td.dst_off = off;
-        td.W = of->wmb * 16, td.H = of->hmb * 16, td.x0 = x0 + rx, td.y0 = y0 + ry, td.w = rw, td.h = rh; // rx, ry even: (x0 + rx) / 2 = x0 / 2 + rx / 2
-        td.sw = sw, td.sh = sh, td.px = px, td.py = py;
-        td.cset = 2 * ((res & 15) - 1) + ((res & H264MI_CSC_FULL_RANGE) ? 1 : 0);
-        td.bilinear = (res & H264MI_CSC_CHROMA_BILINEAR) ? 1 : 0;
-        bilinear_axis(rw, sw, &td.step[0], &td.half[0]);
-        bilinear_axis(rh, sh, &td.step[1], &td.half[1]);
-        bilinear_axis((rw + 1) / 2, (sw + 1) / 2, &td.step[2], &td.half[2]);
-        bilinear_axis((rh + 1) / 2, (sh + 1) / 2, &td.step[3], &td.half[3]);
-        off += one;
-    }
-    if (bytes) *bytes = off;
-    if (off > cap) return H264MI_ECAPACITY;
-    if (n == 0) return H264MI_OK;
-    const int ps = d->tensor_slot ^= 1;
-    if (!d->ev_tensor[ps]) HIP_TRY(hipEventCreateWithFlags(&d->ev_tensor[ps], hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(d->ev_tensor[ps])); // the launch that used this table (two calls ago) has read it
-    if (n > d->tensor_cap[ps]) {
-        if (d->h_tensor[ps]) hipHostFree(d->h_tensor[ps]);
-        if (d->d_tensor[ps]) hipFree(d->d_tensor[ps]);
-        d->h_tensor[ps] = nullptr, d->d_tensor[ps] = nullptr, d->tensor_cap[ps] = 0;
-        const size_t m = std::max<size_t>(n, 64);
-        HIP_TRY(hipHostMalloc(&d->h_tensor[ps], sizeof(TensorDesc) * m));
-        HIP_TRY(hipMalloc(&d->d_tensor[ps], sizeof(TensorDesc) * m));
-        d->tensor_cap[ps] = m;
-    }
-    memcpy(d->h_tensor[ps], descs.data(), sizeof(TensorDesc) * n);
-    // (in order on the decoder's stream, which has waited for the reconstruction of the last executed pass: h264mi_batch_execute)
-    HIP_TRY(hipMemcpyAsync(d->d_tensor[ps], d->h_tensor[ps], sizeof(TensorDesc) * n, hipMemcpyHostToDevice, d->stream));
-    TensorParams P;
-    const bool bgr = (spec->flags & H264MI_TENSOR_BGR) != 0;
-    P.ow = ow, P.oh = oh, P.dtype = spec->dtype, P.hwc = spec->format == H264MI_FMT_RGB24, P.bgr = bgr;
-    for (int p = 0; p < 3; p++) { // by channel position
-        const int c = bgr ? 2 - p : p;
-        P.pad[p] = spec->pad[c], P.scale[p] = spec->scale[c], P.bias[p] = spec->bias[c];
-    }
-    // about 256 thread items of 2 rows x 8 columns per block; a picture that does not start on a thread item's boundary needs one more group and row pair
-    const int ngroups = (ow + 7) / 8 + 1, npairs = (oh + 1) / 2 + 1;
-    P.pairs_per_block = std::max(1, std::min(256 / ngroups, npairs));
-    const dim3 grid(static_cast<uint32_t>(n), (npairs + P.pairs_per_block - 1) / P.pairs_per_block);
-    if (spec->filter == H264MI_SCALE_AREA) hipLaunchKernelGGL(k_tensor_area, grid, dim3(256), 0, d->stream, d->d_tensor[ps], static_cast<uint8_t *>(dst), P);
-    else hipLaunchKernelGGL(k_tensor, grid, dim3(256), 0, d->stream, d->d_tensor[ps], static_cast<uint8_t *>(dst), P);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(d->ev_tensor[ps], d->stream));
-    d->last_pack = d->ev_tensor[ps];
-    return H264MI_OK;
-}
-
-extern "C" int32_t h264mi_items_tensor_device(h264mi_decoder *d, const h264mi_tensor_spec *spec, const h264mi_tensor_item *items, int32_t n, void *dst, size_t cap,
-                                              size_t *bytes) {
-    if (!d || !spec || !dst || n < 0 || (n > 0 && !items)) return H264MI_EINVAL;
-    return tensor_items(d, spec, items, static_cast<size_t>(n), dst, cap, bytes);
-}
-
-extern "C" int32_t h264mi_batch_tensor_device(h264mi_decoder *d, int32_t stream, const h264mi_tensor_spec *spec, void *dst, size_t cap, size_t *bytes) {
-    if (!d || !spec || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
-    std::vector<h264mi_tensor_item> items;
-    const Stage &g = d->stage[d->exec];
-    for (int si = 0; si < static_cast<int>(g.out.size()); si++)
-        if (stream < 0 || stream == si)
-            for (int f = 0; f < static_cast<int>(g.out[si].size()); f++) items.push_back({si, f, 0, 0, 0, 0});
-    return tensor_items(d, spec, items.data(), items.size(), dst, cap, bytes);
 }
 
 extern "C" int32_t h264mi_frame_read_mbrecs(h264mi_decoder *d, int32_t stream, int32_t frame, uint8_t *rec, size_t cap) {
@@ -2866,7 +2117,7 @@ extern "C" int32_t h264mi_frame_read_mbmv1(h264mi_decoder *d, int32_t stream, in
 
 #if defined(H264MI_TEST_HOOKS)
 // ---- test and measurement hooks: built into libh264mi_hooks.so only (csrc/Makefile); the product library exports the ABI of include/h264mi.h and nothing else ----
-// 1 while a pack / convert launch is recorded that the next pass has to wait for before it rewrites frames (last_pack), else 0
+// 1 while an output launch (K6 .. K9, mi_output.cpp) is recorded that the next pass has to wait for before it rewrites frames (last_pack), else 0
 extern "C" int32_t h264mi_internal_pack_pending(h264mi_decoder *d, int32_t *pending) {
     if (!d || !pending) return H264MI_EINVAL;
     *pending = d->last_pack ? 1 : 0;

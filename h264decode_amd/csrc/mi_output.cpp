@@ -1,0 +1,482 @@
+// h264decode_amd/csrc/mi_output.cpp -- the output stage of libh264mi.so: what leaves the frame pool on the device.  K6 (k_pack: tight I420), K7
+// (k_convert: NV12 / RGB), K8 (k_scale: resized) and K9 (k_tensor: model input) over a list of frames of the last executed batch, and the
+// device-free rule functions of include/h264mi.h that say what those kernels compute (h264mi_output_size, _csc_resolve, _scale_taps, _fit_rect,
+// _tensor_size).  The four kernel families share ONE launch discipline (stage_descs / fence_launch below); each has descriptor tables of its own.
+// (the reference has no output process: h264/server.go:113-166 stops at the parsed slice)
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <utility>
+#include "mi_decoder.hpp"
+
+void crop_rect(const OutFrame *of, int crop, int *x0, int *y0, int *w, int *h) {
+    *x0 = *y0 = 0, *w = of->wmb * 16, *h = of->hmb * 16;
+    if (crop) *x0 = of->crop_x, *y0 = of->crop_y, *w = of->width, *h = of->height;
+}
+
+// ---------------------------------------------------------------- the launch discipline of K6 .. K9
+// Every call checks, resolves and sizes all of its frames first: a call that fails launches nothing and waits for nothing.  Then the descriptors go
+// through the family's next table (stage_descs), one launch on the decoder's stream takes them all, and the launch is fenced (fence_launch).
+typedef std::vector<std::pair<int, int>> FrameList; // (stream, frame)
+
+// every frame of `stream`, or of all streams (-1), of the last executed batch
+static FrameList batch_frames(const h264mi_decoder *d, int stream) {
+    FrameList frames;
+    const Stage &g = d->stage[d->exec];
+    for (int si = 0; si < static_cast<int>(g.out.size()); si++)
+        if (stream < 0 || stream == si)
+            for (int f = 0; f < static_cast<int>(g.out[si].size()); f++) frames.push_back({si, f});
+    return frames;
+}
+
+// what every descriptor begins with: the frame's planes and coded size, the rectangle read, the place in the destination
+template <class T> static void set_source(T &ds, const uint8_t *p, const OutFrame *of, int x0, int y0, int w, int h, size_t off) {
+    ds.src = reinterpret_cast<uint64_t>(p), ds.dst_off = off;
+    ds.W = of->wmb * 16, ds.H = of->hmb * 16, ds.x0 = x0, ds.y0 = y0, ds.w = w, ds.h = h;
+}
+
+// the descriptors of a call (at least one) into the next table of `t`, on their way to the device; *dev: where the kernel reads them
+template <class T> static int stage_descs(h264mi_decoder *d, DescTables &t, const std::vector<T> &descs, const T **dev) {
+    const int ps = t.slot ^= 1;
+    if (!t.ev[ps]) HIP_TRY(hipEventCreateWithFlags(&t.ev[ps], hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(t.ev[ps])); // the launch that used this table (two calls ago) has read it
+    const size_t bytes = sizeof(T) * descs.size();
+    if (bytes > t.cap[ps]) {
+        if (t.h[ps]) hipHostFree(t.h[ps]);
+        if (t.d[ps]) hipFree(t.d[ps]);
+        t.h[ps] = nullptr, t.d[ps] = nullptr, t.cap[ps] = 0;
+        const size_t n = sizeof(T) * std::max<size_t>(descs.size(), 64);
+        HIP_TRY(hipHostMalloc(&t.h[ps], n));
+        HIP_TRY(hipMalloc(&t.d[ps], n));
+        t.cap[ps] = n;
+    }
+    memcpy(t.h[ps], descs.data(), bytes);
+    // (in order on the decoder's stream, which has waited for the reconstruction of the last executed pass: h264mi_batch_execute)
+    HIP_TRY(hipMemcpyAsync(t.d[ps], t.h[ps], bytes, hipMemcpyHostToDevice, d->stream));
+    *dev = static_cast<const T *>(t.d[ps]);
+    return H264MI_OK;
+}
+
+// after the launch that reads the table stage_descs gave out: the table's event, which is also what the next pass waits for before it rewrites frames
+static int fence_launch(h264mi_decoder *d, DescTables &t) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(t.ev[t.slot], d->stream));
+    d->last_pack = t.ev[t.slot];
+    return H264MI_OK;
+}
+#define TRY(x)                        \
+    do {                              \
+        const int r_ = (x);           \
+        if (r_ != H264MI_OK) return r_; \
+    } while (0)
+
+// ---------------------------------------------------------------- argument checks shared by the rule functions and the launches
+// `names`: the formats of `allowed` (bit 1 << H264MI_FMT_*) as the message lists them
+static int check_format(const char *what, int format, unsigned allowed, const char *names) {
+    if (format >= 0 && format < 32 && ((allowed >> format) & 1)) return H264MI_OK;
+    set_error("%s format %d: not %s", what, format, names);
+    return H264MI_EINVAL;
+}
+static int check_filter(int filter) {
+    if (filter == H264MI_SCALE_BILINEAR || filter == H264MI_SCALE_AREA) return H264MI_OK;
+    set_error("scale filter %d: not H264MI_SCALE_BILINEAR or H264MI_SCALE_AREA", filter);
+    return H264MI_EINVAL;
+}
+static int check_fit(int fit) {
+    if (fit == H264MI_FIT_STRETCH || fit == H264MI_FIT_LETTERBOX) return H264MI_OK;
+    set_error("fit %d: not H264MI_FIT_STRETCH or H264MI_FIT_LETTERBOX", fit);
+    return H264MI_EINVAL;
+}
+static int check_size(const char *what, int w, int h) {
+    if (w >= 1 && w <= H264MI_SCALE_MAX && h >= 1 && h <= H264MI_SCALE_MAX) return H264MI_OK;
+    set_error("%s size %d x %d: both must be 1 .. %d", what, w, h, H264MI_SCALE_MAX);
+    return H264MI_EINVAL;
+}
+// is csc legal at all (whatever the frames are, and if there are none)
+static int check_csc(int csc) {
+    int probe;
+    return h264mi_csc_resolve(csc, 1, 0, 16, 16, &probe);
+}
+// H264MI_SCALE_AREA from w x h to ow x oh (the `dst`): it only scales down, and the largest weighted sum and its rounding term must fit 32 bits.
+// src_fmt ...: how the message names the source, its size included
+__attribute__((format(printf, 6, 7))) static int check_area(int w, int h, int ow, int oh, const char *dst, const char *src_fmt, ...) {
+    const uint64_t px = static_cast<uint64_t>(w) * h;
+    const bool up = ow > w || oh > h;
+    if (!up && 255 * px + (px >> 1) < (static_cast<uint64_t>(1) << 32)) return H264MI_OK;
+    char src[160];
+    va_list ap;
+    va_start(ap, src_fmt);
+    vsnprintf(src, sizeof src, src_fmt, ap);
+    va_end(ap);
+    if (up) {
+        set_error("H264MI_SCALE_AREA only scales down: %s, the %s %d x %d", src, dst, ow, oh);
+        return H264MI_EINVAL;
+    }
+    set_error("H264MI_SCALE_AREA sums in 32 bits and needs 255 * w * h + ((w * h) >> 1) < 2^32: %s", src);
+    return H264MI_EUNSUPPORTED;
+}
+
+// the coefficient set and the chroma mode of a resolved csc (0: a format that converts nothing), as the descriptors carry them
+static void csc_fields(int res, uint32_t *cset, uint32_t *bilinear) {
+    *cset = res ? 2 * ((res & 15) - 1) + ((res & H264MI_CSC_FULL_RANGE) ? 1 : 0) : 0;
+    *bilinear = (res & H264MI_CSC_CHROMA_BILINEAR) ? 1 : 0;
+}
+
+// ---------------------------------------------------------------- tight I420 (K6)
+static int pack_frames(h264mi_decoder *d, const FrameList &frames, void *dst, size_t cap, size_t *bytes) {
+    GUARD(d);
+    std::vector<PackDesc> descs(frames.size());
+    size_t off = 0;
+    int hmax = 0;
+    for (size_t i = 0; i < frames.size(); i++) {
+        uint8_t *p;
+        const OutFrame *of;
+        int x0, y0, w, h;
+        TRY(frame_ptrs(d, frames[i].first, frames[i].second, &p, &of));
+        crop_rect(of, 1, &x0, &y0, &w, &h);
+        set_source(descs[i], p, of, x0, y0, w, h, off);
+        off += H264MI_I420_SIZE(w, h);
+        hmax = std::max(hmax, h);
+    }
+    if (bytes) *bytes = off;
+    if (off > cap) return H264MI_ECAPACITY;
+    if (frames.empty()) return H264MI_OK;
+    DescTables &t = d->tables[OUT_PACK];
+    const PackDesc *dev;
+    TRY(stage_descs(d, t, descs, &dev));
+    const int rows_per_block = 32;
+    hipLaunchKernelGGL(k_pack, dim3(static_cast<uint32_t>(frames.size()), (hmax + 2 * ((hmax + 1) / 2) + rows_per_block - 1) / rows_per_block), dim3(256), 0, d->stream, dev,
+                       static_cast<uint8_t *>(dst), rows_per_block);
+    return fence_launch(d, t);
+}
+
+extern "C" int32_t h264mi_frame_pack_device(h264mi_decoder *d, int32_t stream, int32_t frame, void *dst, size_t cap) {
+    if (!d || !dst) return H264MI_EINVAL;
+    return pack_frames(d, {{stream, frame}}, dst, cap, nullptr);
+}
+
+extern "C" int32_t h264mi_batch_pack_device(h264mi_decoder *d, int32_t stream, void *dst, size_t cap, size_t *bytes) {
+    if (!d || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    return pack_frames(d, batch_frames(d, stream), dst, cap, bytes);
+}
+
+// ---------------------------------------------------------------- output formats (K7): the rule of include/h264mi.h
+extern "C" int32_t h264mi_output_size(int32_t format, int32_t w, int32_t h, size_t *bytes) {
+    if (!bytes || w <= 0 || h <= 0) return H264MI_EINVAL;
+    switch (format) {
+    case H264MI_FMT_I420:
+    case H264MI_FMT_NV12: *bytes = H264MI_I420_SIZE(w, h); return H264MI_OK;
+    case H264MI_FMT_RGB24:
+    case H264MI_FMT_RGBP: *bytes = static_cast<size_t>(3) * w * h; return H264MI_OK;
+    }
+    set_error("unknown output format %d", format);
+    return H264MI_EINVAL;
+}
+
+extern "C" int32_t h264mi_csc_resolve(int32_t csc, int32_t matrix_coefficients, int32_t video_full_range, int32_t width, int32_t height, int32_t *resolved) {
+    if (!resolved) return H264MI_EINVAL;
+    int matrix = csc & 15;
+    if (csc < 0 || (csc & ~(15 | H264MI_CSC_FULL_RANGE | H264MI_CSC_CHROMA_BILINEAR)) || matrix > H264MI_CSC_BT709) {
+        set_error("csc %d: not a matrix (0 auto, 1 BT.601, 2 BT.709) with H264MI_CSC_FULL_RANGE / H264MI_CSC_CHROMA_BILINEAR", csc);
+        return H264MI_EINVAL;
+    }
+    int full = csc & H264MI_CSC_FULL_RANGE;
+    if (matrix == H264MI_CSC_AUTO) {
+        if (full) {
+            set_error("H264MI_CSC_FULL_RANGE needs an explicit matrix: with H264MI_CSC_AUTO the range comes from the stream");
+            return H264MI_EINVAL;
+        }
+        switch (matrix_coefficients) {
+        case 1: matrix = H264MI_CSC_BT709; break;
+        case 5:
+        case 6: matrix = H264MI_CSC_BT601; break;
+        case 2: matrix = (width >= 1280 || height > 576) ? H264MI_CSC_BT709 : H264MI_CSC_BT601; break;
+        default:
+            set_error("matrix_coefficients %d of the stream is not BT.601 / BT.709 (1, 2, 5, 6): pass an explicit matrix (H264MI_CSC_BT601 / H264MI_CSC_BT709)", matrix_coefficients);
+            return H264MI_EUNSUPPORTED;
+        }
+        full = video_full_range ? H264MI_CSC_FULL_RANGE : 0;
+    }
+    *resolved = matrix | full | (csc & H264MI_CSC_CHROMA_BILINEAR);
+    return H264MI_OK;
+}
+
+static int convert_frames(h264mi_decoder *d, const FrameList &frames, int format, int csc, void *dst, size_t cap, size_t *bytes) {
+    TRY(check_format("output", format, 1u << H264MI_FMT_NV12 | 1u << H264MI_FMT_RGB24 | 1u << H264MI_FMT_RGBP, "H264MI_FMT_NV12, _RGB24 or _RGBP"));
+    if (format == H264MI_FMT_NV12 && csc != 0) {
+        set_error("H264MI_FMT_NV12 converts nothing: csc must be 0, not %d", csc);
+        return H264MI_EINVAL;
+    }
+    TRY(check_csc(csc));
+    GUARD(d);
+    std::vector<ConvDesc> descs(frames.size());
+    size_t off = 0;
+    int hmax = 0;
+    for (size_t i = 0; i < frames.size(); i++) {
+        uint8_t *p;
+        const OutFrame *of;
+        int x0, y0, w, h, res = 0;
+        TRY(frame_ptrs(d, frames[i].first, frames[i].second, &p, &of));
+        crop_rect(of, 1, &x0, &y0, &w, &h);
+        if (format != H264MI_FMT_NV12) TRY(h264mi_csc_resolve(csc, of->matrix_coefficients, of->video_full_range, w, h, &res));
+        ConvDesc &cv = descs[i];
+        set_source(cv, p, of, x0, y0, w, h, off);
+        cv.format = format, cv.pad = 0;
+        csc_fields(res, &cv.cset, &cv.bilinear);
+        size_t sz = 0;
+        h264mi_output_size(format, w, h, &sz);
+        off += sz;
+        hmax = std::max(hmax, h);
+    }
+    if (bytes) *bytes = off;
+    if (off > cap) return H264MI_ECAPACITY;
+    if (frames.empty()) return H264MI_OK;
+    DescTables &t = d->tables[OUT_CONVERT];
+    const ConvDesc *dev;
+    TRY(stage_descs(d, t, descs, &dev));
+    const int pairs_per_block = 8; // 1080p: 8 x 120 items of 2 x 16 pixels for 256 threads, 68 blocks per frame
+    hipLaunchKernelGGL(k_convert, dim3(static_cast<uint32_t>(frames.size()), ((hmax + 1) / 2 + pairs_per_block - 1) / pairs_per_block), dim3(256), 0, d->stream, dev,
+                       static_cast<uint8_t *>(dst), pairs_per_block);
+    return fence_launch(d, t);
+}
+
+extern "C" int32_t h264mi_frame_convert_device(h264mi_decoder *d, int32_t stream, int32_t frame, int32_t format, int32_t csc, void *dst, size_t cap) {
+    if (!d || !dst) return H264MI_EINVAL;
+    return convert_frames(d, {{stream, frame}}, format, csc, dst, cap, nullptr);
+}
+
+extern "C" int32_t h264mi_batch_convert_device(h264mi_decoder *d, int32_t stream, int32_t format, int32_t csc, void *dst, size_t cap, size_t *bytes) {
+    if (!d || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    return convert_frames(d, batch_frames(d, stream), format, csc, dst, cap, bytes);
+}
+
+// ---------------------------------------------------------------- scaled output (K8): the rule of include/h264mi.h, "Scaled output"
+// bilinear: position of output index i on an axis of n_in samples scaled to n_out -- a in the high bits, f in bits 8 .. 15
+static inline void bilinear_axis(int n_in, int n_out, uint32_t *step, int32_t *half) {
+    *step = (static_cast<uint32_t>(n_in) << 16) / static_cast<uint32_t>(n_out); // n_in <= 16384: fits
+    *half = static_cast<int32_t>(*step >> 1) - 32768;
+}
+// the four axes of a frame of w x h scaled to ow x oh: luma x, luma y, chroma x, chroma y
+static void bilinear_axes(int w, int h, int ow, int oh, uint32_t step[4], int32_t half[4]) {
+    bilinear_axis(w, ow, &step[0], &half[0]);
+    bilinear_axis(h, oh, &step[1], &half[1]);
+    bilinear_axis((w + 1) / 2, (ow + 1) / 2, &step[2], &half[2]);
+    bilinear_axis((h + 1) / 2, (oh + 1) / 2, &step[3], &half[3]);
+}
+
+extern "C" int32_t h264mi_scale_taps(int32_t filter, int32_t n_in, int32_t n_out, int32_t i, int32_t *first, int32_t *count, int32_t *weights, int32_t cap) {
+    if (!first || !count || !weights || cap < 0) return H264MI_EINVAL;
+    TRY(check_filter(filter));
+    if (n_in < 1 || n_in > H264MI_SCALE_MAX || n_out < 1 || n_out > H264MI_SCALE_MAX || i < 0 || i >= n_out) {
+        set_error("scale taps: n_in %d, n_out %d must be 1 .. %d and 0 <= i (%d) < n_out", n_in, n_out, H264MI_SCALE_MAX, i);
+        return H264MI_EINVAL;
+    }
+    if (filter == H264MI_SCALE_BILINEAR) {
+        uint32_t step;
+        int32_t half;
+        bilinear_axis(n_in, n_out, &step, &half);
+        const int32_t P = std::min(std::max(static_cast<int32_t>(i * step) + half, 0), (n_in - 1) << 16);
+        *first = P >> 16, *count = 2;
+        if (cap < 2) return H264MI_ECAPACITY;
+        const int32_t f = (P >> 8) & 255;
+        weights[0] = 256 - f, weights[1] = f;
+        return H264MI_OK;
+    }
+    if (n_out > n_in) {
+        set_error("H264MI_SCALE_AREA only scales down: %d -> %d", n_in, n_out);
+        return H264MI_EINVAL;
+    }
+    const int32_t lo = i * n_in, hi = lo + n_in; // <= 2^28
+    const int32_t k0 = lo / n_out, k1 = (hi - 1) / n_out;
+    *first = k0, *count = k1 - k0 + 1;
+    if (cap < *count) return H264MI_ECAPACITY;
+    for (int32_t k = k0; k <= k1; k++) weights[k - k0] = std::min(hi, (k + 1) * n_out) - std::max(lo, k * n_out);
+    return H264MI_OK;
+}
+
+static int scale_frames(h264mi_decoder *d, const FrameList &frames, int format, int csc, int ow, int oh, int filter, void *dst, size_t cap, size_t *bytes) {
+    TRY(check_format("output", format, 1u << H264MI_FMT_I420 | 1u << H264MI_FMT_NV12 | 1u << H264MI_FMT_RGB24 | 1u << H264MI_FMT_RGBP, "H264MI_FMT_I420, _NV12, _RGB24 or _RGBP"));
+    const bool plain = format == H264MI_FMT_I420 || format == H264MI_FMT_NV12;
+    if (plain && csc != 0) {
+        set_error("H264MI_FMT_I420 and H264MI_FMT_NV12 convert nothing: csc must be 0, not %d", csc);
+        return H264MI_EINVAL;
+    }
+    TRY(check_filter(filter));
+    TRY(check_size("output", ow, oh));
+    TRY(check_csc(csc));
+    GUARD(d);
+    std::vector<ScaleDesc> descs(frames.size());
+    size_t one = 0, off = 0;
+    h264mi_output_size(format, ow, oh, &one);
+    for (size_t i = 0; i < frames.size(); i++) {
+        uint8_t *p;
+        const OutFrame *of;
+        int x0, y0, w, h, res = 0;
+        TRY(frame_ptrs(d, frames[i].first, frames[i].second, &p, &of));
+        crop_rect(of, 1, &x0, &y0, &w, &h);
+        if (filter == H264MI_SCALE_AREA) TRY(check_area(w, h, ow, oh, "output", "frame %d of stream %d is %d x %d", frames[i].second, frames[i].first, w, h));
+        // from the frame's SPS and its display (source) size, never from the output size
+        if (!plain) TRY(h264mi_csc_resolve(csc, of->matrix_coefficients, of->video_full_range, w, h, &res));
+        ScaleDesc &sc = descs[i];
+        set_source(sc, p, of, x0, y0, w, h, off);
+        sc.format = format, sc.filter = filter;
+        csc_fields(res, &sc.cset, &sc.bilinear);
+        bilinear_axes(w, h, ow, oh, sc.step, sc.half);
+        off += one;
+    }
+    if (bytes) *bytes = off;
+    if (off > cap) return H264MI_ECAPACITY;
+    if (frames.empty()) return H264MI_OK;
+    DescTables &t = d->tables[OUT_SCALE];
+    const ScaleDesc *dev;
+    TRY(stage_descs(d, t, descs, &dev));
+    // about 256 items of 2 x 16 output pixels per block: 640 wide: 6 row pairs x 40 groups; 224 wide: 18 x 14
+    const int ngroups = (ow + 15) / 16, npairs = (oh + 1) / 2;
+    const int pairs_per_block = std::max(1, std::min(256 / ngroups, npairs));
+    const dim3 grid(static_cast<uint32_t>(frames.size()), (npairs + pairs_per_block - 1) / pairs_per_block);
+    if (filter == H264MI_SCALE_AREA) hipLaunchKernelGGL(k_scale_area, grid, dim3(256), 0, d->stream, dev, static_cast<uint8_t *>(dst), ow, oh, pairs_per_block);
+    else hipLaunchKernelGGL(k_scale, grid, dim3(256), 0, d->stream, dev, static_cast<uint8_t *>(dst), ow, oh, pairs_per_block);
+    return fence_launch(d, t);
+}
+
+extern "C" int32_t h264mi_frame_scale_device(h264mi_decoder *d, int32_t stream, int32_t frame, int32_t format, int32_t csc, int32_t out_w, int32_t out_h, int32_t filter,
+                                             void *dst, size_t cap) {
+    if (!d || !dst) return H264MI_EINVAL;
+    return scale_frames(d, {{stream, frame}}, format, csc, out_w, out_h, filter, dst, cap, nullptr);
+}
+
+extern "C" int32_t h264mi_batch_scale_device(h264mi_decoder *d, int32_t stream, int32_t format, int32_t csc, int32_t out_w, int32_t out_h, int32_t filter, void *dst,
+                                             size_t cap, size_t *bytes) {
+    if (!d || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    return scale_frames(d, batch_frames(d, stream), format, csc, out_w, out_h, filter, dst, cap, bytes);
+}
+
+// ---------------------------------------------------------------- model input (K9): the rule of include/h264mi.h, "Model input"
+extern "C" int32_t h264mi_fit_rect(int32_t fit, int32_t w, int32_t h, int32_t out_w, int32_t out_h, int32_t *px, int32_t *py, int32_t *sw, int32_t *sh) {
+    if (!px || !py || !sw || !sh) return H264MI_EINVAL;
+    TRY(check_fit(fit));
+    if (w < 1 || w > H264MI_SCALE_MAX || h < 1 || h > H264MI_SCALE_MAX || out_w < 1 || out_w > H264MI_SCALE_MAX || out_h < 1 || out_h > H264MI_SCALE_MAX) {
+        set_error("fit rect: source %d x %d and canvas %d x %d must all be 1 .. %d", w, h, out_w, out_h, H264MI_SCALE_MAX);
+        return H264MI_EINVAL;
+    }
+    if (fit == H264MI_FIT_STRETCH) {
+        *px = 0, *py = 0, *sw = out_w, *sh = out_h;
+        return H264MI_OK;
+    }
+    if (w * out_h >= h * out_w) { // the width fills the canvas; products <= 2^28, the rounded quotient's numerator <= 2 * 2^28 + 2^14
+        *sw = out_w, *sh = std::min(std::max((2 * h * out_w + w) / (2 * w), 1), out_h);
+    } else {
+        *sh = out_h, *sw = std::min(std::max((2 * w * out_h + h) / (2 * h), 1), out_w);
+    }
+    *px = (out_w - *sw) >> 1, *py = (out_h - *sh) >> 1;
+    return H264MI_OK;
+}
+
+static inline int tensor_elem_size(int dtype) { return dtype == H264MI_DT_U8 ? 1 : dtype == H264MI_DT_F32 ? 4 : 2; }
+
+extern "C" int32_t h264mi_tensor_size(const h264mi_tensor_spec *spec, size_t *bytes) {
+    if (!spec || !bytes) return H264MI_EINVAL;
+    TRY(check_format("tensor", spec->format, 1u << H264MI_FMT_RGBP | 1u << H264MI_FMT_RGB24, "H264MI_FMT_RGBP or H264MI_FMT_RGB24"));
+    if (spec->dtype != H264MI_DT_U8 && spec->dtype != H264MI_DT_F16 && spec->dtype != H264MI_DT_BF16 && spec->dtype != H264MI_DT_F32) {
+        set_error("tensor dtype %d: not H264MI_DT_U8, _F16, _BF16 or _F32", spec->dtype);
+        return H264MI_EINVAL;
+    }
+    TRY(check_csc(spec->csc));
+    TRY(check_size("tensor", spec->out_w, spec->out_h));
+    TRY(check_filter(spec->filter));
+    TRY(check_fit(spec->fit));
+    if (spec->flags & ~H264MI_TENSOR_BGR) {
+        set_error("tensor flags 0x%x: only H264MI_TENSOR_BGR is defined", static_cast<unsigned>(spec->flags));
+        return H264MI_EINVAL;
+    }
+    for (int c = 0; c < 3; c++) {
+        if (!std::isfinite(spec->scale[c]) || !std::isfinite(spec->bias[c])) {
+            set_error("tensor scale[%d] = %g, bias[%d] = %g: both must be finite", c, static_cast<double>(spec->scale[c]), c, static_cast<double>(spec->bias[c]));
+            return H264MI_EINVAL;
+        }
+        if (spec->dtype == H264MI_DT_U8 && (spec->scale[c] != 1.0f || spec->bias[c] != 0.0f)) {
+            set_error("H264MI_DT_U8 maps nothing: scale[%d] must be 1 and bias[%d] 0, not %g and %g", c, c, static_cast<double>(spec->scale[c]), static_cast<double>(spec->bias[c]));
+            return H264MI_EINVAL;
+        }
+    }
+    *bytes = static_cast<size_t>(3) * spec->out_w * spec->out_h * tensor_elem_size(spec->dtype);
+    return H264MI_OK;
+}
+
+static int tensor_items(h264mi_decoder *d, const h264mi_tensor_spec *spec, const h264mi_tensor_item *items, size_t n, void *dst, size_t cap, size_t *bytes) {
+    size_t one = 0;
+    TRY(h264mi_tensor_size(spec, &one));
+    const int es = tensor_elem_size(spec->dtype), ow = spec->out_w, oh = spec->out_h;
+    if (reinterpret_cast<uintptr_t>(dst) % es) {
+        set_error("tensor destination %p: not aligned to the element size %d", dst, es);
+        return H264MI_EINVAL;
+    }
+    GUARD(d);
+    std::vector<TensorDesc> descs(n);
+    size_t off = 0;
+    for (size_t i = 0; i < n; i++) {
+        const h264mi_tensor_item &it = items[i];
+        uint8_t *p;
+        const OutFrame *of;
+        int x0, y0, w, h, res = 0;
+        const int r = frame_ptrs(d, it.stream, it.frame, &p, &of);
+        if (r != H264MI_OK) {
+            set_error("tensor item %zu: no frame %d of stream %d in the last executed batch", i, it.frame, it.stream);
+            return r;
+        }
+        crop_rect(of, 1, &x0, &y0, &w, &h);
+        int rx = it.x, ry = it.y, rw = it.w, rh = it.h;
+        if (rw == 0 && rh == 0) rw = w, rh = h; // the whole frame (legal from the origin (0, 0) only)
+        if (rx < 0 || ry < 0 || (rx & 1) || (ry & 1) || rw < 1 || rh < 1 || rx > w - rw || ry > h - rh) {
+            set_error("tensor item %zu: region (%d, %d, %d, %d) of frame %d of stream %d (%d x %d): the origin must be even and non-negative, the size at least 1 x 1, all of it inside the frame",
+                      i, it.x, it.y, it.w, it.h, it.frame, it.stream, w, h);
+            return H264MI_EINVAL;
+        }
+        int px, py, sw, sh;
+        TRY(h264mi_fit_rect(spec->fit, rw, rh, ow, oh, &px, &py, &sw, &sh));
+        if (spec->filter == H264MI_SCALE_AREA) TRY(check_area(rw, rh, sw, sh, "picture", "item %zu, region %d x %d of frame %d of stream %d", i, rw, rh, it.frame, it.stream));
+        // from the frame's SPS and its DISPLAY size, never from the region or the canvas
+        TRY(h264mi_csc_resolve(spec->csc, of->matrix_coefficients, of->video_full_range, w, h, &res));
+        TensorDesc &td = descs[i];
+        set_source(td, p, of, x0 + rx, y0 + ry, rw, rh, off); // rx, ry even: (x0 + rx) / 2 = x0 / 2 + rx / 2
+        td.sw = sw, td.sh = sh, td.px = px, td.py = py;
+        csc_fields(res, &td.cset, &td.bilinear);
+        bilinear_axes(rw, rh, sw, sh, td.step, td.half);
+        off += one;
+    }
+    if (bytes) *bytes = off;
+    if (off > cap) return H264MI_ECAPACITY;
+    if (n == 0) return H264MI_OK;
+    DescTables &t = d->tables[OUT_TENSOR];
+    const TensorDesc *dev;
+    TRY(stage_descs(d, t, descs, &dev));
+    TensorParams P;
+    const bool bgr = (spec->flags & H264MI_TENSOR_BGR) != 0;
+    P.ow = ow, P.oh = oh, P.dtype = spec->dtype, P.hwc = spec->format == H264MI_FMT_RGB24, P.bgr = bgr;
+    for (int p = 0; p < 3; p++) { // by channel position
+        const int c = bgr ? 2 - p : p;
+        P.pad[p] = spec->pad[c], P.scale[p] = spec->scale[c], P.bias[p] = spec->bias[c];
+    }
+    // about 256 thread items of 2 rows x 8 columns per block; a picture that does not start on a thread item's boundary needs one more group and row pair
+    const int ngroups = (ow + 7) / 8 + 1, npairs = (oh + 1) / 2 + 1;
+    P.pairs_per_block = std::max(1, std::min(256 / ngroups, npairs));
+    const dim3 grid(static_cast<uint32_t>(n), (npairs + P.pairs_per_block - 1) / P.pairs_per_block);
+    if (spec->filter == H264MI_SCALE_AREA) hipLaunchKernelGGL(k_tensor_area, grid, dim3(256), 0, d->stream, dev, static_cast<uint8_t *>(dst), P);
+    else hipLaunchKernelGGL(k_tensor, grid, dim3(256), 0, d->stream, dev, static_cast<uint8_t *>(dst), P);
+    return fence_launch(d, t);
+}
+
+extern "C" int32_t h264mi_items_tensor_device(h264mi_decoder *d, const h264mi_tensor_spec *spec, const h264mi_tensor_item *items, int32_t n, void *dst, size_t cap,
+                                              size_t *bytes) {
+    if (!d || !spec || !dst || n < 0 || (n > 0 && !items)) return H264MI_EINVAL;
+    return tensor_items(d, spec, items, static_cast<size_t>(n), dst, cap, bytes);
+}
+
+extern "C" int32_t h264mi_batch_tensor_device(h264mi_decoder *d, int32_t stream, const h264mi_tensor_spec *spec, void *dst, size_t cap, size_t *bytes) {
+    if (!d || !spec || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    std::vector<h264mi_tensor_item> items;
+    for (const std::pair<int, int> &f : batch_frames(d, stream)) items.push_back({f.first, f.second, 0, 0, 0, 0});
+    return tensor_items(d, spec, items.data(), items.size(), dst, cap, bytes);
+}

@@ -98,7 +98,7 @@ def test_coefficient_tables_are_the_roundings_of_kr_kb():
     want = [cscutil.coefficients(m, f) for m in (BT601, BT709) for f in (False, True)]
     assert want[0] == (9539, 13075, 3209, 6660, 16525)  # BT.601 limited: 1.1644, 1.5960, 0.3918, 0.8130, 2.0172 in 1/8192
     assert _table_rows(os.path.join(ROOT, "include", "h264mi.h"), "#define H264MI_CSC_COEFFS") == want
-    assert _table_rows(os.path.join(ROOT, "h264decode_amd", "csrc", "k_convert.hip"), "k_csc_coeffs[4][5]") == want
+    assert _table_rows(os.path.join(ROOT, "h264decode_amd", "csrc", "k_output_rule.h"), "k_csc_coeffs[4][5]") == want
 
 
 @pytest.mark.parametrize("matrix", [BT601, BT709])

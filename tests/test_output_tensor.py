@@ -498,6 +498,99 @@ def test_gpu_next_batch_waits_for_the_tensor_launch(cases, sg, H):
         dec.close()
 
 
+def _pending_hook(H):
+    pending = H.load_hooks().h264mi_internal_pack_pending
+    pending.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
+
+    def is_pending(dec):
+        v = ctypes.c_int32(-1)
+        assert pending(dec._h, ctypes.byref(v)) == 0
+        return v.value
+    return is_pending
+
+
+@pytest.mark.gpu
+def test_gpu_descriptor_tables_grow_and_alternate(sg, H):
+    """Three tensor_items calls with no synchronisation between them: 65 items (past the 64 descriptors a table starts with), 1 item (the other table
+    of the pair), 130 items (the first table again, grown a second time while the launch of the first call may still be running).  Every item of every
+    call is exact and nothing is written behind a buffer.  One 16x16 picture, regions of it on an 8x8 canvas, u8."""
+    import torch
+    kw, _ = toc.TABLE["16x16"]
+    raw, rec, _ = sg.encode(**dict(kw, frames=1, seed=3170))
+    size, csc = (8, 8), BT601 | BILIN
+    spec = _spec(H, size, "rgbp", U8, csc=csc)
+    one = 3 * 8 * 8
+    # unlike regions with even origins, all inside the frame
+    regions = []
+    for k in range(65 + 1 + 130):
+        x, y = 2 * (k % 8), 2 * ((k // 8) % 8)
+        regions.append((x, y, 1 + (5 * k) % (16 - x), 1 + (3 * k) % (16 - y)))
+    wants = {}
+    for r in set(regions):
+        wants[r] = tu.elements(tu.item(rec[0], 16, 16, r, size, S, BIL, csc, PAD), U8)
+    assert len(wants) > 100 and all(v.size == one for v in wants.values())
+    calls = [regions[:65], regions[65:66], regions[66:]]
+    dec = _decoder(H, 16, 16, 1)
+    try:
+        dec.decode([raw])
+        assert dec.frame_count(0) == 1
+        bufs = [torch.full((len(c) * one + 64,), 0xA5, dtype=torch.uint8, device="cuda") for c in calls]
+        for c, b in zip(calls, bufs):
+            assert dec.tensor_items(b.data_ptr(), len(c) * one, spec, [(0, 0) + r for r in c]) == len(c) * one
+        dec.sync()
+        for n, (c, b) in enumerate(zip(calls, bufs)):
+            got = b.cpu().numpy()
+            assert (got[len(c) * one:] == 0xA5).all(), ("call", n, "wrote behind its buffer")
+            for i, r in enumerate(c):
+                assert np.array_equal(got[i * one:(i + 1) * one], wants[r]), ("call", n, "item", i, r)
+    finally:
+        dec.close()
+
+
+@pytest.mark.gpu
+def test_gpu_the_four_output_kernels_on_one_batch(cases, H):
+    """pack_batch, convert_batch, scale_batch and tensor_batch of the same batch, one behind the other with no synchronisation, for three rounds (every
+    descriptor table of every family is used again): each call records its launch for the next pass to wait for, the next execute consumes it, all
+    twelve buffers are exact, and a call of any family that fails launches and records nothing."""
+    import torch
+    c = cases["aligned_origin"]
+    size, csc = (48, 32), BT601 | BILIN
+    spec = _spec(H, size, "rgbp", U8, csc=csc)
+    want = {"pack": np.concatenate(list(c.i420)),
+            "convert": cscutil.convert_all(c.i420, c.w, c.h, "rgbp", csc),
+            "scale": np.concatenate([scaleutil.scale_convert(f, c.w, c.h, size[0], size[1], BIL, "rgbp", csc) for f in c.i420]),
+            "tensor": np.concatenate([tu.elements(c.canvas(f, None, size, S, BIL, csc), U8) for f in range(3)])}
+    call = {"pack": lambda dec, p, cap: dec.pack_batch(p, cap),
+            "convert": lambda dec, p, cap: dec.convert_batch(p, cap, "rgbp", csc),
+            "scale": lambda dec, p, cap: dec.scale_batch(p, cap, "rgbp", size, csc, "bilinear"),
+            "tensor": lambda dec, p, cap: dec.tensor_batch(p, cap, spec)}
+    is_pending = _pending_hook(H)
+    dec = _decoder(H, c.info["coded_w"], c.info["coded_h"], c.pictures)
+    try:
+        bufs = [{k: torch.full((v.size + 64,), 0xA5, dtype=torch.uint8, device="cuda") for k, v in want.items()} for _ in range(3)]
+        for rnd in range(3):
+            dec.prepare([c.stream])
+            dec.execute()
+            assert is_pending(dec) == 0, "the execute consumes the event"
+            for k in want:
+                assert call[k](dec, bufs[rnd][k].data_ptr(), want[k].size) == want[k].size
+                assert is_pending(dec) == 1, (k, "the launch is recorded for the next pass to wait for")
+        dec.prepare([c.stream])
+        dec.execute()
+        assert is_pending(dec) == 0
+        for k in want:  # one byte of capacity: nothing is launched, nothing recorded
+            with pytest.raises(H.H264MIError) as e:
+                call[k](dec, bufs[0][k].data_ptr(), 1)
+            assert e.value.code == ECAPACITY and is_pending(dec) == 0, k
+        dec.sync()
+        for rnd in range(3):
+            for k, v in want.items():
+                got = bufs[rnd][k].cpu().numpy()
+                assert np.array_equal(got[:v.size], v) and (got[v.size:] == 0xA5).all(), (rnd, k, _first_diff(got[:v.size], v))
+    finally:
+        dec.close()
+
+
 @pytest.mark.gpu
 def test_gpu_frames_tensor_with_the_model_keywords(pair, H):
     import torch
