@@ -1,13 +1,15 @@
 /*
  * examples/h264mi_decode.c -- the C ABI from plain C: decode an Annex-B file to raw I420 on the GPU.
  *
- *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--conceal...] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH]
+ *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--conceal...] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge] [--field-rate]
  *
  * --nv12 / --rgb write NV12 / tight R, G, B bytes instead of I420: the frames are converted on the device (h264mi_batch_convert_device into a
  * device buffer, matrix and range from each frame's own SPS) and copied to the host from there.  --scale WxH writes every frame at W x H instead of
  * its display size (h264mi_batch_scale_device: bilinear, or the area filter with ":area"; I420 unless --nv12 / --rgb is given).  --tensor WxH writes
  * every frame as a model-input item instead (h264mi_batch_tensor_device): letterboxed into a W x H canvas on grey (114, 114, 114), float32 in three
- * planes R, G, B, each value v / 255 (scale 1 / 255, bias 0), bilinear, matrix and range from each frame's own SPS.  The HIP calls of these
+ * planes R, G, B, each value v / 255 (scale 1 / 255, bias 0), bilinear, matrix and range from each frame's own SPS.  --deinterlace MODE deinterlaces
+ * every frame on the device first (h264mi_batch_deinterlace: the first field's parity is kept) and writes the derived frames -- through whichever of
+ * the paths above is chosen -- instead of the woven ones; with --field-rate two per frame, the first field's then the second's.  The HIP calls of these
  * paths are the only HIP this file needs; they are declared below, so it still builds without the HIP headers.
  *
  * The file includes nothing but include/h264mi.h and the C library.
@@ -40,7 +42,22 @@ static int fail(const char *what, int code) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH]\n", argv[0]);
+        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge] [--field-rate]\n", argv[0]);
+        return 2;
+    }
+    int deint = -1, deint_rate = 1; /* --deinterlace MODE and --field-rate (the last arguments of all): derived frames instead of the woven ones */
+    if (argc > 3 && !strcmp(argv[argc - 1], "--field-rate")) deint_rate = 2, argc--;
+    if (argc > 4 && !strcmp(argv[argc - 2], "--deinterlace")) {
+        const char *m = argv[argc - 1];
+        deint = !strcmp(m, "field") ? H264MI_DEINT_FIELD : !strcmp(m, "blend") ? H264MI_DEINT_BLEND : !strcmp(m, "edge") ? H264MI_DEINT_EDGE : -1;
+        if (deint < 0) {
+            fprintf(stderr, "--deinterlace %s: expected field, blend or edge\n", m);
+            return 2;
+        }
+        argc -= 2;
+    }
+    if (deint < 0 && deint_rate == 2) {
+        fprintf(stderr, "--field-rate needs --deinterlace\n");
         return 2;
     }
     int scale_w = 0, scale_h = 0, scale_filter = H264MI_SCALE_BILINEAR; /* --scale WxH[:area] (the last two arguments): every frame at W x H */
@@ -190,20 +207,24 @@ int main(int argc, char **argv) {
                 const size_t l = b1 - b0;
                 h264mi_batch_info info;
                 if ((r = h264mi_decode_batch(dec, 1, &ptr, &l, &info)) != H264MI_OK) return fail("h264mi_decode_batch", r);
-                int32_t k = 0;
+                int32_t k = 0, src = 0; /* src: the stream the frames are taken from */
                 h264mi_stream_frame_count(dec, 0, &k);
+                if (deint >= 0) { /* one launch makes the derived frames of the batch: frames 0 .. k - 1 of the pseudo-stream */
+                    if ((r = h264mi_batch_deinterlace(dec, 0, deint, deint_rate, &k)) != H264MI_OK) return fail("h264mi_batch_deinterlace", r);
+                    src = H264MI_STREAM_DERIVED;
+                }
                 const size_t need = H264MI_I420_SIZE(info.coded_width, info.coded_height);
                 if (need > frame_cap) frame = (uint8_t *)realloc(frame, frame_cap = need);
                 if (tensor.out_w) { /* one launch makes the items of the batch; the size query as below */
                     size_t bytes = 0;
-                    r = h264mi_batch_tensor_device(dec, 0, &tensor, dev ? dev : (void *)frame, 0, &bytes);
+                    r = h264mi_batch_tensor_device(dec, src, &tensor, dev ? dev : (void *)frame, 0, &bytes);
                     if (r != H264MI_OK && r != H264MI_ECAPACITY) return fail("h264mi_batch_tensor_device", r);
                     if (bytes > dev_cap) {
                         if (dev) hipFree(dev);
                         if (hipMalloc(&dev, dev_cap = bytes) != 0) return fail("hipMalloc", H264MI_ENOMEM);
                     }
                     if (bytes > frame_cap) frame = (uint8_t *)realloc(frame, frame_cap = bytes);
-                    if (bytes && (r = h264mi_batch_tensor_device(dec, 0, &tensor, dev, dev_cap, &bytes)) != H264MI_OK) return fail("h264mi_batch_tensor_device", r);
+                    if (bytes && (r = h264mi_batch_tensor_device(dec, src, &tensor, dev, dev_cap, &bytes)) != H264MI_OK) return fail("h264mi_batch_tensor_device", r);
                     if ((r = h264mi_batch_sync(dec)) != H264MI_OK) return fail("h264mi_batch_sync", r);
                     if (bytes && hipMemcpy(frame, dev, bytes, 2 /* hipMemcpyDeviceToHost */) != 0) return fail("hipMemcpy", H264MI_EDEVICE);
                     fwrite(frame, 1, bytes, out);
@@ -213,8 +234,8 @@ int main(int argc, char **argv) {
                      * H264MI_OK for an empty batch) -- the destination is never touched, it only has to be non-NULL, so before the device buffer exists
                      * the host buffer's address stands in for it */
                     const char *what = scale_w ? "h264mi_batch_scale_device" : "h264mi_batch_convert_device";
-                    r = scale_w ? h264mi_batch_scale_device(dec, 0, format, H264MI_CSC_AUTO, scale_w, scale_h, scale_filter, dev ? dev : (void *)frame, 0, &bytes)
-                                : h264mi_batch_convert_device(dec, 0, format, H264MI_CSC_AUTO, dev ? dev : (void *)frame, 0, &bytes);
+                    r = scale_w ? h264mi_batch_scale_device(dec, src, format, H264MI_CSC_AUTO, scale_w, scale_h, scale_filter, dev ? dev : (void *)frame, 0, &bytes)
+                                : h264mi_batch_convert_device(dec, src, format, H264MI_CSC_AUTO, dev ? dev : (void *)frame, 0, &bytes);
                     if (r != H264MI_OK && r != H264MI_ECAPACITY) return fail(what, r);
                     if (bytes > dev_cap) {
                         if (dev) hipFree(dev);
@@ -222,8 +243,8 @@ int main(int argc, char **argv) {
                     }
                     if (bytes > frame_cap) frame = (uint8_t *)realloc(frame, frame_cap = bytes);
                     if (bytes) {
-                        r = scale_w ? h264mi_batch_scale_device(dec, 0, format, H264MI_CSC_AUTO, scale_w, scale_h, scale_filter, dev, dev_cap, &bytes)
-                                    : h264mi_batch_convert_device(dec, 0, format, H264MI_CSC_AUTO, dev, dev_cap, &bytes);
+                        r = scale_w ? h264mi_batch_scale_device(dec, src, format, H264MI_CSC_AUTO, scale_w, scale_h, scale_filter, dev, dev_cap, &bytes)
+                                    : h264mi_batch_convert_device(dec, src, format, H264MI_CSC_AUTO, dev, dev_cap, &bytes);
                         if (r != H264MI_OK) return fail(what, r);
                     }
                     if ((r = h264mi_batch_sync(dec)) != H264MI_OK) return fail("h264mi_batch_sync", r); /* the launch is asynchronous on the decoder's stream */
@@ -231,7 +252,7 @@ int main(int argc, char **argv) {
                     fwrite(frame, 1, bytes, out);
                 } else
                     for (int fidx = 0; fidx < k; fidx++) {
-                        if ((r = h264mi_frame_read(dec, 0, fidx, 1, frame, frame_cap)) != H264MI_OK) return fail("h264mi_frame_read", r);
+                        if ((r = h264mi_frame_read(dec, src, fidx, 1, frame, frame_cap)) != H264MI_OK) return fail("h264mi_frame_read", r);
                         fwrite(frame, 1, fsz, out);
                     }
                 total += k;

@@ -10,7 +10,8 @@ from .h264 import (  # noqa: F401
     CONCEAL_SLICES, CONCEAL_PICTURES, CONCEAL_FIELDS, CONCEAL_IDR, CONCEAL_LONE_FIELDS, CONCEAL_MAX_GAP,
     FMT_I420, FMT_NV12, FMT_RGB24, FMT_RGBP, CSC_AUTO, CSC_BT601, CSC_BT709, CSC_FULL_RANGE, CSC_CHROMA_BILINEAR,
     SCALE_BILINEAR, SCALE_AREA, scale_taps,
-    DT_U8, DT_F16, DT_BF16, DT_F32, FIT_STRETCH, FIT_LETTERBOX, TENSOR_BGR, fit_rect, tensor_spec)
+    DT_U8, DT_F16, DT_BF16, DT_F32, FIT_STRETCH, FIT_LETTERBOX, TENSOR_BGR, fit_rect, tensor_spec,
+    DEINT_FIELD, DEINT_BLEND, DEINT_EDGE, DEINT_PARITY_FIRST, STREAM_DERIVED, deint_rows)
 from .mbtype import (  # noqa: F401
     MB_TYPE_INFERRED, ISliceMbType, SISliceMbType, PSliceMbType, BSliceMbType, MbTypeName, MbPartPredMode, NumMbPart, PicWidthInMbs,
     PicHeightInMapUnits, PicSizeInMapUnits, FrameHeightInMbs, PicHeightInMbs, PicSizeInMbs, SubWidthC, SubHeightC, MbWidthC, MbHeightC,

@@ -49,6 +49,7 @@ _S = _parse_structs()
 Nal, Sps, Pps, SliceHdr, Config, BatchInfo, FrameInfo = (_S["h264mi_nal"], _S["h264mi_sps"], _S["h264mi_pps"], _S["h264mi_slice_header"],
                                                          _S["h264mi_config"], _S["h264mi_batch_info"], _S["h264mi_frame_info"])
 TensorSpec, TensorItem = _S["h264mi_tensor_spec"], _S["h264mi_tensor_item"]
+FieldInfo, DeintItem = _S["h264mi_field_info"], _S["h264mi_deint_item"]
 
 
 def build(force=False):
@@ -129,6 +130,10 @@ def load():
         "h264mi_tensor_size": [P(TensorSpec), P(SZ)],
         "h264mi_items_tensor_device": [vp, P(TensorSpec), P(TensorItem), I32, vp, SZ, P(SZ)],
         "h264mi_batch_tensor_device": [vp, I32, P(TensorSpec), vp, SZ, P(SZ)],
+        "h264mi_deint_rows": [I32, I32, I32, I32, P(I32), P(I32), P(I32)],
+        "h264mi_frame_fields": [vp, I32, I32, P(FieldInfo)],
+        "h264mi_items_deinterlace": [vp, I32, P(DeintItem), I32, P(I32)],
+        "h264mi_batch_deinterlace": [vp, I32, I32, I32, P(I32)],
         "h264mi_frame_read_mbrecs": [vp, I32, I32, vp, SZ],
         "h264mi_frame_read_mbmv1": [vp, I32, I32, vp, SZ],
         "h264mi_decoder_set_profiling": [vp, I32],
@@ -171,4 +176,5 @@ EXPORTS = ["h264mi_annexb_scan", "h264mi_nal_parse", "h264mi_sps_parse", "h264mi
            "h264mi_frame_concealed", "h264mi_decoder_concealed", "h264mi_decoder_concealed_pictures", "h264mi_decoder_concealed_fields",
            "h264mi_output_size", "h264mi_csc_resolve", "h264mi_frame_colour", "h264mi_frame_convert_device", "h264mi_batch_convert_device",
            "h264mi_scale_taps", "h264mi_frame_scale_device", "h264mi_batch_scale_device",
-           "h264mi_fit_rect", "h264mi_tensor_size", "h264mi_items_tensor_device", "h264mi_batch_tensor_device"]
+           "h264mi_fit_rect", "h264mi_tensor_size", "h264mi_items_tensor_device", "h264mi_batch_tensor_device",
+           "h264mi_deint_rows", "h264mi_frame_fields", "h264mi_items_deinterlace", "h264mi_batch_deinterlace"]

@@ -257,6 +257,7 @@ static void free_all(h264mi_decoder *d) {
             if (t.d[i]) hipFree(t.d[i]);
             if (t.ev[i]) hipEventDestroy(t.ev[i]);
         }
+    if (d->d_derived) hipFree(d->d_derived);
     if (d->d_frames) hipFree(d->d_frames);
     if (d->d_tables) hipFree(d->d_tables);
     if (d->h_tables) hipHostFree(d->h_tables);
@@ -520,6 +521,7 @@ static void reset_stream(StreamState &s, bool keep_parameter_sets) {
 extern "C" int32_t h264mi_decoder_reset(h264mi_decoder *d) {
     if (!d) return H264MI_EINVAL;
     for (auto &s : d->st) reset_stream(s, true);
+    d->derived.clear();
     for (Stage &g : d->stage) {
         g.prepared = false;
         for (auto &o : g.out) o.clear();
@@ -529,6 +531,7 @@ extern "C" int32_t h264mi_decoder_reset(h264mi_decoder *d) {
 extern "C" int32_t h264mi_stream_reset(h264mi_decoder *d, int32_t stream) {
     if (!d || stream < 0 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
     reset_stream(d->st[stream], false);
+    d->derived.clear(); // (all of them: a derived frame does not outlive the batch it was made from)
     for (Stage &g : d->stage) g.out[stream].clear();
     return H264MI_OK;
 }
@@ -570,7 +573,7 @@ extern "C" int32_t h264mi_decoder_concealed_fields(h264mi_decoder *d, int64_t *f
     return H264MI_OK;
 }
 extern "C" int32_t h264mi_frame_concealed(h264mi_decoder *d, int32_t stream, int32_t frame, int32_t *n_macroblocks) {
-    if (!d || !n_macroblocks || stream < 0 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    if (!d || !n_macroblocks || stream < 0 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL; // (H264MI_STREAM_DERIVED too)
     const Stage &g = d->stage[d->exec];
     if (frame < 0 || frame >= static_cast<int>(g.out[stream].size())) return H264MI_EINVAL;
     int32_t n = 0;
@@ -608,12 +611,19 @@ static void finish_picture(h264mi_decoder *d, int si) {
     if (dpb.cur_field) {
         // a field: the frame goes out when its second field is complete -- or, if that never comes, when the next picture starts (flush_pending_field)
         if (dpb.pend_slot < 0) {
-            s.pend_out.poc = dpb.slots[dpb.cur_slot].poc;
+            const Slot &f = dpb.slots[dpb.cur_slot];
+            s.pend_out.poc = f.poc;
+            s.pend_out.top_foc = f.fpoc[0], s.pend_out.bottom_foc = f.fpoc[1];
+            // (pic_order_cnt_type 2 gives both fields of a reference frame one count, and output order is decoding order, 8.2.1.3: this picture is the second field)
+            s.pend_out.first_parity = f.fpoc[0] != f.fpoc[1] ? f.fpoc[1] < f.fpoc[0] : 2 - dpb.cur_field;
             if (dpb.cur_second) s.pend_out.pic2 = s.cur_pic;
             g.out[si].push_back(s.pend_out);
         }
-    } else if (!g.out[si].empty())
-        g.out[si].back().poc = dpb.slots[dpb.cur_slot].poc; // operation 5 rewrites it
+    } else if (!g.out[si].empty()) {
+        OutFrame &o = g.out[si].back();
+        const Slot &f = dpb.slots[dpb.cur_slot];
+        o.poc = f.poc, o.top_foc = f.fpoc[0], o.bottom_foc = f.fpoc[1]; // operation 5 rewrites them (first_parity is from before: start_picture)
+    }
     // Every macroblock of the picture belongs to exactly one slice wavefront (SliceDesc::fill_from / end_mb): order the
     // slices by first_mb (arbitrary slice order is legal in Baseline); a slice's range ends where the next one starts.
     std::vector<uint32_t> idx(pd.n_slices);
@@ -725,6 +735,8 @@ static int flush_pending_field(h264mi_decoder *d, int si, const h264mi_sps *nsps
     const Slot &f = s.dpb.slots[s.dpb.pend_slot];
     OutFrame o = s.pend_out;
     o.poc = f.poc;
+    o.first_parity = f.fields == 1 ? 0 : 1; // the field there is; the missing one is reported with the same count
+    o.top_foc = o.bottom_foc = f.fpoc[o.first_parity];
     g.out[si].push_back(o);
     g.grey.push_back({static_cast<uint32_t>(si), static_cast<uint32_t>(s.dpb.pend_slot), f.fields == 1 ? 1u : 0u, static_cast<uint32_t>(o.wmb * 16), static_cast<uint32_t>(o.hmb * 16)});
     s.dpb.pend_slot = -1;
@@ -969,6 +981,8 @@ static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const
         if (sh.nal_ref_idc && sh.adaptive_ref_pic_marking_mode_flag)
             for (int k = 0; k < sh.n_memory_management_control_operations; k++)
                 if (sh.memory_management_control_operation[k] == 5) of.new_sequence = 1;
+        // (a frame picture: both counts are known now; a frame of two fields gets them when it goes out: finish_picture / flush_pending_field)
+        of.field_coded = sh.field_pic != 0, of.top_foc = sl.fpoc[0], of.bottom_foc = sl.fpoc[1], of.first_parity = !sh.field_pic && sl.fpoc[1] < sl.fpoc[0];
         if (sps.vui_parameters_present && sps.video_signal_type_present) {
             of.video_full_range = sps.video_full_range;
             if (sps.color_description_present) of.matrix_coefficients = sps.matrix_coefficients;
@@ -1689,6 +1703,7 @@ extern "C" int32_t h264mi_batch_execute(h264mi_decoder *d) {
         return H264MI_EINVAL;
     }
     d->exec = d->prep; // sync and the frame accessors refer to this batch from now on
+    d->derived.clear(); // derived frames are functions of the frames this pass rewrites
     d->stage[d->exec].retried = false;
     return execute_stage(d, d->exec, false);
 }
@@ -1985,12 +2000,22 @@ extern "C" int32_t h264mi_last_launch_times(h264mi_decoder *d, int32_t kernel, f
 }
 
 extern "C" int32_t h264mi_stream_frame_count(h264mi_decoder *d, int32_t stream, int32_t *n) {
+    if (d && n && stream == H264MI_STREAM_DERIVED) {
+        *n = static_cast<int32_t>(d->derived.size());
+        return H264MI_OK;
+    }
     if (!d || !n || stream < 0 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
     *n = static_cast<int32_t>(d->stage[d->exec].out[stream].size());
     return H264MI_OK;
 }
 
 int frame_ptrs(h264mi_decoder *d, int stream, int frame, uint8_t **y, const OutFrame **of) {
+    if (d && stream == H264MI_STREAM_DERIVED) {
+        if (frame < 0 || frame >= static_cast<int>(d->derived.size())) return H264MI_EINVAL;
+        *of = &d->derived[frame].of;
+        *y = d->d_derived + d->derived[frame].off;
+        return H264MI_OK;
+    }
     if (!d || stream < 0 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
     const std::vector<OutFrame> &out = d->stage[d->exec].out[stream];
     if (frame < 0 || frame >= static_cast<int>(out.size())) return H264MI_EINVAL;
@@ -2001,6 +2026,7 @@ int frame_ptrs(h264mi_decoder *d, int stream, int frame, uint8_t **y, const OutF
 
 extern "C" int32_t h264mi_frame_device_planes(h264mi_decoder *d, int32_t stream, int32_t frame, void **y, void **cb, void **cr, int32_t *pitch_y, int32_t *pitch_c,
                                               int32_t *cw, int32_t *ch) {
+    if (stream == H264MI_STREAM_DERIVED) return H264MI_EINVAL; // a derived frame is reached through the output calls only
     uint8_t *p;
     const OutFrame *of;
     int r = frame_ptrs(d, stream, frame, &p, &of);
@@ -2050,7 +2076,7 @@ extern "C" int32_t h264mi_frame_read(h264mi_decoder *d, int32_t stream, int32_t 
     int x0, y0, w, h;
     int r = frame_ptrs(d, stream, frame, &p, &of);
     if (r != H264MI_OK) return r;
-    if (!dst) return H264MI_EINVAL;
+    if (!dst || (stream == H264MI_STREAM_DERIVED && !crop)) return H264MI_EINVAL; // (only the display rectangle of a derived frame is written)
     GUARD(d);
     const int W = of->wmb * 16, H = of->hmb * 16;
     crop_rect(of, crop, &x0, &y0, &w, &h);
@@ -2073,6 +2099,16 @@ extern "C" int32_t h264mi_frame_colour(h264mi_decoder *d, int32_t stream, int32_
     if (r != H264MI_OK) return r;
     if (matrix_coefficients) *matrix_coefficients = of->matrix_coefficients;
     if (video_full_range) *video_full_range = of->video_full_range;
+    return H264MI_OK;
+}
+
+extern "C" int32_t h264mi_frame_fields(h264mi_decoder *d, int32_t stream, int32_t frame, h264mi_field_info *out) {
+    uint8_t *p;
+    const OutFrame *of;
+    int r = frame_ptrs(d, stream, frame, &p, &of);
+    if (r != H264MI_OK) return r;
+    if (!out) return H264MI_EINVAL;
+    out->field_coded = of->field_coded, out->top_field_order_cnt = of->top_foc, out->bottom_field_order_cnt = of->bottom_foc, out->first_parity = of->first_parity;
     return H264MI_OK;
 }
 

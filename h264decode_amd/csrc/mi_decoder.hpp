@@ -32,6 +32,9 @@ struct OutFrame { // a decoded picture of the current batch, with the geometry i
     int new_sequence; // IDR picture or memory_management_control_operation 5: picture order counts start over
     int pic2 = -1;    // a frame coded as two field pictures: `pic` / `pic2` are the first / second field's PicDesc (-1: decoded by an earlier batch, or never)
     int matrix_coefficients = 2, video_full_range = 0; // of the picture's own SPS (E.2.1: "unspecified" / 0 where it does not carry them): h264mi_frame_colour
+    // h264mi_frame_fields: coded as two field pictures (one of them may be missing or concealed); TopFieldOrderCnt / BottomFieldOrderCnt (8.2.1, after a
+    // possible operation 5; a missing field's is the other one's); which parity comes first (taken before operation 5 rewrites the counts)
+    int field_coded = 0, top_foc = 0, bottom_foc = 0, first_parity = 0;
 };
 struct StreamState {
     h264mi_sps sps[32];
@@ -123,7 +126,14 @@ struct DescTables {
     hipEvent_t ev[2] = {nullptr, nullptr};
     int slot = 0;
 };
-enum { OUT_PACK, OUT_CONVERT, OUT_SCALE, OUT_TENSOR, OUT_FAMILIES }; // K6, K7, K8, K9
+enum { OUT_PACK, OUT_CONVERT, OUT_SCALE, OUT_TENSOR, OUT_DEINT, OUT_FAMILIES }; // K6, K7, K8, K9, K10
+
+// A derived (deinterlaced) frame: frame k of the pseudo-stream H264MI_STREAM_DERIVED.  `of`: its source's OutFrame (what the accessors report); off: its
+// slot in the arena, in the layout of a frame slot of the source's coded size
+struct DerivedFrame {
+    OutFrame of;
+    size_t off;
+};
 
 struct h264mi_decoder {
     h264mi_config cfg;
@@ -192,8 +202,13 @@ struct h264mi_decoder {
     uint32_t *d_xctl = nullptr, *h_xstatus = nullptr; // [0] K5 tickets, [32] K3 tickets, [64] give-up code (128-byte lines of their own)
     uint32_t x_epoch = 0, x_tk5 = 0, x_tk3 = 0;
     int x_max_wgs = 256, x_cap = 512, x_cap3 = 512; // workgroups per launch: default; capacity of the K5 ring; of the K3 flag array
-    DescTables tables[OUT_FAMILIES]; // of K6 .. K9, a set each: a convert call does not wait for a pack call's table
-    hipEvent_t last_pack = nullptr; // the most recent output launch (K6 .. K9): the reconstruction of a later pass may rewrite the frames it reads
+    DescTables tables[OUT_FAMILIES]; // of K6 .. K10, a set each: a convert call does not wait for a pack call's table
+    hipEvent_t last_pack = nullptr; // the most recent output launch (K6 .. K10): the reconstruction of a later pass may rewrite the frames it reads
+    // K10: the derived frames of the last h264mi_items_deinterlace / h264mi_batch_deinterlace call (emptied by execute and the resets) and their arena,
+    // which grows to the largest call and is kept
+    std::vector<DerivedFrame> derived;
+    uint8_t *d_derived = nullptr;
+    size_t derived_cap = 0;
     std::vector<float> launch_ms[4]; // duration of every launch of the last profiled pass, per kernel
 };
 
@@ -218,7 +233,8 @@ struct DeviceGuard {
         return H264MI_EDEVICE;                                          \
     }
 
-// frame `frame` of stream `stream` of the last executed batch: its Y plane in the frame pool and its geometry (mi_api.cpp)
+// frame `frame` of stream `stream` of the last executed batch: its Y plane in the frame pool and its geometry (mi_api.cpp); of the pseudo-stream
+// H264MI_STREAM_DERIVED: derived frame `frame`, its Y plane in the arena and its SOURCE's geometry
 int frame_ptrs(h264mi_decoder *d, int stream, int frame, uint8_t **y, const OutFrame **of);
 // the picture's own geometry (a new SPS may have activated later in the same batch): the coded frame, or its display rectangle (mi_output.cpp)
 void crop_rect(const OutFrame *of, int crop, int *x0, int *y0, int *w, int *h);

@@ -190,6 +190,17 @@ typedef struct { // uniform per launch; scale, bias and pad by channel POSITION 
 } TensorParams;
 extern "C" __global__ void k_tensor(const TensorDesc *descs, uint8_t *dst, TensorParams P);      // H264MI_SCALE_BILINEAR
 extern "C" __global__ void k_tensor_area(const TensorDesc *descs, uint8_t *dst, TensorParams P); // H264MI_SCALE_AREA
+// K10 (k_deint.hip): a list of (frame, mode, parity) items -> deinterlaced frames, by the rule of include/h264mi.h ("Deinterlaced output"), each into a
+// frame slot of its source's coded size (the same layout: K6 .. K9 read it like a frame of the pool); only the display rectangle is written.
+// grid = (items, ceil((ceil(h_max / 2) + ceil(ceil(h_max / 2) / 2)) / pairs_per_block)), block = 256; a thread owns two rows x 16 columns of one plane
+typedef struct {
+    uint64_t src;     // as PackDesc
+    uint64_t dst_off; // byte offset of the derived frame's slot in the arena
+    uint32_t W, H, x0, y0, w, h;
+    uint32_t mode;   // H264MI_DEINT_FIELD / _BLEND / _EDGE
+    uint32_t parity; // 0 / 1, resolved
+} DeintDesc;
+extern "C" __global__ void k_deint(const DeintDesc *descs, uint8_t *dst, int pairs_per_block);
 
 #ifndef MI_INTRA_WAVES
 #define MI_INTRA_WAVES 16 /* 1024 threads, 128 VGPRs per wavefront: the kernels need 120 once nothing lane-dependent is hoisted out of the macroblock loop */

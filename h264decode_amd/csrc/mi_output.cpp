@@ -1,7 +1,8 @@
 // h264decode_amd/csrc/mi_output.cpp -- the output stage of libh264mi.so: what leaves the frame pool on the device.  K6 (k_pack: tight I420), K7
-// (k_convert: NV12 / RGB), K8 (k_scale: resized) and K9 (k_tensor: model input) over a list of frames of the last executed batch, and the
-// device-free rule functions of include/h264mi.h that say what those kernels compute (h264mi_output_size, _csc_resolve, _scale_taps, _fit_rect,
-// _tensor_size).  The four kernel families share ONE launch discipline (stage_descs / fence_launch below); each has descriptor tables of its own.
+// (k_convert: NV12 / RGB), K8 (k_scale: resized) and K9 (k_tensor: model input) over a list of frames of the last executed batch, K10 (k_deint:
+// deinterlaced frames, which K6 .. K9 read like frames of the batch), and the device-free rule functions of include/h264mi.h that say what those
+// kernels compute (h264mi_output_size, _csc_resolve, _scale_taps, _fit_rect, _tensor_size, _deint_rows).  The five kernel families share ONE launch
+// discipline (stage_descs / fence_launch below); each has descriptor tables of its own.
 // (the reference has no output process: h264/server.go:113-166 stops at the parsed slice)
 #include <algorithm>
 #include <cmath>
@@ -16,19 +17,28 @@ void crop_rect(const OutFrame *of, int crop, int *x0, int *y0, int *w, int *h) {
     if (crop) *x0 = of->crop_x, *y0 = of->crop_y, *w = of->width, *h = of->height;
 }
 
-// ---------------------------------------------------------------- the launch discipline of K6 .. K9
+// ---------------------------------------------------------------- the launch discipline of K6 .. K10
 // Every call checks, resolves and sizes all of its frames first: a call that fails launches nothing and waits for nothing.  Then the descriptors go
 // through the family's next table (stage_descs), one launch on the decoder's stream takes them all, and the launch is fenced (fence_launch).
 typedef std::vector<std::pair<int, int>> FrameList; // (stream, frame)
 
-// every frame of `stream`, or of all streams (-1), of the last executed batch
+// every frame of `stream`, or of all streams (-1), of the last executed batch; of H264MI_STREAM_DERIVED: every derived frame
 static FrameList batch_frames(const h264mi_decoder *d, int stream) {
     FrameList frames;
+    if (stream == H264MI_STREAM_DERIVED) {
+        for (int f = 0; f < static_cast<int>(d->derived.size()); f++) frames.push_back({stream, f});
+        return frames;
+    }
     const Stage &g = d->stage[d->exec];
     for (int si = 0; si < static_cast<int>(g.out.size()); si++)
         if (stream < 0 || stream == si)
             for (int f = 0; f < static_cast<int>(g.out[si].size()); f++) frames.push_back({si, f});
     return frames;
+}
+
+// `stream` of a batch call: -1, a stream of the decoder, or the pseudo-stream of the derived frames
+static bool batch_stream_ok(const h264mi_decoder *d, int stream) {
+    return stream == H264MI_STREAM_DERIVED || (stream >= -1 && stream < static_cast<int>(d->st.size()));
 }
 
 // what every descriptor begins with: the frame's planes and coded size, the rectangle read, the place in the destination
@@ -158,7 +168,7 @@ extern "C" int32_t h264mi_frame_pack_device(h264mi_decoder *d, int32_t stream, i
 }
 
 extern "C" int32_t h264mi_batch_pack_device(h264mi_decoder *d, int32_t stream, void *dst, size_t cap, size_t *bytes) {
-    if (!d || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    if (!d || !dst || !batch_stream_ok(d, stream)) return H264MI_EINVAL;
     return pack_frames(d, batch_frames(d, stream), dst, cap, bytes);
 }
 
@@ -248,7 +258,7 @@ extern "C" int32_t h264mi_frame_convert_device(h264mi_decoder *d, int32_t stream
 }
 
 extern "C" int32_t h264mi_batch_convert_device(h264mi_decoder *d, int32_t stream, int32_t format, int32_t csc, void *dst, size_t cap, size_t *bytes) {
-    if (!d || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    if (!d || !dst || !batch_stream_ok(d, stream)) return H264MI_EINVAL;
     return convert_frames(d, batch_frames(d, stream), format, csc, dst, cap, bytes);
 }
 
@@ -349,7 +359,7 @@ extern "C" int32_t h264mi_frame_scale_device(h264mi_decoder *d, int32_t stream, 
 
 extern "C" int32_t h264mi_batch_scale_device(h264mi_decoder *d, int32_t stream, int32_t format, int32_t csc, int32_t out_w, int32_t out_h, int32_t filter, void *dst,
                                              size_t cap, size_t *bytes) {
-    if (!d || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    if (!d || !dst || !batch_stream_ok(d, stream)) return H264MI_EINVAL;
     return scale_frames(d, batch_frames(d, stream), format, csc, out_w, out_h, filter, dst, cap, bytes);
 }
 
@@ -475,8 +485,134 @@ extern "C" int32_t h264mi_items_tensor_device(h264mi_decoder *d, const h264mi_te
 }
 
 extern "C" int32_t h264mi_batch_tensor_device(h264mi_decoder *d, int32_t stream, const h264mi_tensor_spec *spec, void *dst, size_t cap, size_t *bytes) {
-    if (!d || !spec || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    if (!d || !spec || !dst || !batch_stream_ok(d, stream)) return H264MI_EINVAL;
     std::vector<h264mi_tensor_item> items;
     for (const std::pair<int, int> &f : batch_frames(d, stream)) items.push_back({f.first, f.second, 0, 0, 0, 0});
     return tensor_items(d, spec, items.data(), items.size(), dst, cap, bytes);
+}
+
+// ---------------------------------------------------------------- deinterlaced output (K10): the rule of include/h264mi.h, "Deinterlaced output"
+static int check_deint(int mode, int parity) {
+    if (mode != H264MI_DEINT_FIELD && mode != H264MI_DEINT_BLEND && mode != H264MI_DEINT_EDGE) {
+        set_error("deinterlace mode %d: not H264MI_DEINT_FIELD, _BLEND or _EDGE", mode);
+        return H264MI_EINVAL;
+    }
+    if ((parity != 0 && parity != 1) || (mode == H264MI_DEINT_BLEND && parity != 0)) {
+        set_error("deinterlace parity %d: not 0 or 1%s", parity, mode == H264MI_DEINT_BLEND ? " (H264MI_DEINT_BLEND ignores it: it must be 0)" : "");
+        return H264MI_EINVAL;
+    }
+    return H264MI_OK;
+}
+
+extern "C" int32_t h264mi_deint_rows(int32_t mode, int32_t parity, int32_t n_rows, int32_t y, int32_t *kept, int32_t *up, int32_t *dn) {
+    if (!kept || !up || !dn) return H264MI_EINVAL;
+    TRY(check_deint(mode, parity));
+    if (n_rows < 1 || n_rows > H264MI_SCALE_MAX || y < 0 || y >= n_rows) {
+        set_error("deinterlace rows: n_rows %d must be 1 .. %d and 0 <= y (%d) < n_rows", n_rows, H264MI_SCALE_MAX, y);
+        return H264MI_EINVAL;
+    }
+    if (mode == H264MI_DEINT_BLEND) {
+        *kept = 0, *up = std::max(y - 1, 0), *dn = std::min(y + 1, n_rows - 1);
+        return H264MI_OK;
+    }
+    int u = y - 1, v = y + 1;
+    if (u < 0) u = v;
+    if (v >= n_rows) v = u;
+    if ((y & 1) == parity || u < 0 || u >= n_rows) { // kept, or neither neighbour exists (one row, parity 1)
+        *kept = 1, *up = *dn = y;
+        return H264MI_OK;
+    }
+    *kept = 0, *up = u, *dn = v;
+    return H264MI_OK;
+}
+
+// room for `bytes` of derived frames: the arena grows to the largest call and is kept.  On failure the arena, and so the previous list, is as it was
+static int reserve_derived(h264mi_decoder *d, size_t bytes) {
+    if (bytes <= d->derived_cap) return H264MI_OK;
+    uint8_t *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("deinterlace: no device memory for %zu bytes of derived frames", bytes);
+        return H264MI_ENOMEM;
+    }
+    // only display rectangles are ever written: the rest of a slot stays zero.  The old arena goes once nothing on the stream reads it any more
+    if (hipMemsetAsync(p, 0, bytes, d->stream) != hipSuccess || hipStreamSynchronize(d->stream) != hipSuccess) {
+        hipFree(p);
+        set_error("deinterlace: clearing the arena of derived frames failed");
+        return H264MI_EDEVICE;
+    }
+    if (d->d_derived) hipFree(d->d_derived);
+    d->dev_bytes += bytes - d->derived_cap;
+    d->d_derived = p, d->derived_cap = bytes;
+    d->derived.clear(); // (the caller replaces the list; it never outlives its arena)
+    return H264MI_OK;
+}
+
+static int deint_items(h264mi_decoder *d, int mode, const h264mi_deint_item *items, size_t n, int32_t *n_derived) {
+    TRY(check_deint(mode, 0));
+    GUARD(d);
+    std::vector<DeintDesc> descs(n);
+    std::vector<DerivedFrame> next(n);
+    size_t off = 0;
+    int hmax = 0;
+    for (size_t i = 0; i < n; i++) {
+        const h264mi_deint_item &it = items[i];
+        uint8_t *p;
+        const OutFrame *of;
+        int x0, y0, w, h;
+        if (it.stream == H264MI_STREAM_DERIVED || frame_ptrs(d, it.stream, it.frame, &p, &of) != H264MI_OK) {
+            set_error("deinterlace item %zu: no frame %d of stream %d in the last executed batch (a derived frame cannot be a source)", i, it.frame, it.stream);
+            return H264MI_EINVAL;
+        }
+        const int parity = it.parity == H264MI_DEINT_PARITY_FIRST && mode != H264MI_DEINT_BLEND ? of->first_parity : it.parity;
+        if (check_deint(mode, parity) != H264MI_OK) {
+            set_error("deinterlace item %zu: parity %d is not 0, 1 or H264MI_DEINT_PARITY_FIRST (with H264MI_DEINT_BLEND: not 0)", i, it.parity);
+            return H264MI_EINVAL;
+        }
+        crop_rect(of, 1, &x0, &y0, &w, &h);
+        DeintDesc &dd = descs[i];
+        set_source(dd, p, of, x0, y0, w, h, off);
+        dd.mode = mode, dd.parity = parity;
+        next[i].of = *of, next[i].off = off;
+        off += (static_cast<size_t>(dd.W) * dd.H * 3 / 2 + 255) & ~static_cast<size_t>(255); // a frame slot of the source's coded size
+        hmax = std::max(hmax, h);
+    }
+    if (n) TRY(reserve_derived(d, off));
+    if (n_derived) *n_derived = static_cast<int32_t>(n);
+    // from here on the arena is rewritten: the previous list is gone whatever happens (the launches that read it are ahead of this one on the stream)
+    d->derived.clear();
+    if (n == 0) return H264MI_OK;
+    DescTables &t = d->tables[OUT_DEINT];
+    const DeintDesc *dev;
+    TRY(stage_descs(d, t, descs, &dev));
+    const int pairs_per_block = 8; // 1080p: 8 x 120 items of 2 x 16 samples for 256 threads, 102 blocks per frame
+    const int hc = (hmax + 1) / 2, npairs = (hmax + 1) / 2 + (hc + 1) / 2;
+    hipLaunchKernelGGL(k_deint, dim3(static_cast<uint32_t>(n), (npairs + pairs_per_block - 1) / pairs_per_block), dim3(256), 0, d->stream, dev, d->d_derived, pairs_per_block);
+    TRY(fence_launch(d, t));
+    d->derived.swap(next);
+    return H264MI_OK;
+}
+
+extern "C" int32_t h264mi_items_deinterlace(h264mi_decoder *d, int32_t mode, const h264mi_deint_item *items, int32_t n, int32_t *n_derived) {
+    if (!d || n < 0 || (n > 0 && !items)) return H264MI_EINVAL;
+    return deint_items(d, mode, items, static_cast<size_t>(n), n_derived);
+}
+
+extern "C" int32_t h264mi_batch_deinterlace(h264mi_decoder *d, int32_t stream, int32_t mode, int32_t rate, int32_t *n_derived) {
+    if (!d || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    TRY(check_deint(mode, 0));
+    if ((rate != 1 && rate != 2) || (mode == H264MI_DEINT_BLEND && rate != 1)) {
+        set_error("deinterlace rate %d: not 1 or 2%s", rate, mode == H264MI_DEINT_BLEND ? " (H264MI_DEINT_BLEND has no parity: it needs rate 1)" : "");
+        return H264MI_EINVAL;
+    }
+    std::vector<h264mi_deint_item> items;
+    for (const std::pair<int, int> &f : batch_frames(d, stream)) {
+        uint8_t *p;
+        const OutFrame *of;
+        TRY(frame_ptrs(d, f.first, f.second, &p, &of));
+        const int first = mode == H264MI_DEINT_BLEND ? 0 : of->first_parity;
+        items.push_back({f.first, f.second, first});
+        if (rate == 2) items.push_back({f.first, f.second, 1 - first});
+    }
+    return deint_items(d, mode, items.data(), items.size(), n_derived);
 }

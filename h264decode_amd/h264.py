@@ -210,6 +210,10 @@ _FILTER_NAMES = {"bilinear": SCALE_BILINEAR, "area": SCALE_AREA}
 DT_U8, DT_F16, DT_BF16, DT_F32 = 0, 1, 2, 3           # H264MI_DT_*: element types of tensor_batch / tensor_items / frames_tensor(dtype=...)
 FIT_STRETCH, FIT_LETTERBOX = 0, 1                     # H264MI_FIT_*: how the picture is placed in the canvas
 TENSOR_BGR = 1                                        # H264MI_TENSOR_BGR: colour c at channel position 2 - c
+DEINT_FIELD, DEINT_BLEND, DEINT_EDGE = 0, 1, 2        # H264MI_DEINT_*: modes of Decoder.deinterlace / frames_tensor(deinterlace=...)
+DEINT_PARITY_FIRST = -1                               # H264MI_DEINT_PARITY_FIRST: the frame's own first_parity (Decoder.frame_fields)
+STREAM_DERIVED = 0x40000000                           # H264MI_STREAM_DERIVED: the pseudo-stream of the derived (deinterlaced) frames
+_DEINT_NAMES = {"field": DEINT_FIELD, "blend": DEINT_BLEND, "edge": DEINT_EDGE}
 _DT_NAMES = {"u8": DT_U8, "uint8": DT_U8, "f16": DT_F16, "float16": DT_F16, "bf16": DT_BF16, "bfloat16": DT_BF16, "f32": DT_F32, "float32": DT_F32}
 
 
@@ -227,6 +231,21 @@ def _filter(filter):
             raise H264MIError(-1, "unknown scale filter %r (bilinear, area)" % (filter,))
         return _FILTER_NAMES[filter.lower()]
     return int(filter)
+
+
+def _deint(mode):
+    if isinstance(mode, str):
+        if mode.lower() not in _DEINT_NAMES:
+            raise H264MIError(-1, "unknown deinterlace mode %r (field, blend, edge)" % (mode,))
+        return _DEINT_NAMES[mode.lower()]
+    return int(mode)
+
+
+def deint_rows(mode, parity, n_rows, y):
+    """The deinterlacing rule of include/h264mi.h for row y of a plane of n_rows rows, from the library (h264mi_deint_rows; no GPU): (kept, up, dn)."""
+    v = [ctypes.c_int32(0) for _ in range(3)]
+    check(_lib.load().h264mi_deint_rows(_deint(mode), int(parity), n_rows, y, *[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
 
 
 def _dtype(dtype):
@@ -455,8 +474,8 @@ class Decoder:
         return w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)
 
     def read_frame(self, stream, frame, crop=True):
-        p = self.frame_planes(stream, frame)
-        buf = np.zeros(p["coded_width"] * p["coded_height"] * 3 // 2, dtype=np.uint8)
+        fi = self.frame_info(stream, frame)
+        buf = np.zeros(fi.coded_width * fi.coded_height * 3 // 2, dtype=np.uint8)
         check(self._L.h264mi_frame_read(self._h, stream, frame, int(crop), buf.ctypes.data, buf.nbytes))
         return buf
 
@@ -494,6 +513,30 @@ class Decoder:
         m, f = ctypes.c_int32(0), ctypes.c_int32(0)
         check(self._L.h264mi_frame_colour(self._h, stream, frame, ctypes.byref(m), ctypes.byref(f)))
         return m.value, f.value
+
+    def frame_fields(self, stream, frame):
+        """What the frame's fields are (h264mi_frame_fields): field_coded (coded as two field pictures), top_field_order_cnt, bottom_field_order_cnt,
+        first_parity (1: the bottom field comes first)."""
+        ff = _lib.FieldInfo()
+        check(self._L.h264mi_frame_fields(self._h, stream, frame, ctypes.byref(ff)))
+        return ff
+
+    def deinterlace(self, stream=-1, mode="field", rate=1, items=None):
+        """K10 in one launch: derived (deinterlaced) frames of the last executed batch, which REPLACE the decoder's list of derived frames and are then
+        frames 0 .. n - 1 of the pseudo-stream STREAM_DERIVED for frame_count, frame_info, frame_colour, frame_fields, read_frame(crop=True) and every
+        pack / convert / scale / tensor call.  mode: "field", "blend" or "edge".  Without `items`: every frame of `stream` (-1: of all streams,
+        stream-major); rate 1: one derived frame per frame, of its first parity; rate 2: two, the first parity then the other ("bob"; not for "blend").
+        items: a list of (stream, frame, parity) with parity 0 (top), 1 (bottom) or DEINT_PARITY_FIRST; an empty list empties the list of derived
+        frames.  execute(), reset() and reset_stream() empty it too.  Returns the number of derived frames."""
+        n = ctypes.c_int32(0)
+        if items is None:
+            check(self._L.h264mi_batch_deinterlace(self._h, stream, _deint(mode), int(rate), ctypes.byref(n)))
+            return n.value
+        arr = (_lib.DeintItem * max(len(items), 1))()
+        for a, it in zip(arr, items):
+            a.stream, a.frame, a.parity = (int(v) for v in it)
+        check(self._L.h264mi_items_deinterlace(self._h, _deint(mode), arr, len(items), ctypes.byref(n)))
+        return n.value
 
     def convert_frame(self, stream, frame, dst_ptr, cap, fmt, csc=0):
         """K7 for one frame of the last executed batch: cropped and converted to `fmt` into the DEVICE buffer at dst_ptr (asynchronous on the
@@ -577,7 +620,7 @@ class Decoder:
         return out
 
     def frames_tensor(self, stream, fmt="rgbp", csc=0, size=None, filter="bilinear", *, dtype=None, scale=None, bias=None, mean=None, std=None,
-                      letterbox=False, pad=(114, 114, 114), rois=None, bgr=False):
+                      letterbox=False, pad=(114, 114, 114), rois=None, bgr=False, deinterlace=None, field_rate=False):
         """The frames of `stream` of the last executed batch as one torch uint8 tensor on the decoder's device: [n, 3, h, w] ("rgbp"), [n, h, w, 3]
         ("rgb24") or [n, H264MI_I420_SIZE(w, h)] ("nv12"), converted by one K7 launch.  Raises ValueError if the stream's frames differ in display size.
         With size = (ow, oh) the frames are scaled to that size by one K8 launch (`filter`: "bilinear" or "area"): the shapes are those with (ow, oh) for
@@ -595,9 +638,17 @@ class Decoder:
         rounded once -- giving both forms, or mean / std with uint8, is a ValueError.  letterbox keeps the aspect ratio and fills the rest of the canvas
         with pad = (R, G, B); bgr writes the channels in the order B, G, R (scale, bias, mean, std and pad stay per colour R, G, B).  rois, a list of
         (stream, frame, x, y, w, h) regions in display coordinates with even origins (w = h = 0: the whole frame), replaces "all frames of `stream`":
-        n = len(rois), in list order."""
+        n = len(rois), in list order.
+        deinterlace = "field", "blend" or "edge" (keyword-only): the frames of `stream` are deinterlaced first (one K10 launch: self.deinterlace(stream,
+        mode, rate), which replaces the decoder's derived frames) and everything above is then done for the pseudo-stream STREAM_DERIVED; field_rate
+        makes that two frames per frame, the first field's then the second's.  rois then name frames of STREAM_DERIVED."""
         import torch
         f = _fmt(fmt)
+        if deinterlace is not None:
+            self.deinterlace(stream, deinterlace, 2 if field_rate else 1)
+            stream = STREAM_DERIVED
+        elif field_rate:
+            raise ValueError("frames_tensor: field_rate needs deinterlace")
         if dtype is not None or scale is not None or bias is not None or mean is not None or std is not None or letterbox or rois is not None or bgr:
             return self._model_tensor(stream, f, csc, size, filter, dtype, scale, bias, mean, std, letterbox, pad, rois, bgr)
         if size is not None:

@@ -411,7 +411,8 @@ int32_t h264mi_batch_pack_device(h264mi_decoder *dec, int32_t stream, void *dst_
  * even luma columns, midway between luma rows 2j and 2j + 1): Hrow(r) = 2 C[r][k] for even x, C[r][k] + C[r][min(k + 1, wc - 1)] for odd x;
  * j' = max(j - 1, 0) for even y, min(j + 1, hc - 1) for odd y; c = (3 Hrow(j) + Hrow(j') + 4) >> 3 (weights sum to 8, one rounding).  The clamps are at the
  * edges of the DISPLAY chroma plane: coded samples outside the crop rectangle are never read.  The rule is applied to frames as they are, whether they
- * were coded as frame or field pictures: interlace-aware upsampling, and chroma_sample_loc_type other than 0, are out of scope. */
+ * were coded as frame or field pictures (deinterlace first where that matters: "Deinterlaced output" below); interlace-aware upsampling inside this
+ * rule, and chroma_sample_loc_type other than 0, are out of scope. */
 #define H264MI_FMT_I420 0
 #define H264MI_FMT_NV12 1
 #define H264MI_FMT_RGB24 2
@@ -451,7 +452,7 @@ int32_t h264mi_batch_convert_device(h264mi_decoder *dec, int32_t stream, int32_t
  * independently.  Source samples are those of the tight I420 frame: every clamp is at the edges of the display planes, coded samples outside the crop
  * rectangle are never read.  Chroma planes are scaled as planes, centre-aligned: the siting of chroma_sample_loc_type is not modelled in the scaler
  * (as for the upsampling above, only type 0 is, and only there).  In a monochrome stream the chroma is 128 and stays 128.  Frames are scaled as they are,
- * whether coded as frame or field pictures.
+ * whether coded as frame or field pictures: scaling a woven frame blends its two fields, so deinterlace first ("Deinterlaced output" below).
  * H264MI_SCALE_BILINEAR, for an axis of n_in samples scaled to n_out, output index i:
  *   step = (n_in << 16) / n_out (floor);  P = i step + (step >> 1) - 32768, clamped to 0 .. (n_in - 1) << 16;  a = P >> 16;  f = (P >> 8) & 255;
  *   b = min(a + 1, n_in - 1);  with (ax, bx, fx) of the column and (ay, by, fy) of the row the sample is
@@ -543,6 +544,72 @@ int32_t h264mi_items_tensor_device(h264mi_decoder *dec, const h264mi_tensor_spec
 /* The same for the whole of every frame of the last executed batch: frames of stream `stream` (or of all streams when stream = -1, stream-major) in
  * decoding order -- h264mi_batch_scale_device's order. */
 int32_t h264mi_batch_tensor_device(h264mi_decoder *dec, int32_t stream, const h264mi_tensor_spec *spec, void *dst_device, size_t cap, size_t *bytes);
+
+/* ---- Deinterlaced output (K10): derived frames for the output calls above, on the device ----
+ * The output stage weaves the two fields of a frame into one frame.  A deinterlaced frame is a tight I420 frame of the same display size w x h as its
+ * source, and a function of the source's tight I420 frame (what h264mi_frame_read(crop = 1) returns), a mode and a parity p (0 = top: even rows are kept;
+ * 1 = bottom: odd rows are kept), and of nothing else; this comment is the contract.  Each plane is processed on its own with the same parity: luma has
+ * hp = h rows and wp = w columns, each chroma plane hp = ceil(h / 2) rows and wp = ceil(w / 2) columns.  Parity counts rows of the DISPLAY plane; in
+ * streams with frame_mbs_only_flag 0 the crop units (7.4.2.1.1: two luma rows for monochrome, four otherwise) make the crop origin even in every plane that
+ * carries samples (the chroma of a monochrome stream is 128 throughout), so that is the coded parity as well.  Every clamp is at the edge of the display plane: coded samples outside the crop rectangle are never read.  All
+ * arithmetic is in integers, >> is a floor shift.
+ *   H264MI_DEINT_FIELD  rows with (y & 1) == p are copied.  Any other row: up = y - 1, dn = y + 1; if up < 0 then up = dn; if dn >= hp then dn = up; if
+ *                       neither exists (hp == 1, p == 1) the row is copied; otherwise out[y][x] = (S[up][x] + S[dn][x] + 1) >> 1.
+ *   H264MI_DEINT_BLEND  parity is ignored and must be 0.  Every row: out[y][x] = (S[max(y - 1, 0)][x] + 2 S[y][x] + S[min(y + 1, hp - 1)][x] + 2) >> 2 --
+ *                       one rounding, not two chained averages.
+ *   H264MI_DEINT_EDGE   chroma planes follow FIELD.  Luma: kept rows are copied.  A missing row whose up and dn both exist inside the plane and are
+ *                       distinct tries the directions d = 0, -1, +1 in that order with cost_d = |S[up][cx(x + d)] - S[dn][cx(x - d)]|,
+ *                       cx(t) = clamp(t, 0, wp - 1), takes the first direction of the strictly smallest cost and writes
+ *                       (S[up][cx(x + d)] + S[dn][cx(x - d)] + 1) >> 1.  A missing row at the plane's edge (up == dn after the clamp) is S[up][x]; the
+ *                       hp == 1 case is as in FIELD.
+ * Any other mode is H264MI_EINVAL.  A parity is 0, 1 or H264MI_DEINT_PARITY_FIRST: the first_parity of the frame (h264mi_frame_fields), resolved per frame.
+ * Out of scope: temporal (motion-adaptive) modes, which need the neighbouring frames across batches; interlace-aware chroma upsampling inside K7 (chroma
+ * planes are deinterlaced as planes, then upsampled by the rule of "Output formats"); pulldown detection and SEI pic_struct; MBAFF, as everywhere. */
+#define H264MI_DEINT_FIELD 0
+#define H264MI_DEINT_BLEND 1
+#define H264MI_DEINT_EDGE 2
+#define H264MI_DEINT_PARITY_FIRST (-1)
+/* The rule for row y of a plane of n_rows rows, as a pure function (no decoder, no device).  *kept = 1: the row is copied, *up and *dn are both y.  Else
+ * *up and *dn are the rows above and below after the clamps (FIELD / EDGE: equal at the plane's edge; BLEND: always *kept = 0 and the two clamped
+ * neighbours of y).  H264MI_EINVAL: an unknown mode, a parity outside 0 / 1, a non-zero parity with BLEND, n_rows outside 1 .. H264MI_SCALE_MAX, y outside
+ * 0 .. n_rows - 1, a null pointer. */
+int32_t h264mi_deint_rows(int32_t mode, int32_t parity, int32_t n_rows, int32_t y, int32_t *kept, int32_t *up, int32_t *dn);
+/* What a frame's fields are.  field_coded: 1 if the frame was coded as two field pictures (a frame that went out with one field missing or concealed
+ * counts as 1), else 0.  top_field_order_cnt / bottom_field_order_cnt: TopFieldOrderCnt and BottomFieldOrderCnt (8.2.1), after a possible memory
+ * management operation 5, like pic_order_cnt of h264mi_frame_get_info; of a frame that went out with one field missing both are the count of the field
+ * there is.  first_parity: 1 if the bottom count is lower than the top count, else 0 -- for a picture with operation 5 the relation before the counts
+ * are rewritten; for a frame with one field missing the parity of the field there is; for a frame of two field pictures with EQUAL counts
+ * (pic_order_cnt_type 2 gives both fields of a reference frame one count, and output order is decoding order there, 8.2.1.3) the parity of the field
+ * that was decoded first. */
+typedef struct {
+    int32_t field_coded, top_field_order_cnt, bottom_field_order_cnt, first_parity;
+} h264mi_field_info;
+int32_t h264mi_frame_fields(h264mi_decoder *dec, int32_t stream, int32_t frame, h264mi_field_info *out);
+/* Derived frames.  A deinterlace call makes one derived frame per item, in ONE launch (K10) on the decoder's stream, with the discipline of the output
+ * calls: everything is checked, resolved and sized first, a call that fails launches nothing and leaves the previous list as it was.  Each call REPLACES
+ * the decoder's list of derived frames; n = 0 empties it; h264mi_batch_execute, h264mi_decoder_reset and h264mi_stream_reset (of any stream) empty it too.
+ * *n_derived (may be NULL) receives the length of the new list.  Derived frame k is frame k of the pseudo-stream H264MI_STREAM_DERIVED, and these calls
+ * accept it: h264mi_stream_frame_count; h264mi_frame_get_info, h264mi_frame_colour and h264mi_frame_fields, which report the SOURCE's values;
+ * h264mi_frame_read with crop = 1; every frame, batch and item call of K6 .. K9 (as `stream` of a batch call it means the derived frames only: -1 is
+ * still the frames of the real streams).  Every other per-frame accessor -- h264mi_frame_read with crop = 0, h264mi_frame_device_planes,
+ * h264mi_frame_read_mbrecs, h264mi_frame_read_mbmv1, h264mi_frame_concealed, h264mi_stream_output_order -- returns H264MI_EINVAL for it, and so does a
+ * deinterlace item that names it.  The contract: a deinterlaced and converted / scaled / tensor item is the function of "Output formats" / "Scaled
+ * output" / "Model input" applied to the deinterlaced frame; H264MI_CSC_AUTO still resolves from the source's SPS and display size.
+ * A derived frame lives in decoder-owned device memory in the layout of a frame slot of its source's coded size, of which only the display rectangle is
+ * written, at the source's crop origin.  The arena grows to the largest call and is kept, is zero-filled when allocated, is counted by
+ * h264mi_decoder_memory and freed by h264mi_decoder_destroy; a call that cannot get its memory returns H264MI_ENOMEM with the previous list intact.
+ * There is no limit on n other than that.
+ * h264mi_items_deinterlace: item i is frame `frame` of stream `stream` of the last executed batch under `mode` with `parity` (0, 1 or
+ * H264MI_DEINT_PARITY_FIRST; with H264MI_DEINT_BLEND it must be 0); the same frame may appear in many items.
+ * h264mi_batch_deinterlace: every frame of stream `stream` (or of all streams when stream = -1, stream-major) in decoding order.  rate = 1: one derived
+ * frame per frame, of parity first_parity (0 under BLEND).  rate = 2: two per frame, first_parity then the other -- field rate, "bob"; BLEND needs
+ * rate = 1.  Any other rate is H264MI_EINVAL. */
+#define H264MI_STREAM_DERIVED 0x40000000 /* far above any max_streams */
+typedef struct {
+    int32_t stream, frame, parity;
+} h264mi_deint_item;
+int32_t h264mi_items_deinterlace(h264mi_decoder *dec, int32_t mode, const h264mi_deint_item *items, int32_t n, int32_t *n_derived);
+int32_t h264mi_batch_deinterlace(h264mi_decoder *dec, int32_t stream, int32_t mode, int32_t rate, int32_t *n_derived);
 
 /* Debug / test access to the intermediate macroblock records of a frame (host copy).
  * rec: 128 bytes per MB (layout: h264decode_amd/csrc/mi_types.h struct MbRec). */
