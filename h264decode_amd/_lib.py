@@ -75,6 +75,16 @@ def load_hooks():
         if not os.path.exists(path):
             raise H264MIError(-4, "libh264mi_hooks.so is not built (make -C h264decode_amd/csrc)")
         _hooks = ctypes.CDLL(path)
+        I32 = ctypes.c_int32
+        # k_dbprep / k_dbprep_ip: the routing rule, and the last executed batch checked against k_dbprep (launches_ip, launches_generic, mismatching_bytes)
+        _hooks.h264mi_internal_dbprep_kernel_choice.argtypes = [I32, I32]
+        _hooks.h264mi_internal_dbprep_kernel_choice.restype = I32
+        _hooks.h264mi_internal_dbprep_check.argtypes = [ctypes.c_void_p, ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(ctypes.c_int64)]
+        _hooks.h264mi_internal_dbprep_check.restype = I32
+        _hooks.h264mi_internal_set_dbprep_rows.argtypes = [ctypes.c_void_p, I32]
+        _hooks.h264mi_internal_set_dbprep_rows.restype = I32
+        _hooks.h264mi_internal_dbprep_ip_rows.argtypes = [I32, I32, I32]
+        _hooks.h264mi_internal_dbprep_ip_rows.restype = I32
     return _hooks
 
 

@@ -797,6 +797,23 @@ static int fill_frame_num_gap(h264mi_decoder *d, int si, const h264mi_sps &sps, 
     return H264MI_OK;
 }
 
+// Per level of a batch: which k_dbprep kernel runs on the pictures complete with it (mi_dbprep_kernel_choice), from what their descriptors say now
+static void choose_dbprep_kernels(Stage &g) {
+    g.prep_kernel.assign(g.prep_n.size(), MI_DBPREP_K_GENERIC);
+    for (size_t l = 0; l < g.prep_n.size(); l++) {
+        int n_has_b = 0, n_save_col = 0;
+        for (uint32_t i = 0; i < g.prep_n[l]; i++) {
+            const PicDesc &pd = g.h_pics[g.h_lists[g.prep_off[l] + i]];
+            n_has_b += pd.has_b != 0, n_save_col += pd.save_col != 0;
+        }
+        g.prep_kernel[l] = mi_dbprep_kernel_choice(n_has_b, n_save_col);
+#if defined(H264MI_TEST_HOOKS) /* measurement: the general kernel everywhere, as before there was a kernel for I / P launches */
+        if (const char *e = getenv("H264MI_DBPREP_GENERIC"))
+            if (atoi(e)) g.prep_kernel[l] = MI_DBPREP_K_GENERIC;
+#endif
+    }
+}
+
 // What only B pictures need exists once the first B slice has been seen: the list-1 vector arrays (64 bytes per macroblock and
 // buffer set) and the ColRec arrays (80 bytes per macroblock and frame slot: the motion direct prediction reads).  Reference
 // pictures decoded BEFORE that moment have left no ColRec; the ones of the batch before this one -- where RefPicList1[0] of a
@@ -852,6 +869,7 @@ static int ensure_b_buffers(h264mi_decoder *d) {
                 }
         if (!list.empty()) {
             const int pset = d->last_exec_set;
+            choose_dbprep_kernels(pv); // (that batch executed again writes these ColRec arrays itself: its pictures are flagged save_col now)
             HIP_TRY(hipMemcpyAsync(pv.d_pics, pv.h_pics, sizeof(PicDesc) * pv.n_pics, hipMemcpyHostToDevice, up));
             HIP_TRY(hipMemcpyAsync(d->d_backfill, list.data(), sizeof(uint32_t) * list.size(), hipMemcpyHostToDevice, up));
             HIP_TRY(hipStreamSynchronize(up)); // (`list` is pageable host memory; once per decoder)
@@ -1649,6 +1667,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
             }
         g.prep_n[l] = pos - g.prep_off[l];
     }
+    choose_dbprep_kernels(g);
     // Uploads go to the entropy stream the next execute will use: in order with that pass's entropy kernel, and not behind
     // the batch that is still executing (the caller's stream waits for its reconstruction).  No stream of their own: the
     // runtime multiplexes streams onto 4 hardware queues by default, and a fifth stream ended up sharing a queue with one of
@@ -1711,6 +1730,7 @@ extern "C" int32_t h264mi_batch_execute(h264mi_decoder *d) {
 static int execute_stage(h264mi_decoder *d, int stage_idx, bool exclusive) {
     if (exclusive) d->pass += (MI_SETS - d->pass % MI_SETS) % MI_SETS; // record set 0
     d->last_exec_stage = stage_idx, d->last_exec_set = static_cast<int>(d->pass % MI_SETS);
+    d->dbprep_launches[0] = d->dbprep_launches[1] = 0;
     Stage &g = d->stage[stage_idx];
     if (!g.n_slices && !g.n_pics && g.grey.empty()) return H264MI_OK; // (pictures without slices: inserted for a lone field that an end-of-sequence unit revealed)
     GUARD(d);
@@ -1780,9 +1800,17 @@ static int execute_stage(h264mi_decoder *d, int stage_idx, bool exclusive) {
             if (d->conceal && g.prep_n[lv])
                 hipLaunchKernelGGL(k_conceal, dim3(g.prep_n[lv]), dim3(256), 0, st, g.d_lists + g.prep_off[lv], g.d_pics, g.d_slices, g.d_cmap, static_cast<uint32_t>(g.n_slices),
                                    g.d_status, g.d_bits, d->d_tables, mbrec, d->d_mv1[set], g.d_status + 8 * static_cast<size_t>(g.n_slices));
-            if (g.prep_n[lv])
-                hipLaunchKernelGGL(k_dbprep, dim3((g.mbs_max + MI_DBPREP_MBS - 1) / MI_DBPREP_MBS, (g.prep_n[lv] + 7u) & ~7u), dim3(256), 0, st, g.d_lists + g.prep_off[lv], g.d_pics,
-                                   d->d_tables, mbrec, d->d_mv1[set], d->d_dbprm[set], 0, d->d_imask[set], static_cast<int>(g.prep_n[lv]));
+            if (g.prep_n[lv]) {
+                if (g.prep_kernel[lv] == MI_DBPREP_K_IP) {
+                    const int chunks = std::max(1, (g.wmb_max + 63) / 64), hmax = std::max(1, g.hmb_max);
+                    const int rows = d->dbprep_rows > 0 ? std::min(d->dbprep_rows, hmax) : mi_dbprep_ip_rows(static_cast<int>(g.prep_n[lv]), g.wmb_max, hmax);
+                    hipLaunchKernelGGL(k_dbprep_ip, dim3(static_cast<uint32_t>(chunks * ((hmax + rows - 1) / rows)), (g.prep_n[lv] + 7u) & ~7u), dim3(64), 0, st,
+                                       g.d_lists + g.prep_off[lv], g.d_pics, d->d_tables, mbrec, d->d_dbprm[set], d->d_imask[set], static_cast<int>(g.prep_n[lv]), chunks, rows);
+                } else
+                    hipLaunchKernelGGL(k_dbprep, dim3((g.mbs_max + MI_DBPREP_MBS - 1) / MI_DBPREP_MBS, (g.prep_n[lv] + 7u) & ~7u), dim3(256), 0, st, g.d_lists + g.prep_off[lv], g.d_pics,
+                                       d->d_tables, mbrec, d->d_mv1[set], d->d_dbprm[set], 0, d->d_imask[set], static_cast<int>(g.prep_n[lv]));
+                d->dbprep_launches[g.prep_kernel[lv]]++;
+            }
             if (lv == n_levels - 1 && done) hipEventRecord(done, st);
         }
     };
@@ -2193,6 +2221,70 @@ extern "C" int32_t h264mi_internal_deblock_plan(int32_t wmb, int32_t hmb, int32_
 // 0 k_entropy, 1 k_entropy_f, 2 k_entropy_c.
 extern "C" int32_t h264mi_internal_entropy_kernel_choice(int32_t n_cabac, int32_t n_cavlc, int32_t slice_groups) {
     return mi_entropy_kernel_choice(n_cabac, n_cavlc, slice_groups != 0);
+}
+
+// Not part of the public ABI: which k_dbprep kernel runs on a level's pictures, n_has_b of them with B slices and n_save_col leaving a ColRec array
+// (mi_dbprep_kernel_choice): 0 k_dbprep, 1 k_dbprep_ip.
+extern "C" int32_t h264mi_internal_dbprep_kernel_choice(int32_t n_has_b, int32_t n_save_col) { return mi_dbprep_kernel_choice(n_has_b, n_save_col); }
+
+// Not part of the public ABI: macroblock rows per wavefront of k_dbprep_ip for the launches to come (0: the rule, mi_dbprep_ip_rows) -- short test
+// streams never have pictures enough for the rule to choose strips of more than one row
+extern "C" int32_t h264mi_internal_set_dbprep_rows(h264mi_decoder *d, int32_t rows) {
+    if (!d || rows < 0) return H264MI_EINVAL;
+    d->dbprep_rows = rows;
+    return H264MI_OK;
+}
+// ... and the rule itself
+extern "C" int32_t h264mi_internal_dbprep_ip_rows(int32_t n_pics, int32_t wmb_max, int32_t hmb_max) { return mi_dbprep_ip_rows(n_pics, wmb_max, hmb_max); }
+
+// Not part of the public ABI: the batch executed last once more through k_dbprep -- its records are still resident in its set --, over the same picture
+// lists, into scratch buffers, and what the pass itself produced compared with that: the bytes of the DbPrm records of its pictures and of the intra mask
+// that differ.  launches_ip / launches_generic: the k_dbprep_ip / k_dbprep launches of that pass.
+extern "C" int32_t h264mi_internal_dbprep_check(h264mi_decoder *d, int32_t *launches_ip, int32_t *launches_generic, int64_t *mismatching_bytes) {
+    if (!d || !launches_ip || !launches_generic || !mismatching_bytes || d->last_exec_stage < 0) return H264MI_EINVAL;
+    GUARD(d);
+    HIP_TRY(hipDeviceSynchronize());
+    const Stage &g = d->stage[d->last_exec_stage];
+    const int set = d->last_exec_set;
+    *launches_ip = d->dbprep_launches[MI_DBPREP_K_IP], *launches_generic = d->dbprep_launches[MI_DBPREP_K_GENERIC];
+    *mismatching_bytes = 0;
+    if (!g.mb_used) return H264MI_OK;
+    const size_t mask_bytes = sizeof(unsigned long long) * (g.mb_used / 64 + 2);
+    DbPrm *prm = nullptr;
+    unsigned long long *mask = nullptr;
+    hipError_t e = hipMalloc(&prm, sizeof(DbPrm) * g.mb_used);
+    if (e == hipSuccess) e = hipMalloc(&mask, mask_bytes);
+    if (e == hipSuccess) e = hipMemset(prm, 0xA5, sizeof(DbPrm) * g.mb_used);
+    if (e == hipSuccess) e = hipMemset(mask, 0, mask_bytes);
+    for (size_t lv = 0; e == hipSuccess && lv < g.prep_n.size(); lv++)
+        if (g.prep_n[lv]) {
+            // (the ColRec arrays of save_col pictures are written once more, with the same bytes)
+            hipLaunchKernelGGL(k_dbprep, dim3((g.mbs_max + MI_DBPREP_MBS - 1) / MI_DBPREP_MBS, (g.prep_n[lv] + 7u) & ~7u), dim3(256), 0, d->stream, g.d_lists + g.prep_off[lv],
+                               g.d_pics, d->d_tables, d->d_mbrec[set], d->d_mv1[set], prm, 0, mask, static_cast<int>(g.prep_n[lv]));
+            e = hipGetLastError();
+        }
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    std::vector<uint8_t> a, b;
+    auto differ = [&](const void *x, const void *y, size_t n) {
+        a.resize(n), b.resize(n);
+        if (e == hipSuccess) e = hipMemcpy(a.data(), x, n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(b.data(), y, n, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return;
+        for (size_t i = 0; i < n; i++) *mismatching_bytes += a[i] != b[i];
+    };
+    for (size_t lv = 0; lv < g.prep_n.size(); lv++)
+        for (uint32_t i = 0; i < g.prep_n[lv]; i++) {
+            const PicDesc &pd = g.h_pics[g.h_lists[g.prep_off[lv] + i]];
+            differ(d->d_dbprm[set] + pd.mb_base, prm + pd.mb_base, sizeof(DbPrm) * pd.wmb * pd.hmb);
+        }
+    differ(d->d_imask[set], mask, mask_bytes);
+    if (prm) hipFree(prm);
+    if (mask) hipFree(mask);
+    if (e != hipSuccess) {
+        set_error("h264mi_internal_dbprep_check failed: %s", hipGetErrorString(e));
+        return H264MI_EDEVICE;
+    }
+    return H264MI_OK;
 }
 
 // Not part of the public ABI: the phase clocks a -DMI_DB_STATS build of the banded deblocking kernels leaves (zero otherwise); reading clears them

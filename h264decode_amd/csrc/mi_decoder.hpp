@@ -104,6 +104,7 @@ struct Stage {
     int ent_kernel = MI_ENT_K_GENERAL;       // the I/P entropy kernel of level 0 (mi_entropy_kernel_choice), decided when the batch is prepared
     std::vector<uint32_t> colsave_n;            // per level: pictures whose ColRec array k_dbprep writes (what the cross-pass fence looks at)
     std::vector<uint32_t> prep_off, prep_n;     // per level: the pictures whose last slice is of that level (k_dbprep runs on them after the level), as a range of d_lists
+    std::vector<int> prep_kernel;               // per level: the kernel that runs on them (mi_dbprep_kernel_choice)
     std::vector<uint32_t> wave_b_off, wave_b_n, wave_p_off, wave_p_n, wave_nb_off, wave_nb_n; // per wave: B pictures / inter non-B / non-B
     int n_slices = 0, n_pics = 0, wmb_max = 0, hmb_max = 0, mbs_max = 0;
     uint64_t mb_used = 0;
@@ -167,6 +168,8 @@ struct h264mi_decoder {
     uint64_t pass = 0; // execute() counter
     int last_exec_stage = -1, last_exec_set = 0; // staging set and record set of the most recent execute (ensure_b_buffers)
     bool last_pass_had_b = false;
+    int dbprep_launches[2] = {0, 0};     // launches of the last execute by kernel (MI_DBPREP_K_*), for the test hooks
+    int dbprep_rows = 0;                 // macroblock rows per wavefront of k_dbprep_ip; 0: mi_dbprep_ip_rows (set by a test hook only)
     uint64_t mb_cap = 0;
     uint64_t dev_bytes = 0;              // device memory this decoder holds (h264mi_decoder_memory)
     uint32_t *d_backfill = nullptr;      // picture list of the one-off ColRec back-fill (first B slice of a decoder)

@@ -36,13 +36,20 @@ extern "C" __global__ void k_intra(const uint32_t *pic_list, const PicDesc *pics
 extern "C" __global__ void k_intra_x(const uint32_t *pic_list, const PicDesc *pics, const FramePool *pools, const DevTables *tab, const MbRec *mbrec,
                                      const int16_t *coefs, uint32_t *xdone, uint32_t epoch, int nbands, uint32_t *ticket, uint32_t ticket_base, int wmb_max,
                                      uint32_t *xstatus, int waves_per_row, const unsigned long long *intramask);
-// k_dbprep: boundary strengths + alpha / beta / tC0 of every macroblock of a batch (DbPrm), so that K5 -- one serial dependency chain per
-// picture -- has none of that work in its steps; for the pictures flagged PicDesc::save_col also their ColRec array (the motion later B pictures
-// take their direct prediction from).  grid = (ceil(mbs_max / MI_DBPREP_MBS), pictures of the list), block = 256.
+// k_dbprep (k_dbprep.hip): boundary strengths + alpha / beta / tC0 of every macroblock of a batch (DbPrm), so that K5 -- one serial dependency chain per
+// picture -- has none of that work in its steps, and K3's work list (one bit per intra or undelivered macroblock).  Two kernels write the same bytes:
+//   k_dbprep     any picture: one or two reference lists; for the pictures flagged PicDesc::save_col also their ColRec array (the motion later B
+//                pictures take their direct prediction from); col_only: the one-off ColRec back-fill.  16 lanes per macroblock.
+//                grid = (ceil(mbs_max / MI_DBPREP_MBS), pictures of the list rounded up to a multiple of 8), block = 256.
+//   k_dbprep_ip  launches without a picture that has B slices or leaves a ColRec array (mi_dbprep_kernel_choice): one lane per macroblock, one wavefront
+//                per strip of 64 macroblock columns x `rows` macroblock rows (mi_dbprep_ip_rows).
+//                grid = (ceil(wmb_max / 64) * ceil(hmb_max / rows), pictures of the list rounded up to a multiple of 8), block = 64.
 #ifndef MI_DBPREP_MBS
 #define MI_DBPREP_MBS 64
 #endif
 extern "C" __global__ void k_dbprep(const uint32_t *pic_list, const PicDesc *pics, const DevTables *tab, const MbRec *mbrec, const MbMv1 *mbmv1, DbPrm *out, int col_only, unsigned long long *intramask, int n_pics);
+extern "C" __global__ void k_dbprep_ip(const uint32_t *pic_list, const PicDesc *pics, const DevTables *tab, const MbRec *mbrec, DbPrm *out, unsigned long long *intramask, int n_pics,
+                                       int chunks, int rows);
 // k_conceal (k_conceal.hip): error concealment -- between a level's entropy launch and its k_dbprep, the lost macroblocks of the concealable pictures of
 // the list (MBT_NONE records; every macroblock of a slice with a non-zero status) become zero-vector P_Skip records that point at PicDesc::conceal_ref
 // and at the picture's concealment SliceDesc (slices[conceal_base + picture]).  grid = pictures of the list, block = 256.
@@ -126,6 +133,21 @@ enum { MI_ENT_K_GENERAL = 0, MI_ENT_K_FMO = 1, MI_ENT_K_CABAC = 2 };
 static inline int mi_entropy_kernel_choice(int n_cabac, int n_cavlc, bool slice_groups) {
     if (slice_groups) return MI_ENT_K_FMO;
     return (n_cavlc == 0 && n_cabac > 0) ? MI_ENT_K_CABAC : MI_ENT_K_GENERAL;
+}
+// Which k_dbprep kernel runs on the pictures complete with a level: the one-lane-per-macroblock kernel if none of them has B slices (n_has_b) and none
+// leaves a ColRec array (n_save_col); else -- one such picture is enough -- the general one.
+enum { MI_DBPREP_K_GENERIC = 0, MI_DBPREP_K_IP = 1 };
+static inline int mi_dbprep_kernel_choice(int n_has_b, int n_save_col) { return (n_has_b == 0 && n_save_col == 0) ? MI_DBPREP_K_IP : MI_DBPREP_K_GENERIC; }
+// Macroblock rows per wavefront of k_dbprep_ip.  A wavefront that walks down its strip takes a row's upper neighbours from its own registers, so the
+// higher the strips, the fewer records are fetched twice -- whole columns once the launch has wavefronts enough without cutting them (twice the 4096
+// the chip holds at four per SIMD); a launch of few pictures is cut into as many strips as that takes, down to single rows.
+#define MI_DBPREP_IP_WAVES 8192
+static inline int mi_dbprep_ip_rows(int n_pics, int wmb_max, int hmb_max) {
+    const long columns = static_cast<long>(n_pics > 0 ? n_pics : 1) * ((wmb_max + 63) / 64 > 0 ? (wmb_max + 63) / 64 : 1);
+    long bands = (MI_DBPREP_IP_WAVES + columns - 1) / columns; // strips per column the target asks for
+    if (bands > hmb_max) bands = hmb_max;
+    if (bands < 1) bands = 1;
+    return static_cast<int>((hmb_max + bands - 1) / bands);
 }
 // K6: crop + tight pack of a list of frames into I420; grid = (frames, ceil((h_max + 2 * ceil(h_max / 2)) / rows_per_block)), block = 256
 typedef struct {
