@@ -681,3 +681,50 @@ func (d *Decoder) TensorItems(spec *TensorSpec, items []TensorItem, dst unsafe.P
 	err := status(C.h264mi_items_tensor_device(d.h, &c, &ci[0], C.int32_t(len(items)), dst, C.size_t(capBytes), &n))
 	return int(n), err
 }
+
+// Macroblock side information (K11; include/h264mi.h "Macroblock side information"): motion vectors, reference indices, picture order count
+// distances, macroblock classes, QP, coded-block flags and slice ordinals as int16 planes per 4x4 luma block.  Like the rest of this file these
+// wrappers were written blind: no Go toolchain was at hand to compile them.
+const (
+	SideType  = 0x001 // H264MI_SIDE_TYPE: MbNone .. MbBSkip
+	SideQP    = 0x002
+	SideNZ    = 0x004
+	SideSlice = 0x008
+	SideMVX0  = 0x010
+	SideMVY0  = 0x020
+	SideRef0  = 0x040
+	SideDPOC0 = 0x080
+	SideMVX1  = 0x100
+	SideMVY1  = 0x200
+	SideRef1  = 0x400
+	SideDPOC1 = 0x800
+	SideAll   = 0xFFF
+)
+
+// SideSize: the grid (ceil(w / 4) x ceil(h / 4) cells) and the bytes of one frame's planes.
+func SideSize(planes, w, h int) (gw, gh, bytes int, err error) {
+	var cw, ch C.int32_t
+	var n C.size_t
+	err = status(C.h264mi_side_size(C.int32_t(planes), C.int32_t(w), C.int32_t(h), &cw, &ch, &n))
+	return int(cw), int(ch), int(n), err
+}
+
+// SideBatch writes the selected planes of every frame of the last batch (stream < 0: all streams, stream-major) into device memory `dst` with
+// one kernel launch and returns the byte count.
+func (d *Decoder) SideBatch(stream, planes int, dst unsafe.Pointer, capBytes int) (int, error) {
+	var n C.size_t
+	err := status(C.h264mi_batch_side_device(d.h, C.int32_t(stream), C.int32_t(planes), dst, C.size_t(capBytes), &n))
+	return int(n), err
+}
+
+// RefPocs: the picture order counts of RefPicList0 / 1 of a slice (-1: the concealment pseudo-slice) of a frame of the last batch, and the
+// current picture's count, both as of list-building time.
+func (d *Decoder) RefPocs(stream, frame, slice, list int) (curPoc int, pocs []int, err error) {
+	var cur, n C.int32_t
+	var buf [32]C.int32_t
+	err = status(C.h264mi_frame_ref_pocs(d.h, C.int32_t(stream), C.int32_t(frame), C.int32_t(slice), C.int32_t(list), &cur, &buf[0], 32, &n))
+	for i := 0; i < int(n) && i < 32; i++ {
+		pocs = append(pocs, int(buf[i]))
+	}
+	return int(cur), pocs, err
+}

@@ -50,6 +50,7 @@ Nal, Sps, Pps, SliceHdr, Config, BatchInfo, FrameInfo = (_S["h264mi_nal"], _S["h
                                                          _S["h264mi_config"], _S["h264mi_batch_info"], _S["h264mi_frame_info"])
 TensorSpec, TensorItem = _S["h264mi_tensor_spec"], _S["h264mi_tensor_item"]
 FieldInfo, DeintItem = _S["h264mi_field_info"], _S["h264mi_deint_item"]
+SideItem = _S["h264mi_side_item"]
 
 
 def build(force=False):
@@ -85,6 +86,9 @@ def load_hooks():
         _hooks.h264mi_internal_set_dbprep_rows.restype = I32
         _hooks.h264mi_internal_dbprep_ip_rows.argtypes = [I32, I32, I32]
         _hooks.h264mi_internal_dbprep_ip_rows.restype = I32
+        # 1 while a K11 launch is recorded that the next execute's entropy stream waits for
+        _hooks.h264mi_internal_side_pending.argtypes = [ctypes.c_void_p, ctypes.POINTER(I32)]
+        _hooks.h264mi_internal_side_pending.restype = I32
     return _hooks
 
 
@@ -144,6 +148,10 @@ def load():
         "h264mi_frame_fields": [vp, I32, I32, P(FieldInfo)],
         "h264mi_items_deinterlace": [vp, I32, P(DeintItem), I32, P(I32)],
         "h264mi_batch_deinterlace": [vp, I32, I32, I32, P(I32)],
+        "h264mi_side_size": [I32, I32, I32, P(I32), P(I32), P(SZ)],
+        "h264mi_frame_ref_pocs": [vp, I32, I32, I32, I32, P(I32), P(I32), I32, P(I32)],
+        "h264mi_items_side_device": [vp, I32, P(SideItem), I32, vp, SZ, P(SZ)],
+        "h264mi_batch_side_device": [vp, I32, I32, vp, SZ, P(SZ)],
         "h264mi_frame_read_mbrecs": [vp, I32, I32, vp, SZ],
         "h264mi_frame_read_mbmv1": [vp, I32, I32, vp, SZ],
         "h264mi_decoder_set_profiling": [vp, I32],
@@ -187,4 +195,5 @@ EXPORTS = ["h264mi_annexb_scan", "h264mi_nal_parse", "h264mi_sps_parse", "h264mi
            "h264mi_output_size", "h264mi_csc_resolve", "h264mi_frame_colour", "h264mi_frame_convert_device", "h264mi_batch_convert_device",
            "h264mi_scale_taps", "h264mi_frame_scale_device", "h264mi_batch_scale_device",
            "h264mi_fit_rect", "h264mi_tensor_size", "h264mi_items_tensor_device", "h264mi_batch_tensor_device",
-           "h264mi_deint_rows", "h264mi_frame_fields", "h264mi_items_deinterlace", "h264mi_batch_deinterlace"]
+           "h264mi_deint_rows", "h264mi_frame_fields", "h264mi_items_deinterlace", "h264mi_batch_deinterlace",
+           "h264mi_side_size", "h264mi_frame_ref_pocs", "h264mi_items_side_device", "h264mi_batch_side_device"]

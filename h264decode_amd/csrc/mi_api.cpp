@@ -223,6 +223,8 @@ static void free_all(h264mi_decoder *d) {
         if (g.h_lists) hipHostFree(g.h_lists);
         if (g.d_bext) hipFree(g.d_bext);
         if (g.h_bext) hipHostFree(g.h_bext);
+        if (g.d_dpoc) hipFree(g.d_dpoc);
+        if (g.h_dpoc) hipHostFree(g.h_dpoc);
         if (g.d_cmap) hipFree(g.d_cmap);
         if (g.h_cmap) hipHostFree(g.h_cmap);
         if (g.ev_upload) hipEventDestroy(g.ev_upload);
@@ -358,6 +360,8 @@ extern "C" int32_t h264mi_decoder_create(const h264mi_config *cfg_, h264mi_decod
         TRY_ALLOC(hipHostMalloc(&g.h_pics, sizeof(PicDesc) * d->pics_cap));
         DEV_ALLOC(g.d_status, sizeof(uint32_t) * status_alloc);
         TRY_ALLOC(hipHostMalloc(&g.h_status, sizeof(uint32_t) * status_alloc));
+        DEV_ALLOC(g.d_dpoc, sizeof(int16_t) * 2 * MI_MAX_REFS * slices_alloc);
+        TRY_ALLOC(hipHostMalloc(&g.h_dpoc, sizeof(int16_t) * 2 * MI_MAX_REFS * slices_alloc));
         if (d->conceal) {
             DEV_ALLOC(g.d_cmap, sizeof(uint32_t) * (static_cast<size_t>(d->pics_cap) + d->slices_cap));
             TRY_ALLOC(hipHostMalloc(&g.h_cmap, sizeof(uint32_t) * (static_cast<size_t>(d->pics_cap) + d->slices_cap)));
@@ -889,6 +893,11 @@ static void wave_after(Stage &g, const Dpb &dpb, int pic, int entry) {
         if (p >= 0 && p != pic && p < static_cast<int>(g.pic_wave.size())) g.pic_wave[pic] = std::max(g.pic_wave[pic], g.pic_wave[p] + 1);
 }
 
+// PicOrderCnt of a reference list entry: a field's own count in a field picture (entries name fields: slot | MI_REF_PARITY), the frame's otherwise
+static int list_entry_poc(const Dpb &dpb, int e, bool fieldpic) {
+    return fieldpic ? dpb.slots[MI_REF_SLOT(e)].fpoc[(e & MI_REF_PARITY) ? 1 : 0] : dpb.slots[e].poc;
+}
+
 // The first slice of a new picture (`sh`, of NAL unit type `type`; second: the second field of the frame in Dpb::pend_slot): its frame slot, its place
 // in the batch's tables, its PicDesc and the frame it goes out as.  The picture is then under construction (Dpb::cur_slot, StreamState::cur_*) until finish_picture.
 static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const h264mi_pps &pps, uint32_t pps_id, const h264mi_slice_header &sh, int type, bool second) {
@@ -957,6 +966,10 @@ static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const
         pd.conceal_ref = static_cast<int16_t>(idr_ref);
         wave_after(g, s.dpb, s.cur_pic, idr_ref);
     }
+    // K11: the picture order counts of the picture and of its concealment reference as they are NOW (the slot named may be another picture's by the end
+    // of the batch, and operation 5 rewrites this picture's): what the concealment pseudo-slice reports (h264mi_frame_ref_pocs, slice -1)
+    g.pic_conceal_poc.resize(g.n_pics);
+    g.pic_conceal_poc[s.cur_pic] = {sh.field_pic ? sl.fpoc[sh.bottom_field ? 1 : 0] : sl.poc, pd.conceal_ref >= 0 ? list_entry_poc(s.dpb, pd.conceal_ref, sh.field_pic != 0) : 0};
     if (s.pending_drops) { // slices without a readable header in front of this picture's first good one: lost slices of it, if it can be concealed
         const int n = s.pending_drops, e = s.pending_drop_err;
         s.pending_drops = 0;
@@ -1318,6 +1331,21 @@ static int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref
             g.h_bext[g.n_bext++] = bx;
         }
     }
+    { // K11: the picture order counts the lists were built with, before a memory management operation 5 of this picture rewrites them
+        g.slice_refs.resize(g.n_slices + 1);
+        Stage::SliceRefs &sr = g.slice_refs[g.n_slices];
+        memset(&sr, 0, sizeof(sr));
+        const bool fieldpic = sh.field_pic != 0;
+        const Slot &cur = s.dpb.slots[s.dpb.cur_slot];
+        sr.cur_poc = fieldpic ? cur.fpoc[sh.bottom_field ? 1 : 0] : cur.poc;
+        const int16_t *lists[2] = {st != 2 ? sd.ref_slot : nullptr, st == 1 ? g.h_bext[sd.bext].ref_slot1 : nullptr};
+        const int active[2] = {sh.num_ref_idx_l0_active_minus1 + 1, sh.num_ref_idx_l1_active_minus1 + 1};
+        for (int l = 0; l < 2; l++) {
+            if (!lists[l]) continue;
+            sr.n[l] = static_cast<uint8_t>(std::min(std::max(active[l], 0), MI_MAX_REFS));
+            for (int i = 0; i < sr.n[l]; i++) sr.poc[l][i] = lists[l][i] >= 0 ? list_entry_poc(s.dpb, lists[l][i], fieldpic) : sr.cur_poc;
+        }
+    }
     g.pic_level[s.cur_pic] = std::max(g.pic_level[s.cur_pic], level);
     g.slice_level.resize(g.n_slices + 1);
     g.slice_level[g.n_slices] = level;
@@ -1396,7 +1424,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
     g.epochs.resize(d->st.size());
     for (size_t si = 0; si < d->st.size(); si++) g.epochs[si] = d->st[si].epoch;
     g.n_bext = 0;
-    g.pic_level.clear(), g.slice_level.clear(), g.pic_save_col.clear(), g.pic_wave.clear(), g.pic_init_qp.clear(), g.pic_dropped.clear();
+    g.pic_level.clear(), g.slice_level.clear(), g.pic_save_col.clear(), g.pic_wave.clear(), g.pic_init_qp.clear(), g.pic_dropped.clear(), g.slice_refs.clear(), g.pic_conceal_poc.clear();
     memset(&g.info, 0, sizeof(g.info));
     for (size_t si = 0; si < d->st.size(); si++) {
         StreamState &s = d->st[si];
@@ -1546,7 +1574,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
             // (nothing is decodable before its next IDR picture); the other streams are not affected.
             g.n_pics = pics0, g.n_slices = slices0, g.mb_used = mb0, g.info.n_macroblocks = info_mb0;
             g.n_bext = bext0;
-            g.pic_level.resize(pics0), g.pic_save_col.resize(pics0), g.pic_wave.resize(pics0), g.slice_level.resize(slices0), g.pic_init_qp.resize(pics0), g.pic_dropped.resize(pics0);
+            g.pic_level.resize(pics0), g.pic_save_col.resize(pics0), g.pic_wave.resize(pics0), g.slice_level.resize(slices0), g.pic_init_qp.resize(pics0), g.pic_dropped.resize(pics0), g.slice_refs.resize(slices0), g.pic_conceal_poc.resize(pics0);
             while (!g.fmo_pics.empty() && static_cast<int>(g.fmo_pics.back()) >= pics0) g.fmo_pics.pop_back();
             g.grey.erase(std::remove_if(g.grey.begin(), g.grey.end(), [&](const Stage::GreyFill &f) { return static_cast<int>(f.stream) == si; }), g.grey.end());
             reset_stream(s, true);
@@ -1563,6 +1591,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
     // motion is kept too (8.4.1.2.1).
     g.pic_level.resize(g.n_pics, 0), g.pic_save_col.resize(g.n_pics, 0), g.pic_wave.resize(g.n_pics, 0), g.slice_level.resize(g.n_slices, 0);
     g.pic_init_qp.resize(g.n_pics, 26), g.pic_dropped.resize(g.n_pics, 0);
+    g.slice_refs.resize(g.n_slices), g.pic_conceal_poc.resize(g.n_pics);
     for (int si = 0; si < n_streams; si++)
         for (const Slot &sl : d->st[si].dpb.slots)
             if (sl.ref)
@@ -1581,7 +1610,8 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
         });
         std::vector<SliceDesc> tmp(g.h_slices, g.h_slices + g.n_slices);
         std::vector<int> lv(g.slice_level);
-        for (int i = 0; i < g.n_slices; i++) g.h_slices[i] = tmp[order[i]], g.slice_level[i] = lv[order[i]];
+        std::vector<Stage::SliceRefs> refs(g.slice_refs); // (MbRec::slice_idx indexes the sorted table: K11's table goes with it)
+        for (int i = 0; i < g.n_slices; i++) g.h_slices[i] = tmp[order[i]], g.slice_level[i] = lv[order[i]], g.slice_refs[i] = refs[order[i]];
         g.level_first.assign(n_levels + 1, g.n_slices);
         for (int i = g.n_slices - 1; i >= 0; i--) g.level_first[g.slice_level[i]] = i;
         for (int l = n_levels - 1; l >= 0; l--) g.level_first[l] = std::min(g.level_first[l], g.level_first[l + 1]);
@@ -1609,6 +1639,13 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
                 cd.ref_slot[i] = static_cast<int16_t>(i == 0 ? g.h_pics[p].conceal_ref : -1);
                 cd.wp_lw[i] = 1, cd.wp_cw[i][0] = cd.wp_cw[i][1] = 1;
             }
+        }
+        // ... and K11's view of them: one active entry, the concealment reference, where the picture has one
+        g.slice_refs.resize(g.n_slices + g.n_pics);
+        for (int p = 0; p < g.n_pics; p++) {
+            Stage::SliceRefs &sr = g.slice_refs[g.n_slices + p];
+            memset(&sr, 0, sizeof(sr));
+            sr.cur_poc = g.pic_conceal_poc[p].cur, sr.n[0] = g.h_pics[p].conceal_ref >= 0, sr.poc[0][0] = g.pic_conceal_poc[p].ref;
         }
         uint32_t at = static_cast<uint32_t>(g.n_pics);
         for (int p = 0; p < g.n_pics; p++) g.h_cmap[p] = at, at += g.h_pics[p].n_slices;
@@ -1668,6 +1705,14 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
         g.prep_n[l] = pos - g.prep_off[l];
     }
     choose_dbprep_kernels(g);
+    // K11's device table: PicOrderCnt(entry) - PicOrderCnt(current picture) per slice of the table, list and entry, clamped to int16; 0 behind the active entries
+    for (size_t i = 0; i < g.slice_refs.size(); i++)
+        for (int l = 0; l < 2; l++)
+            for (int e = 0; e < MI_MAX_REFS; e++) {
+                const Stage::SliceRefs &sr = g.slice_refs[i];
+                const int64_t dp = e < sr.n[l] ? static_cast<int64_t>(sr.poc[l][e]) - sr.cur_poc : 0;
+                g.h_dpoc[(i * 2 + l) * MI_MAX_REFS + e] = static_cast<int16_t>(std::min<int64_t>(std::max<int64_t>(dp, -32768), 32767));
+            }
     // Uploads go to the entropy stream the next execute will use: in order with that pass's entropy kernel, and not behind
     // the batch that is still executing (the caller's stream waits for its reconstruction).  No stream of their own: the
     // runtime multiplexes streams onto 4 hardware queues by default, and a fifth stream ended up sharing a queue with one of
@@ -1683,6 +1728,11 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
         HIP_TRY(hipMemcpyAsync(g.d_pics, g.h_pics, sizeof(PicDesc) * g.n_pics, hipMemcpyHostToDevice, up));
         HIP_TRY(hipMemcpyAsync(g.d_lists, g.h_lists, sizeof(uint32_t) * pos, hipMemcpyHostToDevice, up));
         if (g.n_bext) HIP_TRY(hipMemcpyAsync(g.d_bext, g.h_bext, sizeof(BSliceExt) * g.n_bext, hipMemcpyHostToDevice, up));
+        if (g.ev_side) { // a K11 launch on the caller's stream may still be reading this set's table (the batch before last)
+            HIP_TRY(hipStreamWaitEvent(up, g.ev_side, 0));
+            g.ev_side = nullptr;
+        }
+        if (!g.slice_refs.empty()) HIP_TRY(hipMemcpyAsync(g.d_dpoc, g.h_dpoc, sizeof(int16_t) * 2 * MI_MAX_REFS * g.slice_refs.size(), hipMemcpyHostToDevice, up));
     }
     if (d->tables_dirty) {
         // a new PPS added a LevelScale set: the table only grows, so the batch still executing keeps seeing its own sets.
@@ -1822,6 +1872,9 @@ static int execute_stage(h264mi_decoder *d, int stage_idx, bool exclusive) {
         mark(0);
     } else {
         HIP_TRY(hipStreamWaitEvent(es, g.ev_upload, 0));
+        // a K11 launch on the caller's stream reads the records of the pass executed last; the pass that rewrites that set runs on this entropy stream
+        // again (two passes on: the streams alternate), and nothing else orders it behind the caller's stream
+        if (d->last_side) HIP_TRY(hipStreamWaitEvent(es, d->last_side, 0));
         if (d->pass >= MI_SETS) { // pass n-MI_SETS finished reading this set: its reconstruction kernels and its entropy stream
             HIP_TRY(hipStreamWaitEvent(es, d->ev_rec[set], 0));
             HIP_TRY(hipStreamWaitEvent(es, d->ev_col[set], 0));
@@ -1832,6 +1885,7 @@ static int execute_stage(h264mi_decoder *d, int stage_idx, bool exclusive) {
         HIP_TRY(hipEventRecord(d->ev_col[set], es)); // entropy stream through with this pass
         HIP_TRY(hipStreamWaitEvent(d->rec_stream, d->ev_ent[set], 0));
     }
+    d->last_side = nullptr; // (the serialised path runs on the caller's stream, behind the launch)
     hipStream_t rs = prof ? d->stream : d->rec_stream;
     if (d->last_pack && !prof) { // a pack launch may still be reading frames this pass rewrites (the same batch executed again)
         HIP_TRY(hipStreamWaitEvent(rs, d->last_pack, 0));
@@ -2140,6 +2194,41 @@ extern "C" int32_t h264mi_frame_fields(h264mi_decoder *d, int32_t stream, int32_
     return H264MI_OK;
 }
 
+extern "C" int32_t h264mi_frame_ref_pocs(h264mi_decoder *d, int32_t stream, int32_t frame, int32_t slice, int32_t list, int32_t *cur_poc, int32_t *pocs, int32_t cap,
+                                         int32_t *n) {
+    if (!d || !n || cap < 0 || (cap && !pocs) || (list != 0 && list != 1) || stream == H264MI_STREAM_DERIVED) return H264MI_EINVAL;
+    uint8_t *p;
+    const OutFrame *of;
+    int r = frame_ptrs(d, stream, frame, &p, &of);
+    if (r != H264MI_OK) return r;
+    if (of->field_coded) {
+        set_error("frame %d of stream %d was coded as two field pictures: reference lists of field pictures are not reported", frame, stream);
+        return H264MI_EUNSUPPORTED;
+    }
+    const Stage &g = d->stage[d->exec];
+    int idx = -1;
+    if (slice == -1) {
+        if (!d->conceal || static_cast<size_t>(g.n_slices + of->pic) >= g.slice_refs.size()) { // no concealment: no pseudo-slice, no reference
+            if (cur_poc) *cur_poc = of->pic >= 0 && static_cast<size_t>(of->pic) < g.pic_conceal_poc.size() ? g.pic_conceal_poc[of->pic].cur : of->poc;
+            *n = 0;
+            return H264MI_OK;
+        }
+        idx = g.n_slices + of->pic;
+    } else {
+        for (int i = 0; i < g.n_slices && idx < 0; i++)
+            if (static_cast<int>(g.h_slices[i].pic_idx) == of->pic && g.h_slices[i].slice_in_pic == slice) idx = i;
+        if (slice < 0 || idx < 0) {
+            set_error("frame %d of stream %d has no slice %d", frame, stream, slice);
+            return H264MI_EINVAL;
+        }
+    }
+    const Stage::SliceRefs &sr = g.slice_refs[idx];
+    if (cur_poc) *cur_poc = sr.cur_poc;
+    *n = sr.n[list];
+    for (int i = 0; i < sr.n[list] && i < cap; i++) pocs[i] = sr.poc[list][i];
+    return cap < sr.n[list] ? H264MI_ECAPACITY : H264MI_OK;
+}
+
 extern "C" int32_t h264mi_frame_read_mbrecs(h264mi_decoder *d, int32_t stream, int32_t frame, uint8_t *rec, size_t cap) {
     if (!d || !rec || stream < 0 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
     GUARD(d);
@@ -2150,7 +2239,7 @@ extern "C" int32_t h264mi_frame_read_mbrecs(h264mi_decoder *d, int32_t stream, i
             size_t n = static_cast<size_t>(pd.wmb) * pd.hmb * sizeof(MbRec);
             if (cap < n) return H264MI_ECAPACITY;
             HIP_TRY(hipStreamSynchronize(d->stream));
-            HIP_TRY(hipMemcpy(rec, d->d_mbrec[(d->pass + MI_SETS - 1) % MI_SETS] + pd.mb_base, n, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(rec, d->d_mbrec[last_record_set(d)] + pd.mb_base, n, hipMemcpyDeviceToHost));
             return H264MI_OK;
         }
     }
@@ -2161,7 +2250,7 @@ extern "C" int32_t h264mi_frame_read_mbmv1(h264mi_decoder *d, int32_t stream, in
     if (!d || !mv1 || stream < 0 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
     GUARD(d);
     Stage &g = d->stage[d->exec];
-    const int set = static_cast<int>((d->pass + MI_SETS - 1) % MI_SETS);
+    const int set = last_record_set(d);
     for (int i = 0; i < g.n_pics; i++) {
         const PicDesc &pd = g.h_pics[i];
         if (static_cast<int>(pd.stream) == stream && static_cast<int>(pd.order) == frame) {
@@ -2185,6 +2274,13 @@ extern "C" int32_t h264mi_frame_read_mbmv1(h264mi_decoder *d, int32_t stream, in
 extern "C" int32_t h264mi_internal_pack_pending(h264mi_decoder *d, int32_t *pending) {
     if (!d || !pending) return H264MI_EINVAL;
     *pending = d->last_pack ? 1 : 0;
+    return H264MI_OK;
+}
+
+// 1 while a side-information launch (K11) is recorded that the next pass's entropy stream has to wait for (last_side), else 0
+extern "C" int32_t h264mi_internal_side_pending(h264mi_decoder *d, int32_t *pending) {
+    if (!d || !pending) return H264MI_EINVAL;
+    *pending = d->last_side ? 1 : 0;
     return H264MI_OK;
 }
 

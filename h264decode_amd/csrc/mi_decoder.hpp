@@ -94,6 +94,19 @@ struct Stage {
     // B pictures take their direct-mode motion from RefPicList1[0], so that picture's slices must have been entropy-decoded
     // first: slices are launched by level -- 0: I and P slices (k_entropy), n: B slices whose co-located picture is of level
     // n - 1 or older than the batch (k_entropy_b) -- and the slice table is ordered by level.
+    // K11 (side information): per slice of the table -- same indexing as h_slices, the concealment descriptors behind the real slices included -- the
+    // picture order counts its reference lists were built with (add_slice; h264mi_frame_ref_pocs), and the device mirror k_side reads: the differences
+    // entry - current, clamped to int16, [slice][list][16], uploaded with the batch's other descriptors.  ev_side: the last k_side launch that read this
+    // set's mirror (an event of the family's descriptor tables), which the next upload into it waits for
+    struct SliceRefs {
+        int32_t cur_poc, poc[2][MI_MAX_REFS];
+        uint8_t n[2]; // active entries per list
+    };
+    std::vector<SliceRefs> slice_refs;
+    struct ConcealPoc { int32_t cur, ref; }; // per picture: its count and its concealment reference's, taken when the picture starts (start_picture)
+    std::vector<ConcealPoc> pic_conceal_poc;
+    int16_t *d_dpoc = nullptr, *h_dpoc = nullptr;
+    hipEvent_t ev_side = nullptr;
     std::vector<int> pic_level, slice_level; // per picture / per slice of the batch (slice_level in parse order, until the table is sorted)
     std::vector<uint8_t> pic_save_col;       // the picture's motion is kept for later direct prediction (k_dbprep writes its ColRec array)
     std::vector<uint8_t> pic_init_qp;        // error concealment: 26 + pic_init_qp_minus26 of the picture's PPS (QP_Y of its concealment SliceDesc)
@@ -127,7 +140,7 @@ struct DescTables {
     hipEvent_t ev[2] = {nullptr, nullptr};
     int slot = 0;
 };
-enum { OUT_PACK, OUT_CONVERT, OUT_SCALE, OUT_TENSOR, OUT_DEINT, OUT_FAMILIES }; // K6, K7, K8, K9, K10
+enum { OUT_PACK, OUT_CONVERT, OUT_SCALE, OUT_TENSOR, OUT_DEINT, OUT_SIDE, OUT_FAMILIES }; // K6, K7, K8, K9, K10, K11
 
 // A derived (deinterlaced) frame: frame k of the pseudo-stream H264MI_STREAM_DERIVED.  `of`: its source's OutFrame (what the accessors report); off: its
 // slot in the arena, in the layout of a frame slot of the source's coded size
@@ -207,6 +220,9 @@ struct h264mi_decoder {
     int x_max_wgs = 256, x_cap = 512, x_cap3 = 512; // workgroups per launch: default; capacity of the K5 ring; of the K3 flag array
     DescTables tables[OUT_FAMILIES]; // of K6 .. K10, a set each: a convert call does not wait for a pack call's table
     hipEvent_t last_pack = nullptr; // the most recent output launch (K6 .. K10): the reconstruction of a later pass may rewrite the frames it reads
+    // the most recent side-information launch (K11): it reads the macroblock records of the pass executed last, which the entropy stream of a later pass
+    // rewrites -- the next execute makes its entropy stream wait for it (the set's own fences, ev_rec / ev_col, know nothing of the caller's stream)
+    hipEvent_t last_side = nullptr;
     // K10: the derived frames of the last h264mi_items_deinterlace / h264mi_batch_deinterlace call (emptied by execute and the resets) and their arena,
     // which grows to the largest call and is kept
     std::vector<DerivedFrame> derived;
@@ -236,6 +252,9 @@ struct DeviceGuard {
         return H264MI_EDEVICE;                                          \
     }
 
+// the record set (d_mbrec / d_mv1 / ...) of the pass executed last: what the frame accessors and K11 read.  A batch that h264mi_batch_sync repeated
+// for want of residual blocks (retry_exhausted) ran again in set 0 and moved the pass counter there, so this follows it
+static inline int last_record_set(const h264mi_decoder *d) { return static_cast<int>((d->pass + MI_SETS - 1) % MI_SETS); }
 // frame `frame` of stream `stream` of the last executed batch: its Y plane in the frame pool and its geometry (mi_api.cpp); of the pseudo-stream
 // H264MI_STREAM_DERIVED: derived frame `frame`, its Y plane in the arena and its SOURCE's geometry
 int frame_ptrs(h264mi_decoder *d, int stream, int frame, uint8_t **y, const OutFrame **of);

@@ -223,6 +223,21 @@ typedef struct {
     uint32_t parity; // 0 / 1, resolved
 } DeintDesc;
 extern "C" __global__ void k_deint(const DeintDesc *descs, uint8_t *dst, int pairs_per_block);
+// K11 (k_side.hip): a list of frames -> planes of macroblock side information per 4x4 luma block, by the rule of include/h264mi.h ("Macroblock side
+// information"): a re-layout of the pictures' MbRec / MbMv1 records, no sample is read.  grid = (items, ceil(macroblock rows the largest grid touches /
+// rows_per_block)), block = 256; one lane per macroblock, four cells (8 bytes) per store on the aligned path
+typedef struct {
+    uint64_t rec;     // first MbRec of the picture, in the record set of the last executed pass
+    uint64_t mv1;     // first MbMv1 of the picture; 0: the picture has no B slices
+    uint64_t dpoc;    // the batch's table of picture order count differences: int16 [n_slices][2 lists][16 entries], indexed by MbRec::slice_idx
+    uint64_t dst_off; // byte offset of the item in the destination buffer
+    uint32_t wmb, hmb;  // the picture in macroblocks
+    uint32_t bx0, by0;  // coded 4x4 block of cell (0, 0): crop_x >> 2, crop_y >> 2
+    uint32_t gw, gh;    // the grid
+    uint32_t n_slices;  // rows of the dpoc table (a record that names none of them reads 0)
+    uint32_t vec;       // 1: bx0 % 4 == 0, gw % 4 == 0 and the item's first byte is 8-byte aligned -- a macroblock's four cells of a row are one store
+} SideDesc;
+extern "C" __global__ void k_side(const SideDesc *descs, uint8_t *dst, uint32_t planes, int rows_per_block);
 
 #ifndef MI_INTRA_WAVES
 #define MI_INTRA_WAVES 16 /* 1024 threads, 128 VGPRs per wavefront: the kernels need 120 once nothing lane-dependent is hoisted out of the macroblock loop */

@@ -1,8 +1,9 @@
 // h264decode_amd/csrc/mi_output.cpp -- the output stage of libh264mi.so: what leaves the frame pool on the device.  K6 (k_pack: tight I420), K7
 // (k_convert: NV12 / RGB), K8 (k_scale: resized) and K9 (k_tensor: model input) over a list of frames of the last executed batch, K10 (k_deint:
 // deinterlaced frames, which K6 .. K9 read like frames of the batch), and the device-free rule functions of include/h264mi.h that say what those
-// kernels compute (h264mi_output_size, _csc_resolve, _scale_taps, _fit_rect, _tensor_size, _deint_rows).  The five kernel families share ONE launch
-// discipline (stage_descs / fence_launch below); each has descriptor tables of its own.
+// kernels compute (h264mi_output_size, _csc_resolve, _scale_taps, _fit_rect, _tensor_size, _deint_rows, _side_size), and K11 (k_side: the macroblock
+// records of the batch as planes of side information).  The six kernel families share ONE launch discipline (stage_descs / fence_launch below); each
+// has descriptor tables of its own.
 // (the reference has no output process: h264/server.go:113-166 stops at the parsed slice)
 #include <algorithm>
 #include <cmath>
@@ -69,11 +70,12 @@ template <class T> static int stage_descs(h264mi_decoder *d, DescTables &t, cons
     return H264MI_OK;
 }
 
-// after the launch that reads the table stage_descs gave out: the table's event, which is also what the next pass waits for before it rewrites frames
-static int fence_launch(h264mi_decoder *d, DescTables &t) {
+// after the launch that reads the table stage_descs gave out: the table's event, which is also what the next pass waits for before it rewrites what the
+// launch reads -- frames (last_pack: K6 .. K10) or macroblock records (last_side: K11)
+static int fence_launch(h264mi_decoder *d, DescTables &t, hipEvent_t h264mi_decoder::*fence = &h264mi_decoder::last_pack) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(t.ev[t.slot], d->stream));
-    d->last_pack = t.ev[t.slot];
+    d->*fence = t.ev[t.slot];
     return H264MI_OK;
 }
 #define TRY(x)                        \
@@ -615,4 +617,97 @@ extern "C" int32_t h264mi_batch_deinterlace(h264mi_decoder *d, int32_t stream, i
         if (rate == 2) items.push_back({f.first, f.second, 1 - first});
     }
     return deint_items(d, mode, items.data(), items.size(), n_derived);
+}
+
+// ---------------------------------------------------------------- macroblock side information (K11): the rule of include/h264mi.h
+static_assert(H264MI_MB_NONE == MBT_NONE && H264MI_MB_I4x4 == MBT_I4x4 && H264MI_MB_I8x8 == MBT_I8x8 && H264MI_MB_I16x16 == MBT_I16x16 && H264MI_MB_IPCM == MBT_IPCM &&
+                  H264MI_MB_P16x16 == MBT_P16x16 && H264MI_MB_P16x8 == MBT_P16x8 && H264MI_MB_P8x16 == MBT_P8x16 && H264MI_MB_P8x8 == MBT_P8x8 &&
+                  H264MI_MB_PSKIP == MBT_PSKIP && H264MI_MB_B == MBT_B && H264MI_MB_BDIRECT == MBT_BDIRECT && H264MI_MB_BSKIP == MBT_BSKIP,
+              "the public macroblock classes are the TYPE plane's values: MBT_* of mi_types.h as the records carry them");
+static inline int popcount12(int planes) { return __builtin_popcount(static_cast<unsigned>(planes)); }
+
+extern "C" int32_t h264mi_side_size(int32_t planes, int32_t w, int32_t h, int32_t *gw, int32_t *gh, size_t *bytes) {
+    if (planes <= 0 || (planes & ~H264MI_SIDE_ALL)) {
+        set_error("side planes 0x%x: not a non-empty set of H264MI_SIDE_* bits", static_cast<unsigned>(planes));
+        return H264MI_EINVAL;
+    }
+    TRY(check_size("side information frame", w, h));
+    const int cw = (w + 3) / 4, ch = (h + 3) / 4;
+    if (gw) *gw = cw;
+    if (gh) *gh = ch;
+    if (bytes) *bytes = static_cast<size_t>(2) * cw * ch * popcount12(planes);
+    return H264MI_OK;
+}
+
+static int side_items(h264mi_decoder *d, int planes, const h264mi_side_item *items, size_t n, void *dst, size_t cap, size_t *bytes) {
+    size_t probe;
+    TRY(h264mi_side_size(planes, 4, 4, nullptr, nullptr, &probe)); // is `planes` legal at all (whatever the frames are, and if there are none)
+    if (reinterpret_cast<uintptr_t>(dst) % 2) {
+        set_error("side information destination %p: not aligned to 2 bytes", dst);
+        return H264MI_EINVAL;
+    }
+    GUARD(d);
+    const Stage &g = d->stage[d->exec];
+    const int set = last_record_set(d);
+    std::vector<SideDesc> descs(n);
+    size_t off = 0;
+    int nmx_max = 1, nmy_max = 1;
+    for (size_t i = 0; i < n; i++) {
+        const h264mi_side_item &it = items[i];
+        uint8_t *p;
+        const OutFrame *of;
+        if (it.stream == H264MI_STREAM_DERIVED || frame_ptrs(d, it.stream, it.frame, &p, &of) != H264MI_OK) {
+            set_error("side information item %zu: no frame %d of stream %d in the last executed batch (a derived frame has no macroblocks)", i, it.frame, it.stream);
+            return H264MI_EINVAL;
+        }
+        if (of->field_coded || of->pic < 0 || of->pic >= g.n_pics) {
+            set_error("side information item %zu: frame %d of stream %d was coded as two field pictures: a grid for field pictures is not implemented", i, it.frame, it.stream);
+            return H264MI_EUNSUPPORTED;
+        }
+        const PicDesc &pd = g.h_pics[of->pic];
+        int x0, y0, w, h, gw, gh;
+        size_t one;
+        crop_rect(of, 1, &x0, &y0, &w, &h);
+        TRY(h264mi_side_size(planes, w, h, &gw, &gh, &one));
+        SideDesc &sd = descs[i];
+        sd.rec = reinterpret_cast<uint64_t>(d->d_mbrec[set] + pd.mb_base);
+        sd.mv1 = pd.has_b && d->d_mv1[set] ? reinterpret_cast<uint64_t>(d->d_mv1[set] + pd.mb_base) : 0;
+        sd.dpoc = reinterpret_cast<uint64_t>(g.d_dpoc), sd.n_slices = static_cast<uint32_t>(g.slice_refs.size());
+        sd.dst_off = off;
+        sd.wmb = pd.wmb, sd.hmb = pd.hmb, sd.bx0 = static_cast<uint32_t>(x0 >> 2), sd.by0 = static_cast<uint32_t>(y0 >> 2);
+        sd.gw = static_cast<uint32_t>(gw), sd.gh = static_cast<uint32_t>(gh);
+        // (the display rectangle lies inside the coded picture, so every cell does: bx0 + gw <= 4 wmb, by0 + gh <= 4 hmb)
+        sd.vec = sd.bx0 % 4 == 0 && gw % 4 == 0 && (reinterpret_cast<uintptr_t>(dst) + off) % 8 == 0;
+        nmx_max = std::max(nmx_max, static_cast<int>(((sd.bx0 + gw - 1) >> 2) - (sd.bx0 >> 2)) + 1);
+        nmy_max = std::max(nmy_max, static_cast<int>(((sd.by0 + gh - 1) >> 2) - (sd.by0 >> 2)) + 1);
+        off += one;
+    }
+    if (bytes) *bytes = off;
+    if (off > cap) return H264MI_ECAPACITY;
+    if (n == 0) return H264MI_OK;
+    DescTables &t = d->tables[OUT_SIDE];
+    const SideDesc *dev;
+    TRY(stage_descs(d, t, descs, &dev));
+    // one lane per macroblock: about 256 macroblocks per block, whole macroblock rows (1080p: 2 rows of 120)
+    const int rows_per_block = std::max(1, std::min(256 / nmx_max, nmy_max));
+    hipLaunchKernelGGL(k_side, dim3(static_cast<uint32_t>(n), (nmy_max + rows_per_block - 1) / rows_per_block), dim3(256), 0, d->stream, dev, static_cast<uint8_t *>(dst),
+                       static_cast<uint32_t>(planes), rows_per_block);
+    TRY(fence_launch(d, t, &h264mi_decoder::last_side));
+    d->stage[d->exec].ev_side = d->last_side; // (the batch's table of picture order count differences: its next upload waits for this launch)
+    return H264MI_OK;
+}
+
+extern "C" int32_t h264mi_items_side_device(h264mi_decoder *d, int32_t planes, const h264mi_side_item *items, int32_t n, void *dst, size_t cap, size_t *bytes) {
+    if (!d || !dst || n < 0 || (n > 0 && !items)) return H264MI_EINVAL;
+    return side_items(d, planes, items, static_cast<size_t>(n), dst, cap, bytes);
+}
+
+extern "C" int32_t h264mi_batch_side_device(h264mi_decoder *d, int32_t stream, int32_t planes, void *dst, size_t cap, size_t *bytes) {
+    if (!d || !dst || stream < -1 || stream >= static_cast<int>(d->st.size())) { // (H264MI_STREAM_DERIVED too: a derived frame has no macroblocks)
+        if (stream == H264MI_STREAM_DERIVED) set_error("side information: the derived frames have no macroblocks");
+        return H264MI_EINVAL;
+    }
+    std::vector<h264mi_side_item> items;
+    for (const std::pair<int, int> &f : batch_frames(d, stream)) items.push_back({f.first, f.second});
+    return side_items(d, planes, items.data(), items.size(), dst, cap, bytes);
 }

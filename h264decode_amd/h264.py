@@ -212,6 +212,10 @@ FIT_STRETCH, FIT_LETTERBOX = 0, 1                     # H264MI_FIT_*: how the pi
 TENSOR_BGR = 1                                        # H264MI_TENSOR_BGR: colour c at channel position 2 - c
 DEINT_FIELD, DEINT_BLEND, DEINT_EDGE = 0, 1, 2        # H264MI_DEINT_*: modes of Decoder.deinterlace / frames_tensor(deinterlace=...)
 DEINT_PARITY_FIRST = -1                               # H264MI_DEINT_PARITY_FIRST: the frame's own first_parity (Decoder.frame_fields)
+# H264MI_SIDE_*: planes of Decoder.side_batch / side_items / side_info, in the order they are written; SIDE_NAMES[i] is bit 1 << i
+SIDE_NAMES = ("type", "qp", "nz", "slice", "mvx0", "mvy0", "ref0", "dpoc0", "mvx1", "mvy1", "ref1", "dpoc1")
+SIDE_ALL = 0xFFF
+MB_NONE, MB_I4x4, MB_I8x8, MB_I16x16, MB_IPCM, MB_P16x16, MB_P16x8, MB_P8x16, MB_P8x8, MB_PSKIP, MB_B, MB_BDIRECT, MB_BSKIP = range(13)  # H264MI_MB_*: values of the "type" plane
 STREAM_DERIVED = 0x40000000                           # H264MI_STREAM_DERIVED: the pseudo-stream of the derived (deinterlaced) frames
 _DEINT_NAMES = {"field": DEINT_FIELD, "blend": DEINT_BLEND, "edge": DEINT_EDGE}
 _DT_NAMES = {"u8": DT_U8, "uint8": DT_U8, "f16": DT_F16, "float16": DT_F16, "bf16": DT_BF16, "bfloat16": DT_BF16, "f32": DT_F32, "float32": DT_F32}
@@ -231,6 +235,18 @@ def _filter(filter):
             raise H264MIError(-1, "unknown scale filter %r (bilinear, area)" % (filter,))
         return _FILTER_NAMES[filter.lower()]
     return int(filter)
+
+
+def side_planes(planes):
+    """A set of H264MI_SIDE_* bits from an int or from plane names ("mvx0", "dpoc1", ...; SIDE_NAMES)."""
+    if isinstance(planes, int):
+        return planes
+    bits = 0
+    for name in ([planes] if isinstance(planes, str) else planes):
+        if name not in SIDE_NAMES:
+            raise H264MIError(-1, "unknown side-information plane %r (one of %s)" % (name, ", ".join(SIDE_NAMES)))
+        bits |= 1 << SIDE_NAMES.index(name)
+    return bits
 
 
 def _deint(mode):
@@ -680,6 +696,68 @@ class Decoder:
             assert got == out.numel()
             self.sync()
         return out
+
+    @staticmethod
+    def side_size(planes, w, h):
+        """(gw, gh, bytes) of the side information of one w x h frame: a grid of ceil(w / 4) x ceil(h / 4) cells, one int16 plane per selected plane
+        (h264mi_side_size)."""
+        gw, gh, n = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_size_t(0)
+        check(_lib.load().h264mi_side_size(side_planes(planes), w, h, ctypes.byref(gw), ctypes.byref(gh), ctypes.byref(n)))
+        return gw.value, gh.value, n.value
+
+    def ref_pocs(self, stream, frame, slice, list):
+        """(cur_poc, [PicOrderCnt of every active entry of RefPicList`list`]) of slice `slice` (its ordinal in the picture: the "slice" plane; -1: the
+        concealment pseudo-slice) of a frame of the last executed batch, as of list-building time (h264mi_frame_ref_pocs)."""
+        cur, n = ctypes.c_int32(0), ctypes.c_int32(0)
+        pocs = (ctypes.c_int32 * 32)()
+        check(self._L.h264mi_frame_ref_pocs(self._h, stream, frame, slice, list, ctypes.byref(cur), pocs, 32, ctypes.byref(n)))
+        return cur.value, [pocs[i] for i in range(n.value)]
+
+    def side_batch(self, dst_ptr, cap, planes, stream=-1):
+        """K11 in one launch: the macroblock side information (motion vectors, reference indices and picture order count distances, macroblock
+        classes, QP, coded-block flags, slice ordinals; include/h264mi.h) of every frame of the last executed batch (of one stream, or of all streams,
+        stream-major), per 4x4 luma block of the display rectangle, the selected planes in ascending bit order as tight int16 planes, frames back to
+        back in the DEVICE buffer at dst_ptr.  Returns the number of bytes."""
+        n = ctypes.c_size_t(0)
+        check(self._L.h264mi_batch_side_device(self._h, stream, side_planes(planes), dst_ptr, cap, ctypes.byref(n)))
+        return n.value
+
+    def side_items(self, dst_ptr, cap, planes, items):
+        """K11 in one launch over a list of (stream, frame) items of the last executed batch, in item order; the same frame may appear several times.
+        Returns the number of bytes."""
+        arr = (_lib.SideItem * max(len(items), 1))()
+        for a, it in zip(arr, items):
+            a.stream, a.frame = (int(v) for v in it)
+        n = ctypes.c_size_t(0)
+        check(self._L.h264mi_items_side_device(self._h, side_planes(planes), arr, len(items), dst_ptr, cap, ctypes.byref(n)))
+        return n.value
+
+    def side_info(self, stream=-1, planes=SIDE_NAMES, items=None):
+        """The side information of the frames of `stream` (-1: of all streams, stream-major) of the last executed batch, or of the (stream, frame)
+        `items`, as a list of torch int16 views [C, gh, gw] -- one per frame, C planes in ascending bit order (SIDE_NAMES) -- of ONE device tensor
+        filled by one K11 launch.  Synchronises like frames_tensor: torch's current stream before the launch, the decoder's stream after it."""
+        import torch
+        bits = side_planes(planes)
+        c = bin(bits).count("1")
+        frames = list(items) if items is not None else [(s, f) for s in (range(self.max_streams) if stream < 0 else (stream,)) for f in range(self.frame_count(s))]
+        shapes = []
+        for s, f in frames:
+            fi = self.frame_info(s, f)
+            gw, gh, _ = self.side_size(bits, fi.width, fi.height)
+            shapes.append((c, gh, gw))
+        total = sum(a * b * w for a, b, w in shapes)
+        out = torch.empty(total, dtype=torch.int16, device="cuda:%d" % self.device)
+        if total:
+            torch.cuda.current_stream(out.device).synchronize()  # whatever still uses a recycled block has finished before K11 writes it
+            got = self.side_items(out.data_ptr(), 2 * total, bits, frames)
+            assert got == 2 * total
+            self.sync()
+        views, at = [], 0
+        for shp in shapes:
+            n = shp[0] * shp[1] * shp[2]
+            views.append(out[at:at + n].view(shp))
+            at += n
+        return views
 
     def output_order(self, stream=0):
         """Indices (decoding order) of the stream's frames of the last batch in display order: ascending PicOrderCnt per

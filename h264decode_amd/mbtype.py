@@ -17,7 +17,8 @@ Reference                          -> here
 Where the reference is wrong the values here follow the spec: MbPartPredMode answers for both
 partitions and gets B macroblocks right (A32: the reference overwrites "BiPred" with "Direct"); "SP" exists in MbTypeName.
 The macroblock layer itself is decoded on the GPU: NewSliceData does not parse bits, it presents the records the entropy
-kernel wrote (h264mi_frame_read_mbrecs) under the reference's SliceData field names."""
+kernel wrote (h264mi_frame_read_mbrecs) under the reference's SliceData field names.  For whole batches the same data leaves the device as int16
+planes per 4x4 block in one launch: Decoder.side_info / side_batch (K11, include/h264mi.h "Macroblock side information")."""
 import numpy as np
 
 MB_TYPE_INFERRED = 1000  # h264/mbType.go:5

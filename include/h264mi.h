@@ -592,8 +592,8 @@ int32_t h264mi_frame_fields(h264mi_decoder *dec, int32_t stream, int32_t frame, 
  * accept it: h264mi_stream_frame_count; h264mi_frame_get_info, h264mi_frame_colour and h264mi_frame_fields, which report the SOURCE's values;
  * h264mi_frame_read with crop = 1; every frame, batch and item call of K6 .. K9 (as `stream` of a batch call it means the derived frames only: -1 is
  * still the frames of the real streams).  Every other per-frame accessor -- h264mi_frame_read with crop = 0, h264mi_frame_device_planes,
- * h264mi_frame_read_mbrecs, h264mi_frame_read_mbmv1, h264mi_frame_concealed, h264mi_stream_output_order -- returns H264MI_EINVAL for it, and so does a
- * deinterlace item that names it.  The contract: a deinterlaced and converted / scaled / tensor item is the function of "Output formats" / "Scaled
+ * h264mi_frame_read_mbrecs, h264mi_frame_read_mbmv1, h264mi_frame_concealed, h264mi_stream_output_order, h264mi_frame_ref_pocs and the side-information
+ * calls of K11 (a derived frame has no macroblocks) -- returns H264MI_EINVAL for it, and so does a deinterlace item that names it.  The contract: a deinterlaced and converted / scaled / tensor item is the function of "Output formats" / "Scaled
  * output" / "Model input" applied to the deinterlaced frame; H264MI_CSC_AUTO still resolves from the source's SPS and display size.
  * A derived frame lives in decoder-owned device memory in the layout of a frame slot of its source's coded size, of which only the display rectangle is
  * written, at the source's crop origin.  The arena grows to the largest call and is kept, is zero-filled when allocated, is counted by
@@ -610,6 +610,84 @@ typedef struct {
 } h264mi_deint_item;
 int32_t h264mi_items_deinterlace(h264mi_decoder *dec, int32_t mode, const h264mi_deint_item *items, int32_t n, int32_t *n_derived);
 int32_t h264mi_batch_deinterlace(h264mi_decoder *dec, int32_t stream, int32_t mode, int32_t rate, int32_t *n_derived);
+
+/* ---- Macroblock side information (K11): motion, references, types, QP and coded-block flags as planes, on the device ----
+ * What the reference's SliceData holds per macroblock (h264/slice.go:77-102 has no pixel in it), laid out per 4x4 luma block for every frame of a
+ * list in ONE launch.  No sample is read; this comment is the contract.
+ * Grid.  A frame of display size w x h has gw = ceil(w / 4) by gh = ceil(h / 4) cells.  Cell (j, i) (row, column) describes the coded 4x4 luma block that
+ *   holds display sample (4 i, 4 j): the block at column bx = (crop_x >> 2) + i and row by = (crop_y >> 2) + j of the coded picture, block (bx & 3, by & 3) of
+ *   macroblock (bx >> 2, by >> 2), quadrant (8x8 block) ((by & 3) >> 1) * 2 + ((bx & 3) >> 1) of it.  Every cell lies inside the coded picture.
+ * Planes.  `planes` is a bit set; the selected planes are written in ascending bit order, each gh x gw int16, row-major and tight; items follow back to
+ *   back, like K6's frames: h264mi_side_size bytes each.  The value of a cell:
+ *   H264MI_SIDE_TYPE   the macroblock's class, H264MI_MB_*.  H264MI_MB_B stands for every coded inter type of a B slice but B_Direct_16x16.
+ *   H264MI_SIDE_QP     QP_Y of the macroblock as its record holds it: 0 for I_PCM (what deblocking takes), the predicted QP for skipped macroblocks, 0 for
+ *                      H264MI_MB_NONE.
+ *   H264MI_SIDE_NZ     1 if the 4x4 luma block carries a non-zero coefficient, else 0, as the entropy kernels record it for the deblocking filter: with the
+ *                      8x8 transform all four 4x4 blocks of an 8x8 block carry the flag of that 8x8 block; every block of an I_PCM macroblock reads 1.
+ *   H264MI_SIDE_SLICE  ordinal of the macroblock's slice inside its picture, in the order the slices arrived; -1 for a concealed or undelivered macroblock.
+ *   H264MI_SIDE_MVX0, _MVY0   final list-0 vector of the block in quarter luma samples; 0 where the block's quadrant does not use list 0.
+ *   H264MI_SIDE_REF0   ref_idx_l0 of the quadrant; -1 where it does not use list 0.
+ *   H264MI_SIDE_DPOC0  PicOrderCnt(that entry of RefPicList0) - PicOrderCnt(current picture), clamped to -32768 .. 32767; 0 where unused.
+ *   H264MI_SIDE_MVX1, _MVY1, _REF1, _DPOC1   the same for list 1: 0 / 0 / -1 / 0 in pictures without B slices.
+ *   A quadrant uses list X when its macroblock is an inter macroblock and the record names a reference picture for it in that list.  Intra and
+ *   H264MI_MB_NONE macroblocks have vectors 0, references -1 and DPOC 0.  P_Skip, B_Skip and direct macroblocks report the vectors and references derived
+ *   for them (8.4.1.1, 8.4.1.2).  Concealed macroblocks (h264mi_config.conceal_errors) read H264MI_MB_PSKIP, slice -1, a zero vector and ref_idx 0, which
+ *   stands for the concealment reference, with its DPOC.
+ *   The picture order counts are those the slice's reference lists were built with (8.2.4): a memory management operation 5 in the same picture rewrites
+ *   the counts afterwards (h264mi_frame_get_info reports them rewritten); the difference is taken BEFORE that.
+ * Refused: the pseudo-stream H264MI_STREAM_DERIVED (H264MI_EINVAL); a frame coded as two field pictures (h264mi_frame_fields: field_coded) is
+ *   H264MI_EUNSUPPORTED -- its two fields are two pictures with interleaved rows, and a grid for them is a later piece of work.  Frame pictures of
+ *   streams that mix both (PAFF) are served.
+ * Out of scope: residual coefficient magnitudes, intra prediction modes, macroblock-granular output, field pictures, MBAFF (as everywhere).
+ * A launch reads the macroblock records of the last executed batch; the next h264mi_batch_execute waits for it on the device before it reuses them.
+ * When h264mi_batch_sync repeats a batch that ran out of residual blocks (h264mi_decoder_coef_pool), planes launched before that sync show the
+ * pass that failed: launch them after the sync, as one does to read the stream status. */
+#define H264MI_SIDE_TYPE 0x001
+#define H264MI_SIDE_QP 0x002
+#define H264MI_SIDE_NZ 0x004
+#define H264MI_SIDE_SLICE 0x008
+#define H264MI_SIDE_MVX0 0x010
+#define H264MI_SIDE_MVY0 0x020
+#define H264MI_SIDE_REF0 0x040
+#define H264MI_SIDE_DPOC0 0x080
+#define H264MI_SIDE_MVX1 0x100
+#define H264MI_SIDE_MVY1 0x200
+#define H264MI_SIDE_REF1 0x400
+#define H264MI_SIDE_DPOC1 0x800
+#define H264MI_SIDE_ALL 0xFFF
+#define H264MI_MB_NONE 0 /* not delivered by any slice, and not concealed */
+#define H264MI_MB_I4x4 1
+#define H264MI_MB_I8x8 2
+#define H264MI_MB_I16x16 3
+#define H264MI_MB_IPCM 4
+#define H264MI_MB_P16x16 5
+#define H264MI_MB_P16x8 6
+#define H264MI_MB_P8x16 7
+#define H264MI_MB_P8x8 8
+#define H264MI_MB_PSKIP 9
+#define H264MI_MB_B 10
+#define H264MI_MB_BDIRECT 11
+#define H264MI_MB_BSKIP 12
+/* Grid and bytes of one item (pure: no decoder, no device): *gw = ceil(w / 4), *gh = ceil(h / 4), *bytes = 2 gw gh x the number of planes; any of the three
+ * pointers may be NULL.  H264MI_EINVAL: planes == 0 or a bit outside H264MI_SIDE_ALL, w or h outside 1 .. H264MI_SCALE_MAX. */
+int32_t h264mi_side_size(int32_t planes, int32_t w, int32_t h, int32_t *gw, int32_t *gh, size_t *bytes);
+/* The reference lists behind REF and DPOC: the picture order counts of the active entries of RefPicList`list` (0 / 1) of slice `slice` (ordinal in its
+ * picture, the value of H264MI_SIDE_SLICE) of a frame of the last executed batch, and the current picture's count, both as of list-building time
+ * (an entry that names a non-existing frame of a frame_num gap reads that frame's inferred count).  *n receives the number of active entries -- 0 for I
+ * slices and for list 1 of P slices; at most cap values are written (H264MI_ECAPACITY if there are more; *n and *cur_poc are set).  slice = -1 is the
+ * concealment pseudo-slice: *n = 1 if the picture has a concealment reference (list 0 only), else 0.  Needs no device work.  H264MI_EINVAL: no such
+ * frame or slice, list outside 0 / 1, H264MI_STREAM_DERIVED; H264MI_EUNSUPPORTED: a frame coded as two field pictures.  cur_poc and pocs may be NULL. */
+int32_t h264mi_frame_ref_pocs(h264mi_decoder *dec, int32_t stream, int32_t frame, int32_t slice, int32_t list, int32_t *cur_poc, int32_t *pocs,
+                              int32_t cap, int32_t *n);
+typedef struct {
+    int32_t stream, frame; /* a frame of the last executed batch */
+} h264mi_side_item;
+/* The items of the list, in ONE launch (K11), back to back into the DEVICE buffer dst_device (aligned to 2 bytes, else H264MI_EINVAL), asynchronous on the
+ * decoder's stream.  h264mi_batch_scale_device's discipline: every item is checked and sized before anything is launched; *bytes receives the total
+ * size (also on H264MI_ECAPACITY); nothing is written on failure; n = 0 succeeds with *bytes = 0; the same frame may appear in several items. */
+int32_t h264mi_items_side_device(h264mi_decoder *dec, int32_t planes, const h264mi_side_item *items, int32_t n, void *dst_device, size_t cap, size_t *bytes);
+/* The same for every frame of the last executed batch: frames of stream `stream` (or of all streams when stream = -1, stream-major) in decoding order. */
+int32_t h264mi_batch_side_device(h264mi_decoder *dec, int32_t stream, int32_t planes, void *dst_device, size_t cap, size_t *bytes);
 
 /* Debug / test access to the intermediate macroblock records of a frame (host copy).
  * rec: 128 bytes per MB (layout: h264decode_amd/csrc/mi_types.h struct MbRec). */
@@ -657,7 +735,7 @@ const char *h264mi_last_error_string(void);
 const char *h264mi_version(void);
 
 /* Exported but NOT part of the ABI (test hooks of this repository's own suite, may change or vanish): h264mi_internal_poison,
- * h264mi_internal_deblock_plan, h264mi_internal_band_plan, h264mi_internal_pack_pending, h264mi_internal_deblock_phase_clocks, h264mi_internal_vlc_selftest. */
+ * h264mi_internal_deblock_plan, h264mi_internal_band_plan, h264mi_internal_pack_pending, h264mi_internal_side_pending, h264mi_internal_deblock_phase_clocks, h264mi_internal_vlc_selftest. */
 
 #ifdef __cplusplus
 }
