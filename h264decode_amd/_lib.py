@@ -67,7 +67,7 @@ _hooks = None
 
 
 def load_hooks():
-    """The hooks build of the same library (csrc/Makefile: mi_api.cpp with -DH264MI_TEST_HOOKS): the h264mi_internal_* entry points the tests and
+    """The hooks build of the same library (csrc/Makefile: mi_hooks.cpp with -DH264MI_TEST_HOOKS): the h264mi_internal_* entry points the tests and
     tools use.  They work on decoders of the product library too (plain structs, one HIP runtime per process); the product library itself exports
     the ABI of include/h264mi.h and nothing else."""
     global _hooks

@@ -1,5 +1,7 @@
-// h264decode_amd/csrc/mi_decoder.hpp -- the decoder's host state, shared by mi_api.cpp (front end, launch sequence, read-back) and mi_output.cpp (the
-// output stage).  Internal: nothing here is part of the ABI of include/h264mi.h, and nothing depends on H264MI_TEST_HOOKS.
+// h264decode_amd/csrc/mi_decoder.hpp -- the decoder's host state and what the host files share: mi_api.cpp (tables, create / destroy / reset, counters,
+// frame accessors), mi_picture.cpp (what a slice NAL does to the picture under construction), mi_batch.cpp (prepare, execute, sync), mi_output.cpp (the
+// output stage) and mi_hooks.cpp (test hooks and measurement switches).  Internal: nothing here is part of the ABI of include/h264mi.h, and nothing
+// depends on the hooks build.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -91,38 +93,48 @@ struct Stage {
     uint32_t *d_status = nullptr, *h_status = nullptr, *d_lists = nullptr, *h_lists = nullptr;
     BSliceExt *d_bext = nullptr, *h_bext = nullptr; // one per B slice
     int n_bext = 0;
+    int ent_kernel = MI_ENT_K_GENERAL;       // the I/P entropy kernel of level 0 (mi_entropy_kernel_choice), decided when the batch is prepared
+    int n_slices = 0, n_pics = 0, wmb_max = 0, hmb_max = 0, mbs_max = 0;
+    uint64_t mb_used = 0;
+    // ---- the batch's host-side facts: one record per picture, per slice, per reconstruction wave and per entropy level
+    struct ConcealPoc { int32_t cur, ref; };
+    struct Pic { // [n_pics], beside h_pics
+        int level = 0;  // the latest level among its slices
+        int wave = 0;   // reconstruction wave: 0 for a picture that reads no picture of this batch, else 1 + the latest wave among its references
+        uint8_t save_col = 0; // the picture's motion is kept for later direct prediction (k_dbprep writes its ColRec array)
+        uint8_t init_qp = 26; // error concealment: 26 + pic_init_qp_minus26 of the picture's PPS (QP_Y of its concealment SliceDesc)
+        uint16_t dropped = 0; // error concealment: slice NAL units whose header did not parse and that were dropped as lost (add_slice)
+        ConcealPoc conceal_poc = {0, 0}; // K11: its count and its concealment reference's when it starts: what the pseudo-slice reports (start_picture)
+    };
     // B pictures take their direct-mode motion from RefPicList1[0], so that picture's slices must have been entropy-decoded
     // first: slices are launched by level -- 0: I and P slices (k_entropy), n: B slices whose co-located picture is of level
     // n - 1 or older than the batch (k_entropy_b) -- and the slice table is ordered by level.
-    // K11 (side information): per slice of the table -- same indexing as h_slices, the concealment descriptors behind the real slices included -- the
-    // picture order counts its reference lists were built with (add_slice; h264mi_frame_ref_pocs), and the device mirror k_side reads: the differences
-    // entry - current, clamped to int16, [slice][list][16], uploaded with the batch's other descriptors.  ev_side: the last k_side launch that read this
-    // set's mirror (an event of the family's descriptor tables), which the next upload into it waits for
+    // K11 (side information): the picture order counts a slice's reference lists were built with (add_slice; h264mi_frame_ref_pocs), and the device
+    // mirror k_side reads: the differences entry - current, clamped to int16, [slice][list][16], uploaded with the batch's other descriptors.
+    // ev_side: the last k_side launch that read this set's mirror (an event of the family's descriptor tables), which the next upload into it waits for
     struct SliceRefs {
         int32_t cur_poc, poc[2][MI_MAX_REFS];
         uint8_t n[2]; // active entries per list
     };
-    std::vector<SliceRefs> slice_refs;
-    struct ConcealPoc { int32_t cur, ref; }; // per picture: its count and its concealment reference's, taken when the picture starts (start_picture)
-    std::vector<ConcealPoc> pic_conceal_poc;
+    struct Slice { // beside h_slices: in parse order until the table is sorted, the concealment pseudo-slices (one per picture) behind the real ones
+        int level = 0;
+        SliceRefs refs = {};
+    };
+    struct ListRange { uint32_t off = 0, n = 0; }; // pictures, as a range of h_lists / d_lists
+    struct Wave { ListRange all, p, b; }; // all pictures (K3, K5) / the inter pictures without B slices (k_inter) / the pictures with B slices (k_inter_b)
+    struct Level {
+        int first = 0, n = 0;   // its slices in the sorted table
+        uint32_t colsave_n = 0; // pictures whose ColRec array k_dbprep writes (what the cross-pass fence looks at)
+        ListRange prep;         // the pictures whose last slice is of this level: k_conceal and k_dbprep run on them after the level
+        int prep_kernel = MI_DBPREP_K_GENERIC; // ... and the k_dbprep kernel that does (mi_dbprep_kernel_choice)
+    };
+    std::vector<Pic> pics;
+    std::vector<Slice> slices;
+    std::vector<Wave> waves;
+    std::vector<Level> levels;
     int16_t *d_dpoc = nullptr, *h_dpoc = nullptr;
     hipEvent_t ev_side = nullptr;
-    std::vector<int> pic_level, slice_level; // per picture / per slice of the batch (slice_level in parse order, until the table is sorted)
-    std::vector<uint8_t> pic_save_col;       // the picture's motion is kept for later direct prediction (k_dbprep writes its ColRec array)
-    std::vector<uint8_t> pic_init_qp;        // error concealment: 26 + pic_init_qp_minus26 of the picture's PPS (QP_Y of its concealment SliceDesc)
     uint32_t *d_cmap = nullptr, *h_cmap = nullptr; // error concealment: per picture where its slices are in the sorted slice table (k_conceal)
-    std::vector<uint16_t> pic_dropped;       // error concealment: per picture, slice NAL units whose header did not parse and that were dropped as lost (add_slice)
-    std::vector<int> pic_wave;               // reconstruction wave of the picture: 0 for a picture that reads no picture of this batch, else 1 + the latest wave among its references
-    std::vector<int> level_first;            // first slice of each level in the sorted table (+ end marker)
-    int ent_kernel = MI_ENT_K_GENERAL;       // the I/P entropy kernel of level 0 (mi_entropy_kernel_choice), decided when the batch is prepared
-    std::vector<uint32_t> colsave_n;            // per level: pictures whose ColRec array k_dbprep writes (what the cross-pass fence looks at)
-    std::vector<uint32_t> prep_off, prep_n;     // per level: the pictures whose last slice is of that level (k_dbprep runs on them after the level), as a range of d_lists
-    std::vector<int> prep_kernel;               // per level: the kernel that runs on them (mi_dbprep_kernel_choice)
-    std::vector<uint32_t> wave_b_off, wave_b_n, wave_p_off, wave_p_n, wave_nb_off, wave_nb_n; // per wave: B pictures / inter non-B / non-B
-    int n_slices = 0, n_pics = 0, wmb_max = 0, hmb_max = 0, mbs_max = 0;
-    uint64_t mb_used = 0;
-    std::vector<std::vector<uint32_t>> waves, waves_inter;
-    std::vector<uint32_t> wave_off, wave_inter_off;
     std::vector<std::vector<OutFrame>> out; // per stream: frames of this batch in decoding order
     bool prepared = false, executed = false;
     bool harvested = true; // the entropy kernels' per-slice status words of the last execute have been looked at (harvest_status)
@@ -130,6 +142,14 @@ struct Stage {
     h264mi_batch_info info;
     hipEvent_t ev_upload = nullptr; // H2D copies of this batch are complete
     hipEvent_t ev_done = nullptr;   // the last pass over this batch has finished (nothing reads or writes its buffers any more)
+    // What a stream adds to the batch sits at the tail of every table: a mark taken before its parse, and a stream that fails is taken out again
+    struct Mark { int n_pics, n_slices, n_bext; uint64_t mb_used; int64_t info_mbs; size_t n_fmo, n_grey; };
+    Mark mark() const { return {n_pics, n_slices, n_bext, mb_used, info.n_macroblocks, fmo_pics.size(), grey.size()}; }
+    void truncate(const Mark &m, int stream) {
+        n_pics = m.n_pics, n_slices = m.n_slices, n_bext = m.n_bext, mb_used = m.mb_used, info.n_macroblocks = m.info_mbs;
+        pics.resize(m.n_pics), slices.resize(m.n_slices), fmo_pics.resize(m.n_fmo), grey.resize(m.n_grey);
+        out[stream].clear();
+    }
 };
 
 // The descriptor tables of one output kernel family: two pinned tables and their device mirrors, used alternately, each fenced by an event -- an
@@ -255,6 +275,25 @@ struct DeviceGuard {
 // the record set (d_mbrec / d_mv1 / ...) of the pass executed last: what the frame accessors and K11 read.  A batch that h264mi_batch_sync repeated
 // for want of residual blocks (retry_exhausted) ran again in set 0 and moved the pass counter there, so this follows it
 static inline int last_record_set(const h264mi_decoder *d) { return static_cast<int>((d->pass + MI_SETS - 1) % MI_SETS); }
+// where the picture in frame slot `slot` of stream `stream` leaves its motion (ColRec): a bottom field's (par 1) in the second half of the slot's array
+static inline uint64_t colrec_of(const h264mi_decoder *d, size_t stream, size_t slot, int par) {
+    return reinterpret_cast<uint64_t>(d->d_colrec + (stream * d->n_slots + slot) * d->colrec_per_slot + (par ? d->colrec_per_slot / 2 : 0));
+}
+void build_vlc(uint16_t *c, int *mismatches); // ---- mi_api.cpp
+void build_scaling(const uint8_t s4[6][16], const uint8_t s8[2][64], ScalingSet *o);
+void reset_stream(StreamState &s, bool keep_parameter_sets);
+// ---- mi_picture.cpp: one slice NAL of stream `si`, staged at `off` / `rlen`; the picture under construction is complete; a lone first field goes out
+int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref_idc, int type);
+void finish_picture(h264mi_decoder *d, int si);
+int flush_pending_field(h264mi_decoder *d, int si, const h264mi_sps *nsps = nullptr, const h264mi_pps *npps = nullptr, const h264mi_slice_header *next = nullptr);
+int ensure_b_buffers(h264mi_decoder *d); // ---- mi_batch.cpp
+int drain(h264mi_decoder *d); // both entropy streams, the reconstruction stream and the caller's stream have run dry
+// ---- mi_hooks.cpp: the measurement switches of the hooks build, called where they act; in the product build they do nothing
+void hook_create_entropy(h264mi_decoder *d, int *ent_cus); // H264MI_ENT_LDS_PAD, H264MI_ENT_CUS
+void hook_create_k5(h264mi_decoder *d);                    // H264MI_K5_WAVES
+int hook_entropy_kernel(int chosen);                       // H264MI_ENT_GENERIC
+int hook_dbprep_kernel(int chosen);                        // H264MI_DBPREP_GENERIC
+void hook_after_sync(const h264mi_decoder *d);             // H264MI_SLICE_STATS, H264MI_SLICE_TIMELINE
 // frame `frame` of stream `stream` of the last executed batch: its Y plane in the frame pool and its geometry (mi_api.cpp); of the pseudo-stream
 // H264MI_STREAM_DERIVED: derived frame `frame`, its Y plane in the arena and its SOURCE's geometry
 int frame_ptrs(h264mi_decoder *d, int stream, int frame, uint8_t **y, const OutFrame **of);

@@ -1,6 +1,6 @@
 // h264decode_amd/csrc/mi_dpb.hpp -- picture management (clause 8.2) of one stream, in plain C++: picture order counts (8.2.1), reference picture
 // lists (8.2.4), reference marking (8.2.5) with the sliding window and the frames inferred for gaps in frame_num, and the frame slots all of it
-// works on.  No device, no batch: mi_api.cpp places pictures in its tables and asks here which slot, which count, which lists.
+// works on.  No device, no batch: mi_picture.cpp places pictures in the batch's tables and asks here which slot, which count, which lists.
 #pragma once
 #include <cstdint>
 #include <vector>

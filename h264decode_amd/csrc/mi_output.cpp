@@ -672,7 +672,7 @@ static int side_items(h264mi_decoder *d, int planes, const h264mi_side_item *ite
         SideDesc &sd = descs[i];
         sd.rec = reinterpret_cast<uint64_t>(d->d_mbrec[set] + pd.mb_base);
         sd.mv1 = pd.has_b && d->d_mv1[set] ? reinterpret_cast<uint64_t>(d->d_mv1[set] + pd.mb_base) : 0;
-        sd.dpoc = reinterpret_cast<uint64_t>(g.d_dpoc), sd.n_slices = static_cast<uint32_t>(g.slice_refs.size());
+        sd.dpoc = reinterpret_cast<uint64_t>(g.d_dpoc), sd.n_slices = static_cast<uint32_t>(g.slices.size());
         sd.dst_off = off;
         sd.wmb = pd.wmb, sd.hmb = pd.hmb, sd.bx0 = static_cast<uint32_t>(x0 >> 2), sd.by0 = static_cast<uint32_t>(y0 >> 2);
         sd.gw = static_cast<uint32_t>(gw), sd.gh = static_cast<uint32_t>(gh);

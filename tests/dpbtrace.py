@@ -19,7 +19,8 @@ def build(tmp):
 
 
 def cases(sg):
-    """name -> (recipe, conceal_errors, [chunk, ...]): one batch per chunk, on one decoder."""
+    """name -> (recipe, conceal_errors, [chunk, ...]): one batch per chunk, on one decoder.  A chunk that is a list is a batch of that many
+    streams, prepared with isolation on."""
     out = {}
     for name, kw in sorted(FULL_MATRIX.items()):
         stream = sg.encode(want_recon=False, **kw)[0]
@@ -34,6 +35,12 @@ def cases(sg):
         damaged = c2.lose_pictures(sg.encode(want_recon=False, **kw)[0], lost).damaged
         out["lost_pictures/" + name] = (kw, SLICES | PICTURES | FIELDS, [damaged])
         out["lost_pictures_refused/" + name] = (kw, 0, [damaged])
+        # the rollback of a refused stream: [good, refused, good] in two batches -- without concealment the damaged stream, all of it in the first
+        # batch, is refused where its frame_num gap shows, with pictures and slices of the batch already placed -- and the same two good streams as
+        # [good, good]: the good streams' traces must not tell the two apart (rollback_parts)
+        good = _halves(sg.encode(want_recon=False, **kw)[0])
+        out["rollback/" + name] = (kw, 0, [[good[0], damaged, good[0]], [good[1], b"", good[1]]])
+        out["rollback_pair/" + name] = (kw, 0, [[g, g] for g in good])
     for name, kw in sorted(cu.CONCEAL_MATRIX.items()):
         out["lost_slices/" + name] = (kw, SLICES, [cu.make(sg.encode(want_recon=False, **kw)[0], mode="lost")[0]])
     for name, kw in sorted(c2.FIELD_CASES.items()):
@@ -43,10 +50,31 @@ def cases(sg):
     return out
 
 
+def _halves(stream):
+    """The stream as two chunks, cut at the access-unit boundary nearest the middle (by count)."""
+    aus = c2.access_units(stream)
+    return [b"".join(aus[:len(aus) // 2]), b"".join(aus[len(aus) // 2:])]
+
+
+def rollback_parts(text):
+    """A multi-stream trace as {(batch, stream): text}."""
+    out, key = {}, None
+    for line in text.splitlines():
+        if line.startswith("batch "):
+            batch = int(line.split()[1])
+        elif line.startswith("stream "):
+            key = (batch, int(line.split()[1]))
+            out[key] = []
+        else:
+            out[key].append(line)
+    return out
+
+
 def trace(prog, tmp, kw, conceal, chunks):
     """The program's output for one case."""
-    paths = []
-    for i, chunk in enumerate(chunks):
+    n_streams = len(chunks[0]) if isinstance(chunks[0], list) else 0
+    paths = ["-s%d" % n_streams] if n_streams else []
+    for i, chunk in enumerate(c for b in chunks for c in (b if n_streams else [b])):
         paths.append(os.path.join(str(tmp), "chunk%d.h264" % i))
         with open(paths[-1], "wb") as f:
             f.write(chunk)

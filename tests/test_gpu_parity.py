@@ -931,7 +931,7 @@ def _access_units(H, stream):
 
 
 def test_gpu_reconstruction_waves_follow_the_prediction_dependencies(H, sg):
-    """Pictures that do not predict from one another are reconstructed side by side (mi_api.cpp: Stage::pic_wave): an all-intra stream is ONE
+    """Pictures that do not predict from one another are reconstructed side by side (mi_picture.cpp: Stage::Pic::wave): an all-intra stream is ONE
     launch of K3 / K5 however many pictures it has, two GOPs in one batch share their waves, the B pictures between two anchors share one wave,
     and a batch that continues a GOP starts at wave 0 again -- with the pictures bit-exact in every case.  (The launch count is read through the
     profiling accessor: one K3 launch per wave.)"""

@@ -1,6 +1,6 @@
 """h264mi_frame_fields and the list of derived frames on the CPU: the product's host side built against the null device of tools/hoststub (kernels are
 not run, device memory is host memory), loaded through ctypes.  What a frame's fields are is picture management (8.2.1 and the field bookkeeping of
-mi_api.cpp), and the lifetime of the derived frames is host state: both can be held to the generator's recipes without a GPU.  What this cannot show
+mi_picture.cpp), and the lifetime of the derived frames is host state: both can be held to the generator's recipes without a GPU.  What this cannot show
 is a single sample -- tests/test_output_deinterlace.py does that on the device."""
 import ctypes
 import os

@@ -1,4 +1,4 @@
-"""The product's picture management on the CPU: mi_dpb.cpp with mi_api.cpp + mi_parse.cpp around it, built against the null device of tools/hoststub (kernels are
+"""The product's picture management on the CPU: mi_dpb.cpp with mi_picture.cpp + mi_batch.cpp + mi_parse.cpp around it, built against the null device of tools/hoststub (kernels are
 not run) prepare every matrix stream, and the PicOrderCnt / frame_num / IDR flag they report per picture (h264mi_frame_get_info) must
 be the generator's -- 8.2.1 for all three pic_order_cnt_types, memory management operation 5, frame_num gaps, B pictures in coding
 order, non-reference pictures, and a bottom field that is not at the top field's count (POC_MATRIX).  The oracle is held to the same

@@ -1,6 +1,6 @@
 """Host code under sanitizers, on the CPU (no GPU: tools/hoststub stands in for the HIP runtime, kernels are not run).
 
-The parsers, the host side of the decoder (mi_api.cpp + mi_dpb.cpp: picture boundaries, DPB, reference lists, slice-group maps,
+The parsers, the host side of the decoder (mi_picture.cpp + mi_batch.cpp + mi_dpb.cpp: picture boundaries, DPB, reference lists, slice-group maps,
 batching, staging layout, error paths) and the oracle are fed intact and damaged copies of the test matrix under AddressSanitizer + UBSan;
 any report makes the program exit non-zero.  Short slices of what tools/host_asan.sh / tools/parser_asan.sh run at length."""
 import os

@@ -1,6 +1,6 @@
 // tools/hoststub/hip/hip_runtime.h -- TEST TOOLING, never part of the product build.
-// A "null device" stand-in for the handful of HIP runtime calls the host side of libh264mi makes, so that mi_api.cpp and
-// mi_output.cpp (+ mi_dpb.cpp, mi_parse.cpp, which make none) compile with g++ under AddressSanitizer / UBSan and the host logic (NAL / header parsing, picture
+// A "null device" stand-in for the handful of HIP runtime calls the host side of libh264mi makes, so that mi_api.cpp, mi_picture.cpp, mi_batch.cpp,
+// mi_hooks.cpp and mi_output.cpp (+ mi_dpb.cpp, mi_parse.cpp, which make none) compile with g++ under AddressSanitizer / UBSan and the host logic (NAL / header parsing, picture
 // boundaries, DPB and reference lists, slice-group maps, batching, staging-buffer layout, error paths) can be driven
 // with damaged streams on a machine without a GPU (tools/host_asan.sh).  Device memory is host memory, copies are
 // memcpy, kernels are NOT run (every status word stays 0 = "no error", the pixels stay whatever the allocation held),
