@@ -86,6 +86,12 @@ def load_hooks():
         _hooks.h264mi_internal_set_dbprep_rows.restype = I32
         _hooks.h264mi_internal_dbprep_ip_rows.argtypes = [I32, I32, I32]
         _hooks.h264mi_internal_dbprep_ip_rows.restype = I32
+        # K5: wavefronts per picture of k_deblock for the launches to come; the edge functions of k_deblock / k_deblock_x alone on the device
+        # (impl, chroma, mb_edge, samples, bs, alpha, beta, tc0, out, n)
+        _hooks.h264mi_internal_set_k5_waves.argtypes = [ctypes.c_void_p, I32]
+        _hooks.h264mi_internal_set_k5_waves.restype = I32
+        _hooks.h264mi_internal_deblock_edge_probe.argtypes = [I32, I32, I32] + [ctypes.c_void_p] * 6 + [ctypes.c_int64]
+        _hooks.h264mi_internal_deblock_edge_probe.restype = I32
         # 1 while a K11 launch is recorded that the next execute's entropy stream waits for
         _hooks.h264mi_internal_side_pending.argtypes = [ctypes.c_void_p, ctypes.POINTER(I32)]
         _hooks.h264mi_internal_side_pending.restype = I32

@@ -7,6 +7,10 @@
 #include <cstdlib>
 #include <vector>
 #include "mi_decoder.hpp"
+#if defined(H264MI_TEST_HOOKS) && defined(__HIP__)
+#include "k_deblock_edge.h" // filter_edge: the edge function of k_deblock_x
+#include "k_deblock_pk.h"   // pk_luma_edge / pk_chroma_edge: the edge functions of k_deblock
+#endif
 
 #if !defined(H264MI_TEST_HOOKS)
 void hook_create_entropy(h264mi_decoder *, int *) {}
@@ -135,6 +139,111 @@ extern "C" int32_t h264mi_internal_set_dbprep_rows(h264mi_decoder *d, int32_t ro
     d->dbprep_rows = rows;
     return H264MI_OK;
 }
+// Not part of the public ABI: wavefronts per picture of k_deblock for the launches to come, clamped as hook_create_k5 clamps H264MI_K5_WAVES -- short
+// test pictures never have groups enough for a wavefront's second and third round over a picture, nor for the two-buffer plan of the last ring
+extern "C" int32_t h264mi_internal_set_k5_waves(h264mi_decoder *d, int32_t n) {
+    if (!d) return H264MI_EINVAL;
+    d->k5_max_waves = std::min(std::max(static_cast<int>(n), 1), MI_DEBLOCK8_MAX_WAVES);
+    return H264MI_OK;
+}
+
+// Not part of the public ABI: the edge functions of the two K5 kernel families alone on the device, on n lines of samples with their parameters
+// (tests/test_deblock_edges.py compares with 8.7.2.3 / 8.7.2.4 written in numpy).  No decoder: host arrays in, one launch, host arrays out.
+// samples / out: n x 8 bytes p3 p2 p1 p0 q0 q1 q2 q3 (luma) or n x 4 bytes p1 p0 q0 q1 (chroma); bs / alpha / beta / tc0: n bytes each.
+// impl 0: pk_luma_edge<MBEDGE> / pk_chroma_edge<MBEDGE> (k_deblock_pk.h): lines 2k and 2k + 1 are the two halves of lane k % 64 of wavefront k / 64.
+//   A luma lane has one bS, alpha, beta and tC0 (lane_on / lane_strong are per lane): a pair that differs is H264MI_EINVAL.  A chroma lane has one bS;
+//   its halves are the Cb and the Cr line and carry their own alpha, beta and tC0 (+ 1, as at k_deblock's call sites).
+// impl 1: filter_edge<Q, CHROMA, N> (k_deblock_edge.h), line k on lane k % 64 of wavefront k / 64, in the instantiations k_deblock_x uses: luma N = 20 with
+//   Q = 4 (macroblock edge) or 8 / 12 / 16 by wavefront (inner edges), chroma N = 12 with Q = 4 or 8.
+// n: a multiple of 128.  bS 0..4, 4 on macroblock edges only.
+#if defined(__HIP__)
+template <bool MBEDGE, bool CHROMA>
+__global__ void __launch_bounds__(64) k_edge_probe_pk(const uint8_t *samples, const uint8_t *bs, const uint8_t *alpha, const uint8_t *beta, const uint8_t *tc0, uint8_t *out) {
+    const uint32_t l0 = 2u * (blockIdx.x * 64u + threadIdx.x), l1 = l0 + 1u; // the lane's two lines; the grid covers n / 2 lanes exactly
+    const uint32_t b = bs[l0], on = b != 0u ? ~0u : 0u, strong = b == 4u ? ~0u : 0u;
+    auto pair = [](const uint8_t *a, uint32_t i, uint32_t j) { return pk2{static_cast<short>(a[i]), static_cast<short>(a[j])}; };
+    if (CHROMA) {
+        pk2 v[4];
+        for (uint32_t i = 0; i < 4; i++) v[i] = pair(samples, l0 * 4 + i, l1 * 4 + i);
+        pk_chroma_edge<MBEDGE>(v[0], v[1], v[2], v[3], pair(alpha, l0, l1), pair(beta, l0, l1), pair(tc0, l0, l1) + pk_splat(1), on, MBEDGE ? strong : 0u);
+        for (uint32_t i = 0; i < 4; i++) out[l0 * 4 + i] = static_cast<uint8_t>(v[i].x), out[l1 * 4 + i] = static_cast<uint8_t>(v[i].y);
+    } else {
+        pk2 v[8];
+        for (uint32_t i = 0; i < 8; i++) v[i] = pair(samples, l0 * 8 + i, l1 * 8 + i);
+        pk_luma_edge<MBEDGE>(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], pk_splat(alpha[l0]), pk_splat(beta[l0]), pk_splat(tc0[l0]), on, MBEDGE ? strong : 0u);
+        for (uint32_t i = 0; i < 8; i++) out[l0 * 8 + i] = static_cast<uint8_t>(v[i].x), out[l1 * 8 + i] = static_cast<uint8_t>(v[i].y);
+    }
+}
+template <int Q, bool CHROMA, int N>
+__device__ __forceinline__ void edge_probe_line(const uint8_t *samples, uint8_t *out, uint32_t l, int bs, int alpha, int beta, int tc0) {
+    constexpr int H = CHROMA ? 2 : 4; // samples on each side of the edge
+    int px[N];
+    for (int i = 0; i < N; i++) px[i] = 0;
+    for (int i = 0; i < 2 * H; i++) px[Q - H + i] = samples[l * (2 * H) + i];
+    filter_edge<Q, CHROMA>(px, bs, alpha, beta, tc0);
+    for (int i = 0; i < 2 * H; i++) out[l * (2 * H) + i] = static_cast<uint8_t>(px[Q - H + i]);
+}
+template <bool MBEDGE, bool CHROMA>
+__global__ void __launch_bounds__(64) k_edge_probe_x(const uint8_t *samples, const uint8_t *bs, const uint8_t *alpha, const uint8_t *beta, const uint8_t *tc0, uint8_t *out) {
+    const uint32_t l = blockIdx.x * 64u + threadIdx.x; // the grid covers n lines exactly
+    const int b = bs[l], a = alpha[l], be = beta[l], t = tc0[l];
+    if (CHROMA) {
+        if (MBEDGE) edge_probe_line<4, true, 12>(samples, out, l, b, a, be, t);
+        else edge_probe_line<8, true, 12>(samples, out, l, b, a, be, t);
+    } else if (MBEDGE)
+        edge_probe_line<4, false, 20>(samples, out, l, b, a, be, t);
+    else {
+        const uint32_t e = blockIdx.x % 3u; // wave-uniform: filter_edge holds ballots
+        if (e == 0) edge_probe_line<8, false, 20>(samples, out, l, b, a, be, t);
+        else if (e == 1) edge_probe_line<12, false, 20>(samples, out, l, b, a, be, t);
+        else edge_probe_line<16, false, 20>(samples, out, l, b, a, be, t);
+    }
+}
+#endif
+extern "C" int32_t h264mi_internal_deblock_edge_probe(int32_t impl, int32_t chroma, int32_t mb_edge, const uint8_t *samples, const uint8_t *bs, const uint8_t *alpha,
+                                                      const uint8_t *beta, const uint8_t *tc0, uint8_t *out, int64_t n) {
+    if (!samples || !bs || !alpha || !beta || !tc0 || !out || impl < 0 || impl > 1 || n < 128 || n % 128 != 0 || n > (int64_t(1) << 24)) return H264MI_EINVAL;
+    for (int64_t i = 0; i < n; i++)
+        if (bs[i] > 4 || (bs[i] == 4 && !mb_edge)) return H264MI_EINVAL;
+    if (impl == 0)
+        for (int64_t i = 0; i < n; i += 2)
+            if (bs[i] != bs[i + 1] || (!chroma && (alpha[i] != alpha[i + 1] || beta[i] != beta[i + 1] || tc0[i] != tc0[i + 1]))) return H264MI_EINVAL;
+#if defined(__HIP__)
+    const size_t un = static_cast<size_t>(n), line = chroma ? 4 : 8;
+    uint8_t *dev = nullptr; // samples | out | bs | alpha | beta | tc0
+    hipError_t e = hipMalloc(&dev, un * (2 * line + 4));
+    uint8_t *d_s = dev, *d_o = dev + un * line, *d_p = dev + un * 2 * line;
+    if (e == hipSuccess) e = hipMemcpy(d_s, samples, un * line, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_o, 0xA5, un * line);
+    const uint8_t *prm[4] = {bs, alpha, beta, tc0};
+    for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipMemcpy(d_p + un * k, prm[k], un, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const dim3 grid(static_cast<uint32_t>(impl == 0 ? un / 128 : un / 64)), block(64);
+#define PROBE(K, M, C) hipLaunchKernelGGL((K<M, C>), grid, block, 0, 0, d_s, d_p, d_p + un, d_p + 2 * un, d_p + 3 * un, d_o)
+        if (impl == 0) {
+            if (mb_edge) { if (chroma) PROBE(k_edge_probe_pk, true, true); else PROBE(k_edge_probe_pk, true, false); }
+            else { if (chroma) PROBE(k_edge_probe_pk, false, true); else PROBE(k_edge_probe_pk, false, false); }
+        } else {
+            if (mb_edge) { if (chroma) PROBE(k_edge_probe_x, true, true); else PROBE(k_edge_probe_x, true, false); }
+            else { if (chroma) PROBE(k_edge_probe_x, false, true); else PROBE(k_edge_probe_x, false, false); }
+        }
+#undef PROBE
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d_o, un * line, hipMemcpyDeviceToHost);
+    if (dev) hipFree(dev);
+    if (e != hipSuccess) {
+        set_error("h264mi_internal_deblock_edge_probe failed: %s", hipGetErrorString(e));
+        return H264MI_EDEVICE;
+    }
+    return H264MI_OK;
+#else
+    set_error("h264mi_internal_deblock_edge_probe: this build holds no device code");
+    return H264MI_ENODEVICE;
+#endif
+}
+
 // ... and the rule itself
 extern "C" int32_t h264mi_internal_dbprep_ip_rows(int32_t n_pics, int32_t wmb_max, int32_t hmb_max) { return mi_dbprep_ip_rows(n_pics, wmb_max, hmb_max); }
 

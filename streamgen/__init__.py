@@ -22,7 +22,8 @@ class Params(ctypes.Structure):
         ("direct_temporal", ctypes.c_int), ("weighted_bipred", ctypes.c_int), ("bskip_permille", ctypes.c_int),
         ("motion_x4", ctypes.c_int), ("motion_y4", ctypes.c_int), ("interlace_sps", ctypes.c_int), ("fn_gap_period", ctypes.c_int), ("fn_gap_declared", ctypes.c_int),
         ("b_pyramid", ctypes.c_int), ("slice_groups", ctypes.c_int), ("fmo_type", ctypes.c_int), ("aso", ctypes.c_int), ("field_pics", ctypes.c_int), ("poc_bottom_delta", ctypes.c_int), ("mono", ctypes.c_int),
-        ("wp_range", ctypes.c_int), ("poc_step", ctypes.c_int), ("mv_reach", ctypes.c_int), ("mv_margin", ctypes.c_int), ("contrast", ctypes.c_int)]
+        ("wp_range", ctypes.c_int), ("poc_step", ctypes.c_int), ("mv_reach", ctypes.c_int), ("mv_margin", ctypes.c_int), ("contrast", ctypes.c_int),
+        ("dbf_per_slice", ctypes.c_int), ("trace_deblock", ctypes.c_int)]
 
 
 def build(force=False):
@@ -49,6 +50,7 @@ def lib():
         _lib.sg_last_pocs.argtypes = [ctypes.c_void_p, ctypes.c_int]
         _lib.sg_last_features.restype = ctypes.c_uint32
         _lib.sg_last_ranges.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        _lib.sg_last_deblock_trace.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
     return _lib
 
 
@@ -96,7 +98,16 @@ RANGE_NAMES = (
     "half1_clip0", "half1_clip255", "halfj_clip0", "halfj_clip255",
     "w1_clip0", "w1_clip255", "w2_clip0", "w2_clip255", "denom_mask",
     "w_min", "w_max", "o_min", "o_max", "neg_weight", "odd_neg_offsets",
-    "tbtd_clipped", "dsf_clipped", "implicit_fallback", "implicit_pairs", "implicit_w1_min", "implicit_w1_max", "scaling_forms", "guard_zeroed", "ref_twice")
+    "tbtd_clipped", "dsf_clipped", "implicit_fallback", "implicit_pairs", "implicit_w1_min", "implicit_w1_max", "scaling_forms", "guard_zeroed", "ref_twice") + tuple(
+    # deblocking (the SG_R_DB_* counters)
+    "db_%s_%s_bs%d" % (f, pl, b) for pl in ("luma", "chroma") for f in ("filt", "rej") for b in (1, 2, 3, 4)) + (
+    "db_rej_alpha", "db_rej_beta_p", "db_rej_beta_q", "db_ap0_aq0", "db_ap0_aq1", "db_ap1_aq0", "db_ap1_aq1",
+    "db_delta_lo", "db_delta_hi", "db_delta_in", "db_p1_lo", "db_p1_hi", "db_q1_lo", "db_q1_hi",
+    "db_p0_at0", "db_p0_at255", "db_q0_at0", "db_q0_at255", "db_tc0_zero", "db_tc0_zero_ap", "db_bs4_small", "db_bs4_not_small",
+    "db_bs4_strong_p0_q0", "db_bs4_strong_p0_q1", "db_bs4_strong_p1_q0", "db_bs4_strong_p1_q1",
+    "db_index_a_min", "db_index_a_max", "db_index_b_min", "db_index_b_max", "db_index_a_clip0", "db_index_a_clip51",
+    "db_qp_odd", "db_pcm_edge", "db_cbcr_alpha", "db_pair_differs", "db_cbcr_pair_differs", "db_seg_none", "db_field_bs3",
+    "db_b_bs1_crossed", "db_b_bs1_straight", "db_b_bs0_crossed", "db_slice_offsets", "db_idc1_modified", "db_idc2_skipped")
 
 
 def last_ranges():
@@ -106,6 +117,34 @@ def last_ranges():
     out = np.zeros(n, dtype=np.int32)
     lib().sg_last_ranges(out.ctypes.data, n)
     return {k: int(v) for k, v in zip(RANGE_NAMES, out)}
+
+
+# sg_dbmb (sg_int.h), one per macroblock: what 8.7 needs to know about it
+DBMB = np.dtype(dict(names=["intra", "t8x8", "qp", "qpc", "dbf_idc", "alpha_off", "beta_off", "slice_id", "nzmask", "mv", "refid", "mv1", "refid1", "pcm"],
+                     formats=["u1", "u1", "u1", ("u1", 2), "u1", "i1", "i1", "u2", "u2", ("i2", (16, 2)), ("i4", 4), ("i2", (16, 2)), ("i4", 4), "u1"],
+                     offsets=[0, 1, 2, 3, 5, 6, 7, 8, 10, 12, 76, 92, 156, 172], itemsize=176))
+
+
+def last_deblock_trace():
+    """For every picture of the last encode(trace_deblock=1, ...) of this thread, in coding order, a dict: `planes` = (Y, Cb, Cr) before sg_deblock,
+    `after` = the same after it, `mbs` = the sg_dbmb table as a structured array [rows, columns] (intra, t8x8, qp, qpc, dbf_idc, alpha_off / beta_off
+    = filterOffsetA / B, slice_id, nzmask, refid / refid1 and mv / mv1 per 8x8 / 4x4 block, pcm), `field` = 0 frame / 1 top / 2 bottom field, `mono`,
+    `frame` = the frame of the reconstruction the picture belongs to."""
+    n = lib().sg_last_deblock_trace(-1, None, None, None, 0, None, 0)
+    out = []
+    for i in range(n):
+        info = np.zeros(8, dtype=np.int32)
+        lib().sg_last_deblock_trace(i, info.ctypes.data, None, None, 0, None, 0)
+        w, h, wmb, hmb, field, mono, frame, size = (int(v) for v in info)
+        assert size == DBMB.itemsize, (size, DBMB.itemsize)
+        before, after = np.zeros(w * h * 3 // 2, dtype=np.uint8), np.zeros(w * h * 3 // 2, dtype=np.uint8)
+        mbs = np.zeros((hmb, wmb), dtype=DBMB)
+        lib().sg_last_deblock_trace(i, None, before.ctypes.data, after.ctypes.data, before.nbytes, mbs.ctypes.data, mbs.nbytes)
+
+        def planes(a):
+            return a[:w * h].reshape(h, w), a[w * h:w * h * 5 // 4].reshape(h // 2, w // 2), a[w * h * 5 // 4:].reshape(h // 2, w // 2)
+        out.append(dict(planes=planes(before), after=planes(after), mbs=mbs, field=field, mono=mono, frame=frame))
+    return out
 
 
 SCALING_FORMS = dict(absent_first=1, absent_next=2, use_default=4, cut_short=8, wrap=16, entry_1=32, entry_255=64, full=128,

@@ -113,6 +113,12 @@ typedef struct {
     /* 1: the source is a hard 0 / 255 pattern: per 16x16 region of the (moving) scene flat, stripes or checks of period 1..3 samples,
      * in luma and in both chroma planes */
     int contrast;
+    /* deblocking stimulus: all 0 = the streams of before, byte for byte.
+     * dbf_per_slice 1: every slice draws its own disable_deblocking_filter_idc from {0, 1, 2} and its own slice_alpha_c0_offset_div2 and
+     * slice_beta_offset_div2 from -6..6 (deblock_idc, alpha_off_div2 and beta_off_div2 are then ignored) */
+    int dbf_per_slice;
+    /* 1: sg_last_deblock_trace() keeps, for every picture of this call, the planes before sg_deblock and the sg_dbmb table; changes nothing else */
+    int trace_deblock;
 } sg_params;
 
 void sg_default_params(sg_params *p);
@@ -149,6 +155,34 @@ enum {
     SG_R_SCALING_FORMS,                           /* scaling-list forms written: the SG_SF_* bits */
     SG_R_GUARD_ZEROED,                            /* levels set to 0 because they would have left the 16-bit range of 8.5.12 */
     SG_R_REF_TWICE,                               /* wp_range 2: slices' lists with one picture at two indices */
+    /* deblocking (8.7), counted in sg_deblock / edge_line on the final reconstruction of every picture.  A "line" is the samples across an edge at
+     * one position; "clipped" means that the clip changed the value */
+    SG_R_DB_FILT_LUMA,                            /* [4]: luma lines filtered with bS 1, 2, 3, 4 */
+    SG_R_DB_REJ_LUMA = SG_R_DB_FILT_LUMA + 4,     /* [4]: luma lines with bS 1 .. 4 that one of the three tests of 8.7.2.2 left alone */
+    SG_R_DB_FILT_CHROMA = SG_R_DB_REJ_LUMA + 4,   /* [4], [4]: the same for lines of Cb and Cr */
+    SG_R_DB_REJ_CHROMA = SG_R_DB_FILT_CHROMA + 4,
+    SG_R_DB_REJ_ALPHA = SG_R_DB_REJ_CHROMA + 4, SG_R_DB_REJ_BETA_P, SG_R_DB_REJ_BETA_Q, /* the first test that failed: |p0 - q0|, |p1 - p0|, |q1 - q0| */
+    SG_R_DB_APAQ,                                 /* [4]: filtered luma lines with bS < 4 by ap * 2 + aq */
+    SG_R_DB_DELTA_LO = SG_R_DB_APAQ + 4, SG_R_DB_DELTA_HI, SG_R_DB_DELTA_IN, /* bS < 4: delta clipped at -tc, at +tc, not clipped */
+    SG_R_DB_P1_LO, SG_R_DB_P1_HI, SG_R_DB_Q1_LO, SG_R_DB_Q1_HI, /* the p1 / q1 correction clipped at -tC0 / at +tC0 */
+    SG_R_DB_P0_AT0, SG_R_DB_P0_AT255, SG_R_DB_Q0_AT0, SG_R_DB_Q0_AT255, /* p0 + delta / q0 - delta clipped at 0 / at 255 */
+    SG_R_DB_TC0_ZERO, SG_R_DB_TC0_ZERO_AP,        /* filtered luma lines with bS < 4 and tC0 = 0; those of them with ap set */
+    SG_R_DB_BS4_SMALL, SG_R_DB_BS4_NOT_SMALL,     /* filtered luma lines with bS 4: |p0 - q0| < (alpha >> 2) + 2 or not */
+    SG_R_DB_BS4_STRONG,                           /* [4]: ... by (strong filter on the p side) * 2 + (on the q side) */
+    SG_R_DB_IA_MIN = SG_R_DB_BS4_STRONG + 4, SG_R_DB_IA_MAX, SG_R_DB_IB_MIN, SG_R_DB_IB_MAX, /* indexA / indexB of filtered edges */
+    SG_R_DB_IA_CLIP0, SG_R_DB_IA_CLIP51,          /* edges (per plane) whose qPav + filterOffsetA lay below 0 / above 51 */
+    SG_R_DB_QP_ODD,                               /* edges with qp_p != qp_q and an odd sum */
+    SG_R_DB_PCM_EDGE,                             /* edges with an I_PCM macroblock on either side */
+    SG_R_DB_CBCR_ALPHA,                           /* edges where Cb and Cr get different alpha */
+    SG_R_DB_PAIR_DIFFERS,                         /* luma lines 2k and 2k + 1 of a segment of which one is filtered and one is not */
+    SG_R_DB_CBCR_PAIR_DIFFERS,                    /* the Cb and the Cr line at one position of which one is filtered and one is not */
+    SG_R_DB_SEG_NONE,                             /* segments (per plane) with bS > 0 and no line filtered */
+    SG_R_DB_FIELD_BS3,                            /* field pictures: segments with bS 3 on a horizontal macroblock edge */
+    SG_R_DB_B_BS1_CROSSED, SG_R_DB_B_BS1_STRAIGHT, SG_R_DB_B_BS0_CROSSED, /* two vectors on both sides: bS 1 although the pictures pair crossed /
+                                                   * straight; bS 0 through the crossed pairing */
+    SG_R_DB_SLICE_OFFSETS,                        /* filtered edges between two slices with different filter offsets */
+    SG_R_DB_IDC1_MODIFIED,                        /* edges that changed a sample of a macroblock whose own slice has disable_deblocking_filter_idc 1 */
+    SG_R_DB_IDC2_SKIPPED,                         /* macroblock edges left alone only because of idc 2 (the neighbour is in another slice) */
     SG_R_COUNT
 };
 enum {
@@ -158,6 +192,11 @@ enum {
     SG_SF_SPS_MATRIX = 256, SG_SF_PPS_RULE_A = 512, SG_SF_PPS_RULE_B = 1024, SG_SF_PPS_SIX_LISTS = 2048
 };
 int sg_last_ranges(int32_t *dst, int cap);
+/* sg_params::trace_deblock: the pictures of the last sg_encode() call of this thread, in coding order.  Returns their number; for picture
+ * `index` info receives {width, height (of the picture: a field has half the frame's rows), macroblock columns, macroblock rows, field (0 frame,
+ * 1 top, 2 bottom), mono, the frame of recon[] the picture belongs to, sizeof(sg_dbmb)}, before / after the picture's I420 planes before and
+ * after sg_deblock, mbs its sg_dbmb table (each optional, each with its capacity in bytes) */
+int sg_last_deblock_trace(int index, int32_t info[8], uint8_t *before, uint8_t *after, size_t planes_cap, void *mbs, size_t mbs_cap);
 
 #ifdef __cplusplus
 }

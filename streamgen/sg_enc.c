@@ -55,6 +55,7 @@ typedef struct {
     uint64_t rng;
     sg_bw bw;
     int qp, prev_dqp_nz, slice_id, slice_type, skip_run, init_idc, nref_active;
+    int dbf_idc, dbf_alpha_div2, dbf_beta_div2; /* deblocking fields of the current slice's header (sg_params::dbf_per_slice: drawn per slice) */
     int ls4[6][6][16], ls8[2][6][64];
     uint8_t s4[6][16], s8[2][64]; /* scaling lists, zig-zag */
     /* scaling_matrix 2 / 3: the lists in force after the SPS (flat without a matrix), whether it had a matrix, parameter sets sent so far,
@@ -868,9 +869,10 @@ static void end_mb(enc *e) {
         d->qp = 0, d->qpc[0] = tmp.qpc[0], d->qpc[1] = tmp.qpc[1];
     } else
         d->qp = m->qp, d->qpc[0] = m->qpc[0], d->qpc[1] = m->qpc[1];
-    d->dbf_idc = (uint8_t)e->p.deblock_idc;
-    d->alpha_off = (int8_t)(2 * e->p.alpha_off_div2);
-    d->beta_off = (int8_t)(2 * e->p.beta_off_div2);
+    d->pcm = m->type == T_PCM;
+    d->dbf_idc = (uint8_t)e->dbf_idc;
+    d->alpha_off = (int8_t)(2 * e->dbf_alpha_div2);
+    d->beta_off = (int8_t)(2 * e->dbf_beta_div2);
     d->slice_id = m->slice_id;
     d->nzmask = m->nzmask;
     memcpy(d->mv, m->mv, sizeof(d->mv));
@@ -2156,10 +2158,10 @@ static void write_slice_header(enc *e, int first_mb, int idr, int frame_num, int
     }
     if (p->cabac && is_p) sg_put_ue(w, (uint32_t)e->init_idc);
     sg_put_se(w, e->slice_qp - p->qp); /* slice_qp_delta (pic_init_qp = p->qp) */
-    sg_put_ue(w, (uint32_t)p->deblock_idc);
-    if (p->deblock_idc != 1) {
-        sg_put_se(w, p->alpha_off_div2);
-        sg_put_se(w, p->beta_off_div2);
+    sg_put_ue(w, (uint32_t)e->dbf_idc);
+    if (e->dbf_idc != 1) {
+        sg_put_se(w, e->dbf_alpha_div2);
+        sg_put_se(w, e->dbf_beta_div2);
     }
     if (p->slice_groups > 1 && p->fmo_type >= 3 && p->fmo_type <= 5 && e->sg_cycle_bits) sg_put(w, (uint32_t)e->sg_cycle, e->sg_cycle_bits);
 }
@@ -2176,6 +2178,58 @@ uint32_t sg_last_features(void) { return g_feat; }
 int sg_last_ranges(int32_t *dst, int cap) {
     for (int i = 0; i < SG_R_COUNT && i < cap && dst; i++) dst[i] = g_rng[i];
     return SG_R_COUNT;
+}
+/* sg_params::trace_deblock: per thread, like the counters */
+typedef struct {
+    int32_t info[8];
+    uint8_t *before, *after; /* I420 planes of the picture */
+    sg_dbmb *mbs;
+} db_trace;
+static _Thread_local db_trace *g_trace;
+static _Thread_local int g_ntrace, g_trace_cap;
+static void trace_clear(void) {
+    for (int i = 0; i < g_ntrace; i++) free(g_trace[i].before), free(g_trace[i].after), free(g_trace[i].mbs);
+    g_ntrace = 0;
+}
+static void trace_planes(const sg_pic *p, uint8_t *dst) {
+    memcpy(dst, p->pl[0], (size_t)p->w * p->h);
+    memcpy(dst + (size_t)p->w * p->h, p->pl[1], (size_t)p->w * p->h / 4);
+    memcpy(dst + (size_t)p->w * p->h * 5 / 4, p->pl[2], (size_t)p->w * p->h / 4);
+}
+static void trace_picture(const enc *e, int frame, int after) {
+    const sg_pic *p = e->cur;
+    const size_t psz = (size_t)p->w * p->h * 3 / 2, msz = sizeof(sg_dbmb) * (size_t)e->wmb * e->hmb;
+    if (after) {
+        if (g_ntrace > 0 && g_trace[g_ntrace - 1].after) trace_planes(p, g_trace[g_ntrace - 1].after);
+        return;
+    }
+    if (g_ntrace == g_trace_cap) {
+        db_trace *n = (db_trace *)realloc(g_trace, sizeof(db_trace) * (size_t)(g_trace_cap ? 2 * g_trace_cap : 16));
+        if (!n) return;
+        g_trace = n, g_trace_cap = g_trace_cap ? 2 * g_trace_cap : 16;
+    }
+    db_trace *t = &g_trace[g_ntrace];
+    t->before = (uint8_t *)malloc(psz), t->after = (uint8_t *)malloc(psz), t->mbs = (sg_dbmb *)malloc(msz);
+    if (!t->before || !t->after || !t->mbs) {
+        free(t->before), free(t->after), free(t->mbs);
+        return;
+    }
+    const int32_t info[8] = {p->w, p->h, e->wmb, e->hmb, e->field ? 1 + e->bottom : 0, e->p.mono, frame, (int32_t)sizeof(sg_dbmb)};
+    memcpy(t->info, info, sizeof(info));
+    trace_planes(p, t->before);
+    memcpy(t->mbs, e->db, msz);
+    g_ntrace++;
+}
+int sg_last_deblock_trace(int index, int32_t info[8], uint8_t *before, uint8_t *after, size_t planes_cap, void *mbs, size_t mbs_cap) {
+    if (index >= 0 && index < g_ntrace) {
+        const db_trace *t = &g_trace[index];
+        const size_t psz = (size_t)t->info[0] * t->info[1] * 3 / 2, msz = sizeof(sg_dbmb) * (size_t)t->info[2] * t->info[3];
+        if (info) memcpy(info, t->info, sizeof(t->info));
+        if (before && planes_cap >= psz) memcpy(before, t->before, psz);
+        if (after && planes_cap >= psz) memcpy(after, t->after, psz);
+        if (mbs && mbs_cap >= msz) memcpy(mbs, t->mbs, msz);
+    }
+    return g_ntrace;
 }
 int sg_last_pocs(int32_t *dst, int cap) {
     for (int i = 0; i < g_npocs && i < cap && dst; i++) dst[i] = g_pocs[i];
@@ -2806,6 +2860,8 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
     g_feat = 0, g_npocs = 0;
     memset(g_rng, 0, sizeof(g_rng));
     g_rng[SG_R_W_MIN] = g_rng[SG_R_O_MIN] = g_rng[SG_R_IMPLICIT_W1_MIN] = 1 << 20, g_rng[SG_R_W_MAX] = g_rng[SG_R_O_MAX] = g_rng[SG_R_IMPLICIT_W1_MAX] = -(1 << 20);
+    g_rng[SG_R_DB_IA_MIN] = g_rng[SG_R_DB_IB_MIN] = 1 << 20, g_rng[SG_R_DB_IA_MAX] = g_rng[SG_R_DB_IB_MAX] = -(1 << 20);
+    trace_clear();
     const int pstep = p->poc_step > 1 && p->poc_type != 2 ? (p->poc_step > 31 ? 31 : p->poc_step) : 1;
     /* coding order.  Without B pictures it is the display order.  With them every (bframes + 1)-th picture is an anchor
      * (I or P) and the pictures between two anchors are B pictures coded right after the later anchor -- unless that anchor
@@ -3025,6 +3081,11 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
             if (e->slice_qp != p->qp) g_feat |= 1u << 13;
             sg_bw_init(&e->bw, rbsp, slice_cap);
             if (p->wp_range && !intra_pic && (bpic ? p->weighted_bipred == 1 : p->weighted_pred != 0)) draw_weights(e, bpic);
+            e->dbf_idc = p->deblock_idc, e->dbf_alpha_div2 = p->alpha_off_div2, e->dbf_beta_div2 = p->beta_off_div2;
+            if (p->dbf_per_slice) { /* (idc 1 carries no offsets: the macroblocks of such a slice keep 0, which nothing reads) */
+                e->dbf_idc = rnd_range(e, 0, 2);
+                e->dbf_alpha_div2 = e->dbf_idc == 1 ? 0 : rnd_range(e, -6, 6), e->dbf_beta_div2 = e->dbf_idc == 1 ? 0 : rnd_range(e, -6, 6);
+            }
             write_slice_header(e, first, idr, frame_num, idr_id, pic_poc & (p->poc_step > 1 ? 65535 : 255));
             e->qp = e->slice_qp, e->prev_dqp_nz = 0, e->skip_run = 0;
             if (p->cabac) {
@@ -3109,7 +3170,11 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
             }
             out += n;
         }
-        sg_deblock(e->cur, e->db, e->wmb, e->hmb);
+        if (p->trace_deblock) trace_picture(e, t, 0);
+        sg_db_count = g_rng;
+        sg_deblock(e->cur, e->db, e->wmb, e->hmb, p->mono);
+        sg_db_count = NULL;
+        if (p->trace_deblock) trace_picture(e, t, 1);
         if (e->field) {
             e->cur->is_ref = e->nal_ref_idc ? 1 : 0; /* (short-term or not: what colZeroFlag asks of RefPicList1[0]; the window lives on the frames) */
             if (e->nal_ref_idc && p->bframes > 0) { /* a later B field may take this field as its co-located picture */

@@ -83,8 +83,11 @@ typedef struct {
     int32_t refid[4];
     int16_t mv1[16][2]; /* list 1 of B macroblocks; refid / refid1 = -1 where a list is not used */
     int32_t refid1[4];
+    uint8_t pcm; /* I_PCM (qp is 0 then) */
 } sg_dbmb;
-void sg_deblock(sg_pic *p, const sg_dbmb *mbs, int wmb, int hmb);
+void sg_deblock(sg_pic *p, const sg_dbmb *mbs, int wmb, int hmb, int mono);
+/* while set, sg_deblock() counts into the SG_R_DB_* entries of this array of SG_R_COUNT counters.  Per thread. */
+extern _Thread_local int32_t *sg_db_count;
 /* field pictures: coefficients in field scan order (8.5.6, 8.5.7); deblocking with the rules for field macroblocks (8.7.2.1:
  * horizontal edges of intra macroblocks get bS 3, vertical vector differences count from 4 quarter FRAME samples = 2 field ones) */
 void sg_set_field_mode(int on);

@@ -583,7 +583,10 @@ void sg_quant_chroma_dc(const int *s, int ls00, int qpc, double dead, int16_t *l
 }
 
 /* ------------------------------------------------------------------ deblocking 8.7 */
-static void edge_line(uint8_t *q0p, int step, int bs, int alpha, int beta, int tc0, int is_chroma) {
+_Thread_local int32_t *sg_db_count;
+#define DBC(i) do { if (sg_db_count) sg_db_count[i]++; } while (0)
+/* returns bit 0: the line was filtered, bit 1: a sample on the p side changed */
+static int edge_line(uint8_t *q0p, int step, int bs, int alpha, int beta, int tc0, int is_chroma) {
     int p[4], q[4];
     for (int i = 0; i < 4; i++) {
         if (is_chroma && i >= 2) {
@@ -593,7 +596,12 @@ static void edge_line(uint8_t *q0p, int step, int bs, int alpha, int beta, int t
         p[i] = q0p[-(i + 1) * step];
         q[i] = q0p[i * step];
     }
-    if (abs(p[0] - q[0]) >= alpha || abs(p[1] - p[0]) >= beta || abs(q[1] - q[0]) >= beta) return;
+    if (abs(p[0] - q[0]) >= alpha || abs(p[1] - p[0]) >= beta || abs(q[1] - q[0]) >= beta) {
+        DBC((is_chroma ? SG_R_DB_REJ_CHROMA : SG_R_DB_REJ_LUMA) + bs - 1);
+        DBC(abs(p[0] - q[0]) >= alpha ? SG_R_DB_REJ_ALPHA : (abs(p[1] - p[0]) >= beta ? SG_R_DB_REJ_BETA_P : SG_R_DB_REJ_BETA_Q));
+        return 0;
+    }
+    DBC((is_chroma ? SG_R_DB_FILT_CHROMA : SG_R_DB_FILT_LUMA) + bs - 1);
     int np[3] = {p[0], p[1], p[2]}, nq[3] = {q[0], q[1], q[2]};
     if (bs == 4) {
         if (is_chroma) {
@@ -613,30 +621,50 @@ static void edge_line(uint8_t *q0p, int step, int bs, int alpha, int beta, int t
                 nq[2] = (2 * q[3] + 3 * q[2] + q[1] + q[0] + p[0] + 4) >> 3;
             } else
                 nq[0] = (2 * q[1] + q[0] + p[1] + 2) >> 2;
+            DBC(strong ? SG_R_DB_BS4_SMALL : SG_R_DB_BS4_NOT_SMALL);
+            DBC(SG_R_DB_BS4_STRONG + 2 * (strong && abs(p[2] - p[0]) < beta) + (strong && abs(q[2] - q[0]) < beta));
         }
     } else {
         int tc = tc0;
         if (is_chroma)
             tc += 1;
         else {
-            if (abs(p[2] - p[0]) < beta) {
+            const int ap = abs(p[2] - p[0]) < beta, aq = abs(q[2] - q[0]) < beta;
+            if (ap) {
+                const int c = (p[2] + ((p[0] + q[0] + 1) >> 1) - 2 * p[1]) >> 1;
                 tc++;
-                np[1] = p[1] + iclip((p[2] + ((p[0] + q[0] + 1) >> 1) - 2 * p[1]) >> 1, -tc0, tc0);
+                np[1] = p[1] + iclip(c, -tc0, tc0);
+                if (c < -tc0) DBC(SG_R_DB_P1_LO);
+                if (c > tc0) DBC(SG_R_DB_P1_HI);
             }
-            if (abs(q[2] - q[0]) < beta) {
+            if (aq) {
+                const int c = (q[2] + ((p[0] + q[0] + 1) >> 1) - 2 * q[1]) >> 1;
                 tc++;
-                nq[1] = q[1] + iclip((q[2] + ((p[0] + q[0] + 1) >> 1) - 2 * q[1]) >> 1, -tc0, tc0);
+                nq[1] = q[1] + iclip(c, -tc0, tc0);
+                if (c < -tc0) DBC(SG_R_DB_Q1_LO);
+                if (c > tc0) DBC(SG_R_DB_Q1_HI);
             }
+            DBC(SG_R_DB_APAQ + 2 * ap + aq);
+            if (tc0 == 0) DBC(SG_R_DB_TC0_ZERO);
+            if (tc0 == 0 && ap) DBC(SG_R_DB_TC0_ZERO_AP);
         }
-        int dlt = iclip((4 * (q[0] - p[0]) + (p[1] - q[1]) + 4) >> 3, -tc, tc);
+        const int raw = (4 * (q[0] - p[0]) + (p[1] - q[1]) + 4) >> 3;
+        int dlt = iclip(raw, -tc, tc);
+        DBC(raw < -tc ? SG_R_DB_DELTA_LO : (raw > tc ? SG_R_DB_DELTA_HI : SG_R_DB_DELTA_IN));
+        if (p[0] + dlt < 0) DBC(SG_R_DB_P0_AT0);
+        if (p[0] + dlt > 255) DBC(SG_R_DB_P0_AT255);
+        if (q[0] - dlt < 0) DBC(SG_R_DB_Q0_AT0);
+        if (q[0] - dlt > 255) DBC(SG_R_DB_Q0_AT255);
         np[0] = clip255(p[0] + dlt);
         nq[0] = clip255(q[0] - dlt);
     }
-    int n = is_chroma ? 1 : 3;
+    int n = is_chroma ? 1 : 3, changed = 0;
     for (int i = 0; i < n; i++) {
+        changed |= np[i] != p[i];
         q0p[-(i + 1) * step] = (uint8_t)np[i];
         q0p[i * step] = (uint8_t)nq[i];
     }
+    return 1 | changed << 1;
 }
 /* motion of one 4x4 block as a sorted set of (picture, vector) pairs: which list a picture came through is irrelevant (8.7.2.1) */
 typedef struct {
@@ -661,10 +689,15 @@ static int strength(const sg_dbmb *mp, int bp, const sg_dbmb *mq, int bq, int on
     int straight = P.pic[0] == Q.pic[0] && P.pic[1] == Q.pic[1], crossed = P.pic[0] == Q.pic[1] && P.pic[1] == Q.pic[0];
     if (!straight && !crossed) return 1;
     if (straight && close_mv(&P, 0, &Q, 0) && close_mv(&P, 1, &Q, 1)) return 0;
-    if (crossed && close_mv(&P, 0, &Q, 1) && close_mv(&P, 1, &Q, 0)) return 0;
+    if (crossed && close_mv(&P, 0, &Q, 1) && close_mv(&P, 1, &Q, 0)) {
+        DBC(SG_R_DB_B_BS0_CROSSED);
+        return 0;
+    }
+    if (crossed) DBC(SG_R_DB_B_BS1_CROSSED);
+    if (straight) DBC(SG_R_DB_B_BS1_STRAIGHT);
     return 1;
 }
-void sg_deblock(sg_pic *pic, const sg_dbmb *mbs, int wmb, int hmb) {
+void sg_deblock(sg_pic *pic, const sg_dbmb *mbs, int wmb, int hmb, int mono) {
     for (int my = 0; my < hmb; my++)
         for (int mx = 0; mx < wmb; mx++) {
             const sg_dbmb *cur = &mbs[my * wmb + mx];
@@ -673,7 +706,10 @@ void sg_deblock(sg_pic *pic, const sg_dbmb *mbs, int wmb, int hmb) {
                 const sg_dbmb *nb = NULL;
                 if (vertical_edges && mx > 0) nb = cur - 1;
                 if (!vertical_edges && my > 0) nb = cur - wmb;
-                if (nb && cur->dbf_idc == 2 && nb->slice_id != cur->slice_id) nb = NULL;
+                if (nb && cur->dbf_idc == 2 && nb->slice_id != cur->slice_id) {
+                    DBC(SG_R_DB_IDC2_SKIPPED);
+                    nb = NULL;
+                }
                 for (int e = 0; e < 4; e++) {
                     const sg_dbmb *pm = e ? cur : nb;
                     if (!pm) continue;
@@ -684,20 +720,53 @@ void sg_deblock(sg_pic *pic, const sg_dbmb *mbs, int wmb, int hmb) {
                         int bp = vertical_edges ? 4 * s + (e ? e - 1 : 3) : 4 * (e ? e - 1 : 3) + s;
                         bs[s] = strength(pm, bp, cur, bq, e == 0, vertical_edges);
                         any |= bs[s];
+                        if (g_field && e == 0 && !vertical_edges && bs[s] == 3) DBC(SG_R_DB_FIELD_BS3);
                     }
                     if (!any) continue;
-                    for (int plane = 0; plane < 3; plane++) {
+                    int did[3][16], filtered = 0, p_changed = 0, alpha_of[3] = {0, 0, 0}; /* did[plane][line]: what edge_line returned */
+                    memset(did, 0, sizeof(did));
+                    for (int plane = 0; plane < (mono ? 1 : 3); plane++) { /* (monochrome: the chroma planes of 128 are no part of the picture) */
                         if (plane && (e & 1)) break;
                         int stride = plane ? pic->w / 2 : pic->w, mbsz = plane ? 8 : 16;
                         int qa = plane ? (pm->qpc[plane - 1] + cur->qpc[plane - 1] + 1) >> 1 : (pm->qp + cur->qp + 1) >> 1;
                         int ia = iclip(qa + cur->alpha_off, 0, 51), ib = iclip(qa + cur->beta_off, 0, 51);
                         uint8_t *org = pic->pl[plane] + my * mbsz * stride + mx * mbsz;
                         int epos = plane ? e * 2 : e * 4;
+                        alpha_of[plane] = sg_alpha[ia];
                         for (int i = 0; i < mbsz; i++) {
                             int b = bs[plane ? i >> 1 : i >> 2];
                             if (!b) continue;
                             uint8_t *q0 = vertical_edges ? org + i * stride + epos : org + epos * stride + i;
-                            edge_line(q0, vertical_edges ? 1 : stride, b, sg_alpha[ia], sg_beta[ib], b < 4 ? sg_tc0[ia][b - 1] : 0, plane != 0);
+                            did[plane][i] = edge_line(q0, vertical_edges ? 1 : stride, b, sg_alpha[ia], sg_beta[ib], b < 4 ? sg_tc0[ia][b - 1] : 0, plane != 0);
+                            filtered |= did[plane][i] & 1, p_changed |= did[plane][i] >> 1;
+                        }
+                        if (sg_db_count) {
+                            int32_t *c = sg_db_count;
+                            if (ia < c[SG_R_DB_IA_MIN]) c[SG_R_DB_IA_MIN] = ia;
+                            if (ia > c[SG_R_DB_IA_MAX]) c[SG_R_DB_IA_MAX] = ia;
+                            if (ib < c[SG_R_DB_IB_MIN]) c[SG_R_DB_IB_MIN] = ib;
+                            if (ib > c[SG_R_DB_IB_MAX]) c[SG_R_DB_IB_MAX] = ib;
+                            c[SG_R_DB_IA_CLIP0] += qa + cur->alpha_off < 0, c[SG_R_DB_IA_CLIP51] += qa + cur->alpha_off > 51;
+                            for (int s = 0; s < 4; s++) { /* segments of 4 luma / 2 chroma lines */
+                                const int n = mbsz / 4;
+                                int f = 0;
+                                for (int i = 0; i < n; i++) f += did[plane][s * n + i] & 1;
+                                c[SG_R_DB_SEG_NONE] += bs[s] && !f;
+                                if (!plane) c[SG_R_DB_PAIR_DIFFERS] += ((did[0][4 * s] ^ did[0][4 * s + 1]) & 1) + ((did[0][4 * s + 2] ^ did[0][4 * s + 3]) & 1);
+                            }
+                        }
+                    }
+                    if (sg_db_count) {
+                        int32_t *c = sg_db_count;
+                        c[SG_R_DB_QP_ODD] += pm->qp != cur->qp && ((pm->qp + cur->qp) & 1);
+                        c[SG_R_DB_PCM_EDGE] += pm->pcm || cur->pcm;
+                        if (!(e & 1) && !mono) {
+                            c[SG_R_DB_CBCR_ALPHA] += alpha_of[1] != alpha_of[2];
+                            for (int i = 0; i < 8; i++) c[SG_R_DB_CBCR_PAIR_DIFFERS] += (did[1][i] ^ did[2][i]) & 1;
+                        }
+                        if (e == 0) {
+                            c[SG_R_DB_SLICE_OFFSETS] += filtered && pm->slice_id != cur->slice_id && (pm->alpha_off != cur->alpha_off || pm->beta_off != cur->beta_off);
+                            c[SG_R_DB_IDC1_MODIFIED] += p_changed && pm->dbf_idc == 1;
                         }
                     }
                 }

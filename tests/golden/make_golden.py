@@ -72,6 +72,22 @@ def value_range_vectors():
 
 value_range_vectors()
 
+
+def deblock_vectors():
+    """tests/deblockutil.py: the recipes whose deblocking branches are counted, and the geometries k_deblock distinguishes."""
+    import deblockutil
+    out = {}
+    for name in sorted(deblockutil.RECIPES):
+        s, rec, _ = streamgen.encode(**deblockutil.RECIPES[name])
+        frames, _ = oracle.decode(s, crop=False)
+        assert (frames == rec).all(), name
+        out[name] = {"stream_md5": hashlib.md5(s).hexdigest(), "frames_md5": hashlib.md5(rec.tobytes()).hexdigest(), "stream_bytes": len(s)}
+    json.dump(out, open(os.path.join(HERE, "deblock_md5.json"), "w"), indent=1, sort_keys=True)
+    print("wrote", len(out), "deblocking vectors")
+
+
+deblock_vectors()
+
 # the characterisation trace of the product's picture management (tests/dpbtrace.py; CPU, null device): MD5 of the trace text of every case.  It
 # pins what the code DOES, so it is written once and not again for a change that is meant to keep behaviour.  Only with --dpb-trace.
 if "--dpb-trace" in sys.argv[1:]:
