@@ -9,13 +9,7 @@
 // Absent from the reference (only the slice-header fields are parsed: h264/slice.go:1021-1027).
 #include <hip/hip_runtime.h>
 #include "mi_kernels.h"
-
-#define WAVE_SYNC()                                            \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                       \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
-    } while (0)
+#include "k_common.h" // WAVE_SYNC, v4u, xcd_pic_block
 
 // 8.7.2.1 with one list (I / P pictures)
 // (strong: the bS of an intra macroblock edge -- 4, but 3 on the horizontal macroblock edges of a field picture; vlim: the vertical vector
@@ -70,11 +64,8 @@ extern "C" __global__ void __launch_bounds__(256) k_dbprep(const uint32_t *pic_l
     __shared__ PrepSub subs[4][4];
     __shared__ uint8_t s_alpha[52], s_beta[52], s_tc0[52][4];
     const int tid = static_cast<int>(threadIdx.x), wave = tid >> 6, lane = tid & 63, sub = lane >> 4, li = lane & 15;
-    // XCD-aware order: workgroups are dealt round-robin to the 8 XCDs, each with its own L2, and a macroblock's upper neighbour is a record another
-    // workgroup of the picture loads as its own -- so an XCD takes WHOLE pictures (picture p goes to XCD p mod 8; grid.y is a multiple of 8), and the row
-    // above comes out of the L2 that fetched it a moment ago
-    const uint32_t w = blockIdx.y * gridDim.x + blockIdx.x, in_xcd = w >> 3;
-    const uint32_t pic = (in_xcd / gridDim.x) * 8u + (w & 7u), blk = in_xcd % gridDim.x;
+    uint32_t pic, blk; // XCD-aware order: the row above comes out of the L2 that fetched it a moment ago
+    xcd_pic_block(pic, blk);
     if (pic >= static_cast<uint32_t>(n_pics)) return;
     const PicDesc *pd = &pics[pic_list[pic]];
     const int wmb = static_cast<int>(pd->wmb), nmb = wmb * static_cast<int>(pd->hmb);
@@ -90,7 +81,6 @@ extern "C" __global__ void __launch_bounds__(256) k_dbprep(const uint32_t *pic_l
     const MbMv1 *recs1 = two ? mbmv1 + pd->mb_base : nullptr;
     DbPrm *outs = out + pd->mb_base;
     PrepSub *ss = &subs[wave][sub];
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
     for (int it = wave; it < MI_DBPREP_MBS / 4; it += 4) {
         const int mb = mb_first + it * 4 + sub;
         const bool valid = mb < nmb;
@@ -279,10 +269,8 @@ extern "C" __global__ void __launch_bounds__(64) k_dbprep_ip(const uint32_t *pic
     __shared__ __attribute__((aligned(16))) uint32_t st[IP_WAVE_DWORDS];
     __shared__ uint32_t s_at[52], s_b[52]; // alpha | tC0 for bS 1..3 << 8 (by indexA); beta (by indexB)
     const int lane = static_cast<int>(threadIdx.x);
-    // the XCD-aware order of k_dbprep: workgroups are dealt round-robin to the 8 XCDs, and an XCD takes WHOLE pictures, so that the record to the left of
-    // a strip comes out of the L2 that fetches it for the strip it belongs to
-    const uint32_t w = blockIdx.y * gridDim.x + blockIdx.x, in_xcd = w >> 3;
-    const uint32_t pic = (in_xcd / gridDim.x) * 8u + (w & 7u), strip = in_xcd % gridDim.x;
+    uint32_t pic, strip; // XCD-aware order: the record to the left of a strip comes out of the L2 that fetches it for the strip it belongs to
+    xcd_pic_block(pic, strip);
     if (pic >= static_cast<uint32_t>(n_pics)) return;
     const PicDesc *pd = &pics[pic_list[pic]];
     const int wmb = static_cast<int>(pd->wmb), hmb = static_cast<int>(pd->hmb);
@@ -294,7 +282,6 @@ extern "C" __global__ void __launch_bounds__(64) k_dbprep_ip(const uint32_t *pic
         s_b[lane] = tab->beta[lane];
     }
     WAVE_SYNC();
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
     const MbRec *recs = mbrec + pd->mb_base;
     DbPrm *outs = out + pd->mb_base;
     const bool fieldpic = pd->field != 0;

@@ -8,7 +8,7 @@
 // before the horizontal-edge pass of the same step.
 //
 // Mapping (round 5).  One workgroup owns a picture; a wavefront owns a GROUP of 8 consecutive macroblock rows ("sub-rows"), 8 lanes
-// per macroblock -- 9 wavefronts and ONE round for 1080p.  At step t sub-row s works on macroblock column x = t - s.  The edge filters
+// per macroblock -- for 1080p 9 groups on 8 wavefronts (MI_DEBLOCK8_MAX_WAVES), TWO rounds: the ninth group is wavefront 0's second (mi_deblock8_plan).  At step t sub-row s works on macroblock column x = t - s.  The edge filters
 // run on two lines at once in packed 16-bit arithmetic (k_deblock_pk.h): in the vertical-edge pass lane j owns luma rows 2j, 2j + 1 (one
 // boundary-strength segment) and chroma row j of Cb and of Cr (one half each); in the horizontal-edge pass luma columns 2j, 2j + 1 and
 // chroma column j.  The transposition between the passes goes through an LDS window of four macroblock columns per sub-row whose luma
@@ -31,14 +31,8 @@
 // Absent from the reference (only the slice-header fields are parsed: h264/slice.go:1021-1027).
 #include <hip/hip_runtime.h>
 #include "mi_kernels.h"
+#include "k_common.h" // WAVE_SYNC, OPAQUE, STAMP, the address-space-1 typedefs and GLD* / GST*, PicPlace
 #include "k_deblock_pk.h"
-
-#define WAVE_SYNC()                                            \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                       \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
-    } while (0)
 
 struct Db8Shared { // followed in dynamic LDS by the wavefronts' windows and the hand-off rings
     int prog[MI_DEBLOCK8_MAX_GROUPS]; // per group: macroblock columns of its LAST row whose rows 12..15 are in the ring
@@ -58,15 +52,6 @@ static_assert(MI_DEBLOCK8_WAVE_BYTES == 9 * T_BYTES + 2 * 8 * sizeof(DbPrm) && T
 // ring slot: rows 12..15 of one macroblock column in window format: row pairs 6, 7 (32 bytes each), chroma rows 6, 7 (16 bytes each)
 static_assert(MI_DEBLOCK_SLOT_BYTES == 96, "LDS layout constants");
 
-typedef __attribute__((address_space(1))) uint8_t g8;
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-typedef uint32_t v2u __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(1))) v4u g_uint4;
-typedef __attribute__((address_space(1))) v2u g_uint2;
-#define GLD16(base, off) (*reinterpret_cast<const g_uint4 *>((base) + (off)))
-#define GLD8(base, off) (*reinterpret_cast<const g_uint2 *>((base) + (off)))
-#define GST16(base, off, v) (*reinterpret_cast<g_uint4 *>((base) + (off)) = (v))
-#define GST8(base, off, v) (*reinterpret_cast<g_uint2 *>((base) + (off)) = (v))
 // Loads are issued through inline assembly and waited for by ONE explicit s_waitcnt at the end of a step: gfx9 counts loads and stores in one
 // in-order counter, and the compiler, which cannot see across the loop's back edge which registers a load may still be writing, guards their
 // every use -- a guard behind freshly issued memory operations puts their whole round trip (18 k clocks measured) into the step.  The
@@ -107,16 +92,7 @@ typedef __attribute__((address_space(3))) uint32_t l_uint1;
 #define LST8(off, v) (*reinterpret_cast<l_uint2 *>(lds + (off)) = (v))
 #define LST4(off, v) (*reinterpret_cast<l_uint1 *>(lds + (off)) = (v))
 #define LST1(off, v) (lds[off] = static_cast<uint8_t>(v))
-// keeps lane-dependent values from being hoisted out of the step loop
-#define OPAQUE(x) asm volatile("" : "+v"(x))
 #define PERM(hi, lo, sel) __builtin_amdgcn_perm(static_cast<uint32_t>(hi), static_cast<uint32_t>(lo), static_cast<uint32_t>(sel))
-// diagnostic build (-DMI_DB_STATS): shader clocks per phase of the step loop, summed over one wavefront's steps, added to xstatus[8 + phase]
-// by the wavefront of group 0 of every picture (tools/deblock_phase_probe.py)
-#if defined(MI_DB_STATS)
-#define STAMP(k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); st_acc[k] += static_cast<uint32_t>(now_ - st_last); st_last = now_; } while (0)
-#else
-#define STAMP(k) do { } while (0)
-#endif
 
 // byte k of w in both halves
 __device__ __forceinline__ pk2 splat_byte(uint32_t w, int k) { return pk_from(PERM(0u, w, 0x0C000C00u + 0x00010001u * static_cast<uint32_t>(k))); }
@@ -135,12 +111,11 @@ extern "C" __global__ void __launch_bounds__(MI_DEBLOCK8_MAX_WAVES * 64) k_deblo
     int lane_v = tid & 63;
     const PicDesc *pd = &pics[pic_list[blockIdx.x]];
     const int wmb = static_cast<int>(pd->wmb), hmb = static_cast<int>(pd->hmb);
-    // the picture's place in its frame slot (PicDesc): W = bytes from one luma row of the PICTURE to the next (a field picture lives in the
-    // rows of its parity: twice the frame's pitch, first row y_off bytes in); offsets are relative to the slot's first byte
+    // W = bytes from one luma row of the PICTURE to the next; the planes' offsets are relative to the slot's first byte (PicPlace)
     const int W = static_cast<int>(pd->pitch), Wc = W / 2;
-    g8 *const py = (g8 *)(pd->pool_base + static_cast<uint64_t>(pd->slot) * pd->slot_bytes);
-    const uint32_t y_off = pd->field == 2 ? pd->pitch >> 1 : 0u;
-    const uint32_t cb_off = pd->plane + (y_off >> 1), cr_off = cb_off + (pd->plane >> 2);
+    const PicPlace pp(pd);
+    g8 *const py = pp.base;
+    const uint32_t y_off = pp.y, cb_off = pp.cb, cr_off = pp.cr;
     for (int i = tid; i < MI_DEBLOCK8_MAX_GROUPS; i += nthreads) sh.prog[i] = 0, sh.cons[i] = 0;
     __syncthreads();
     const g8 *const prms = (const g8 *)(dbprm + pd->mb_base);
@@ -162,7 +137,7 @@ extern "C" __global__ void __launch_bounds__(MI_DEBLOCK8_MAX_WAVES * 64) k_deblo
         const int in_depth = in_last ? ring_last : ring;
         const uint32_t in_ring = rings_off + static_cast<uint32_t>(in_wave * ring + (in_last && g > 0 ? (((g - 1) / nwaves) % last_bufs) * ring_last : 0)) * MI_DEBLOCK_SLOT_BYTES;
         // ---- memory traffic is COOPERATIVE: a vector memory instruction costs what its lanes touch in distinct cache lines (the CU's L1 looks up one line
-        // per clock: with a lane per row, 64 lines per instruction, 9 wavefronts spent 11 k of a step's 18 k clocks issuing them), so whole
+        // per clock: with a lane per row, 64 lines per instruction, the then 9 wavefronts of a picture spent 11 k of a step's 18 k clocks issuing them), so whole
         // wavefronts move blocks of one sub-row between HBM and its LDS window, eight / four (loads) or two (stores) adjacent lanes per row:
         //   luma load    GA[k] / GB[k], rows 0..7 / 8..15 of sub-row k, EIGHT macroblock columns at once = whole 128-byte lines: lane = (row L >> 3, column L & 7),
         //                16 bytes; landed pieces enter the window one column per step (the slot of column x + 1 is free from the end of step x on), raw rows --

@@ -37,14 +37,8 @@
 // Absent from the reference (only the slice-header fields are parsed: h264/slice.go:1021-1027).
 #include <hip/hip_runtime.h>
 #include "mi_kernels.h"
+#include "k_common.h"       // WAVE_SYNC, OPAQUE, STAMP, the address-space-1 typedefs and GLD* / GST*, pack4 / unpack4, PicPlace
 #include "k_deblock_edge.h" // adiff, clip3, filter_edge
-
-#define WAVE_SYNC()                                            \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                       \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
-    } while (0)
 
 struct DbSub { // state of one of the 4 macroblock rows a wavefront works on
     // luma tile, rows -4..15 of the macroblock: bytes 12..15 of a row = columns -4..-1, bytes 16..31 = columns 0..15
@@ -71,39 +65,9 @@ struct DbShared { // followed in dynamic LDS by DbWave[nwaves] and the hand-off 
 static_assert(sizeof(DbShared) <= MI_DEBLOCK_HDR_BYTES && sizeof(DbWave) == MI_DEBLOCK_WAVE_BYTES && sizeof(GroupSlot) == MI_DEBLOCK_SLOT_BYTES,
               "LDS layout constants");
 
-// Global memory through an explicit address-space-1 pointer with a wave-uniform base and a 32-bit per-lane offset: the
-// frame pointers are built from integers (FramePool::base), which the compiler would otherwise treat as generic (flat_*
-// instructions, two wait counters) and keep as 64-bit per-lane pointers in registers for the whole kernel.
-typedef __attribute__((address_space(1))) uint8_t g8;
-typedef uint32_t v4u __attribute__((ext_vector_type(4))); // native vectors: assignable across address spaces (HIP's uint4 is a struct)
-typedef uint32_t v2u __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(1))) v4u g_uint4;
-typedef __attribute__((address_space(1))) v2u g_uint2;
-#define GLD16(base, off) (*reinterpret_cast<const g_uint4 *>((base) + (off)))
-#define GLD8(base, off) (*reinterpret_cast<const g_uint2 *>((base) + (off)))
 // (Streaming / non-temporal stores and DbPrm loads were tried in round 4 to keep the XCD's L2 for the sample lines: no faster, and WRITE_SIZE grew
 // from 0.85 to 1.10 GB per launch -- partial lines leave the L2 before the rest of the line arrives.)
-#define GST16(base, off, v) (*reinterpret_cast<g_uint4 *>((base) + (off)) = (v))
-#define GST8(base, off, v) (*reinterpret_cast<g_uint2 *>((base) + (off)) = (v))
-typedef __attribute__((address_space(1))) uint32_t g_uint1;
-#define GST4(base, off, v) (*reinterpret_cast<g_uint1 *>((base) + (off)) = (v))
-// keeps lane-dependent values from being hoisted out of the step loop (dozens of loop-invariant addresses would otherwise
-// live in registers for the whole kernel)
-#define OPAQUE(x) asm volatile("" : "+v"(x))
-// diagnostic build (-DMI_DB_STATS): shader clocks per phase of the step loop, summed over one wavefront's steps, added to xstatus[8 + phase]
-// by the wavefront of group 0 of every picture (tools/deblock_phase_probe.py); k_deblock gets the status words as an extra argument in that build
-#if defined(MI_DB_STATS)
-#define STAMP(k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); st_acc[k] += static_cast<uint32_t>(now_ - st_last); st_last = now_; } while (0)
-#else
-#define STAMP(k) do { } while (0)
-#endif
-
-__device__ __forceinline__ void unpack4(uint32_t w, int &a, int &b, int &c, int &d) {
-    a = static_cast<int>(w & 255u), b = static_cast<int>(__builtin_amdgcn_ubfe(w, 8, 8)), c = static_cast<int>(__builtin_amdgcn_ubfe(w, 16, 8)), d = static_cast<int>(w >> 24);
-}
-__device__ __forceinline__ uint32_t pack4(int a, int b, int c, int d) {
-    return static_cast<uint32_t>(a) | (static_cast<uint32_t>(b) << 8) | (static_cast<uint32_t>(c) << 16) | (static_cast<uint32_t>(d) << 24);
-}
+#define GST4(base, off, v) (*reinterpret_cast<g32 *>((base) + (off)) = (v))
 
 typedef __attribute__((address_space(1))) unsigned long long gu64;
 extern "C" __global__ void __launch_bounds__(MI_DEBLOCK_MAX_WAVES * 64) k_deblock_x(const uint32_t *pic_list, const PicDesc *pics, const DbPrm *dbprm, int ring, int ring_last,
@@ -123,12 +87,11 @@ extern "C" __global__ void __launch_bounds__(MI_DEBLOCK_MAX_WAVES * 64) k_debloc
     const int band = static_cast<int>(tk - pic_i * static_cast<uint32_t>(nbands));
     const PicDesc *pd = &pics[pic_list[pic_i]];
     const int wmb = static_cast<int>(pd->wmb), hmb = static_cast<int>(pd->hmb);
-    // the picture's place in its frame slot (PicDesc): W = bytes from one luma row of the PICTURE to the next (a field picture lives in the
-    // rows of its parity: twice the frame's pitch, first row y_off bytes in); offsets are relative to the slot's first byte
+    // W = bytes from one luma row of the PICTURE to the next; the planes' offsets are relative to the slot's first byte (PicPlace)
     const int W = static_cast<int>(pd->pitch), Wc = W / 2;
-    g8 *const py = (g8 *)(pd->pool_base + static_cast<uint64_t>(pd->slot) * pd->slot_bytes);
-    const uint32_t y_off = pd->field == 2 ? pd->pitch >> 1 : 0u;
-    const uint32_t cb_off = pd->plane + (y_off >> 1), cr_off = cb_off + (pd->plane >> 2);
+    const PicPlace pp(pd);
+    g8 *const py = pp.base;
+    const uint32_t y_off = pp.y, cb_off = pp.cb, cr_off = pp.cr;
     for (int i = tid; i < 192; i += nthreads) sh.prog[i] = 0, sh.cons[i] = 0;
     __syncthreads();
     const DbPrm *prms = dbprm + pd->mb_base;

@@ -24,6 +24,7 @@
 // prediction are absent from the reference and follow ITU-T H.264 7.3.5, 8.3.1.1, 8.4.1, 9.2, 9.3.
 #include <hip/hip_runtime.h>
 #include "mi_kernels.h"
+#include "k_common.h" // OPAQUE
 
 // Register budget: 512 / MI_ENT_MINWAVES VGPRs per wavefront.  The reconstruction kernels of the previous pass
 // must find free registers next to the long-lived entropy wavefronts: measured at 256 streams, 6 (80 VGPRs, a few
@@ -354,7 +355,6 @@ FI int get_se(Ent &e) {
 // (7 vector instructions less per bin, but a vector -> scalar hop behind the compare) lost 3 - 14 %, and why every vector instruction saved
 // without such a hop shows up in the step time.
 #define VGPR(x) asm volatile("" : "+v"(x))
-#define OPAQUE(x) asm volatile("" : "+v"(x))
 #define UNI(cond) (__builtin_amdgcn_ballot_w64(cond) != 0)
 // a context state as it sits in a register lane: pStateIdx | valMPS << 6 (the byte kept in LDS and in DevTables::ctx_init) and valMPS once more in bit 31
 FI uint32_t ctx_word(uint32_t b) { return b | (b & 64u) << 25; }

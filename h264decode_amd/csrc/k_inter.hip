@@ -20,18 +20,9 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include "mi_kernels.h"
+#include "k_common.h"
+#include "k_residual.h"
 
-#define WAVE_SYNC()                                            \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                       \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
-    } while (0)
-
-typedef __attribute__((address_space(1))) uint8_t g8;
-typedef __attribute__((address_space(1))) uint16_t g16;
-typedef __attribute__((address_space(1))) uint32_t g32;
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 typedef short s2 __attribute__((ext_vector_type(2)));
 
 // The clamped value is made opaque on purpose: left alone, the compiler fuses "shift, clamp, pack two bytes" into gfx950's
@@ -44,9 +35,6 @@ __device__ __forceinline__ int clip255(int v) {
 }
 __device__ __forceinline__ uint32_t lerp8(uint32_t a, uint32_t b) { return __builtin_amdgcn_lerp(a, b, 0x01010101u); } // (a + b + 1) >> 1 per byte
 __device__ __forceinline__ uint32_t align8(uint32_t hi, uint32_t lo, uint32_t sh) { return __builtin_amdgcn_alignbyte(hi, lo, sh); }
-__device__ __forceinline__ uint32_t pack4(int a, int b, int c, int d) {
-    return static_cast<uint32_t>(a) | (static_cast<uint32_t>(b) << 8) | (static_cast<uint32_t>(c) << 16) | (static_cast<uint32_t>(d) << 24);
-}
 __device__ __forceinline__ s2 as_s2(uint32_t v) { return __builtin_bit_cast(s2, v); }
 __device__ __forceinline__ uint32_t as_u32(s2 v) { return __builtin_bit_cast(uint32_t, v); }
 
@@ -59,24 +47,7 @@ __device__ __forceinline__ uint32_t add_clip4(uint32_t p, int r0, int r1, int r2
     return __builtin_amdgcn_perm(as_u32(__builtin_elementwise_min(__builtin_elementwise_max(hi, z), m)), as_u32(__builtin_elementwise_min(__builtin_elementwise_max(lo, z), m)), 0x06040200u);
 }
 
-// ------------------------------------------------------------------ 1-D inverse transforms / scaling (8.5.12, 8.5.13)
-__device__ __forceinline__ void inv4(int d0, int d1, int d2, int d3, int &o0, int &o1, int &o2, int &o3) {
-    int e0 = d0 + d2, e1 = d0 - d2, e2 = (d1 >> 1) - d3, e3 = d1 + (d3 >> 1);
-    o0 = e0 + e3, o1 = e1 + e2, o2 = e1 - e2, o3 = e0 - e3;
-}
-__device__ __forceinline__ void inv8(const int *d, int *o) {
-    int e0 = d[0] + d[4], e1 = -d[3] + d[5] - d[7] - (d[7] >> 1), e2 = d[0] - d[4], e3 = d[1] + d[7] - d[3] - (d[3] >> 1);
-    int e4 = (d[2] >> 1) - d[6], e5 = -d[1] + d[7] + d[5] + (d[5] >> 1), e6 = d[2] + (d[6] >> 1), e7 = d[3] + d[5] + d[1] + (d[1] >> 1);
-    int f0 = e0 + e6, f1 = e1 + (e7 >> 2), f2 = e2 + e4, f3 = e3 + (e5 >> 2);
-    int f4 = e2 - e4, f5 = (e3 >> 2) - e5, f6 = e0 - e6, f7 = e7 - (e1 >> 2);
-    o[0] = f0 + f7, o[1] = f2 + f5, o[2] = f4 + f3, o[3] = f6 + f1;
-    o[4] = f6 - f1, o[5] = f4 - f3, o[6] = f2 - f5, o[7] = f0 - f7;
-}
-__device__ __forceinline__ int scale4(int c, int ls, int qp) { // 8.5.12.1
-    int per = qp / 6;
-    return per >= 4 ? (c * ls) << (per - 4) : (c * ls + (1 << (3 - per))) >> (4 - per);
-}
-// The same with the case distinction taken out of the per-coefficient work: ((c * ls + rnd) >> sr) << sl with (sl, sr, rnd) = (per - 4, 0, 0) or
+// 8.5.12.1 (scale4, k_residual.h) with the case distinction taken out of the per-coefficient work: ((c * ls + rnd) >> sr) << sl with (sl, sr, rnd) = (per - 4, 0, 0) or
 // (0, 4 - per, 1 << (3 - per)) -- one multiply-add and two shifts by a per-lane amount, no select (one of the shifts is by 0).
 struct Scale4 {
     int sl, sr, rnd;
@@ -86,10 +57,6 @@ struct Scale4 {
     }
     __device__ __forceinline__ int operator()(int c, int ls) const { return ((c * ls + rnd) >> sr) << sl; }
 };
-__device__ __forceinline__ int scale8(int c, int ls, int qp) { // 8.5.13
-    int per = qp / 6;
-    return per >= 6 ? (c * ls) << (per - 6) : (c * ls + (1 << (5 - per))) >> (6 - per);
-}
 // the 16 coefficients of a 32-byte block: two 16-byte loads, sign-extended halves
 __device__ __forceinline__ void load_block(const int16_t *coefs, uint32_t blk, int (&c)[16]) {
     const v4u *src = reinterpret_cast<const v4u *>(coefs) + 2 * static_cast<size_t>(blk);
@@ -565,6 +532,8 @@ __device__ __forceinline__ void inter4(InterLds *lds, const uint32_t *pic_list, 
     }
     // ---- reconstruct + store ----
     if (inter) {
+        // (PicPlace of k_common.h, written out with the fld / fpitch / plane K4 holds for its reference fields anyway: with the helper's own
+        // loads of them the whole kernel is scheduled and allocated differently)
         g8 *dst = (g8 *)(pd->pool_base + static_cast<uint64_t>(pd->slot) * pd->slot_bytes) + (fld == 2 ? fpitch : 0u);
         const bool any_l = has_l || has_8;
 #pragma unroll

@@ -1,8 +1,8 @@
-// h264decode_amd/csrc/k_recon.hip -- K3 (intra reconstruction) and K6 (crop + pack), gfx950.  (K4 is k_inter.hip.)
+// h264decode_amd/csrc/k_recon.hip -- K3: intra reconstruction, gfx950.  (K4 is k_inter.hip, K6 k_pack.hip.)
 //
 // Everything here is byte / int16 work bounded by HBM traffic and LDS latency (no MFMA):
 //   residual: scaling (8.5.9, 8.5.12.1) + Intra16x16 / chroma DC transforms (8.5.10, 8.5.11) +
-//             4x4 / 8x8 inverse transforms (8.5.12.2, 8.5.13), two LDS passes (rows, columns);
+//             4x4 / 8x8 inverse transforms (8.5.12.2, 8.5.13: k_residual.h), two LDS passes (rows, columns);
 //   K3 intra: macroblocks depend on their left / top / top-right neighbours, so a picture is
 //             decoded by ONE workgroup (no cross-CU visibility problem): wavefront w owns
 //             macroblock rows w, w+16, ..., and waits on an LDS progress counter of the row above
@@ -14,21 +14,12 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include "mi_kernels.h"
+#include "k_common.h"   // WAVE_SYNC, OPAQUE, g8 / g16 / g32 (why frame memory goes through them), PicPlace
+#include "k_residual.h" // inv4, inv8, scale4, scale8
 
-#define WAVE_SYNC()                                             \
-    do {                                                        \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  \
-        __builtin_amdgcn_wave_barrier();                        \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  \
-    } while (0)
-
-// Frame memory through explicit address-space-1 pointers: the frame pool's address arrives as an integer (PicDesc::pool_base),
-// and a pointer made from an integer is generic -- flat_load / flat_store, which are slower and count against the LDS wait
-// counter as well.
-typedef __attribute__((address_space(1))) uint8_t g8;
-typedef __attribute__((address_space(1))) uint16_t g16;
-typedef __attribute__((address_space(1))) uint32_t g32;
-
+// A plain clamp, and K3's own on purpose: K4's clip255 (k_inter.hip) hides its result from the compiler because of what "shift, clamp, pack"
+// fused into v_ashr_pk_u8_i32 did to its packed samples.  Every sample K3 packs is the clamp of prediction + residual -- an addition, no
+// shift in front of the pack -- so there is nothing to hide here and the two are not shared.
 __device__ __forceinline__ int clip255(int v) { return min(max(v, 0), 255); }
 
 struct ResBuf {
@@ -37,28 +28,6 @@ struct ResBuf {
     int16_t chroma[2][64]; // residual, raster 8x8 per plane
     int32_t dc[24];        // Intra16x16 DC (16, block raster) + chroma DC (2 x 4)
 };
-
-// ------------------------------------------------------------------ 1-D inverse transforms
-__device__ __forceinline__ void inv4(int d0, int d1, int d2, int d3, int &o0, int &o1, int &o2, int &o3) {
-    int e0 = d0 + d2, e1 = d0 - d2, e2 = (d1 >> 1) - d3, e3 = d1 + (d3 >> 1);
-    o0 = e0 + e3, o1 = e1 + e2, o2 = e1 - e2, o3 = e0 - e3;
-}
-__device__ __forceinline__ void inv8(const int *d, int *o) {
-    int e0 = d[0] + d[4], e1 = -d[3] + d[5] - d[7] - (d[7] >> 1), e2 = d[0] - d[4], e3 = d[1] + d[7] - d[3] - (d[3] >> 1);
-    int e4 = (d[2] >> 1) - d[6], e5 = -d[1] + d[7] + d[5] + (d[5] >> 1), e6 = d[2] + (d[6] >> 1), e7 = d[3] + d[5] + d[1] + (d[1] >> 1);
-    int f0 = e0 + e6, f1 = e1 + (e7 >> 2), f2 = e2 + e4, f3 = e3 + (e5 >> 2);
-    int f4 = e2 - e4, f5 = (e3 >> 2) - e5, f6 = e0 - e6, f7 = e7 - (e1 >> 2);
-    o[0] = f0 + f7, o[1] = f2 + f5, o[2] = f4 + f3, o[3] = f6 + f1;
-    o[4] = f6 - f1, o[5] = f4 - f3, o[6] = f2 - f5, o[7] = f0 - f7;
-}
-__device__ __forceinline__ int scale4(int c, int ls, int qp) { // 8.5.12.1
-    int per = qp / 6;
-    return per >= 4 ? (c * ls) << (per - 4) : (c * ls + (1 << (3 - per))) >> (4 - per);
-}
-__device__ __forceinline__ int scale8(int c, int ls, int qp) { // 8.5.13 scaling
-    int per = qp / 6;
-    return per >= 6 ? (c * ls) << (per - 6) : (c * ls + (1 << (5 - per))) >> (6 - per);
-}
 
 // Residual of one macroblock, computed by one wavefront (lane = 0..63).  Results in rb->luma / rb->chroma.
 __device__ __forceinline__ void mb_residual(int lane, const MbRec *rec, const int16_t *coef, const ScalingSet *sc, ResBuf *rb) {
@@ -516,6 +485,31 @@ __device__ void intra_mb(int lane, IntraWave *ws, const MbRec *rec, const int16_
     }
 }
 
+// ------------------------------------------------------------------ one macroblock step, shared by the two K3 kernels
+// k_intra and k_intra_x differ in how they deal macroblocks to wavefronts and in the flag that crosses workgroups; what a wavefront does
+// with the macroblock it was dealt is below, once: record -> LDS, wait for the intra macroblocks it predicts from, coefficients -> LDS,
+// intra_mb<>, publish.  (All __forceinline__ and intra_mb<> called from ONE place per kernel: a second copy of it costs 200 spilled registers.)
+
+// What a workgroup knows about its picture.  Constructing it also issues the copy of the LevelScale tables of the picture's PPS into LDS
+// (2688 bytes; visible after the kernel's next __syncthreads()).
+struct IntraPic {
+    int wmb, hmb, nchunks; // nchunks: 64-macroblock chunks per macroblock row
+    int W;                 // bytes from one luma row of the PICTURE to the next -- twice the frame's for a field picture, which lives in the rows of its parity
+    g8 *py, *pcb, *pcr;    // the picture's first luma / Cb / Cr row (PicPlace)
+    uint64_t mb_base;      // the picture's first macroblock in the batch's record array and bit mask
+    const MbRec *recs;
+    __device__ __forceinline__ IntraPic(const PicDesc *pd, const DevTables *tab, const MbRec *mbrec, ScalingSet *sc, int tid, int nthreads) {
+        wmb = static_cast<int>(pd->wmb), hmb = static_cast<int>(pd->hmb);
+        W = static_cast<int>(pd->pitch);
+        const PicPlace pp(pd);
+        py = pp.base + pp.y, pcb = pp.base + pp.cb, pcr = pp.base + pp.cr;
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(&tab->scaling[pd->scaling_set]);
+        for (int i = tid; i < static_cast<int>(sizeof(ScalingSet) / 4); i += nthreads) reinterpret_cast<uint32_t *>(sc)[i] = src[i];
+        nchunks = (wmb + 63) >> 6;
+        mb_base = pd->mb_base, recs = mbrec + mb_base;
+    }
+};
+
 // 64 bits of the batch's intra mask (k_dbprep: one bit per macroblock, index = position in the record array) from bit `first` on, the first `n` of them
 __device__ __forceinline__ unsigned long long intra_bits(const unsigned long long *mask, unsigned long long first, int n) {
     const unsigned long long w = first >> 6;
@@ -525,34 +519,79 @@ __device__ __forceinline__ unsigned long long intra_bits(const unsigned long lon
     return n >= 64 ? m : (m & ((1ull << n) - 1ull));
 }
 
+typedef unsigned long long IntraRows[MI_INTRA_MAX_ROWS][MI_INTRA_MAX_CHUNKS]; // sh.pend as pass 1 left it: which macroblocks K3 owns
+
+// Pass 1: the intra masks of rows [first_row, end_row), cut out of the batch's bit mask (k_dbprep; macroblocks no slice delivered -- type
+// MBT_NONE -- are in it too: the intra path paints them mid-grey), into sh->pend, which loses its bits as macroblocks finish, and into
+// s_intra, which keeps them.  One thread per (row, 64-macroblock chunk).
+__device__ __forceinline__ void load_intra_masks(const IntraPic &ip, const unsigned long long *intramask, IntraShared *sh, IntraRows &s_intra, int first_row, int end_row, int tid,
+                                                 int nthreads) {
+    for (int i = tid; i < (end_row - first_row) * ip.nchunks; i += nthreads) {
+        const int mby = first_row + i / ip.nchunks, c = i % ip.nchunks;
+        const unsigned long long m = intra_bits(intramask, ip.mb_base + static_cast<unsigned long long>(mby) * ip.wmb + c * 64, ip.wmb - c * 64);
+        sh->pend[mby][c] = m, s_intra[mby][c] = m;
+    }
+}
+
+// the macroblock's record -> the wavefront's LDS copy
+__device__ __forceinline__ void load_rec(IntraWave *ws, const MbRec *rec, int ln) {
+    if (ln < 32) reinterpret_cast<uint32_t *>(&ws->rec)[ln] = reinterpret_cast<const uint32_t *>(rec)[ln];
+    WAVE_SYNC();
+}
+
+// until macroblock (x, y), an intra one of another wavefront of this workgroup, is done
+__device__ __forceinline__ void wait_mb(IntraShared *sh, int x, int y) {
+    const unsigned long long bit = 1ull << (x & 63);
+    while (__hip_atomic_load(&sh->pend[y][x >> 6], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) & bit) __builtin_amdgcn_s_sleep(1);
+}
+
+// the macroblocks a macroblock predicts from in the row above, columns xl .. xr = mbx - 1 .. mbx + 1 inside the picture: their bits in the (at
+// most two) 64-macroblock chunks c0, c1 of that row
+struct AboveSpan {
+    int xl, xr, c0, c1;
+    unsigned long long m0, m1;
+    __device__ __forceinline__ AboveSpan(int mbx, int wmb) {
+        xl = max(mbx - 1, 0), xr = min(mbx + 1, wmb - 1);
+        c0 = xl >> 6, c1 = xr >> 6;
+        const unsigned long long span = ((xr - xl + 1) >= 64 ? ~0ull : ((1ull << (xr - xl + 1)) - 1));
+        m0 = span << (xl & 63), m1 = c1 != c0 ? span >> (64 - (xl & 63)) : 0ull;
+    }
+};
+// until the intra macroblocks among them are done; row mby - 1 belongs to this workgroup
+__device__ __forceinline__ void wait_row_above(IntraShared *sh, int mby, const AboveSpan &up) {
+    while ((__hip_atomic_load(&sh->pend[mby - 1][up.c0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) & up.m0) ||
+           (up.m1 && (__hip_atomic_load(&sh->pend[mby - 1][up.c1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) & up.m1)))
+        __builtin_amdgcn_s_sleep(1);
+}
+
+// coefficient blocks of the macroblock in ws->rec: pool -> dense LDS layout (absent blocks are zero)
+__device__ __forceinline__ void gather_coefs(IntraWave *ws, const int16_t *coefs, int ln) {
+    const uint32_t cmask = ws->rec.coef_mask;
+    uint4 c0 = make_uint4(0, 0, 0, 0), c1 = c0;
+    if (ln < MI_COEF_BLOCKS && ((cmask >> ln) & 1)) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(coefs) + 2 * (static_cast<size_t>(ws->rec.coef_off) + __builtin_popcount(cmask & ((1u << ln) - 1u)));
+        c0 = src[0], c1 = src[1];
+    }
+    if (ln < MI_COEF_BLOCKS) reinterpret_cast<uint4 *>(ws->coef)[2 * ln] = c0, reinterpret_cast<uint4 *>(ws->coef)[2 * ln + 1] = c1;
+    WAVE_SYNC();
+}
+
+// done: the release orders this wavefront's sample stores before the bit is cleared
+__device__ __forceinline__ void mb_done(IntraShared *sh, int mbx, int mby, int ln) {
+    if (ln == 0) __hip_atomic_fetch_and(&sh->pend[mby][mbx >> 6], ~(1ull << (mbx & 63)), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// ------------------------------------------------------------------ k_intra: one workgroup per picture
 extern "C" __global__ void __launch_bounds__(MI_INTRA_WAVES * 64) k_intra(const uint32_t *pic_list, const PicDesc *pics, const FramePool *pools, const DevTables *tab,
                                                                           const MbRec *mbrec, const int16_t *coefs, const unsigned long long *intramask) {
     __shared__ IntraShared sh;
-    __shared__ unsigned long long s_intra[MI_INTRA_MAX_ROWS][MI_INTRA_MAX_CHUNKS]; // sh.pend as pass 1 left it: which macroblocks K3 owns
-    __shared__ uint32_t s_prefix[MI_INTRA_MAX_ROWS + 1];                          // intra macroblocks in the rows before row r
+    __shared__ IntraRows s_intra;
+    __shared__ uint32_t s_prefix[MI_INTRA_MAX_ROWS + 1]; // intra macroblocks in the rows before row r
     __shared__ uint32_t s_next;
     const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
-    const PicDesc *pd = &pics[pic_list[blockIdx.x]];
-    const int wmb = static_cast<int>(pd->wmb), hmb = static_cast<int>(pd->hmb);
-    // the picture's place in its frame slot (PicDesc): W = bytes from one luma row of the PICTURE to the next -- twice the frame's
-    // for a field picture, which lives in the rows of its parity
-    const int W = static_cast<int>(pd->pitch);
-    const uint32_t par_off = pd->field == 2 ? pd->pitch >> 1 : 0u;
-    g8 *py = (g8 *)(pd->pool_base + static_cast<uint64_t>(pd->slot) * pd->slot_bytes) + par_off;
-    g8 *pcb = py - par_off + pd->plane + (par_off >> 1), *pcr = pcb + (pd->plane >> 2);
-    { // LevelScale tables of this picture's PPS -> LDS (2688 bytes)
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(&tab->scaling[pd->scaling_set]);
-        for (int i = tid; i < static_cast<int>(sizeof(ScalingSet) / 4); i += MI_INTRA_WAVES * 64) reinterpret_cast<uint32_t *>(&sh.sc)[i] = src[i];
-    }
-    const int nchunks = (wmb + 63) >> 6;
-    const MbRec *recs = mbrec + pd->mb_base;
-    // ---- pass 1: intra masks of every row, cut out of the batch's bit mask (k_dbprep; macroblocks no slice delivered -- type MBT_NONE -- are in
-    // it too: the intra path paints them mid-grey).  One thread per (row, 64-macroblock chunk). ----
-    for (int i = tid; i < hmb * nchunks; i += MI_INTRA_WAVES * 64) {
-        const int mby = i / nchunks, c = i - mby * nchunks;
-        const unsigned long long m = intra_bits(intramask, pd->mb_base + static_cast<unsigned long long>(mby) * wmb + c * 64, wmb - c * 64);
-        sh.pend[mby][c] = m, s_intra[mby][c] = m;
-    }
+    const IntraPic ip(&pics[pic_list[blockIdx.x]], tab, mbrec, &sh.sc, tid, MI_INTRA_WAVES * 64);
+    const int wmb = ip.wmb, hmb = ip.hmb, nchunks = ip.nchunks;
+    load_intra_masks(ip, intramask, &sh, s_intra, 0, hmb, tid, MI_INTRA_WAVES * 64);
     if (tid == 0) s_next = 0;
     __syncthreads();
     if (tid == 0) { // running sums of the rows' counts (at most 320 rows)
@@ -575,7 +614,7 @@ extern "C" __global__ void __launch_bounds__(MI_INTRA_WAVES * 64) k_intra(const 
     const bool sparse = n_intra * 4u < static_cast<uint32_t>(wmb * hmb);
     int row = wave, chunk = -1; // dense: the (row, chunk) whose remaining macroblocks are in `mask`
     unsigned long long mask = 0;
-    for (;;) { // (one loop, so that the macroblock body is inlined once: twice costs 200 spilled registers)
+    for (;;) { // (one loop for both ways of dealing, so that the macroblock step below stands once)
         int mbx, mby;
         if (sparse) {
             uint32_t n = 0;
@@ -609,41 +648,18 @@ extern "C" __global__ void __launch_bounds__(MI_INTRA_WAVES * 64) k_intra(const 
         }
         mbx = __builtin_amdgcn_readfirstlane(mbx), mby = __builtin_amdgcn_readfirstlane(mby); // (wave-uniform: say so, or every address below is per-ln arithmetic)
         int ln = lane;
-        asm volatile("" : "+v"(ln)); // (keeps lane-dependent addresses of the body from being hoisted out of the loop and spilled)
-        // one macroblock: wait for the intra macroblocks it predicts from, reconstruct, publish
-        const int c = mbx >> 6, k = mbx & 63;
-        if (ln < 32) reinterpret_cast<uint32_t *>(&ws->rec)[ln] = reinterpret_cast<const uint32_t *>(recs + static_cast<uint64_t>(mby) * wmb + mbx)[ln];
-        WAVE_SYNC();
-        if (sparse && mbx > 0) { // (rows dealt out macroblock by macroblock: the left neighbour may be another wavefront's)
-            const unsigned long long bit = 1ull << ((mbx - 1) & 63);
-            while (__hip_atomic_load(&sh.pend[mby][(mbx - 1) >> 6], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) & bit) __builtin_amdgcn_s_sleep(1);
-        }
-        if (mby > 0) { // the intra macroblocks among (mbx-1 .. mbx+1, mby-1) must be done
-            const int xl = max(mbx - 1, 0), xr = min(mbx + 1, wmb - 1);
-            const int c0 = xl >> 6, c1 = xr >> 6;
-            const unsigned long long span = ((xr - xl + 1) >= 64 ? ~0ull : ((1ull << (xr - xl + 1)) - 1));
-            const unsigned long long m0 = span << (xl & 63), m1 = c1 != c0 ? span >> (64 - (xl & 63)) : 0ull;
-            while ((__hip_atomic_load(&sh.pend[mby - 1][c0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) & m0) ||
-                   (m1 && (__hip_atomic_load(&sh.pend[mby - 1][c1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) & m1)))
-                __builtin_amdgcn_s_sleep(1);
-        }
-        { // coefficient blocks of this macroblock: pool -> dense LDS layout (absent blocks are zero)
-            const uint32_t cmask = ws->rec.coef_mask;
-            uint4 c0 = make_uint4(0, 0, 0, 0), c1 = c0;
-            if (ln < MI_COEF_BLOCKS && ((cmask >> ln) & 1)) {
-                const uint4 *src = reinterpret_cast<const uint4 *>(coefs) + 2 * (static_cast<size_t>(ws->rec.coef_off) + __builtin_popcount(cmask & ((1u << ln) - 1u)));
-                c0 = src[0], c1 = src[1];
-            }
-            if (ln < MI_COEF_BLOCKS) reinterpret_cast<uint4 *>(ws->coef)[2 * ln] = c0, reinterpret_cast<uint4 *>(ws->coef)[2 * ln + 1] = c1;
-            WAVE_SYNC();
-        }
-        intra_mb<false>(ln, ws, &ws->rec, ws->coef, &sh.sc, py, pcb, pcr, W, mbx, mby);
-        // done: the release orders this wavefront's sample stores before the bit is cleared
-        if (ln == 0) __hip_atomic_fetch_and(&sh.pend[mby][c], ~(1ull << k), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        OPAQUE(ln);
+        load_rec(ws, ip.recs + static_cast<uint64_t>(mby) * wmb + mbx, ln);
+        if (sparse && mbx > 0) wait_mb(&sh, mbx - 1, mby); // (rows dealt out macroblock by macroblock: the left neighbour may be another wavefront's)
+        if (mby > 0) wait_row_above(&sh, mby, AboveSpan(mbx, wmb));
+        gather_coefs(ws, coefs, ln);
+        intra_mb<false>(ln, ws, &ws->rec, ws->coef, &sh.sc, ip.py, ip.pcb, ip.pcr, ip.W, mbx, mby);
+        mb_done(&sh, mbx, mby, ln);
     }
 }
 
-// K3 spread over several workgroups per picture, for launches with fewer pictures than the chip has CUs: workgroup = a band of
+// ------------------------------------------------------------------ k_intra_x: a picture spread over several workgroups
+// For launches with fewer pictures than the chip has CUs: workgroup = a band of
 // consecutive macroblock rows, wavefront w of it owns rows r0 + w, r0 + w + nwaves, ...  Inside a band the LDS bit masks order
 // the rows as in k_intra.  The first row of a band waits for the intra macroblocks of the row above -- another workgroup's --
 // through one agent-scope flag word per macroblock column (tag = this launch's epoch), which the band above sets after it has
@@ -657,7 +673,7 @@ extern "C" __global__ void __launch_bounds__(MI_INTRA_WAVES * 64) k_intra_x(cons
     // few and mostly independent of each other, so the busiest row -- which bounds the kernel -- finishes wpr times sooner; a
     // macroblock whose left neighbour is an intra one too waits for that neighbour's bit like it waits for the row above.
     __shared__ IntraShared sh;
-    __shared__ unsigned long long s_intra[MI_INTRA_MAX_ROWS][MI_INTRA_MAX_CHUNKS]; // sh.pend as pass 1 left it: which macroblocks K3 owns
+    __shared__ IntraRows s_intra;
     __shared__ uint32_t s_ticket;
     const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6, nthreads = static_cast<int>(blockDim.x), nwaves = nthreads >> 6;
     if (tid == 0) s_ticket = atomicAdd(ticket, 1u) - ticket_base;
@@ -668,67 +684,41 @@ extern "C" __global__ void __launch_bounds__(MI_INTRA_WAVES * 64) k_intra_x(cons
     const int wmb = static_cast<int>(pd->wmb), hmb = static_cast<int>(pd->hmb);
     const int r0 = band * hmb / nbands, r1 = (band + 1) * hmb / nbands;
     if (r0 >= r1) return; // (pictures smaller than the launch's largest can leave bands empty)
-    const int W = static_cast<int>(pd->pitch); // (see k_intra)
-    const uint32_t par_off = pd->field == 2 ? pd->pitch >> 1 : 0u;
-    g8 *py = (g8 *)(pd->pool_base + static_cast<uint64_t>(pd->slot) * pd->slot_bytes) + par_off;
-    g8 *pcb = py - par_off + pd->plane + (par_off >> 1), *pcr = pcb + (pd->plane >> 2);
-    {
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(&tab->scaling[pd->scaling_set]);
-        for (int i = tid; i < static_cast<int>(sizeof(ScalingSet) / 4); i += nthreads) reinterpret_cast<uint32_t *>(&sh.sc)[i] = src[i];
-    }
-    const int nchunks = (wmb + 63) >> 6;
-    const MbRec *recs = mbrec + pd->mb_base;
+    const IntraPic ip(pd, tab, mbrec, &sh.sc, tid, nthreads);
+    const int nchunks = ip.nchunks;
     typedef __attribute__((address_space(1))) uint32_t gflag;
     int pband = band - 1; // the band that owns row r0 - 1
     while (pband > 0 && pband * hmb / nbands == (pband + 1) * hmb / nbands) pband--;
     gflag *const xin = (gflag *)xdone_ + (static_cast<size_t>(pic_i) * nbands + (pband > 0 ? pband : 0)) * static_cast<size_t>(wmb_max);
     gflag *const xout = (gflag *)xdone_ + (static_cast<size_t>(pic_i) * nbands + band) * static_cast<size_t>(wmb_max);
-    // ---- pass 1: intra masks of the band's rows and of the row above it (that one is never cleared here: it says which flags to wait for) ----
-    {
-        const int rf = r0 > 0 ? r0 - 1 : 0;
-        for (int i = tid; i < (r1 - rf) * nchunks; i += nthreads) {
-            const int mby = rf + i / nchunks, c = i % nchunks;
-            const unsigned long long m = intra_bits(intramask, pd->mb_base + static_cast<unsigned long long>(mby) * wmb + c * 64, wmb - c * 64);
-            sh.pend[mby][c] = m, s_intra[mby][c] = m;
-        }
-    }
+    // the band's rows and the row above it (that one is never cleared here: it says which flags to wait for)
+    load_intra_masks(ip, intramask, &sh, s_intra, r0 > 0 ? r0 - 1 : 0, r1, tid, nthreads);
     __syncthreads();
     IntraWave *ws = &sh.w[wave];
     const int row_slot = wave / wpr, turn = wave - row_slot * wpr, row_slots = nwaves / wpr;
     for (int mby = r0 + row_slot; mby < r1; mby += row_slots) {
-        const MbRec *row = recs + static_cast<uint64_t>(mby) * wmb;
+        const MbRec *row = ip.recs + static_cast<uint64_t>(mby) * wmb;
         const bool publish = mby == r1 - 1 && r1 < hmb; // the band below waits for this row
         int nth = 0; // ordinal of the intra macroblock inside the row
         for (int c = 0; c < nchunks; c++) {
-            const unsigned long long row_mask = s_intra[mby][c]; // (sh.pend loses bits as the row's other wavefronts finish macroblocks)
-            unsigned long long mask = row_mask;
+            unsigned long long mask = s_intra[mby][c]; // (sh.pend loses bits as the row's other wavefronts finish macroblocks)
             while (mask) {
                 const int k = __ffsll(static_cast<long long>(mask)) - 1;
                 mask &= mask - 1;
                 if (wpr > 1 && (nth++ % wpr) != turn) continue; // another wavefront's macroblock
                 const int mbx = c * 64 + k;
                 int ln = lane;
-                asm volatile("" : "+v"(ln)); // (keeps lane-dependent addresses of the body from being hoisted out of the loops and spilled)
-                if (ln < 32) reinterpret_cast<uint32_t *>(&ws->rec)[ln] = reinterpret_cast<const uint32_t *>(row + mbx)[ln];
-                WAVE_SYNC();
-                if (wpr > 1 && mbx > 0) { // the left neighbour, if it is an intra macroblock, belongs to another wavefront of this row
-                    const int xl = mbx - 1;
-                    const unsigned long long bit = 1ull << (xl & 63);
-                    if (s_intra[mby][xl >> 6] & bit)
-                        while (__hip_atomic_load(&sh.pend[mby][xl >> 6], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) & bit) __builtin_amdgcn_s_sleep(1);
-                }
+                OPAQUE(ln);
+                load_rec(ws, row + mbx, ln);
+                // the left neighbour, if it is an intra macroblock, belongs to another wavefront of this row
+                if (wpr > 1 && mbx > 0 && (s_intra[mby][(mbx - 1) >> 6] & (1ull << ((mbx - 1) & 63)))) wait_mb(&sh, mbx - 1, mby);
                 if (mby > 0) {
-                    const int xl = max(mbx - 1, 0), xr = min(mbx + 1, wmb - 1);
-                    const int c0 = xl >> 6, c1 = xr >> 6;
-                    const unsigned long long span = ((xr - xl + 1) >= 64 ? ~0ull : ((1ull << (xr - xl + 1)) - 1));
-                    const unsigned long long m0 = span << (xl & 63), m1 = c1 != c0 ? span >> (64 - (xl & 63)) : 0ull;
-                    if (mby > r0) {
-                        while ((__hip_atomic_load(&sh.pend[mby - 1][c0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) & m0) ||
-                               (m1 && (__hip_atomic_load(&sh.pend[mby - 1][c1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) & m1)))
-                            __builtin_amdgcn_s_sleep(1);
-                    } else { // another workgroup's row: ln i watches the flag of column xl + i if that macroblock is an intra one
-                        const int col = xl + ln;
-                        const bool need = ln < 3 && col <= xr && ((sh.pend[mby - 1][col >> 6] >> (col & 63)) & 1ull);
+                    const AboveSpan up(mbx, wmb);
+                    if (mby > r0)
+                        wait_row_above(&sh, mby, up);
+                    else { // another workgroup's row: ln i watches the flag of column xl + i if that macroblock is an intra one
+                        const int col = up.xl + ln;
+                        const bool need = ln < 3 && col <= up.xr && ((sh.pend[mby - 1][col >> 6] >> (col & 63)) & 1ull);
                         const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
                         for (;;) {
                             const uint32_t v = need ? __hip_atomic_load(xin + col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : epoch;
@@ -742,54 +732,14 @@ extern "C" __global__ void __launch_bounds__(MI_INTRA_WAVES * 64) k_intra_x(cons
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); // (no instruction: the sample loads below stay below the poll)
                     }
                 }
-                {
-                    const uint32_t cmask = ws->rec.coef_mask;
-                    uint4 c0 = make_uint4(0, 0, 0, 0), c1 = c0;
-                    if (ln < MI_COEF_BLOCKS && ((cmask >> ln) & 1)) {
-                        const uint4 *src = reinterpret_cast<const uint4 *>(coefs) + 2 * (static_cast<size_t>(ws->rec.coef_off) + __builtin_popcount(cmask & ((1u << ln) - 1u)));
-                        c0 = src[0], c1 = src[1];
-                    }
-                    if (ln < MI_COEF_BLOCKS) reinterpret_cast<uint4 *>(ws->coef)[2 * ln] = c0, reinterpret_cast<uint4 *>(ws->coef)[2 * ln + 1] = c1;
-                    WAVE_SYNC();
-                }
-                intra_mb<true>(ln, ws, &ws->rec, ws->coef, &sh.sc, py, pcb, pcr, W, mbx, mby);
+                gather_coefs(ws, coefs, ln);
+                intra_mb<true>(ln, ws, &ws->rec, ws->coef, &sh.sc, ip.py, ip.pcb, ip.pcr, ip.W, mbx, mby);
                 if (publish) { // every sample store of this wavefront has left the CU before the flag does
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     if (ln == 0) __hip_atomic_store(xout + mbx, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
-                if (ln == 0) __hip_atomic_fetch_and(&sh.pend[mby][c], ~(1ull << k), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                mb_done(&sh, mbx, mby, ln);
             }
-        }
-    }
-}
-
-// ================================================================== K6: crop + pack to tight I420
-// One launch packs any number of frames (a whole batch): blockIdx.x = frame, blockIdx.y = a chunk of its rows (luma rows,
-// then the Cb rows, then the Cr rows).  A thread moves 16 bytes when source and destination rows are 16-byte aligned
-// (1080p: always), single bytes otherwise.
-extern "C" __global__ void __launch_bounds__(256) k_pack(const PackDesc *descs, uint8_t *dst, int rows_per_block) {
-    const PackDesc pd = descs[blockIdx.x];
-    const int w = static_cast<int>(pd.w), h = static_cast<int>(pd.h), W = static_cast<int>(pd.W), H = static_cast<int>(pd.H);
-    const int wc = (w + 1) / 2, hc = (h + 1) / 2; // chroma plane of the packed frame (H264MI_I420_SIZE; odd w or h: monochrome streams only)
-    const int nrows = h + 2 * hc; // h luma rows + hc Cb rows + hc Cr rows
-    const uint8_t *src = reinterpret_cast<const uint8_t *>(pd.src);
-    uint8_t *out = dst + pd.dst_off;
-    const int r0 = static_cast<int>(blockIdx.y) * rows_per_block, r1 = min(r0 + rows_per_block, nrows);
-    for (int r = r0; r < r1; r++) {
-        const uint8_t *s;
-        uint8_t *d;
-        int n;
-        if (r < h) {
-            s = src + static_cast<size_t>(r + pd.y0) * W + pd.x0, d = out + static_cast<size_t>(r) * w, n = w;
-        } else {
-            const int c = r - h >= hc, rc = r - h - c * hc;
-            s = src + static_cast<size_t>(W) * H + static_cast<size_t>(c) * (W / 2) * (H / 2) + static_cast<size_t>(rc + pd.y0 / 2) * (W / 2) + pd.x0 / 2;
-            d = out + static_cast<size_t>(w) * h + static_cast<size_t>(c) * wc * hc + static_cast<size_t>(rc) * wc, n = wc;
-        }
-        if ((((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d)) & 15) == 0) && (n & 15) == 0) {
-            for (int i = static_cast<int>(threadIdx.x) * 16; i < n; i += 256 * 16) *reinterpret_cast<uint4 *>(d + i) = *reinterpret_cast<const uint4 *>(s + i);
-        } else {
-            for (int i = static_cast<int>(threadIdx.x); i < n; i += 256) d[i] = s[i];
         }
     }
 }

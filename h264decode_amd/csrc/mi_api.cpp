@@ -5,8 +5,8 @@
 // mi_hooks.cpp.  The decoder's state, which all of them work on, is mi_decoder.hpp.
 //
 // There is deliberately NO CPU pixel path in this library: every sample is produced by the HIP
-// kernels in k_entropy.hip / k_recon.hip / k_deblock.hip.  If no device is usable the create call
-// fails (H264MI_ENODEVICE).
+// kernels of the k_*.hip files (decoded by k_entropy / k_recon / k_inter / k_deblock, brought into the caller's
+// layout by k_pack and the rest of the output stage).  If no device is usable the create call fails (H264MI_ENODEVICE).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstddef>

@@ -110,7 +110,7 @@ static inline void mi_deblock_bands(int n_pics, int wmb, int hmb, int max_wgs, i
 // double-buffered by round: the last wavefront's group of round r must not wait until wavefront 0 has read ALL of round
 // r - 1's ring, because wavefront 0's group of round r can only finish when the groups below it -- up to the last
 // wavefront's, through the short rings -- make progress: with a single buffer wide pictures deadlock.  As many wavefronts as fit.
-// 1080p: 9 wavefronts, one round.
+// 1080p (120 x 68): 9 groups on 8 wavefronts (MI_DEBLOCK8_MAX_WAVES), two rounds -- the ninth group is wavefront 0's second --, so ring_last = wmb.
 static inline void mi_deblock8_plan(int wmb, int hmb, int *nwaves, int *ring, int *ring_last, int *last_bufs, int max_waves = MI_DEBLOCK8_MAX_WAVES) {
     const int ngroups = (hmb + 7) / 8;
     const int w1 = wmb > 0 ? wmb : 1;
