@@ -371,6 +371,8 @@ extern "C" int32_t h264mi_decoder_create(const h264mi_config *cfg_, h264mi_decod
                                      static_cast<uint64_t>(d->slices_cap + 1) * MI_COEF_CHUNK;
             d->pool_blocks = std::min<uint64_t>(std::min<uint64_t>(worst, typical), 0xFFFF0000ull / MI_SETS);
             DEV_ALLOC(d->d_pool_head, sizeof(uint32_t) * MI_SETS);
+            // (h264mi_decoder_coef_pool reports the largest of the MI_SETS heads: those of sets that have not run yet must read 0, not what the allocation held)
+            TRY_ALLOC(hipMemset(d->d_pool_head, 0, sizeof(uint32_t) * MI_SETS));
         }
         // the MI_SETS pools are ONE allocation: a pass that ran out of residual blocks is repeated on its own with all of it (retry_exhausted)
         if (i == 0) DEV_ALLOC(d->d_coef[0], d->pool_blocks * 32 * MI_SETS);

@@ -23,7 +23,7 @@ class Params(ctypes.Structure):
         ("motion_x4", ctypes.c_int), ("motion_y4", ctypes.c_int), ("interlace_sps", ctypes.c_int), ("fn_gap_period", ctypes.c_int), ("fn_gap_declared", ctypes.c_int),
         ("b_pyramid", ctypes.c_int), ("slice_groups", ctypes.c_int), ("fmo_type", ctypes.c_int), ("aso", ctypes.c_int), ("field_pics", ctypes.c_int), ("poc_bottom_delta", ctypes.c_int), ("mono", ctypes.c_int),
         ("wp_range", ctypes.c_int), ("poc_step", ctypes.c_int), ("mv_reach", ctypes.c_int), ("mv_margin", ctypes.c_int), ("contrast", ctypes.c_int),
-        ("dbf_per_slice", ctypes.c_int), ("trace_deblock", ctypes.c_int)]
+        ("dbf_per_slice", ctypes.c_int), ("trace_deblock", ctypes.c_int), ("syntax_stim", ctypes.c_int)]
 
 
 def build(force=False):
@@ -50,6 +50,8 @@ def lib():
         _lib.sg_last_pocs.argtypes = [ctypes.c_void_p, ctypes.c_int]
         _lib.sg_last_features.restype = ctypes.c_uint32
         _lib.sg_last_ranges.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        _lib.sg_last_syntax.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        _lib.sg_cavlc_level_bits.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
         _lib.sg_last_deblock_trace.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
     return _lib
 
@@ -117,6 +119,44 @@ def last_ranges():
     out = np.zeros(n, dtype=np.int32)
     lib().sg_last_ranges(out.ctypes.data, n)
     return {k: int(v) for k, v in zip(RANGE_NAMES, out)}
+
+
+# the SG_S_* words of sg.h: (name, number of words).  Bitmaps of more than 32 bits and tables with several rows are lists of words.
+SYNTAX_WORDS = (
+    ("token", 15), ("nc_one", 1), ("nc_none", 1), ("tz16", 15), ("tz15", 15), ("tzc", 3), ("run", 7),
+    ("prefix_max", 1), ("p14_sl", 1), ("p15_sl", 1), ("p16_sl", 1), ("level_max", 1), ("start_sl1", 1), ("cavlc_8x8_full", 1),
+    ("egk_max", 1), ("level_max_cabac", 1), ("cat_blocks", 6), ("last_at_end", 6), ("all_nonzero", 6), ("inc0_sat", 1), ("gt1_sat", 1),
+    ("cbf_inc", 5), ("cbf_unavail_intra", 1), ("cbf_unavail_inter", 1),
+    ("dqp_min", 1), ("dqp_max", 1), ("dqp_wrap_up", 1), ("dqp_wrap_down", 1), ("qpy_min", 1), ("qpy_max", 1),
+    ("dqp_after_skip", 1), ("dqp_after_pcm", 1), ("dqp_after_nodelta", 1), ("qpc_clip0", 1), ("qpc_clip51", 1),
+    ("cbp_intra", 2), ("cbp_inter", 2), ("mbtype_i", 1), ("rem4", 1), ("rem8", 1),
+    ("skip_run_max", 1), ("end_in_skip", 1), ("end_in_pcm", 1), ("mb_bits_max", 1), ("thinned", 1))
+_SIGNED = ("dqp_min", "dqp_max", "qpy_min", "qpy_max")
+
+
+def last_syntax():
+    """What the entropy writers of the last encode() call wrote (the SG_S_* words of sg.h), as a dict: a number per counter, a list of numbers per table;
+    bitmaps are unsigned (`token`: five tables of three words, bit 4 * TotalCoeff + TrailingOnes; `cbp_*`: two words)."""
+    n = lib().sg_last_syntax(None, 0)
+    assert n == sum(k for _, k in SYNTAX_WORDS), (n, sum(k for _, k in SYNTAX_WORDS))
+    raw = np.zeros(n, dtype=np.int32)
+    lib().sg_last_syntax(raw.ctypes.data, n)
+    out, at = {}, 0
+    for name, k in SYNTAX_WORDS:
+        words = [int(v) if name in _SIGNED else int(v) & 0xFFFFFFFF for v in raw[at:at + k]]
+        out[name] = words[0] if k == 1 else words
+        at += k
+    out["token"] = [sum(w << (32 * i) for i, w in enumerate(out["token"][3 * t:3 * t + 3])) for t in range(5)]
+    for k in ("cbp_intra", "cbp_inter"):
+        out[k] = out[k][0] | out[k][1] << 32
+    return out
+
+
+def cavlc_level_bits(level, suffix_len, minus2, escape16=1):
+    """The bits of one CAVLC coefficient level as the generator writes it, as a string of '0' / '1' (None: the level cannot be written)."""
+    bits = ctypes.c_uint64(0)
+    n = lib().sg_cavlc_level_bits(level, suffix_len, minus2, escape16, ctypes.byref(bits))
+    return None if n < 0 else format(bits.value, "0%db" % n)
 
 
 # sg_dbmb (sg_int.h), one per macroblock: what 8.7 needs to know about it

@@ -119,6 +119,23 @@ typedef struct {
     int dbf_per_slice;
     /* 1: sg_last_deblock_trace() keeps, for every picture of this call, the planes before sg_deblock and the sg_dbmb table; changes nothing else */
     int trace_deblock;
+    /* entropy-syntax stimulus: 0 = the streams of before, byte for byte.  1: the 16-bit range guard of sg_recon.c is on, and
+     * - after every quantiser call and before the reconstruction is made from the levels, most blocks get their levels replaced by a drawn pattern
+     *   (a target per block: TotalCoeff biased to 0, 1, max - 1 and max, TrailingOnes 0..3, the position of the last coefficient up to the last scan
+     *   position, the zeros as one long run or as many short ones, magnitudes at the ends of the binarisations: 1, 2, 3, 14..17, 15 * 2^(s - 1) and its
+     *   neighbours, "ladders" that take suffixLength to s = 0..6 and then need level_prefix 14, 15 or (High, CAVLC) 16, 2063 / 2064 and beyond), the density
+     *   drawn per neighbourhood of macroblocks; a large level goes where it passes the guard alone (low QP, small LevelScale), the guard runs after the
+     *   replacement and the reconstruction is made from what is left;
+     * - profile_idc 66 / 77 with CAVLC: no |level| above 2063 (level_prefix <= 15, A.2); profile_idc 100 writes the escape of 9.2.2.1;
+     * - one macroblock in twelve is heavy (every block full, the levels as large as their share of the guard's range allows); a macroblock of more
+     *   than 3200 bits (A.3.1) is coded again with a thinner pattern, up to three times, the last time without any level;
+     * - QP_Y is drawn from the whole 0..51, mb_qp_delta takes -26 and +25 and the wrapped form (QP_Y + mb_qp_delta outside 0..51) where the straight
+     *   one is out of range, and a non-zero delta is preferred after a skipped, an I_PCM and a delta-less macroblock;
+     * - slices get forced runs of skipped macroblocks longer than a row, and end in a skip run or in an I_PCM macroblock.
+     * 2: the same without the second coding of large macroblocks.  3 is taken as 0.  Adding 4 to 1 or 2 changes no stream: sg_last_syntax() then counts
+     * what the B slices contain and leaves the I and P slices out (a stream with B pictures has all three).
+     * What the stream then really contains is counted by the entropy writers: sg_last_syntax(). */
+    int syntax_stim;
 } sg_params;
 
 void sg_default_params(sg_params *p);
@@ -192,6 +209,48 @@ enum {
     SG_SF_SPS_MATRIX = 256, SG_SF_PPS_RULE_A = 512, SG_SF_PPS_RULE_B = 1024, SG_SF_PPS_SIX_LISTS = 2048
 };
 int sg_last_ranges(int32_t *dst, int cap);
+/* what the entropy writers of the last sg_encode() call of this thread wrote (cavlc_block, cabac_block, the mb_qp_delta / coded_block_pattern / skip /
+ * mb_type writers of sg_enc.c; never counted where the stimulus draws).  Counted for every stream, with or without syntax_stim.  A set of its own
+ * beside SG_R_*: the entries are mostly bitmaps, one 32-bit word per table row.  Returns the number of words; dst receives up to cap of them. */
+enum {
+    SG_S_TOKEN,                                   /* [5][3]: coeff_token table (nC 0-1, 2-3, 4-7, 8+, chroma DC), bit 4 * TotalCoeff + TrailingOnes over three words */
+    SG_S_NC_ONE = SG_S_TOKEN + 15, SG_S_NC_NONE,  /* blocks whose nC came from one neighbour / from none (nC = 0) */
+    SG_S_TZ16,                                    /* [15]: total_zeros of blocks of 16 coefficients: word tzVlcIndex - 1, bit total_zeros */
+    SG_S_TZ15 = SG_S_TZ16 + 15,                   /* [15]: the same for AC blocks of 15 coefficients */
+    SG_S_TZC = SG_S_TZ15 + 15,                    /* [3]: chroma DC */
+    SG_S_RUN = SG_S_TZC + 3,                      /* [7]: run_before: word Min(zerosLeft, 7) - 1, bit run_before (0..14 in the last word) */
+    SG_S_PREFIX_MAX = SG_S_RUN + 7,               /* largest level_prefix */
+    SG_S_P14_SL, SG_S_P15_SL, SG_S_P16_SL,        /* bit s: level_prefix 14 / 15 / 16 and above written at suffixLength s */
+    SG_S_LEVEL_MAX,                               /* largest |level| of a CAVLC block */
+    SG_S_START_SL1,                               /* blocks that start at suffixLength 1 (TotalCoeff > 10, TrailingOnes < 3) */
+    SG_S_CAVLC_8X8_FULL,                          /* CAVLC 8x8 blocks (four interleaved 4x4 blocks) with 16 coefficients in every part */
+    SG_S_EGK_MAX,                                 /* CABAC: largest k reached by the Exp-Golomb suffix of coeff_abs_level_minus1 */
+    SG_S_LEVEL_MAX_CABAC,                         /* largest |level| of a CABAC block */
+    SG_S_CAT_BLOCKS,                              /* [6]: CABAC blocks with a coefficient, per ctxBlockCat 0..5 */
+    SG_S_LAST_AT_END = SG_S_CAT_BLOCKS + 6,       /* [6]: ... whose last coefficient is at the last scan position (no last_significant_coeff_flag for it) */
+    SG_S_ALL_NONZERO = SG_S_LAST_AT_END + 6,      /* [6]: ... with every coefficient non-zero */
+    SG_S_INC0_SAT = SG_S_ALL_NONZERO + 6,         /* bit cat: ctxIdxInc of the first bin of coeff_abs_level_minus1 reached 4 (three or more levels of 1 before) */
+    SG_S_GT1_SAT,                                 /* bit cat: the count of levels above 1 reached its cap in the ctxIdxInc of the later bins (4; 3 for chroma DC) */
+    SG_S_CBF_INC,                                 /* [5]: per ctxBlockCat 0..4, bit ctxIdxInc of coded_block_flag */
+    SG_S_CBF_UNAVAIL_INTRA = SG_S_CBF_INC + 5, SG_S_CBF_UNAVAIL_INTER, /* coded_block_flag increments with an unavailable neighbour, in intra / inter macroblocks */
+    SG_S_DQP_MIN, SG_S_DQP_MAX,                   /* smallest / largest mb_qp_delta written */
+    SG_S_DQP_WRAP_UP, SG_S_DQP_WRAP_DOWN,         /* QP_Y,PRED + mb_qp_delta above 51 / below 0 */
+    SG_S_QPY_MIN, SG_S_QPY_MAX,                   /* smallest / largest QP_Y after an mb_qp_delta */
+    SG_S_DQP_AFTER_SKIP, SG_S_DQP_AFTER_PCM, SG_S_DQP_AFTER_NODELTA, /* non-zero mb_qp_delta directly after a skipped / an I_PCM / a macroblock without mb_qp_delta */
+    SG_S_QPC_CLIP0, SG_S_QPC_CLIP51,              /* macroblocks with an mb_qp_delta whose QP_Y + chroma_qp_index_offset lay below 0 / above 51 */
+    SG_S_CBP_INTRA, SG_S_CBP_INTER = SG_S_CBP_INTRA + 2, /* [2], [2]: bit coded_block_pattern (0..47) over two words */
+    SG_S_MBTYPE_I = SG_S_CBP_INTER + 2,           /* bit mb_type (0..25) of macroblocks of I slices */
+    SG_S_REM4, SG_S_REM8,                         /* bit rem_intra4x4_pred_mode / rem_intra8x8_pred_mode 0..7, bit 8: the predicted mode was used */
+    SG_S_SKIP_RUN_MAX,                            /* longest run of skipped macroblocks inside a slice (mb_skip_run, or mb_skip_flags in a row) */
+    SG_S_END_IN_SKIP, SG_S_END_IN_PCM,            /* slices whose last macroblock is skipped / I_PCM */
+    SG_S_MB_BITS_MAX,                             /* the largest macroblock, in bits (CABAC: bits the arithmetic coder put out for it) */
+    SG_S_THINNED,                                 /* macroblocks coded again with a thinner pattern because they had more than 3200 bits */
+    SG_S_COUNT
+};
+int sg_last_syntax(int32_t *dst, int cap);
+/* the bits of one CAVLC coefficient level as cavlc_block() writes it (see sg_put_cavlc_level in sg_int.h): returns their number, or -1; bits receives them
+ * from the first one down, in the low end of the word */
+int sg_cavlc_level_bits(int level, int suffix_len, int minus2, int escape16, uint64_t *bits);
 /* sg_params::trace_deblock: the pictures of the last sg_encode() call of this thread, in coding order.  Returns their number; for picture
  * `index` info receives {width, height (of the picture: a field has half the frame's rows), macroblock columns, macroblock rows, field (0 frame,
  * 1 top, 2 bottom), mono, the frame of recon[] the picture belongs to, sizeof(sg_dbmb)}, before / after the picture's I420 planes before and

@@ -75,6 +75,12 @@ typedef struct {
     /* slice groups (sg_params::slice_groups): PPS contents and the macroblock-to-slice-group map of the current picture */
     uint8_t *sgmap, *sg_ids;
     int sg_rl[8], sg_tl[8], sg_br[8], sg_dir, sg_rate, sg_cycle, sg_cycle_bits;
+    /* sg_params::syntax_stim: the knob; per picture: a counter; per slice: macroblocks (counted from the slice's first) forced to be skipped, the last one
+     * forced to I_PCM; per macroblock: how often it was coded again (thinner every time), heavy (every block full, every level as large as its share of the
+     * guard's range allows: what takes a macroblock past 3200 bits), its coefficient density (0 empty .. 3 full), 8x8 luma blocks /
+     * Intra16x16 AC / chroma AC / all chroma levels to leave empty, I_PCM forced; what the macroblock before was (0 one with an mb_qp_delta or none, 1
+     * skipped, 2 I_PCM, 3 one without mb_qp_delta), whether this one wrote an mb_qp_delta, the run of skipped macroblocks so far */
+    int stim, pic_no, sk_from, sk_to, pcm_last, thin, heavy, dens, kill8, kill_ac16, kill_cac, kill_c, force_pcm, prev_kind, had_dqp, run_len;
 } enc;
 
 static char g_err[256];
@@ -99,6 +105,16 @@ static void rng_window(const sg_pic *ref, int ix, int iy, int w, int h) {
     if (iy - 2 > ref->h - 1) g_rng[SG_R_OUT_BOTTOM]++;
 }
 const char *sg_last_error(void) { return g_err; }
+/* sg_last_syntax(): what the entropy writers wrote, per thread like g_rng */
+static _Thread_local int32_t g_syn[SG_S_COUNT];
+static void syn_bit(int word, int bit) { g_syn[word + (bit >> 5)] = (int32_t)((uint32_t)g_syn[word + (bit >> 5)] | 1u << (bit & 31)); }
+static void syn_max(int word, int v) {
+    if (v > g_syn[word]) g_syn[word] = v;
+}
+int sg_last_syntax(int32_t *dst, int cap) {
+    for (int i = 0; i < SG_S_COUNT && i < cap && dst; i++) dst[i] = g_syn[i];
+    return SG_S_COUNT;
+}
 
 void sg_default_params(sg_params *p) {
     memset(p, 0, sizeof(*p));
@@ -251,6 +267,44 @@ static void build_scale(enc *e) {
 }
 
 /* ------------------------------------------------------------------ CAVLC writers (9.2) */
+/* 9.2.2.1, read as a rule for the writer: levelCode = (Min(15, level_prefix) << suffixLength) + level_suffix, plus 15 when level_prefix >= 15 and
+ * suffixLength = 0, plus (1 << (level_prefix - 3)) - 4096 when level_prefix >= 16; level_suffix has suffixLength bits, 4 bits after level_prefix 14 at
+ * suffixLength 0 and level_prefix - 3 bits after level_prefix >= 15.  So the prefixes below 15 carry the codes below 15 << suffixLength (below 30 at
+ * suffixLength 0), prefix 15 the 4096 codes after them, and every prefix p >= 16 the 1 << (p - 3) codes after those of p - 1. */
+int sg_put_cavlc_level(sg_bw *w, int level, int suffix_len, int minus2, int escape16) {
+    int code = level > 0 ? 2 * level - 2 : -2 * level - 1; /* levelCode */
+    if (minus2) code -= 2;
+    int prefix, size = 0;
+    uint32_t suffix = 0;
+    if (suffix_len == 0 && code < 14)
+        prefix = code;
+    else if (suffix_len == 0 && code < 30)
+        prefix = 14, size = 4, suffix = (uint32_t)(code - 14);
+    else if (suffix_len > 0 && code < (15 << suffix_len))
+        prefix = code >> suffix_len, size = suffix_len, suffix = (uint32_t)(code & ((1 << suffix_len) - 1));
+    else {
+        int rest = code - (15 << suffix_len) - (suffix_len == 0 ? 15 : 0), below = 0; /* codes carried by the escape prefixes before this one */
+        prefix = 15, size = 12;
+        while (rest - below >= (1 << size)) below += 1 << size, prefix++, size++;
+        suffix = (uint32_t)(rest - below);
+        if (prefix > 15 && !escape16) return -1;
+    }
+    sg_put(w, 1, prefix + 1);
+    if (size) sg_put(w, suffix, size);
+    return prefix;
+}
+int sg_cavlc_level_bits(int level, int suffix_len, int minus2, int escape16, uint64_t *bits) {
+    uint8_t buf[16] = {0};
+    sg_bw w;
+    sg_bw_init(&w, buf, sizeof(buf));
+    if (level == 0 || sg_put_cavlc_level(&w, level, suffix_len, minus2, escape16) < 0) return -1;
+    int n = (int)w.pos * 8 + w.nacc;
+    while (w.nacc) sg_put(&w, 0, 1);
+    *bits = 0;
+    for (int i = 0; i < 8; i++) *bits = *bits << 8 | buf[i];
+    *bits >>= 64 - n;
+    return n <= 64 ? n : -1;
+}
 static void cavlc_block(enc *e, const int16_t *coef, int maxnum, int nC) {
     sg_bw *w = &e->bw;
     int level[16], run[16], total = 0, t1s = 0, last = -1;
@@ -267,42 +321,29 @@ static void cavlc_block(enc *e, const int16_t *coef, int maxnum, int nC) {
         if (abs(level[i]) != 1) break;
         t1s++;
     }
-    if (nC == -1)
+    if (nC == -1) {
         sg_put(w, sg_chroma_dc_token_bits[4 * total + t1s], sg_chroma_dc_token_len[4 * total + t1s]);
-    else {
+        syn_bit(SG_S_TOKEN + 3 * 4, 4 * total + t1s);
+    } else {
         int tbl = nC < 2 ? 0 : (nC < 4 ? 1 : (nC < 8 ? 2 : 3));
         sg_put(w, sg_coeff_token_bits[tbl][4 * total + t1s], sg_coeff_token_len[tbl][4 * total + t1s]);
+        syn_bit(SG_S_TOKEN + 3 * tbl, 4 * total + t1s);
     }
     if (!total) return;
     int suffix_len = (total > 10 && t1s < 3) ? 1 : 0;
+    g_syn[SG_S_START_SL1] += suffix_len;
     for (int i = 0; i < total; i++) {
         if (i < t1s) {
             sg_put(w, level[i] < 0, 1);
             continue;
         }
         int v = level[i];
-        int code = v > 0 ? 2 * v - 2 : -2 * v - 1; /* levelCode */
-        if (i == t1s && t1s < 3) code -= 2;
-        /* 9.2.2.1 inverse */
-        int prefix, suffix = 0, size = 0;
-        if (suffix_len == 0) {
-            if (code < 14)
-                prefix = code;
-            else if (code < 30)
-                prefix = 14, size = 4, suffix = code - 14;
-            else
-                prefix = 15, size = 12, suffix = code - 30;
-        } else {
-            if (code < (15 << suffix_len))
-                prefix = code >> suffix_len, size = suffix_len, suffix = code & ((1 << suffix_len) - 1);
-            else
-                prefix = 15, size = 12, suffix = code - (15 << suffix_len);
-        }
-        if (prefix == 15 && suffix >= 4096) { /* would need level_prefix >= 16: clamp (never hit at sane QPs) */
-            suffix = 4095;
-        }
-        sg_put(w, 1, prefix + 1);
-        if (size) sg_put(w, (uint32_t)suffix, size);
+        /* level_prefix > 15 exists in the High profiles only (A.2); the quantisers stay below 2001 and the stimulus keeps to the profile, so that a level
+         * that cannot be written is a defect of the generator: the stream is given up, never written differently from its reconstruction */
+        int prefix = sg_put_cavlc_level(w, v, suffix_len, i == t1s && t1s < 3, e->p.profile_idc == 100);
+        if (prefix < 0) w->overflow = 1;
+        syn_max(SG_S_PREFIX_MAX, prefix), syn_max(SG_S_LEVEL_MAX, abs(v));
+        if (prefix >= 14) g_syn[prefix == 14 ? SG_S_P14_SL : (prefix == 15 ? SG_S_P15_SL : SG_S_P16_SL)] |= 1 << suffix_len;
         if (suffix_len == 0) suffix_len = 1;
         if (abs(v) > (3 << (suffix_len - 1)) && suffix_len < 6) suffix_len++;
     }
@@ -313,11 +354,13 @@ static void cavlc_block(enc *e, const int16_t *coef, int maxnum, int nC) {
             sg_put(w, sg_chroma_dc_total_zeros_bits[total - 1][total_zeros], sg_chroma_dc_total_zeros_len[total - 1][total_zeros]);
         else
             sg_put(w, sg_total_zeros_bits[total - 1][total_zeros], sg_total_zeros_len[total - 1][total_zeros]);
+        g_syn[(maxnum == 4 ? SG_S_TZC : (maxnum == 15 ? SG_S_TZ15 : SG_S_TZ16)) + total - 1] |= 1 << total_zeros;
     }
     int zl = total_zeros;
     for (int i = 0; i < total - 1 && zl > 0; i++) {
         int t = (zl > 7 ? 7 : zl) - 1;
         sg_put(w, sg_run_bits[t][run[i]], sg_run_len[t][run[i]]);
+        g_syn[SG_S_RUN + t] |= 1 << run[i];
         zl -= run[i];
     }
 }
@@ -330,12 +373,14 @@ static int nc_luma(enc *e, int bx, int by) {
     int ia, ib;
     emb *a = lnb(e, bx - 1, by, &ia), *b = lnb(e, bx, by - 1, &ib);
     if (a && b) return (a->nnz[ia] + b->nnz[ib] + 1) >> 1;
+    g_syn[a || b ? SG_S_NC_ONE : SG_S_NC_NONE]++;
     return a ? a->nnz[ia] : (b ? b->nnz[ib] : 0);
 }
 static int nc_chroma(enc *e, int c, int cx, int cy) {
     int ia, ib;
     emb *a = cnb(e, cx - 1, cy, &ia), *b = cnb(e, cx, cy - 1, &ib);
     if (a && b) return (a->nnz[16 + 4 * c + ia] + b->nnz[16 + 4 * c + ib] + 1) >> 1;
+    g_syn[a || b ? SG_S_NC_ONE : SG_S_NC_NONE]++;
     return a ? a->nnz[16 + 4 * c + ia] : (b ? b->nnz[16 + 4 * c + ib] : 0);
 }
 
@@ -346,8 +391,12 @@ static void cabac_block(enc *e, const int16_t *coef, int cat, int maxnum, int cb
     int n = count_nz(coef, maxnum);
     if (cbf_inc >= 0) {
         sg_cabac_bin(w, 85 + cat * 4 + cbf_inc, n != 0);
+        g_syn[SG_S_CBF_INC + cat] |= 1 << cbf_inc;
         if (!n) return;
     }
+    g_syn[SG_S_CAT_BLOCKS + cat]++;
+    if (coef[maxnum - 1]) g_syn[SG_S_LAST_AT_END + cat]++;
+    if (n == maxnum) g_syn[SG_S_ALL_NONZERO + cat]++;
     int lastpos = maxnum - 1;
     while (lastpos > 0 && !coef[lastpos]) lastpos--;
     for (int i = 0; i < maxnum - 1; i++) {
@@ -371,11 +420,14 @@ static void cabac_block(enc *e, const int16_t *coef, int cat, int maxnum, int cb
         int a = abs(coef[i]) - 1; /* coeff_abs_level_minus1 */
         int inc0 = gt1 ? 0 : (1 + eq1 < 4 ? 1 + eq1 : 4);
         sg_cabac_bin(w, base + inc0, a > 0);
+        if (inc0 == 4) g_syn[SG_S_INC0_SAT] |= 1 << cat;
+        syn_max(SG_S_LEVEL_MAX_CABAC, a + 1);
         if (a == 0)
             eq1++;
         else {
             int lim = 4 - (cat == 3), inc = 5 + (gt1 < lim ? gt1 : lim);
             int pre = a < 14 ? a : 14;
+            if (gt1 >= lim) g_syn[SG_S_GT1_SAT] |= 1 << cat;
             for (int k = 1; k < pre; k++) sg_cabac_bin(w, base + inc, 1);
             if (a < 14)
                 sg_cabac_bin(w, base + inc, 0);
@@ -386,6 +438,7 @@ static void cabac_block(enc *e, const int16_t *coef, int cat, int maxnum, int cb
                     s -= 1 << k;
                     k++;
                 }
+                syn_max(SG_S_EGK_MAX, k);
                 sg_cabac_bypass(w, 0);
                 while (k--) sg_cabac_bypass(w, (s >> k) & 1);
             }
@@ -396,6 +449,7 @@ static void cabac_block(enc *e, const int16_t *coef, int cat, int maxnum, int cb
 }
 static int cbf_inc2(enc *e, emb *a, int fa, emb *b, int fb) {
     int ci = IS_INTRA(CURMB(e)->type);
+    if (!a || !b) g_syn[ci ? SG_S_CBF_UNAVAIL_INTRA : SG_S_CBF_UNAVAIL_INTER]++;
     return (a ? fa : ci) + 2 * (b ? fb : ci);
 }
 static int cbf_luma(enc *e, int bx, int by) {
@@ -561,6 +615,29 @@ static void cabac_dqp(enc *e, int dqp) {
     sg_cabac_bin(&e->bw, 60 + ctx, 0);
 }
 
+/* mb_qp_delta for a macroblock that wants QP_Y qp: the straight difference, or the wrapped one where that leaves -26..25 (7.4.5: the decoder takes
+ * (QP_Y,PRED + mb_qp_delta + 52) % 52) */
+static void code_dqp(enc *e, int qp) {
+    int dqp = qp - e->qp;
+    if (dqp > 25) dqp -= 52;
+    if (dqp < -26) dqp += 52;
+    if (e->p.cabac)
+        cabac_dqp(e, dqp);
+    else
+        sg_put_se(&e->bw, dqp);
+    if (dqp < g_syn[SG_S_DQP_MIN]) g_syn[SG_S_DQP_MIN] = dqp;
+    syn_max(SG_S_DQP_MAX, dqp);
+    if (e->qp + dqp > 51) g_syn[SG_S_DQP_WRAP_UP]++;
+    if (e->qp + dqp < 0) g_syn[SG_S_DQP_WRAP_DOWN]++;
+    if (qp < g_syn[SG_S_QPY_MIN]) g_syn[SG_S_QPY_MIN] = qp;
+    syn_max(SG_S_QPY_MAX, qp);
+    if (dqp && e->prev_kind) g_syn[SG_S_DQP_AFTER_SKIP + e->prev_kind - 1]++;
+    if (!e->p.mono && qp + e->p.chroma_qp_offset < 0) g_syn[SG_S_QPC_CLIP0]++;
+    if (!e->p.mono && qp + e->p.chroma_qp_offset > 51) g_syn[SG_S_QPC_CLIP51]++;
+    e->prev_dqp_nz = dqp != 0;
+    e->qp = qp, e->had_dqp = 1;
+}
+
 /* ------------------------------------------------------------------ motion vector prediction (8.4.1.3) */
 typedef struct {
     int ok, ref, x, y;
@@ -675,6 +752,112 @@ static int pred_ipm(enc *e, int bx, int by) {
 }
 static double deadzone(int intra) { return intra ? 1.0 / 3 : 1.0 / 6; }
 
+/* ------------------------------------------------------------------ syntax stimulus (sg_params::syntax_stim)
+ * One block of L coefficients in scan order: a drawn TotalCoeff, TrailingOnes, total_zeros, distribution of the zeros and magnitudes (see sg.h).  cap[k] is
+ * the largest |level| that passes the range guard alone at scan index k, maxmag the largest the profile can write. */
+static const int16_t stim_mags[] = {1, 1, 2, 2, 3, 3, 4, 7, 8, 13, 14, 15, 16, 17, 25, 29, 30, 31, 49, 59, 60, 61, 119, 120, 121, 239, 240, 241, 479, 480, 481,
+                                    1000, 2062, 2063, 2064, 2065, 4109, 4110, 6200, 8200};
+static void stim_pattern(enc *e, int16_t *out, int L, const int *cap, int maxmag) {
+    int mag[64], pos[64], runs[64], tc, r = (int)(rnd(e) % 100);
+    memset(out, 0, sizeof(int16_t) * (size_t)L);
+    if (r < 55)
+        tc = rnd_range(e, 0, L);
+    else if (e->dens == 0)
+        tc = r < 92 ? 0 : 1;
+    else if (e->dens == 1)
+        tc = rnd_range(e, 0, L < 3 ? L : 3);
+    else if (e->dens == 2)
+        tc = rnd_range(e, L < 2 ? L : 2, L < 9 ? L : 9);
+    else
+        tc = r < 65 ? L : (r < 80 ? L - 1 : rnd_range(e, L / 2, L));
+    if (e->heavy && !e->thin) tc = L;
+    if (e->thin == 1 && tc > (L > 16 ? 12 : 5)) tc = L > 16 ? 12 : 5;
+    if (e->thin >= 2 && tc > 1) tc = 1;
+    if (!tc) return;
+    /* magnitudes, from the highest frequency down */
+    int t1 = (int)(rnd(e) % 4), target = -1;
+    if (t1 > tc) t1 = tc;
+    for (int i = 0; i < tc; i++) {
+        mag[i] = i < t1 ? 1 : stim_mags[rnd(e) % (e->thin ? 8 : sizeof(stim_mags) / sizeof(stim_mags[0]))];
+        if (i == t1 && t1 < 3 && mag[i] == 1) mag[i] = 2;
+        if (rnd(e) & 1) mag[i] = -mag[i];
+    }
+    if (!e->thin && !e->p.cabac && tc > t1 && rnd(e) % 100 < 40) {
+        /* a ladder: the levels that take suffixLength to s, then one that needs level_prefix P there, then small ones */
+        int s = (int)(rnd(e) % 7), P = 14 + (int)(rnd(e) % (maxmag > 2063 ? 3 : 2)), sl0 = tc > 10 && t1 < 3, i = t1;
+        static const int step[5] = {4, 7, 13, 25, 49};
+        if (s == 0 && sl0) s = 1;
+        if (s == 1 && !sl0) mag[i++] = (rnd(e) & 1) ? 2 : -3;
+        for (int k = 0; k + 2 <= s; k++) mag[i++] = (rnd(e) & 1) ? step[k] : -step[k];
+        if (i < tc) {
+            int lo = s == 0 ? (P == 14 ? 14 : 30 + 4096 * (P - 15)) : (P == 14 ? 14 << s : (15 << s) + 4096 * (P - 15));
+            int hi = s == 0 ? (P == 14 ? 29 : (P == 15 ? 30 + 4095 : 30 + 12287)) : (P == 14 ? (15 << s) - 1 : (15 << s) + (P == 15 ? 4095 : 12287));
+            int pick = (int)(rnd(e) % 4), code = pick == 0 ? lo : (pick == 1 ? hi : (pick == 2 ? lo + 1 : rnd_range(e, lo, hi)));
+            if (i == t1 && t1 < 3) code += 2;
+            mag[i] = code & 1 ? -(code + 1) / 2 : (code + 2) / 2;
+            target = i;
+            for (int k = i + 1; k < tc; k++) mag[k] = (rnd(e) & 1) ? 1 + (int)(rnd(e) % 3) : -1 - (int)(rnd(e) % 3);
+        }
+    }
+    /* positions: total_zeros, and where the zeros lie; drawn again while the target does not fit where it would land */
+    for (int attempt = 0; attempt < 12; attempt++) {
+        int q = (int)(rnd(e) % 6), tz = q == 0 ? 0 : (q == 1 ? L - tc : rnd_range(e, 0, L - tc)), mode = (int)(rnd(e) % 3);
+        memset(runs, 0, sizeof(runs));
+        if (mode == 0) { /* one long run */
+            int slot = (rnd(e) & 1) ? 0 : (int)(rnd(e) % (uint32_t)tc), len = (rnd(e) & 1) ? tz : rnd_range(e, 0, tz);
+            runs[slot] += len, runs[tc - 1] += tz - len;
+        } else if (mode == 1)
+            for (int z = 0; z < tz; z++) runs[rnd(e) % (uint32_t)tc]++;
+        else
+            runs[tc - 1] = tz;
+        pos[0] = tc + tz - 1;
+        for (int i = 1; i < tc; i++) pos[i] = pos[i - 1] - 1 - runs[i - 1];
+        if (target < 0 || abs(mag[target]) <= (tc == 1 ? cap[pos[target]] : cap[pos[target]] * 3 / 4)) break;
+    }
+    /* one coefficient (the target, or any) may take three quarters of what the guard allows at its place, the others share one quarter: the sum of the scaled
+     * coefficients bounds the intermediates of the inverse transform, so that a full block stays full */
+    const int big = target >= 0 ? target : (int)(rnd(e) % (uint32_t)tc);
+    for (int i = 0; i < tc; i++) {
+        int lim = tc == 1 ? cap[pos[i]] : (i == big ? cap[pos[i]] * 3 / 4 : cap[pos[i]] / (4 * tc)), a = abs(mag[i]);
+        if (lim > maxmag) lim = maxmag;
+        if (e->thin && a > (e->thin == 1 ? 61 : 3)) a = 3;
+        if (e->heavy && !e->thin && i != big && i >= t1 && (rnd(e) & 1)) a = lim;
+        if (a > lim) a = lim > 0 ? lim : 1;
+        out[pos[i]] = (int16_t)(mag[i] < 0 ? -a : a);
+    }
+}
+/* the levels of one block after its quantiser: n = 16 (first = 1: an AC block of 15), 64, 0 (the 16 luma DC levels; ls points at LevelScale(0, 0)) or
+ * 4 (chroma DC, the same); kill: the block stays empty */
+static void stim(enc *e, int16_t *lev, int n, int first, int kill, const int *ls, int qp) {
+    if (!e->stim) return;
+    const int L = n == 0 ? 16 : n - first, maxmag = e->p.cabac || e->p.profile_idc == 100 ? 32767 : 2063;
+    int cap[64];
+    if (kill || e->thin >= 3)
+        memset(lev, 0, sizeof(int16_t) * (size_t)(n ? n : 16));
+    else if (e->thin >= 2 || e->heavy || rnd(e) % 100 < 85) {
+        for (int k = 0; k < L; k++) cap[k] = sg_guard_cap(n, k + first, ls, qp, first);
+        if (n == 64 && !e->p.cabac) /* CAVLC: four interleaved blocks of 16 */
+            for (int b4 = 0; b4 < 4; b4++) {
+                int16_t part[16];
+                int pcap[16];
+                for (int i = 0; i < 16; i++) pcap[i] = cap[4 * i + b4];
+                stim_pattern(e, part, 16, pcap, maxmag);
+                for (int i = 0; i < 16; i++) lev[4 * i + b4] = part[i];
+            }
+        else
+            stim_pattern(e, lev + first, L, cap, maxmag);
+    } else if (maxmag < 32767) /* (the quantisers stay below 2001) */
+        for (int k = 0; k < (n ? n : 16); k++) lev[k] = (int16_t)(lev[k] > maxmag ? maxmag : (lev[k] < -maxmag ? -maxmag : lev[k]));
+    if (n == 16)
+        sg_guard4(lev, ls, qp, first);
+    else if (n == 64)
+        sg_guard8(lev, ls, qp);
+    else if (n == 0)
+        sg_guard_luma_dc(lev, ls[0], qp);
+    else
+        sg_guard_chroma_dc(lev, ls[0], qp);
+}
+
 static void code_chroma(enc *e, int intra, const uint8_t pred[2][64]) {
     emb *m = CURMB(e);
     int W2 = e->W / 2, any_dc = 0, any_ac = 0;
@@ -694,10 +877,12 @@ static void code_chroma(enc *e, int intra, const uint8_t pred[2][64]) {
             e->cac[c][b][0] = 0;
             int16_t lev[16];
             sg_quant4(res, ls, qp, deadzone(intra), 1, lev);
+            stim(e, lev, 16, 1, e->kill_cac || e->kill_c || e->p.mono, ls, qp);
             memcpy(e->cac[c][b], lev, sizeof(lev));
             if (count_nz(lev, 16)) any_ac = 1;
         }
         sg_quant_chroma_dc(sums, ls[0], qp, deadzone(intra), e->cdc[c]);
+        stim(e, e->cdc[c], 4, 0, e->kill_c || e->p.mono, ls, qp);
         if (count_nz(e->cdc[c], 4)) any_dc = 1;
     }
     m->cbp_chroma = any_ac ? 2 : (any_dc ? 1 : 0);
@@ -735,6 +920,7 @@ static void code_luma_inter(enc *e, const uint8_t *pred /*16x16*/) {
             for (int y = 0; y < 8; y++)
                 for (int x = 0; x < 8; x++) res[y * 8 + x] = src[(y8 + y) * e->W + x8 + x] - pred[(y8 + y) * 16 + x8 + x];
             sg_quant8(res, e->ls8[1][qp % 6], qp, deadzone(0), e->luma8[b8]);
+            stim(e, e->luma8[b8], 64, 0, e->kill8 >> b8 & 1, e->ls8[1][qp % 6], qp);
             if (count_nz(e->luma8[b8], 64)) m->cbp_luma |= 1 << b8;
         } else
             for (int b4 = 0; b4 < 4; b4++) {
@@ -742,6 +928,7 @@ static void code_luma_inter(enc *e, const uint8_t *pred /*16x16*/) {
                 for (int y = 0; y < 4; y++)
                     for (int x = 0; x < 4; x++) res[y * 4 + x] = src[(yo + y) * e->W + xo + x] - pred[(yo + y) * 16 + xo + x];
                 sg_quant4(res, e->ls4[3][qp % 6], qp, deadzone(0), 0, e->luma[idx]);
+                stim(e, e->luma[idx], 16, 0, e->kill8 >> b8 & 1, e->ls4[3][qp % 6], qp);
                 if (count_nz(e->luma[idx], 16)) m->cbp_luma |= 1 << b8;
             }
     }
@@ -786,7 +973,7 @@ static void write_residual(enc *e) {
             if (n) m->nzmask |= (uint16_t)(0x33 << (by0 * 4 + bx0));
             continue;
         }
-        int any = 0;
+        int any = 0, full = 0;
         for (int b4 = 0; b4 < 4; b4++) {
             int idx = b8 * 4 + b4, r = blk_raster(idx), bx = r & 3, by = r >> 2, n;
             int16_t tmp[16];
@@ -810,7 +997,9 @@ static void write_residual(enc *e) {
             }
             m->nnz[r] = (uint8_t)n;
             if (n) m->nzmask |= (uint16_t)(1 << r), any = 1;
+            full += n == 16;
         }
+        if (m->t8x8 && full == 4) g_syn[SG_S_CAVLC_8X8_FULL]++;
         if (m->t8x8 && any) m->nzmask |= (uint16_t)(0x33 << (by0 * 4 + bx0));
     }
     if (m->cbp_chroma) {
@@ -887,6 +1076,24 @@ static void end_mb(enc *e) {
 
 /* choose the QP this MB would like to use */
 static int want_qp(enc *e) {
+    if (e->stim) { /* the whole 0..51: code_dqp() wraps where the straight difference is out of range */
+        int r = (int)(rnd(e) % 16), q;
+        if (r < (e->prev_kind ? 2 : 7)) return e->qp;
+        r = (int)(rnd(e) % 10);
+        if (r < 3)
+            q = e->slice_qp;
+        else if (r == 3)
+            q = (e->qp + 26) % 52; /* mb_qp_delta -26 */
+        else if (r == 4)
+            q = (e->qp + 25) % 52; /* +25 */
+        else if (r == 5)
+            q = (rnd(e) & 1) ? 0 : 51;
+        else if (r < 8)
+            q = e->slice_qp + rnd_range(e, -3, 3);
+        else
+            q = rnd_range(e, 0, 51);
+        return q < 0 ? 0 : (q > 51 ? 51 : q);
+    }
     if (!e->p.qp_jitter || rnd(e) % 8) return e->qp;
     int q = e->p.qp + rnd_range(e, -e->p.qp_jitter, e->p.qp_jitter);
     q = q < 10 ? 10 : (q > 51 ? 51 : q);
@@ -903,7 +1110,7 @@ static void encode_intra(enc *e, int islice) {
     const uint8_t *src = e->src + e->mby * 16 * W + e->mbx * 16;
     uint8_t *dst = e->cur->pl[0] + e->mby * 16 * W + e->mbx * 16;
     int r = rnd(e) % 1000, kind;
-    if (r < e->p.pcm_permille)
+    if (r < e->p.pcm_permille || e->force_pcm)
         kind = T_PCM;
     else {
         int k = rnd(e) % 100;
@@ -920,6 +1127,7 @@ static void encode_intra(enc *e, int islice) {
         for (int y = 0; y < 16; y++) memcpy(dst + y * W, e->pcm + 16 * y, 16);
         for (int c = 0; c < 2; c++)
             for (int y = 0; y < 8; y++) memcpy(e->cur->pl[1 + c] + (e->mby * 8 + y) * (W / 2) + e->mbx * 8, e->pcm + 256 + 64 * c + 8 * y, 8);
+        if (islice) g_syn[SG_S_MBTYPE_I] |= 1 << 25;
         if (cabac) {
             if (islice)
                 cabac_intra_type(e, 3, 1, 25);
@@ -960,9 +1168,11 @@ static void encode_intra(enc *e, int islice) {
             for (int y = 0; y < 4; y++)
                 for (int x = 0; x < 4; x++) res[y * 4 + x] = src[(yo + y) * W + xo + x] - best[(yo + y) * 16 + xo + x], sums[rr] += res[y * 4 + x];
             sg_quant4(res, e->ls4[0][qp % 6], qp, deadzone(1), 1, e->luma[idx]);
+            stim(e, e->luma[idx], 16, 1, e->kill_ac16, e->ls4[0][qp % 6], qp);
             if (count_nz(e->luma[idx], 16)) any_ac = 1;
         }
         sg_quant_luma_dc(sums, e->ls4[0][qp % 6][0], qp, deadzone(1), e->i16dc);
+        stim(e, e->i16dc, 0, 0, 0, e->ls4[0][qp % 6], qp);
         m->cbp_luma = any_ac ? 15 : 0;
         if (!any_ac) memset(e->luma, 0, sizeof(e->luma));
         int dc[16];
@@ -990,6 +1200,7 @@ static void encode_intra(enc *e, int islice) {
             for (int y = 0; y < 4; y++)
                 for (int x = 0; x < 4; x++) res[y * 4 + x] = src[(yo + y) * W + xo + x] - best[y * 4 + x];
             sg_quant4(res, e->ls4[0][qp % 6], qp, deadzone(1), 0, e->luma[idx]);
+            stim(e, e->luma[idx], 16, 0, e->kill8 >> (idx >> 2) & 1, e->ls4[0][qp % 6], qp);
             /* cbp is per 8x8: decide after the 4th block of each 8x8; reconstruct assuming "coded" and
              * fix up below if the whole 8x8 quantised to zero (then residual is zero anyway) */
             sg_residual4(e->luma[idx], e->ls4[0][qp % 6], qp, 0, 0, res);
@@ -1014,6 +1225,7 @@ static void encode_intra(enc *e, int islice) {
             for (int y = 0; y < 8; y++)
                 for (int x = 0; x < 8; x++) res[y * 8 + x] = src[(yo + y) * W + xo + x] - best[y * 8 + x];
             sg_quant8(res, e->ls8[0][qp % 6], qp, deadzone(1), e->luma8[b8]);
+            stim(e, e->luma8[b8], 64, 0, e->kill8 >> b8 & 1, e->ls8[0][qp % 6], qp);
             if (count_nz(e->luma8[b8], 64)) {
                 m->cbp_luma |= (uint8_t)(1 << b8);
                 sg_residual8(e->luma8[b8], e->ls8[0][qp % 6], qp, res);
@@ -1041,6 +1253,7 @@ static void encode_intra(enc *e, int islice) {
     /* ---- syntax ---- */
     int it = kind == T_I16 ? 1 + m->i16mode + 4 * m->cbp_chroma + (m->cbp_luma ? 12 : 0) : 0;
     e->raw_type = islice ? it : it + (e->slice_type == 1 ? 23 : 5);
+    if (islice) g_syn[SG_S_MBTYPE_I] |= 1 << it;
     if (cabac) {
         if (islice)
             cabac_intra_type(e, 3, 1, it);
@@ -1067,6 +1280,7 @@ static void encode_intra(enc *e, int islice) {
             /* pred_ipm must only see modes of blocks that precede this one: ipm of later blocks is still
              * final here, but the derivation only looks left/up, which always precede. */
             int pred = pred_ipm(e, bx, by), mode = m->ipm[rr];
+            g_syn[n == 4 ? SG_S_REM8 : SG_S_REM4] |= mode == pred ? 1 << 8 : 1 << (mode < pred ? mode : mode - 1);
             if (mode == pred) {
                 if (cabac)
                     sg_cabac_bin(w, 68, 1);
@@ -1100,6 +1314,7 @@ static void encode_intra(enc *e, int islice) {
         sg_put_ue(w, m->chroma_mode);
     if (kind != T_I16) {
         int cbp = m->cbp_luma | (m->cbp_chroma << 4);
+        syn_bit(SG_S_CBP_INTRA, cbp);
         if (cabac)
             cabac_cbp(e, cbp);
         else {
@@ -1109,13 +1324,7 @@ static void encode_intra(enc *e, int islice) {
         }
     }
     if (m->cbp_luma || m->cbp_chroma || kind == T_I16) {
-        int dqp = qp - e->qp;
-        if (cabac)
-            cabac_dqp(e, dqp);
-        else
-            sg_put_se(w, dqp);
-        e->prev_dqp_nz = dqp != 0;
-        e->qp = qp;
+        code_dqp(e, qp);
         write_residual(e);
     } else {
         e->prev_dqp_nz = 0;
@@ -1353,6 +1562,7 @@ static void encode_inter(enc *e, int kind) {
         }
     }
     int cbp = m->cbp_luma | (m->cbp_chroma << 4);
+    syn_bit(SG_S_CBP_INTER, cbp);
     if (cabac)
         cabac_cbp(e, cbp);
     else {
@@ -1368,13 +1578,7 @@ static void encode_inter(enc *e, int kind) {
             sg_put(w, m->t8x8, 1);
     }
     if (cbp) {
-        int dqp = qp - e->qp;
-        if (cabac)
-            cabac_dqp(e, dqp);
-        else
-            sg_put_se(w, dqp);
-        e->prev_dqp_nz = dqp != 0;
-        e->qp = qp;
+        code_dqp(e, qp);
         write_residual(e);
     } else {
         e->prev_dqp_nz = 0;
@@ -1779,6 +1983,7 @@ static void encode_b(enc *e, int kind) {
             }
         }
     int cbp = m->cbp_luma | (m->cbp_chroma << 4);
+    syn_bit(SG_S_CBP_INTER, cbp);
     if (cabac)
         cabac_cbp(e, cbp);
     else {
@@ -1794,13 +1999,7 @@ static void encode_b(enc *e, int kind) {
             sg_put(w, m->t8x8, 1);
     }
     if (cbp) {
-        int dqp = qp - e->qp;
-        if (cabac)
-            cabac_dqp(e, dqp);
-        else
-            sg_put_se(w, dqp);
-        e->prev_dqp_nz = dqp != 0;
-        e->qp = qp;
+        code_dqp(e, qp);
         write_residual(e);
     } else {
         e->prev_dqp_nz = 0;
@@ -2848,7 +3047,10 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
     memset(e->s8, 16, sizeof(e->s8));
     if (p->scaling_matrix < 0 || p->scaling_matrix > 3) p->scaling_matrix = 1;
     e->t8_req = p->transform8x8;
-    sg_set_range_guard(p->scaling_matrix >= 2);
+    e->stim = p->syntax_stim < 0 || (p->syntax_stim & 3) == 3 ? 0 : p->syntax_stim & 3;
+    sg_set_range_guard(p->scaling_matrix >= 2 || e->stim);
+    memset(g_syn, 0, sizeof(g_syn));
+    g_syn[SG_S_DQP_MIN] = g_syn[SG_S_QPY_MIN] = 1 << 20, g_syn[SG_S_DQP_MAX] = g_syn[SG_S_QPY_MAX] = -(1 << 20);
     if (p->scaling_matrix == 1) {
         for (int l = 0; l < 6; l++) memcpy(e->s4[l], l < 3 ? sg_default4x4_intra : sg_default4x4_inter, 16);
         memcpy(e->s8[0], sg_default8x8_intra, 64);
@@ -3041,6 +3243,7 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
             for (int i = 0; i < 4; i++)
                 for (int c = 0; c < 2; c++) e->wp_cw[i][c] = e->wb_cw1[i][c] = 1 << e->wp_cd, e->wp_co[i][c] = e->wb_co1[i][c] = 0;
         for (int i = 0; i < e->wmb * e->hmb; i++) e->mb[i].type = T_NONE;
+        e->pic_no++;
         /* the slices of this picture: (first macroblock, macroblock count), in the order they will be sent */
         int sl_first[512], sl_count[512], nsl = 0;
         if (p->slice_groups > 1) {
@@ -3088,13 +3291,48 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
             }
             write_slice_header(e, first, idr, frame_num, idr_id, pic_poc & (p->poc_step > 1 ? 65535 : 255));
             e->qp = e->slice_qp, e->prev_dqp_nz = 0, e->skip_run = 0;
+            e->prev_kind = e->run_len = 0, e->sk_from = e->sk_to = -1, e->pcm_last = 0;
+            int32_t syn_slice[SG_S_COUNT];
+            memcpy(syn_slice, g_syn, sizeof(syn_slice));
+            if (e->stim) { /* a run of skipped macroblocks longer than a row, a slice that ends in a run, one that ends in I_PCM */
+                const int mode = (int)(rnd(e) % 4), n = sl_count[s], len = e->wmb + 1 + (int)(rnd(e) % 3);
+                if (mode == 1 && !intra_pic && n > len + 1)
+                    e->sk_from = rnd_range(e, 0, n - len - 1), e->sk_to = e->sk_from + len;
+                else if (mode == 2 && !intra_pic)
+                    e->sk_from = n - 1 - (n > 3 ? (int)(rnd(e) % 3) : 0), e->sk_to = n;
+                else if (mode == 3)
+                    e->pcm_last = 1;
+            }
             if (p->cabac) {
                 while (!sg_bw_aligned(&e->bw)) sg_put(&e->bw, 1, 1);
                 sg_cabac_init_ctx(&e->bw, intra_pic ? 0 : 1 + e->init_idc, e->slice_qp);
                 sg_cabac_start(&e->bw);
             }
             for (int addr = first, left = sl_count[s]; left > 0; left--, addr = sg_next_mb(e, addr)) {
+                /* syntax_stim: the macroblock is coded again, thinner, while it has more than 3200 bits; everything it changed outside its own samples and
+                 * its own entries of the tables is put back first */
+                const sg_bw bw0 = e->bw;
+                const int qp0 = e->qp, nz0 = e->prev_dqp_nz, run0 = e->skip_run, len0 = e->run_len, idx = sl_count[s] - left;
+                const int32_t zeroed0 = sg_guard_zeroed;
+                int32_t rng0[SG_R_COUNT], syn0[SG_S_COUNT];
+                memcpy(rng0, g_rng, sizeof(rng0)), memcpy(syn0, g_syn, sizeof(syn0));
+                e->thin = 0;
+              again:
                 begin_mb(e, addr);
+                e->had_dqp = 0, e->force_pcm = 0;
+                const int force_skip = idx >= e->sk_from && idx < e->sk_to;
+                if (e->stim) {
+                    const uint32_t h = hash32(p->seed ^ (uint32_t)((e->mbx >> 1) * 7919 + (e->mby >> 1) * 104729 + e->pic_no * 1299709));
+                    e->dens = (int)((rnd(e) % 100 < 60 ? h : rnd(e)) & 3);
+                    e->kill8 = 0;
+                    for (int b8 = 0; b8 < 4; b8++) e->kill8 |= (rnd(e) % 5 < 2) << b8;
+                    if (rnd(e) % 8 == 0) e->kill8 = 15;
+                    e->kill_ac16 = rnd(e) % 4 == 0, e->kill_cac = rnd(e) % 4 == 0, e->kill_c = rnd(e) % 5 == 0;
+                    if (rnd(e) % 10 == 0) e->kill8 = 15, e->kill_c = 1; /* nothing coded: no mb_qp_delta unless it is Intra16x16 */
+                    e->heavy = rnd(e) % 12 == 0;
+                    if (e->heavy && !e->thin) e->kill8 = e->kill_ac16 = e->kill_cac = e->kill_c = 0;
+                    e->force_pcm = e->pcm_last && left == 1;
+                }
                 if (intra_pic)
                     encode_intra(e, 1);
                 else if (bpic) {
@@ -3109,6 +3347,8 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
                         kind = T_P16x8 + (int)(rnd(e) % 3);
                     else
                         kind = T_P16;
+                    if (force_skip) kind = T_BSKIP;
+                    if (e->force_pcm) kind = T_I4;
                     if (p->cabac) {
                         emb *a = MBA(e), *b = MBB(e);
                         sg_cabac_bin(&e->bw, 24 + (a && !IS_SKIPPED(a->type)) + (b && !IS_SKIPPED(b->type)), kind == T_BSKIP);
@@ -3132,6 +3372,8 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
                         kind = T_P16x8 + (int)(rnd(e) % 3);
                     else
                         kind = T_P16;
+                    if (force_skip) kind = T_SKIP;
+                    if (e->force_pcm) kind = T_I4;
                     if (p->cabac) {
                         emb *a = MBA(e), *b = MBB(e);
                         sg_cabac_bin(&e->bw, 11 + (a && a->type != T_SKIP) + (b && b->type != T_SKIP), kind == T_SKIP);
@@ -3149,8 +3391,26 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
                         encode_inter(e, kind);
                 }
                 end_mb(e);
+                {
+                    const int bits = (int)(e->bw.pos - bw0.pos) * 8 + e->bw.nacc - bw0.nacc + e->bw.outstanding - bw0.outstanding;
+                    if (e->stim == 1 && bits > 3200 && e->thin < 3) {
+                        e->bw = bw0, e->qp = qp0, e->prev_dqp_nz = nz0, e->skip_run = run0, e->run_len = len0, sg_guard_zeroed = zeroed0;
+                        memcpy(g_rng, rng0, sizeof(rng0)), memcpy(g_syn, syn0, sizeof(syn0));
+                        g_syn[SG_S_THINNED]++, memcpy(syn0, g_syn, sizeof(syn0));
+                        e->thin++;
+                        goto again;
+                    }
+                    syn_max(SG_S_MB_BITS_MAX, bits);
+                    const int t = CURMB(e)->type;
+                    e->run_len = IS_SKIPPED(t) ? e->run_len + 1 : 0;
+                    syn_max(SG_S_SKIP_RUN_MAX, e->run_len);
+                    e->prev_kind = IS_SKIPPED(t) ? 1 : (t == T_PCM ? 2 : (e->had_dqp ? 0 : 3));
+                    if (left == 1 && IS_SKIPPED(t)) g_syn[SG_S_END_IN_SKIP]++;
+                    if (left == 1 && t == T_PCM) g_syn[SG_S_END_IN_PCM]++;
+                }
                 if (p->cabac) sg_cabac_terminate(&e->bw, left == 1);
             }
+            if (e->stim && (p->syntax_stim & 4) && !bpic) memcpy(g_syn, syn_slice, sizeof(syn_slice)); /* count B slices only */
             if (p->cabac)
                 while (!sg_bw_aligned(&e->bw)) sg_put(&e->bw, 0, 1);
             else {

@@ -95,5 +95,16 @@ void sg_set_field_mode(int on);
  * (scaling lists with large entries); sg_guard_zeroed counts them since the call */
 void sg_set_range_guard(int on);
 extern _Thread_local int32_t sg_guard_zeroed;
+/* the guard alone, as the quantisers apply it (nothing happens while it is off): for levels that were changed after the quantiser ran */
+void sg_guard4(int16_t *lev_scan, const int *ls, int qp, int skip_dc);
+void sg_guard8(int16_t *lev_scan, const int *ls, int qp);
+void sg_guard_luma_dc(int16_t *lev_scan, int ls00, int qp);
+void sg_guard_chroma_dc(int16_t *lev4, int ls00, int qpc);
+/* the largest |level| at scan index k of a block of n = 16 / 64 coefficients (n = 0: a luma DC level, n = 4: a chroma DC level; ls then points at
+ * LevelScale(0, 0)) that the guard lets through when it stands alone in its block */
+int sg_guard_cap(int n, int k, const int *ls, int qp, int skip_dc);
+/* 9.2.2.1: one coefficient level of a CAVLC block (level_prefix, level_suffix) at suffixLength suffix_len; minus2 = the first level after fewer than
+ * three trailing ones.  Returns level_prefix, or -1 where the level needs level_prefix > 15 and escape16 is 0 (Baseline / Main / Extended) */
+int sg_put_cavlc_level(sg_bw *w, int level, int suffix_len, int minus2, int escape16);
 
 #endif

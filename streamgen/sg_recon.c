@@ -442,6 +442,33 @@ static void guard_block(int16_t *lev, int n, int first, const int *ls, int qp, i
         lev[big] = 0, sg_guard_zeroed++;
     }
 }
+void sg_guard4(int16_t *lev, const int *ls, int qp, int skip_dc) {
+    if (g_guard) guard_block(lev, 16, skip_dc ? 1 : 0, ls, qp, skip_dc ? GUARD_AC : GUARD_ALL);
+}
+void sg_guard8(int16_t *lev, const int *ls, int qp) {
+    if (g_guard) guard_block(lev, 64, 0, ls, qp, GUARD_ALL);
+}
+/* the largest |level| at scan index k of a block of n = 16 / 64 coefficients (n = 0: a luma DC level, n = 4: a chroma DC level) that the guard lets
+ * through when it stands alone in its block */
+int sg_guard_cap(int n, int k, const int *ls, int qp, int skip_dc) {
+    const int per = qp / 6;
+    long long cap;
+    if (n == 0)
+        cap = per >= 6 ? (long long)GUARD_DC / ((long long)ls[0] << (per - 6)) : ((long long)GUARD_DC << (6 - per)) / ls[0];
+    else if (n == 4)
+        cap = ((long long)GUARD_DC << 5) / ((long long)ls[0] << per);
+    else {
+        const long long limit = (skip_dc ? GUARD_AC : GUARD_ALL) - 40, l = ls[n == 16 ? g_scan4[k] : g_scan8[k]];
+        const int sh = n == 16 ? 4 : 6;
+        cap = per >= sh ? limit / (l << (per - sh)) : (limit << (sh - per)) / l;
+        if (n == 64) { /* an odd row or column of the 8x8 transform reaches 3 / 2 of its coefficient on the way */
+            const int pos = g_scan8[k];
+            cap = cap * 4 / (((pos & 1) ? 3 : 2) * ((pos & 8) ? 3 : 2)) - 8;
+        }
+    }
+    cap -= 1;
+    return cap < 0 ? 0 : (cap > 32767 ? 32767 : (int)cap);
+}
 static void hadamard4(const int *in, int *out) {
     int t[16];
     for (int r = 0; r < 4; r++) {
@@ -529,7 +556,7 @@ void sg_quant4(const int *resid, const int *ls, int qp, double dead, int skip_dc
         /* resid ~= lev * ls * scale * B / 64 */
         lev[k] = dead_round(64.0 * acc / (norm4[u] * norm4[v] * ls[pos] * scale), dead);
     }
-    if (g_guard) guard_block(lev, 16, skip_dc ? 1 : 0, ls, qp, skip_dc ? GUARD_AC : GUARD_ALL);
+    sg_guard4(lev, ls, qp, skip_dc);
 }
 void sg_quant8(const int *resid, const int *ls, int qp, double dead, int16_t *lev) {
     init_basis();
@@ -541,7 +568,7 @@ void sg_quant8(const int *resid, const int *ls, int qp, double dead, int16_t *le
             for (int x = 0; x < 8; x++) acc += resid[y * 8 + x] * basis8[v][y] * basis8[u][x];
         lev[k] = dead_round(64.0 * acc / (norm8[u] * norm8[v] * ls[pos] * scale), dead);
     }
-    if (g_guard) guard_block(lev, 64, 0, ls, qp, GUARD_ALL);
+    sg_guard8(lev, ls, qp);
 }
 void sg_quant_luma_dc(const int *sums, int ls00, int qp, double dead, int16_t *lev) {
     /* wanted DC coefficient of block i: d_i = 64 * sum_i / 16; d = (H c H) * ls00 * 2^(qp/6-6)  =>  c = H d H / 16 / (...) */
@@ -550,8 +577,11 @@ void sg_quant_luma_dc(const int *sums, int ls00, int qp, double dead, int16_t *l
     hadamard4(d4, f);
     double scale = ls00 * ldexp(1.0, qp / 6 - 6);
     for (int k = 0; k < 16; k++) lev[k] = dead_round(4.0 * f[g_scan4[k]] / 16.0 / scale, dead);
+    sg_guard_luma_dc(lev, ls00, qp);
+}
+void sg_guard_luma_dc(int16_t *lev, int ls00, int qp) {
     while (g_guard) { /* the transformed levels and the scaled DC values (8.5.10) */
-        int c[16], pk = 0, big = 0;
+        int c[16], f[16], pk = 0, big = 0;
         for (int k = 0; k < 16; k++) c[g_scan4[k]] = lev[k], big = abs(lev[k]) > abs(lev[big]) ? k : big;
         hadamard4(c, f);
         long long worst = 0;
@@ -568,6 +598,9 @@ void sg_quant_chroma_dc(const int *s, int ls00, int qpc, double dead, int16_t *l
     int f[4] = {s[0] + s[1] + s[2] + s[3], s[0] - s[1] + s[2] - s[3], s[0] + s[1] - s[2] - s[3], s[0] - s[1] - s[2] + s[3]};
     double scale = ls00 * ldexp(1.0, qpc / 6) / 32.0;
     for (int i = 0; i < 4; i++) lev[i] = dead_round(4.0 * f[i] / 4.0 / scale, dead);
+    sg_guard_chroma_dc(lev, ls00, qpc);
+}
+void sg_guard_chroma_dc(int16_t *lev, int ls00, int qpc) {
     while (g_guard) { /* 8.5.11 */
         int big = 0;
         long long worst = 0;

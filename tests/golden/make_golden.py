@@ -88,6 +88,23 @@ def deblock_vectors():
 
 deblock_vectors()
 
+
+def entropy_syntax_vectors():
+    """tests/syntaxutil.py: the recipes at the ends of the entropy syntax (streamgen's syntax_stim)."""
+    import syntaxutil
+    out = {}
+    for name in sorted(syntaxutil.RECIPES):
+        s, rec, _ = streamgen.encode(**syntaxutil.RECIPES[name])
+        pocs = [int(x) for x in streamgen.last_pocs()]
+        frames, _ = oracle.decode(s, crop=False)
+        assert (frames == rec).all(), name
+        out[name] = {"stream_md5": hashlib.md5(s).hexdigest(), "frames_md5": hashlib.md5(rec.tobytes()).hexdigest(), "stream_bytes": len(s), "pocs": pocs}
+    json.dump(out, open(os.path.join(HERE, "entropy_syntax_md5.json"), "w"), indent=1, sort_keys=True)
+    print("wrote", len(out), "entropy syntax vectors")
+
+
+entropy_syntax_vectors()
+
 # the characterisation trace of the product's picture management (tests/dpbtrace.py; CPU, null device): MD5 of the trace text of every case.  It
 # pins what the code DOES, so it is written once and not again for a change that is meant to keep behaviour.  Only with --dpb-trace.
 if "--dpb-trace" in sys.argv[1:]:

@@ -51,15 +51,18 @@ def test_golden_file_lists_the_recipes():
 
 
 def test_new_knobs_at_zero_change_nothing(sg):
-    """wp_range, poc_step, mv_reach, mv_margin, contrast and dbf_per_slice at 0 are today's streams, byte for byte (the golden files of the matrices show the same
+    """wp_range, poc_step, mv_reach, mv_margin, contrast, dbf_per_slice and syntax_stim at 0 are today's streams, byte for byte (the golden files of the matrices show the same
     for every recipe there is); out-of-range settings of the knobs do not leave the generator's clamps."""
     kw = dict(width=64, height=48, frames=4, idr_period=0, profile_idc=77, cabac=1, weighted_pred=1, num_ref_frames=2, seed=5)
     a = sg.encode(**kw)[0]
-    assert a == sg.encode(**dict(kw, wp_range=0, poc_step=0, mv_reach=0, mv_margin=0, contrast=0, dbf_per_slice=0, trace_deblock=0))[0] == sg.encode(**dict(kw, poc_step=1))[0]
+    assert a == sg.encode(**dict(kw, wp_range=0, poc_step=0, mv_reach=0, mv_margin=0, contrast=0, dbf_per_slice=0, trace_deblock=0, syntax_stim=0))[0] == sg.encode(**dict(kw, poc_step=1))[0]
     assert sg.last_ranges()["scaling_forms"] == 0 and sg.last_ranges()["guard_zeroed"] == 0
     assert sg.last_deblock_trace() == []
-    for k in ("wp_range", "poc_step", "mv_reach", "contrast", "dbf_per_slice"):
+    for k in ("wp_range", "poc_step", "mv_reach", "contrast", "dbf_per_slice", "syntax_stim"):
         assert a != sg.encode(**dict(kw, **{k: 2}))[0], k
+    assert a != sg.encode(**dict(kw, syntax_stim=1))[0]
+    # adding 4 only says which slices the syntax counters count; 3 is no stimulus
+    assert sg.encode(**dict(kw, syntax_stim=1))[0] == sg.encode(**dict(kw, syntax_stim=5))[0] and a == sg.encode(**dict(kw, syntax_stim=3))[0]
     # the deblocking trace is a record, not a knob: the same stream and reconstruction with it, one entry per picture
     b, rec, _ = sg.encode(**dict(kw, trace_deblock=1))
     assert a == b and np.array_equal(rec, sg.encode(**kw)[1]) and sg.last_deblock_trace() == []
