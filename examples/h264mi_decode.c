@@ -1,7 +1,7 @@
 /*
  * examples/h264mi_decode.c -- the C ABI from plain C: decode an Annex-B file to raw I420 on the GPU.
  *
- *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--conceal...] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge] [--field-rate]
+ *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--conceal...] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge|motion|motion-edge] [--field-rate]
  *
  * --nv12 / --rgb write NV12 / tight R, G, B bytes instead of I420: the frames are converted on the device (h264mi_batch_convert_device into a
  * device buffer, matrix and range from each frame's own SPS) and copied to the host from there.  --scale WxH writes every frame at W x H instead of
@@ -9,7 +9,10 @@
  * every frame as a model-input item instead (h264mi_batch_tensor_device): letterboxed into a W x H canvas on grey (114, 114, 114), float32 in three
  * planes R, G, B, each value v / 255 (scale 1 / 255, bias 0), bilinear, matrix and range from each frame's own SPS.  --deinterlace MODE deinterlaces
  * every frame on the device first (h264mi_batch_deinterlace: the first field's parity is kept) and writes the derived frames -- through whichever of
- * the paths above is chosen -- instead of the woven ones; with --field-rate two per frame, the first field's then the second's.  The HIP calls of these
+ * the paths above is chosen -- instead of the woven ones; with --field-rate two per frame, the first field's then the second's.  --deinterlace motion /
+ * motion-edge are the motion-adaptive modes that pull from field / edge (h264mi_batch_deinterlace_motion with H264MI_DEINT_HISTORY): a frame is
+ * deinterlaced against the frame before it in output order, and the first frame of a batch against the last one of the batch before, so a file decoded
+ * in several batches (frames_per_batch) comes out as if it had been decoded in one.  The HIP calls of these
  * paths are the only HIP this file needs; they are declared below, so it still builds without the HIP headers.
  *
  * The file includes nothing but include/h264mi.h and the C library.
@@ -42,16 +45,18 @@ static int fail(const char *what, int code) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge] [--field-rate]\n", argv[0]);
+        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge|motion|motion-edge] [--field-rate]\n", argv[0]);
         return 2;
     }
-    int deint = -1, deint_rate = 1; /* --deinterlace MODE and --field-rate (the last arguments of all): derived frames instead of the woven ones */
+    int deint = -1, deint_rate = 1, deint_motion = 0; /* --deinterlace MODE and --field-rate (the last arguments of all): derived frames instead of the woven ones */
     if (argc > 3 && !strcmp(argv[argc - 1], "--field-rate")) deint_rate = 2, argc--;
     if (argc > 4 && !strcmp(argv[argc - 2], "--deinterlace")) {
         const char *m = argv[argc - 1];
+        deint_motion = !strncmp(m, "motion", 6); /* motion: pulled from field; motion-edge: from edge */
+        if (deint_motion) m = !strcmp(m, "motion") ? "field" : !strcmp(m, "motion-edge") ? "edge" : "";
         deint = !strcmp(m, "field") ? H264MI_DEINT_FIELD : !strcmp(m, "blend") ? H264MI_DEINT_BLEND : !strcmp(m, "edge") ? H264MI_DEINT_EDGE : -1;
         if (deint < 0) {
-            fprintf(stderr, "--deinterlace %s: expected field, blend or edge\n", m);
+            fprintf(stderr, "--deinterlace %s: expected field, blend, edge, motion or motion-edge\n", argv[argc - 1]);
             return 2;
         }
         argc -= 2;
@@ -210,7 +215,10 @@ int main(int argc, char **argv) {
                 int32_t k = 0, src = 0; /* src: the stream the frames are taken from */
                 h264mi_stream_frame_count(dec, 0, &k);
                 if (deint >= 0) { /* one launch makes the derived frames of the batch: frames 0 .. k - 1 of the pseudo-stream */
-                    if ((r = h264mi_batch_deinterlace(dec, 0, deint, deint_rate, &k)) != H264MI_OK) return fail("h264mi_batch_deinterlace", r);
+                    if (deint_motion) { /* with the history: the batch's first frame in output order is pulled from the last one of the batch before */
+                        if ((r = h264mi_batch_deinterlace_motion(dec, 0, deint, deint_rate, H264MI_DEINT_HISTORY, &k)) != H264MI_OK) return fail("h264mi_batch_deinterlace_motion", r);
+                    } else if ((r = h264mi_batch_deinterlace(dec, 0, deint, deint_rate, &k)) != H264MI_OK)
+                        return fail("h264mi_batch_deinterlace", r);
                     src = H264MI_STREAM_DERIVED;
                 }
                 const size_t need = H264MI_I420_SIZE(info.coded_width, info.coded_height);

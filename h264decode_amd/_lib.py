@@ -51,6 +51,7 @@ Nal, Sps, Pps, SliceHdr, Config, BatchInfo, FrameInfo = (_S["h264mi_nal"], _S["h
 TensorSpec, TensorItem = _S["h264mi_tensor_spec"], _S["h264mi_tensor_item"]
 FieldInfo, DeintItem = _S["h264mi_field_info"], _S["h264mi_deint_item"]
 SideItem = _S["h264mi_side_item"]
+DeintMotionItem = _S["h264mi_deint_motion_item"]
 
 
 def build(force=False):
@@ -154,6 +155,10 @@ def load():
         "h264mi_frame_fields": [vp, I32, I32, P(FieldInfo)],
         "h264mi_items_deinterlace": [vp, I32, P(DeintItem), I32, P(I32)],
         "h264mi_batch_deinterlace": [vp, I32, I32, I32, P(I32)],
+        "h264mi_deint_motion_pixel": [P(ctypes.c_uint8), P(ctypes.c_uint8), I32, P(I32)],
+        "h264mi_items_deinterlace_motion": [vp, I32, P(DeintMotionItem), I32, P(I32)],
+        "h264mi_batch_deinterlace_motion": [vp, I32, I32, I32, I32, P(I32)],
+        "h264mi_derived_prev": [vp, I32, P(I32)],
         "h264mi_side_size": [I32, I32, I32, P(I32), P(I32), P(SZ)],
         "h264mi_frame_ref_pocs": [vp, I32, I32, I32, I32, P(I32), P(I32), I32, P(I32)],
         "h264mi_items_side_device": [vp, I32, P(SideItem), I32, vp, SZ, P(SZ)],
@@ -202,4 +207,5 @@ EXPORTS = ["h264mi_annexb_scan", "h264mi_nal_parse", "h264mi_sps_parse", "h264mi
            "h264mi_scale_taps", "h264mi_frame_scale_device", "h264mi_batch_scale_device",
            "h264mi_fit_rect", "h264mi_tensor_size", "h264mi_items_tensor_device", "h264mi_batch_tensor_device",
            "h264mi_deint_rows", "h264mi_frame_fields", "h264mi_items_deinterlace", "h264mi_batch_deinterlace",
+           "h264mi_deint_motion_pixel", "h264mi_items_deinterlace_motion", "h264mi_batch_deinterlace_motion", "h264mi_derived_prev",
            "h264mi_side_size", "h264mi_frame_ref_pocs", "h264mi_items_side_device", "h264mi_batch_side_device"]

@@ -465,6 +465,7 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
         (void)harvest_status(d, g); // a batch nobody synchronised on: its failures still mark their streams (need_idr) before this parse
     }
     reset_staging_set(d, g, prev_stage);
+    g.seq = ++d->prep_seq;
     Scan sc;
     int r = scan_and_stage(d, g, n_streams, bufs, lens, sc);
     if (r == H264MI_OK) r = parse_streams(d, g, n_streams, bufs, lens, sc);

@@ -136,6 +136,7 @@ struct Stage {
     hipEvent_t ev_side = nullptr;
     uint32_t *d_cmap = nullptr, *h_cmap = nullptr; // error concealment: per picture where its slices are in the sorted slice table (k_conceal)
     std::vector<std::vector<OutFrame>> out; // per stream: frames of this batch in decoding order
+    uint64_t seq = 0; // which h264mi_batch_prepare made this batch, counted from 1 (h264mi_decoder::prep_seq): what a deinterlacing history is dated by
     bool prepared = false, executed = false;
     bool harvested = true; // the entropy kernels' per-slice status words of the last execute have been looked at (harvest_status)
     bool retried = false;  // the batch has been repeated with the whole residual pool (retry_exhausted)
@@ -160,13 +161,23 @@ struct DescTables {
     hipEvent_t ev[2] = {nullptr, nullptr};
     int slot = 0;
 };
-enum { OUT_PACK, OUT_CONVERT, OUT_SCALE, OUT_TENSOR, OUT_DEINT, OUT_SIDE, OUT_FAMILIES }; // K6, K7, K8, K9, K10, K11
+enum { OUT_PACK, OUT_CONVERT, OUT_SCALE, OUT_TENSOR, OUT_DEINT, OUT_SIDE, OUT_DEINT_MOTION, OUT_FAMILIES }; // K6, K7, K8, K9, K10, K11, K10 motion-adaptive
 
 // A derived (deinterlaced) frame: frame k of the pseudo-stream H264MI_STREAM_DERIVED.  `of`: its source's OutFrame (what the accessors report); off: its
-// slot in the arena, in the layout of a frame slot of the source's coded size
+// slot in the arena, in the layout of a frame slot of the source's coded size; prev: what it was made from besides its source (h264mi_derived_prev) -- a
+// frame of the source's stream, H264MI_DEINT_PREV_NONE (every frame of the spatial modes) or H264MI_DEINT_PREV_HISTORY
 struct DerivedFrame {
     OutFrame of;
     size_t off;
+    int prev = H264MI_DEINT_PREV_NONE;
+};
+// K10, motion-adaptive: a stream's history -- the source of its last frame in output order of the last batch that h264mi_batch_deinterlace_motion took
+// one from, in the stream's slot of h264mi_decoder::d_history.  valid: cleared by the resets; batch: Stage::seq of that batch (the history serves the
+// batch prepared right after it and no other); of: the frame's geometry, which a frame that takes it as its predecessor must share
+struct DeintHistory {
+    bool valid = false;
+    uint64_t batch = 0;
+    OutFrame of;
 };
 
 struct h264mi_decoder {
@@ -248,6 +259,10 @@ struct h264mi_decoder {
     std::vector<DerivedFrame> derived;
     uint8_t *d_derived = nullptr;
     size_t derived_cap = 0;
+    // K10, motion-adaptive: one frame slot per stream (slot_bytes each), allocated by the first call that takes a history and kept; what is in them
+    uint8_t *d_history = nullptr;
+    std::vector<DeintHistory> history;
+    uint64_t prep_seq = 0; // h264mi_batch_prepare calls so far
     std::vector<float> launch_ms[4]; // duration of every launch of the last profiled pass, per kernel
 };
 

@@ -223,6 +223,18 @@ typedef struct {
     uint32_t parity; // 0 / 1, resolved
 } DeintDesc;
 extern "C" __global__ void k_deint(const DeintDesc *descs, uint8_t *dst, int pairs_per_block);
+// K10, motion-adaptive (k_deint_motion.hip): a list of (frame, predecessor, spatial mode, parity) items -> deinterlaced frames, by the rule of
+// include/h264mi.h ("Motion-adaptive deinterlacing"); slots, grid and thread item as k_deint.  The predecessor has the source's layout: a frame of the
+// pool, or a stream's history slot
+typedef struct {
+    uint64_t src;     // as PackDesc
+    uint64_t dst_off; // as DeintDesc
+    uint32_t W, H, x0, y0, w, h;
+    uint32_t mode;   // H264MI_DEINT_FIELD / _EDGE: what a missing row is without motion information, and what it is pulled from
+    uint32_t parity; // 0 / 1, resolved
+    uint64_t prev;   // Y plane of the predecessor (the same coded size and display rectangle); 0: none -- the frame is mode's frame
+} DeintMotionDesc;
+extern "C" __global__ void k_deint_motion(const DeintMotionDesc *descs, uint8_t *dst, int pairs_per_block);
 // K11 (k_side.hip): a list of frames -> planes of macroblock side information per 4x4 luma block, by the rule of include/h264mi.h ("Macroblock side
 // information"): a re-layout of the pictures' MbRec / MbMv1 records, no sample is read.  grid = (items, ceil(macroblock rows the largest grid touches /
 // rows_per_block)), block = 256; one lane per macroblock, four cells (8 bytes) per store on the aligned path

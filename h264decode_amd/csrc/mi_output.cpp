@@ -1,8 +1,8 @@
 // h264decode_amd/csrc/mi_output.cpp -- the output stage of libh264mi.so: what leaves the frame pool on the device.  K6 (k_pack: tight I420), K7
-// (k_convert: NV12 / RGB), K8 (k_scale: resized) and K9 (k_tensor: model input) over a list of frames of the last executed batch, K10 (k_deint:
-// deinterlaced frames, which K6 .. K9 read like frames of the batch), and the device-free rule functions of include/h264mi.h that say what those
-// kernels compute (h264mi_output_size, _csc_resolve, _scale_taps, _fit_rect, _tensor_size, _deint_rows, _side_size), and K11 (k_side: the macroblock
-// records of the batch as planes of side information).  The six kernel families share ONE launch discipline (stage_descs / fence_launch below); each
+// (k_convert: NV12 / RGB), K8 (k_scale: resized) and K9 (k_tensor: model input) over a list of frames of the last executed batch, K10 (k_deint and
+// k_deint_motion: deinterlaced frames, which K6 .. K9 read like frames of the batch), and the device-free rule functions of include/h264mi.h that say what those
+// kernels compute (h264mi_output_size, _csc_resolve, _scale_taps, _fit_rect, _tensor_size, _deint_rows, _deint_motion_pixel, _side_size), and K11 (k_side: the macroblock
+// records of the batch as planes of side information).  The seven kernel families share ONE launch discipline (stage_descs / fence_launch below); each
 // has descriptor tables of its own.
 // (the reference has no output process: h264/server.go:113-166 stops at the parsed slice)
 #include <algorithm>
@@ -617,6 +617,185 @@ extern "C" int32_t h264mi_batch_deinterlace(h264mi_decoder *d, int32_t stream, i
         if (rate == 2) items.push_back({f.first, f.second, 1 - first});
     }
     return deint_items(d, mode, items.data(), items.size(), n_derived);
+}
+
+// ---------------------------------------------------------------- motion-adaptive deinterlacing (K10, second kernel): the rule of include/h264mi.h
+extern "C" int32_t h264mi_deint_motion_pixel(const uint8_t s[3], const uint8_t p[3], int32_t sp, int32_t *out) {
+    if (!s || !out) return H264MI_EINVAL;
+    if (sp < 0 || sp > 255) {
+        set_error("motion-adaptive pixel: the spatial value %d is not 0 .. 255", sp);
+        return H264MI_EINVAL;
+    }
+    if (!p) {
+        *out = sp;
+        return H264MI_OK;
+    }
+    int m = 0;
+    for (int i = 0; i < 3; i++) m = std::max(m, std::abs(static_cast<int>(s[i]) - static_cast<int>(p[i])));
+    const int t = s[1];
+    *out = std::min(std::max(sp, t - m), t + m);
+    return H264MI_OK;
+}
+
+static int check_deint_motion(int mode) {
+    if (mode == H264MI_DEINT_FIELD || mode == H264MI_DEINT_EDGE) return H264MI_OK;
+    set_error("motion-adaptive deinterlace mode %d: not H264MI_DEINT_FIELD or _EDGE (H264MI_DEINT_BLEND has no parity)", mode);
+    return H264MI_EINVAL;
+}
+// coded size and display rectangle
+static bool same_geometry(const OutFrame *a, const OutFrame *b) {
+    return a->wmb == b->wmb && a->hmb == b->hmb && a->crop_x == b->crop_x && a->crop_y == b->crop_y && a->width == b->width && a->height == b->height;
+}
+// may frame `of` of stream `si` of the last executed batch take the stream's history as its predecessor
+static bool history_valid(const h264mi_decoder *d, int si, const OutFrame *of) {
+    if (!d->d_history || si < 0 || si >= static_cast<int>(d->history.size())) return false;
+    const DeintHistory &hs = d->history[si];
+    return hs.valid && hs.batch + 1 == d->stage[d->exec].seq && same_geometry(&hs.of, of);
+}
+// the arena of the histories: a frame slot per stream, zero-filled on the decoder's stream (ahead of everything that reads or writes it).  On failure
+// everything is as it was
+static int reserve_history(h264mi_decoder *d) {
+    if (d->d_history) return H264MI_OK;
+    const size_t bytes = d->st.size() * d->slot_bytes;
+    uint8_t *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("deinterlace: no device memory for %zu bytes of history (a frame slot per stream)", bytes);
+        return H264MI_ENOMEM;
+    }
+    if (hipMemsetAsync(p, 0, bytes, d->stream) != hipSuccess) {
+        hipFree(p);
+        set_error("deinterlace: clearing the arena of the histories failed");
+        return H264MI_EDEVICE;
+    }
+    d->d_history = p, d->dev_bytes += bytes;
+    d->history.assign(d->st.size(), DeintHistory());
+    return H264MI_OK;
+}
+
+// take: (stream, frame) whose source becomes the stream's history, behind the launch on the decoder's stream and inside its fence
+static int motion_items(h264mi_decoder *d, int mode, const h264mi_deint_motion_item *items, size_t n, int32_t *n_derived, const FrameList &take) {
+    TRY(check_deint_motion(mode));
+    GUARD(d);
+    std::vector<DeintMotionDesc> descs(n);
+    std::vector<DerivedFrame> next(n);
+    size_t off = 0;
+    int hmax = 0;
+    for (size_t i = 0; i < n; i++) {
+        const h264mi_deint_motion_item &it = items[i];
+        uint8_t *p, *pp = nullptr;
+        const OutFrame *of, *pof;
+        int x0, y0, w, h;
+        if (it.stream == H264MI_STREAM_DERIVED || frame_ptrs(d, it.stream, it.frame, &p, &of) != H264MI_OK) {
+            set_error("deinterlace item %zu: no frame %d of stream %d in the last executed batch (a derived frame cannot be a source)", i, it.frame, it.stream);
+            return H264MI_EINVAL;
+        }
+        const int parity = it.parity == H264MI_DEINT_PARITY_FIRST ? of->first_parity : it.parity;
+        if (parity != 0 && parity != 1) {
+            set_error("deinterlace item %zu: parity %d is not 0, 1 or H264MI_DEINT_PARITY_FIRST", i, it.parity);
+            return H264MI_EINVAL;
+        }
+        if (it.prev_frame == H264MI_DEINT_PREV_HISTORY) {
+            if (!history_valid(d, it.stream, of)) {
+                set_error("deinterlace item %zu: stream %d has no valid history for frame %d (none was taken in the batch before, or its size differs, or a reset came in between)",
+                          i, it.stream, it.frame);
+                return H264MI_EINVAL;
+            }
+            pp = d->d_history + static_cast<size_t>(it.stream) * d->slot_bytes;
+        } else if (it.prev_frame != H264MI_DEINT_PREV_NONE) {
+            if (frame_ptrs(d, it.stream, it.prev_frame, &pp, &pof) != H264MI_OK) {
+                set_error("deinterlace item %zu: prev_frame %d is not a frame of stream %d in the last executed batch, H264MI_DEINT_PREV_NONE or _PREV_HISTORY", i, it.prev_frame,
+                          it.stream);
+                return H264MI_EINVAL;
+            }
+            if (!same_geometry(of, pof)) {
+                set_error("deinterlace item %zu: frames %d and %d of stream %d differ in coded size or display rectangle", i, it.frame, it.prev_frame, it.stream);
+                return H264MI_EINVAL;
+            }
+        }
+        crop_rect(of, 1, &x0, &y0, &w, &h);
+        DeintMotionDesc &dd = descs[i];
+        set_source(dd, p, of, x0, y0, w, h, off);
+        dd.mode = mode, dd.parity = parity, dd.prev = reinterpret_cast<uint64_t>(pp);
+        next[i].of = *of, next[i].off = off, next[i].prev = it.prev_frame;
+        off += (static_cast<size_t>(dd.W) * dd.H * 3 / 2 + 255) & ~static_cast<size_t>(255); // a frame slot of the source's coded size
+        hmax = std::max(hmax, h);
+    }
+    if (n) TRY(reserve_derived(d, off));
+    if (n_derived) *n_derived = static_cast<int32_t>(n);
+    d->derived.clear(); // (as in deint_items: from here on the arena is rewritten)
+    if (n == 0) return H264MI_OK;
+    DescTables &t = d->tables[OUT_DEINT_MOTION];
+    const DeintMotionDesc *dev;
+    TRY(stage_descs(d, t, descs, &dev));
+    const int pairs_per_block = 8; // as k_deint
+    const int hc = (hmax + 1) / 2, npairs = (hmax + 1) / 2 + (hc + 1) / 2;
+    hipLaunchKernelGGL(k_deint_motion, dim3(static_cast<uint32_t>(n), (npairs + pairs_per_block - 1) / pairs_per_block), dim3(256), 0, d->stream, dev, d->d_derived,
+                       pairs_per_block);
+    // the histories, behind the launch that may read them: the whole coded frame, so that a slot has the layout of the frame it stands for
+    for (const std::pair<int, int> &f : take) {
+        uint8_t *p;
+        const OutFrame *of;
+        TRY(frame_ptrs(d, f.first, f.second, &p, &of));
+        DeintHistory &hs = d->history[f.first];
+        hs.valid = false;
+        HIP_TRY(hipMemcpyAsync(d->d_history + static_cast<size_t>(f.first) * d->slot_bytes, p, static_cast<size_t>(of->wmb) * of->hmb * 384, hipMemcpyDeviceToDevice, d->stream));
+        hs.valid = true, hs.batch = d->stage[d->exec].seq, hs.of = *of;
+    }
+    TRY(fence_launch(d, t));
+    d->derived.swap(next);
+    return H264MI_OK;
+}
+
+extern "C" int32_t h264mi_items_deinterlace_motion(h264mi_decoder *d, int32_t mode, const h264mi_deint_motion_item *items, int32_t n, int32_t *n_derived) {
+    if (!d || n < 0 || (n > 0 && !items)) return H264MI_EINVAL;
+    return motion_items(d, mode, items, static_cast<size_t>(n), n_derived, {});
+}
+
+extern "C" int32_t h264mi_batch_deinterlace_motion(h264mi_decoder *d, int32_t stream, int32_t mode, int32_t rate, int32_t flags, int32_t *n_derived) {
+    if (!d || stream < -1 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
+    TRY(check_deint_motion(mode));
+    if (rate != 1 && rate != 2) {
+        set_error("deinterlace rate %d: not 1 or 2", rate);
+        return H264MI_EINVAL;
+    }
+    if (flags & ~H264MI_DEINT_HISTORY) {
+        set_error("deinterlace flags 0x%x: only H264MI_DEINT_HISTORY is defined", static_cast<unsigned>(flags));
+        return H264MI_EINVAL;
+    }
+    const bool history = (flags & H264MI_DEINT_HISTORY) != 0;
+    if (history) {
+        GUARD(d);
+        TRY(reserve_history(d));
+    }
+    std::vector<h264mi_deint_motion_item> items;
+    FrameList take;
+    const Stage &g = d->stage[d->exec];
+    for (int si = 0; si < static_cast<int>(g.out.size()); si++) {
+        const int nf = static_cast<int>(g.out[si].size());
+        if ((stream >= 0 && stream != si) || nf == 0) continue;
+        std::vector<int32_t> order(nf), prev(nf);
+        int32_t k;
+        TRY(h264mi_stream_output_order(d, si, order.data(), nf, &k));
+        for (int i = 0; i < nf; i++) { // the frame before it in output order; the first one: the history
+            const OutFrame *of = &g.out[si][order[i]];
+            if (i) prev[order[i]] = same_geometry(of, &g.out[si][order[i - 1]]) ? order[i - 1] : H264MI_DEINT_PREV_NONE;
+            else prev[order[i]] = history && history_valid(d, si, of) ? H264MI_DEINT_PREV_HISTORY : H264MI_DEINT_PREV_NONE;
+        }
+        for (int f = 0; f < nf; f++) {
+            const int first = g.out[si][f].first_parity;
+            items.push_back({si, f, first, prev[f]});
+            if (rate == 2) items.push_back({si, f, 1 - first, prev[f]});
+        }
+        if (history) take.push_back({si, order[nf - 1]});
+    }
+    return motion_items(d, mode, items.data(), items.size(), n_derived, take);
+}
+
+extern "C" int32_t h264mi_derived_prev(h264mi_decoder *d, int32_t k, int32_t *prev) {
+    if (!d || !prev || k < 0 || k >= static_cast<int>(d->derived.size())) return H264MI_EINVAL;
+    *prev = d->derived[k].prev;
+    return H264MI_OK;
 }
 
 // ---------------------------------------------------------------- macroblock side information (K11): the rule of include/h264mi.h

@@ -218,6 +218,9 @@ SIDE_ALL = 0xFFF
 MB_NONE, MB_I4x4, MB_I8x8, MB_I16x16, MB_IPCM, MB_P16x16, MB_P16x8, MB_P8x16, MB_P8x8, MB_PSKIP, MB_B, MB_BDIRECT, MB_BSKIP = range(13)  # H264MI_MB_*: values of the "type" plane
 STREAM_DERIVED = 0x40000000                           # H264MI_STREAM_DERIVED: the pseudo-stream of the derived (deinterlaced) frames
 _DEINT_NAMES = {"field": DEINT_FIELD, "blend": DEINT_BLEND, "edge": DEINT_EDGE}
+_DEINT_MOTION_NAMES = {"motion": DEINT_FIELD, "motion_edge": DEINT_EDGE}  # the motion-adaptive modes of Decoder.deinterlace, by the spatial mode they pull from
+DEINT_PREV_NONE, DEINT_PREV_HISTORY = -1, -2          # H264MI_DEINT_PREV_*: prev_frame of a motion-adaptive item / Decoder.derived_prev
+DEINT_HISTORY = 1                                     # H264MI_DEINT_HISTORY: flag of h264mi_batch_deinterlace_motion (Decoder.deinterlace(history=True))
 _DT_NAMES = {"u8": DT_U8, "uint8": DT_U8, "f16": DT_F16, "float16": DT_F16, "bf16": DT_BF16, "bfloat16": DT_BF16, "f32": DT_F32, "float32": DT_F32}
 
 
@@ -262,6 +265,15 @@ def deint_rows(mode, parity, n_rows, y):
     v = [ctypes.c_int32(0) for _ in range(3)]
     check(_lib.load().h264mi_deint_rows(_deint(mode), int(parity), n_rows, y, *[ctypes.byref(x) for x in v]))
     return tuple(x.value for x in v)
+
+
+def deint_motion_pixel(s, p, sp):
+    """The motion-adaptive rule of include/h264mi.h for one sample, from the library (h264mi_deint_motion_pixel; no GPU): s and p are the samples of the
+    source and of the predecessor at rows (up, y, dn), p = None: no predecessor; sp is the spatial value."""
+    out = ctypes.c_int32(0)
+    a3 = ctypes.c_uint8 * 3
+    check(_lib.load().h264mi_deint_motion_pixel(a3(*s), None if p is None else a3(*p), int(sp), ctypes.byref(out)))
+    return out.value
 
 
 def _dtype(dtype):
@@ -537,14 +549,32 @@ class Decoder:
         check(self._L.h264mi_frame_fields(self._h, stream, frame, ctypes.byref(ff)))
         return ff
 
-    def deinterlace(self, stream=-1, mode="field", rate=1, items=None):
+    def deinterlace(self, stream=-1, mode="field", rate=1, items=None, history=False):
         """K10 in one launch: derived (deinterlaced) frames of the last executed batch, which REPLACE the decoder's list of derived frames and are then
         frames 0 .. n - 1 of the pseudo-stream STREAM_DERIVED for frame_count, frame_info, frame_colour, frame_fields, read_frame(crop=True) and every
         pack / convert / scale / tensor call.  mode: "field", "blend" or "edge".  Without `items`: every frame of `stream` (-1: of all streams,
         stream-major); rate 1: one derived frame per frame, of its first parity; rate 2: two, the first parity then the other ("bob"; not for "blend").
         items: a list of (stream, frame, parity) with parity 0 (top), 1 (bottom) or DEINT_PARITY_FIRST; an empty list empties the list of derived
-        frames.  execute(), reset() and reset_stream() empty it too.  Returns the number of derived frames."""
+        frames.  execute(), reset() and reset_stream() empty it too.  Returns the number of derived frames.
+        mode "motion" or "motion_edge": motion-adaptive ("Motion-adaptive deinterlacing" of include/h264mi.h), pulling from "field" or "edge".  Without
+        `items` a frame's predecessor is the frame before it in output order; history=True gives the first one the stream's history, if the batch
+        before left a valid one, and takes this batch's.  items are then (stream, frame, parity, prev_frame), prev_frame a frame of the same stream,
+        DEINT_PREV_NONE or DEINT_PREV_HISTORY."""
         n = ctypes.c_int32(0)
+        if isinstance(mode, str) and mode.lower() in _DEINT_MOTION_NAMES:
+            m = _DEINT_MOTION_NAMES[mode.lower()]
+            if items is None:
+                check(self._L.h264mi_batch_deinterlace_motion(self._h, stream, m, int(rate), DEINT_HISTORY if history else 0, ctypes.byref(n)))
+                return n.value
+            if history:
+                raise ValueError("deinterlace: history goes with the batch form; an item names DEINT_PREV_HISTORY itself")
+            arr = (_lib.DeintMotionItem * max(len(items), 1))()
+            for a, it in zip(arr, items):
+                a.stream, a.frame, a.parity, a.prev_frame = (int(v) for v in it)
+            check(self._L.h264mi_items_deinterlace_motion(self._h, m, arr, len(items), ctypes.byref(n)))
+            return n.value
+        if history:
+            raise ValueError("deinterlace: history needs mode \"motion\" or \"motion_edge\"")
         if items is None:
             check(self._L.h264mi_batch_deinterlace(self._h, stream, _deint(mode), int(rate), ctypes.byref(n)))
             return n.value
@@ -553,6 +583,13 @@ class Decoder:
             a.stream, a.frame, a.parity = (int(v) for v in it)
         check(self._L.h264mi_items_deinterlace(self._h, _deint(mode), arr, len(items), ctypes.byref(n)))
         return n.value
+
+    def derived_prev(self, k):
+        """What derived frame k was made from besides its source (h264mi_derived_prev): a frame index of the source's stream, DEINT_PREV_NONE (also for
+        every frame of "field", "blend" and "edge") or DEINT_PREV_HISTORY."""
+        v = ctypes.c_int32(0)
+        check(self._L.h264mi_derived_prev(self._h, int(k), ctypes.byref(v)))
+        return v.value
 
     def convert_frame(self, stream, frame, dst_ptr, cap, fmt, csc=0):
         """K7 for one frame of the last executed batch: cropped and converted to `fmt` into the DEVICE buffer at dst_ptr (asynchronous on the
@@ -636,7 +673,7 @@ class Decoder:
         return out
 
     def frames_tensor(self, stream, fmt="rgbp", csc=0, size=None, filter="bilinear", *, dtype=None, scale=None, bias=None, mean=None, std=None,
-                      letterbox=False, pad=(114, 114, 114), rois=None, bgr=False, deinterlace=None, field_rate=False):
+                      letterbox=False, pad=(114, 114, 114), rois=None, bgr=False, deinterlace=None, field_rate=False, deinterlace_history=False):
         """The frames of `stream` of the last executed batch as one torch uint8 tensor on the decoder's device: [n, 3, h, w] ("rgbp"), [n, h, w, 3]
         ("rgb24") or [n, H264MI_I420_SIZE(w, h)] ("nv12"), converted by one K7 launch.  Raises ValueError if the stream's frames differ in display size.
         With size = (ow, oh) the frames are scaled to that size by one K8 launch (`filter`: "bilinear" or "area"): the shapes are those with (ow, oh) for
@@ -657,14 +694,16 @@ class Decoder:
         n = len(rois), in list order.
         deinterlace = "field", "blend" or "edge" (keyword-only): the frames of `stream` are deinterlaced first (one K10 launch: self.deinterlace(stream,
         mode, rate), which replaces the decoder's derived frames) and everything above is then done for the pseudo-stream STREAM_DERIVED; field_rate
-        makes that two frames per frame, the first field's then the second's.  rois then name frames of STREAM_DERIVED."""
+        makes that two frames per frame, the first field's then the second's.  rois then name frames of STREAM_DERIVED.  deinterlace = "motion" or
+        "motion_edge" is the motion-adaptive route of self.deinterlace, and deinterlace_history its history=True: the first frame in output order is
+        pulled from the last frame of the batch before."""
         import torch
         f = _fmt(fmt)
         if deinterlace is not None:
-            self.deinterlace(stream, deinterlace, 2 if field_rate else 1)
+            self.deinterlace(stream, deinterlace, 2 if field_rate else 1, history=deinterlace_history)
             stream = STREAM_DERIVED
-        elif field_rate:
-            raise ValueError("frames_tensor: field_rate needs deinterlace")
+        elif field_rate or deinterlace_history:
+            raise ValueError("frames_tensor: field_rate and deinterlace_history need deinterlace")
         if dtype is not None or scale is not None or bias is not None or mean is not None or std is not None or letterbox or rois is not None or bgr:
             return self._model_tensor(stream, f, csc, size, filter, dtype, scale, bias, mean, std, letterbox, pad, rois, bgr)
         if size is not None:

@@ -563,7 +563,8 @@ int32_t h264mi_batch_tensor_device(h264mi_decoder *dec, int32_t stream, const h2
  *                       (S[up][cx(x + d)] + S[dn][cx(x - d)] + 1) >> 1.  A missing row at the plane's edge (up == dn after the clamp) is S[up][x]; the
  *                       hp == 1 case is as in FIELD.
  * Any other mode is H264MI_EINVAL.  A parity is 0, 1 or H264MI_DEINT_PARITY_FIRST: the first_parity of the frame (h264mi_frame_fields), resolved per frame.
- * Out of scope: temporal (motion-adaptive) modes, which need the neighbouring frames across batches; interlace-aware chroma upsampling inside K7 (chroma
+ * The three modes are spatial: they read one frame.  The motion-adaptive modes, which also read the frame before it -- across batch boundaries too -- have
+ * entry points of their own: "Motion-adaptive deinterlacing" below.  Out of scope: look-ahead (a successor frame); interlace-aware chroma upsampling inside K7 (chroma
  * planes are deinterlaced as planes, then upsampled by the rule of "Output formats"); pulldown detection and SEI pic_struct; MBAFF, as everywhere. */
 #define H264MI_DEINT_FIELD 0
 #define H264MI_DEINT_BLEND 1
@@ -610,6 +611,58 @@ typedef struct {
 } h264mi_deint_item;
 int32_t h264mi_items_deinterlace(h264mi_decoder *dec, int32_t mode, const h264mi_deint_item *items, int32_t n, int32_t *n_derived);
 int32_t h264mi_batch_deinterlace(h264mi_decoder *dec, int32_t stream, int32_t mode, int32_t rate, int32_t *n_derived);
+
+/* ---- Motion-adaptive deinterlacing (K10, second kernel): derived frames from a frame AND its predecessor ----
+ * A motion-adaptive deinterlaced frame is a function of the source's tight I420 frame S, a predecessor's tight I420 frame P of the same display size or
+ * "none", a spatial mode M -- H264MI_DEINT_FIELD or H264MI_DEINT_EDGE -- and a parity p, and of nothing else; this comment is the contract.  Each plane is
+ * processed on its own with the same parity; plane sizes, parity and clamps are those of "Deinterlaced output" (luma h x w, chroma ceil(h / 2) x
+ * ceil(w / 2), every clamp at the edge of the display plane); all arithmetic is in integers.
+ *   Kept rows     A row for which h264mi_deint_rows(M, p, hp, y) says kept is copied from S (the one-row, p = 1 case included).
+ *   Missing rows  With up / dn of row y from the same function:
+ *                   sp[x] = the value mode M writes there: FIELD's average, or on luma EDGE's directional value with its up == dn case (chroma
+ *                           follows FIELD);
+ *                   t[x]  = S[y][x], the sample of the other field: the weave;
+ *                   m[x]  = max(|S[up][x] - P[up][x]|, |S[dn][x] - P[dn][x]|, |S[y][x] - P[y][x]|): how far each of the three rows moved since the
+ *                           predecessor, same parity against same parity;
+ *                   out[y][x] = min(max(sp[x], t[x] - m[x]), t[x] + m[x]): the spatial value, pulled to within m of the weave.
+ *   Properties    Where nothing moved (m = 0) the woven sample goes out, at full vertical resolution; where much moved the spatial value goes out; the
+ *                 result always lies in 0 .. 255 (between sp and t).
+ *   No predecessor  out = sp: the frame equals mode M's frame bit for bit.
+ *   P is S itself   the frame equals the source frame bit for bit (m = 0 everywhere).
+ * The rule is causal on purpose: it adds no latency and needs nothing from the next batch.  Not supported: H264MI_DEINT_BLEND has no parity and is
+ * H264MI_EINVAL here; look-ahead (a successor frame), pulldown detection, SEI pic_struct and MBAFF stay out of scope.
+ * h264mi_deint_motion_pixel: the rule of one sample as a pure function (no decoder, no device).  s and p hold the samples of S and P at rows up, y and dn
+ * (in that order) of one column, sp the spatial value (0 .. 255); p = NULL means no predecessor (*out = sp).  H264MI_EINVAL: s or out NULL, sp outside
+ * 0 .. 255.
+ * Derived frames: the two calls below have the discipline of h264mi_items_deinterlace -- everything is checked first, a call that fails launches
+ * nothing and leaves the list of derived frames intact, a call that succeeds REPLACES it, in ONE launch on the decoder's stream -- and share its list,
+ * its arena and the pseudo-stream H264MI_STREAM_DERIVED.
+ * h264mi_items_deinterlace_motion: item i is frame `frame` of stream `stream` of the last executed batch under `mode` with `parity` (0, 1 or
+ * H264MI_DEINT_PARITY_FIRST) against `prev_frame`: a frame of the SAME stream in the last executed batch (it may be `frame` itself),
+ * H264MI_DEINT_PREV_NONE, or H264MI_DEINT_PREV_HISTORY -- the stream's history, which must be valid (below).  A predecessor whose coded size or display
+ * rectangle differs from the source's is H264MI_EINVAL, and so are any other prev_frame, a history that is not valid, and H264MI_STREAM_DERIVED as a source.
+ * h264mi_batch_deinterlace_motion: items and their order are h264mi_batch_deinterlace's (decoding order, stream-major; rate 2: the first parity, then
+ * the other).  A frame's predecessor is the frame before it in h264mi_stream_output_order of its stream; both derived frames of a rate-2 frame share it;
+ * a predecessor of another coded size or display rectangle resolves to none.  The first frame in output order takes the stream's history if
+ * flags & H264MI_DEINT_HISTORY and the history is valid, and has none otherwise.  Any other flag bit, and H264MI_STREAM_DERIVED, are H264MI_EINVAL.
+ * History: one frame slot per stream in an arena of the decoder's own, allocated on first use (the first batch call with H264MI_DEINT_HISTORY),
+ * zero-filled, counted by h264mi_decoder_memory and freed by h264mi_decoder_destroy; H264MI_ENOMEM leaves everything as it was.  With the flag the batch
+ * call copies, after its launch and on the decoder's stream, the source of each covered stream's last frame in output order into that stream's slot; the
+ * next pass waits for the launch and the copies.  A history is valid only if it was taken in the batch prepared immediately before the one executed
+ * last, its coded size and display rectangle equal the source's, and neither h264mi_stream_reset of that stream nor h264mi_decoder_reset came in between:
+ * executing the same prepared batch again does not make its own history its predecessor, and a batch in between that took no history ends it.
+ * h264mi_derived_prev: what derived frame k was made from: a frame index, H264MI_DEINT_PREV_NONE, or H264MI_DEINT_PREV_HISTORY; for a derived frame of
+ * the three spatial modes H264MI_DEINT_PREV_NONE.  H264MI_EINVAL: no such derived frame, a null pointer. */
+#define H264MI_DEINT_PREV_NONE (-1)
+#define H264MI_DEINT_PREV_HISTORY (-2)
+#define H264MI_DEINT_HISTORY 1 /* flags of h264mi_batch_deinterlace_motion */
+typedef struct {
+    int32_t stream, frame, parity, prev_frame;
+} h264mi_deint_motion_item;
+int32_t h264mi_deint_motion_pixel(const uint8_t s[3], const uint8_t p[3], int32_t sp, int32_t *out);
+int32_t h264mi_items_deinterlace_motion(h264mi_decoder *dec, int32_t mode, const h264mi_deint_motion_item *items, int32_t n, int32_t *n_derived);
+int32_t h264mi_batch_deinterlace_motion(h264mi_decoder *dec, int32_t stream, int32_t mode, int32_t rate, int32_t flags, int32_t *n_derived);
+int32_t h264mi_derived_prev(h264mi_decoder *dec, int32_t k, int32_t *prev);
 
 /* ---- Macroblock side information (K11): motion, references, types, QP and coded-block flags as planes, on the device ----
  * What the reference's SliceData holds per macroblock (h264/slice.go:77-102 has no pixel in it), laid out per 4x4 luma block for every frame of a

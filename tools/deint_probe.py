@@ -1,10 +1,14 @@
-"""K10 (k_deint) next to K6 (k_pack) over the same frames: both are one-read, one-write frame kernels.
+"""K10 (k_deint, k_deint_motion) next to K6 (k_pack) over the same frames: one-read, one-write frame kernels, and the two-read motion-adaptive one.
 
     python tools/deint_probe.py [--streams 64] [--distinct 32] [--frames 30] [--reps 5]
 
 One process, the bench's clean 1080p batch (bench.gen_stream: the same generator recipe and seeds).  Every figure is the median of --reps launches, wall
 clock around launch + synchronise of the decoder's stream, as ms and as GB/s of the ALGORITHMIC bytes per pixel: 1.5 read + 1.5 written for K6 and for
-BLEND; FIELD and EDGE read the kept rows only (0.75) and write 1.5.  The arena of the derived frames is allocated by the warm-up call, outside the timing.
+BLEND; FIELD and EDGE read the kept rows only (0.75) and write 1.5; the motion-adaptive modes read the frame and its predecessor whole and write one
+frame (4.5) -- their rows give EVERY frame a predecessor through the item call (frame f - 1; frame 0: frame 1), with the item array built once, outside the
+timing.  "motion batch" and "motion batch+history" are the batch call without and with H264MI_DEINT_HISTORY over the same frames (the first frame of each
+stream has no predecessor there, or the history): their difference is the cost of the history copies, one frame per stream.  The arena of the derived
+frames is allocated by the warm-up call, outside the timing.
 Before timing, FIELD's kept rows are compared with K6's frames and BLEND of a frame with itself through torch.  The expectation: FIELD and BLEND take at
 most 1.25 x K6's time; EDGE is reported without a bound.  If the I420 copy of the batch and the arena do not fit beside the decoder, run with fewer --streams."""
 import argparse
@@ -86,19 +90,36 @@ def main():
         dec.sync()
         y = ya[:8].to(torch.int32)
         assert torch.equal(((y[:, :-2] + 2 * y[:, 1:-1] + y[:, 2:] + 2) >> 2).to(torch.uint8), yb[:8, 1:-1]), "BLEND is not (a + 2 b + c + 2) >> 2"
+        # motion-adaptive: a frame against itself is the frame (m = 0 everywhere)
+        assert dec.deinterlace(mode="motion_edge", items=[(s, f, 0, f) for s in range(S) for f in range(F)]) == n
+        dec.pack_batch(got.data_ptr(), got.numel(), stream=H.STREAM_DERIVED)
+        dec.sync()
+        assert torch.equal(got, i420), "motion-adaptive: a frame that is its own predecessor is not itself"
         del got, ya, yb, y, mid
 
     row("k_pack (K6) I420", lambda: dec.pack_batch(i420.data_ptr(), i420.numel()), 3.0)
     row("k_deint field", lambda: dec.deinterlace(-1, "field", 1), 2.25)
     row("k_deint blend", lambda: dec.deinterlace(-1, "blend", 1), 3.0)
     row("k_deint edge", lambda: dec.deinterlace(-1, "edge", 1), 2.25)
+    from h264decode_amd import _lib
+    arr = (_lib.DeintMotionItem * n)()
+    for i, a in enumerate(arr):
+        a.stream, a.frame, a.parity = i // F, i % F, 0
+        a.prev_frame = a.frame - 1 if a.frame else min(1, F - 1)
+
+    def motion_items(mode):
+        _lib.check(dec._L.h264mi_items_deinterlace_motion(dec._h, mode, arr, n, None))
+    row("k_deint_motion motion", lambda: motion_items(H.DEINT_FIELD), 4.5)
+    row("k_deint_motion motion_edge", lambda: motion_items(H.DEINT_EDGE), 4.5)
+    row("k_deint_motion motion batch", lambda: dec.deinterlace(-1, "motion", 1), 4.5)
+    row("k_deint_motion motion batch+history", lambda: dec.deinterlace(-1, "motion", 1, history=True), 4.5)
     dec.close()
     for r in rows:
         print(json.dumps(r))
     if args.only:
         return 0
     k6 = rows[0]["ms"]
-    ratios = {r["what"].split()[-1]: round(r["ms"] / k6, 3) for r in rows[1:]}
+    ratios = {r["what"].split(" ", 1)[1]: round(r["ms"] / k6, 3) for r in rows[1:]}
     ok = ratios["field"] <= 1.25 and ratios["blend"] <= 1.25
     print(json.dumps({"frames": n, "size": "%dx%d" % (w, h), "reps": args.reps, "time_over_k_pack": ratios, "field_and_blend_within_1.25x_k_pack": ok}))
     return 0 if ok else 1
