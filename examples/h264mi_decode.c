@@ -1,7 +1,7 @@
 /*
  * examples/h264mi_decode.c -- the C ABI from plain C: decode an Annex-B file to raw I420 on the GPU.
  *
- *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--conceal...] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge|motion|motion-edge] [--field-rate]
+ *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--conceal...] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge|motion|motion-edge] [--field-rate] [--stats]
  *
  * --nv12 / --rgb write NV12 / tight R, G, B bytes instead of I420: the frames are converted on the device (h264mi_batch_convert_device into a
  * device buffer, matrix and range from each frame's own SPS) and copied to the host from there.  --scale WxH writes every frame at W x H instead of
@@ -12,8 +12,10 @@
  * the paths above is chosen -- instead of the woven ones; with --field-rate two per frame, the first field's then the second's.  --deinterlace motion /
  * motion-edge are the motion-adaptive modes that pull from field / edge (h264mi_batch_deinterlace_motion with H264MI_DEINT_HISTORY): a frame is
  * deinterlaced against the frame before it in output order, and the first frame of a batch against the last one of the batch before, so a file decoded
- * in several batches (frames_per_batch) comes out as if it had been decoded in one.  The HIP calls of these
- * paths are the only HIP this file needs; they are declared below, so it still builds without the HIP headers.
+ * in several batches (frames_per_batch) comes out as if it had been decoded in one.  --stats prints one line per decoded frame to stdout, in decoding
+ * order: its mean luma, its mean absolute luma difference against the frame before it in output order, and how many luma samples changed by more than 8
+ * (h264mi_batch_stats_device with H264MI_STATS_HISTORY -- on the first batch too, or no later batch had a predecessor for its first frame).  The HIP
+ * calls of these paths are the only HIP this file needs; they are declared below, so it still builds without the HIP headers.
  *
  * The file includes nothing but include/h264mi.h and the C library.
  *
@@ -45,9 +47,11 @@ static int fail(const char *what, int code) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge|motion|motion-edge] [--field-rate]\n", argv[0]);
+        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge|motion|motion-edge] [--field-rate] [--stats]\n", argv[0]);
         return 2;
     }
+    int stats = 0; /* --stats (the last argument of all): the frame statistics of every batch, on stdout */
+    if (argc > 3 && !strcmp(argv[argc - 1], "--stats")) stats = 1, argc--;
     int deint = -1, deint_rate = 1, deint_motion = 0; /* --deinterlace MODE and --field-rate (the last arguments of all): derived frames instead of the woven ones */
     if (argc > 3 && !strcmp(argv[argc - 1], "--field-rate")) deint_rate = 2, argc--;
     if (argc > 4 && !strcmp(argv[argc - 2], "--deinterlace")) {
@@ -148,6 +152,11 @@ int main(int argc, char **argv) {
     size_t frame_cap = 0;
     void *dev = NULL; /* --nv12 / --rgb: the converted frames of a batch on the device */
     size_t dev_cap = 0;
+    void *sdev = NULL; /* --stats: the records of a batch on the device, and their host copy */
+    h264mi_frame_stats *srec = NULL;
+    size_t sdev_cap = 0;
+    long stats_total = 0; /* frames reported so far (total counts what is written: two per frame with --field-rate) */
+    const h264mi_stats_spec sspec = {0, 0, 8, 0}; /* no grid; changed_y counts |S - P| > 8 */
     long total = 0;
     int start = 0, pics = 0, seen_vcl = 0;
     /* parameter sets by id and the slices of the current picture, for the picture-boundary test */
@@ -214,6 +223,26 @@ int main(int argc, char **argv) {
                 if ((r = h264mi_decode_batch(dec, 1, &ptr, &l, &info)) != H264MI_OK) return fail("h264mi_decode_batch", r);
                 int32_t k = 0, src = 0; /* src: the stream the frames are taken from */
                 h264mi_stream_frame_count(dec, 0, &k);
+                if (stats) { /* one launch makes the records of the batch (without a grid a record is an item); the size query as for the formats below */
+                    size_t bytes = 0;
+                    r = h264mi_batch_stats_device(dec, 0, &sspec, H264MI_STATS_HISTORY, sdev ? sdev : (void *)nals, 0, &bytes);
+                    if (r != H264MI_OK && r != H264MI_ECAPACITY) return fail("h264mi_batch_stats_device", r);
+                    if (bytes > sdev_cap) {
+                        if (sdev) hipFree(sdev);
+                        if (hipMalloc(&sdev, sdev_cap = bytes) != 0) return fail("hipMalloc", H264MI_ENOMEM);
+                        srec = (h264mi_frame_stats *)realloc(srec, bytes);
+                    }
+                    if (bytes && (r = h264mi_batch_stats_device(dec, 0, &sspec, H264MI_STATS_HISTORY, sdev, sdev_cap, &bytes)) != H264MI_OK) return fail("h264mi_batch_stats_device", r);
+                    if ((r = h264mi_batch_sync(dec)) != H264MI_OK) return fail("h264mi_batch_sync", r);
+                    if (bytes && hipMemcpy(srec, sdev, bytes, 2 /* hipMemcpyDeviceToHost */) != 0) return fail("hipMemcpy", H264MI_EDEVICE);
+                    for (size_t q = 0; q < bytes / sizeof(h264mi_frame_stats); q++) {
+                        const h264mi_frame_stats *s = &srec[q];
+                        const double px = (double)s->w * s->h;
+                        printf("stats %ld: mean_y %.3f sad_y/px %.3f changed_y %u (sum_y %llu sad_y %llu has_prev %u)\n", stats_total + (long)q, (double)s->sum_y / px, (double)s->sad_y / px,
+                               s->changed_y, (unsigned long long)s->sum_y, (unsigned long long)s->sad_y, s->has_prev);
+                    }
+                    stats_total += (long)(bytes / sizeof(h264mi_frame_stats));
+                }
                 if (deint >= 0) { /* one launch makes the derived frames of the batch: frames 0 .. k - 1 of the pseudo-stream */
                     if (deint_motion) { /* with the history: the batch's first frame in output order is pulled from the last one of the batch before */
                         if ((r = h264mi_batch_deinterlace_motion(dec, 0, deint, deint_rate, H264MI_DEINT_HISTORY, &k)) != H264MI_OK) return fail("h264mi_batch_deinterlace_motion", r);
@@ -277,6 +306,7 @@ int main(int argc, char **argv) {
         if ((conceal & H264MI_CONCEAL_LONE_FIELDS) && h264mi_decoder_concealed_fields(dec, &cs) == H264MI_OK) fprintf(stderr, "concealed: %lld fields\n", (long long)cs);
     }
     if (dev) hipFree(dev);
+    if (sdev) hipFree(sdev);
     h264mi_decoder_destroy(dec);
     fprintf(stderr, "%s: %ld frames %dx%d -> %s\n", h264mi_version(), total, sps.width, sps.height, argv[2]);
     return 0;

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _HEADER = os.path.join(_HERE, "..", "include", "h264mi.h")
 _LIBPATH = os.environ.get("H264MI_LIB") or os.path.join(_HERE, "libh264mi.so")  # H264MI_LIB: a diagnostic build of the same library (csrc/Makefile)
 
-_CT = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64, "uint8_t": ctypes.c_uint8,
+_CT = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "uint8_t": ctypes.c_uint8,
        "double": ctypes.c_double, "float": ctypes.c_float, "void": None}
 
 
@@ -52,6 +52,7 @@ TensorSpec, TensorItem = _S["h264mi_tensor_spec"], _S["h264mi_tensor_item"]
 FieldInfo, DeintItem = _S["h264mi_field_info"], _S["h264mi_deint_item"]
 SideItem = _S["h264mi_side_item"]
 DeintMotionItem = _S["h264mi_deint_motion_item"]
+FrameStats, StatsSpec, StatsItem = _S["h264mi_frame_stats"], _S["h264mi_stats_spec"], _S["h264mi_stats_item"]
 
 
 def build(force=False):
@@ -163,6 +164,10 @@ def load():
         "h264mi_frame_ref_pocs": [vp, I32, I32, I32, I32, P(I32), P(I32), I32, P(I32)],
         "h264mi_items_side_device": [vp, I32, P(SideItem), I32, vp, SZ, P(SZ)],
         "h264mi_batch_side_device": [vp, I32, I32, vp, SZ, P(SZ)],
+        "h264mi_stats_size": [P(StatsSpec), I32, I32, P(I32), P(I32), P(SZ)],
+        "h264mi_items_stats_device": [vp, P(StatsSpec), P(StatsItem), I32, vp, SZ, P(SZ)],
+        "h264mi_batch_stats_plan": [vp, I32, I32, P(StatsItem), I32, P(I32)],
+        "h264mi_batch_stats_device": [vp, I32, P(StatsSpec), I32, vp, SZ, P(SZ)],
         "h264mi_frame_read_mbrecs": [vp, I32, I32, vp, SZ],
         "h264mi_frame_read_mbmv1": [vp, I32, I32, vp, SZ],
         "h264mi_decoder_set_profiling": [vp, I32],
@@ -208,4 +213,5 @@ EXPORTS = ["h264mi_annexb_scan", "h264mi_nal_parse", "h264mi_sps_parse", "h264mi
            "h264mi_fit_rect", "h264mi_tensor_size", "h264mi_items_tensor_device", "h264mi_batch_tensor_device",
            "h264mi_deint_rows", "h264mi_frame_fields", "h264mi_items_deinterlace", "h264mi_batch_deinterlace",
            "h264mi_deint_motion_pixel", "h264mi_items_deinterlace_motion", "h264mi_batch_deinterlace_motion", "h264mi_derived_prev",
-           "h264mi_side_size", "h264mi_frame_ref_pocs", "h264mi_items_side_device", "h264mi_batch_side_device"]
+           "h264mi_side_size", "h264mi_frame_ref_pocs", "h264mi_items_side_device", "h264mi_batch_side_device",
+           "h264mi_stats_size", "h264mi_items_stats_device", "h264mi_batch_stats_plan", "h264mi_batch_stats_device"]

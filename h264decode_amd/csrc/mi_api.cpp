@@ -209,7 +209,7 @@ static void free_all(h264mi_decoder *d) {
     }
     each(hipStreamDestroy, d->ent_stream[0], d->ent_stream[1], d->rec_stream);
     for (DescTables &t : d->tables) each(hipFree, t.d[0], t.d[1]), each(hipHostFree, t.h[0], t.h[1]), each(hipEventDestroy, t.ev[0], t.ev[1]);
-    each(hipFree, d->d_coef[0], d->d_pool_head, d->d_colrec, d->d_backfill, d->d_xring, d->d_xdone, d->d_xctl, d->d_pools, d->d_derived, d->d_history, d->d_frames, d->d_tables);
+    each(hipFree, d->d_coef[0], d->d_pool_head, d->d_colrec, d->d_backfill, d->d_xring, d->d_xdone, d->d_xctl, d->d_pools, d->d_derived, d->hist[HIST_DEINT].arena, d->hist[HIST_STATS].arena, d->d_frames, d->d_tables);
     each(hipHostFree, d->h_xstatus, d->h_tables);
     each(hipEventDestroy, d->ev_user);
     for (auto e : d->ev) hipEventDestroy(e);
@@ -463,7 +463,8 @@ extern "C" int32_t h264mi_decoder_reset(h264mi_decoder *d) {
     if (!d) return H264MI_EINVAL;
     for (auto &s : d->st) reset_stream(s, true);
     d->derived.clear();
-    for (DeintHistory &hs : d->history) hs.valid = false;
+    for (HistorySet &hs : d->hist)
+        for (FrameHistory &fh : hs.slots) fh.valid = false;
     for (Stage &g : d->stage) {
         g.prepared = false;
         for (auto &o : g.out) o.clear();
@@ -474,7 +475,8 @@ extern "C" int32_t h264mi_stream_reset(h264mi_decoder *d, int32_t stream) {
     if (!d || stream < 0 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL;
     reset_stream(d->st[stream], false);
     d->derived.clear(); // (all of them: a derived frame does not outlive the batch it was made from)
-    if (stream < static_cast<int>(d->history.size())) d->history[stream].valid = false;
+    for (HistorySet &hs : d->hist)
+        if (stream < static_cast<int>(hs.slots.size())) hs.slots[stream].valid = false;
     for (Stage &g : d->stage) g.out[stream].clear();
     return H264MI_OK;
 }

@@ -136,7 +136,7 @@ struct Stage {
     hipEvent_t ev_side = nullptr;
     uint32_t *d_cmap = nullptr, *h_cmap = nullptr; // error concealment: per picture where its slices are in the sorted slice table (k_conceal)
     std::vector<std::vector<OutFrame>> out; // per stream: frames of this batch in decoding order
-    uint64_t seq = 0; // which h264mi_batch_prepare made this batch, counted from 1 (h264mi_decoder::prep_seq): what a deinterlacing history is dated by
+    uint64_t seq = 0; // which h264mi_batch_prepare made this batch, counted from 1 (h264mi_decoder::prep_seq): what a history (HistorySet) is dated by
     bool prepared = false, executed = false;
     bool harvested = true; // the entropy kernels' per-slice status words of the last execute have been looked at (harvest_status)
     bool retried = false;  // the batch has been repeated with the whole residual pool (retry_exhausted)
@@ -161,7 +161,7 @@ struct DescTables {
     hipEvent_t ev[2] = {nullptr, nullptr};
     int slot = 0;
 };
-enum { OUT_PACK, OUT_CONVERT, OUT_SCALE, OUT_TENSOR, OUT_DEINT, OUT_SIDE, OUT_DEINT_MOTION, OUT_FAMILIES }; // K6, K7, K8, K9, K10, K11, K10 motion-adaptive
+enum { OUT_PACK, OUT_CONVERT, OUT_SCALE, OUT_TENSOR, OUT_DEINT, OUT_SIDE, OUT_DEINT_MOTION, OUT_STATS, OUT_FAMILIES }; // K6, K7, K8, K9, K10, K11, K10 motion-adaptive, K12
 
 // A derived (deinterlaced) frame: frame k of the pseudo-stream H264MI_STREAM_DERIVED.  `of`: its source's OutFrame (what the accessors report); off: its
 // slot in the arena, in the layout of a frame slot of the source's coded size; prev: what it was made from besides its source (h264mi_derived_prev) -- a
@@ -171,13 +171,21 @@ struct DerivedFrame {
     size_t off;
     int prev = H264MI_DEINT_PREV_NONE;
 };
-// K10, motion-adaptive: a stream's history -- the source of its last frame in output order of the last batch that h264mi_batch_deinterlace_motion took
-// one from, in the stream's slot of h264mi_decoder::d_history.  valid: cleared by the resets; batch: Stage::seq of that batch (the history serves the
-// batch prepared right after it and no other); of: the frame's geometry, which a frame that takes it as its predecessor must share
-struct DeintHistory {
+// A stream's history -- the source of its last frame in output order of the last batch that a batch call took one from, in the stream's slot of the
+// arena.  valid: cleared by the resets; batch: Stage::seq of that batch (the history serves the batch prepared right after it and no other); of: the
+// frame's geometry, which a frame that takes it as its predecessor must share
+struct FrameHistory {
     bool valid = false;
     uint64_t batch = 0;
     OutFrame of;
+};
+// The histories of one consumer: one frame slot per stream (slot_bytes each), allocated by the first call that takes a history and kept.  Each consumer
+// has its own -- h264mi_batch_deinterlace_motion (K10, motion-adaptive) and h264mi_batch_stats_device (K12) -- so that two calls in one batch each date
+// their own slot: with one shared slot the second call of the next batch would find the first one's date and no predecessor
+enum { HIST_DEINT, HIST_STATS, HIST_KINDS };
+struct HistorySet {
+    uint8_t *arena = nullptr;
+    std::vector<FrameHistory> slots;
 };
 
 struct h264mi_decoder {
@@ -259,9 +267,7 @@ struct h264mi_decoder {
     std::vector<DerivedFrame> derived;
     uint8_t *d_derived = nullptr;
     size_t derived_cap = 0;
-    // K10, motion-adaptive: one frame slot per stream (slot_bytes each), allocated by the first call that takes a history and kept; what is in them
-    uint8_t *d_history = nullptr;
-    std::vector<DeintHistory> history;
+    HistorySet hist[HIST_KINDS]; // K10, motion-adaptive, and K12: a history each
     uint64_t prep_seq = 0; // h264mi_batch_prepare calls so far
     std::vector<float> launch_ms[4]; // duration of every launch of the last profiled pass, per kernel
 };

@@ -250,6 +250,32 @@ typedef struct {
     uint32_t vec;       // 1: bx0 % 4 == 0, gw % 4 == 0 and the item's first byte is 8-byte aligned -- a macroblock's four cells of a row are one store
 } SideDesc;
 extern "C" __global__ void k_side(const SideDesc *descs, uint8_t *dst, uint32_t planes, int rows_per_block);
+// K12 (k_stats.hip): a list of (frame, predecessor) items -> one h264mi_frame_stats record each and, with a grid, planes of per-cell sums behind it, by
+// the rule of include/h264mi.h ("Frame statistics").  The project's one reduction: the host clears the destination range, blocks add their partial
+// results with integer atomics.  grid = (items, mi_stats_blocks(h_max)), block = 256; a block takes a band of MI_STATS_LUMA_ROWS luma rows -- whole
+// cell rows of every cell size -- or MI_STATS_CHROMA_ROWS rows of the Cb-then-Cr row space; a thread item is 8 rows x 16 columns of one plane
+#define MI_STATS_LUMA_ROWS 64    /* a multiple of the largest cell */
+#define MI_STATS_CHROMA_ROWS 128 /* of ceil(hc / 8) * 8 rows of Cb followed by as many of Cr */
+typedef struct {
+    uint64_t src;     // as PackDesc
+    uint64_t dst_off; // byte offset of the item (its record; the planes follow) in the destination buffer
+    uint32_t W, H, x0, y0, w, h;
+    uint64_t prev;   // Y plane of the predecessor (the same coded size and display rectangle); 0: none
+    uint32_t gw, gh; // the grid; 0, 0: none
+    // what the blocks of an item tell each other, zero when the table is uploaded: a minimum cannot be accumulated into a cleared field, so each block
+    // adds 255 - (its smallest sample) to inv_min with an atomic maximum, and the block that draws the last ticket writes min_y and the record's constants
+    uint32_t inv_min, ticket;
+} StatsDesc;
+__host__ __device__ static inline int mi_stats_luma_blocks(int h) { return (h + MI_STATS_LUMA_ROWS - 1) / MI_STATS_LUMA_ROWS; }
+__host__ __device__ static inline int mi_stats_chroma_blocks(int h) { return (2 * (((h + 1) / 2 + 7) / 8 * 8) + MI_STATS_CHROMA_ROWS - 1) / MI_STATS_CHROMA_ROWS; }
+static inline int mi_stats_blocks(int h) { return mi_stats_luma_blocks(h) + mi_stats_chroma_blocks(h); } // (monotonic in h: a launch is sized by its tallest item)
+// The 32-bit partial sums.  A thread's: its share of a band, ceil(rows / 8 * groups / 256) thread items of 128 samples, of at most 255 * 255 each; a
+// block's sums of samples, of differences and its counts (the squares are reduced in 64 bits): rows * width * 255.  At H264MI_SCALE_MAX = 16384:
+#define MI_STATS_MAX_AXIS 16384
+static_assert((MI_STATS_CHROMA_ROWS / 8 * (MI_STATS_MAX_AXIS / 16) / 256 + 1) * 128ull * 255 * 255 < (1ull << 32) && MI_STATS_CHROMA_ROWS >= MI_STATS_LUMA_ROWS,
+              "a thread's 32-bit partial sum of squares overflows");
+static_assert(static_cast<unsigned long long>(MI_STATS_CHROMA_ROWS) * MI_STATS_MAX_AXIS * 255 < (1ull << 32), "a block's 32-bit sums overflow");
+extern "C" __global__ void k_stats(StatsDesc *descs, uint8_t *dst, uint32_t cell_log2, uint32_t planes, uint32_t thresh);
 
 #ifndef MI_INTRA_WAVES
 #define MI_INTRA_WAVES 16 /* 1024 threads, 128 VGPRs per wavefront: the kernels need 120 once nothing lane-dependent is hoisted out of the macroblock loop */

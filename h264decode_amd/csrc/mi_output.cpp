@@ -2,8 +2,9 @@
 // (k_convert: NV12 / RGB), K8 (k_scale: resized) and K9 (k_tensor: model input) over a list of frames of the last executed batch, K10 (k_deint and
 // k_deint_motion: deinterlaced frames, which K6 .. K9 read like frames of the batch), and the device-free rule functions of include/h264mi.h that say what those
 // kernels compute (h264mi_output_size, _csc_resolve, _scale_taps, _fit_rect, _tensor_size, _deint_rows, _deint_motion_pixel, _side_size), and K11 (k_side: the macroblock
-// records of the batch as planes of side information).  The seven kernel families share ONE launch discipline (stage_descs / fence_launch below); each
-// has descriptor tables of its own.
+// records of the batch as planes of side information), and K12 (k_stats: sums, a histogram and differences against a predecessor, per frame and per
+// cell of a grid -- h264mi_stats_size and the statistics history).  The eight kernel families share ONE launch discipline (stage_descs / fence_launch
+// below); each has descriptor tables of its own.
 // (the reference has no output process: h264/server.go:113-166 stops at the parsed slice)
 #include <algorithm>
 #include <cmath>
@@ -646,30 +647,67 @@ static int check_deint_motion(int mode) {
 static bool same_geometry(const OutFrame *a, const OutFrame *b) {
     return a->wmb == b->wmb && a->hmb == b->hmb && a->crop_x == b->crop_x && a->crop_y == b->crop_y && a->width == b->width && a->height == b->height;
 }
+// The histories (HistorySet): `which` is HIST_DEINT (K10, motion-adaptive) or HIST_STATS (K12); both follow one rule, in an arena each
+static const char *const HIST_NAMES[HIST_KINDS] = {"deinterlace", "frame statistics"};
+static_assert(H264MI_STATS_PREV_NONE == H264MI_DEINT_PREV_NONE && H264MI_STATS_PREV_HISTORY == H264MI_DEINT_PREV_HISTORY, "output_predecessors serves both");
 // may frame `of` of stream `si` of the last executed batch take the stream's history as its predecessor
-static bool history_valid(const h264mi_decoder *d, int si, const OutFrame *of) {
-    if (!d->d_history || si < 0 || si >= static_cast<int>(d->history.size())) return false;
-    const DeintHistory &hs = d->history[si];
-    return hs.valid && hs.batch + 1 == d->stage[d->exec].seq && same_geometry(&hs.of, of);
+static bool history_valid(const h264mi_decoder *d, int which, int si, const OutFrame *of) {
+    const HistorySet &hs = d->hist[which];
+    if (!hs.arena || si < 0 || si >= static_cast<int>(hs.slots.size())) return false;
+    const FrameHistory &fh = hs.slots[si];
+    return fh.valid && fh.batch + 1 == d->stage[d->exec].seq && same_geometry(&fh.of, of);
 }
 // the arena of the histories: a frame slot per stream, zero-filled on the decoder's stream (ahead of everything that reads or writes it).  On failure
 // everything is as it was
-static int reserve_history(h264mi_decoder *d) {
-    if (d->d_history) return H264MI_OK;
+static int reserve_history(h264mi_decoder *d, int which) {
+    HistorySet &hs = d->hist[which];
+    if (hs.arena) return H264MI_OK;
     const size_t bytes = d->st.size() * d->slot_bytes;
     uint8_t *p = nullptr;
     if (hipMalloc(&p, bytes) != hipSuccess) {
         (void)hipGetLastError();
-        set_error("deinterlace: no device memory for %zu bytes of history (a frame slot per stream)", bytes);
+        set_error("%s: no device memory for %zu bytes of history (a frame slot per stream)", HIST_NAMES[which], bytes);
         return H264MI_ENOMEM;
     }
     if (hipMemsetAsync(p, 0, bytes, d->stream) != hipSuccess) {
         hipFree(p);
-        set_error("deinterlace: clearing the arena of the histories failed");
+        set_error("%s: clearing the arena of the histories failed", HIST_NAMES[which]);
         return H264MI_EDEVICE;
     }
-    d->d_history = p, d->dev_bytes += bytes;
-    d->history.assign(d->st.size(), DeintHistory());
+    hs.arena = p, d->dev_bytes += bytes;
+    hs.slots.assign(d->st.size(), FrameHistory());
+    return H264MI_OK;
+}
+// take: (stream, frame) whose source becomes the stream's history, behind the launch that may read it on the decoder's stream and inside its fence: the
+// whole coded frame, so that a slot has the layout of the frame it stands for
+static int take_history(h264mi_decoder *d, int which, const FrameList &take) {
+    HistorySet &hs = d->hist[which];
+    for (const std::pair<int, int> &f : take) {
+        uint8_t *p;
+        const OutFrame *of;
+        TRY(frame_ptrs(d, f.first, f.second, &p, &of));
+        FrameHistory &fh = hs.slots[f.first];
+        fh.valid = false;
+        HIP_TRY(hipMemcpyAsync(hs.arena + static_cast<size_t>(f.first) * d->slot_bytes, p, static_cast<size_t>(of->wmb) * of->hmb * 384, hipMemcpyDeviceToDevice, d->stream));
+        fh.valid = true, fh.batch = d->stage[d->exec].seq, fh.of = *of;
+    }
+    return H264MI_OK;
+}
+// prev[f] of every frame f (decoding order) of stream si of the last executed batch, nf > 0 of them: the frame before it in output order, none where that
+// one's geometry differs; the first one: the history, if `history` and it is valid.  *last: the last frame in output order
+static int output_predecessors(h264mi_decoder *d, int which, int si, bool history, std::vector<int32_t> &prev, int *last) {
+    const std::vector<OutFrame> &out = d->stage[d->exec].out[si];
+    const int nf = static_cast<int>(out.size());
+    std::vector<int32_t> order(nf);
+    int32_t k;
+    prev.assign(nf, H264MI_DEINT_PREV_NONE);
+    TRY(h264mi_stream_output_order(d, si, order.data(), nf, &k));
+    for (int i = 0; i < nf; i++) {
+        const OutFrame *of = &out[order[i]];
+        if (i) prev[order[i]] = same_geometry(of, &out[order[i - 1]]) ? order[i - 1] : H264MI_DEINT_PREV_NONE;
+        else prev[order[i]] = history && history_valid(d, which, si, of) ? H264MI_DEINT_PREV_HISTORY : H264MI_DEINT_PREV_NONE;
+    }
+    *last = order[nf - 1];
     return H264MI_OK;
 }
 
@@ -696,12 +734,12 @@ static int motion_items(h264mi_decoder *d, int mode, const h264mi_deint_motion_i
             return H264MI_EINVAL;
         }
         if (it.prev_frame == H264MI_DEINT_PREV_HISTORY) {
-            if (!history_valid(d, it.stream, of)) {
+            if (!history_valid(d, HIST_DEINT, it.stream, of)) {
                 set_error("deinterlace item %zu: stream %d has no valid history for frame %d (none was taken in the batch before, or its size differs, or a reset came in between)",
                           i, it.stream, it.frame);
                 return H264MI_EINVAL;
             }
-            pp = d->d_history + static_cast<size_t>(it.stream) * d->slot_bytes;
+            pp = d->hist[HIST_DEINT].arena + static_cast<size_t>(it.stream) * d->slot_bytes;
         } else if (it.prev_frame != H264MI_DEINT_PREV_NONE) {
             if (frame_ptrs(d, it.stream, it.prev_frame, &pp, &pof) != H264MI_OK) {
                 set_error("deinterlace item %zu: prev_frame %d is not a frame of stream %d in the last executed batch, H264MI_DEINT_PREV_NONE or _PREV_HISTORY", i, it.prev_frame,
@@ -732,16 +770,7 @@ static int motion_items(h264mi_decoder *d, int mode, const h264mi_deint_motion_i
     const int hc = (hmax + 1) / 2, npairs = (hmax + 1) / 2 + (hc + 1) / 2;
     hipLaunchKernelGGL(k_deint_motion, dim3(static_cast<uint32_t>(n), (npairs + pairs_per_block - 1) / pairs_per_block), dim3(256), 0, d->stream, dev, d->d_derived,
                        pairs_per_block);
-    // the histories, behind the launch that may read them: the whole coded frame, so that a slot has the layout of the frame it stands for
-    for (const std::pair<int, int> &f : take) {
-        uint8_t *p;
-        const OutFrame *of;
-        TRY(frame_ptrs(d, f.first, f.second, &p, &of));
-        DeintHistory &hs = d->history[f.first];
-        hs.valid = false;
-        HIP_TRY(hipMemcpyAsync(d->d_history + static_cast<size_t>(f.first) * d->slot_bytes, p, static_cast<size_t>(of->wmb) * of->hmb * 384, hipMemcpyDeviceToDevice, d->stream));
-        hs.valid = true, hs.batch = d->stage[d->exec].seq, hs.of = *of;
-    }
+    TRY(take_history(d, HIST_DEINT, take)); // behind the launch that may read them
     TRY(fence_launch(d, t));
     d->derived.swap(next);
     return H264MI_OK;
@@ -766,7 +795,7 @@ extern "C" int32_t h264mi_batch_deinterlace_motion(h264mi_decoder *d, int32_t st
     const bool history = (flags & H264MI_DEINT_HISTORY) != 0;
     if (history) {
         GUARD(d);
-        TRY(reserve_history(d));
+        TRY(reserve_history(d, HIST_DEINT));
     }
     std::vector<h264mi_deint_motion_item> items;
     FrameList take;
@@ -774,20 +803,15 @@ extern "C" int32_t h264mi_batch_deinterlace_motion(h264mi_decoder *d, int32_t st
     for (int si = 0; si < static_cast<int>(g.out.size()); si++) {
         const int nf = static_cast<int>(g.out[si].size());
         if ((stream >= 0 && stream != si) || nf == 0) continue;
-        std::vector<int32_t> order(nf), prev(nf);
-        int32_t k;
-        TRY(h264mi_stream_output_order(d, si, order.data(), nf, &k));
-        for (int i = 0; i < nf; i++) { // the frame before it in output order; the first one: the history
-            const OutFrame *of = &g.out[si][order[i]];
-            if (i) prev[order[i]] = same_geometry(of, &g.out[si][order[i - 1]]) ? order[i - 1] : H264MI_DEINT_PREV_NONE;
-            else prev[order[i]] = history && history_valid(d, si, of) ? H264MI_DEINT_PREV_HISTORY : H264MI_DEINT_PREV_NONE;
-        }
+        std::vector<int32_t> prev;
+        int last;
+        TRY(output_predecessors(d, HIST_DEINT, si, history, prev, &last));
         for (int f = 0; f < nf; f++) {
             const int first = g.out[si][f].first_parity;
             items.push_back({si, f, first, prev[f]});
             if (rate == 2) items.push_back({si, f, 1 - first, prev[f]});
         }
-        if (history) take.push_back({si, order[nf - 1]});
+        if (history) take.push_back({si, last});
     }
     return motion_items(d, mode, items.data(), items.size(), n_derived, take);
 }
@@ -889,4 +913,145 @@ extern "C" int32_t h264mi_batch_side_device(h264mi_decoder *d, int32_t stream, i
     std::vector<h264mi_side_item> items;
     for (const std::pair<int, int> &f : batch_frames(d, stream)) items.push_back({f.first, f.second});
     return side_items(d, planes, items.data(), items.size(), dst, cap, bytes);
+}
+
+// ---------------------------------------------------------------- frame statistics (K12): the rule of include/h264mi.h, "Frame statistics"
+static_assert(sizeof(h264mi_frame_stats) == 1120 && offsetof(h264mi_frame_stats, min_y) == 64 && offsetof(h264mi_frame_stats, hist_y) == 96,
+              "the record of include/h264mi.h: 8 x uint64_t, 8 x uint32_t, 256 x uint32_t, no padding");
+static_assert(MI_STATS_MAX_AXIS == H264MI_SCALE_MAX, "the overflow bounds of mi_kernels.h are stated for the largest frame h264mi_stats_size accepts");
+
+extern "C" int32_t h264mi_stats_size(const h264mi_stats_spec *spec, int32_t w, int32_t h, int32_t *gw, int32_t *gh, size_t *bytes) {
+    if (!spec) return H264MI_EINVAL;
+    const int cell = spec->cell, planes = spec->planes;
+    const bool grid = cell == 8 || cell == 16 || cell == 32 || cell == 64;
+    if ((!grid && cell != 0) || (planes & ~(H264MI_STATS_CELL_SUM | H264MI_STATS_CELL_SAD)) || (cell == 0) != (planes == 0)) {
+        set_error("statistics grid: cell %d with planes 0x%x: cell must be 8, 16, 32 or 64 with a non-empty set of H264MI_STATS_CELL_* bits, or 0 with planes 0", cell,
+                  static_cast<unsigned>(planes));
+        return H264MI_EINVAL;
+    }
+    if (spec->thresh < 0 || spec->thresh > 255 || spec->flags != 0) {
+        set_error("statistics spec: thresh %d must be 0 .. 255 and flags 0x%x must be 0", spec->thresh, static_cast<unsigned>(spec->flags));
+        return H264MI_EINVAL;
+    }
+    TRY(check_size("statistics frame", w, h));
+    const int cw = grid ? (w + cell - 1) / cell : 0, ch = grid ? (h + cell - 1) / cell : 0;
+    if (gw) *gw = cw;
+    if (gh) *gh = ch;
+    if (bytes) *bytes = sizeof(h264mi_frame_stats) + ((static_cast<size_t>(4) * cw * ch * popcount12(planes) + 15) & ~static_cast<size_t>(15));
+    return H264MI_OK;
+}
+
+// take: as motion_items', for the statistics history; its arena is reserved here, once the call can no longer be refused
+static int stats_items(h264mi_decoder *d, const h264mi_stats_spec *spec, const h264mi_stats_item *items, size_t n, void *dst, size_t cap, size_t *bytes,
+                       const FrameList &take) {
+    TRY(h264mi_stats_size(spec, 1, 1, nullptr, nullptr, nullptr)); // is the spec legal at all (whatever the frames are, and if there are none)
+    if (reinterpret_cast<uintptr_t>(dst) % 16) {
+        set_error("statistics destination %p: not aligned to 16 bytes", dst);
+        return H264MI_EINVAL;
+    }
+    GUARD(d);
+    std::vector<StatsDesc> descs(n);
+    size_t off = 0;
+    int hmax = 0;
+    for (size_t i = 0; i < n; i++) {
+        const h264mi_stats_item &it = items[i];
+        uint8_t *p, *pp = nullptr;
+        const OutFrame *of, *pof;
+        if (frame_ptrs(d, it.stream, it.frame, &p, &of) != H264MI_OK) {
+            set_error("statistics item %zu: no frame %d of stream %d in the last executed batch", i, it.frame, it.stream);
+            return H264MI_EINVAL;
+        }
+        if (it.prev_frame == H264MI_STATS_PREV_HISTORY) {
+            if (it.stream == H264MI_STREAM_DERIVED || !history_valid(d, HIST_STATS, it.stream, of)) {
+                set_error("statistics item %zu: stream %d has no valid history for frame %d (none was taken in the batch before, or its size differs, or a reset came in between; "
+                          "a derived frame has none)", i, it.stream, it.frame);
+                return H264MI_EINVAL;
+            }
+            pp = d->hist[HIST_STATS].arena + static_cast<size_t>(it.stream) * d->slot_bytes;
+        } else if (it.prev_frame != H264MI_STATS_PREV_NONE) {
+            if (frame_ptrs(d, it.stream, it.prev_frame, &pp, &pof) != H264MI_OK) {
+                set_error("statistics item %zu: prev_frame %d is not a frame of stream %d in the last executed batch, H264MI_STATS_PREV_NONE or _PREV_HISTORY", i, it.prev_frame,
+                          it.stream);
+                return H264MI_EINVAL;
+            }
+            if (!same_geometry(of, pof)) {
+                set_error("statistics item %zu: frames %d and %d of stream %d differ in coded size or display rectangle", i, it.frame, it.prev_frame, it.stream);
+                return H264MI_EINVAL;
+            }
+        }
+        int x0, y0, w, h, gw, gh;
+        size_t one;
+        crop_rect(of, 1, &x0, &y0, &w, &h);
+        TRY(h264mi_stats_size(spec, w, h, &gw, &gh, &one));
+        StatsDesc &sd = descs[i];
+        set_source(sd, p, of, x0, y0, w, h, off);
+        sd.prev = reinterpret_cast<uint64_t>(pp), sd.gw = static_cast<uint32_t>(gw), sd.gh = static_cast<uint32_t>(gh);
+        sd.inv_min = 0, sd.ticket = 0;
+        off += one;
+        hmax = std::max(hmax, h);
+    }
+    if (bytes) *bytes = off;
+    if (off > cap) return H264MI_ECAPACITY;
+    if (n == 0) return H264MI_OK;
+    if (!take.empty()) TRY(reserve_history(d, HIST_STATS)); // only now: a call that is refused or too small for its destination (a size query) allocates nothing
+    DescTables &t = d->tables[OUT_STATS];
+    const StatsDesc *dev;
+    TRY(stage_descs(d, t, descs, &dev));
+    // the blocks ADD to what is there: records and planes start from zero.  (The overflow bounds of the partial sums: the static_asserts of mi_kernels.h)
+    HIP_TRY(hipMemsetAsync(dst, 0, off, d->stream));
+    int cell_log2 = 0;
+    while (spec->cell >> (cell_log2 + 1)) cell_log2++;
+    hipLaunchKernelGGL(k_stats, dim3(static_cast<uint32_t>(n), static_cast<uint32_t>(mi_stats_blocks(hmax))), dim3(256), 0, d->stream, const_cast<StatsDesc *>(dev),
+                       static_cast<uint8_t *>(dst), static_cast<uint32_t>(cell_log2), static_cast<uint32_t>(spec->planes), static_cast<uint32_t>(spec->thresh));
+    TRY(take_history(d, HIST_STATS, take)); // behind the launch that may read them
+    return fence_launch(d, t);
+}
+
+extern "C" int32_t h264mi_items_stats_device(h264mi_decoder *d, const h264mi_stats_spec *spec, const h264mi_stats_item *items, int32_t n, void *dst, size_t cap,
+                                             size_t *bytes) {
+    if (!d || !spec || !dst || n < 0 || (n > 0 && !items)) return H264MI_EINVAL;
+    return stats_items(d, spec, items, static_cast<size_t>(n), dst, cap, bytes, {});
+}
+
+// the items of the batch call and, with `take`, the frames whose sources become the histories
+static int stats_plan(h264mi_decoder *d, int stream, int flags, std::vector<h264mi_stats_item> &items, FrameList *take) {
+    if (stream < -1 || stream >= static_cast<int>(d->st.size())) {
+        if (stream == H264MI_STREAM_DERIVED) set_error("statistics plan: the derived frames have no output order; name them through h264mi_items_stats_device");
+        return H264MI_EINVAL;
+    }
+    if (flags & ~H264MI_STATS_HISTORY) {
+        set_error("statistics flags 0x%x: only H264MI_STATS_HISTORY is defined", static_cast<unsigned>(flags));
+        return H264MI_EINVAL;
+    }
+    const bool history = (flags & H264MI_STATS_HISTORY) != 0;
+    const Stage &g = d->stage[d->exec];
+    for (int si = 0; si < static_cast<int>(g.out.size()); si++) {
+        const int nf = static_cast<int>(g.out[si].size());
+        if ((stream >= 0 && stream != si) || nf == 0) continue;
+        std::vector<int32_t> prev;
+        int last;
+        TRY(output_predecessors(d, HIST_STATS, si, history, prev, &last));
+        for (int f = 0; f < nf; f++) items.push_back({si, f, prev[f]});
+        if (history && take) take->push_back({si, last});
+    }
+    return H264MI_OK;
+}
+
+extern "C" int32_t h264mi_batch_stats_plan(h264mi_decoder *d, int32_t stream, int32_t flags, h264mi_stats_item *items, int32_t cap, int32_t *n) {
+    if (!d || !n || cap < 0 || (cap > 0 && !items)) return H264MI_EINVAL;
+    std::vector<h264mi_stats_item> plan;
+    TRY(stats_plan(d, stream, flags, plan, nullptr));
+    *n = static_cast<int32_t>(plan.size());
+    if (plan.size() > static_cast<size_t>(cap)) return H264MI_ECAPACITY;
+    std::copy(plan.begin(), plan.end(), items);
+    return H264MI_OK;
+}
+
+extern "C" int32_t h264mi_batch_stats_device(h264mi_decoder *d, int32_t stream, const h264mi_stats_spec *spec, int32_t flags, void *dst, size_t cap, size_t *bytes) {
+    if (!d || !spec || !dst) return H264MI_EINVAL;
+    TRY(h264mi_stats_size(spec, 1, 1, nullptr, nullptr, nullptr));
+    std::vector<h264mi_stats_item> plan;
+    FrameList take;
+    TRY(stats_plan(d, stream, flags, plan, &take));
+    return stats_items(d, spec, plan.data(), plan.size(), dst, cap, bytes, take);
 }

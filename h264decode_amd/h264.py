@@ -221,6 +221,14 @@ _DEINT_NAMES = {"field": DEINT_FIELD, "blend": DEINT_BLEND, "edge": DEINT_EDGE}
 _DEINT_MOTION_NAMES = {"motion": DEINT_FIELD, "motion_edge": DEINT_EDGE}  # the motion-adaptive modes of Decoder.deinterlace, by the spatial mode they pull from
 DEINT_PREV_NONE, DEINT_PREV_HISTORY = -1, -2          # H264MI_DEINT_PREV_*: prev_frame of a motion-adaptive item / Decoder.derived_prev
 DEINT_HISTORY = 1                                     # H264MI_DEINT_HISTORY: flag of h264mi_batch_deinterlace_motion (Decoder.deinterlace(history=True))
+STATS_CELL_SUM, STATS_CELL_SAD = 1, 2                 # H264MI_STATS_CELL_*: planes of Decoder.stats_batch / stats_items / frame_stats
+STATS_PLANE_NAMES = ("cell_sum", "cell_sad")          # ... by name, in the order they are written; STATS_PLANE_NAMES[i] is bit 1 << i
+STATS_PREV_NONE, STATS_PREV_HISTORY = -1, -2          # H264MI_STATS_PREV_*: prev_frame of a statistics item
+STATS_HISTORY = 1                                     # H264MI_STATS_HISTORY: flag of h264mi_batch_stats_plan / _device (history=True)
+# the scalar fields of h264mi_frame_stats in record order: 8 x uint64 at byte 0, 8 x uint32 at byte 64; hist_y[256] follows at byte 96
+STATS_U64 = ("sum_y", "sum_y2", "sum_cb", "sum_cr", "sad_y", "sse_y", "sad_cb", "sad_cr")
+STATS_U32 = ("min_y", "max_y", "changed_y", "has_prev", "w", "h", "gw", "gh")
+_ECAPACITY = -7                                       # H264MI_ECAPACITY
 _DT_NAMES = {"u8": DT_U8, "uint8": DT_U8, "f16": DT_F16, "float16": DT_F16, "bf16": DT_BF16, "bfloat16": DT_BF16, "f32": DT_F32, "float32": DT_F32}
 
 
@@ -250,6 +258,23 @@ def side_planes(planes):
             raise H264MIError(-1, "unknown side-information plane %r (one of %s)" % (name, ", ".join(SIDE_NAMES)))
         bits |= 1 << SIDE_NAMES.index(name)
     return bits
+
+
+def stats_planes(planes):
+    """A set of H264MI_STATS_CELL_* bits from an int or from plane names ("cell_sum", "cell_sad"; STATS_PLANE_NAMES)."""
+    if isinstance(planes, int):
+        return planes
+    bits = 0
+    for name in planes:
+        if name not in STATS_PLANE_NAMES:
+            raise H264MIError(-1, "unknown statistics plane %r (one of %s)" % (name, ", ".join(STATS_PLANE_NAMES)))
+        bits |= 1 << STATS_PLANE_NAMES.index(name)
+    return bits
+
+
+def stats_spec(cell=0, planes=0, thresh=0):
+    """An h264mi_stats_spec: the cell size of the grid (0: none; 8, 16, 32, 64), its planes, and the threshold of changed_y."""
+    return _lib.StatsSpec(int(cell), stats_planes(planes), int(thresh), 0)
 
 
 def _deint(mode):
@@ -797,6 +822,83 @@ class Decoder:
             views.append(out[at:at + n].view(shp))
             at += n
         return views
+
+    @staticmethod
+    def stats_size(w, h, cell=0, planes=0, thresh=0):
+        """(gw, gh, bytes) of the statistics item of one w x h frame: the 1120-byte record and, behind it, one uint32 plane of ceil(h / cell) x
+        ceil(w / cell) cells per selected plane, rounded up to 16 bytes (h264mi_stats_size)."""
+        gw, gh, n = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_size_t(0)
+        check(_lib.load().h264mi_stats_size(ctypes.byref(stats_spec(cell, planes, thresh)), w, h, ctypes.byref(gw), ctypes.byref(gh), ctypes.byref(n)))
+        return gw.value, gh.value, n.value
+
+    def stats_plan(self, stream=-1, history=False):
+        """The (stream, frame, prev_frame) items stats_batch would use (h264mi_batch_stats_plan; no device work): every frame of `stream` (-1: of all
+        streams, stream-major) in decoding order against the frame before it in output order, STATS_PREV_NONE, or -- the first one, with history=True
+        and a valid history -- STATS_PREV_HISTORY."""
+        n = ctypes.c_int32(0)
+        flags = STATS_HISTORY if history else 0
+        code = self._L.h264mi_batch_stats_plan(self._h, stream, flags, None, 0, ctypes.byref(n))
+        if code != _ECAPACITY:
+            check(code)
+        arr = (_lib.StatsItem * max(n.value, 1))()
+        check(self._L.h264mi_batch_stats_plan(self._h, stream, flags, arr, n.value, ctypes.byref(n)))
+        return [(a.stream, a.frame, a.prev_frame) for a in arr[:n.value]]
+
+    def stats_batch(self, dst_ptr, cap, stream=-1, cell=0, planes=0, thresh=0, history=False):
+        """K12 in one launch: the frame statistics ("Frame statistics" of include/h264mi.h) of every frame of the last executed batch (of one stream, or
+        of all streams, stream-major) against the frame before it in output order, items back to back in the DEVICE buffer at dst_ptr (16-byte aligned).
+        history=True gives each stream's first frame the stream's statistics history, if the batch before took one, and takes one.  Returns the number
+        of bytes."""
+        n = ctypes.c_size_t(0)
+        check(self._L.h264mi_batch_stats_device(self._h, stream, ctypes.byref(stats_spec(cell, planes, thresh)), STATS_HISTORY if history else 0, dst_ptr, cap, ctypes.byref(n)))
+        return n.value
+
+    def stats_items(self, dst_ptr, cap, items, cell=0, planes=0, thresh=0):
+        """K12 in one launch over a list of (stream, frame, prev_frame) items of the last executed batch, in item order; prev_frame is a frame of the same
+        stream, STATS_PREV_NONE or STATS_PREV_HISTORY.  Returns the number of bytes."""
+        arr = (_lib.StatsItem * max(len(items), 1))()
+        for a, it in zip(arr, items):
+            a.stream, a.frame, a.prev_frame = (int(v) for v in it)
+        n = ctypes.c_size_t(0)
+        check(self._L.h264mi_items_stats_device(self._h, ctypes.byref(stats_spec(cell, planes, thresh)), arr, len(items), dst_ptr, cap, ctypes.byref(n)))
+        return n.value
+
+    def frame_stats(self, stream=-1, cell=0, planes=(), thresh=0, items=None, history=False):
+        """The statistics of the frames of `stream` (-1: of all streams, stream-major) of the last executed batch, each against the frame before it in
+        output order (stats_plan), or of the (stream, frame, prev_frame) `items`: one dict per item of torch views of ONE device buffer filled by one K12
+        launch.  The uint64 fields of the record are int64 scalars (0-d tensors), the uint32 scalars int32 ones -- exact, by the bounds of the contract
+        --, "hist_y" is int32[256], and each selected plane ("cell_sum", "cell_sad") is int32[gh, gw].  Synchronises like side_info."""
+        import torch
+        bits = stats_planes(planes)
+        if items is not None and history:
+            raise ValueError("frame_stats: history goes with the batch form; an item names STATS_PREV_HISTORY itself")
+        todo = [tuple(int(v) for v in it) for it in items] if items is not None else self.stats_plan(stream, history)
+        sizes = []
+        for s, f, _ in todo:
+            fi = self.frame_info(s, f)
+            sizes.append(self.stats_size(fi.width, fi.height, cell, bits, thresh))
+        total = sum(n for _, _, n in sizes)
+        out = torch.empty(max(total, 16) // 8, dtype=torch.int64, device="cuda:%d" % self.device)  # (torch allocations are at least 16-byte aligned)
+        if total:
+            torch.cuda.current_stream(out.device).synchronize()  # whatever still uses a recycled block has finished before K12 writes it
+            if items is not None:
+                got = self.stats_items(out.data_ptr(), total, todo, cell, bits, thresh)
+            else:
+                got = self.stats_batch(out.data_ptr(), total, stream, cell, bits, thresh, history)
+            assert got == total
+            self.sync()
+        as32 = out.view(torch.int32)
+        res, at = [], 0
+        for gw, gh, n in sizes:
+            q, d = at // 8, at // 4
+            rec = {name: out[q + i] for i, name in enumerate(STATS_U64)}
+            rec.update({name: as32[d + 16 + i] for i, name in enumerate(STATS_U32)})
+            rec["hist_y"] = as32[d + 24:d + 280]
+            for k, name in enumerate(pn for b, pn in enumerate(STATS_PLANE_NAMES) if bits >> b & 1):
+                rec[name] = as32[d + 280 + k * gw * gh:d + 280 + (k + 1) * gw * gh].view(gh, gw)
+            res.append(rec)
+            at += n
+        return res
 
     def output_order(self, stream=0):
         """Indices (decoding order) of the stream's frames of the last batch in display order: ascending PicOrderCnt per

@@ -742,6 +742,85 @@ int32_t h264mi_items_side_device(h264mi_decoder *dec, int32_t planes, const h264
 /* The same for every frame of the last executed batch: frames of stream `stream` (or of all streams when stream = -1, stream-major) in decoding order. */
 int32_t h264mi_batch_side_device(h264mi_decoder *dec, int32_t stream, int32_t planes, void *dst_device, size_t cap, size_t *bytes);
 
+/* ---- Frame statistics (K12): sums, a histogram and differences against a predecessor, on the device ----
+ * What a caller needs to decide which frames are worth converting -- shot boundaries, frozen or black frames, the part of a frame that changed -- without
+ * moving a sample off the device or through a tensor.  The reference has no such stage (h264/server.go:113-166 stops at the parsed slice).
+ * The statistics of an item are a function of the source's tight I420 frame S (what h264mi_frame_read(crop = 1) returns), a predecessor's tight I420
+ * frame P of the same display size or "none", a cell size and a threshold, and of nothing else; this comment is the contract.  Luma is h x w, each
+ * chroma plane ceil(h / 2) x ceil(w / 2), as in "Deinterlaced output"; only samples of the display rectangle are read; the chroma of a monochrome stream
+ * is 128 throughout and is counted like any other.  All arithmetic is in integers.
+ * Record.  h264mi_frame_stats, 1120 bytes, naturally aligned, little-endian, written by the device:
+ *   sum_y, sum_y2            the sum of S and of S * S over luma
+ *   sum_cb, sum_cr           the sum of S over Cb and over Cr
+ *   sad_y, sse_y             the sum of |S - P| and of (S - P) * (S - P) over luma
+ *   sad_cb, sad_cr           the sum of |S - P| over Cb and over Cr.  All four difference sums are 0 with no predecessor.
+ *   min_y, max_y             the smallest and the largest luma sample
+ *   changed_y                the number of luma samples with |S - P| > thresh; 0 with no predecessor
+ *   has_prev                 1 with a predecessor, else 0
+ *   w, h                     the display size
+ *   gw, gh                   the grid size; 0, 0 without a grid
+ *   hist_y[v]                the number of luma samples equal to v
+ * Grid.  cell is 8, 16, 32 or 64; gw = ceil(w / cell), gh = ceil(h / cell).  Cell (j, i) (row, column) covers display luma rows j * cell ..
+ *   min((j + 1) * cell, h) - 1 and the columns likewise: edge cells are partial, and cells are anchored at the display origin, not the coded one.
+ *   `planes` is a bit set: H264MI_STATS_CELL_SUM is the sum of S over the cell, H264MI_STATS_CELL_SAD the sum of |S - P| over it (all 0 without a
+ *   predecessor).  The selected planes follow the record in ascending bit order, each gh x gw uint32_t, row-major and tight.  cell = 0 goes with
+ *   planes = 0 and only with it: no grid.
+ * Item.  One item occupies 1120 + roundup16(4 * gw * gh * popcount(planes)) bytes (h264mi_stats_size); items follow one another back to back, so every
+ *   record is 16-byte aligned when dst_device is -- it must be, else H264MI_EINVAL.
+ * Spec.  h264mi_stats_spec: cell and planes as above, thresh 0 .. 255, flags 0; anything else is H264MI_EINVAL.
+ * Bounds.  With w, h <= H264MI_SCALE_MAX every uint64_t field is below 2^46 (2^28 samples x 255 x 255 < 2^44) and every uint32_t field below 2^31 (a
+ *   count is at most 2^28, a cell sum at most 64 x 64 x 255 < 2^20): signed 64- and 32-bit views of a record are exact.
+ * Invariants.  The sum of hist_y is w * h; the sum of v * hist_y[v] is sum_y; hist_y[min_y] and hist_y[max_y] are the first and the last non-zero bin;
+ *   the CELL_SUM plane sums to sum_y and the CELL_SAD plane to sad_y; with P = S every difference field and changed_y are 0 and has_prev is 1.
+ * h264mi_stats_size: grid and bytes of one item of a w x h frame as a pure function (no decoder, no device); any of the three pointers may be NULL.
+ *   H264MI_EINVAL: a null or illegal spec, w or h outside 1 .. H264MI_SCALE_MAX.
+ * h264mi_items_stats_device: item i is frame `frame` of stream `stream` of the last executed batch against `prev_frame`: a frame of the SAME stream in
+ *   the last executed batch (it may be `frame` itself), H264MI_STATS_PREV_NONE, or H264MI_STATS_PREV_HISTORY -- the stream's statistics history, which
+ *   must be valid (below).  A predecessor whose coded size or display rectangle differs from the source's is H264MI_EINVAL, and so is any other
+ *   prev_frame.  The source may be a frame of H264MI_STREAM_DERIVED; its prev_frame is then H264MI_STATS_PREV_NONE or another derived frame, and
+ *   H264MI_STATS_PREV_HISTORY is H264MI_EINVAL.  The discipline is h264mi_items_side_device's: every item is checked and sized before anything is
+ *   launched; *bytes receives the total size (also on H264MI_ECAPACITY); nothing is written and nothing is launched on failure; n = 0 succeeds with
+ *   *bytes = 0; the same frame may appear in many items.  ONE launch (K12) on the decoder's stream, behind a clear of the destination range on the same
+ *   stream; the next pass waits for it before it rewrites the frames.
+ * h264mi_batch_stats_plan: the items h264mi_batch_stats_device would use, without a device: every frame of `stream` (of all streams for -1,
+ *   stream-major) in decoding order, each against the frame before it in h264mi_stream_output_order of its stream; a predecessor of another coded size
+ *   or display rectangle resolves to H264MI_STATS_PREV_NONE.  The first frame in output order takes H264MI_STATS_PREV_HISTORY if
+ *   flags & H264MI_STATS_HISTORY and the history is valid, and H264MI_STATS_PREV_NONE otherwise.  *n receives the number of items (also on
+ *   H264MI_ECAPACITY: more than cap; nothing is written then); items may be NULL when cap is 0.  Any other flag bit, and H264MI_STREAM_DERIVED, are
+ *   H264MI_EINVAL.
+ * h264mi_batch_stats_device: the plan, then the item call; with H264MI_STATS_HISTORY it also takes the history, after the launch.
+ * History: the rule of the deinterlacing history ("Motion-adaptive deinterlacing"), in an arena of its own: one frame slot per stream, allocated on first
+ *   use (the first batch call with H264MI_STATS_HISTORY that launches: neither a refused call nor one that returns H264MI_ECAPACITY allocates it), zero-filled, counted by h264mi_decoder_memory and freed by h264mi_decoder_destroy;
+ *   H264MI_ENOMEM leaves everything as it was.  With the flag the batch call copies, after its launch and on the decoder's stream, the whole coded frame
+ *   of each covered stream's last frame in output order into that stream's slot; the next pass waits for the launch and the copies.  A history is valid
+ *   only if it was taken in the batch prepared immediately before the one executed last, its coded size and display rectangle equal the source's, and
+ *   neither h264mi_stream_reset of that stream nor h264mi_decoder_reset came in between.  It is a SECOND history: a statistics call and a motion-adaptive
+ *   deinterlacing call in the same batch each date their own slot, so neither ends the other's.
+ * Out of scope: scene-cut decisions (a threshold is a policy: the caller's arithmetic on the records), chroma histograms and chroma cells, per-item cell
+ *   sizes, windowed metrics, look-ahead, the two fields of a frame separately, MBAFF (as everywhere). */
+#define H264MI_STATS_CELL_SUM 1
+#define H264MI_STATS_CELL_SAD 2
+#define H264MI_STATS_PREV_NONE (-1)
+#define H264MI_STATS_PREV_HISTORY (-2)
+#define H264MI_STATS_HISTORY 1 /* flags of h264mi_batch_stats_plan / h264mi_batch_stats_device */
+typedef struct {
+    uint64_t sum_y, sum_y2, sum_cb, sum_cr;
+    uint64_t sad_y, sse_y, sad_cb, sad_cr;
+    uint32_t min_y, max_y, changed_y, has_prev, w, h, gw, gh;
+    uint32_t hist_y[256];
+} h264mi_frame_stats;
+typedef struct {
+    int32_t cell, planes, thresh, flags;
+} h264mi_stats_spec;
+typedef struct {
+    int32_t stream, frame, prev_frame;
+} h264mi_stats_item;
+int32_t h264mi_stats_size(const h264mi_stats_spec *spec, int32_t w, int32_t h, int32_t *gw, int32_t *gh, size_t *bytes);
+int32_t h264mi_items_stats_device(h264mi_decoder *dec, const h264mi_stats_spec *spec, const h264mi_stats_item *items, int32_t n, void *dst_device, size_t cap,
+                                  size_t *bytes);
+int32_t h264mi_batch_stats_plan(h264mi_decoder *dec, int32_t stream, int32_t flags, h264mi_stats_item *items, int32_t cap, int32_t *n);
+int32_t h264mi_batch_stats_device(h264mi_decoder *dec, int32_t stream, const h264mi_stats_spec *spec, int32_t flags, void *dst_device, size_t cap, size_t *bytes);
+
 /* Debug / test access to the intermediate macroblock records of a frame (host copy).
  * rec: 128 bytes per MB (layout: h264decode_amd/csrc/mi_types.h struct MbRec). */
 int32_t h264mi_frame_read_mbrecs(h264mi_decoder *dec, int32_t stream, int32_t frame, uint8_t *rec, size_t cap);
