@@ -330,6 +330,17 @@ extern "C" int32_t h264mi_internal_band_plan(int32_t n_pics, int32_t wmb, int32_
     return H264MI_OK;
 }
 
+// Not part of the public ABI: the launch plan of K3 alone (mi_intra_bands), with p_only as execute_batch() passes it for a launch without an
+// intra-only picture.  bands 1 = k_intra, more = k_intra_x with `wpr` wavefronts per row; row0 = the first macroblock row of band `band` as
+// k_intra_x cuts a picture of hmb rows (band * hmb / bands).  Reports, changes nothing.
+extern "C" int32_t h264mi_internal_intra_plan(int32_t n_pics, int32_t hmb, int32_t max_wgs, int32_t p_only, int32_t band, int32_t *bands, int32_t *waves, int32_t *wpr, int32_t *row0) {
+    if (!bands || !waves || !wpr || !row0 || n_pics < 1 || hmb < 1 || band < 0) return H264MI_EINVAL;
+    int nb = 1, nw = 1, w = 1;
+    mi_intra_bands(n_pics, hmb, max_wgs, p_only != 0, &nb, &nw, &w);
+    *bands = nb, *waves = nw, *wpr = w, *row0 = band < nb ? band * hmb / nb : hmb;
+    return H264MI_OK;
+}
+
 // Not part of the public ABI: the epoch / ticket counters of the banded kernels set to a value shortly before their 32-bit wrap
 // (tests/test_gpu_parity.py::test_gpu_banded_kernels_across_the_epoch_wrap)
 extern "C" int32_t h264mi_internal_set_epoch(h264mi_decoder *d, uint32_t v) {

@@ -23,7 +23,8 @@ class Params(ctypes.Structure):
         ("motion_x4", ctypes.c_int), ("motion_y4", ctypes.c_int), ("interlace_sps", ctypes.c_int), ("fn_gap_period", ctypes.c_int), ("fn_gap_declared", ctypes.c_int),
         ("b_pyramid", ctypes.c_int), ("slice_groups", ctypes.c_int), ("fmo_type", ctypes.c_int), ("aso", ctypes.c_int), ("field_pics", ctypes.c_int), ("poc_bottom_delta", ctypes.c_int), ("mono", ctypes.c_int),
         ("wp_range", ctypes.c_int), ("poc_step", ctypes.c_int), ("mv_reach", ctypes.c_int), ("mv_margin", ctypes.c_int), ("contrast", ctypes.c_int),
-        ("dbf_per_slice", ctypes.c_int), ("trace_deblock", ctypes.c_int), ("syntax_stim", ctypes.c_int)]
+        ("dbf_per_slice", ctypes.c_int), ("trace_deblock", ctypes.c_int), ("syntax_stim", ctypes.c_int),
+        ("intra_stim", ctypes.c_int), ("trace_intra", ctypes.c_int)]
 
 
 def build(force=False):
@@ -53,6 +54,7 @@ def lib():
         _lib.sg_last_syntax.argtypes = [ctypes.c_void_p, ctypes.c_int]
         _lib.sg_cavlc_level_bits.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
         _lib.sg_last_deblock_trace.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
+        _lib.sg_last_intra_trace.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
     return _lib
 
 
@@ -109,7 +111,12 @@ RANGE_NAMES = (
     "db_bs4_strong_p0_q0", "db_bs4_strong_p0_q1", "db_bs4_strong_p1_q0", "db_bs4_strong_p1_q1",
     "db_index_a_min", "db_index_a_max", "db_index_b_min", "db_index_b_max", "db_index_a_clip0", "db_index_a_clip51",
     "db_qp_odd", "db_pcm_edge", "db_cbcr_alpha", "db_pair_differs", "db_cbcr_pair_differs", "db_seg_none", "db_field_bs3",
-    "db_b_bs1_crossed", "db_b_bs1_straight", "db_b_bs0_crossed", "db_slice_offsets", "db_idc1_modified", "db_idc2_skipped")
+    "db_b_bs1_crossed", "db_b_bs1_straight", "db_b_bs0_crossed", "db_slice_offsets", "db_idc1_modified", "db_idc2_skipped") + tuple(
+    # intra prediction (the SG_R_IP_* counters): availability masks per (kind, mode), top-right use per block index, clips, foreign samples
+    "ip_av%s_m%d" % (k, m) for k, n in (("4", 9), ("8", 9), ("16", 4), ("c", 4)) for m in range(n)) + tuple(
+    "ip_tr%d_b%d" % (k, b) for k, n in ((4, 16), (8, 4)) for b in range(n)) + (
+    "ip_plane16_lo", "ip_plane16_hi", "ip_planec_lo", "ip_planec_hi", "ip_rec_luma_at0", "ip_rec_luma_at255", "ip_rec_chroma_at0", "ip_rec_chroma_at255",
+    "ip_from_inter", "ip_from_pcm", "ip_f8_top_no_tl", "ip_f8_left_no_tl")
 
 
 def last_ranges():
@@ -184,6 +191,34 @@ def last_deblock_trace():
         def planes(a):
             return a[:w * h].reshape(h, w), a[w * h:w * h * 5 // 4].reshape(h // 2, w // 2), a[w * h * 5 // 4:].reshape(h // 2, w // 2)
         out.append(dict(planes=planes(before), after=planes(after), mbs=mbs, field=field, mono=mono, frame=frame))
+    return out
+
+
+# sg_ipmb (sg.h), one per macroblock: what 8.3 needs to know about it
+IPMB = np.dtype(dict(names=["kind", "i16mode", "chroma_mode", "ipm", "slice_id"], formats=["u1", "u1", "u1", ("i1", 16), "u2"], offsets=[0, 1, 2, 4, 20], itemsize=24))
+KIND_INTER, KIND_I4, KIND_I8, KIND_I16, KIND_PCM = range(5)
+
+
+def last_intra_trace():
+    """For every picture of the last encode(trace_intra=1, ...) of this thread, in coding order, what last_deblock_trace() gives (`planes` before
+    sg_deblock, `after`, `mbs`, `field`, `mono`, `frame`) and: `pred` / `res` = (Y, Cb, Cr) of the prediction (uint8) and residual (int16) sample of every
+    intra-predicted sample, 0 elsewhere; `ipmbs` = the sg_ipmb table [rows, columns] (kind: 0 inter, 1 Intra4x4, 2 Intra8x8, 3 Intra16x16, 4 I_PCM; ipm per
+    4x4 block at 4 * row + column; i16mode; chroma_mode; slice_id); `constrained_intra`."""
+    out = last_deblock_trace()
+    for i, t in enumerate(out):
+        info = np.zeros(9, dtype=np.int32)
+        lib().sg_last_intra_trace(i, info.ctypes.data, None, None, 0, None, 0)
+        w, h, wmb, hmb, size = int(info[0]), int(info[1]), int(info[2]), int(info[3]), int(info[7])
+        if size == 0:  # a picture kept for trace_deblock alone
+            continue
+        assert size == IPMB.itemsize, (size, IPMB.itemsize)
+        n = w * h * 3 // 2
+        pred, res, mbs = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int16), np.zeros((hmb, wmb), dtype=IPMB)
+        lib().sg_last_intra_trace(i, None, pred.ctypes.data, res.ctypes.data, n, mbs.ctypes.data, mbs.nbytes)
+
+        def planes(a):
+            return a[:w * h].reshape(h, w), a[w * h:w * h * 5 // 4].reshape(h // 2, w // 2), a[w * h * 5 // 4:].reshape(h // 2, w // 2)
+        t.update(pred=planes(pred), res=planes(res), ipmbs=mbs, constrained_intra=int(info[8]))
     return out
 
 

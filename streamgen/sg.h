@@ -136,6 +136,15 @@ typedef struct {
      * what the B slices contain and leaves the I and P slices out (a stream with B pictures has all three).
      * What the stream then really contains is counted by the entropy writers: sg_last_syntax(). */
     int syntax_stim;
+    /* intra-prediction stimulus (8.3): both 0 = the streams of before, byte for byte, and not one more draw of the generator.
+     * intra_stim 1: among the modes that sg_intra_mode_allowed() permits for a block, the one whose cell (kind, mode, the availability combination the
+     * block sees) was chosen least often so far in this sg_encode() call wins, the SAD score (with its drawn jitter) breaking ties; the same for the
+     * Intra16x16 and the chroma mode; among Intra4x4 / Intra8x8 / Intra16x16 the kind is drawn as before.  Slices of a picture without slice
+     * groups are then split by macroblock COUNT, not by rows, so that they start in the middle of a row.  What was reached: the SG_R_IP_* counters */
+    int intra_stim;
+    /* 1: sg_last_intra_trace() keeps, for every picture of this call, the prediction and residual sample of every intra-predicted sample and the sg_ipmb
+     * table (and what trace_deblock keeps); changes nothing else */
+    int trace_intra;
 } sg_params;
 
 void sg_default_params(sg_params *p);
@@ -200,6 +209,22 @@ enum {
     SG_R_DB_SLICE_OFFSETS,                        /* filtered edges between two slices with different filter offsets */
     SG_R_DB_IDC1_MODIFIED,                        /* edges that changed a sample of a macroblock whose own slice has disable_deblocking_filter_idc 1 */
     SG_R_DB_IDC2_SKIPPED,                         /* macroblock edges left alone only because of idc 2 (the neighbour is in another slice) */
+    /* intra prediction (8.3), counted in encode_intra on the mode finally chosen.  An availability combination is left | top << 1 | topleft << 2 |
+     * topright << 3 as the BLOCK sees it (Intra16x16 and chroma: as the macroblock sees it) */
+    SG_R_IP_AV4,                                  /* [9]: per Intra4x4PredMode, bit c: a block with combination c was predicted in that mode */
+    SG_R_IP_AV8 = SG_R_IP_AV4 + 9,                /* [9]: the same per Intra8x8PredMode */
+    SG_R_IP_AV16 = SG_R_IP_AV8 + 9,               /* [4]: per Intra16x16PredMode */
+    SG_R_IP_AVC = SG_R_IP_AV16 + 4,               /* [4]: per intra_chroma_pred_mode (not counted in monochrome streams) */
+    SG_R_IP_TR4 = SG_R_IP_AVC + 4,                /* [16]: per luma4x4BlkIdx, modes 3 and 7: bit 0 real samples above and to the right were read, bit 1 they were substituted */
+    SG_R_IP_TR8 = SG_R_IP_TR4 + 16,               /* [4]: the same per luma8x8BlkIdx */
+    SG_R_IP_PLANE16_LO = SG_R_IP_TR8 + 4, SG_R_IP_PLANE16_HI, /* samples of an Intra16x16 plane prediction below 0 / above 255 before the clip */
+    SG_R_IP_PLANEC_LO, SG_R_IP_PLANEC_HI,         /* ... of a chroma plane prediction (Cb and Cr) */
+    SG_R_IP_REC_LUMA_AT0, SG_R_IP_REC_LUMA_AT255, /* luma samples of intra-predicted macroblocks whose prediction + residual lay below 0 / above 255 */
+    SG_R_IP_REC_CHROMA_AT0, SG_R_IP_REC_CHROMA_AT255,
+    SG_R_IP_FROM_INTER,                           /* bit 0 left, 1 top, 2 topleft, 3 topright: a block's mode read samples of that direction (8.3; Intra8x8: what
+                                                   * 8.3.2.2.1 reads for them included) and they belong to an inter macroblock */
+    SG_R_IP_FROM_PCM,                             /* ... to an I_PCM macroblock */
+    SG_R_IP_F8_TOP_NO_TL, SG_R_IP_F8_LEFT_NO_TL,  /* Intra8x8 blocks whose mode reads the row above / the column to the left, with p'[0,-1] / p'[-1,0] filtered without p[-1,-1] */
     SG_R_COUNT
 };
 enum {
@@ -256,6 +281,16 @@ int sg_cavlc_level_bits(int level, int suffix_len, int minus2, int escape16, uin
  * 1 top, 2 bottom), mono, the frame of recon[] the picture belongs to, sizeof(sg_dbmb)}, before / after the picture's I420 planes before and
  * after sg_deblock, mbs its sg_dbmb table (each optional, each with its capacity in bytes) */
 int sg_last_deblock_trace(int index, int32_t info[8], uint8_t *before, uint8_t *after, size_t planes_cap, void *mbs, size_t mbs_cap);
+/* sg_params::trace_intra: the same pictures (sg_last_deblock_trace() serves them too).  info receives {width, height, macroblock columns, macroblock
+ * rows, field, mono, frame, sizeof(sg_ipmb), constrained_intra_pred_flag}; pred (bytes) / res (int16_t) the picture's I420 planes of prediction and
+ * residual samples, 0 where a sample was not intra-predicted, planes_cap counted in samples; mbs its sg_ipmb table */
+typedef struct {
+    uint8_t kind;        /* 0 inter (skipped included), 1 Intra4x4, 2 Intra8x8, 3 Intra16x16, 4 I_PCM */
+    uint8_t i16mode, chroma_mode, pad;
+    int8_t ipm[16];      /* Intra4x4PredMode / Intra8x8PredMode of the 4x4 block at raster position 4 * row + column */
+    uint16_t slice_id, pad2;
+} sg_ipmb;
+int sg_last_intra_trace(int index, int32_t info[9], uint8_t *pred, int16_t *res, size_t planes_cap, void *mbs, size_t mbs_cap);
 
 #ifdef __cplusplus
 }

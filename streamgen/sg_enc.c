@@ -81,6 +81,10 @@ typedef struct {
      * Intra16x16 AC / chroma AC / all chroma levels to leave empty, I_PCM forced; what the macroblock before was (0 one with an mb_qp_delta or none, 1
      * skipped, 2 I_PCM, 3 one without mb_qp_delta), whether this one wrote an mb_qp_delta, the run of skipped macroblocks so far */
     int stim, pic_no, sk_from, sk_to, pcm_last, thin, heavy, dens, kill8, kill_ac16, kill_cac, kill_c, force_pcm, prev_kind, had_dqp, run_len;
+    /* sg_params::trace_intra: prediction and residual samples of the current picture (I420 planes of the picture's size), its sg_ipmb table */
+    uint8_t *ip_pred;
+    int16_t *ip_res;
+    sg_ipmb *ipmb;
 } enc;
 
 static char g_err[256];
@@ -710,6 +714,7 @@ static void put_block(uint8_t *dst, int stride, const uint8_t *pred, int n, cons
             dst[y * stride + x] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
         }
 }
+static void put_intra(enc *e, int plane, int x, int y, const uint8_t *pred, int n, const int *res); /* (with the intra counters, below) */
 static sg_avail mb_avail(enc *e) {
     sg_avail a;
     a.left = intra_ok(e, e->mbx - 1, e->mby);
@@ -899,8 +904,13 @@ static void code_chroma(enc *e, int intra, const uint8_t pred[2][64]) {
             for (int y = 0; y < 4; y++) memcpy(pb + 4 * y, pred[c] + (yo + y) * 8 + xo, 4);
             if (m->cbp_chroma) {
                 sg_residual4(e->cac[c][b], ls, qp, 1, dc[b], res);
-                put_block(dst + yo * W2 + xo, W2, pb, 4, res);
-            } else
+                if (intra)
+                    put_intra(e, 1 + c, e->mbx * 8 + xo, e->mby * 8 + yo, pb, 4, res);
+                else
+                    put_block(dst + yo * W2 + xo, W2, pb, 4, res);
+            } else if (intra)
+                put_intra(e, 1 + c, e->mbx * 8 + xo, e->mby * 8 + yo, pb, 4, NULL);
+            else
                 put_block(dst + yo * W2 + xo, W2, pb, 4, NULL);
         }
     }
@@ -1072,6 +1082,13 @@ static void end_mb(enc *e) {
         if (m->ref[i] < 0) d->refid[i] = -1;
         if (m->ref1[i] < 0) d->refid1[i] = -1;
     }
+    if (e->ipmb) {
+        sg_ipmb *t = &e->ipmb[e->addr];
+        memset(t, 0, sizeof(*t));
+        t->kind = (uint8_t)(m->type == T_I4 ? 1 : (m->type == T_I8 ? 2 : (m->type == T_I16 ? 3 : (m->type == T_PCM ? 4 : 0))));
+        t->i16mode = m->i16mode, t->chroma_mode = m->chroma_mode, t->slice_id = m->slice_id;
+        memcpy(t->ipm, m->ipm, sizeof(t->ipm));
+    }
 }
 
 /* choose the QP this MB would like to use */
@@ -1100,6 +1117,53 @@ static int want_qp(enc *e) {
     if (q - e->qp > 25) q = e->qp + 25;
     if (q - e->qp < -26) q = e->qp - 26;
     return q;
+}
+
+/* ------------------------------------------------------------------ intra stimulus, counters and trace (sg_params::intra_stim, trace_intra) */
+/* how often a cell (0 Intra4x4, 1 Intra8x8, 2 Intra16x16, 3 chroma; mode; availability combination) was chosen in this sg_encode() call.  Per thread. */
+static _Thread_local int32_t g_ip_visits[4][9][16];
+static int av_comb(const sg_avail *a) { return a->left | a->top << 1 | a->topleft << 2 | a->topright << 3; }
+/* what a candidate mode is compared by: its SAD (jitter included) and, under intra_stim, ahead of it the visits of its cell */
+static int64_t ip_score(const enc *e, int kslot, int mode, const sg_avail *a, int s) {
+    return e->p.intra_stim == 1 ? ((int64_t)g_ip_visits[kslot][mode][av_comb(a)] << 32) + s : s;
+}
+/* the directions (bit 0 left, 1 top, 2 topleft, 3 topright) whose samples a mode reads: 8.3.1.2.x / 8.3.2.2.x, 8.3.3.x, 8.3.4.x (DC: those that are there) */
+static const uint8_t ip_reads4[9] = {2, 1, 3, 10, 7, 7, 7, 10, 1}, ip_reads16[4] = {2, 1, 3, 7}, ip_readsc[4] = {3, 1, 2, 7};
+/* the mode finally chosen for a block of sz x sz 4x4 blocks at (bx, by) of the current macroblock into the SG_R_IP_* counters */
+static void ip_count(enc *e, int kslot, int mode, const sg_avail *a, int bx, int by, int sz, int blkidx) {
+    static const int base[4] = {SG_R_IP_AV4, SG_R_IP_AV8, SG_R_IP_AV16, SG_R_IP_AVC};
+    const int c = av_comb(a);
+    g_ip_visits[kslot][mode][c]++;
+    g_rng[base[kslot] + mode] |= 1 << c;
+    int r = (kslot < 2 ? ip_reads4 : (kslot == 2 ? ip_reads16 : ip_readsc))[mode] & c;
+    if (kslot < 2 && (mode == 3 || mode == 7)) g_rng[(kslot ? SG_R_IP_TR8 : SG_R_IP_TR4) + blkidx] |= a->topright ? 1 : 2;
+    if (kslot == 1) { /* 8.3.2.2.1: p'[0,-1] and p'[-1,0] read p[-1,-1], p'[7,-1] reads p[8,-1] */
+        if ((r & 2) && !a->topleft) g_rng[SG_R_IP_F8_TOP_NO_TL]++;
+        if ((r & 1) && !a->topleft) g_rng[SG_R_IP_F8_LEFT_NO_TL]++;
+        if (r & 2) r |= 12 & c;
+        if (r & 1) r |= 4 & c;
+    }
+    for (int dir = 0; dir < 4; dir++) {
+        if (!(r >> dir & 1)) continue;
+        const int x = dir == 1 ? bx : (dir == 3 ? bx + sz : bx - 1), y = dir == 0 ? by : by - 1;
+        const int dx = x < 0 ? -1 : (x >= 4 ? 1 : 0), dy = y < 0 ? -1 : 0;
+        if (!dx && !dy) continue; /* samples of this macroblock */
+        const int t = e->mb[(e->mby + dy) * e->wmb + e->mbx + dx].type;
+        if (IS_INTER(t)) g_rng[SG_R_IP_FROM_INTER] |= 1 << dir;
+        if (t == T_PCM) g_rng[SG_R_IP_FROM_PCM] |= 1 << dir;
+    }
+}
+/* put_block() for a block of an intra-predicted macroblock at (x, y) of a plane: counts the clip, keeps prediction and residual for the trace */
+static void put_intra(enc *e, int plane, int x, int y, const uint8_t *pred, int n, const int *res) {
+    const int stride = plane ? e->W / 2 : e->W;
+    const size_t off = (plane == 0 ? 0 : (size_t)e->W * e->H + (size_t)(plane - 1) * (e->W * e->H / 4)) + (size_t)y * stride + x;
+    for (int j = 0; j < n; j++)
+        for (int i = 0; i < n; i++) {
+            const int v = pred[j * n + i] + (res ? res[j * n + i] : 0);
+            g_rng[(plane ? SG_R_IP_REC_CHROMA_AT0 : SG_R_IP_REC_LUMA_AT0) + (v > 255)] += v < 0 || v > 255;
+            if (e->ip_pred) e->ip_pred[off + (size_t)j * stride + i] = pred[j * n + i], e->ip_res[off + (size_t)j * stride + i] = (int16_t)(res ? res[j * n + i] : 0);
+        }
+    put_block(e->cur->pl[plane] + (size_t)y * stride + x, stride, pred, n, res);
 }
 
 /* ------------------------------------------------------------------ intra MB */
@@ -1153,14 +1217,21 @@ static void encode_intra(enc *e, int islice) {
     /* ---- luma ---- */
     if (kind == T_I16) {
         uint8_t pred[256], best[256];
-        int bs = 1 << 30, bm = 2;
+        int64_t bs = INT64_MAX;
+        int bm = 2;
         for (int mode = 0; mode < 4; mode++) {
             if (!sg_intra_mode_allowed(16, mode, &ma)) continue;
             sg_pred_i16(e->cur, e->mbx * 16, e->mby * 16, mode, &ma, pred);
-            int s = sad(src, W, pred, 16, 16, 16) + (int)(rnd(e) % 64);
+            int64_t s = ip_score(e, 2, mode, &ma, sad(src, W, pred, 16, 16, 16) + (int)(rnd(e) % 64));
             if (s < bs) bs = s, bm = mode, memcpy(best, pred, 256);
         }
         m->i16mode = (uint8_t)bm;
+        ip_count(e, 2, bm, &ma, 0, 0, 4, 0);
+        if (bm == 3) { /* the plane predictor once more, counting what its clip does */
+            sg_plane_clip_count = &g_rng[SG_R_IP_PLANE16_LO];
+            sg_pred_i16(e->cur, e->mbx * 16, e->mby * 16, 3, &ma, pred);
+            sg_plane_clip_count = NULL;
+        }
         int sums[16], any_ac = 0;
         for (int idx = 0; idx < 16; idx++) {
             int rr = blk_raster(idx), xo = (rr & 3) * 4, yo = (rr >> 2) * 4, res[16];
@@ -1182,21 +1253,23 @@ static void encode_intra(enc *e, int islice) {
             uint8_t pb[16];
             for (int y = 0; y < 4; y++) memcpy(pb + 4 * y, best + (yo + y) * 16 + xo, 4);
             sg_residual4(e->luma[idx], e->ls4[0][qp % 6], qp, 1, dc[rr], res);
-            put_block(dst + yo * W + xo, W, pb, 4, res);
+            put_intra(e, 0, e->mbx * 16 + xo, e->mby * 16 + yo, pb, 4, res);
         }
     } else if (kind == T_I4) {
         for (int idx = 0; idx < 16; idx++) {
             int rr = blk_raster(idx), bx = rr & 3, by = rr >> 2, xo = bx * 4, yo = by * 4, res[16];
             sg_avail a = blk4_avail(e, bx, by);
             uint8_t pred[16], best[16];
-            int bs = 1 << 30, bm = 2;
+            int64_t bs = INT64_MAX;
+            int bm = 2;
             for (int mode = 0; mode < 9; mode++) {
                 if (!sg_intra_mode_allowed(4, mode, &a)) continue;
                 sg_pred_i4(e->cur, e->mbx * 16 + xo, e->mby * 16 + yo, mode, &a, pred);
-                int s = sad(src + yo * W + xo, W, pred, 4, 4, 4) + (int)(rnd(e) % 24);
+                int64_t s = ip_score(e, 0, mode, &a, sad(src + yo * W + xo, W, pred, 4, 4, 4) + (int)(rnd(e) % 24));
                 if (s < bs) bs = s, bm = mode, memcpy(best, pred, 16);
             }
             m->ipm[rr] = (int8_t)bm;
+            ip_count(e, 0, bm, &a, bx, by, 1, idx);
             for (int y = 0; y < 4; y++)
                 for (int x = 0; x < 4; x++) res[y * 4 + x] = src[(yo + y) * W + xo + x] - best[y * 4 + x];
             sg_quant4(res, e->ls4[0][qp % 6], qp, deadzone(1), 0, e->luma[idx]);
@@ -1204,7 +1277,7 @@ static void encode_intra(enc *e, int islice) {
             /* cbp is per 8x8: decide after the 4th block of each 8x8; reconstruct assuming "coded" and
              * fix up below if the whole 8x8 quantised to zero (then residual is zero anyway) */
             sg_residual4(e->luma[idx], e->ls4[0][qp % 6], qp, 0, 0, res);
-            put_block(dst + yo * W + xo, W, best, 4, res);
+            put_intra(e, 0, e->mbx * 16 + xo, e->mby * 16 + yo, best, 4, res);
             if (count_nz(e->luma[idx], 16)) m->cbp_luma |= (uint8_t)(1 << (idx >> 2));
         }
     } else { /* T_I8 */
@@ -1213,13 +1286,15 @@ static void encode_intra(enc *e, int islice) {
             int xo = (b8 & 1) * 8, yo = (b8 >> 1) * 8, res[64];
             sg_avail a = blk8_avail(e, b8);
             uint8_t pred[64], best[64];
-            int bs = 1 << 30, bm = 2;
+            int64_t bs = INT64_MAX;
+            int bm = 2;
             for (int mode = 0; mode < 9; mode++) {
                 if (!sg_intra_mode_allowed(8, mode, &a)) continue;
                 sg_pred_i8(e->cur, e->mbx * 16 + xo, e->mby * 16 + yo, mode, &a, pred);
-                int s = sad(src + yo * W + xo, W, pred, 8, 8, 8) + (int)(rnd(e) % 48);
+                int64_t s = ip_score(e, 1, mode, &a, sad(src + yo * W + xo, W, pred, 8, 8, 8) + (int)(rnd(e) % 48));
                 if (s < bs) bs = s, bm = mode, memcpy(best, pred, 64);
             }
+            ip_count(e, 1, bm, &a, (b8 & 1) * 2, (b8 >> 1) * 2, 2, b8);
             int r0 = (b8 >> 1) * 8 + (b8 & 1) * 2;
             m->ipm[r0] = m->ipm[r0 + 1] = m->ipm[r0 + 4] = m->ipm[r0 + 5] = (int8_t)bm;
             for (int y = 0; y < 8; y++)
@@ -1229,15 +1304,16 @@ static void encode_intra(enc *e, int islice) {
             if (count_nz(e->luma8[b8], 64)) {
                 m->cbp_luma |= (uint8_t)(1 << b8);
                 sg_residual8(e->luma8[b8], e->ls8[0][qp % 6], qp, res);
-                put_block(dst + yo * W + xo, W, best, 8, res);
+                put_intra(e, 0, e->mbx * 16 + xo, e->mby * 16 + yo, best, 8, res);
             } else
-                put_block(dst + yo * W + xo, W, best, 8, NULL);
+                put_intra(e, 0, e->mbx * 16 + xo, e->mby * 16 + yo, best, 8, NULL);
         }
     }
     /* ---- chroma ---- */
     {
         uint8_t pred[2][64], tmp[2][64];
-        int bs = 1 << 30, bm = 0;
+        int64_t bs = INT64_MAX;
+        int bm = 0;
         for (int mode = 0; mode < (e->p.mono ? 1 : 4); mode++) { /* (monochrome: no intra_chroma_pred_mode -- DC of planes that are 128 everywhere) */
             if (!sg_intra_mode_allowed(0, mode, &ma)) continue;
             int s = (int)(rnd(e) % 32);
@@ -1245,9 +1321,15 @@ static void encode_intra(enc *e, int islice) {
                 sg_pred_chroma(e->cur, 1 + c, e->mbx * 8, e->mby * 8, mode, &ma, tmp[c]);
                 s += sad(e->src + W * e->H + c * (W * e->H / 4) + e->mby * 8 * (W / 2) + e->mbx * 8, W / 2, tmp[c], 8, 8, 8);
             }
-            if (s < bs) bs = s, bm = mode, memcpy(pred, tmp, sizeof(pred));
+            if (ip_score(e, 3, mode, &ma, s) < bs) bs = ip_score(e, 3, mode, &ma, s), bm = mode, memcpy(pred, tmp, sizeof(pred));
         }
         m->chroma_mode = (uint8_t)bm;
+        if (!e->p.mono) ip_count(e, 3, bm, &ma, 0, 0, 4, 0);
+        if (bm == 3) {
+            sg_plane_clip_count = &g_rng[SG_R_IP_PLANEC_LO];
+            for (int c = 0; c < 2; c++) sg_pred_chroma(e->cur, 1 + c, e->mbx * 8, e->mby * 8, 3, &ma, tmp[c]);
+            sg_plane_clip_count = NULL;
+        }
         code_chroma(e, 1, pred);
     }
     /* ---- syntax ---- */
@@ -2383,11 +2465,16 @@ typedef struct {
     int32_t info[8];
     uint8_t *before, *after; /* I420 planes of the picture */
     sg_dbmb *mbs;
+    /* trace_intra */
+    int32_t constrained;
+    uint8_t *pred;
+    int16_t *res;
+    sg_ipmb *ipmbs;
 } db_trace;
 static _Thread_local db_trace *g_trace;
 static _Thread_local int g_ntrace, g_trace_cap;
 static void trace_clear(void) {
-    for (int i = 0; i < g_ntrace; i++) free(g_trace[i].before), free(g_trace[i].after), free(g_trace[i].mbs);
+    for (int i = 0; i < g_ntrace; i++) free(g_trace[i].before), free(g_trace[i].after), free(g_trace[i].mbs), free(g_trace[i].pred), free(g_trace[i].res), free(g_trace[i].ipmbs);
     g_ntrace = 0;
 }
 static void trace_planes(const sg_pic *p, uint8_t *dst) {
@@ -2409,8 +2496,14 @@ static void trace_picture(const enc *e, int frame, int after) {
     }
     db_trace *t = &g_trace[g_ntrace];
     t->before = (uint8_t *)malloc(psz), t->after = (uint8_t *)malloc(psz), t->mbs = (sg_dbmb *)malloc(msz);
-    if (!t->before || !t->after || !t->mbs) {
-        free(t->before), free(t->after), free(t->mbs);
+    t->pred = NULL, t->res = NULL, t->ipmbs = NULL, t->constrained = e->p.constrained_intra;
+    if (e->ip_pred) {
+        t->pred = (uint8_t *)malloc(psz), t->res = (int16_t *)malloc(psz * sizeof(int16_t)), t->ipmbs = (sg_ipmb *)malloc(sizeof(sg_ipmb) * (size_t)e->wmb * e->hmb);
+        if (t->pred && t->res && t->ipmbs)
+            memcpy(t->pred, e->ip_pred, psz), memcpy(t->res, e->ip_res, psz * sizeof(int16_t)), memcpy(t->ipmbs, e->ipmb, sizeof(sg_ipmb) * (size_t)e->wmb * e->hmb);
+    }
+    if (!t->before || !t->after || !t->mbs || (e->ip_pred && (!t->pred || !t->res || !t->ipmbs))) {
+        free(t->before), free(t->after), free(t->mbs), free(t->pred), free(t->res), free(t->ipmbs);
         return;
     }
     const int32_t info[8] = {p->w, p->h, e->wmb, e->hmb, e->field ? 1 + e->bottom : 0, e->p.mono, frame, (int32_t)sizeof(sg_dbmb)};
@@ -2427,6 +2520,17 @@ int sg_last_deblock_trace(int index, int32_t info[8], uint8_t *before, uint8_t *
         if (before && planes_cap >= psz) memcpy(before, t->before, psz);
         if (after && planes_cap >= psz) memcpy(after, t->after, psz);
         if (mbs && mbs_cap >= msz) memcpy(mbs, t->mbs, msz);
+    }
+    return g_ntrace;
+}
+int sg_last_intra_trace(int index, int32_t info[9], uint8_t *pred, int16_t *res, size_t planes_cap, void *mbs, size_t mbs_cap) {
+    if (index >= 0 && index < g_ntrace && g_trace[index].pred) {
+        const db_trace *t = &g_trace[index];
+        const size_t psz = (size_t)t->info[0] * t->info[1] * 3 / 2, msz = sizeof(sg_ipmb) * (size_t)t->info[2] * t->info[3];
+        if (info) memcpy(info, t->info, sizeof(t->info)), info[7] = (int32_t)sizeof(sg_ipmb), info[8] = t->constrained;
+        if (pred && planes_cap >= psz) memcpy(pred, t->pred, psz);
+        if (res && planes_cap >= psz) memcpy(res, t->res, psz * sizeof(int16_t));
+        if (mbs && mbs_cap >= msz) memcpy(mbs, t->ipmbs, msz);
     }
     return g_ntrace;
 }
@@ -3064,6 +3168,11 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
     g_rng[SG_R_W_MIN] = g_rng[SG_R_O_MIN] = g_rng[SG_R_IMPLICIT_W1_MIN] = 1 << 20, g_rng[SG_R_W_MAX] = g_rng[SG_R_O_MAX] = g_rng[SG_R_IMPLICIT_W1_MAX] = -(1 << 20);
     g_rng[SG_R_DB_IA_MIN] = g_rng[SG_R_DB_IB_MIN] = 1 << 20, g_rng[SG_R_DB_IA_MAX] = g_rng[SG_R_DB_IB_MAX] = -(1 << 20);
     trace_clear();
+    memset(g_ip_visits, 0, sizeof(g_ip_visits));
+    if (p->trace_intra) {
+        e->ip_pred = (uint8_t *)calloc(fsz, 1), e->ip_res = (int16_t *)calloc(fsz, sizeof(int16_t));
+        e->ipmb = (sg_ipmb *)calloc((size_t)e->wmb * e->hmb, sizeof(sg_ipmb));
+    }
     const int pstep = p->poc_step > 1 && p->poc_type != 2 ? (p->poc_step > 31 ? 31 : p->poc_step) : 1;
     /* coding order.  Without B pictures it is the display order.  With them every (bframes + 1)-th picture is an anchor
      * (I or P) and the pictures between two anchors are B pictures coded right after the later anchor -- unless that anchor
@@ -3243,6 +3352,7 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
             for (int i = 0; i < 4; i++)
                 for (int c = 0; c < 2; c++) e->wp_cw[i][c] = e->wb_cw1[i][c] = 1 << e->wp_cd, e->wp_co[i][c] = e->wb_co1[i][c] = 0;
         for (int i = 0; i < e->wmb * e->hmb; i++) e->mb[i].type = T_NONE;
+        if (e->ip_pred) memset(e->ip_pred, 0, fsz), memset(e->ip_res, 0, fsz * sizeof(int16_t));
         e->pic_no++;
         /* the slices of this picture: (first macroblock, macroblock count), in the order they will be sent */
         int sl_first[512], sl_count[512], nsl = 0;
@@ -3268,7 +3378,11 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
         } else
             for (int s = 0; s < p->slices; s++) {
                 int row0 = e->hmb * s / p->slices, row1 = e->hmb * (s + 1) / p->slices;
-                if (row1 > row0) sl_first[nsl] = row0 * e->wmb, sl_count[nsl++] = (row1 - row0) * e->wmb;
+                if (p->intra_stim == 1) { /* by macroblock count: a slice may start in the middle of a row */
+                    const int a0 = e->wmb * e->hmb * s / p->slices, a1 = e->wmb * e->hmb * (s + 1) / p->slices;
+                    if (a1 > a0) sl_first[nsl] = a0, sl_count[nsl++] = a1 - a0;
+                } else if (row1 > row0)
+                    sl_first[nsl] = row0 * e->wmb, sl_count[nsl++] = (row1 - row0) * e->wmb;
             }
         if (p->aso) /* arbitrary slice order: a rotation plus a swap, different for every picture */
             for (int k = nsl - 1; k > 0; k--) {
@@ -3430,11 +3544,11 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
             }
             out += n;
         }
-        if (p->trace_deblock) trace_picture(e, t, 0);
+        if (p->trace_deblock || p->trace_intra) trace_picture(e, t, 0);
         sg_db_count = g_rng;
         sg_deblock(e->cur, e->db, e->wmb, e->hmb, p->mono);
         sg_db_count = NULL;
-        if (p->trace_deblock) trace_picture(e, t, 1);
+        if (p->trace_deblock || p->trace_intra) trace_picture(e, t, 1);
         if (e->field) {
             e->cur->is_ref = e->nal_ref_idc ? 1 : 0; /* (short-term or not: what colZeroFlag asks of RefPicList1[0]; the window lives on the frames) */
             if (e->nal_ref_idc && p->bframes > 0) { /* a later B field may take this field as its co-located picture */
@@ -3488,6 +3602,7 @@ done:
     for (int i = 0; i < 6; i++) free(e->pics[i].pl[0]), free(e->pics[i].motion), free(e->fpics[i][0].pl[0]), free(e->fpics[i][1].pl[0]), free(e->fpics[i][0].motion), free(e->fpics[i][1].motion);
     free(e->mb);
     free(e->db);
+    free(e->ip_pred), free(e->ip_res), free(e->ipmb);
     free(e->src);
     free(frame_src);
     free(e->sgmap);

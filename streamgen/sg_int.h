@@ -62,6 +62,9 @@ void sg_mc_luma(const sg_pic *ref, int x, int y, int w, int h, int mvx, int mvy,
 /* while set, sg_mc_luma() counts the half samples that its result is made of and that the clip changed: [0] / [1] = b, h, s, m
  * (one 6-tap filter) below 0 / above 255, [2] / [3] = j (two filters).  The motion search leaves it NULL.  Per thread. */
 extern _Thread_local int32_t *sg_mc_clip_count;
+/* while set, the plane predictors of sg_pred_i16() / sg_pred_chroma() count their samples below 0 ([0]) and above 255 ([1]) before the clip.  The mode
+ * search leaves it NULL.  Per thread. */
+extern _Thread_local int32_t *sg_plane_clip_count;
 void sg_mc_chroma(const sg_pic *ref, int plane, int x, int y, int w, int h, int mvx, int mvy, uint8_t *dst, int dstride);
 
 /* levels in scan order -> residual samples (raster).  ls = LevelScale for qP%6, raster order. */

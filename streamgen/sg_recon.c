@@ -169,6 +169,7 @@ void sg_pred_i8(const sg_pic *p, int x, int y, int mode, const sg_avail *a, uint
     else
         directional(&f, 8, mode, pred);
 }
+_Thread_local int32_t *sg_plane_clip_count;
 static void plane_mode(const edges *e, int n, uint8_t *pred) {
     int hh = 0, vv = 0, m = n / 2;
     for (int k = 1; k <= m; k++) {
@@ -179,7 +180,11 @@ static void plane_mode(const edges *e, int n, uint8_t *pred) {
     int b = n == 16 ? (5 * hh + 32) >> 6 : (34 * hh + 32) >> 6;
     int c = n == 16 ? (5 * vv + 32) >> 6 : (34 * vv + 32) >> 6;
     for (int y = 0; y < n; y++)
-        for (int x = 0; x < n; x++) pred[y * n + x] = (uint8_t)clip255((a + b * (x - m + 1) + c * (y - m + 1) + 16) >> 5);
+        for (int x = 0; x < n; x++) {
+            const int v = (a + b * (x - m + 1) + c * (y - m + 1) + 16) >> 5;
+            if (sg_plane_clip_count) sg_plane_clip_count[0] += v < 0, sg_plane_clip_count[1] += v > 255;
+            pred[y * n + x] = (uint8_t)clip255(v);
+        }
 }
 void sg_pred_i16(const sg_pic *p, int x, int y, int mode, const sg_avail *a, uint8_t *pred) {
     edges ed, *e = &ed;

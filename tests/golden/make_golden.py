@@ -105,6 +105,27 @@ def entropy_syntax_vectors():
 
 entropy_syntax_vectors()
 
+
+def intra_vectors():
+    """tests/intrautil.py: the recipes whose intra-prediction cells are counted, and the geometries K3's schedules distinguish."""
+    import intrautil
+    out, lines = {}, []
+    for name in sorted(intrautil.RECIPES):
+        s, rec, _ = streamgen.encode(**intrautil.RECIPES[name])
+        lines.append(intrautil.counter_line(name, streamgen.last_ranges()))
+        frames, _ = oracle.decode(s, crop=False)
+        assert (frames == rec).all(), name
+        out[name] = {"stream_md5": hashlib.md5(s).hexdigest(), "frames_md5": hashlib.md5(rec.tobytes()).hexdigest(), "stream_bytes": len(s)}
+    json.dump(out, open(os.path.join(HERE, "intra_md5.json"), "w"), indent=1, sort_keys=True)
+    open(os.path.join(HERE, "intra_counters.txt"), "w").write(
+        "streamgen.last_ranges() of the recipes of tests/intrautil.py at the seeds chosen there (what met the conditions of intrautil.unmet()).\n"
+        "cells = cells reached; 4 / 8 / 16 / c = per prediction mode the mask of availability combinations (left | top << 1 | topleft << 2 | topright << 3);\n"
+        "tr4 / tr8 = per block index, modes 3 and 7: 1 real samples above right, 2 substituted, 3 both.\n" + "\n".join(lines) + "\n")
+    print("wrote", len(out), "intra vectors")
+
+
+intra_vectors()
+
 # the characterisation trace of the product's picture management (tests/dpbtrace.py; CPU, null device): MD5 of the trace text of every case.  It
 # pins what the code DOES, so it is written once and not again for a change that is meant to keep behaviour.  Only with --dpb-trace.
 if "--dpb-trace" in sys.argv[1:]:
