@@ -1,7 +1,7 @@
 /*
  * examples/h264mi_decode.c -- the C ABI from plain C: decode an Annex-B file to raw I420 on the GPU.
  *
- *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--conceal...] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge|motion|motion-edge] [--field-rate] [--stats]
+ *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--random-access] [--conceal...] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge|motion|motion-edge] [--field-rate] [--stats]
  *
  * --nv12 / --rgb write NV12 / tight R, G, B bytes instead of I420: the frames are converted on the device (h264mi_batch_convert_device into a
  * device buffer, matrix and range from each frame's own SPS) and copied to the host from there.  --scale WxH writes every frame at W x H instead of
@@ -47,7 +47,7 @@ static int fail(const char *what, int code) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge|motion|motion-edge] [--field-rate] [--stats]\n", argv[0]);
+        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--random-access] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge|motion|motion-edge] [--field-rate] [--stats]\n", argv[0]);
         return 2;
     }
     int stats = 0; /* --stats (the last argument of all): the frame statistics of every batch, on stdout */
@@ -106,6 +106,10 @@ int main(int argc, char **argv) {
     /* --conceal-lone-fields: what --conceal-all conceals, and the wholly lost field of a frame coded as two field pictures */
     else if (argc > 3 && !strcmp(argv[argc - 1], "--conceal-lone-fields"))
         conceal = H264MI_CONCEAL_SLICES | H264MI_CONCEAL_PICTURES | H264MI_CONCEAL_FIELDS | H264MI_CONCEAL_LONE_FIELDS, argc--;
+    /* --random-access (last argument but for the concealment): a file that starts in the middle of a stream -- cut from a broadcast, or read from a seek
+     * position on -- is decoded from its first recovery point on (h264mi_decoder_set_random_access); without it only from an IDR picture on */
+    int random_access = 0;
+    if (argc > 3 && !strcmp(argv[argc - 1], "--random-access")) random_access = 1, argc--;
     const int per_batch = argc > 3 ? atoi(argv[3]) : 30;
     FILE *f = fopen(argv[1], "rb");
     if (!f) return fail("fopen", -1);
@@ -145,6 +149,7 @@ int main(int argc, char **argv) {
     cfg.conceal_errors = conceal;
     h264mi_decoder *dec = NULL;
     if ((r = h264mi_decoder_create(&cfg, &dec)) != H264MI_OK) return fail("h264mi_decoder_create", r);
+    if (random_access && (r = h264mi_decoder_set_random_access(dec, H264MI_RA_RECOVERY_POINT)) != H264MI_OK) return fail("h264mi_decoder_set_random_access", r);
 
     FILE *out = fopen(argv[2], "wb");
     const size_t fsz = H264MI_I420_SIZE(sps.width, sps.height);

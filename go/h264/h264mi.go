@@ -464,6 +464,59 @@ func (d *Decoder) SetIsolation(on bool) error {
 	}
 	return status(C.h264mi_decoder_set_isolation(d.h, C.int32_t(v)))
 }
+// SetRandomAccess: with on, a stream that has decoded nothing yet, or that an error took out, starts at its next IDR picture or at its next
+// non-IDR picture whose access unit carried a recovery point SEI message with recovery_frame_cnt 0 (h264mi_decoder_set_random_access); the slices
+// in front of it are skipped without an error, the pictures that precede the entry picture in output order are dropped.
+func (d *Decoder) SetRandomAccess(on bool) error {
+	v := 0 // H264MI_RA_OFF
+	if on {
+		v = 1 // H264MI_RA_RECOVERY_POINT
+	}
+	return status(C.h264mi_decoder_set_random_access(d.h, C.int32_t(v)))
+}
+
+// RecoveryPoint mirrors h264mi_recovery_point: the recovery point SEI message (D.1.7) of an SEI NAL unit.
+type RecoveryPoint struct {
+	Found                                   bool
+	RecoveryFrameCnt, ChangingSliceGroupIdc int
+	ExactMatchFlag, BrokenLinkFlag          bool
+}
+
+// SEIRecoveryPoint walks the messages of one SEI NAL unit (from its header byte on, emulation prevention still in) for the first recovery point.
+func SEIRecoveryPoint(nal []byte) (RecoveryPoint, error) {
+	var c C.h264mi_recovery_point
+	if len(nal) == 0 {
+		return RecoveryPoint{}, status(C.H264MI_EINVAL)
+	}
+	if err := status(C.h264mi_sei_recovery_point((*C.uint8_t)(unsafe.Pointer(&nal[0])), C.size_t(len(nal)), &c)); err != nil {
+		return RecoveryPoint{}, err
+	}
+	return RecoveryPoint{Found: c.found != 0, RecoveryFrameCnt: int(c.recovery_frame_cnt), ChangingSliceGroupIdc: int(c.changing_slice_group_idc),
+		ExactMatchFlag: c.exact_match_flag != 0, BrokenLinkFlag: c.broken_link_flag != 0}, nil
+}
+
+// FrameEntry mirrors h264mi_frame_entry_info: what the access unit of a frame said about random access, and whether the stream entered there.
+type FrameEntry struct {
+	RecoveryPoint
+	Entry bool
+}
+
+func (d *Decoder) FrameEntry(stream, frame int) (FrameEntry, error) {
+	var c C.h264mi_frame_entry_info
+	if err := status(C.h264mi_frame_entry(d.h, C.int32_t(stream), C.int32_t(frame), &c)); err != nil {
+		return FrameEntry{}, err
+	}
+	return FrameEntry{RecoveryPoint: RecoveryPoint{Found: c.recovery_point != 0, RecoveryFrameCnt: int(c.recovery_frame_cnt), ChangingSliceGroupIdc: int(c.changing_slice_group_idc),
+		ExactMatchFlag: c.exact_match_flag != 0, BrokenLinkFlag: c.broken_link_flag != 0}, Entry: c.entry != 0}, nil
+}
+
+// RandomAccessStats: non-IDR entry points taken, slice NAL units skipped while the stream waited, leading pictures dropped (h264mi_stream_random_access_stats).
+func (d *Decoder) RandomAccessStats(stream int) (entries, skippedWaitingNals, skippedLeadingPictures int64, err error) {
+	var c C.h264mi_random_access_stats
+	err = status(C.h264mi_stream_random_access_stats(d.h, C.int32_t(stream), &c))
+	return int64(c.entries), int64(c.skipped_waiting_nals), int64(c.skipped_leading_pictures), err
+}
+
 func (d *Decoder) StreamStatus(stream int) (int, error) {
 	var st C.int32_t
 	err := status(C.h264mi_stream_status(d.h, C.int32_t(stream), &st))

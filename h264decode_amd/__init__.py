@@ -7,7 +7,7 @@ from ._lib import H264MIError, build, lib, load, load_hooks  # noqa: F401
 from .h264 import (  # noqa: F401
     NALU_TYPE_NAMES, PPS, SPS, Decoder, NalUnit, NewNalUnit, NewPPS, NewSPS, NewSliceContext, SliceContext, SliceHeader,
     VideoStream, read_nal_units, MapUnitToSliceGroupMap, MbToSliceGroupMap, nextMbAddress, AccessUnitSplitter, DisplayOrder, H264Reader, handleConnection, ByteStreamReader, BatchServer,
-    CONCEAL_SLICES, CONCEAL_PICTURES, CONCEAL_FIELDS, CONCEAL_IDR, CONCEAL_LONE_FIELDS, CONCEAL_MAX_GAP,
+    CONCEAL_SLICES, CONCEAL_PICTURES, CONCEAL_FIELDS, CONCEAL_IDR, CONCEAL_LONE_FIELDS, CONCEAL_MAX_GAP, RA_OFF, RA_RECOVERY_POINT,
     FMT_I420, FMT_NV12, FMT_RGB24, FMT_RGBP, CSC_AUTO, CSC_BT601, CSC_BT709, CSC_FULL_RANGE, CSC_CHROMA_BILINEAR,
     SCALE_BILINEAR, SCALE_AREA, scale_taps,
     DT_U8, DT_F16, DT_BF16, DT_F32, FIT_STRETCH, FIT_LETTERBOX, TENSOR_BGR, fit_rect, tensor_spec,

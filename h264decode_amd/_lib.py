@@ -53,6 +53,7 @@ FieldInfo, DeintItem = _S["h264mi_field_info"], _S["h264mi_deint_item"]
 SideItem = _S["h264mi_side_item"]
 DeintMotionItem = _S["h264mi_deint_motion_item"]
 FrameStats, StatsSpec, StatsItem = _S["h264mi_frame_stats"], _S["h264mi_stats_spec"], _S["h264mi_stats_item"]
+RecoveryPoint, FrameEntryInfo, RandomAccessStats = _S["h264mi_recovery_point"], _S["h264mi_frame_entry_info"], _S["h264mi_random_access_stats"]
 
 
 def build(force=False):
@@ -129,6 +130,10 @@ def load():
         "h264mi_stream_reset": [vp, I32],
         "h264mi_stream_status": [vp, I32, P(I32)],
         "h264mi_decoder_set_isolation": [vp, I32],
+        "h264mi_decoder_set_random_access": [vp, I32],
+        "h264mi_sei_recovery_point": [u8p, SZ, P(RecoveryPoint)],
+        "h264mi_frame_entry": [vp, I32, I32, P(FrameEntryInfo)],
+        "h264mi_stream_random_access_stats": [vp, I32, P(RandomAccessStats)],
         "h264mi_frame_get_info": [vp, I32, I32, P(FrameInfo)],
         "h264mi_stream_output_order": [vp, I32, P(I32), I32, P(I32)],
         "h264mi_batch_prepare": [vp, I32, P(vp), P(SZ), P(BatchInfo)],
@@ -214,4 +219,5 @@ EXPORTS = ["h264mi_annexb_scan", "h264mi_nal_parse", "h264mi_sps_parse", "h264mi
            "h264mi_deint_rows", "h264mi_frame_fields", "h264mi_items_deinterlace", "h264mi_batch_deinterlace",
            "h264mi_deint_motion_pixel", "h264mi_items_deinterlace_motion", "h264mi_batch_deinterlace_motion", "h264mi_derived_prev",
            "h264mi_side_size", "h264mi_frame_ref_pocs", "h264mi_items_side_device", "h264mi_batch_side_device",
-           "h264mi_stats_size", "h264mi_items_stats_device", "h264mi_batch_stats_plan", "h264mi_batch_stats_device"]
+           "h264mi_stats_size", "h264mi_items_stats_device", "h264mi_batch_stats_plan", "h264mi_batch_stats_device",
+           "h264mi_decoder_set_random_access", "h264mi_sei_recovery_point", "h264mi_frame_entry", "h264mi_stream_random_access_stats"]

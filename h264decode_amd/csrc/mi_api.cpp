@@ -452,7 +452,9 @@ void reset_stream(StreamState &s, bool keep_parameter_sets) {
     s.n_pics_in_batch = 0;
     s.pending_drops = 0;
     s.ref_seq = StreamState::RefSeq();
+    s.sei = {0, 0, 0, 0, 0}, s.decoded_any = s.lead = s.skipping = false; // random access: the stream waits for an entry point again
     if (!keep_parameter_sets) {
+        s.ra = {0, 0, 0};
         memset(s.sps_ok, 0, sizeof(s.sps_ok));
         memset(s.pps_ok, 0, sizeof(s.pps_ok));
         s.active_sps = -1, s.wmb = s.hmb = 0;
@@ -488,6 +490,17 @@ extern "C" int32_t h264mi_stream_status(h264mi_decoder *d, int32_t stream, int32
 extern "C" int32_t h264mi_decoder_set_isolation(h264mi_decoder *d, int32_t on) {
     if (!d) return H264MI_EINVAL;
     d->isolate = on != 0;
+    return H264MI_OK;
+}
+extern "C" int32_t h264mi_decoder_set_random_access(h264mi_decoder *d, int32_t mode) {
+    if (!d || (mode != H264MI_RA_OFF && mode != H264MI_RA_RECOVERY_POINT)) return H264MI_EINVAL;
+    d->random_access = mode == H264MI_RA_RECOVERY_POINT;
+    return H264MI_OK;
+}
+extern "C" int32_t h264mi_sei_recovery_point(const uint8_t *nal, size_t n, h264mi_recovery_point *out) { return sei_recovery_point(nal, n, out); }
+extern "C" int32_t h264mi_stream_random_access_stats(h264mi_decoder *d, int32_t stream, h264mi_random_access_stats *s) {
+    if (!d || !s || stream < 0 || stream >= static_cast<int>(d->st.size())) return H264MI_EINVAL; // (H264MI_STREAM_DERIVED too)
+    *s = d->st[stream].ra;
     return H264MI_OK;
 }
 extern "C" int32_t h264mi_decoder_memory(h264mi_decoder *d, int64_t *device_bytes) {
@@ -668,6 +681,16 @@ extern "C" int32_t h264mi_frame_fields(h264mi_decoder *d, int32_t stream, int32_
     if (const int r = frame_ptrs(d, stream, frame, &p, &of)) return r;
     if (!out) return H264MI_EINVAL;
     out->field_coded = of->field_coded, out->top_field_order_cnt = of->top_foc, out->bottom_field_order_cnt = of->bottom_foc, out->first_parity = of->first_parity;
+    return H264MI_OK;
+}
+
+extern "C" int32_t h264mi_frame_entry(h264mi_decoder *d, int32_t stream, int32_t frame, h264mi_frame_entry_info *info) {
+    if (!info || stream == H264MI_STREAM_DERIVED) return H264MI_EINVAL;
+    uint8_t *p;
+    const OutFrame *of;
+    if (const int r = frame_ptrs(d, stream, frame, &p, &of)) return r;
+    info->recovery_point = of->rp.found, info->recovery_frame_cnt = of->rp.recovery_frame_cnt, info->exact_match_flag = of->rp.exact_match_flag;
+    info->broken_link_flag = of->rp.broken_link_flag, info->changing_slice_group_idc = of->rp.changing_slice_group_idc, info->entry = of->entry;
     return H264MI_OK;
 }
 

@@ -270,6 +270,11 @@ static int parse_stream(h264mi_decoder *d, int si, const uint8_t *buf, const Sca
             r = add_slice(d, si, sg.off, sg.rlen, nal.ref_idc, nal.type);
             break;
         }
+        case 6: { // SEI: the recovery point message (D.1.7), for the picture that starts next; every other payload, and a unit that does not parse, is passed over
+            h264mi_recovery_point rp;
+            if (sei_recovery_point(p, nal.num_bytes, &rp) == H264MI_OK && rp.found) s.sei = rp;
+            break;
+        }
         case 9:
         case 10:
         case 11:
@@ -295,10 +300,12 @@ static int parse_streams(h264mi_decoder *d, Stage &g, int n_streams, const uint8
         if (!bufs[si] || !lens[si]) continue;
         StreamState &s = d->st[si];
         const Stage::Mark mark = g.mark();
+        const h264mi_random_access_stats ra = s.ra;
         const int r = parse_stream(d, si, bufs[si], sc);
         if (r != H264MI_OK) {
             g.truncate(mark, si);
             reset_stream(s, true);
+            s.ra = ra; // (random access: the entry state of the chunk goes with its pictures, and what was counted in it)
             s.need_idr = true;
             s.status = r;
             if (!d->isolate) return r;

@@ -37,6 +37,10 @@ struct OutFrame { // a decoded picture of the current batch, with the geometry i
     // h264mi_frame_fields: coded as two field pictures (one of them may be missing or concealed); TopFieldOrderCnt / BottomFieldOrderCnt (8.2.1, after a
     // possible operation 5; a missing field's is the other one's); which parity comes first (taken before operation 5 rewrites the counts)
     int field_coded = 0, top_foc = 0, bottom_foc = 0, first_parity = 0;
+    // h264mi_frame_entry: the recovery point SEI message of the picture's access unit (a frame of two fields: the first field's), and whether the
+    // stream entered here after waiting (random access)
+    h264mi_recovery_point rp = {0, 0, 0, 0, 0};
+    int entry = 0;
 };
 struct StreamState {
     h264mi_sps sps[32];
@@ -72,6 +76,15 @@ struct StreamState {
             return wmb == o.wmb && hmb == o.hmb && chroma_format == o.chroma_format && frame_mbs_only == o.frame_mbs_only && log2_max_frame_num_minus4 == o.log2_max_frame_num_minus4;
         }
     } ref_seq;
+    // Random access (h264mi_decoder_set_random_access; the rule: include/h264mi.h).  sei: the recovery point of the SEI NAL unit parsed last (either
+    // mode), which the next picture that starts takes and clears.  decoded_any: a picture has started since create / the resets -- with the mode on a
+    // stream without one, or a marked one (need_idr), waits for an entry point.  lead: pictures with a PicOrderCnt below lead_poc -- that of the non-IDR
+    // entry picture -- are leading pictures and are skipped; skipping / skip_sh: the slices of the leading picture being skipped (its first one).
+    h264mi_recovery_point sei = {0, 0, 0, 0, 0};
+    bool decoded_any = false, lead = false, skipping = false;
+    int lead_poc = 0;
+    h264mi_slice_header skip_sh;
+    h264mi_random_access_stats ra = {0, 0, 0}; // counted in prepare; a chunk that fails takes its counts with it (parse_streams)
 };
 
 // Everything one prepared batch owns: the pinned staging buffers and their device mirrors, the descriptors, the launch
@@ -242,6 +255,7 @@ struct h264mi_decoder {
     int64_t concealed_pics = 0;                      // (h264mi_decoder_concealed_pictures)
     int64_t concealed_fields = 0;                    // (h264mi_decoder_concealed_fields)
     bool isolate = false; // h264mi_decoder_set_isolation: a broken stream does not fail the batch
+    bool random_access = false; // h264mi_decoder_set_random_access: streams start and resume at recovery points too (add_slice)
     // profiling
     bool profiling = false;
     std::vector<hipEvent_t> ev;

@@ -13,7 +13,7 @@ static int frame_num_wrap(int frame_num, int cur, int max_fn) { return frame_num
 
 void Dpb::reset() {
     for (auto &sl : slots) sl = Slot();
-    cur_slot = -1, cur_field = 0, cur_second = false, pend_slot = -1;
+    cur_slot = -1, cur_field = 0, cur_second = false, pend_slot = -1, skipped_slot = -1;
     prev_poc_msb = prev_poc_lsb = prev_frame_num = prev_frame_num_offset = prev_ref_frame_num = 0;
 }
 void Dpb::drop_references() { for (auto &sl : slots) sl.ref = 0; }
@@ -125,7 +125,7 @@ bool Dpb::initial_lists(const h264mi_sps &sps, int frame_num, int field, bool bs
             const int cur_poc = slots[cur_slot].poc;
             std::vector<int> before, after;
             for (int i : st) {
-                if (slots[i].nonexisting && sps.pic_order_count_type == 0) continue; // 8.2.4.2.3: no PicOrderCnt, not in the lists of B slices
+                if (slots[i].nonexisting && !slots[i].poc_known && sps.pic_order_count_type == 0) continue; // 8.2.4.2.3: no PicOrderCnt, not in the lists of B slices
                 (slots[i].poc < cur_poc ? before : after).push_back(i);
             }
             std::sort(before.begin(), before.end(), [&](int a, int b) { return slots[a].poc > slots[b].poc; });
@@ -146,7 +146,7 @@ bool Dpb::initial_lists(const h264mi_sps &sps, int frame_num, int field, bool bs
             const int cur_poc = slots[cur_slot].fpoc[bottom];
             std::vector<std::pair<int, int>> before, after; // (PicOrderCnt, slot)
             for (int i : st) {
-                if (slots[i].nonexisting) continue;
+                if (slots[i].nonexisting && !slots[i].poc_known) continue;
                 const int fp = i == cur_slot ? slots[i].fpoc[!bottom] : slots[i].poc;
                 (fp <= cur_poc ? before : after).push_back({fp, i});
             }
@@ -384,6 +384,59 @@ bool Dpb::add_nonexisting_frame(const h264mi_sps &sps, int fn) {
         sl.poc = compute_poc(sps, f);
     }
     prev_ref_frame_num = fn;
+    return true;
+}
+
+bool Dpb::start_at_entry(const h264mi_sps &sps, int frame_num) {
+    drop_references();
+    prev_poc_msb = prev_poc_lsb = prev_frame_num = prev_frame_num_offset = 0;
+    prev_ref_frame_num = frame_num;
+    skipped_slot = -1;
+    // What the sliding window held when the encoder coded this picture is known without having seen it: the max_num_ref_frames - 1 reference frames
+    // with the frame_num values before this one's.  They enter as non-existing frames, oldest first, with counts below any the stream can reach and
+    // rising with frame_num: behind every real picture in P lists (FrameNumWrap) and in the earlier half of B lists (PicOrderCnt), and IN FRONT of the
+    // later half of list 0 -- where the encoder's list has the pictures they stand for.  They leave through the sliding window as those did.
+    const int max_fn = max_frame_num(sps), n = std::min(std::max(sps.max_num_ref_frames, 1) - 1, max_fn - 1);
+    for (int k = n; k >= 1; k--) {
+        const int slot = first_free_slot();
+        if (slot < 0) return false;
+        Slot &sl = slots[slot];
+        sl = Slot();
+        sl.ref = 1, sl.nonexisting = true, sl.poc_known = true, sl.frame_num = (frame_num - k + max_fn) % max_fn, sl.fields = 3;
+        sl.poc = sl.fpoc[0] = sl.fpoc[1] = -(1 << 24) - 2 * k;
+    }
+    return true;
+}
+
+int Dpb::peek_poc(const h264mi_sps &sps, const h264mi_slice_header &sh) const {
+    Dpb history; // (no slots: compute_poc reads and writes the history only)
+    history.prev_poc_msb = prev_poc_msb, history.prev_poc_lsb = prev_poc_lsb, history.prev_frame_num = prev_frame_num, history.prev_frame_num_offset = prev_frame_num_offset;
+    return history.compute_poc(sps, sh);
+}
+
+bool Dpb::skip_picture(const h264mi_sps &sps, const h264mi_slice_header &sh) {
+    const int poc = compute_poc(sps, sh);
+    if (!sh.nal_ref_idc) return true;
+    if (sh.field_pic && skipped_slot >= 0) { // the second field of the frame skipped last?
+        Slot &f = slots[skipped_slot];
+        if (f.ref == 1 && f.nonexisting && f.poc_known && f.frame_num == sh.frame_num && f.fields == (sh.bottom_field ? 1 : 2)) {
+            f.fpoc[sh.bottom_field ? 1 : 0] = poc, f.poc = std::min(f.fpoc[0], f.fpoc[1]), f.fields = 3;
+            skipped_slot = -1;
+            return true;
+        }
+    }
+    sliding_window(sps, sh.frame_num);
+    const int slot = first_free_slot();
+    if (slot < 0) return false;
+    Slot &sl = slots[slot];
+    sl = Slot();
+    sl.ref = 1, sl.nonexisting = true, sl.poc_known = true, sl.frame_num = sh.frame_num, sl.poc = poc;
+    sl.field_coded = sh.field_pic != 0;
+    if (sh.field_pic)
+        sl.fields = sh.bottom_field ? 2 : 1, sl.fpoc[0] = sl.fpoc[1] = poc, skipped_slot = slot;
+    else
+        sl.fields = 3, sl.fpoc[0] = poc_top, sl.fpoc[1] = poc_bot, skipped_slot = -1;
+    prev_ref_frame_num = sh.frame_num;
     return true;
 }
 

@@ -17,6 +17,7 @@ struct Slot {
     // batch still holds the samples earlier pictures of the batch predict from.)
     bool held = false;
     bool nonexisting = false; // a frame inferred by the gaps-in-frame_num process (8.2.5.2): a place in the window, no picture
+    bool poc_known = false;   // ... a non-existing frame that stands for a leading reference picture (random access): no samples, but its PicOrderCnt -- it keeps its place in the lists of B slices
     int pic = -1; // index into the PicDesc table of the batch being prepared, -1: decoded by an earlier batch (field-coded frames: fpic[])
     // Fields (h264/slice.go:867-872 field_pic_flag / bottom_field_flag; h264/sps.go:316-322).  A frame slot holds both fields of a frame, however
     // they were coded: a frame picture fills both at once (fields = 3), a field picture the rows of its parity.
@@ -42,6 +43,7 @@ struct Dpb {
     // A frame whose first field has been decoded waits here for its second field (the next picture, if it is a field of the other parity
     // with the same frame_num, 7.4.1.2.4 / 3.30).  The wait may span a batch boundary.
     int pend_slot = -1;
+    int skipped_slot = -1; // skip_picture: the frame of the reference field skipped last, which its second field joins
 
     void reset();           // forget all slots and the POC / frame_num history
     void drop_references(); // after a failed slice: nothing is a reference picture any more
@@ -52,6 +54,17 @@ struct Dpb {
     int missing_frames(const h264mi_sps &sps, const h264mi_slice_header &sh) const;
     // 8.2.5.2: one "non-existing" short-term frame with frame_num `fn`, through the sliding window like a decoded one; false: no free slot
     bool add_nonexisting_frame(const h264mi_sps &sps, int fn);
+    // Random access: the stream starts at the non-IDR picture with this frame_num as if nothing had come before -- no reference picture with samples,
+    // the history of 8.2.1 zero, PrevRefFrameNum such that the picture is no frame_num gap -- except that the window is filled with non-existing frames
+    // for the frame_num values a sliding window held in front of it, so that later lists carry the pictures to come at the indices the encoder meant.
+    // (The slots stay held as they are: their samples may still be read.)  false: no free slot
+    bool start_at_entry(const h264mi_sps &sps, int frame_num);
+    // PicOrderCnt (8.2.1) the picture `sh` starts would get, without touching the history
+    int peek_poc(const h264mi_sps &sps, const h264mi_slice_header &sh) const;
+    // Random access: a leading picture `sh` starts, which is not decoded.  The counts of 8.2.1 advance as for any picture; a reference picture enters
+    // the window as a non-existing frame with its frame_num and its PicOrderCnt (the second field of such a frame joins it) and the sliding window
+    // runs.  false: no free slot
+    bool skip_picture(const h264mi_sps &sps, const h264mi_slice_header &sh);
     // The picture `sh` starts lives in `slot` (second: it is the second field of the frame waiting there) and is PicDesc `pic` of the batch: the
     // slot is set up and gets the picture's PicOrderCnt (8.2.1).  The picture is under construction until finish_picture.
     void begin_picture(const h264mi_sps &sps, const h264mi_slice_header &sh, int slot, bool second, int pic);

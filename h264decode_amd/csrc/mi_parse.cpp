@@ -127,6 +127,40 @@ size_t unescape(const uint8_t *src, size_t n, uint8_t *dst) {
     return o;
 }
 
+// 7.3.2.3 / D.1.7: the sei_message()s of one SEI NAL unit (from its header byte on, emulation prevention still in), looking for the first recovery
+// point (payloadType 6); every other payload is passed over by its size
+int sei_recovery_point(const uint8_t *nal, size_t len, h264mi_recovery_point *out) {
+    if (!nal || !out || len < 1 || (nal[0] & 31) != 6) return H264MI_EINVAL;
+    memset(out, 0, sizeof(*out));
+    std::vector<uint8_t> rbsp(len);
+    size_t n = unescape(nal + 1, len - 1, rbsp.data()), i = 0;
+    while (n > 0 && rbsp[n - 1] == 0) n--; // (cabac_zero_words / trailing zeros)
+    // more_rbsp_data(): messages are byte aligned, so what is left is either another message or the byte of rbsp_trailing_bits
+    while (i < n && !(i == n - 1 && rbsp[i] == 0x80)) {
+        size_t val[2] = {0, 0}; // payloadType, payloadSize: ff_byte adds 255 each
+        for (size_t &v : val) {
+            while (i < n && rbsp[i] == 0xFF) v += 255, i++;
+            if (i >= n) return H264MI_EBITSTREAM;
+            v += rbsp[i++];
+        }
+        if (val[1] > n - i) return H264MI_EBITSTREAM;
+        if (val[0] == 6) {
+            BitReader br(rbsp.data() + i, val[1]);
+            out->recovery_frame_cnt = static_cast<int32_t>(br.ue());
+            out->exact_match_flag = static_cast<int32_t>(br.u(1)), out->broken_link_flag = static_cast<int32_t>(br.u(1));
+            out->changing_slice_group_idc = static_cast<int32_t>(br.u(2));
+            if (br.overrun()) {
+                memset(out, 0, sizeof(*out));
+                return H264MI_EBITSTREAM;
+            }
+            out->found = 1;
+            return H264MI_OK;
+        }
+        i += val[1];
+    }
+    return H264MI_OK;
+}
+
 // NewNalUnit (h264/nalUnit.go:75-131): header fields + RBSP
 int nal_parse(const uint8_t *nal, size_t len, h264mi_nal *h, uint8_t *rbsp, size_t *rbsp_len) {
     if (!nal || len < 1 || !h) return H264MI_EINVAL;

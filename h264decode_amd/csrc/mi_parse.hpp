@@ -32,6 +32,7 @@ int annexb_scan(const uint8_t *buf, size_t len, h264mi_nal *out, int cap, int *n
 int nal_parse(const uint8_t *nal, size_t len, h264mi_nal *hdr, uint8_t *rbsp, size_t *rbsp_len);
 // RBSP extraction only (header byte(s) skipped by the caller via `skip`)
 size_t unescape(const uint8_t *src, size_t n, uint8_t *dst);
+int sei_recovery_point(const uint8_t *nal, size_t len, h264mi_recovery_point *out); // the one SEI payload the product reads (D.1.7)
 int parse_sps(const uint8_t *rbsp, size_t len, h264mi_sps *s);
 // CropUnitX / CropUnitY (7.4.2.1.1) in luma samples: 1 x (2 - frame_mbs_only_flag) for ChromaArrayType 0, else SubWidthC x SubHeightC * (2 - frame_mbs_only_flag)
 // (4:2:0 values; 4:2:2 / 4:4:4 streams parse but are refused before anything is cropped)

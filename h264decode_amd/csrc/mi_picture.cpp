@@ -399,11 +399,19 @@ int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref_idc, i
         return H264MI_ECAPACITY;
     }
     uint8_t *rbsp = g.h_bits + off;
+    // random access: the stream waits for an entry point -- no slice in front of it is an error, whatever it lacks (skip_waiting)
+    const bool waiting = d->random_access && (s.need_idr || !s.decoded_any);
+    auto skip_waiting = [&s] {
+        s.ra.skipped_waiting_nals++;
+        s.sei = {0, 0, 0, 0, 0}; // (the message belonged to this picture)
+        return H264MI_OK;
+    };
     // peek pps id: first_mb_in_slice, slice_type, pic_parameter_set_id
     BitReader br(rbsp, rlen);
     br.ue();
     br.ue();
     uint32_t pps_id = br.ue();
+    if (waiting && (pps_id > 255 || !s.pps_ok[pps_id] || !s.sps_ok[s.pps[pps_id].sps_id])) return skip_waiting();
     if (pps_id > 255 || !s.pps_ok[pps_id]) {
         set_error("stream %d: slice refers to missing PPS %u", si, pps_id);
         return H264MI_EBITSTREAM;
@@ -416,6 +424,7 @@ int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref_idc, i
     const h264mi_sps &sps = s.sps[pps.sps_id];
     h264mi_slice_header sh;
     int r = parse_slice_header(&sps, &pps, ref_idc, type, rbsp, rlen, &sh);
+    if (r != H264MI_OK && waiting) return skip_waiting();
     if (r != H264MI_OK) {
         // error concealment: a damaged slice header is a lost slice -- its macroblocks stay undelivered and k_conceal fills them in -- but only in a
         // picture that is concealable; anywhere else it fails the stream as without the mode.  Which picture a slice without a header belongs to is not
@@ -435,8 +444,25 @@ int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref_idc, i
         return r;
     }
     if (sh.redundant_pic_cnt > 0) return H264MI_OK; // redundant pictures are dropped
-    if (s.need_idr) { // after an error nothing can be trusted before the next IDR picture
-        if (type != 5) return H264MI_OK;
+    bool entry = false; // random access: the stream enters at the picture this slice starts
+    if (waiting) {
+        // an entry point: an IDR picture, or a primary coded picture whose access unit carried a recovery point with recovery_frame_cnt 0
+        if (type != 5 && !(s.sei.found && s.sei.recovery_frame_cnt == 0)) return skip_waiting();
+        entry = true;
+        s.need_idr = false;
+        if (type != 5) { // empty picture management, and what precedes the picture in output order is not coming: leading pictures
+            if (!s.dpb.start_at_entry(sps, sh.frame_num)) {
+                set_error("stream %d: frame pool exhausted", si);
+                return H264MI_ECAPACITY;
+            }
+            s.lead = true, s.skipping = false;
+            s.ra.entries++;
+        }
+    } else if (s.need_idr) { // after an error nothing can be trusted before the next IDR picture
+        if (type != 5) {
+            s.sei = {0, 0, 0, 0, 0};
+            return H264MI_OK;
+        }
         s.need_idr = false;
     }
     const int st = sh.slice_type % 5;
@@ -490,6 +516,29 @@ int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref_idc, i
     // started begins a new picture whatever the headers say.  Not "first_mb_in_slice == 0": with slice groups or arbitrary slice
     // order that slice may come late.)
     const bool restarts = std::find(s.cur_first_mbs.begin(), s.cur_first_mbs.end(), sh.first_mb_in_slice) != s.cur_first_mbs.end();
+    if (type == 5) s.lead = s.skipping = false; // the counts start over: nothing after this precedes the entry picture
+    if (s.lead && !entry) {
+        // random access, leading pictures: a picture behind the non-IDR entry picture in decoding order and in front of it in output order predicts
+        // from pictures the stream never had -- it is neither decoded nor output (Dpb::skip_picture)
+        if (s.skipping && !new_picture(sps, s.skip_sh, sh) && sh.first_mb_in_slice != s.skip_sh.first_mb_in_slice) return H264MI_OK; // one more slice of it
+        s.skipping = false;
+        if (s.dpb.cur_slot < 0 || restarts || new_picture(sps, s.dpb.first_sh, sh)) { // the first slice of a picture
+            if (s.dpb.cur_slot >= 0) finish_picture(d, si); // (its marking may move the counts: operation 5)
+            if (s.lead && s.dpb.peek_poc(sps, sh) < s.lead_poc) {
+                r = flush_pending_field(d, si, &sps, &pps, &sh); // (a lone first field: its second field would not have been a leading picture)
+                if (r == H264MI_OK) r = fill_frame_num_gap(d, si, sps, sh);
+                if (r != H264MI_OK) return r;
+                if (!s.dpb.skip_picture(sps, sh)) {
+                    set_error("stream %d: frame pool exhausted", si);
+                    return H264MI_ECAPACITY;
+                }
+                s.skipping = true, s.skip_sh = sh;
+                s.ra.skipped_leading_pictures++;
+                s.sei = {0, 0, 0, 0, 0};
+                return H264MI_OK;
+            }
+        }
+    }
     if (s.dpb.cur_slot >= 0 && (restarts || new_picture(sps, s.dpb.first_sh, sh))) finish_picture(d, si);
     if (s.active_sps != pps.sps_id || s.wmb != wmb || s.hmb != hmb) { // (re)activate: new sequence geometry
         if (sh.nal_unit_type != 5 && s.active_sps >= 0 && (s.wmb != wmb || s.hmb != hmb)) {
@@ -506,7 +555,7 @@ int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref_idc, i
         bool second = false;
         if (s.dpb.pend_slot >= 0) {
             const Slot &f = s.dpb.slots[s.dpb.pend_slot];
-            if (sh.field_pic && type != 5 && f.fields == (sh.bottom_field ? 1 : 2) && f.frame_num == sh.frame_num && (f.ref != 0) == (ref_idc != 0))
+            if (sh.field_pic && type != 5 && !entry && f.fields == (sh.bottom_field ? 1 : 2) && f.frame_num == sh.frame_num && (f.ref != 0) == (ref_idc != 0))
                 second = true;
             else if ((r = flush_pending_field(d, si, &sps, &pps, &sh)) != H264MI_OK)
                 return r;
@@ -518,6 +567,18 @@ int add_slice(h264mi_decoder *d, int si, size_t off, size_t rlen, int ref_idc, i
         }
         r = start_picture(d, si, sps, pps, pps_id, sh, type, second);
         if (r != H264MI_OK) return r;
+        // random access: what the access unit said about it goes with the frame (h264mi_frame_entry: a second field adds nothing); a non-IDR entry
+        // picture starts a sequence of its own, and what has a smaller count than it from now on is a leading picture
+        if (OutFrame *of = second ? nullptr : (sh.field_pic ? &s.pend_out : &g.out[si].back())) {
+            of->rp = s.sei, of->entry = entry;
+            if (entry && type != 5) of->new_sequence = 1;
+        }
+        s.sei = {0, 0, 0, 0, 0};
+        s.decoded_any = true;
+        if (entry && type != 5) s.lead_poc = sh.field_pic ? s.dpb.slots[s.dpb.cur_slot].fpoc[sh.bottom_field ? 1 : 0] : s.dpb.slots[s.dpb.cur_slot].poc;
+        if (s.lead && ref_idc && sh.adaptive_ref_pic_marking_mode_flag)
+            for (int k = 0; k < sh.n_memory_management_control_operations; k++)
+                if (sh.memory_management_control_operation[k] == 5) s.lead = false; // the counts start over
     }
     if (s.cur_slices >= d->cfg.max_slices_per_frame) {
         set_error("stream %d: more than %d slices in a frame", si, d->cfg.max_slices_per_frame);

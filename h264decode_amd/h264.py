@@ -201,6 +201,7 @@ CONCEAL_SLICES, CONCEAL_PICTURES, CONCEAL_FIELDS = 1, 2, 4  # bits of h264mi_con
 CONCEAL_IDR = 16                         # H264MI_CONCEAL_IDR (bit 8 is unassigned)
 CONCEAL_LONE_FIELDS = 64                 # H264MI_CONCEAL_LONE_FIELDS (only together with CONCEAL_SLICES | CONCEAL_FIELDS; bit 32 is unassigned)
 CONCEAL_MAX_GAP = 16                     # H264MI_CONCEAL_MAX_GAP: the longest run of lost frames that is concealed
+RA_OFF, RA_RECOVERY_POINT = 0, 1         # H264MI_RA_*: Decoder.set_random_access
 FMT_I420, FMT_NV12, FMT_RGB24, FMT_RGBP = 0, 1, 2, 3  # H264MI_FMT_*: output formats of convert_frame / convert_batch / frames_tensor
 CSC_AUTO, CSC_BT601, CSC_BT709 = 0, 1, 2              # H264MI_CSC_*: the matrix (AUTO: from each frame's own SPS) ...
 CSC_FULL_RANGE, CSC_CHROMA_BILINEAR = 16, 32          # ... | full range (explicit matrix only) | bilinear chroma upsampling (default: nearest)
@@ -403,6 +404,27 @@ class Decoder:
     def set_isolation(self, on=True):
         """With isolation a broken stream is dropped from the batch and marked instead of failing prepare() / sync()."""
         check(self._L.h264mi_decoder_set_isolation(self._h, int(on)))
+
+    def set_random_access(self, mode=True):
+        """True / RA_RECOVERY_POINT: a stream that has decoded nothing yet, or that an error took out, starts at its next IDR picture OR at its next
+        non-IDR picture with a recovery point SEI message of recovery_frame_cnt 0; the slices in front of it are skipped without an error, the
+        pictures that precede the entry picture in output order (leading pictures) are dropped.  False (default): IDR pictures only.  From the
+        next prepare() on."""
+        check(self._L.h264mi_decoder_set_random_access(self._h, int(mode)))
+
+    def frame_entry(self, stream, frame):
+        """h264mi_frame_entry_info of a decoded frame: the recovery point SEI message of its access unit (recovery_point, recovery_frame_cnt,
+        exact_match_flag, broken_link_flag, changing_slice_group_idc; either mode) and `entry`: the stream entered here after waiting."""
+        fe = _lib.FrameEntryInfo()
+        check(self._L.h264mi_frame_entry(self._h, stream, frame, ctypes.byref(fe)))
+        return fe
+
+    def random_access_stats(self, stream=0):
+        """(entries, skipped_waiting_nals, skipped_leading_pictures) of a stream since it was created / reset_stream(): non-IDR entry points taken,
+        slice NAL units skipped while it waited for one, leading pictures dropped."""
+        s = _lib.RandomAccessStats()
+        check(self._L.h264mi_stream_random_access_stats(self._h, stream, ctypes.byref(s)))
+        return s.entries, s.skipped_waiting_nals, s.skipped_leading_pictures
 
     def stream_status(self, stream):
         st = ctypes.c_int32(0)
@@ -1117,12 +1139,14 @@ class H264Reader:
     display_order=N -- in display order through a DisplayOrder buffer of depth N (streams with B pictures)."""
 
     def __init__(self, connection, decoder=None, on_frames=None, max_width=1920, max_height=1088, frames_per_batch=30, read_size=1 << 16, display_order=0,
-                 conceal_errors=False):
+                 conceal_errors=False, random_access=False):
         self.Stream = connection
         self.frames_per_batch = frames_per_batch
         self.decoder = decoder or Decoder(max_streams=1, max_width=(max_width + 15) // 16 * 16, max_height=(max_height + 15) // 16 * 16,
                                           max_frames_per_batch=_frames_with_headroom(frames_per_batch, conceal_errors), max_slices_per_frame=16,
                                           conceal_errors=conceal_errors)
+        if random_access:  # a connection that starts in the middle of a stream: decode from its first recovery point on (Decoder.set_random_access)
+            self.decoder.set_random_access(random_access)
         self.on_frames = on_frames
         self.read_size = read_size
         self.splitter = AccessUnitSplitter(frames_per_batch)
@@ -1191,10 +1215,13 @@ class BatchServer:
     batch scheduler the reference's per-connection goroutine (main.go:12-21) lacks.  `on_frames(slot, frames)` receives
     the cropped I420 frames of a connection in decoding order; `on_close(slot, n_frames)` when its peer is done."""
 
-    def __init__(self, max_connections=8, max_width=1920, max_height=1088, frames_per_batch=30, on_frames=None, on_close=None, read_size=1 << 16, conceal_errors=False):
+    def __init__(self, max_connections=8, max_width=1920, max_height=1088, frames_per_batch=30, on_frames=None, on_close=None, read_size=1 << 16, conceal_errors=False,
+                 random_access=False):
         self.decoder = Decoder(max_streams=max_connections, max_width=(max_width + 15) // 16 * 16, max_height=(max_height + 15) // 16 * 16,
                                max_frames_per_batch=_frames_with_headroom(frames_per_batch, conceal_errors), max_slices_per_frame=16, conceal_errors=conceal_errors)
         self.decoder.set_isolation(True)  # one bad client must not take the other connections' chunks down with it
+        if random_access:  # clients may connect in the middle of a stream, and a stream that lost a picture comes back at its next recovery point
+            self.decoder.set_random_access(random_access)
         self.errors = [0] * max_connections
         self.n = max_connections
         self.frames_per_batch = frames_per_batch

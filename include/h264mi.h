@@ -324,7 +324,7 @@ int32_t h264mi_stream_reset(h264mi_decoder *dec, int32_t stream);
 /* Error isolation for batches of unrelated streams (one connection each).  Off (default): the first stream error fails
  * h264mi_batch_prepare / h264mi_batch_sync.  On: a stream whose chunk cannot be parsed, or whose slices fail in the
  * entropy kernel, is dropped from the batch and marked; the calls return H264MI_OK and the other streams decode
- * normally.  A marked stream resumes at its next IDR picture.  (With h264mi_config.conceal_errors a failed slice of a concealable picture
+ * normally.  A marked stream resumes at its next IDR picture (with H264MI_RA_RECOVERY_POINT: at its next entry point, see "Random access").  (With h264mi_config.conceal_errors a failed slice of a concealable picture
  * marks nothing: only what cannot be concealed takes a stream out.) */
 int32_t h264mi_decoder_set_isolation(h264mi_decoder *dec, int32_t on);
 /* Status of a stream in the current batch: H264MI_OK or the H264MI_E* that took it out (valid after prepare; entropy
@@ -862,6 +862,73 @@ int32_t h264mi_decoder_concealed_pictures(h264mi_decoder *dec, int64_t *pictures
 /* Fields inserted for wholly lost fields (H264MI_CONCEAL_LONE_FIELDS) since the decoder was created, counted the same way (h264mi_decoder_concealed_pictures
  * does not count them).  Their macroblocks are part of h264mi_frame_concealed of their frame and of the macroblock total of h264mi_decoder_concealed. */
 int32_t h264mi_decoder_concealed_fields(h264mi_decoder *dec, int64_t *fields);
+
+/* ---- Random access: start and resume decoding at recovery points ----
+ * Off (H264MI_RA_OFF, the default): a stream begins at an IDR picture, and a marked stream (h264mi_decoder_set_isolation) resumes at one; nothing else
+ * about the decoder changes.  With H264MI_RA_RECOVERY_POINT (any other mode: H264MI_EINVAL; the mode takes effect with the next prepare):
+ * - Waiting.  A stream WAITS FOR AN ENTRY POINT while it has decoded no picture since the decoder was created or since h264mi_stream_reset /
+ *   h264mi_decoder_reset, and while it is marked.
+ * - Entry point.  An IDR picture, or a primary coded picture whose access unit carried a recovery point SEI message (D.1.7 / D.2.7) with
+ *   recovery_frame_cnt = 0.  The values of the message are kept in the stream's state when the SEI NAL unit is parsed; the next picture that starts takes
+ *   them and clears them.  A recovery point with recovery_frame_cnt > 0 (gradual refresh) is recorded and reported (h264mi_frame_entry) but is no entry point.
+ * - Slices while waiting.  No slice NAL unit in front of the entry point is an error: a slice whose PPS or SPS is missing, or whose header does not
+ *   parse, and every slice of a picture that is no entry point is skipped and counted (skipped_waiting_nals), and the stream's status stays H264MI_OK.
+ *   SPS and PPS NAL units are handled as always.
+ * - State at entry.  At a non-IDR entry picture E the stream starts from empty picture management: no reference picture that holds samples;
+ *   prevPicOrderCntMsb, prevPicOrderCntLsb, prevFrameNumOffset and prevFrameNum 0; PrevRefFrameNum such that E is no frame_num gap.  E is reported
+ *   with new_sequence = 1 (h264mi_stream_output_order starts over there).  PicOrderCnt values from E on differ from those of a decoder that saw the
+ *   whole stream by one constant per entry.  The window is not left empty, though: it is filled with non-existing frames for the
+ *   max_num_ref_frames - 1 frame_num values in front of E's -- what a sliding window held there --, with picture order counts below any the stream
+ *   reaches.  They hold no samples and leave through the sliding window; they are there because RefPicList0 of a B picture lists the earlier
+ *   pictures in front of the later ones, so that with an empty window every later picture would stand at a smaller index than the encoder meant
+ *   for as long as a picture from before E is in the encoder's window.  (A stream whose window was not full in front of E, or was managed by marking
+ *   scripts there, is not reproduced by this.)
+ * - Leading pictures.  After a non-IDR entry E a picture that follows E in decoding order and whose PicOrderCnt is smaller than E's (a field: its own
+ *   count, against that of E's first field or frame) is a leading picture, until the counts start over at an IDR picture or at memory management
+ *   operation 5.  It is neither decoded nor output.  A non-reference leading picture leaves no reference picture; a REFERENCE leading picture (B
+ *   pyramids) goes through picture management as a picture without samples: the counts of 8.2.1 advance, it enters the window as a non-existing
+ *   frame with its frame_num and its PicOrderCnt (two fields as one frame) and the sliding window runs (its own marking script, if it has one, is not
+ *   run), so that later lists carry the surviving pictures at the indices the encoder meant.  A slice that predicts from such a frame is not detected.
+ * - Short lists.  Reference lists shorter than num_ref_idx_active are padded with "no reference picture" as always; a slice that names such an
+ *   entry fails in the entropy kernel, the stream is marked, and under this mode it waits for the next ENTRY POINT, not for the next IDR picture.
+ * - A stream whose chunk fails in prepare loses the entry state and the counts of that chunk together with its pictures.
+ * Out of scope: entering at recovery_frame_cnt > 0, decoding leading pictures approximately, I pictures without the SEI message as entry points,
+ * acting on broken_link_flag while a stream is decoded continuously, every other SEI payload. */
+#define H264MI_RA_OFF 0
+#define H264MI_RA_RECOVERY_POINT 1
+int32_t h264mi_decoder_set_random_access(h264mi_decoder *dec, int32_t mode);
+typedef struct {
+    int32_t found;
+    int32_t recovery_frame_cnt;
+    int32_t exact_match_flag;
+    int32_t broken_link_flag;
+    int32_t changing_slice_group_idc;
+} h264mi_recovery_point;
+/* The recovery point SEI message of one SEI NAL unit (pure: no decoder).  nal: the unit from its NAL header byte on, emulation prevention bytes still
+ * in.  Every sei_message() of the unit is walked (0xFF extension bytes of payload type and size included), other payloads are skipped; the first
+ * payload of type 6 is reported, found = 0 if there is none.  H264MI_EBITSTREAM: the unit ends inside a message; H264MI_EINVAL: not a unit of type 6.
+ * The only SEI parsing this library does. */
+int32_t h264mi_sei_recovery_point(const uint8_t *nal, size_t n, h264mi_recovery_point *out);
+/* What the access unit of a frame of the last batch said about random access (valid after prepare; the pseudo-stream H264MI_STREAM_DERIVED is refused).
+ * recovery_point and the four values of the message: reported in either mode (a frame of two fields: the first field's).  entry: 1 only on the first
+ * picture decoded after the stream waited, IDR picture or not, and only with H264MI_RA_RECOVERY_POINT. */
+typedef struct {
+    int32_t recovery_point;
+    int32_t recovery_frame_cnt;
+    int32_t exact_match_flag;
+    int32_t broken_link_flag;
+    int32_t changing_slice_group_idc;
+    int32_t entry;
+} h264mi_frame_entry_info;
+int32_t h264mi_frame_entry(h264mi_decoder *dec, int32_t stream, int32_t frame, h264mi_frame_entry_info *info);
+/* Counted in prepare, per stream, since the decoder was created or h264mi_stream_reset: non-IDR entry points taken; slice NAL units skipped while the
+ * stream waited; leading pictures skipped (a field counts as a picture). */
+typedef struct {
+    int64_t entries;
+    int64_t skipped_waiting_nals;
+    int64_t skipped_leading_pictures;
+} h264mi_random_access_stats;
+int32_t h264mi_stream_random_access_stats(h264mi_decoder *dec, int32_t stream, h264mi_random_access_stats *s);
 
 const char *h264mi_last_error_string(void);
 const char *h264mi_version(void);

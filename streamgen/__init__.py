@@ -24,7 +24,7 @@ class Params(ctypes.Structure):
         ("b_pyramid", ctypes.c_int), ("slice_groups", ctypes.c_int), ("fmo_type", ctypes.c_int), ("aso", ctypes.c_int), ("field_pics", ctypes.c_int), ("poc_bottom_delta", ctypes.c_int), ("mono", ctypes.c_int),
         ("wp_range", ctypes.c_int), ("poc_step", ctypes.c_int), ("mv_reach", ctypes.c_int), ("mv_margin", ctypes.c_int), ("contrast", ctypes.c_int),
         ("dbf_per_slice", ctypes.c_int), ("trace_deblock", ctypes.c_int), ("syntax_stim", ctypes.c_int),
-        ("intra_stim", ctypes.c_int), ("trace_intra", ctypes.c_int)]
+        ("intra_stim", ctypes.c_int), ("trace_intra", ctypes.c_int), ("open_gop_period", ctypes.c_int)]
 
 
 def build(force=False):
@@ -50,6 +50,7 @@ def lib():
         _lib.sg_source_frame.argtypes = [ctypes.POINTER(Params), ctypes.c_int, ctypes.c_void_p]
         _lib.sg_last_pocs.argtypes = [ctypes.c_void_p, ctypes.c_int]
         _lib.sg_last_features.restype = ctypes.c_uint32
+        _lib.sg_last_entries.argtypes = [ctypes.c_void_p, ctypes.c_int]
         _lib.sg_last_ranges.argtypes = [ctypes.c_void_p, ctypes.c_int]
         _lib.sg_last_syntax.argtypes = [ctypes.c_void_p, ctypes.c_int]
         _lib.sg_cavlc_level_bits.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
@@ -95,6 +96,18 @@ def last_pocs():
 def last_features():
     """Bit set of the picture-management syntax the last encode() call emitted (see sg.h)."""
     return int(lib().sg_last_features())
+
+
+FEATURE_OPEN_GOP = 1 << 16
+
+
+def last_entries():
+    """The entry points of the last encode(open_gop_period=N, ...): per non-IDR I picture with a recovery point (frame of the reconstruction, i.e. its
+    place in coding order; leading pictures that follow it, a field counting as one)."""
+    n = lib().sg_last_entries(None, 0)
+    out = np.zeros(2 * n, dtype=np.int32)
+    lib().sg_last_entries(out.ctypes.data, 2 * n)
+    return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(n)]
 
 
 RANGE_NAMES = (

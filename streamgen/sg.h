@@ -145,6 +145,17 @@ typedef struct {
     /* 1: sg_last_intra_trace() keeps, for every picture of this call, the prediction and residual sample of every intra-predicted sample and the sg_ipmb
      * table (and what trace_deblock keeps); changes nothing else */
     int trace_intra;
+    /* open groups of pictures: 0 = the streams of before, byte for byte, and not one more draw of the generator.  N > 0 (rounded up to a multiple of
+     * bframes + 1, like idr_period): the anchor at every display index that is a positive multiple of N, and no IDR picture, is coded as a non-IDR I
+     * picture (field_pics: two I fields).  In front of it, in its access unit, stand the SPS and the PPS again, byte for byte, and an SEI NAL unit with a
+     * recovery point message (D.1.7): recovery_frame_cnt 0, exact_match_flag 1, broken_link_flag 0.  The B pictures between the anchor before and this
+     * one are coded after it as for any anchor and predict across it: a decoder that starts at the anchor cannot decode them (leading pictures).
+     * The reference barrier: a picture behind such an anchor in display order predicts from no picture in front of the anchor in display order, and from
+     * no list entry that has a picture coded before the anchor and shown before it in front of it in the list (a decoder that started at the anchor
+     * with an empty window finds the entries behind such a picture at other indices).  That restricts the choice of reference indices only -- a P macroblock is not skipped
+     * where entry 0 is barred --; list sizes and orders are what the whole DPB gives.  Refused together with rplm, mmco, idr_long_term, fn_gap_period,
+     * wp_range 2 (list modification) and direct_temporal (the index comes from the co-located block). */
+    int open_gop_period;
 } sg_params;
 
 void sg_default_params(sg_params *p);
@@ -160,8 +171,12 @@ const char *sg_last_error(void);
 int sg_last_pocs(int32_t *dst, int cap);
 /* what the last sg_encode() call actually emitted: bit k = memory_management_control_operation k (1..6), bit 8/9/10 =
  * modification_of_pic_nums_idc 0/1/2, bit 11 = a long-term picture in an active reference list, bit 12 = non-reference
- * picture, bit 13 = slice_qp_delta != 0, bit 14 = pic_order_cnt_type 1 with delta_pic_order_cnt[0] != 0 */
+ * picture, bit 13 = slice_qp_delta != 0, bit 14 = pic_order_cnt_type 1 with delta_pic_order_cnt[0] != 0, bit 15 = a frame_num gap,
+ * bit 16 = a non-IDR I picture with a recovery point SEI message (open_gop_period) */
 uint32_t sg_last_features(void);
+/* open_gop_period: the entry points of the last sg_encode() call, two numbers each -- the frame of recon[] (coding order) the non-IDR I picture is, and
+ * the leading PICTURES that follow it (a field counts as one).  Returns the number of entry points; dst receives up to cap numbers. */
+int sg_last_entries(int32_t *dst, int cap);
 /* what the last sg_encode() call really reached, counted where the generator builds the prediction that goes into its
  * reconstruction (never in the motion search).  Returns the number of counters; dst receives up to cap of them. */
 enum {

@@ -85,7 +85,16 @@ typedef struct {
     uint8_t *ip_pred;
     int16_t *ip_res;
     sg_ipmb *ipmb;
+    /* sg_params::open_gop_period, the reference barrier of the current picture: bit i of allow[l] = entry i of list l may be predicted from */
+    uint32_t allow[2];
 } enc;
+/* the entry of list l to predict from when `r` was drawn: `r` itself unless the barrier bars it, then the first entry that it lets through */
+static int barrier_ref(const enc *e, int l, int r) {
+    if (e->allow[l] >> r & 1) return r;
+    for (int i = 0; i < 4; i++)
+        if (e->allow[l] >> i & 1) return i;
+    return r;
+}
 
 static char g_err[256];
 /* sg_last_ranges(): per thread (callers generate streams in parallel threads: counters shared between them would be wrong, and a cache line
@@ -1528,7 +1537,7 @@ static void encode_inter(enc *e, int kind) {
     m->type = (uint8_t)kind;
     /* reference indices */
     int refs4[4];
-    for (int i = 0; i < 4; i++) refs4[i] = (nref > 1 && rnd(e) % 100 < 35) ? rnd_range(e, 0, nref - 1) : 0;
+    for (int i = 0; i < 4; i++) refs4[i] = barrier_ref(e, 0, (nref > 1 && rnd(e) % 100 < 35) ? rnd_range(e, 0, nref - 1) : 0);
     if (kind == T_P16)
         refs4[1] = refs4[2] = refs4[3] = refs4[0];
     else if (kind == T_P16x8)
@@ -1966,12 +1975,12 @@ static void encode_b(enc *e, int kind) {
     for (int l = 0; l < 2; l++) {
         if (kind == T_P8x8) { /* one index per non-direct quadrant that uses the list */
             for (int i = 0; i < 4; i++)
-                if (b_sub_mode[m->sub[i]] >> l & 1) EREF(m, l)[i] = (int8_t)((nref[l] > 1 && rnd(e) % 100 < 35) ? rnd_range(e, 0, nref[l] - 1) : 0);
+                if (b_sub_mode[m->sub[i]] >> l & 1) EREF(m, l)[i] = (int8_t)barrier_ref(e, l, (nref[l] > 1 && rnd(e) % 100 < 35) ? rnd_range(e, 0, nref[l] - 1) : 0);
             continue;
         }
         for (int i = 0; i < np; i++) {
             if (!(pt[i].mode >> l & 1)) continue;
-            int r = (nref[l] > 1 && rnd(e) % 100 < 35) ? rnd_range(e, 0, nref[l] - 1) : 0;
+            int r = barrier_ref(e, l, (nref[l] > 1 && rnd(e) % 100 < 35) ? rnd_range(e, 0, nref[l] - 1) : 0);
             for (int y = pt[i].by >> 1; y < (pt[i].by + pt[i].h + 1) >> 1; y++)
                 for (int x = pt[i].bx >> 1; x < (pt[i].bx + pt[i].w + 1) >> 1; x++) EREF(m, l)[y * 2 + x] = (int8_t)r;
         }
@@ -2455,6 +2464,12 @@ static void write_slice_header(enc *e, int first_mb, int idr, int frame_num, int
 static uint32_t g_feat;
 static int32_t g_pocs[8192];
 static int g_npocs;
+static int32_t g_entries[4096][2]; /* sg_last_entries() */
+static int g_nentries;
+int sg_last_entries(int32_t *dst, int cap) {
+    for (int i = 0; i < 2 * g_nentries && i < cap && dst; i++) dst[i] = g_entries[i / 2][i % 2];
+    return g_nentries;
+}
 uint32_t sg_last_features(void) { return g_feat; }
 int sg_last_ranges(int32_t *dst, int cap) {
     for (int i = 0; i < SG_R_COUNT && i < cap && dst; i++) dst[i] = g_rng[i];
@@ -3078,6 +3093,12 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
     if (p->slices < 1) p->slices = 1;
     if (p->fn_gap_period > 0 && p->num_ref_frames < 3) p->num_ref_frames = 3; /* up to two non-existing frames enter the window: a real picture must survive them */
     if (p->profile_idc != 100) p->transform8x8 = 0, p->scaling_matrix = 0;
+    if (p->open_gop_period > 0 && (p->rplm || p->mmco || p->idr_long_term || p->fn_gap_period > 0 || p->wp_range == 2 || p->direct_temporal)) {
+        snprintf(g_err, sizeof(g_err), "open_gop_period cannot be combined with rplm, mmco, idr_long_term, fn_gap_period, wp_range 2 or direct_temporal");
+        free(e);
+        return 0;
+    }
+    if (p->open_gop_period < 0) p->open_gop_period = 0;
     if (p->profile_idc == 66) p->cabac = 0, p->weighted_pred = 0, p->bframes = 0;
     if (p->bframes > 0) { /* B pictures: two anchors must be referable, and the output order differs from the coding order */
         if (p->num_ref_frames < 2) p->num_ref_frames = 2;
@@ -3086,6 +3107,7 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
         if (p->bframes < 2) p->b_pyramid = 0;
         /* the coding-order planner below puts an anchor every (bframes + 1) pictures: an IDR picture must be one of them */
         if (p->idr_period > 0 && p->idr_period % (p->bframes + 1)) p->idr_period += (p->bframes + 1) - p->idr_period % (p->bframes + 1);
+        if (p->open_gop_period % (p->bframes + 1)) p->open_gop_period += (p->bframes + 1) - p->open_gop_period % (p->bframes + 1);
         if (p->b_pyramid) p->num_ref_frames = 4; /* two anchors, the reference B picture of this group and the one of the group before */
     } else
         p->b_pyramid = 0;
@@ -3201,11 +3223,24 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
         }
     }
     int idr_disp = 0;
+    /* open_gop_period: the parameter sets as they stand in the stream (sent again, byte for byte, in front of every non-IDR I anchor), and the two
+     * anchors last coded that way -- display index and coding index; the later one is no barrier yet for the B pictures in front of it */
+    size_t ps_off = 0, ps_len = 0;
+    int bar_dsp[2] = {-1, -1}, bar_ct[2] = {-1, -1};
+    g_nentries = 0;
     for (int t = 0; t < p->frames; t++) {
         size_t au_start = out;
         const int dsp = disp[t], bpic = is_b[t];
         const int idr_frame = dsp == 0 || (p->idr_period > 0 && dsp % p->idr_period == 0);
-        if (idr_frame) idr_disp = dsp;
+        const int og_frame = p->open_gop_period > 0 && dsp > 0 && dsp % p->open_gop_period == 0 && !idr_frame && !bpic;
+        if (idr_frame) idr_disp = dsp, bar_dsp[0] = bar_dsp[1] = -1;
+        if (og_frame) {
+            int lead = 0;
+            for (int u = t + 1; u < p->frames && is_b[u]; u++) lead += disp[u] < dsp ? (p->field_pics ? 2 : 1) : 0;
+            bar_dsp[0] = bar_dsp[1], bar_ct[0] = bar_ct[1], bar_dsp[1] = dsp, bar_ct[1] = t;
+            if (g_nentries < 4096) g_entries[g_nentries][0] = t, g_entries[g_nentries++][1] = lead;
+            g_feat |= 1u << 16;
+        }
         mark_state ms;
         field_drops fd;
         fd.n = 0;
@@ -3215,7 +3250,7 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
       for (int fld = 0; fld < (as_fields ? 2 : 1); fld++) { /* the picture(s) of frame t: the frame, or its two fields */
         /* only the first field of an IDR frame is an IDR picture; the second one is a P field (it may predict from the first) or an I field */
         const int idr = idr_frame && fld == 0;
-        int intra_pic = idr || (idr_frame && fld == 1 && (p->seed + (unsigned)t) % 3 == 0);
+        int intra_pic = idr || (idr_frame && fld == 1 && (p->seed + (unsigned)t) % 3 == 0) || og_frame;
         e->field = as_fields, e->bottom = as_fields ? (p->field_pics == 2) ^ fld : 0;
         e->H = as_fields ? e->fH / 2 : e->fH, e->hmb = e->H / 16; /* the PICTURE: a frame or one field */
         sg_set_field_mode(as_fields);
@@ -3236,12 +3271,30 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
             frame_num = 0, poc = 0, e->nrefs = 0, refs_since_reset = 0, since_idr = 0;
             /* scaling_matrix 3: the pictures under every third PPS do without the 8x8 transform (a matrix of six lists) */
             if (p->scaling_matrix == 3) p->transform8x8 = e->t8_req && (e->n_param_sets + (int)(p->seed % 3u)) % 3 != 2;
+            ps_off = out;
             size_t n = write_sps(e, stream + out, cap - out);
             out += n;
             n = write_pps(e, stream + out, cap - out);
             out += n;
+            ps_len = out - ps_off;
             e->n_param_sets++;
             for (int i = 0; i < 6; i++) e->pics[i].is_ref = 0;
+        }
+        if (og_frame && fld == 0) { /* the parameter sets again, and the recovery point: recovery_frame_cnt ue(0), exact_match_flag 1, broken_link_flag 0, changing_slice_group_idc 0 */
+            static const uint8_t sei[3] = {6, 1, 0xC4}; /* payloadType 6, payloadSize 1, the payload with its alignment bit */
+            uint8_t sei_rbsp[4];
+            size_t n = 0;
+            if (ps_len && out + ps_len <= cap) {
+                memmove(stream + out, stream + ps_off, ps_len);
+                memcpy(sei_rbsp, sei, 3), sei_rbsp[3] = 0x80; /* rbsp_trailing_bits */
+                n = sg_write_nal(stream + out + ps_len, cap - out - ps_len, p->long_start_code, 0, 6, sei_rbsp, 4);
+            }
+            if (!n) {
+                snprintf(g_err, sizeof(g_err), "stream buffer too small");
+                out = 0;
+                goto done;
+            }
+            out += ps_len + n;
         }
         /* frame_num gap (8.2.5.2): the skipped values enter the window as non-existing frames, oldest pictures leave */
         if (p->fn_gap_period > 0 && p->bframes == 0 && !p->mmco && !idr && since_idr > 0 && since_idr % p->fn_gap_period == 0) {
@@ -3270,6 +3323,8 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
                 if (!e->pics[i].is_ref) e->cur_frame = &e->pics[i];
             e->cur_frame->nonexist = 0, e->cur_frame->frame_num = frame_num, e->cur_frame->poc = poc;
             e->fpics[e->cur_frame - e->pics][0].dropped = e->fpics[e->cur_frame - e->pics][1].dropped = 0;
+            e->cur_frame->dsp = e->fpics[e->cur_frame - e->pics][0].dsp = e->fpics[e->cur_frame - e->pics][1].dsp = dsp;
+            e->cur_frame->ct = e->fpics[e->cur_frame - e->pics][0].ct = e->fpics[e->cur_frame - e->pics][1].ct = t;
         }
         e->cur = e->field ? &e->fpics[e->cur_frame - e->pics][e->bottom] : e->cur_frame;
         e->cur->nonexist = 0;
@@ -3302,6 +3357,27 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
         /* field streams with marking scripts: a frame picture may find no frame with both fields still marked (and a field, in principle,
          * no field at all) -- such a picture is coded as a non-IDR I picture */
         if (p->field_pics && !bpic && !intra_pic && e->nref_active == 0) intra_pic = 1, e->slice_type = 2;
+        /* open_gop_period, the reference barrier (sg.h): the anchor this picture lies behind in display order, and what of its lists it leaves */
+        e->allow[0] = e->allow[1] = ~0u;
+        const int bar = bar_dsp[1] >= 0 && dsp > bar_dsp[1] ? 1 : (bar_dsp[0] >= 0 && dsp > bar_dsp[0] ? 0 : -1);
+        if (bar >= 0 && !intra_pic) {
+            for (int l = 0; l < (bpic ? 2 : 1); l++) {
+                sg_pic **list = l ? e->refs1 : e->refs;
+                const int n = l ? e->nref1_active : e->nref_active;
+                int shifted = 0; /* an entry in front that a decoder which started at the anchor does not have */
+                e->allow[l] = 0;
+                for (int i = 0; i < n && i < 4; i++) {
+                    if (list[i]->dsp >= bar_dsp[bar] && !shifted) e->allow[l] |= 1u << i;
+                    if (list[i]->dsp < bar_dsp[bar] && list[i]->ct < bar_ct[bar]) shifted = 1;
+                }
+            }
+            if (!bpic && !e->allow[0]) intra_pic = 1, e->slice_type = 2, e->allow[0] = ~0u; /* nothing to predict from: a non-IDR I picture */
+            if (bpic && (!(e->allow[0] & 1) || !(e->allow[1] & 1))) { /* (does not happen: entry 0 of either list is the nearest picture on its side) */
+                snprintf(g_err, sizeof(g_err), "open_gop_period: direct prediction of a B picture would cross the reference barrier");
+                out = 0;
+                goto done;
+            }
+        }
         if (getenv("SG_DEBUG")) {
             fprintf(stderr, "t=%d fn=%d ref_idc=%d list:", t, frame_num, e->nal_ref_idc);
             for (int i = 0; i < e->nref_active && !idr; i++) fprintf(stderr, " id%d(fn%d,%s%d)", e->refs[i]->id, e->refs[i]->frame_num, e->refs[i]->is_ref == 2 ? "L" : "s", e->refs[i]->long_idx);
@@ -3487,6 +3563,7 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
                     else
                         kind = T_P16;
                     if (force_skip) kind = T_SKIP;
+                    if (kind == T_SKIP && !(e->allow[0] & 1)) kind = T_P16; /* (the reference barrier: P_Skip predicts from entry 0) */
                     if (e->force_pcm) kind = T_I4;
                     if (p->cabac) {
                         emb *a = MBA(e), *b = MBB(e);

@@ -47,6 +47,7 @@ typedef struct {
     int dropped;     /* field pictures: this field was marked "unused for reference" on its own (memory_management_control_operation 1) */
     int parity, fid; /* field pictures (sg_params::field_pics): 0 top / 1 bottom, and the frame the field belongs to */
     void *motion; /* the picture's macroblock motion (an emb array of sg_enc.c): co-located data of later B pictures */
+    int dsp, ct;  /* the frame's place in display order and in coding order (sg_params::open_gop_period: the reference barrier) */
 } sg_pic;
 
 typedef struct {

@@ -31,6 +31,9 @@ def main():
     ap.add_argument("--conceal-idr", action="store_true", help="... and lost or damaged slices of IDR pictures that still have a reference frame are concealed too (implies --conceal)")
     ap.add_argument("--conceal-fields", action="store_true", help="... and lost or damaged slices of field pictures are concealed too (implies --conceal)")
     ap.add_argument("--conceal-lone-fields", action="store_true", help="... and the wholly lost field of a frame coded as two field pictures is concealed too (implies --conceal-fields)")
+    ap.add_argument("--random-access", action="store_true",
+                    help="a connection that starts in the middle of a stream is decoded from its first recovery point on (a non-IDR I picture with a recovery point SEI "
+                         "message), and a stream that lost a picture comes back there; default: IDR pictures only")
     ap.add_argument("--batch", type=int, default=0, help="decode up to N concurrent connections side by side in one batched decoder (H.BatchServer)")
     args = ap.parse_args()
     conceal = (H.CONCEAL_PICTURES if args.conceal_pictures else 0) | (H.CONCEAL_FIELDS if args.conceal_fields else 0) | (H.CONCEAL_IDR if args.conceal_idr else 0)
@@ -45,6 +48,7 @@ def main():
     if args.batch > 0:  # several connections, one batched GPU decoder
         import select
         bs = H.BatchServer(max_connections=args.batch, max_width=args.max_width, max_height=args.max_height, frames_per_batch=args.frames_per_batch, conceal_errors=conceal,
+                           random_access=args.random_access,
                            on_frames=lambda i, f: print("slot %d: %d frames md5 %s" % (i, len(f), hashlib.md5(f.tobytes()).hexdigest()), flush=True),
                            on_close=lambda i, n: print("slot %d closed after %d frames" % (i, n), flush=True))
         srv.setblocking(False)
@@ -66,7 +70,7 @@ def main():
 
         try:
             H.ByteStreamReader(conn, on_frames=on_frames, max_width=args.max_width, max_height=args.max_height, frames_per_batch=args.frames_per_batch,
-                               display_order=args.display_order, conceal_errors=conceal)
+                               display_order=args.display_order, conceal_errors=conceal, random_access=args.random_access)
         except H.H264MIError as e:
             print("%s: decode error: %s" % (peer[0], e), flush=True)
         if args.once:
