@@ -1,7 +1,7 @@
 /*
  * examples/h264mi_decode.c -- the C ABI from plain C: decode an Annex-B file to raw I420 on the GPU.
  *
- *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--random-access] [--conceal...] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge|motion|motion-edge] [--field-rate] [--stats]
+ *   h264mi_decode in.h264 out.yuv [frames_per_batch] [--random-access] [--conceal...] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge|motion|motion-edge] [--field-rate] [--stats] [--jpeg PREFIX [--quality N]]
  *
  * --nv12 / --rgb write NV12 / tight R, G, B bytes instead of I420: the frames are converted on the device (h264mi_batch_convert_device into a
  * device buffer, matrix and range from each frame's own SPS) and copied to the host from there.  --scale WxH writes every frame at W x H instead of
@@ -14,7 +14,10 @@
  * deinterlaced against the frame before it in output order, and the first frame of a batch against the last one of the batch before, so a file decoded
  * in several batches (frames_per_batch) comes out as if it had been decoded in one.  --stats prints one line per decoded frame to stdout, in decoding
  * order: its mean luma, its mean absolute luma difference against the frame before it in output order, and how many luma samples changed by more than 8
- * (h264mi_batch_stats_device with H264MI_STATS_HISTORY -- on the first batch too, or no later batch had a predecessor for its first frame).  The HIP
+ * (h264mi_batch_stats_device with H264MI_STATS_HISTORY -- on the first batch too, or no later batch had a predecessor for its first frame).  --jpeg PREFIX
+ * writes every frame (with --deinterlace: every derived frame) as a baseline JPEG file PREFIX%05d.jpg as well, encoded on the device
+ * (h264mi_batch_jpeg_device, H264MI_JPEG_RANGE_AUTO; --quality N, 1 .. 100, default 90): a slot of the header plus w * h / 2 bytes per frame, and a
+ * second call with the size they asked for if frames report H264MI_JPEG_TRUNCATED.  The HIP
  * calls of these paths are the only HIP this file needs; they are declared below, so it still builds without the HIP headers.
  *
  * The file includes nothing but include/h264mi.h and the C library.
@@ -47,10 +50,14 @@ static int fail(const char *what, int code) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--random-access] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge|motion|motion-edge] [--field-rate] [--stats]\n", argv[0]);
+        fprintf(stderr, "usage: %s in.h264 out.yuv [frames_per_batch] [--random-access] [--conceal | --conceal-all | --conceal-idr | --conceal-lone-fields] [--nv12 | --rgb] [--scale WxH[:area] | --tensor WxH] [--deinterlace field|blend|edge|motion|motion-edge] [--field-rate] [--stats] [--jpeg PREFIX [--quality N]]\n", argv[0]);
         return 2;
     }
-    int stats = 0; /* --stats (the last argument of all): the frame statistics of every batch, on stdout */
+    const char *jpeg_prefix = NULL; /* --jpeg PREFIX [--quality N] (the last arguments of all): every frame as PREFIX%05d.jpg too */
+    int jpeg_quality = 90;
+    if (argc > 6 && !strcmp(argv[argc - 2], "--quality") && !strcmp(argv[argc - 4], "--jpeg")) jpeg_quality = atoi(argv[argc - 1]), argc -= 2;
+    if (argc > 4 && !strcmp(argv[argc - 2], "--jpeg")) jpeg_prefix = argv[argc - 1], argc -= 2;
+    int stats = 0; /* --stats (the last argument before those): the frame statistics of every batch, on stdout */
     if (argc > 3 && !strcmp(argv[argc - 1], "--stats")) stats = 1, argc--;
     int deint = -1, deint_rate = 1, deint_motion = 0; /* --deinterlace MODE and --field-rate (the last arguments of all): derived frames instead of the woven ones */
     if (argc > 3 && !strcmp(argv[argc - 1], "--field-rate")) deint_rate = 2, argc--;
@@ -160,6 +167,10 @@ int main(int argc, char **argv) {
     void *sdev = NULL; /* --stats: the records of a batch on the device, and their host copy */
     h264mi_frame_stats *srec = NULL;
     size_t sdev_cap = 0;
+    void *jdev = NULL; /* --jpeg: results and slots of a batch on the device, and their host copy */
+    uint8_t *jhost = NULL;
+    size_t jdev_cap = 0, jslot = 0;
+    long jpeg_total = 0;
     long stats_total = 0; /* frames reported so far (total counts what is written: two per frame with --field-rate) */
     const h264mi_stats_spec sspec = {0, 0, 8, 0}; /* no grid; changed_y counts |S - P| > 8 */
     long total = 0;
@@ -255,6 +266,41 @@ int main(int argc, char **argv) {
                         return fail("h264mi_batch_deinterlace", r);
                     src = H264MI_STREAM_DERIVED;
                 }
+                if (jpeg_prefix && k > 0) { /* three launches make the files of the batch; a second round if a slot was too small */
+                    const h264mi_jpeg_spec jspec = {jpeg_quality, H264MI_JPEG_RANGE_AUTO, 0, 0};
+                    size_t hb = 0;
+                    if ((r = h264mi_jpeg_size(&jspec, info.coded_width, info.coded_height, 0, &hb, NULL)) != H264MI_OK) return fail("h264mi_jpeg_size", r);
+                    if (!jslot) jslot = (hb + (size_t)info.coded_width * info.coded_height / 2 + 15) & ~(size_t)15;
+                    for (int round = 0; round < 2; round++) {
+                        const size_t head = ((size_t)16 * k + 255) & ~(size_t)255;
+                        size_t bytes = head + (size_t)k * jslot, need_slot = 0;
+                        if (bytes > jdev_cap) {
+                            if (jdev) hipFree(jdev);
+                            if (hipMalloc(&jdev, jdev_cap = bytes) != 0) return fail("hipMalloc", H264MI_ENOMEM);
+                            jhost = (uint8_t *)realloc(jhost, bytes);
+                        }
+                        if ((r = h264mi_batch_jpeg_device(dec, src, &jspec, jslot, jdev, jdev_cap, &bytes)) != H264MI_OK) return fail("h264mi_batch_jpeg_device", r);
+                        if ((r = h264mi_batch_sync(dec)) != H264MI_OK) return fail("h264mi_batch_sync", r);
+                        if (hipMemcpy(jhost, jdev, bytes, 2 /* hipMemcpyDeviceToHost */) != 0) return fail("hipMemcpy", H264MI_EDEVICE);
+                        const h264mi_jpeg_result *res = (const h264mi_jpeg_result *)jhost;
+                        for (int q = 0; q < k; q++)
+                            if (res[q].status == H264MI_JPEG_TRUNCATED && res[q].bytes > need_slot) need_slot = res[q].bytes;
+                        if (need_slot && round == 0) { /* the size they asked for; it stays for the batches to come */
+                            jslot = (need_slot + 15) & ~(size_t)15;
+                            continue;
+                        }
+                        for (int q = 0; q < k; q++) {
+                            char name[1024];
+                            snprintf(name, sizeof name, "%s%05ld.jpg", jpeg_prefix, jpeg_total + q);
+                            FILE *jf = fopen(name, "wb");
+                            if (!jf || res[q].status != 0) return fail(name, H264MI_EINVAL);
+                            fwrite(jhost + head + (size_t)q * jslot, 1, res[q].bytes, jf);
+                            fclose(jf);
+                        }
+                        break;
+                    }
+                    jpeg_total += k;
+                }
                 const size_t need = H264MI_I420_SIZE(info.coded_width, info.coded_height);
                 if (need > frame_cap) frame = (uint8_t *)realloc(frame, frame_cap = need);
                 if (tensor.out_w) { /* one launch makes the items of the batch; the size query as below */
@@ -312,6 +358,7 @@ int main(int argc, char **argv) {
     }
     if (dev) hipFree(dev);
     if (sdev) hipFree(sdev);
+    if (jdev) hipFree(jdev);
     h264mi_decoder_destroy(dec);
     fprintf(stderr, "%s: %ld frames %dx%d -> %s\n", h264mi_version(), total, sps.width, sps.height, argv[2]);
     return 0;

@@ -14,6 +14,7 @@ from .h264 import (  # noqa: F401
     DEINT_FIELD, DEINT_BLEND, DEINT_EDGE, DEINT_PARITY_FIRST, STREAM_DERIVED, deint_rows,
     DEINT_PREV_NONE, DEINT_PREV_HISTORY, DEINT_HISTORY, deint_motion_pixel,
     STATS_CELL_SUM, STATS_CELL_SAD, STATS_PLANE_NAMES, STATS_PREV_NONE, STATS_PREV_HISTORY, STATS_HISTORY, STATS_U64, STATS_U32, stats_planes, stats_spec,
+    JPEG_RANGE_AUTO, JPEG_RANGE_KEEP, JPEG_RANGE_FULL, JPEG_TRUNCATED, jpeg_spec, jpeg_size, jpeg_quant_table, jpeg_block,
     SIDE_NAMES, SIDE_ALL, side_planes, MB_NONE, MB_I4x4, MB_I8x8, MB_I16x16, MB_IPCM, MB_P16x16, MB_P16x8, MB_P8x16, MB_P8x8, MB_PSKIP, MB_B, MB_BDIRECT, MB_BSKIP)
 from .mbtype import (  # noqa: F401
     MB_TYPE_INFERRED, ISliceMbType, SISliceMbType, PSliceMbType, BSliceMbType, MbTypeName, MbPartPredMode, NumMbPart, PicWidthInMbs,

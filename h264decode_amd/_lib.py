@@ -53,6 +53,7 @@ FieldInfo, DeintItem = _S["h264mi_field_info"], _S["h264mi_deint_item"]
 SideItem = _S["h264mi_side_item"]
 DeintMotionItem = _S["h264mi_deint_motion_item"]
 FrameStats, StatsSpec, StatsItem = _S["h264mi_frame_stats"], _S["h264mi_stats_spec"], _S["h264mi_stats_item"]
+JpegSpec, JpegItem, JpegResult = _S["h264mi_jpeg_spec"], _S["h264mi_jpeg_item"], _S["h264mi_jpeg_result"]
 RecoveryPoint, FrameEntryInfo, RandomAccessStats = _S["h264mi_recovery_point"], _S["h264mi_frame_entry_info"], _S["h264mi_random_access_stats"]
 
 
@@ -173,6 +174,12 @@ def load():
         "h264mi_items_stats_device": [vp, P(StatsSpec), P(StatsItem), I32, vp, SZ, P(SZ)],
         "h264mi_batch_stats_plan": [vp, I32, I32, P(StatsItem), I32, P(I32)],
         "h264mi_batch_stats_device": [vp, I32, P(StatsSpec), I32, vp, SZ, P(SZ)],
+        "h264mi_jpeg_quant_table": [I32, I32, P(ctypes.c_uint16)],
+        "h264mi_jpeg_block": [P(ctypes.c_uint8), P(ctypes.c_uint16), P(ctypes.c_int16)],
+        "h264mi_jpeg_size": [P(JpegSpec), I32, I32, I32, P(SZ), P(SZ)],
+        "h264mi_items_jpeg_device": [vp, P(JpegSpec), P(JpegItem), I32, SZ, vp, SZ, P(SZ)],
+        "h264mi_batch_jpeg_device": [vp, I32, P(JpegSpec), SZ, vp, SZ, P(SZ)],
+        "h264mi_i420_jpeg_device": [vp, P(JpegSpec), vp, I32, I32, I32, I32, SZ, vp, SZ, P(SZ)],
         "h264mi_frame_read_mbrecs": [vp, I32, I32, vp, SZ],
         "h264mi_frame_read_mbmv1": [vp, I32, I32, vp, SZ],
         "h264mi_decoder_set_profiling": [vp, I32],
@@ -220,4 +227,5 @@ EXPORTS = ["h264mi_annexb_scan", "h264mi_nal_parse", "h264mi_sps_parse", "h264mi
            "h264mi_deint_motion_pixel", "h264mi_items_deinterlace_motion", "h264mi_batch_deinterlace_motion", "h264mi_derived_prev",
            "h264mi_side_size", "h264mi_frame_ref_pocs", "h264mi_items_side_device", "h264mi_batch_side_device",
            "h264mi_stats_size", "h264mi_items_stats_device", "h264mi_batch_stats_plan", "h264mi_batch_stats_device",
+           "h264mi_jpeg_quant_table", "h264mi_jpeg_block", "h264mi_jpeg_size", "h264mi_items_jpeg_device", "h264mi_batch_jpeg_device", "h264mi_i420_jpeg_device",
            "h264mi_decoder_set_random_access", "h264mi_sei_recovery_point", "h264mi_frame_entry", "h264mi_stream_random_access_stats"]

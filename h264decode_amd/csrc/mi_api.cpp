@@ -209,7 +209,7 @@ static void free_all(h264mi_decoder *d) {
     }
     each(hipStreamDestroy, d->ent_stream[0], d->ent_stream[1], d->rec_stream);
     for (DescTables &t : d->tables) each(hipFree, t.d[0], t.d[1]), each(hipHostFree, t.h[0], t.h[1]), each(hipEventDestroy, t.ev[0], t.ev[1]);
-    each(hipFree, d->d_coef[0], d->d_pool_head, d->d_colrec, d->d_backfill, d->d_xring, d->d_xdone, d->d_xctl, d->d_pools, d->d_derived, d->hist[HIST_DEINT].arena, d->hist[HIST_STATS].arena, d->d_frames, d->d_tables);
+    each(hipFree, d->d_coef[0], d->d_pool_head, d->d_colrec, d->d_backfill, d->d_xring, d->d_xdone, d->d_xctl, d->d_pools, d->d_derived, d->hist[HIST_DEINT].arena, d->hist[HIST_STATS].arena, d->d_jpeg_ivl, d->d_frames, d->d_tables);
     each(hipHostFree, d->h_xstatus, d->h_tables);
     each(hipEventDestroy, d->ev_user);
     for (auto e : d->ev) hipEventDestroy(e);

@@ -41,6 +41,7 @@ struct OutFrame { // a decoded picture of the current batch, with the geometry i
     // stream entered here after waiting (random access)
     h264mi_recovery_point rp = {0, 0, 0, 0, 0};
     int entry = 0;
+    int mono = 0; // chroma_format_idc 0 of the picture's own SPS: K13 writes one component
 };
 struct StreamState {
     h264mi_sps sps[32];
@@ -174,7 +175,7 @@ struct DescTables {
     hipEvent_t ev[2] = {nullptr, nullptr};
     int slot = 0;
 };
-enum { OUT_PACK, OUT_CONVERT, OUT_SCALE, OUT_TENSOR, OUT_DEINT, OUT_SIDE, OUT_DEINT_MOTION, OUT_STATS, OUT_FAMILIES }; // K6, K7, K8, K9, K10, K11, K10 motion-adaptive, K12
+enum { OUT_PACK, OUT_CONVERT, OUT_SCALE, OUT_TENSOR, OUT_DEINT, OUT_SIDE, OUT_DEINT_MOTION, OUT_STATS, OUT_JPEG, OUT_FAMILIES }; // K6, K7, K8, K9, K10, K11, K10 motion-adaptive, K12, K13
 
 // A derived (deinterlaced) frame: frame k of the pseudo-stream H264MI_STREAM_DERIVED.  `of`: its source's OutFrame (what the accessors report); off: its
 // slot in the arena, in the layout of a frame slot of the source's coded size; prev: what it was made from besides its source (h264mi_derived_prev) -- a
@@ -282,6 +283,10 @@ struct h264mi_decoder {
     uint8_t *d_derived = nullptr;
     size_t derived_cap = 0;
     HistorySet hist[HIST_KINDS]; // K10, motion-adaptive, and K12: a history each
+    // K13: the interval table (a length, then an offset, per restart interval of a call), allocated by the first call that launches, grown to the largest
+    // call and kept
+    uint32_t *d_jpeg_ivl = nullptr;
+    size_t jpeg_ivl_cap = 0; // entries
     uint64_t prep_seq = 0; // h264mi_batch_prepare calls so far
     std::vector<float> launch_ms[4]; // duration of every launch of the last profiled pass, per kernel
 };

@@ -276,6 +276,37 @@ static_assert((MI_STATS_CHROMA_ROWS / 8 * (MI_STATS_MAX_AXIS / 16) / 256 + 1) * 
               "a thread's 32-bit partial sum of squares overflows");
 static_assert(static_cast<unsigned long long>(MI_STATS_CHROMA_ROWS) * MI_STATS_MAX_AXIS * 255 < (1ull << 32), "a block's 32-bit sums overflow");
 extern "C" __global__ void k_stats(StatsDesc *descs, uint8_t *dst, uint32_t cell_log2, uint32_t planes, uint32_t thresh);
+// K13 (k_jpeg.hip): a list of frames -> baseline JPEG files, one per slot of the destination, by the rule of include/h264mi.h ("JPEG snapshots").  A
+// one-wavefront workgroup owns a restart interval; the grid is flat over the intervals of all items (JpegDesc::ivl_base ascends: a workgroup finds its
+// item by bisection).  Three launches: k_jpeg_size leaves every interval's stuffed byte length in the interval table, k_jpeg_scan turns the lengths of an
+// item into offsets inside its slot and writes the item's h264mi_jpeg_result, k_jpeg_write encodes again and stores header, intervals, markers.
+// The table of a launch: one JpegParams, then the JpegDescs
+#define MI_JPEG_HDR_MAX 640      /* the longest header (4:2:0: 629 bytes) */
+#define MI_JPEG_BLOCK_BITS 1660  /* the most bits a block can take: DC 11 + 11, 63 x (16 + 10) for AC -- the derivation is h264mi_jpeg_size's */
+#define MI_JPEG_BUF_WORDS 256    /* the wavefront's bit buffer in LDS: 4 words a lane; it is flushed once a worst-case block may no longer fit */
+static_assert(MI_JPEG_BUF_WORDS * 32 >= 2 * MI_JPEG_BLOCK_BITS + 64, "the bit buffer must hold a block behind the flush threshold");
+typedef struct {
+    uint64_t y, cb, cr;   // first sample of the display rectangle in each plane (cb, cr unused for mono)
+    uint64_t slot_off;    // byte offset of the item's slot in the destination
+    uint32_t ystride, cstride;
+    uint32_t w, h;        // display size; chroma planes are ceil(w / 2) x ceil(h / 2)
+    uint32_t mono, full;  // one component; limited -> full range
+    uint32_t mcus_w, n_mcus; // MCUs per row, MCUs in all
+    uint32_t restart, n_int; // MCUs per restart interval (resolved), intervals
+    uint32_t ivl_base;    // the item's first entry of the interval table
+    uint32_t pad;
+} JpegDesc;
+typedef struct {
+    uint16_t q[2][64];       // quantisation tables, natural order
+    uint32_t dc[2][12];      // Huffman codes by symbol: length << 16 | code
+    uint32_t ac[2][256];
+    uint8_t hdr[2][MI_JPEG_HDR_MAX]; // SOI .. SOS for 4:2:0 and for mono, with zero size and restart interval
+    uint32_t hdr_len[2], sof_off[2], dri_off[2]; // length; where height (2 bytes, then width) and the restart interval go
+    uint32_t n_items, slot_bytes;
+} JpegParams;
+extern "C" __global__ void k_jpeg_size(const uint8_t *table, uint32_t *ivl, uint32_t total);
+extern "C" __global__ void k_jpeg_scan(const uint8_t *table, uint32_t *ivl, uint8_t *dst);
+extern "C" __global__ void k_jpeg_write(const uint8_t *table, const uint32_t *ivl, uint8_t *dst, uint32_t total);
 
 #ifndef MI_INTRA_WAVES
 #define MI_INTRA_WAVES 16 /* 1024 threads, 128 VGPRs per wavefront: the kernels need 120 once nothing lane-dependent is hoisted out of the macroblock loop */

@@ -3,7 +3,8 @@
 // k_deint_motion: deinterlaced frames, which K6 .. K9 read like frames of the batch), and the device-free rule functions of include/h264mi.h that say what those
 // kernels compute (h264mi_output_size, _csc_resolve, _scale_taps, _fit_rect, _tensor_size, _deint_rows, _deint_motion_pixel, _side_size), and K11 (k_side: the macroblock
 // records of the batch as planes of side information), and K12 (k_stats: sums, a histogram and differences against a predecessor, per frame and per
-// cell of a grid -- h264mi_stats_size and the statistics history).  The eight kernel families share ONE launch discipline (stage_descs / fence_launch
+// cell of a grid -- h264mi_stats_size and the statistics history), and K13 (k_jpeg: baseline JPEG files of frames, and the rule functions
+// h264mi_jpeg_quant_table, _jpeg_block, _jpeg_size over k_jpeg_rule.h).  The nine kernel families share ONE launch discipline (stage_descs / fence_launch
 // below); each has descriptor tables of its own.
 // (the reference has no output process: h264/server.go:113-166 stops at the parsed slice)
 #include <algorithm>
@@ -13,6 +14,7 @@
 #include <cstring>
 #include <utility>
 #include "mi_decoder.hpp"
+#include "k_jpeg_rule.h"
 
 void crop_rect(const OutFrame *of, int crop, int *x0, int *y0, int *w, int *h) {
     *x0 = *y0 = 0, *w = of->wmb * 16, *h = of->hmb * 16;
@@ -1054,4 +1056,231 @@ extern "C" int32_t h264mi_batch_stats_device(h264mi_decoder *d, int32_t stream, 
     FrameList take;
     TRY(stats_plan(d, stream, flags, plan, &take));
     return stats_items(d, spec, plan.data(), plan.size(), dst, cap, bytes, take);
+}
+
+// ---------------------------------------------------------------- JPEG snapshots (K13): the rule of include/h264mi.h, "JPEG snapshots"
+static_assert(sizeof(h264mi_jpeg_result) == 16 && sizeof(JpegDesc) % 8 == 0 && sizeof(JpegParams) % 8 == 0, "the destination's records; descriptors follow the parameters aligned");
+
+extern "C" int32_t h264mi_jpeg_quant_table(int32_t quality, int32_t chroma, uint16_t q[64]) {
+    if (!q || quality < 1 || quality > 100 || (chroma != 0 && chroma != 1)) return H264MI_EINVAL;
+    for (int i = 0; i < 64; i++) q[i] = static_cast<uint16_t>(jpeg_q(quality, chroma, i));
+    return H264MI_OK;
+}
+
+extern "C" int32_t h264mi_jpeg_block(const uint8_t s[64], const uint16_t q[64], int16_t level[64]) {
+    if (!s || !q || !level) return H264MI_EINVAL;
+    for (int i = 0; i < 64; i++)
+        if (q[i] < 1 || q[i] > 255) return H264MI_EINVAL;
+    int16_t x[64], rt[64]; // rt: the row pass, transposed
+    for (int i = 0; i < 64; i++) x[i] = static_cast<int16_t>(s[i] - 128);
+    for (int y = 0; y < 8; y++)
+        for (int k = 0; k < 8; k++) rt[8 * k + y] = static_cast<int16_t>(jpeg_row_term(x + 8 * y, k));
+    for (int v = 0; v < 8; v++)
+        for (int k = 0; k < 8; k++) level[8 * v + k] = static_cast<int16_t>(jpeg_level(jpeg_col_term(rt + 8 * k, v), q[8 * v + k]));
+    return H264MI_OK;
+}
+
+static int check_jpeg_spec(const h264mi_jpeg_spec *spec, bool auto_ok) {
+    if (spec->quality < 1 || spec->quality > 100) {
+        set_error("JPEG quality %d: not 1 .. 100", spec->quality);
+        return H264MI_EINVAL;
+    }
+    if (spec->range != H264MI_JPEG_RANGE_KEEP && spec->range != H264MI_JPEG_RANGE_FULL && !(auto_ok && spec->range == H264MI_JPEG_RANGE_AUTO)) {
+        set_error("JPEG range %d: not H264MI_JPEG_RANGE_KEEP or _FULL%s", spec->range, auto_ok ? " or _AUTO" : " (_AUTO needs a stream: there is none behind caller-held frames)");
+        return H264MI_EINVAL;
+    }
+    if (spec->restart_mcus < 0 || spec->restart_mcus > 65535 || spec->flags != 0) {
+        set_error("JPEG spec: restart_mcus %d must be 0 .. 65535 and flags 0x%x must be 0", spec->restart_mcus, static_cast<unsigned>(spec->flags));
+        return H264MI_EINVAL;
+    }
+    return H264MI_OK;
+}
+
+// the segments of a header in file order; `sof`, `dri`: where the size and the restart interval go
+static size_t jpeg_header(int quality, bool mono, uint8_t *o, uint32_t *sof, uint32_t *dri) {
+    size_t n = 0;
+    auto put = [&](std::initializer_list<int> b) { for (int v : b) o[n++] = static_cast<uint8_t>(v); };
+    put({0xff, 0xd8, 0xff, 0xe0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});
+    for (int t = 0; t < (mono ? 1 : 2); t++) {
+        put({0xff, 0xdb, 0, 67, t});
+        for (int z = 0; z < 64; z++) o[n++] = static_cast<uint8_t>(jpeg_q(quality, t, jpeg_zigzag(z)));
+    }
+    const int nc = mono ? 1 : 3;
+    put({0xff, 0xc0, 0, 8 + 3 * nc, 8});
+    *sof = static_cast<uint32_t>(n);
+    put({0, 0, 0, 0, nc});
+    for (int c = 0; c < nc; c++) put({c + 1, c == 0 && !mono ? 0x22 : 0x11, c ? 1 : 0});
+    for (int t = 0; t < (mono ? 1 : 2); t++)
+        for (int ac = 0; ac < 2; ac++) {
+            int nv;
+            const uint8_t *bits = jpeg_huff_bits(ac, t), *vals = jpeg_huff_vals(ac, t, &nv);
+            put({0xff, 0xc4, 0, 19 + nv, ac << 4 | t});
+            memcpy(o + n, bits, 16), n += 16;
+            memcpy(o + n, vals, nv), n += nv;
+        }
+    put({0xff, 0xdd, 0, 4});
+    *dri = static_cast<uint32_t>(n);
+    put({0, 0, 0xff, 0xda, 0, 6 + 2 * nc, nc});
+    for (int c = 0; c < nc; c++) put({c + 1, c ? 0x11 : 0x00});
+    put({0, 63, 0});
+    return n;
+}
+static const size_t JPEG_HEADER_BYTES[2] = {629, 334}; // 4:2:0, mono (jpeg_core checks them against jpeg_header)
+
+// MCUs per row, MCUs, MCUs per interval, intervals of a w x h item
+static void jpeg_geometry(const h264mi_jpeg_spec *spec, int w, int h, bool mono, uint32_t *mcus_w, uint32_t *n_mcus, uint32_t *restart, uint32_t *n_int) {
+    const int mcu = mono ? 8 : 16;
+    *mcus_w = static_cast<uint32_t>((w + mcu - 1) / mcu);
+    *n_mcus = *mcus_w * static_cast<uint32_t>((h + mcu - 1) / mcu);
+    *restart = spec->restart_mcus ? static_cast<uint32_t>(spec->restart_mcus) : *mcus_w;
+    *n_int = (*n_mcus + *restart - 1) / *restart;
+}
+
+extern "C" int32_t h264mi_jpeg_size(const h264mi_jpeg_spec *spec, int32_t w, int32_t h, int32_t mono, size_t *header_bytes, size_t *bound_bytes) {
+    if (!spec) return H264MI_EINVAL;
+    TRY(check_jpeg_spec(spec, true));
+    TRY(check_size("JPEG frame", w, h));
+    uint32_t mcus_w, n_mcus, restart, n_int;
+    jpeg_geometry(spec, w, h, mono != 0, &mcus_w, &n_mcus, &restart, &n_int);
+    const size_t hdr = JPEG_HEADER_BYTES[mono ? 1 : 0];
+    if (header_bytes) *header_bytes = hdr;
+    // (the largest: 1024 x 1024 MCUs of 6 blocks, 2 596 274 176 bytes with an interval per MCU)
+    if (bound_bytes) *bound_bytes = (hdr + static_cast<size_t>(2 * ((MI_JPEG_BLOCK_BITS + 7) / 8)) * n_mcus * (mono ? 1 : 6) + static_cast<size_t>(2) * n_int + 15) & ~static_cast<size_t>(15);
+    return H264MI_OK;
+}
+
+// the interval table holds `entries`; on failure everything is as it was
+static int reserve_jpeg_intervals(h264mi_decoder *d, size_t entries) {
+    if (entries <= d->jpeg_ivl_cap) return H264MI_OK;
+    uint32_t *p = nullptr;
+    if (hipMalloc(&p, 4 * entries) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("JPEG: no device memory for the interval table (%zu bytes)", 4 * entries);
+        return H264MI_ENOMEM;
+    }
+    if (d->d_jpeg_ivl) hipFree(d->d_jpeg_ivl); // (waits for the launches that use it)
+    d->dev_bytes += 4 * entries - 4 * d->jpeg_ivl_cap;
+    d->d_jpeg_ivl = p, d->jpeg_ivl_cap = entries;
+    return H264MI_OK;
+}
+
+// descs: source, size, mono and full of every item; the rest is filled in here
+static int jpeg_core(h264mi_decoder *d, const h264mi_jpeg_spec *spec, std::vector<JpegDesc> &descs, size_t slot_bytes, void *dst, size_t cap, size_t *bytes) {
+    const size_t n = descs.size();
+    const size_t res_bytes = (16 * n + 255) & ~static_cast<size_t>(255);
+    uint64_t total_int = 0;
+    for (size_t i = 0; i < n; i++) {
+        JpegDesc &jd = descs[i];
+        if (slot_bytes < JPEG_HEADER_BYTES[jd.mono]) {
+            set_error("JPEG item %zu: slot_bytes %zu is below the header's %zu bytes", i, slot_bytes, JPEG_HEADER_BYTES[jd.mono]);
+            return H264MI_EINVAL;
+        }
+        jpeg_geometry(spec, static_cast<int>(jd.w), static_cast<int>(jd.h), jd.mono != 0, &jd.mcus_w, &jd.n_mcus, &jd.restart, &jd.n_int);
+        jd.slot_off = res_bytes + i * slot_bytes, jd.ivl_base = static_cast<uint32_t>(total_int), jd.pad = 0;
+        total_int += jd.n_int;
+    }
+    if (bytes) *bytes = n ? res_bytes + n * slot_bytes : 0;
+    if (n && res_bytes + n * slot_bytes > cap) return H264MI_ECAPACITY;
+    if (n == 0) return H264MI_OK;
+    if (total_int >= (static_cast<uint64_t>(1) << 31) || n >= (static_cast<size_t>(1) << 31)) {
+        set_error("JPEG: %llu restart intervals in one call: split it", static_cast<unsigned long long>(total_int));
+        return H264MI_EUNSUPPORTED;
+    }
+    TRY(reserve_jpeg_intervals(d, static_cast<size_t>(total_int))); // only now: a call that is refused or too small for its destination allocates nothing
+    std::vector<uint8_t> table(sizeof(JpegParams) + sizeof(JpegDesc) * n);
+    JpegParams P;
+    memset(&P, 0, sizeof P);
+    for (int t = 0; t < 2; t++) {
+        for (int i = 0; i < 64; i++) P.q[t][i] = static_cast<uint16_t>(jpeg_q(spec->quality, t, i));
+        jpeg_huff_codes(0, t, P.dc[t], 12);
+        jpeg_huff_codes(1, t, P.ac[t], 256);
+        P.hdr_len[t] = static_cast<uint32_t>(jpeg_header(spec->quality, t == 1, P.hdr[t], &P.sof_off[t], &P.dri_off[t]));
+        if (P.hdr_len[t] != JPEG_HEADER_BYTES[t]) {
+            set_error("JPEG: internal error: a header of %u bytes", P.hdr_len[t]);
+            return H264MI_EDEVICE;
+        }
+    }
+    P.n_items = static_cast<uint32_t>(n), P.slot_bytes = static_cast<uint32_t>(std::min<size_t>(slot_bytes, 0xfffffff0u)); // (no item is longer: h264mi_jpeg_size)
+    memcpy(table.data(), &P, sizeof P);
+    memcpy(table.data() + sizeof P, descs.data(), sizeof(JpegDesc) * n);
+    DescTables &t = d->tables[OUT_JPEG];
+    const uint8_t *dev;
+    TRY(stage_descs(d, t, table, &dev));
+    const uint32_t total = static_cast<uint32_t>(total_int);
+    hipLaunchKernelGGL(k_jpeg_size, dim3(total), dim3(64), 0, d->stream, dev, d->d_jpeg_ivl, total);
+    hipLaunchKernelGGL(k_jpeg_scan, dim3(static_cast<uint32_t>(n)), dim3(64), 0, d->stream, dev, d->d_jpeg_ivl, static_cast<uint8_t *>(dst));
+    hipLaunchKernelGGL(k_jpeg_write, dim3(total), dim3(64), 0, d->stream, dev, d->d_jpeg_ivl, static_cast<uint8_t *>(dst), total);
+    return fence_launch(d, t);
+}
+
+static int check_jpeg_dst(size_t slot_bytes, const void *dst) {
+    if (slot_bytes % 16) {
+        set_error("JPEG slot_bytes %zu: not a multiple of 16", slot_bytes);
+        return H264MI_EINVAL;
+    }
+    if (reinterpret_cast<uintptr_t>(dst) % 16) {
+        set_error("JPEG destination %p: not aligned to 16 bytes", dst);
+        return H264MI_EINVAL;
+    }
+    return H264MI_OK;
+}
+
+static int jpeg_items(h264mi_decoder *d, const h264mi_jpeg_spec *spec, const h264mi_jpeg_item *items, size_t n, size_t slot_bytes, void *dst, size_t cap, size_t *bytes) {
+    TRY(check_jpeg_spec(spec, true));
+    TRY(check_jpeg_dst(slot_bytes, dst));
+    GUARD(d);
+    std::vector<JpegDesc> descs(n);
+    for (size_t i = 0; i < n; i++) {
+        uint8_t *p;
+        const OutFrame *of;
+        if (frame_ptrs(d, items[i].stream, items[i].frame, &p, &of) != H264MI_OK) {
+            set_error("JPEG item %zu: no frame %d of stream %d in the last executed batch", i, items[i].frame, items[i].stream);
+            return H264MI_EINVAL;
+        }
+        int x0, y0, w, h;
+        crop_rect(of, 1, &x0, &y0, &w, &h);
+        TRY(check_size("JPEG frame", w, h));
+        const size_t W = static_cast<size_t>(of->wmb) * 16, H = static_cast<size_t>(of->hmb) * 16;
+        JpegDesc &jd = descs[i];
+        memset(&jd, 0, sizeof jd);
+        jd.y = reinterpret_cast<uint64_t>(p + static_cast<size_t>(y0) * W + x0);
+        jd.cb = reinterpret_cast<uint64_t>(p + W * H + static_cast<size_t>(y0 / 2) * (W / 2) + x0 / 2), jd.cr = jd.cb + W * H / 4;
+        jd.ystride = static_cast<uint32_t>(W), jd.cstride = static_cast<uint32_t>(W / 2);
+        jd.w = static_cast<uint32_t>(w), jd.h = static_cast<uint32_t>(h), jd.mono = of->mono ? 1 : 0;
+        jd.full = spec->range == H264MI_JPEG_RANGE_FULL || (spec->range == H264MI_JPEG_RANGE_AUTO && of->video_full_range == 0);
+    }
+    return jpeg_core(d, spec, descs, slot_bytes, dst, cap, bytes);
+}
+
+extern "C" int32_t h264mi_items_jpeg_device(h264mi_decoder *d, const h264mi_jpeg_spec *spec, const h264mi_jpeg_item *items, int32_t n, size_t slot_bytes, void *dst, size_t cap,
+                                            size_t *bytes) {
+    if (!d || !spec || !dst || n < 0 || (n > 0 && !items)) return H264MI_EINVAL;
+    return jpeg_items(d, spec, items, static_cast<size_t>(n), slot_bytes, dst, cap, bytes);
+}
+
+extern "C" int32_t h264mi_batch_jpeg_device(h264mi_decoder *d, int32_t stream, const h264mi_jpeg_spec *spec, size_t slot_bytes, void *dst, size_t cap, size_t *bytes) {
+    if (!d || !spec || !dst || !batch_stream_ok(d, stream)) return H264MI_EINVAL;
+    std::vector<h264mi_jpeg_item> items;
+    for (const std::pair<int, int> &f : batch_frames(d, stream)) items.push_back({f.first, f.second});
+    return jpeg_items(d, spec, items.data(), items.size(), slot_bytes, dst, cap, bytes);
+}
+
+extern "C" int32_t h264mi_i420_jpeg_device(h264mi_decoder *d, const h264mi_jpeg_spec *spec, const void *src, int32_t w, int32_t h, int32_t mono, int32_t n, size_t slot_bytes,
+                                           void *dst, size_t cap, size_t *bytes) {
+    if (!d || !spec || !dst || n < 0 || (n > 0 && !src)) return H264MI_EINVAL;
+    TRY(check_jpeg_spec(spec, false));
+    TRY(check_size("JPEG frame", w, h));
+    TRY(check_jpeg_dst(slot_bytes, dst));
+    GUARD(d);
+    std::vector<JpegDesc> descs(static_cast<size_t>(n));
+    const size_t cw = (static_cast<size_t>(w) + 1) / 2, ch = (static_cast<size_t>(h) + 1) / 2;
+    for (size_t i = 0; i < descs.size(); i++) {
+        JpegDesc &jd = descs[i];
+        memset(&jd, 0, sizeof jd);
+        jd.y = reinterpret_cast<uint64_t>(static_cast<const uint8_t *>(src) + i * H264MI_I420_SIZE(w, h));
+        jd.cb = jd.y + static_cast<size_t>(w) * h, jd.cr = jd.cb + cw * ch;
+        jd.ystride = static_cast<uint32_t>(w), jd.cstride = static_cast<uint32_t>(cw);
+        jd.w = static_cast<uint32_t>(w), jd.h = static_cast<uint32_t>(h), jd.mono = mono ? 1 : 0, jd.full = spec->range == H264MI_JPEG_RANGE_FULL;
+    }
+    return jpeg_core(d, spec, descs, slot_bytes, dst, cap, bytes);
 }

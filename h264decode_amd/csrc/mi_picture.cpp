@@ -246,6 +246,7 @@ static int start_picture(h264mi_decoder *d, int si, const h264mi_sps &sps, const
             for (int k = 0; k < sh.n_memory_management_control_operations; k++)
                 if (sh.memory_management_control_operation[k] == 5) of.new_sequence = 1;
         // (a frame picture: both counts are known now; a frame of two fields gets them when it goes out: finish_picture / flush_pending_field)
+        of.mono = sps.chroma_format == 0;
         of.field_coded = sh.field_pic != 0, of.top_foc = sl.fpoc[0], of.bottom_foc = sl.fpoc[1], of.first_parity = !sh.field_pic && sl.fpoc[1] < sl.fpoc[0];
         if (sps.vui_parameters_present && sps.video_signal_type_present) {
             of.video_full_range = sps.video_full_range;

@@ -16,6 +16,7 @@ New (the reference has no pixel type): Decoder -- batched GPU decode to Y/Cb/Cr 
 
 Error behaviour: the reference panics / os.Exit()s on malformed input (h264/server.go:136-143); here
 every failure raises H264MIError carrying the C status code."""
+import builtins
 import ctypes
 
 import numpy as np
@@ -229,6 +230,9 @@ STATS_HISTORY = 1                                     # H264MI_STATS_HISTORY: fl
 # the scalar fields of h264mi_frame_stats in record order: 8 x uint64 at byte 0, 8 x uint32 at byte 64; hist_y[256] follows at byte 96
 STATS_U64 = ("sum_y", "sum_y2", "sum_cb", "sum_cr", "sad_y", "sse_y", "sad_cb", "sad_cr")
 STATS_U32 = ("min_y", "max_y", "changed_y", "has_prev", "w", "h", "gw", "gh")
+JPEG_RANGE_AUTO, JPEG_RANGE_KEEP, JPEG_RANGE_FULL = 0, 1, 2  # H264MI_JPEG_RANGE_*: `range` of Decoder.frames_jpeg / i420_jpeg ("auto", "keep", "full")
+JPEG_TRUNCATED = 1                                    # H264MI_JPEG_TRUNCATED: status of an item that did not fit its slot
+_JPEG_RANGE_NAMES = {"auto": JPEG_RANGE_AUTO, "keep": JPEG_RANGE_KEEP, "full": JPEG_RANGE_FULL}
 _ECAPACITY = -7                                       # H264MI_ECAPACITY
 _DT_NAMES = {"u8": DT_U8, "uint8": DT_U8, "f16": DT_F16, "float16": DT_F16, "bf16": DT_BF16, "bfloat16": DT_BF16, "f32": DT_F32, "float32": DT_F32}
 
@@ -276,6 +280,37 @@ def stats_planes(planes):
 def stats_spec(cell=0, planes=0, thresh=0):
     """An h264mi_stats_spec: the cell size of the grid (0: none; 8, 16, 32, 64), its planes, and the threshold of changed_y."""
     return _lib.StatsSpec(int(cell), stats_planes(planes), int(thresh), 0)
+
+
+def jpeg_spec(quality=90, range="auto", restart_mcus=0):
+    """An h264mi_jpeg_spec: quality 1 .. 100, range "auto" / "keep" / "full" (or a JPEG_RANGE_* value), MCUs per restart interval (0: an MCU row)."""
+    if isinstance(range, str):
+        if range.lower() not in _JPEG_RANGE_NAMES:
+            raise H264MIError(-1, "unknown JPEG range %r (one of %s)" % (range, ", ".join(_JPEG_RANGE_NAMES)))
+        range = _JPEG_RANGE_NAMES[range.lower()]
+    return _lib.JpegSpec(int(quality), int(range), int(restart_mcus), 0)
+
+
+def jpeg_size(w, h, mono=False, quality=90, range="keep", restart_mcus=0):
+    """(header_bytes, bound_bytes) of the JPEG file of a w x h frame (h264mi_jpeg_size): the length of SOI .. SOS, and an upper bound of any file of
+    that shape -- a slot of bound_bytes never truncates."""
+    hb, bb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    check(_lib.load().h264mi_jpeg_size(ctypes.byref(jpeg_spec(quality, range, restart_mcus)), int(w), int(h), int(bool(mono)), ctypes.byref(hb), ctypes.byref(bb)))
+    return hb.value, bb.value
+
+
+def jpeg_quant_table(quality, chroma=False):
+    """The quantisation table of `quality` for luma or chroma, 64 values in natural order (h264mi_jpeg_quant_table)."""
+    q = (ctypes.c_uint16 * 64)()
+    check(_lib.load().h264mi_jpeg_quant_table(int(quality), int(bool(chroma)), q))
+    return list(q)
+
+
+def jpeg_block(samples, q):
+    """The block rule (h264mi_jpeg_block): 64 samples and a table, natural order -> 64 levels."""
+    s, t, lv = (ctypes.c_uint8 * 64)(*[int(v) for v in samples]), (ctypes.c_uint16 * 64)(*[int(v) for v in q]), (ctypes.c_int16 * 64)()
+    check(_lib.load().h264mi_jpeg_block(s, t, lv))
+    return list(lv)
 
 
 def _deint(mode):
@@ -921,6 +956,114 @@ class Decoder:
             res.append(rec)
             at += n
         return res
+
+    jpeg_size = staticmethod(jpeg_size)  # (header_bytes, bound_bytes): the module's function, also by the decoder's name
+
+    def jpeg_items(self, dst_ptr, cap, slot_bytes, items, quality=90, range="auto", restart_mcus=0):
+        """K13 over a list of (stream, frame) items of the last executed batch ("JPEG snapshots" of include/h264mi.h): 16-byte results (bytes, status, w,
+        h), rounded up to 256 bytes, then a slot of slot_bytes per item with the item's file at its start, in the DEVICE buffer at dst_ptr (16-byte
+        aligned).  Returns the number of bytes of the destination."""
+        arr = (_lib.JpegItem * max(len(items), 1))()
+        for a, it in zip(arr, items):
+            a.stream, a.frame = (int(v) for v in it)
+        n = ctypes.c_size_t(0)
+        check(self._L.h264mi_items_jpeg_device(self._h, ctypes.byref(jpeg_spec(quality, range, restart_mcus)), arr, len(items), slot_bytes, dst_ptr, cap, ctypes.byref(n)))
+        return n.value
+
+    def jpeg_batch(self, dst_ptr, cap, slot_bytes, stream=-1, quality=90, range="auto", restart_mcus=0):
+        """K13 for every frame of the last executed batch (of one stream, or of all streams, stream-major): jpeg_items' contract."""
+        n = ctypes.c_size_t(0)
+        check(self._L.h264mi_batch_jpeg_device(self._h, stream, ctypes.byref(jpeg_spec(quality, range, restart_mcus)), slot_bytes, dst_ptr, cap, ctypes.byref(n)))
+        return n.value
+
+    def jpeg_i420(self, dst_ptr, cap, slot_bytes, src_ptr, w, h, n, mono=False, quality=90, range="keep", restart_mcus=0):
+        """K13 for n caller-held tight I420 frames of one size at src_ptr (DEVICE memory, back to back): jpeg_items' contract; "auto" is refused."""
+        got = ctypes.c_size_t(0)
+        check(self._L.h264mi_i420_jpeg_device(self._h, ctypes.byref(jpeg_spec(quality, range, restart_mcus)), src_ptr, int(w), int(h), int(bool(mono)), int(n), slot_bytes,
+                                              dst_ptr, cap, ctypes.byref(got)))
+        return got.value
+
+    def _jpeg_files(self, n, slot_bytes, launch):
+        """launch(indices, dst_ptr, cap, slot_bytes) encodes the items `indices` of n; items reported JPEG_TRUNCATED are encoded once more, with the size
+        they asked for.  Returns the files as bytes, in item order.  Synchronises like side_info."""
+        import torch
+        files, todo = [None] * n, list(range(n))
+        for _ in range(2):
+            if not todo:
+                break
+            head = (16 * len(todo) + 255) & ~255
+            out = torch.empty(head + len(todo) * slot_bytes, dtype=torch.uint8, device="cuda:%d" % self.device)
+            torch.cuda.current_stream(out.device).synchronize()  # whatever still uses a recycled block has finished before K13 writes it
+            got = launch(todo, out.data_ptr(), out.numel(), slot_bytes)
+            assert got == out.numel()
+            self.sync()
+            res = out[:16 * len(todo)].cpu().numpy().view(np.uint32).reshape(-1, 4)
+            again, need = [], 0
+            for k, i in enumerate(todo):
+                if res[k, 1] == 0:
+                    files[i] = out[head + k * slot_bytes:head + k * slot_bytes + int(res[k, 0])].cpu().numpy().tobytes()
+                else:
+                    again.append(i)
+                    need = max(need, int(res[k, 0]))
+            todo, slot_bytes = again, (need + 15) & ~15
+        assert not todo, "an item was truncated in a slot of the size it asked for"
+        return files
+
+    def i420_jpeg(self, tensor, w, h, mono=False, quality=90, range="keep", restart_mcus=0, slot_bytes=None):
+        """The JPEG files (a list of bytes) of caller-held tight I420 frames of size w x h: `tensor` is a contiguous uint8 tensor on the decoder's device,
+        [n, i420_size(w, h)] (for mono the luma is read and the rest ignored).  frames_tensor(..., fmt="i420", size=...) makes such tensors.  The
+        default slot is the header plus w * h / 2 bytes; an item that does not fit is encoded once more with the size it asked for."""
+        import torch
+        assert tensor.dtype == torch.uint8 and tensor.is_contiguous() and tensor.dim() == 2 and tensor.shape[1] == self.i420_size(w, h)
+        if slot_bytes is None:
+            slot_bytes = (jpeg_size(w, h, mono, quality, range, restart_mcus)[0] + w * h // 2 + 15) & ~15
+        stride = tensor.shape[1]
+        torch.cuda.current_stream(tensor.device).synchronize()  # the frames are complete before K13 reads them on the decoder's stream
+
+        def launch(idx, dst, cap, slot):
+            if idx == list(builtins.range(idx[0], idx[0] + len(idx))):  # a contiguous run: one call
+                return self.jpeg_i420(dst, cap, slot, tensor.data_ptr() + idx[0] * stride, w, h, len(idx), mono, quality, range, restart_mcus)
+            sub = tensor[idx].contiguous()
+            torch.cuda.current_stream(tensor.device).synchronize()
+            launch.keep = sub
+            return self.jpeg_i420(dst, cap, slot, sub.data_ptr(), w, h, len(idx), mono, quality, range, restart_mcus)
+        return self._jpeg_files(tensor.shape[0], slot_bytes, launch)
+
+    def frames_jpeg(self, stream=-1, quality=90, range="auto", restart_mcus=0, items=None, size=None, filter="area", slot_bytes=None):
+        """The frames of `stream` (-1: of all streams, stream-major) of the last executed batch, or the (stream, frame) `items`, as baseline JPEG files: a
+        list of bytes, encoded on the device (K13).  range "auto" expands limited-range streams to JPEG's full range and keeps full-range ones.
+        size = (ow, oh) scales every frame first (K8 to I420, `filter` "area" or "bilinear") and encodes the scaled frames as 4:2:0 -- thumbnails.  The
+        default slot is the header plus w * h / 2 bytes of the largest frame; an item that does not fit is encoded once more with the size it asked
+        for."""
+        if items is None:
+            items = [(s, f) for s in (builtins.range(self.max_streams) if stream < 0 else (stream,)) for f in builtins.range(self.frame_count(s))]
+        items = [(int(s), int(f)) for s, f in items]
+        if not items:
+            return []
+        if size is not None:
+            import torch
+            ow, oh = int(size[0]), int(size[1])
+            one = self.i420_size(ow, oh)
+            t = torch.empty((len(items), one), dtype=torch.uint8, device="cuda:%d" % self.device)
+            torch.cuda.current_stream(t.device).synchronize()
+            for k, (s, f) in enumerate(items):
+                self.scale_frame(s, f, t.data_ptr() + k * one, one, "i420", (ow, oh), 0, filter)
+            self.sync()
+            r = jpeg_spec(quality, range, restart_mcus).range
+            full = [r == JPEG_RANGE_FULL or (r == JPEG_RANGE_AUTO and self.frame_colour(s, f)[1] == 0) for s, f in items]
+            files = [None] * len(items)
+            for want in (False, True):
+                idx = [k for k, v in enumerate(full) if v == want]
+                if idx:
+                    sub = t if len(idx) == len(items) else t[idx].contiguous()
+                    for k, data in zip(idx, self.i420_jpeg(sub, ow, oh, False, quality, "full" if want else "keep", restart_mcus, slot_bytes)):
+                        files[k] = data
+            return files
+        if slot_bytes is None:
+            infos = [self.frame_info(s, f) for s, f in items]
+            slot_bytes = max((jpeg_size(fi.width, fi.height, False, quality, range, restart_mcus)[0] + fi.width * fi.height // 2 + 15) & ~15 for fi in infos)
+        return self._jpeg_files(len(items), slot_bytes,
+                                lambda idx, dst, cap, slot: self.jpeg_items(dst, cap, slot, [items[i] for i in idx], quality, range, restart_mcus))
 
     def output_order(self, stream=0):
         """Indices (decoding order) of the stream's frames of the last batch in display order: ascending PicOrderCnt per

@@ -821,6 +821,90 @@ int32_t h264mi_items_stats_device(h264mi_decoder *dec, const h264mi_stats_spec *
 int32_t h264mi_batch_stats_plan(h264mi_decoder *dec, int32_t stream, int32_t flags, h264mi_stats_item *items, int32_t cap, int32_t *n);
 int32_t h264mi_batch_stats_device(h264mi_decoder *dec, int32_t stream, const h264mi_stats_spec *spec, int32_t flags, void *dst_device, size_t cap, size_t *bytes);
 
+/* ---- JPEG snapshots (K13): baseline JPEG files of decoded frames, on the device ----
+ * A thumbnail for a seek bar, an evidence still, the key frame of an index: a frame as a FILE, without moving its samples off the device first.  A frame
+ * is 8-bit 4:2:0 Y / Cb / Cr, which is JPEG's own layout: nothing is converted.  The reference has no such stage (h264/server.go:113-166 stops at the
+ * parsed slice).  The bytes of an item are a function of the source's tight I420 frame S (what h264mi_frame_read(crop = 1) returns), of whether the
+ * stream is monochrome, and of the spec, and of nothing else; this comment is the contract.  All arithmetic is in integers; "div" truncates
+ * (all its operands are non-negative), ">>" is an arithmetic shift.
+ * Geometry.  4:2:0: three components, Y sampled 2 x 2 and Cb, Cr 1 x 1 (component ids 1, 2, 3); an MCU is 16 x 16 luma samples, its blocks in the order
+ *   Y00 Y01 Y10 Y11 Cb Cr (Y01 is the block to the right of Y00, Y10 the one below it).  Monochrome (chroma_format_idc 0): one component, an MCU is one
+ *   8 x 8 block.  MCUs go in raster order, ceil(w / 16) x ceil(h / 16) of them (mono: ceil(w / 8) x ceil(h / 8)).  SOF0 carries the display size
+ *   w x h; odd sizes are allowed.  Samples beyond the display rectangle are the rectangle's last column or row, replicated, per plane -- chroma over its
+ *   ceil(w / 2) x ceil(h / 2) plane -- and never the coded samples outside the crop.
+ * Quantisation tables.  Annex K.1's two tables (K.1 for Y, K.2 for Cb and Cr) scaled the IJG way: quality q is 1 .. 100, sc = 5000 div q for q < 50,
+ *   else 200 - 2q, and Q = clamp((base * sc + 50) div 100, 1, 255).  (These are the tables libjpeg writes for the same quality.)
+ * Block rule (forward DCT and quantisation).  A block s[y][n] (row y, column n) gives x = s - 128.  M[k][n] = rint(16384 * a_k * cos((2n + 1) k pi / 16)),
+ *   a_0 = sqrt(1/8), a_k = 1/2 otherwise: M[0][*] = 5793, M[1] = 8035 6811 4551 1598 -1598 -4551 -6811 -8035, ...
+ *   Rows:     r[y][k] = (sum over n of M[k][n] * x[y][n] + 128) >> 8
+ *   Columns:  c[v][k] = sum over y of M[v][y] * r[y][k]
+ *   Level:    level[v][k] = sign(c) * ((|c| + (Q << 19)) div (Q << 20)), Q the table's entry for (v, k)
+ *   Everything fits int32: the absolute values of a row of M sum to at most 46344, so |r| <= 46344 * 128 >> 8 = 23172, |c| <= 46344 * 23172 < 1.08e9,
+ *   and the addend is at most 255 << 19 < 1.34e8.  |level| <= 1024, and <= 1023 for AC coefficients (their rows of M sum to at most 41990).
+ *   Against an orthonormal floating-point DCT with round-half-away the level never differs by more than 1 (measured over 42 000 blocks -- uniform noise,
+ *   0 / 255 blocks, a narrow Gaussian: in 0.79 % of the coefficients at quality 100, 0.13 % at 90, 0.024 % at 50, 0.016 % at 10).
+ * Entropy coding.  Baseline Huffman with the four tables of Annex K.3.3 (K.3, K.4 for DC; K.5, K.6 for AC), which are written into the file.  DC
+ *   differences are taken per component and start from 0 in every restart interval.  Zigzag order; a run of 16 or more zeros takes ZRL codes; EOB is
+ *   written unless coefficient 63 is non-zero.  Magnitude categories go up to 11 for DC and 10 for AC; a negative value v of category s is written as the
+ *   low s bits of v - 1.
+ * Restart intervals.  restart_mcus = 0: one MCU row per interval; 1 .. 65535: that many MCUs in raster order (an interval may span rows).  DRI is always
+ *   written.  After every interval but the last come pad 1-bits to a byte boundary, then RST(j mod 8) for interval j = 0, 1, ...; the last interval is
+ *   padded the same way and followed by EOI.  Every 0xFF byte of entropy-coded data is followed by 0x00, a byte that padding completed included.
+ * File.  SOI; APP0 "JFIF" 1.01, density 1:1 without units, no thumbnail; DQT 0; DQT 1 (not for mono); SOF0; DHT DC 0, DHT AC 0, DHT DC 1, DHT AC 1 (mono:
+ *   the first two), a segment each; DRI; SOS; the data; EOI.  Luma uses tables 0, chroma tables 1.  The header is 629 bytes (mono: 334).
+ * Sample range, `range` of the spec.  H264MI_JPEG_RANGE_KEEP: samples as they are.  H264MI_JPEG_RANGE_FULL: limited to full range, per plane:
+ *   Y' = (255 * (clamp(Y, 16, 235) - 16) + 109) div 219;  C' = clamp(128 +- (255 * |clamp(C, 16, 240) - 128| + 112) div 224, 0, 255), the sign that of
+ *   C - 128.  H264MI_JPEG_RANGE_AUTO: FULL exactly when the frame's video_full_range is 0 (h264mi_frame_colour).  JFIF can only say BT.601: a BT.709 stream
+ *   keeps its matrix and comes out slightly off in hue in a viewer; matrix conversion is out of scope.
+ * Pure functions (no decoder, no device).  h264mi_jpeg_quant_table: the table of `quality` for luma (chroma = 0) or chroma (1), natural order
+ *   (8 * row + column).  h264mi_jpeg_block: the block rule for 64 samples and a table, both in natural order.  h264mi_jpeg_size: the header's length and
+ *   an upper bound of the length of ANY item of a w x h frame under `spec` (either pointer may be NULL).  The bound: a block takes at most
+ *   1660 bits -- a DC code of at most 11 bits and 11 magnitude bits, and 63 AC coefficients of at most 16 + 10 bits each (a ZRL code replaces 16
+ *   coefficients by 11 bits, and EOB is shorter than a coefficient) -- so with the padding of its interval at most 208 bytes a block; stuffing at most
+ *   doubles every byte; every interval is followed by two marker bytes: bound_bytes = roundup16(header_bytes + 416 * blocks + 2 * intervals), below 2^32
+ *   for every legal size.  H264MI_EINVAL: a null or illegal spec (quality outside 1 .. 100, an unknown range, restart_mcus outside 0 .. 65535, a flag
+ *   bit), w or h outside 1 .. H264MI_SCALE_MAX.
+ * Destination.  n h264mi_jpeg_result records of 16 bytes, rounded up to a multiple of 256 bytes; then n slots of slot_bytes each.  slot_bytes must be a
+ *   multiple of 16 and at least the header's length, dst_device 16-byte aligned (else H264MI_EINVAL).  An item that fits its slot gets status 0 and
+ *   bytes = its length, and its file lies at the start of its slot.  An item that does not fit gets status H264MI_JPEG_TRUNCATED and bytes = the length
+ *   it needs, so that the caller can try again; its slot's content is unspecified, and nothing is written outside its own slot.  A slot of bound_bytes
+ *   never truncates.  w, h: the size SOF0 carries.
+ * h264mi_items_jpeg_device: item i is frame `frame` of stream `stream` of the last executed batch; frames of H264MI_STREAM_DERIVED are legal sources.  The
+ *   discipline is h264mi_items_stats_device's: every item is checked and sized before anything is launched; *bytes receives the total size (also on
+ *   H264MI_ECAPACITY); nothing is written and nothing is launched on failure; n = 0 succeeds with *bytes = 0; the same frame may appear in many items.
+ *   Three launches (K13: sizing, a scan of the interval lengths, writing) on the decoder's stream; the next pass waits for them before it rewrites the
+ *   frames.  The one piece of scratch is the interval table, 4 bytes per restart interval of the call: allocated on first use by a call that launches
+ *   (neither a refused call nor one that returns H264MI_ECAPACITY allocates), grown to the largest call, counted by h264mi_decoder_memory and freed by
+ *   h264mi_decoder_destroy; H264MI_ENOMEM leaves everything as it was.
+ * h264mi_batch_jpeg_device: the same for every frame of `stream` (of all streams for -1, stream-major) in decoding order.
+ * h264mi_i420_jpeg_device: n caller-held tight I420 frames of one size w x h (1 .. H264MI_SCALE_MAX) in device memory, back to back at
+ *   H264MI_I420_SIZE(w, h) stride; with mono != 0 only their luma is read.  H264MI_FMT_I420 of "Scaled output" is the intended source: scale, then
+ *   encode, gives thumbnails without a new resize rule.  H264MI_JPEG_RANGE_AUTO is H264MI_EINVAL here (there is no stream to ask).  The caller orders the
+ *   writes of src_device ahead of the call on the decoder's stream.
+ * Out of scope: progressive and arithmetic coding, optimised Huffman tables, 4:4:4 / 4:2:2 output, EXIF / ICC, the pixel aspect ratio of the VUI, rate
+ *   control to a target size, matrix conversion, MBAFF (as everywhere). */
+#define H264MI_JPEG_RANGE_AUTO 0
+#define H264MI_JPEG_RANGE_KEEP 1
+#define H264MI_JPEG_RANGE_FULL 2
+#define H264MI_JPEG_TRUNCATED 1 /* h264mi_jpeg_result.status */
+typedef struct {
+    int32_t quality, range, restart_mcus, flags;
+} h264mi_jpeg_spec;
+typedef struct {
+    int32_t stream, frame;
+} h264mi_jpeg_item;
+typedef struct {
+    uint32_t bytes, status, w, h;
+} h264mi_jpeg_result;
+int32_t h264mi_jpeg_quant_table(int32_t quality, int32_t chroma, uint16_t q[64]);
+int32_t h264mi_jpeg_block(const uint8_t s[64], const uint16_t q[64], int16_t level[64]);
+int32_t h264mi_jpeg_size(const h264mi_jpeg_spec *spec, int32_t w, int32_t h, int32_t mono, size_t *header_bytes, size_t *bound_bytes);
+int32_t h264mi_items_jpeg_device(h264mi_decoder *dec, const h264mi_jpeg_spec *spec, const h264mi_jpeg_item *items, int32_t n, size_t slot_bytes, void *dst_device,
+                                 size_t cap, size_t *bytes);
+int32_t h264mi_batch_jpeg_device(h264mi_decoder *dec, int32_t stream, const h264mi_jpeg_spec *spec, size_t slot_bytes, void *dst_device, size_t cap, size_t *bytes);
+int32_t h264mi_i420_jpeg_device(h264mi_decoder *dec, const h264mi_jpeg_spec *spec, const void *src_device, int32_t w, int32_t h, int32_t mono, int32_t n,
+                                size_t slot_bytes, void *dst_device, size_t cap, size_t *bytes);
+
 /* Debug / test access to the intermediate macroblock records of a frame (host copy).
  * rec: 128 bytes per MB (layout: h264decode_amd/csrc/mi_types.h struct MbRec). */
 int32_t h264mi_frame_read_mbrecs(h264mi_decoder *dec, int32_t stream, int32_t frame, uint8_t *rec, size_t cap);
