@@ -62,12 +62,36 @@
 #define ENT_CABAC(e) ((e).cabac)
 #define IF_CAVLC(x) (x)
 #endif
+// Fifth build (k_entropy_m.hip: MI_ENT_CABAC = 1 and MI_ENT_MAIN = 1): the CABAC-only kernel for launches in which no picture has the 8x8
+// transform switched on (transform_8x8_mode_flag 0: every Main stream, and the High streams whose PPS leaves it off) and none is monochrome.
+// PicDesc::t8x8_mode and PicDesc::mono read as the constant 0: no transform_size_8x8_flag bins, no Intra8x8 mode loop, no ctxBlockCat 5 in
+// residual_block_cabac and its schedule, no ChromaArrayType 0 arms, and the 8x8 significance maps (Ent::v_maps) are not even loaded.
+#ifndef MI_ENT_MAIN
+#define MI_ENT_MAIN 0
+#endif
+#if MI_ENT_MAIN
+#if !MI_ENT_CABAC
+#error "MI_ENT_MAIN is a refinement of the CABAC-only build"
+#endif
+#define ENT_T8X8_MODE(e) 0
+#define ENT_MONO(e) 0
+#define IF_T8X8(x) 0 /* an expression of the 8x8 transform: not instantiated in the Main build (always the dead arm of an ENT_T8X8_MODE test) */
+#define ENT_CAT5(cat) false
+#else
+#define ENT_T8X8_MODE(e) ((e).t8x8_mode)
+#define ENT_MONO(e) ((e).mono)
+#define IF_T8X8(x) (x)
+#define ENT_CAT5(cat) ((cat) == 5)
+#endif
 #if MI_ENT_B
 #define NL 2
 #define MI_ENT_KERNEL k_entropy_b
 #elif MI_ENT_FMO
 #define NL 1
 #define MI_ENT_KERNEL k_entropy_f
+#elif MI_ENT_MAIN
+#define NL 1
+#define MI_ENT_KERNEL k_entropy_m
 #elif MI_ENT_CABAC
 #define NL 1
 #define MI_ENT_KERNEL k_entropy_c
@@ -184,7 +208,9 @@ struct Ent {
     int wk_valid;            // per lane: 1 = the lane belongs to the category's own contexts (an int, not a bool: a lane predicate kept in a scalar register pair costs
                              // three mask instructions per residual block to carry around the loop)
     uint32_t v_rlps, v_trans; // lane p: rangeTabLPS[p][0..3] / next state after an LPS for valMPS 0
+#if !MI_ENT_MAIN
     uint32_t v_maps;         // lane i: sig8x8[i] | last8x8[i] << 8 | zigzag8[i] << 16 | zigzag4[i & 15] << 24
+#endif
     uint32_t v_pos;          // lane i: where the coefficient of scan index i goes, one byte per position mode: zigzag4[i & 15] | zigzag4[(i + 1) & 15] << 8 (AC blocks: scan index
                              // i is coefficient i + 1) | zigzag8[i] << 16 | i << 24 (field pictures: the field scans)
     uint32_t v_cat0, v_cat1; // lane ctxBlockCat: packed block-category parameters (cat_word0/1)
@@ -196,7 +222,7 @@ struct Ent {
     uint32_t qpw0, qpw1;     // QP_Y << 16 | QP_C(Cb) << 24 and QP_C(Cr) of the current QP_Y: the record's bytes 2..4 (set_qp)
     int cabac, islice, wmb, hmb;
     int mono;                // chroma_format_idc 0 (h264/sps.go:226-243): no chroma syntax; the reconstruction's chroma planes are 128 by construction
-    int cip, t8x8_mode, cqp_off0, cqp_off1, nref;
+    int cip, t8x8_mode, cqp_off0, cqp_off1, nref; // (mono, t8x8_mode: read through ENT_MONO / ENT_T8X8_MODE, constants in the Main build)
     uint64_t mb_base;
 #if MI_ENT_B
     int nref1, direct_spatial, d8inf, col_short, direct8; // direct8: 8x8 blocks of the current macroblock predicted in direct mode
@@ -536,7 +562,7 @@ FI int cabac_residual(Ent &e, int16_t *dst, int cat_, int cbf_inc) {
         const int home = static_cast<int>((c1n >> (10 * (grp > 2 ? 2 : grp))) & 1023) + (l < 32 ? li : l - 32);
         // lanes outside the category's own context ranges would hold copies of other categories' states and must never
         // be written back (for 8x8 blocks ctxIdx 417 appears in both the sig and the last group)
-        const int nsig = cat == 5 ? 15 : static_cast<int>(c0n & 255) - 1, nlast = static_cast<int>((c0n >> 24) & 15);
+        const int nsig = ENT_CAT5(cat) ? 15 : static_cast<int>(c0n & 255) - 1, nlast = static_cast<int>((c0n >> 24) & 15);
         e.wk_valid = (grp == 0 ? li < nsig : (grp == 1 ? li < nlast : l < 42)) ? 1 : 0;
         e.wk_home = home < 464 ? home : 463;
         LDS_SYNC(); // the scatter above may alias the gather below
@@ -547,12 +573,12 @@ FI int cabac_residual(Ent &e, int16_t *dst, int cat_, int cbf_inc) {
     // the lane tables of the deferred significance map (cabac_decide_once, wk_advance), gathered while coded_block_flag is decoded: that bin reads cb, and the
     // wk states stand still until the map is over
     const uint32_t rlw = wk_lane_table(e, e.v_rlps), tr = wk_lane_table(e, e.v_trans);
-    if (cat != 5 && !BIN_B(e, 64 + ((c0 >> 8) & 255) + cbf_inc)) {
+    if (!ENT_CAT5(cat) && !BIN_B(e, 64 + ((c0 >> 8) & 255) + cbf_inc)) {
         MI_R(e, 2);
         return 0;
     }
     const int last = static_cast<int>(c0 & 255) - 1; // maxNumCoeff - 1
-    const bool is8 = cat == 5;
+    const bool is8 = ENT_CAT5(cat);
     // the significant coefficients as a bit set with the HIGHEST frequency in the LOWEST bit (coefficient i = bit 63 - i): the levels come highest
     // frequency first (7.3.5.3.3), which is then find-first-one / clear-that-bit
     uint64_t sig = 0;
@@ -562,6 +588,7 @@ FI int cabac_residual(Ent &e, int16_t *dst, int cat_, int cbf_inc) {
     // structurizer more than the select), running off the end means the final coefficient is significant by inference.
     // (ctxIdxInc of a 4x4 / 2x2 block is the scan position itself: Min(numDecod / NumC8x8, 2) only bites with 4:2:2 chroma DC blocks.)
     uint64_t used = 0, ones = 0;
+#if !MI_ENT_MAIN
     if (is8) { // (Table 9-43 maps several scan positions to one context: the transition stays immediate)
         for (i = 0; i < last; i++) {
             const uint32_t m = RDL(e.v_maps, i);
@@ -570,7 +597,9 @@ FI int cabac_residual(Ent &e, int16_t *dst, int cat_, int cbf_inc) {
                 if (BIN_W(e, 16 + ((m >> 8) & 255))) i = 64;
             }
         }
-    } else {
+    } else
+#endif
+    {
         for (i = 0; i < last; i++) {
             if (BIN_1(e, rlw, i)) {
                 sig |= 0x8000000000000000ull >> i;
@@ -774,8 +803,9 @@ FI uint32_t step_word(int st) {
     }
     return 0;
 }
-FI void parse_residual_cabac(Ent &e, int cbp_luma, int cbp_chroma, int t8x8) {
+FI void parse_residual_cabac(Ent &e, int cbp_luma, int cbp_chroma, int t8x8_) {
     Shared *s = e.s;
+    const int t8x8 = IF_T8X8(t8x8_); // (the Main build: no 8x8 term in the step and category words)
     const int i16 = e.cur_type == MBT_I16x16;
     // the neighbourhood as one flag per LANE (lane = bit position of the layout above): a block's two context bits are two v_readlane with the
     // step word as lane select, a coded block sets its lane -- the scalar ALU, the scarce unit, does none of it
@@ -795,12 +825,12 @@ FI void parse_residual_cabac(Ent &e, int cbp_luma, int cbp_chroma, int t8x8) {
         const uint32_t d = RDL(e.v_step, step);
         const int cat = static_cast<int>((cats >> ((d >> 24) & 12u)) & 15);
         const int own = static_cast<int>((d >> 12) & 63);
-        const int dst = cat == 5 ? (step - 1) * 16 : static_cast<int>((d >> 18) & 255) * 4;
+        const int dst = ENT_CAT5(cat) ? (step - 1) * 16 : static_cast<int>((d >> 18) & 255) * 4;
         const int inc = static_cast<int>(RDL(vnz, d) + 2 * RDL(vnz, d >> 6)); // (the lane select is taken modulo 64)
         slide_window(e); // (see cavlc: a macroblock_layer() beyond A.3.1's 3200 bits must not run off the window; one block is at most 92 words)
         if (cabac_residual(e, s->coef + dst, cat, inc)) {
             // the block's lane -- an 8x8 block stands for its four 4x4 positions: own, own + 1, own + 6, own + 7 -- through a mask made on the scalar side
-            const uint64_t m = (cat == 5 ? 0xC3ull : 1ull) << own;
+            const uint64_t m = (ENT_CAT5(cat) ? 0xC3ull : 1ull) << own;
             asm("v_cndmask_b32_e64 %0, %0, 1, %1" : "+v"(vnz) : "s"(m));
         }
     }
@@ -1381,7 +1411,7 @@ FI void decode_mb(Ent &e, int skipped) {
             i16mode = (it - 1) & 3;
             cbp_chroma = ((it - 1) >> 2) % 3;
             cbp_luma = it >= 13 ? 15 : 0;
-            if (cbp_chroma && e.mono) e.err = 25, cbp_chroma = 0; // (no such mb_type in a monochrome stream)
+            if (cbp_chroma && ENT_MONO(e)) e.err = 25, cbp_chroma = 0; // (no such mb_type in a monochrome stream)
         } else if (it == 25)
             type = MBT_IPCM;
         else {
@@ -1397,7 +1427,7 @@ FI void decode_mb(Ent &e, int skipped) {
             if (cabac) pos -= static_cast<uint32_t>(RFL(e.avail));
             seek(e, (pos + 7) & ~7u);
             uint32_t *pcm = reinterpret_cast<uint32_t *>(s->coef);
-            for (int i = 0; i < 96; i++) pcm[i] = (e.mono && i >= 64) ? 0x80808080u : __builtin_bswap32(get_bits(e, 32)); // 384 sample bytes in stream order (monochrome: 256; chroma 128)
+            for (int i = 0; i < 96; i++) pcm[i] = (ENT_MONO(e) && i >= 64) ? 0x80808080u : __builtin_bswap32(get_bits(e, 32)); // 384 sample bytes in stream order (monochrome: 256; chroma 128)
             if (cabac) cabac_start(e);
             for (int i = 0; i < 16; i++) {
                 s->nnz_c[GI(i & 3, i >> 2)] = 16, s->ref_c[0][GI(i & 3, i >> 2)] = -1;
@@ -1541,12 +1571,12 @@ FI void decode_mb(Ent &e, int skipped) {
 #endif
             } else {
                 // ---- intra: transform_size_8x8_flag, prediction modes, intra_chroma_pred_mode ----
-                if (type == MBT_I4x4 && e.t8x8_mode) {
-                    t8x8 = cabac ? BINI_T8(e, (a.ok() && a.t8x8()) + (b.ok() && b.t8x8())) : IF_CAVLC(static_cast<int>(get_bit(e)));
+                if (type == MBT_I4x4 && ENT_T8X8_MODE(e)) {
+                    t8x8 = IF_T8X8(cabac ? BINI_T8(e, (a.ok() && a.t8x8()) + (b.ok() && b.t8x8())) : IF_CAVLC(static_cast<int>(get_bit(e))));
                     if (t8x8) type = MBT_I8x8, e.cur_type = type;
                 }
-                if (type == MBT_I4x4 || type == MBT_I8x8) {
-                    const int n = type == MBT_I8x8 ? 4 : 16;
+                if (type == MBT_I4x4 || IF_T8X8(type == MBT_I8x8)) {
+                    const int n = IF_T8X8(type == MBT_I8x8) ? 4 : 16; // (the Main build: the sixteen 4x4 modes only)
                     for (int i = 0; i < n; i++) {
                         int bx, by;
                         if (n == 4)
@@ -1571,7 +1601,7 @@ FI void decode_mb(Ent &e, int skipped) {
                     }
                     if (LANE < 30) s->ipm_c[LANE] = static_cast<int8_t>(e.v_ipm); // for the record / neighbour write-out
                 }
-                if (e.mono)
+                if (ENT_MONO(e))
                     chroma_mode = 0; // ChromaArrayType 0: no intra_chroma_pred_mode (K3 predicts the DC of planes that are 128 everywhere)
                 else if (cabac) {
                     int inc = (a.ok() && MB_IS_INTRA(a.type()) && a.type() != MBT_IPCM && a.chroma_mode() != 0) +
@@ -1604,18 +1634,19 @@ FI void decode_mb(Ent &e, int skipped) {
                         cbp |= BINI_B(e, 73 + (!ca) + 2 * (!cb)) << b8;
                     }
                     int ca = a.ok() && (a.type() == MBT_IPCM || (a.cbp() >> 4) != 0), cb = b.ok() && (b.type() == MBT_IPCM || (b.cbp() >> 4) != 0);
-                    if (!e.mono && BIN_B(e, 77 + ca + 2 * cb)) { // (ChromaArrayType 0: the prefix only)
+                    if (!ENT_MONO(e) && BIN_B(e, 77 + ca + 2 * cb)) { // (ChromaArrayType 0: the prefix only)
                         ca = a.ok() && (a.type() == MBT_IPCM || (a.cbp() >> 4) == 2);
                         cb = b.ok() && (b.type() == MBT_IPCM || (b.cbp() >> 4) == 2);
                         cbp |= (1 + BINI_B(e, 77 + 4 + ca + 2 * cb)) << 4;
                     }
                 } else {
                     uint32_t k = IF_CAVLC(get_ue(e));
-                    if (k > (e.mono ? 15u : 47u)) e.err = 23, k = 0;
-                    if (e.mono) k += 48; // the ChromaArrayType 0 column of Table 9-4 (h264/bit_reader.go:118-135) sits behind the 48 entries of the other
+                    if (k > (ENT_MONO(e) ? 15u : 47u)) e.err = 23, k = 0;
+                    if (ENT_MONO(e)) k += 48; // the ChromaArrayType 0 column of Table 9-4 (h264/bit_reader.go:118-135) sits behind the 48 entries of the other
                     cbp = IF_CAVLC(RFL(static_cast<int>(MB_IS_INTRA(type) ? e.tab->me_intra[k] : e.tab->me_inter[k])));
                 }
                 cbp_luma = cbp & 15, cbp_chroma = cbp >> 4;
+#if !MI_ENT_MAIN
                 if (cbp_luma && e.t8x8_mode && MB_IS_INTER(type)) {
 #if MI_ENT_B
                     const int all8 = no_sub8;
@@ -1626,6 +1657,7 @@ FI void decode_mb(Ent &e, int skipped) {
 #endif
                     if (all8) t8x8 = cabac ? BINI_T8(e, (a.ok() && a.t8x8()) + (b.ok() && b.t8x8())) : IF_CAVLC(static_cast<int>(get_bit(e)));
                 }
+#endif
             }
             // ---- mb_qp_delta + residual ----
             if (cbp_luma || cbp_chroma || type == MBT_I16x16) {
@@ -1865,7 +1897,9 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
     }
     // coefficient scans of the picture (8.5.6, 8.5.7): zig-zag, or the field scan in a field picture (h264/slice.go:867-872 field_pic_flag)
     const uint8_t *scan4 = pd->field ? tab->fieldscan4 : tab->zigzag4, *scan8 = pd->field ? tab->fieldscan8 : tab->zigzag8;
+#if !MI_ENT_MAIN
     e.v_maps = (pd->field ? tab->sig8x8_field[l] : tab->sig8x8[l]) | (tab->last8x8[l] << 8) | (scan8[l] << 16) | (static_cast<uint32_t>(scan4[l & 15]) << 24);
+#endif
     e.v_pos = scan4[l & 15] | (scan4[(l + 1) & 15] << 8) | (scan8[l] << 16) | (static_cast<uint32_t>(l) << 24);
     e.mono = RFL(static_cast<int>(pd->mono));
     e.v_cat0 = cat_word0(l), e.v_cat1 = cat_word1(l, pd->field != 0); // (CAVLC slices: v_cat0 is replaced by the run_before tables below, one entry per lane)

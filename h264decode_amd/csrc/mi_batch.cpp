@@ -341,7 +341,9 @@ static void order_slices_by_level(Stage &g) {
     for (int l = 1; l < n_levels; l++) g.levels[l].first = g.levels[l - 1].first + g.levels[l - 1].n;
     int n_mode[2] = {0, 0}; // level 0 by entropy coding mode: CAVLC, CABAC slices
     for (int i = 0; i < g.levels[0].n; i++) n_mode[g.h_pics[g.h_slices[i].pic_idx].cabac != 0]++;
-    g.ent_kernel = hook_entropy_kernel(mi_entropy_kernel_choice(n_mode[1], n_mode[0], !g.fmo_pics.empty()));
+    int n_t8x8_mono = 0; // pictures of the batch with the 8x8 transform switched on, or monochrome: none in a batch of Main streams
+    for (int p = 0; p < g.n_pics; p++) n_t8x8_mono += g.h_pics[p].t8x8_mode != 0 || g.h_pics[p].mono != 0;
+    g.ent_kernel = hook_entropy_kernel(mi_entropy_kernel_choice(n_mode[1], n_mode[0], !g.fmo_pics.empty(), n_t8x8_mono));
 }
 
 // Error concealment.  Behind the slices of the batch one SliceDesc per picture -- what MbRec::slice_idx of a concealed macroblock names, so that
@@ -564,7 +566,7 @@ static int execute_stage(h264mi_decoder *d, int stage_idx, bool exclusive) {
             if (lv > 0) fence();
             if (n > 0) {
                 if (lv == 0)
-                    hipLaunchKernelGGL(g.ent_kernel == MI_ENT_K_FMO ? k_entropy_f : (g.ent_kernel == MI_ENT_K_CABAC ? k_entropy_c : k_entropy), dim3(n), dim3(64), lds_pad, st, g.d_slices, g.d_pics, g.d_bits, d->d_tables, mbrec, coef, d->d_pool_head + set,
+                    hipLaunchKernelGGL(g.ent_kernel == MI_ENT_K_FMO ? k_entropy_f : (g.ent_kernel == MI_ENT_K_MAIN ? k_entropy_m : (g.ent_kernel == MI_ENT_K_CABAC ? k_entropy_c : k_entropy)), dim3(n), dim3(64), lds_pad, st, g.d_slices, g.d_pics, g.d_bits, d->d_tables, mbrec, coef, d->d_pool_head + set,
                                        pool_blocks, g.d_status, d->d_toprows[set], g.wmb_max, static_cast<uint32_t>(first));
                 else
                     hipLaunchKernelGGL(k_entropy_b, dim3(n), dim3(64), 0, st, g.d_slices, g.d_pics, g.d_bits, d->d_tables, mbrec, coef, d->d_pool_head + set,

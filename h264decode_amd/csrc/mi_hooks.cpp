@@ -27,9 +27,11 @@ void hook_create_entropy(h264mi_decoder *d, int *ent_cus) {
 void hook_create_k5(h264mi_decoder *d) { // fewer wavefronts per picture in k_deblock
     if (const char *e = getenv("H264MI_K5_WAVES")) d->k5_max_waves = std::min(std::max(atoi(e), 1), MI_DEBLOCK8_MAX_WAVES);
 }
-int hook_entropy_kernel(int chosen) { // the general kernel for CABAC launches too, as before there was a CABAC-only build
+int hook_entropy_kernel(int chosen) { // 1: the general kernel for CABAC launches too, as before there was a CABAC-only build; 2: k_entropy_c for Main launches, as before there was a Main build
     const char *e = getenv("H264MI_ENT_GENERIC");
-    return e && atoi(e) && chosen == MI_ENT_K_CABAC ? MI_ENT_K_GENERAL : chosen;
+    const int v = e ? atoi(e) : 0;
+    if (v == 2) return chosen == MI_ENT_K_MAIN ? MI_ENT_K_CABAC : chosen;
+    return v && (chosen == MI_ENT_K_CABAC || chosen == MI_ENT_K_MAIN) ? MI_ENT_K_GENERAL : chosen;
 }
 int hook_dbprep_kernel(int chosen) { // the general kernel everywhere, as before there was a kernel for I / P launches
     const char *e = getenv("H264MI_DBPREP_GENERIC");
@@ -123,9 +125,14 @@ extern "C" int32_t h264mi_internal_deblock_plan(int32_t wmb, int32_t hmb, int32_
 }
 
 // Not part of the public ABI: which I/P entropy kernel a level 0 of n_cabac CABAC and n_cavlc CAVLC slices runs on (mi_entropy_kernel_choice):
-// 0 k_entropy, 1 k_entropy_f, 2 k_entropy_c.
+// 0 k_entropy, 1 k_entropy_f, 2 k_entropy_c.  (The choice as far as the coding mode and the slice groups decide it: of the two CABAC-only builds it names k_entropy_c.)
 extern "C" int32_t h264mi_internal_entropy_kernel_choice(int32_t n_cabac, int32_t n_cavlc, int32_t slice_groups) {
-    return mi_entropy_kernel_choice(n_cabac, n_cavlc, slice_groups != 0);
+    const int k = mi_entropy_kernel_choice(n_cabac, n_cavlc, slice_groups != 0, 0);
+    return k == MI_ENT_K_MAIN ? MI_ENT_K_CABAC : k;
+}
+// The whole choice: n_t8x8_mono pictures of the batch have the 8x8 transform switched on or are monochrome.  3 k_entropy_m.
+extern "C" int32_t h264mi_internal_entropy_kernel_choice4(int32_t n_cabac, int32_t n_cavlc, int32_t slice_groups, int32_t n_t8x8_mono) {
+    return mi_entropy_kernel_choice(n_cabac, n_cavlc, slice_groups != 0, n_t8x8_mono);
 }
 
 // Not part of the public ABI: which k_dbprep kernel runs on a level's pictures, n_has_b of them with B slices and n_save_col leaving a ColRec array
@@ -450,7 +457,9 @@ extern "C" int32_t h264mi_internal_dpb_trace(h264mi_decoder *d, int32_t stream, 
         put_range("prep", level_prep(l));
         put(" colsave_n=%u prep_kernel=%d\n", level_colsave_n(l), level_prep_kernel(l));
     }
-    put("tables ent_kernel=%d wmb_max=%d hmb_max=%d mbs_max=%d n_bext=%d", g.ent_kernel, g.wmb_max, g.hmb_max, g.mbs_max, g.n_bext);
+    // (ent_kernel: the choice as far as coding mode and slice groups decide it, as the three-argument entry above -- this trace pins picture management
+    // and the batch's tables against tests/golden/dpb_trace_md5.json, not which of the two CABAC-only builds runs; h264mi_internal_entropy_kernel_choice4 says that)
+    put("tables ent_kernel=%d wmb_max=%d hmb_max=%d mbs_max=%d n_bext=%d", g.ent_kernel == MI_ENT_K_MAIN ? MI_ENT_K_CABAC : g.ent_kernel, g.wmb_max, g.hmb_max, g.mbs_max, g.n_bext);
     put_list("fmo_pics", g.fmo_pics.data(), static_cast<int>(g.fmo_pics.size()));
     put("%s", " grey=");
     for (size_t i = 0; i < g.grey.size(); i++) put(i ? ",%u:%u:%u:%ux%u" : "%u:%u:%u:%ux%u", g.grey[i].stream, g.grey[i].slot, g.grey[i].parity, g.grey[i].w, g.grey[i].h);

@@ -12,6 +12,9 @@ extern "C" __global__ void k_entropy_f(const SliceDesc *slices, const PicDesc *p
 // the same with the entropy coding mode fixed to CABAC (k_entropy_c.hip): for launches whose slices are all CABAC-coded
 extern "C" __global__ void k_entropy_c(const SliceDesc *slices, const PicDesc *pics, const uint8_t *bitstream, const DevTables *tab, MbRec *mbrec, int16_t *coefs,
                                        uint32_t *pool_head, uint32_t pool_blocks, uint32_t *status, uint32_t *toprows, int wmb_max, uint32_t slice_base);
+// the CABAC-only kernel with transform_8x8_mode = 0 and 4:2:0 fixed as well (k_entropy_m.hip): for all-CABAC launches of batches without an 8x8 or monochrome picture
+extern "C" __global__ void k_entropy_m(const SliceDesc *slices, const PicDesc *pics, const uint8_t *bitstream, const DevTables *tab, MbRec *mbrec, int16_t *coefs,
+                                       uint32_t *pool_head, uint32_t pool_blocks, uint32_t *status, uint32_t *toprows, int wmb_max, uint32_t slice_base);
 // the same for B slices (k_entropy_b.hip): two reference lists, direct prediction from the ColRec array of RefPicList1[0]; toprows = 18 dwords per column
 extern "C" __global__ void k_entropy_b(const SliceDesc *slices, const PicDesc *pics, const uint8_t *bitstream, const DevTables *tab, MbRec *mbrec, int16_t *coefs,
                                        uint32_t *pool_head, uint32_t pool_blocks, uint32_t *status, uint32_t *toprows, int wmb_max, uint32_t slice_base,
@@ -128,11 +131,14 @@ static inline void mi_deblock8_plan(int wmb, int hmb, int *nwaves, int *ring, in
 }
 // Which build of the I/P entropy kernel level 0 of a batch runs on: the slice-group build if a picture of the batch has slice groups (it reads the
 // mode per slice); else the CABAC-only build if every slice of the level is CABAC-coded; else -- one CAVLC slice is enough -- the general one.
-// (An empty level 0, a batch of B slices only, launches nothing: any id will do.)
-enum { MI_ENT_K_GENERAL = 0, MI_ENT_K_FMO = 1, MI_ENT_K_CABAC = 2 };
-static inline int mi_entropy_kernel_choice(int n_cabac, int n_cavlc, bool slice_groups) {
+// (An empty level 0, a batch of B slices only, launches nothing: any id will do.)  Of the CABAC-only builds the Main one, when no picture of the batch
+// has the 8x8 transform switched on (PicDesc::t8x8_mode) or is monochrome (n_t8x8_mono, known when the batch is prepared like the slices' modes): every
+// Main stream, and every High stream whose PPS leaves transform_8x8_mode_flag off; one such picture sends the launch to the CABAC-only kernel.
+enum { MI_ENT_K_GENERAL = 0, MI_ENT_K_FMO = 1, MI_ENT_K_CABAC = 2, MI_ENT_K_MAIN = 3 };
+static inline int mi_entropy_kernel_choice(int n_cabac, int n_cavlc, bool slice_groups, int n_t8x8_mono) {
     if (slice_groups) return MI_ENT_K_FMO;
-    return (n_cavlc == 0 && n_cabac > 0) ? MI_ENT_K_CABAC : MI_ENT_K_GENERAL;
+    if (n_cavlc != 0 || n_cabac <= 0) return MI_ENT_K_GENERAL;
+    return n_t8x8_mono == 0 ? MI_ENT_K_MAIN : MI_ENT_K_CABAC;
 }
 // Which k_dbprep kernel runs on the pictures complete with a level: the one-lane-per-macroblock kernel if none of them has B slices (n_has_b) and none
 // leaves a ColRec array (n_save_col); else -- one such picture is enough -- the general one.

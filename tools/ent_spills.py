@@ -5,7 +5,7 @@ Input: the `hipcc -S -gline-tables-only` assembly of k_entropy.hip or of one of 
 attributed to the source line of its .loc (the innermost inlined callee, as tools/isa_lines.py does), and the line to a region of
 k_entropy.hip: the regions are named by the `// @region <name>` lines of that file, each running to the next one.  The compiler spills
 scalar registers into the lanes of a VGPR that it names itself in the assembly ("SGPR spill to VGPR lane"); a spill is a v_writelane_b32
-to that register, a reload a v_readlane_b32 from it.
+to that register, a reload a v_readlane_b32 from it.  Instructions without a source line (`.loc` with line 0) are counted in a row of their own.
 
 Usage: ent_spills.py file.s [k_entropy.hip]
    or: hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 --cuda-device-only -S -gline-tables-only k_entropy_c.hip -o - | ent_spills.py -"""
@@ -15,6 +15,9 @@ import re
 import sys
 
 SOURCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "h264decode_amd", "csrc", "k_entropy.hip")
+# `.loc <file> 0`: an instruction the compiler gives no line (block glue, loop exits, merged code).  It belongs to no region of the source -- least of all to
+# 'other', the lines in front of the first marker -- and gets a row of its own, behind the regions.
+NO_LINE = "(no source line)"
 _INSN = re.compile(r"\s+((?:[sv]|ds|global|buffer|flat|scratch)_[a-z0-9_]+)\s*(.*)")
 
 
@@ -50,6 +53,7 @@ def table(asm_text, source=SOURCE):
     ours = {n for n, f in files.items() if os.path.basename(f) == src_name}
     sv = ["v" + v[4:] for v in spill_vgprs(asm_text)]
     out = collections.OrderedDict((n, collections.Counter()) for _, n in regs)
+    out[NO_LINE] = collections.Counter()
     foreign = 0
     cur = None
     for line in asm_text.splitlines():
@@ -63,7 +67,7 @@ def table(asm_text, source=SOURCE):
         if cur[0] not in ours:
             foreign += 1
             continue
-        c = out[region_of(cur[1], regs)]
+        c = out[region_of(cur[1], regs) if cur[1] else NO_LINE]
         c["insts"] += 1
         op, args = m.group(1), [a.strip() for a in m.group(2).split(";")[0].split(",")]
         if op == "v_writelane_b32" and args[0] in sv:
