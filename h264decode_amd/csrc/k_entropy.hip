@@ -83,6 +83,9 @@
 #define IF_T8X8(x) (x)
 #define ENT_CAT5(cat) ((cat) == 5)
 #endif
+// The two CABAC-only I/P builds (k_entropy_c, k_entropy_m) read mb_type in front of the neighbour caches and send a P_L0_16x16 macroblock
+// through p16_fast() (see decode_mb); the other three builds keep the one road through fill_caches() and decode_mb(), token for token.
+#define MI_ENT_P16 (MI_ENT_CABAC && !MI_ENT_B && !MI_ENT_FMO)
 #if MI_ENT_B
 #define NL 2
 #define MI_ENT_KERNEL k_entropy_b
@@ -271,6 +274,17 @@ struct Ent {
 #define MI_S(e, k) ((void)0)
 #endif
 #define RFL(x) __builtin_amdgcn_readfirstlane(x)
+// MI_ENT_P16 builds: a slice constant as it is read where it is tested -- the opaque move keeps the compiler from working the test out once per
+// slice and carrying its lane mask, a spilled register pair, through the macroblock loop ("NOT worth doing" item 7: worth doing
+// once p16_fast needs the registers)
+#if MI_ENT_P16
+FI int fresh(int x) {
+    asm volatile("" : "+s"(x));
+    return x;
+}
+#else
+#define fresh(x) (x)
+#endif
 #define RDL(v, i) static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), static_cast<int>(i)))
 // v_writelane_b32: clang has no builtin for it, the LLVM intrinsic is bound by name
 extern "C" __device__ int mi_writelane(int val, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
@@ -524,6 +538,10 @@ FI void set_qp(Ent &e, int qp) { // QP_Y and the two chroma QPs it maps to (8.5.
     e.qp = qp;
     e.qpw0 = static_cast<uint32_t>(qp) << 16 | RDL(e.v_qpc, min(max(qp + e.cqp_off0, 0), 51)) << 24;
     e.qpw1 = RDL(e.v_qpc, min(max(qp + e.cqp_off1, 0), 51));
+#if MI_ENT_P16
+    VGPR(e.qpw0);
+    VGPR(e.qpw1); // only lanes read them (the record's first two words): kept on the vector side, they are not spilled around the residual
+#endif
 }
 // ------------------------------------------------------------------ neighbour MBs
 FI bool nb_ok(const Ent &e, int i) { return e.s->nb[i].type != MBT_NONE && (i != NB_TOP + 1 || e.mbx + 1 < e.wmb); } // macroblock D, A, B, C available
@@ -1027,7 +1045,7 @@ FI uint32_t build_role(int l) {
 FI void fill_caches(Ent &e) {
     Shared *s = e.s; // (e.aw / e.bw -- the first dword of the left / upper entry -- were read by the macroblock loop: the skip decision needs only them)
     const bool a_ok = (e.aw & 255) != 0, b_ok = (e.bw & 255) != 0;
-    const int cip = e.cip;
+    const int cip = fresh(e.cip);
     int l = LANE;
     OPAQUE(l); // keeps lane-dependent addresses from being hoisted out of the macroblock loop and spilled
     const uint32_t role = s->role[l], off = role & NO_SRC;
@@ -1211,7 +1229,41 @@ FI void read_ref_idx(Ent &e, const int L, int bx, int by, int w, int h, int nref
         LDS_SYNC();
     }
 }
-// mvd_lX of a partition (se(v) or UEG3 9.3.2.3 / 9.3.3.1.1.7), prediction 8.4.1.3, result into the caches
+// one component of mvd_lX, CABAC: UEG3, uCoff 9, signed (9.3.2.3, 9.3.3.1.1.7); `sum`: the neighbours' absolute values added up
+FI int read_mvd_cabac(Ent &e, int comp, int sum) {
+    const int base = comp ? 47 : 40;
+    int v = 0;
+    if (BIN_A(e, base + (sum > 2) + (sum > 32))) {
+        int ctx = base + 3;
+        v = 1;
+        while (v < 9 && BIN_A(e, ctx)) {
+            if (v < 4) ctx++;
+            v++;
+        }
+        if (v >= 9) v += cabac_egk(e, 3);
+        if (cabac_bypass(e)) v = -v;
+    }
+    return v;
+}
+// coded_block_pattern, CABAC (9.3.3.1.1.4): a = left, b = upper macroblock
+FI int read_cbp_cabac(Ent &e, const Nb a, const Nb b) {
+    const int cbp_a = a.ok() ? (a.type() == MBT_IPCM ? 0x2F : a.cbp()) : 0x0F;
+    const int cbp_b = b.ok() ? (b.type() == MBT_IPCM ? 0x2F : b.cbp()) : 0x0F;
+    int cbp = 0;
+    for (int b8 = 0; b8 < 4; b8++) {
+        int ca = (b8 & 1) ? (cbp >> (b8 - 1)) & 1 : (cbp_a >> (b8 + 1)) & 1;
+        int cb = (b8 & 2) ? (cbp >> (b8 - 2)) & 1 : (cbp_b >> (b8 + 2)) & 1;
+        cbp |= BINI_B(e, 73 + (!ca) + 2 * (!cb)) << b8;
+    }
+    int ca = a.ok() && (a.type() == MBT_IPCM || (a.cbp() >> 4) != 0), cb = b.ok() && (b.type() == MBT_IPCM || (b.cbp() >> 4) != 0);
+    if (!ENT_MONO(e) && BIN_B(e, 77 + ca + 2 * cb)) { // (ChromaArrayType 0: the prefix only)
+        ca = a.ok() && (a.type() == MBT_IPCM || (a.cbp() >> 4) == 2);
+        cb = b.ok() && (b.type() == MBT_IPCM || (b.cbp() >> 4) == 2);
+        cbp |= (1 + BINI_B(e, 77 + 4 + ca + 2 * cb)) << 4;
+    }
+    return cbp;
+}
+// mvd_lX of a partition (se(v) or UEG3), prediction 8.4.1.3, result into the caches
 FI void read_mv(Ent &e, const int L, int p) {
     Shared *s = e.s;
     const int bx = p & 3, by = (p >> 2) & 3, w = ((p >> 4) & 3) + 1, h = ((p >> 6) & 3) + 1, shape = (p >> 8) & 7;
@@ -1219,21 +1271,9 @@ FI void read_mv(Ent &e, const int L, int p) {
     int d[2];
     for (int comp = 0; comp < 2; comp++) {
         int v;
-        if (ENT_CABAC(e)) { // UEG3, uCoff 9, signed (9.3.2.3, 9.3.3.1.1.7)
-            const int sum = s->mvd_c[L][GI(bx - 1, by)][comp] + s->mvd_c[L][GI(bx, by - 1)][comp];
-            const int base = comp ? 47 : 40;
-            v = 0;
-            if (BIN_A(e, base + (sum > 2) + (sum > 32))) {
-                int ctx = base + 3;
-                v = 1;
-                while (v < 9 && BIN_A(e, ctx)) {
-                    if (v < 4) ctx++;
-                    v++;
-                }
-                if (v >= 9) v += cabac_egk(e, 3);
-                if (cabac_bypass(e)) v = -v;
-            }
-        } else
+        if (ENT_CABAC(e))
+            v = read_mvd_cabac(e, comp, s->mvd_c[L][GI(bx - 1, by)][comp] + s->mvd_c[L][GI(bx, by - 1)][comp]);
+        else
             v = IF_CAVLC(get_se(e));
         d[comp] = v;
     }
@@ -1242,18 +1282,13 @@ FI void read_mv(Ent &e, const int L, int p) {
     set_part(e, L, bx, by, w, h, ref, px + d[0], py + d[1], d[0], d[1]);
 }
 
-// @region pskip_fast
-// ------------------------------------------------------------------ P_Skip without the general machinery
-// A skipped macroblock of a P slice has no syntax: its vector comes from the neighbours A, B, C / D (8.4.1.1, 8.4.1.3 with refIdx 0), its
-// record and its edge entry are that vector sixteen / four times over next to constants.  Everything is taken straight from the four
-// neighbour entries (no neighbour caches are built, no record is staged in LDS): lanes 0..11 hold one dword of the new edge entry, lanes
-// 32..63 one dword of the record.  A quarter of the macroblocks of a typical P picture take this path.
 #if !MI_ENT_B
-FI void pskip_fast(Ent &e) {
-    Shared *s = e.s;
-    int l = LANE;
-    OPAQUE(l);
-    const uint32_t *nbw = reinterpret_cast<const uint32_t *>(s->nb); // TOP_DW dwords per entry: [0] type.., [5] ref_idx, [6..9] vectors
+// The list-0 vector predictor of a macroblock that is one 16x16 partition with reference index `ref` (8.4.1.3), straight from the four
+// neighbour entries: A = left, B = above, C = above right, else D = above left (6.4.11.7).  SKIP: the P_Skip rule of 8.4.1.1 in front (a
+// zero vector when A or B is missing or is a still block of picture 0; `ref` is 0 then).  Both halves of the result in one word, x low.
+template <bool SKIP>
+FI uint32_t predict_mv16(const Ent &e, int ref) {
+    const uint32_t *nbw = reinterpret_cast<const uint32_t *>(e.s->nb); // TOP_DW dwords per entry: [0] type.., [5] ref_idx, [6..9] vectors
     const uint32_t tA = e.aw, tB = e.bw, tC = nbw[(NB_TOP + 1) * TOP_DW], tD = nbw[NB_TL * TOP_DW];
     const uint32_t rA = nbw[NB_LEFT * TOP_DW + 5], rB = nbw[NB_TOP * TOP_DW + 5], rC = nbw[(NB_TOP + 1) * TOP_DW + 5], rD = nbw[NB_TL * TOP_DW + 5];
     const uint32_t mA = nbw[NB_LEFT * TOP_DW + 6], mB = nbw[NB_TOP * TOP_DW + 6], mC = nbw[(NB_TOP + 1) * TOP_DW + 6], mD = nbw[NB_TL * TOP_DW + 9];
@@ -1263,14 +1298,15 @@ FI void pskip_fast(Ent &e) {
         return type == MBT_NONE ? -2 : (MB_IS_INTER(type) ? static_cast<int>(static_cast<int8_t>((r >> (8 * byte)) & 255u)) : -1);
     };
     auto mv_of = [](uint32_t t, uint32_t m) { return MB_IS_INTER(static_cast<int>(t & 255u)) ? m : 0u; };
-    const int ra = ref_of(tA, rA, 0), rb = ref_of(tB, rB, 0);
+    int ra = ref_of(tA, rA, 0), rb = ref_of(tB, rB, 0);
     const bool c_ok = e.mbx + 1 < e.wmb && (tC & 255u) != MBT_NONE; // C, else D (6.4.11.7)
-    const int rc = c_ok ? ref_of(tC, rC, 0) : ref_of(tD, rD, 1);
-    const uint32_t va = mv_of(tA, mA), vb = mv_of(tB, mB), vc = c_ok ? mv_of(tC, mC) : mv_of(tD, mD);
+    int rc = c_ok ? ref_of(tC, rC, 0) : ref_of(tD, rD, 1);
+    uint32_t va = mv_of(tA, mA), vb = mv_of(tB, mB), vc = c_ok ? mv_of(tC, mC) : mv_of(tD, mD);
     uint32_t mvw = 0;
-    const bool zero = ra == -2 || rb == -2 || (ra == 0 && va == 0) || (rb == 0 && vb == 0); // 8.4.1.1
-    if (!zero) { // 8.4.1.3.1 with refIdx 0: the one neighbour that uses picture 0, else the median
-        const int na = ra == 0, nb_ = rb == 0, nc = rc == 0;
+    const bool zero = SKIP && (ra == -2 || rb == -2 || (ra == 0 && va == 0) || (rb == 0 && vb == 0)); // 8.4.1.1
+    if (!zero) { // 8.4.1.3.1: the one neighbour that uses the same picture, else the median
+        if (!SKIP && rb == -2 && rc == -2 && ra != -2) rb = rc = ra, vb = vc = va; // only A there: A (P_Skip: a zero vector, above)
+        const int na = ra == ref, nb_ = rb == ref, nc = rc == ref;
         if (na + nb_ + nc == 1)
             mvw = na ? va : (nb_ ? vb : vc);
         else {
@@ -1279,13 +1315,31 @@ FI void pskip_fast(Ent &e) {
             mvw = (static_cast<uint32_t>(median3(ax, bx, cx)) & 0xffffu) | (static_cast<uint32_t>(median3(ay, by, cy)) << 16);
         }
     }
-    e.cur_type = MBT_PSKIP;
+    return mvw;
+}
+#endif
+
+// @region pskip_fast
+// ------------------------------------------------------------------ P_Skip without the general machinery
+// A skipped macroblock of a P slice has no syntax: its vector comes from the neighbours A, B, C / D (8.4.1.1, 8.4.1.3 with refIdx 0), its
+// record and its edge entry are that vector sixteen / four times over next to constants.  Everything is taken straight from the four
+// neighbour entries (no neighbour caches are built, no record is staged in LDS): lanes 0..11 hold one dword of the new edge entry, lanes
+// 32..63 one dword of the record.  A quarter of the macroblocks of a typical P picture take this path.
+#if !MI_ENT_B
+// Record and edge entry of a macroblock that is ONE vector and nothing else, from registers: P_Skip, or (P16) P_L0_16x16 without residual --
+// `refw` ref_idx_l0 in every byte, `slotw` its frame slot in both halves, `mvdw` min(|mvd|, 255) of x | y << 8 in both halves.
+template <bool P16>
+FI void onevec_out(Ent &e, int l, uint32_t mvw, uint32_t refw, uint32_t slotw, uint32_t mvdw) {
+    Shared *s = e.s;
+    const uint32_t type = P16 ? MBT_P16x16 : MBT_PSKIP;
+    e.cur_type = static_cast<int>(type);
     e.prev_dqp_nz = 0;
     // (MbRec::avail -- the intra-prediction neighbour availability -- is 0 in the record of an inter macroblock: only K3 reads it, for intra ones)
     // ---- the new edge entry (the same for the row below and for the macroblock to the right), the window on the row above moves on ----
     if (l < TOP_DW) {
         const uint32_t row = MI_ENT_FMO ? static_cast<uint32_t>(e.mby + 1) << 16 : 0u;
-        const uint32_t nw = l == 0 ? static_cast<uint32_t>(MBT_PSKIP) : (l == 1 ? row : (l == 2 ? 0xFFFFFFFFu : ((l >= 6 && l < 10) ? mvw : 0u)));
+        uint32_t nw = l == 0 ? type : (l == 1 ? row : (l == 2 ? 0xFFFFFFFFu : ((l >= 6 && l < 10) ? mvw : 0u)));
+        if (P16) nw = l == 5 ? (refw & 0xffffu) : (l >= 10 ? mvdw : nw);
         uint32_t *tl = reinterpret_cast<uint32_t *>(&s->nb[NB_TL]), *tp = reinterpret_cast<uint32_t *>(&s->nb[NB_TOP]), *tr = reinterpret_cast<uint32_t *>(&s->nb[NB_TOP + 1]);
         const uint32_t old_top = tp[l], w1 = tr[l];
         tl[l] = old_top;
@@ -1297,17 +1351,109 @@ FI void pskip_fast(Ent &e) {
     } else if (l >= 32) { // ---- the record: one dword per lane ----
         const int k = l - 32;
         const uint32_t t = s->skip_tmpl[k];
-        const uint32_t w = k == 0 ? (static_cast<uint32_t>(MBT_PSKIP) | e.qpw0) : (k == 1 ? e.qpw1 : ((k >= 12 && k < 28) ? mvw : t));
+        uint32_t w = k == 0 ? (type | e.qpw0) : (k == 1 ? e.qpw1 : ((k >= 12 && k < 28) ? mvw : t));
+        if (P16) w = k == 8 ? refw : ((k == 9 || k == 10) ? slotw : w);
         const uint64_t mbi = e.mb_base + static_cast<uint64_t>(e.mby) * e.wmb + e.mbx;
         reinterpret_cast<uint32_t *>(e.mbrec + mbi)[k] = w;
     }
     LDS_SYNC();
 }
+FI void pskip_fast(Ent &e) {
+    int l = LANE;
+    OPAQUE(l);
+    onevec_out<false>(e, l, predict_mv16<true>(e, 0), 0u, 0u, 0u);
+}
+#endif
+
+// @region p16_fast
+// ------------------------------------------------------------------ P_L0_16x16 without the general machinery
+// mb_type said P_L0_16x16 (mb_syntax() reads it in front of the neighbour caches): what follows is ref_idx_l0, the two mvd_l0 and
+// coded_block_pattern -- 10 to 12 bins whose contexts come from the left and the upper entry alone -- and a vector prediction from the four
+// neighbour entries (predict_mv16).  Without residual (cbp 0) record and edge entry leave from registers as in pskip_fast: no neighbour
+// caches, no partition schedule, no staged record.  With residual the function returns false and `h` says what was decoded: the caller
+// builds the caches, enters the partition (p16_enter) and goes on in the tail half of decode_mb.
+#if MI_ENT_P16
+struct P16 {
+    int ref, cbp, t8x8, dx, dy;
+    uint32_t mvw;
+};
+FI bool p16_fast(Ent &e, P16 &h) {
+    Shared *s = e.s;
+    int l = LANE;
+    OPAQUE(l);
+    const uint32_t *nbw = reinterpret_cast<const uint32_t *>(s->nb);
+    const Nb a{e.aw}, b{e.bw};
+    const bool a_inter = MB_IS_INTER(a.type()), b_inter = MB_IS_INTER(b.type()); // (an entry that is not there has type 0)
+    // ---- ref_idx_l0 (9.3.3.1.1.6): "refIdx > 0" of A and B, what fill_caches() would enter from TopInfo::ref[0][0] ----
+    int ref = 0;
+    const int nref = fresh(e.nref);
+    if (nref > 1) {
+        const int ra = static_cast<int8_t>(RFL(nbw[NB_LEFT * TOP_DW + 5]) & 255u), rb = static_cast<int8_t>(RFL(nbw[NB_TOP * TOP_DW + 5]) & 255u);
+        int ctx = (a_inter && ra > 0) + 2 * (b_inter && rb > 0);
+        while (BIN_A(e, 54 + ctx)) {
+            ctx = (ctx >> 2) + 4;
+            if (++ref > 31) {
+                e.err = 3;
+                break;
+            }
+        }
+        if (ref >= nref || ref >= MI_MAX_REFS) e.err = 13, ref = 0;
+    }
+    // ---- mvd_l0: the context sums from TopInfo::mvd[0][0] of A and B (0 for a missing, an intra or a skipped neighbour) ----
+    const uint32_t da = a_inter ? RFL(nbw[NB_LEFT * TOP_DW + 10]) : 0u, db = b_inter ? RFL(nbw[NB_TOP * TOP_DW + 10]) : 0u;
+    int dx = 0, dy = 0;
+#pragma nounroll
+    for (int comp = 0; comp < 2; comp++) { // (one copy of the binarisation's code for both components)
+        const int v = read_mvd_cabac(e, comp, static_cast<int>(((da >> (8 * comp)) & 255u) + ((db >> (8 * comp)) & 255u)));
+        if (comp)
+            dy = v;
+        else
+            dx = v;
+    }
+    const uint32_t pw = predict_mv16<false>(e, ref);
+    const int mvx = static_cast<int16_t>(pw & 0xffffu) + dx, mvy = (static_cast<int32_t>(pw) >> 16) + dy;
+    const uint32_t mvw = (static_cast<uint32_t>(mvx) & 0xffffu) | (static_cast<uint32_t>(mvy) << 16);
+    const int cbp = read_cbp_cabac(e, a, b);
+    MI_T(e, 1);
+    if (cbp) {
+        h.ref = ref, h.cbp = cbp, h.dx = dx, h.dy = dy, h.mvw = mvw;
+        // (transform_size_8x8_flag of an inter macroblock with coded luma: the one bin between coded_block_pattern and the tail half)
+        h.t8x8 = ((cbp & 15) && fresh(ENT_T8X8_MODE(e))) ? IF_T8X8(BINI_T8(e, (a.ok() && a.t8x8()) + (b.ok() && b.t8x8()))) : 0;
+        return false;
+    }
+    const uint32_t refw = static_cast<uint32_t>(ref) * 0x01010101u;
+    const uint32_t slot = static_cast<uint16_t>(s->ref_slot[0][ref & (MI_MAX_REFS - 1)]);
+    const uint32_t mvdw = static_cast<uint32_t>(min(abs(dx), 255) | (min(abs(dy), 255) << 8));
+    onevec_out<true>(e, l, mvw, refw, slot | slot << 16, mvdw | mvdw << 16);
+    return true;
+}
+// the hand-over: the partition of p16_fast() entered into the neighbour caches fill_caches() has just built, as read_ref_idx() and read_mv() leave it
+FI void p16_enter(Ent &e, const P16 &h) {
+    Shared *s = e.s;
+    const int l = LANE;
+    if (l < 16) s->refi_c[0][GI(l & 3, l >> 2)] = static_cast<int8_t>(h.ref);
+    if (l < 4) s->refs8[0][l] = static_cast<int8_t>(h.ref);
+    set_part(e, 0, 0, 0, 4, 4, h.ref, static_cast<int16_t>(h.mvw & 0xffffu), static_cast<int32_t>(h.mvw) >> 16, h.dx, h.dy);
+}
 #endif
 
 // @region decode_mb
 // ------------------------------------------------------------------ macroblock_layer() 7.3.5
+// The two CABAC-only I/P builds (MI_ENT_P16) compile the function as two halves, each inlined once -- mb_syntax(): mb_type to
+// coded_block_pattern, with fill_caches() behind mb_type; mb_tail(): mb_qp_delta, residual, write-out -- so that a P_L0_16x16 macroblock leaves
+// after mb_type for p16_fast() and, when it has residual, joins again at the tail.  The other three builds see decode_mb() as it always
+// was, to the token: their instruction streams depend on it (a split into two inlined functions alone moves k_entropy's allocation).
+#if MI_ENT_P16
+struct MbSyn { // what the syntax half leaves to the tail half
+    int type, raw, cbp_luma, cbp_chroma, t8x8, i16mode, chroma_mode, has_coef;
+    int coded; // neither skipped nor I_PCM: mb_qp_delta and residual follow if anything is coded
+};
+FI bool mb_syntax(Ent &e, MbSyn &m) { // false: p16_fast() has finished the macroblock
+    const int skipped = 0;            // (P_Skip never comes here: pskip_fast)
+    int coded = 0;
+#else
 FI void decode_mb(Ent &e, int skipped) {
+#endif
     Shared *s = e.s;
     MbRec &r = s->rec;
     const int cabac = ENT_CABAC(e), islice = e.islice;
@@ -1396,6 +1542,24 @@ FI void decode_mb(Ent &e, int skipped) {
             }
         } else
             raw = IF_CAVLC(static_cast<int>(get_ue(e)));
+#if MI_ENT_P16
+        // ---- P_L0_16x16: everything up to coded_block_pattern without the neighbour caches; they are built only if residual follows ----
+        {
+            P16 h;
+            const bool p16 = !islice && raw == 0;
+            if (p16 && p16_fast(e, h)) return false;
+            MI_T(e, 1);
+            fill_caches(e);
+            MI_T(e, 0);
+            if (p16) {
+                p16_enter(e, h);
+                e.cur_type = MBT_P16x16;
+                m.type = MBT_P16x16, m.raw = 0, m.cbp_luma = h.cbp & 15, m.cbp_chroma = h.cbp >> 4, m.t8x8 = h.t8x8;
+                m.i16mode = m.chroma_mode = m.has_coef = 0, m.coded = 1;
+                return true;
+            }
+        }
+#endif
         const int it = islice ? raw : raw - (MI_ENT_B ? 23 : 5);
 #if MI_ENT_B
         if (raw < 23)
@@ -1624,22 +1788,9 @@ FI void decode_mb(Ent &e, int skipped) {
             // ---- coded_block_pattern ----
             if (type != MBT_I16x16) {
                 int cbp;
-                if (cabac) { // 9.3.3.1.1.4
-                    const int cbp_a = a.ok() ? (a.type() == MBT_IPCM ? 0x2F : a.cbp()) : 0x0F;
-                    const int cbp_b = b.ok() ? (b.type() == MBT_IPCM ? 0x2F : b.cbp()) : 0x0F;
-                    cbp = 0;
-                    for (int b8 = 0; b8 < 4; b8++) {
-                        int ca = (b8 & 1) ? (cbp >> (b8 - 1)) & 1 : (cbp_a >> (b8 + 1)) & 1;
-                        int cb = (b8 & 2) ? (cbp >> (b8 - 2)) & 1 : (cbp_b >> (b8 + 2)) & 1;
-                        cbp |= BINI_B(e, 73 + (!ca) + 2 * (!cb)) << b8;
-                    }
-                    int ca = a.ok() && (a.type() == MBT_IPCM || (a.cbp() >> 4) != 0), cb = b.ok() && (b.type() == MBT_IPCM || (b.cbp() >> 4) != 0);
-                    if (!ENT_MONO(e) && BIN_B(e, 77 + ca + 2 * cb)) { // (ChromaArrayType 0: the prefix only)
-                        ca = a.ok() && (a.type() == MBT_IPCM || (a.cbp() >> 4) == 2);
-                        cb = b.ok() && (b.type() == MBT_IPCM || (b.cbp() >> 4) == 2);
-                        cbp |= (1 + BINI_B(e, 77 + 4 + ca + 2 * cb)) << 4;
-                    }
-                } else {
+                if (cabac)
+                    cbp = read_cbp_cabac(e, a, b);
+                else {
                     uint32_t k = IF_CAVLC(get_ue(e));
                     if (k > (ENT_MONO(e) ? 15u : 47u)) e.err = 23, k = 0;
                     if (ENT_MONO(e)) k += 48; // the ChromaArrayType 0 column of Table 9-4 (h264/bit_reader.go:118-135) sits behind the 48 entries of the other
@@ -1659,6 +1810,24 @@ FI void decode_mb(Ent &e, int skipped) {
                 }
 #endif
             }
+#if MI_ENT_P16
+            coded = 1;
+        }
+    }
+    m.type = type, m.raw = raw, m.cbp_luma = cbp_luma, m.cbp_chroma = cbp_chroma, m.t8x8 = t8x8, m.i16mode = i16mode, m.chroma_mode = chroma_mode;
+    m.has_coef = has_coef, m.coded = coded;
+    return true;
+}
+FI void mb_tail(Ent &e, const MbSyn &m) {
+    Shared *s = e.s;
+    MbRec &r = s->rec;
+    const int cabac = ENT_CABAC(e);
+    const int type = m.type, raw = m.raw, cbp_luma = m.cbp_luma, cbp_chroma = m.cbp_chroma, t8x8 = m.t8x8, i16mode = m.i16mode, chroma_mode = m.chroma_mode;
+    int has_coef = m.has_coef;
+    const Nb a{e.aw}, b{e.bw};
+    if (m.coded) {
+        { // (two scopes, closed by the text that the halves share with decode_mb() of the other builds)
+#endif
             // ---- mb_qp_delta + residual ----
             if (cbp_luma || cbp_chroma || type == MBT_I16x16) {
                 int dqp;
@@ -1704,7 +1873,7 @@ FI void decode_mb(Ent &e, int skipped) {
     r.i16mode = static_cast<uint8_t>(i16mode);
     {
         // neighbour availability for intra prediction (6.4.x; constrained_intra_pred 8.3.1.2)
-        const int cip = e.cip;
+        const int cip = fresh(e.cip);
         int av = 0;
         if (MB_IS_INTRA(type)) { // (only K3 reads it, for intra macroblocks: an inter macroblock's record says 0)
             const int td = s->nb[NB_TL].type, tc = nb_ok(e, NB_TOP + 1) ? s->nb[NB_TOP + 1].type : MBT_NONE;
@@ -1868,6 +2037,10 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
     e.sd = sd, e.pd = pd;
     e.rbsp32 = reinterpret_cast<const uint32_t *>(bitstream + sd->rbsp_off); // slices are 16-byte aligned in the staging buffer
     e.rbsp_words = RFL((sd->rbsp_size + 3) >> 2);
+#if MI_ENT_P16
+    // (the four arrive in one s_load_dwordx8, and the compiler spills and reloads that tuple whole: a register pair of its own for each)
+    asm volatile("" : "+s"(mbrec), "+s"(coefs), "+s"(pool_head), "+s"(pool_blocks));
+#endif
     e.mbrec = mbrec;
     e.coefs = coefs;
     e.pool_head = pool_head, e.pool_blocks = pool_blocks;
@@ -1885,6 +2058,9 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
     e.cqp_off0 = RFL(static_cast<int>(pd->cqp_off[0])), e.cqp_off1 = RFL(static_cast<int>(pd->cqp_off[1]));
     e.nref = RFL(static_cast<int>(sd->num_ref_idx_active));
     e.mb_base = (static_cast<uint64_t>(RFL(static_cast<uint32_t>(pd->mb_base >> 32))) << 32) | RFL(static_cast<uint32_t>(pd->mb_base));
+#if MI_ENT_P16
+    e.mbrec += e.mb_base, e.mb_base = 0; // the picture's first record as ONE pointer
+#endif
     e.prev_dqp_nz = 0;
     e.range = 510, e.value = 0, e.avail = 0;
     e.mbx = e.mby = 0, e.cur_type = 0;
@@ -2050,12 +2226,19 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
             pskip_fast(e);
         } else
 #endif
+#if MI_ENT_P16
+        { // (the neighbour caches are built behind mb_type, if at all: mb_syntax)
+            MbSyn m;
+            if (mb_syntax(e, m)) mb_tail(e, m);
+        }
+#else
         {
             MI_T(e, 1);
             fill_caches(e);
             MI_T(e, 0);
             decode_mb(e, skipped);
         }
+#endif
         MI_T(e, 3);
         if (e.err) break; // the record of this macroblock cannot be trusted: it is blanked with the rest of the range
         n_mbs++;
