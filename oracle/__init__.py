@@ -39,6 +39,7 @@ def lib():
         L.h264o_decode_stream.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int,
                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(StreamInfo)]
         L.h264o_set_mb_trace.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+        L.h264o_set_motion_trace.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
         L.h264o_last_features.argtypes = [ctypes.c_void_p]
         L.h264o_last_features.restype = ctypes.c_uint32
         L.h264o_last_pocs.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
@@ -68,9 +69,11 @@ def probe(stream: bytes) -> "StreamInfo":
         L.h264o_decoder_destroy(d)
 
 
-def decode(stream: bytes, crop=True, trace=False, info=None):
-    """Decode an Annex-B stream.  Returns (frames uint8[n, w*h + 2*ceil(w/2)*ceil(h/2)], info[, trace int32[nmb,8]]).
-    With `info` (from probe()) the sizing pass is skipped: exactly one decode runs (used for timing)."""
+def decode(stream: bytes, crop=True, trace=False, info=None, motion=False):
+    """Decode an Annex-B stream.  Returns (frames uint8[n, w*h + 2*ceil(w/2)*ceil(h/2)], info[, trace int32[nmb,8]][, motion int32[nmb,76]]).
+    With `info` (from probe()) the sizing pass is skipped: exactly one decode runs (used for timing).  motion: every macroblock in decoding order
+    as {address, slice_type, picture in decoding order, 0, vectors of list 0 and of list 1 per 4x4 block, indices of list 0 and of list 1 per quadrant}
+    (h264o_set_motion_trace)."""
     L = lib()
     d = L.h264o_decoder_create()
     try:
@@ -88,6 +91,10 @@ def decode(stream: bytes, crop=True, trace=False, info=None):
         if trace:
             tr = np.zeros((int(info.n_mbs), 8), dtype=np.int32)
             L.h264o_set_mb_trace(d, tr.ctypes.data, tr.shape[0])
+        mo = None
+        if motion:
+            mo = np.zeros((int(info.n_mbs), 76), dtype=np.int32)
+            L.h264o_set_motion_trace(d, mo.ctypes.data, mo.shape[0])
         r = L.h264o_decode_stream(d, stream, len(stream), int(crop), out.ctypes.data, out.nbytes, ctypes.byref(info))
         if r < 0:
             raise OracleError(L.h264o_last_error(d).decode())
@@ -96,6 +103,6 @@ def decode(stream: bytes, crop=True, trace=False, info=None):
         n = L.h264o_last_pocs(d, None, 0)
         last_pocs = np.zeros(n, dtype=np.int32)
         L.h264o_last_pocs(d, last_pocs.ctypes.data, n)
-        return (out, info, tr) if trace else (out, info)
+        return (out, info) + ((tr,) if trace else ()) + ((mo,) if motion else ())
     finally:
         L.h264o_decoder_destroy(d)

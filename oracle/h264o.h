@@ -169,6 +169,10 @@ int h264o_decode_stream(h264o_decoder *d, const uint8_t *buf, size_t len, int cr
  * 8 int32 per MB: {mb_type_raw, cbp, qp, intra16/chroma mode, t8x8, mv0x, mv0y, ref0}.
  * Pass NULL to disable. cap in MBs across all frames. */
 void h264o_set_mb_trace(h264o_decoder *d, int32_t *trace, size_t cap_mbs);
+/* The motion of every macroblock of the LAST decoded frames, in decoding order (for tests of the derivation of 8.4.1): all sixteen 4x4 blocks and
+ * both lists.  76 int32 per MB: {macroblock address, slice_type % 5, pictures begun before this one, 0, then per list 0 / 1 the sixteen vectors
+ * (x, y at 4 * row + column), then per list the four reference indices per quadrant (-1: list not used / intra)}.  Pass NULL to disable. */
+void h264o_set_motion_trace(h264o_decoder *d, int32_t *trace, size_t cap_mbs);
 const char *h264o_last_error(h264o_decoder *d);
 /* Test instrumentation of the last h264o_decode_stream() call.
  * features: bit k = memory_management_control_operation k executed (1..6), bit 8/9/10 = modification_of_pic_nums_idc

@@ -44,6 +44,11 @@ void h264o_set_mb_trace(h264o_decoder *d, int32_t *trace, size_t cap) {
     d->trace_cap = cap;
     d->trace_pos = 0;
 }
+void h264o_set_motion_trace(h264o_decoder *d, int32_t *trace, size_t cap) {
+    d->mtrace = trace;
+    d->mtrace_cap = cap;
+    d->mtrace_pos = 0;
+}
 
 /* CropUnitX / CropUnitY of 7.4.2.1.1 in luma samples: SubWidthC x SubHeightC * (2 - frame_mbs_only_flag), and 1 x (2 - frame_mbs_only_flag)
  * for ChromaArrayType 0 (4:2:0 and monochrome are all that activate() lets through) */
@@ -643,6 +648,7 @@ static h264o_pic *make_view(h264o_decoder *d, h264o_pic *p, int parity, int poc)
 }
 
 static int start_picture(h264o_decoder *d) {
+    d->pic_no++;
     const h264o_slice_header *sh = &d->sh;
     d->field_pic = sh->field_pic_flag, d->bottom = sh->bottom_field_flag;
     d->hmb = d->field_pic ? d->fhmb / 2 : d->fhmb;
@@ -743,7 +749,7 @@ int h264o_decode_stream(h264o_decoder *d, const uint8_t *buf, size_t len, int cr
     d->out = out;
     d->out_cap = out_cap;
     d->out_pos = 0;
-    d->trace_pos = 0;
+    d->trace_pos = 0, d->mtrace_pos = 0, d->pic_no = 0;
     d->feat = 0, d->n_pocs = 0;
     for (int i = 0; i < d->n_pics; i++) d->pics[i].ref = 0, d->pics[i].in_use = 0, d->pics[i].fields = 0;
     d->cur = d->curf = d->pend = NULL;

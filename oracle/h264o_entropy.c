@@ -842,6 +842,14 @@ static int direct_pred(h264o_decoder *d, int mask8) {
 
 /* ------------------------------------------------------------------ macroblock_layer() 7.3.5 */
 static void trace_mb(h264o_decoder *d, h264o_mb *m) {
+    if (d->mtrace && d->mtrace_pos < d->mtrace_cap) {
+        int32_t *t = d->mtrace + 76 * d->mtrace_pos++;
+        const int intra = d->c.type >= MBT_I4x4 && d->c.type <= MBT_IPCM;
+        t[0] = d->c.addr, t[1] = d->sh.slice_type % 5, t[2] = d->pic_no - 1, t[3] = 0;
+        for (int i = 0; i < 16; i++)
+            for (int c = 0; c < 2; c++) t[4 + 2 * i + c] = m->mv[i][c], t[36 + 2 * i + c] = m->mv1[i][c];
+        for (int q = 0; q < 4; q++) t[68 + q] = intra ? -1 : m->ref[q], t[72 + q] = intra ? -1 : m->ref1[q];
+    }
     if (!d->trace || d->trace_pos >= d->trace_cap) return;
     int32_t *t = d->trace + 8 * d->trace_pos++;
     t[0] = d->c.mb_type_raw;

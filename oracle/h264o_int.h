@@ -111,6 +111,9 @@ struct h264o_decoder {
     h264o_stream_info info;
     int32_t *trace;
     size_t trace_cap, trace_pos;
+    int32_t *mtrace;
+    size_t mtrace_cap, mtrace_pos;
+    int pic_no; /* pictures begun so far */
     char err[256];
     uint8_t *rbsp;
     size_t rbsp_cap;

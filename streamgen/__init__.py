@@ -24,7 +24,8 @@ class Params(ctypes.Structure):
         ("b_pyramid", ctypes.c_int), ("slice_groups", ctypes.c_int), ("fmo_type", ctypes.c_int), ("aso", ctypes.c_int), ("field_pics", ctypes.c_int), ("poc_bottom_delta", ctypes.c_int), ("mono", ctypes.c_int),
         ("wp_range", ctypes.c_int), ("poc_step", ctypes.c_int), ("mv_reach", ctypes.c_int), ("mv_margin", ctypes.c_int), ("contrast", ctypes.c_int),
         ("dbf_per_slice", ctypes.c_int), ("trace_deblock", ctypes.c_int), ("syntax_stim", ctypes.c_int),
-        ("intra_stim", ctypes.c_int), ("trace_intra", ctypes.c_int), ("open_gop_period", ctypes.c_int)]
+        ("intra_stim", ctypes.c_int), ("trace_intra", ctypes.c_int),
+        ("direct_4x4", ctypes.c_int), ("trace_motion", ctypes.c_int), ("motion_stim", ctypes.c_int), ("open_gop_period", ctypes.c_int)]
 
 
 def build(force=False):
@@ -56,6 +57,8 @@ def lib():
         _lib.sg_cavlc_level_bits.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
         _lib.sg_last_deblock_trace.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
         _lib.sg_last_intra_trace.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
+        _lib.sg_last_motion.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        _lib.sg_last_motion_trace.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
     return _lib
 
 
@@ -233,6 +236,62 @@ def last_intra_trace():
             return a[:w * h].reshape(h, w), a[w * h:w * h * 5 // 4].reshape(h // 2, w // 2), a[w * h * 5 // 4:].reshape(h // 2, w // 2)
         t.update(pred=planes(pred), res=planes(res), ipmbs=mbs, constrained_intra=int(info[8]))
     return out
+
+
+# sg_mvmb / sg_mvslice (sg.h): what a derivation of 8.4.1 starts from, and what it must arrive at
+MVMB = np.dtype(dict(names=["kind", "raw", "sub", "direct8", "slice", "ref_idx", "mvd", "mv", "ref"],
+                     formats=["u1", "i1", ("u1", 4), "u1", "u2", ("i1", (2, 4)), ("i2", (2, 16, 2)), ("i2", (2, 16, 2)), ("i1", (2, 4))],
+                     offsets=[0, 1, 2, 6, 8, 10, 18, 146, 274], itemsize=282))
+MVSLICE = np.dtype([("type", "i4"), ("direct_spatial", "i4"), ("cur_poc", "i4"), ("first_mb", "i4"), ("count", "i4"), ("nref", "i4", 2),
+                    ("pic", "i4", (2, 4)), ("poc", "i4", (2, 4)), ("long_term", "i4", (2, 4)), ("col_index", "i4")])
+MV_INTRA, MV_16x16, MV_16x8, MV_8x16, MV_8x8, MV_PSKIP, MV_BDIRECT, MV_BSKIP = range(8)
+
+
+def last_motion_trace():
+    """For every picture of the last encode(trace_motion=1, ...) of this thread, in coding order, a dict: `mbs` = the sg_mvmb table [rows, columns]
+    (kind MV_*, raw mb_type, sub_mb_type, direct8, slice, ref_idx and signed mvd as written, and the final mv / ref per list: the thing to be checked),
+    `slices` = the sg_mvslice table in sending order (type 0 P / 1 B / 2 I, direct_spatial, cur_poc, first_mb, count, nref and the entries of both
+    lists as picture identity `pic`, `poc` and `long_term`, col_index = the index in this list of the picture that is RefPicList1[0]), `field`, `frame`
+    = the frame of the reconstruction the picture belongs to, `pic` = the picture's identity."""
+    n = lib().sg_last_motion_trace(-1, None, None, 0, None, 0)
+    out = []
+    for i in range(n):
+        info = np.zeros(8, dtype=np.int32)
+        lib().sg_last_motion_trace(i, info.ctypes.data, None, 0, None, 0)
+        wmb, hmb, field, frame, pic, nsl, msize, ssize = (int(v) for v in info)
+        assert (msize, ssize) == (MVMB.itemsize, MVSLICE.itemsize), (msize, ssize, MVMB.itemsize, MVSLICE.itemsize)
+        mbs, slices = np.zeros((hmb, wmb), dtype=MVMB), np.zeros(nsl, dtype=MVSLICE)
+        lib().sg_last_motion_trace(i, None, mbs.ctypes.data, mbs.nbytes, slices.ctypes.data, slices.nbytes)
+        out.append(dict(mbs=mbs, slices=slices, field=field, frame=frame, pic=pic))
+    return out
+
+
+_M_SHAPES = ("med", "16x8u", "16x8l", "8x16l", "8x16r")
+_M_RULES = ("dir", "onlyA", "oneA", "oneB", "oneC", "med0", "med2", "med3")
+_M_SLOTS = (("P", 0), ("B", 0), ("B", 1))
+# the SG_M_* words of sg.h in order: the derivation counters as (cell, ...) names, the syntax words by name
+MOTION_NAMES = tuple(("pred", st, lst, shape, rule) for st, lst in _M_SLOTS for shape in _M_SHAPES for rule in _M_RULES) + tuple(
+    ("csrc", st, lst, c) for st, lst in _M_SLOTS for c in ("C", "D", "none")) + tuple(
+    ("pskip", w) for w in ("A_missing", "B_missing", "A_still", "B_still", "predicted_nonzero", "predicted_zero")) + tuple(
+    ("sd_ref", lst, src) for lst in (0, 1) for src in ("A", "B", "C", "none")) + (("sd_bothneg",),) + tuple(
+    ("sd_out", lst, o) for lst in (0, 1) for o in ("neg", "zeroed", "kept0", "keptpos_flag")) + (
+    ("col", "intra"), ("col", "l0"), ("col", "l1only"), ("td_ref", "zero"), ("td_ref", "pos"), ("td", "long"), ("td", "neg_remainder"),
+    "mbtype_p", "mbtype_b", "subtype_p", "subtype_b", "ref_inc", "ref_ge3", "ref_direct_nb", "ref_te1", "ref_ue") + tuple(
+    "mvd_band_%s_%d" % (c, b) for c in "xy" for b in range(3)) + ("mvd_suffix", "skip_inc_p", "skip_inc_b", "btype_inc") + tuple(
+    ("geo", pos, w) for pos in range(41) for w in ("in_done", "in_later", "B", "C", "outside")) + tuple(("geo_d", pos) for pos in range(41)) + tuple(
+    ("nolist", w) for w in ("in_done", "A", "B", "C", "D")) + (("direct_nb", "spatial"), ("direct_nb", "temporal"), ("sd_col", "short"), ("sd_col", "long"),
+    ("sd_refcol", "zero"), ("sd_refcol", "pos")) + tuple(("sd_mvcol", c, v) for c in (0, 1) for v in (-2, -1, 0, 1, 2)) + (
+    ("col", "corner_differs"), ("col", "four_unlike"), ("td", "mb16"), ("td", "quadrant"))
+
+
+def last_motion():
+    """What the last encode() call did about motion (the SG_M_* words of sg.h), as a dict: the derivation counters under the cell names of
+    tests/motionutil.py (tuples), the syntax words under strings (bit masks: mbtype_*, subtype_*, ref_inc, skip_inc_*, btype_inc)."""
+    n = lib().sg_last_motion(None, 0)
+    assert n == len(MOTION_NAMES), (n, len(MOTION_NAMES))
+    out = np.zeros(n, dtype=np.int32)
+    lib().sg_last_motion(out.ctypes.data, n)
+    return {k: int(v) for k, v in zip(MOTION_NAMES, out)}
 
 
 SCALING_FORMS = dict(absent_first=1, absent_next=2, use_default=4, cut_short=8, wrap=16, entry_1=32, entry_255=64, full=128,

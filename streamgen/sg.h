@@ -49,7 +49,8 @@ typedef struct {
     /* picture management stimulus (8.2.1, 8.2.4.3, 8.2.5.4); all 0 = sliding window, default lists, every picture a reference */
     int rplm;               /* 1: P slices carry random ref_pic_list_modification() commands (idc 0, 1 and, with long-term pictures, 2) */
     int mmco;               /* 1: reference P pictures carry random memory_management_control_operation scripts (1..6) */
-    int idr_long_term;      /* 1: IDR pictures set long_term_reference_flag */
+    int idr_long_term;      /* 1: IDR pictures set long_term_reference_flag (with bframes: the long-term picture closes both lists of a B picture, 8.2.4.2.3,
+                             * and is RefPicList1[0] of the B pictures between an IDR picture and the anchor after it; not with b_pyramid or field_pics) */
     int nonref_period;      /* N > 1: every N-th P picture is a non-reference picture (nal_ref_idc 0) */
     int slice_qp_delta;     /* d != 0: slice_qp_delta cycles through -d, 0, +d per slice */
     /* B pictures (Main / High): `bframes` non-reference B pictures between two anchors (display order I B B P -> coding
@@ -145,6 +146,23 @@ typedef struct {
     /* 1: sg_last_intra_trace() keeps, for every picture of this call, the prediction and residual sample of every intra-predicted sample and the sg_ipmb
      * table (and what trace_deblock keeps); changes nothing else */
     int trace_intra;
+    /* motion derivation (8.4.1): all three 0 = the streams of before, byte for byte, and not one more draw of the generator.
+     * direct_4x4 1: the SPS carries direct_8x8_inference_flag = 0 (frame-only streams: refused together with field_pics and interlace_sps).  The
+     * co-located block of a 4x4 block is then the 4x4 block at the same place (no corner substitution), direct prediction gives every 4x4 block of a
+     * direct quadrant a vector of its own, and a direct quadrant counts as smaller than 8x8: no transform_size_8x8_flag follows a B_8x8 macroblock with
+     * a direct quadrant nor a B_Direct_16x16 macroblock (7.3.5) */
+    int direct_4x4;
+    /* 1: sg_last_motion_trace() keeps, for every picture of this call, the sg_mvmb table and the sg_mvslice table; changes nothing else */
+    int trace_motion;
+    /* motion stimulus: 0 = the streams of before, byte for byte, and not one more draw of the generator.  1: where the generator draws the kind of an inter
+     * macroblock (P: 16x16, 16x8, 8x16, 8x8; B: the mb_type 1 .. 22, partition shape and prediction modes in one), a sub_mb_type or a ref_idx, it takes the
+     * candidate that was taken least often so far in this sg_encode() call, the drawn one winning among equals; a ref_idx must lie inside its list and
+     * pass the reference barrier.  Skipped, direct and intra macroblocks are drawn as before.  In CAVLC P slices with more than one active reference,
+     * P_8x8ref0 (mb_type 4: four indices of 0, not written) is a fifth kind, and any P_8x8 macroblock whose four indices are 0 is written that way.
+     * Vectors still come from the motion search, but one partition in four takes one that changes what the blocks after it see in their neighbours --
+     * the vector of its neighbour A, B or C (where that neighbour uses the list), a zero vector where its own index is 0 (the conditions of P_Skip and
+     * of colZeroFlag), or a vector whose components come from -2 .. 2 (the boundary of colZeroFlag); it passes the same limits as any other. */
+    int motion_stim;
     /* open groups of pictures: 0 = the streams of before, byte for byte, and not one more draw of the generator.  N > 0 (rounded up to a multiple of
      * bframes + 1, like idr_period): the anchor at every display index that is a positive multiple of N, and no IDR picture, is coded as a non-IDR I
      * picture (field_pics: two I fields).  In front of it, in its access unit, stand the SPS and the PPS again, byte for byte, and an SEI NAL unit with a
@@ -288,6 +306,48 @@ enum {
     SG_S_COUNT
 };
 int sg_last_syntax(int32_t *dst, int cap);
+/* what the last sg_encode() call of this thread did about motion (8.4.1): a third set beside SG_R_* and SG_S_*, counted for every stream.  The derivation
+ * counters are counted where the generator builds the predictor that goes into the stream (mv_pred / mv_pred_l, skip_mv, b_direct; never in the motion
+ * search), the syntax ones where the entropy writers write.  "slot" = 0: list 0 of a P slice, 1 / 2: list 0 / 1 of a B slice.  A direct block counts
+ * once per 4x4 block it covers.  Returns the number of words; dst receives up to cap of them. */
+enum {
+    SG_M_PRED,                                    /* [3 slots][5 shapes: median, 16x8 upper, lower, 8x16 left, right][8 rules: directional hit, only A available,
+                                                   * single match at A, at B, at C, median with 0, 2, 3 matches]: predictors of coded partitions and of P_Skip */
+    SG_M_CSRC = SG_M_PRED + 120,                  /* [3 slots][3]: neighbour C of those predictors was C itself, D in its place, neither */
+    SG_M_PSKIP = SG_M_CSRC + 9,                   /* [6]: P_Skip: zero because A is missing, B is missing, A is still (index 0, zero vector), B is still; predicted and non-zero, and zero */
+    SG_M_SD_REF = SG_M_PSKIP + 6,                 /* [2 lists][4]: spatial direct, per macroblock derivation: the index came from A, B, C, none (negative) */
+    SG_M_SD_BOTHNEG = SG_M_SD_REF + 8,            /* ... both lists negative: index 0 on both */
+    SG_M_SD_OUT,                                  /* [2 lists][4]: per 4x4 block: list not used; zeroed by colZeroFlag; kept with index 0; kept with a positive index although the flag is set */
+    SG_M_COL = SG_M_SD_OUT + 8,                   /* [3]: per 4x4 block of a direct block: the co-located block was intra, used list 0, used list 1 only */
+    SG_M_TD_REF = SG_M_COL + 3,                   /* [2]: temporal direct, per 4x4 block: refIdxL0 0, above 0 */
+    SG_M_TD_LONG = SG_M_TD_REF + 2,               /* ... RefPicList0[refIdxL0] long-term: vector copied, list 1 zero */
+    SG_M_TD_NEG_REMAINDER,                        /* ... a negative component of mvCol whose product with DistScaleFactor, plus 128, is no multiple of 256 */
+    SG_M_MBTYPE_P, SG_M_MBTYPE_B,                 /* bit mb_type (0..4 / 0..22) written in P / B slices (inter types only) */
+    SG_M_SUBTYPE_P, SG_M_SUBTYPE_B,               /* bit sub_mb_type (0..3 / 0..12) */
+    SG_M_REF_INC,                                 /* CABAC: bit ctxIdxInc 0..3 of the first bin of ref_idx */
+    SG_M_REF_GE3,                                 /* ref_idx values of at least 3 written (CABAC or CAVLC) */
+    SG_M_REF_DIRECT_NB,                           /* CABAC: ref_idx whose neighbour A or B is a direct or skipped block of a B slice (counted as index 0) */
+    SG_M_REF_TE1, SG_M_REF_UE,                    /* CAVLC: ref_idx as the one-bit form of te() / as ue() */
+    SG_M_MVD_BAND,                                /* [2 components][3]: CABAC: mvd whose context sum was below 3, 3 .. 32, above 32 */
+    SG_M_MVD_SUFFIX = SG_M_MVD_BAND + 6,          /* CABAC: |mvd| of 9 and above (prefix of nine ones and an Exp-Golomb suffix) */
+    SG_M_SKIP_INC_P, SG_M_SKIP_INC_B,             /* CABAC: bit ctxIdxInc 0..2 of mb_skip_flag in P / B slices */
+    SG_M_BTYPE_INC,                               /* CABAC: bit ctxIdxInc 0..2 of the first bin of a B mb_type */
+    SG_M_GEO,                                     /* [41 partition positions][5]: where neighbour C of a counted predictor lies: inside the macroblock and decoded, inside and
+                                                   * not yet, in the macroblock above (there), above right (there), nowhere that is there.  Positions: 0 16x16, 1 / 2 16x8,
+                                                   * 3 / 4 8x16, 5 + q 8x8, 9 + 2 q + k 8x4, 17 + 2 q + k 4x8, 25 + 4 q + k 4x4 (q quadrant, k partition of it) */
+    SG_M_GEO_D = SG_M_GEO + 205,                  /* [41]: ... D stood in for C */
+    SG_M_NOLIST = SG_M_GEO_D + 41,                /* [5]: a neighbour (A, B, or what serves as C) of a counted predictor is an available inter partition that does not use the
+                                                   * list: it lies inside the macroblock, in macroblock A, B, C, D */
+    SG_M_DIRECT_NB = SG_M_NOLIST + 5,             /* [2]: ... is a direct quadrant of the same macroblock (and uses the list): spatial, temporal */
+    SG_M_SD_COL = SG_M_DIRECT_NB + 2,             /* [2]: spatial direct, per 4x4 block: RefPicList1[0] short-term, long-term */
+    SG_M_SD_REFCOL = SG_M_SD_COL + 2,             /* [2]: ... the co-located block is not intra and refIdxCol is 0, above 0 */
+    SG_M_SD_MVCOL = SG_M_SD_REFCOL + 2,           /* [2 components][5]: ... short-term, refIdxCol 0, the other component in -1 .. 1, and this one is -2, -1, 0, 1, 2 */
+    SG_M_COL_CORNER = SG_M_SD_MVCOL + 10,         /* direct quadrants (inference on) whose co-located corner block has another vector than the first block of its quadrant */
+    SG_M_COL_FOUR,                                /* direct quadrants (inference off) with four different co-located vectors */
+    SG_M_TD_MB16, SG_M_TD_QUADRANT,               /* temporal direct derivations for a whole macroblock (B_Skip, B_Direct_16x16) / for direct quadrants of B_8x8 */
+    SG_M_COUNT
+};
+int sg_last_motion(int32_t *dst, int cap);
 /* the bits of one CAVLC coefficient level as cavlc_block() writes it (see sg_put_cavlc_level in sg_int.h): returns their number, or -1; bits receives them
  * from the first one down, in the low end of the word */
 int sg_cavlc_level_bits(int level, int suffix_len, int minus2, int escape16, uint64_t *bits);
@@ -306,6 +366,33 @@ typedef struct {
     uint16_t slice_id, pad2;
 } sg_ipmb;
 int sg_last_intra_trace(int index, int32_t info[9], uint8_t *pred, int16_t *res, size_t planes_cap, void *mbs, size_t mbs_cap);
+/* sg_params::trace_motion: the pictures of the last sg_encode() call of this thread, in coding order: what a derivation of 8.4.1 starts from (the syntax
+ * as written, nothing taken from the predictor) and what it must arrive at (the final vectors and indices).  Returns the number of pictures; for picture
+ * `index` info receives {macroblock columns, macroblock rows, field (0 frame, 1 top, 2 bottom), the frame of recon[] the picture belongs to, the
+ * picture's identity (the numbers of sg_mvslice::pic), slices, sizeof(sg_mvmb), sizeof(sg_mvslice)}, mbs its sg_mvmb table in macroblock address order,
+ * slices its sg_mvslice table in the order the slices were sent (each optional, each with its capacity in bytes) */
+typedef struct {
+    uint8_t kind;        /* 0 intra, 1 16x16, 2 16x8, 3 8x16, 4 8x8, 5 P_Skip, 6 B_Direct_16x16, 7 B_Skip */
+    int8_t raw;          /* mb_type as written (per slice type: Table 7-13 / 7-14; P_8x8ref0 = 4); -1: none written (skipped) or intra */
+    uint8_t sub[4];      /* sub_mb_type as written (kind 4) */
+    uint8_t direct8;     /* bit q: quadrant q is predicted in direct mode */
+    uint8_t pad;
+    uint16_t slice;      /* ordinal of the macroblock's slice in sg_mvslice order */
+    int8_t ref_idx[2][4];   /* per list and quadrant: ref_idx as written (or 0 where a single active entry leaves nothing to write); -1: none for that quadrant */
+    int16_t mvd[2][16][2];  /* per list: signed mvd (x, y) as written, at the 4x4 block (4 * row + column) of the partition's upper left corner; 0 elsewhere */
+    int16_t mv[2][16][2];   /* the thing to be checked: final vector per list and 4x4 block (0 where the list is not used) */
+    int8_t ref[2][4];       /* ... and final reference index per list and quadrant (-1: the list is not used; intra: -1) */
+} sg_mvmb;
+typedef struct {
+    int32_t type;            /* 0 P, 1 B, 2 I */
+    int32_t direct_spatial;  /* direct_spatial_mv_pred_flag (B slices) */
+    int32_t cur_poc;         /* PicOrderCnt(CurrPic) */
+    int32_t first_mb, count; /* the slice's first macroblock address and its number of macroblocks */
+    int32_t nref[2];         /* active entries of RefPicList0 / RefPicList1 */
+    int32_t pic[2][4], poc[2][4], long_term[2][4]; /* the entries: picture identity, PicOrderCnt, 1 for a long-term picture */
+    int32_t col_index;       /* B slices: the index (in this trace) of the picture that is RefPicList1[0]; -1: not traced */
+} sg_mvslice; /* (four entries per list and 512 slices per picture are the generator's own limits: it builds no longer list and sends no more slices) */
+int sg_last_motion_trace(int index, int32_t info[8], void *mbs, size_t mbs_cap, void *slices, size_t slices_cap);
 
 #ifdef __cplusplus
 }

@@ -87,6 +87,15 @@ typedef struct {
     sg_ipmb *ipmb;
     /* sg_params::open_gop_period, the reference barrier of the current picture: bit i of allow[l] = entry i of list l may be predicted from */
     uint32_t allow[2];
+    /* sg_params::trace_motion: the sg_mvmb table of the current picture, and its slices so far */
+    sg_mvmb *mvmb;
+    sg_mvslice mvsl[512];
+    int n_mvsl;
+    /* sg_params::motion_stim: the vector the next pick_mv() call has to give instead of its own choice */
+    int force_mv, forced[2];
+    int quiet_pred; /* mot_pred() does not count */
+    int pred_h;     /* height in blocks of the partition whose predictor comes next (mot_geo) */
+    int col_list;   /* col_block(): 1 the co-located block used list 0, 2 list 1 only */
 } enc;
 /* the entry of list l to predict from when `r` was drawn: `r` itself unless the barrier bars it, then the first entry that it lets through */
 static int barrier_ref(const enc *e, int l, int r) {
@@ -121,6 +130,13 @@ const char *sg_last_error(void) { return g_err; }
 /* sg_last_syntax(): what the entropy writers wrote, per thread like g_rng */
 static _Thread_local int32_t g_syn[SG_S_COUNT];
 static void syn_bit(int word, int bit) { g_syn[word + (bit >> 5)] = (int32_t)((uint32_t)g_syn[word + (bit >> 5)] | 1u << (bit & 31)); }
+/* sg_last_motion(): the SG_M_* words, per thread like the others */
+static _Thread_local int32_t g_mot[SG_M_COUNT];
+int sg_last_motion(int32_t *dst, int cap) {
+    for (int i = 0; i < SG_M_COUNT && i < cap && dst; i++) dst[i] = g_mot[i];
+    return SG_M_COUNT;
+}
+static void mot_te(int range, int ref) { g_mot[range > 1 ? SG_M_REF_UE : SG_M_REF_TE1]++, g_mot[SG_M_REF_GE3] += ref >= 3; }
 static void syn_max(int word, int v) {
     if (v > g_syn[word]) g_syn[word] = v;
 }
@@ -485,6 +501,7 @@ static void cabac_mvd(enc *e, int comp, int bx, int by, int v) {
     emb *a = lnb(e, bx - 1, by, &ia), *b = lnb(e, bx, by - 1, &ib);
     int sum = (a ? a->mvd[ia][comp] : 0) + (b ? b->mvd[ib][comp] : 0), base = comp ? 47 : 40, m = abs(v);
     sg_cabac_bin(w, base + (sum > 2) + (sum > 32), m != 0);
+    g_mot[SG_M_MVD_BAND + 3 * comp + (sum > 2) + (sum > 32)]++, g_mot[SG_M_MVD_SUFFIX] += m >= 9;
     if (!m) return;
     int ctx = base + 3;
     for (int k = 1; k < (m < 9 ? m : 9); k++) {
@@ -510,6 +527,7 @@ static void cabac_ref(enc *e, int bx, int by, int ref) {
     emb *a = lnb(e, bx - 1, by, &ia), *b = lnb(e, bx, by - 1, &ib);
     int ra = a ? a->ref[(ia >> 3) * 2 + ((ia & 3) >> 1)] : 0, rb = b ? b->ref[(ib >> 3) * 2 + ((ib & 3) >> 1)] : 0;
     int ctx = (ra > 0) + 2 * (rb > 0);
+    g_mot[SG_M_REF_INC] |= 1 << ctx, g_mot[SG_M_REF_GE3] += ref >= 3;
     for (int k = 0; k < ref; k++) {
         sg_cabac_bin(&e->bw, 54 + ctx, 1);
         ctx = (ctx >> 2) + 4;
@@ -540,6 +558,7 @@ static void cabac_b_type_bin0(enc *e, int bin) {
     emb *a = MBA(e), *b = MBB(e);
     int inc = (a && a->type != T_BSKIP && a->type != T_BDIRECT) + (b && b->type != T_BSKIP && b->type != T_BDIRECT);
     sg_cabac_bin(&e->bw, 27 + inc, bin);
+    g_mot[SG_M_BTYPE_INC] |= 1 << inc;
 }
 static void cabac_b_intra_prefix(enc *e) { /* "111101", then the intra suffix at ctxIdxOffset 32 */
     sg_bw *w = &e->bw;
@@ -654,9 +673,32 @@ static void code_dqp(enc *e, int qp) {
 /* ------------------------------------------------------------------ motion vector prediction (8.4.1.3) */
 typedef struct {
     int ok, ref, x, y;
+    int inter, where, direct; /* an inter partition; 0 inside the macroblock, 1 .. 4 macroblock A, B, C, D; a direct quadrant of the current macroblock */
 } nmv;
+static int nmv_where(int bx, int by) { return bx >= 0 && bx <= 3 && by >= 0 ? 0 : (bx < 0 ? (by < 0 ? 4 : 1) : (bx > 3 ? 3 : 2)); }
+/* SG_M_PRED / SG_M_CSRC: one predictor that goes into the stream (e->quiet_pred: the 16x16 predictor of spatial direct prediction, which is no partition's) */
+static void mot_pred(const enc *e, int l, int shape, int rule, int csrc) {
+    const int slot = e->slice_type == 1 ? 1 + l : 0;
+    if (e->quiet_pred) return;
+    g_mot[SG_M_PRED + (slot * 5 + shape) * 8 + rule]++, g_mot[SG_M_CSRC + slot * 3 + csrc]++;
+}
+/* SG_M_GEO / SG_M_GEO_D / SG_M_NOLIST / SG_M_DIRECT_NB: the geometry of the same predictor: the partition at (bx, by), w x e->pred_h blocks; c_ok: C itself was
+ * there; n: A, B and what serves as C */
+static void mot_geo(const enc *e, int bx, int by, int w, int c_ok, int csrc, const nmv *n) {
+    if (e->quiet_pred) return;
+    const int h = e->pred_h, q = (by >> 1) * 2 + (bx >> 1);
+    const int pos = w == 4 ? (h == 4 ? 0 : 1 + (by >> 1)) : (h == 4 ? 3 + (bx >> 1) : (w == 2 ? (h == 2 ? 5 + q : 9 + 2 * q + (by & 1)) : (h == 2 ? 17 + 2 * q + (bx & 1) : 25 + 4 * q + 2 * (by & 1) + (bx & 1))));
+    const int cx = bx + w, cy = by - 1;
+    const int where = cy < 0 ? (c_ok ? (cx > 3 ? 3 : 2) : 4) : (cx > 3 ? 4 : (c_ok ? 0 : 1));
+    g_mot[SG_M_GEO + 5 * pos + where]++, g_mot[SG_M_GEO_D + pos] += csrc == 1;
+    for (int i = 0; i < 3; i++) {
+        if (n[i].ok && n[i].inter && n[i].ref < 0) g_mot[SG_M_NOLIST + n[i].where]++;
+        if (n[i].ref >= 0 && n[i].where == 0 && n[i].direct) g_mot[SG_M_DIRECT_NB + (e->p.direct_temporal != 0)]++;
+    }
+}
 static nmv get_nmv(enc *e, int bx, int by) {
     nmv r = {0, -1, 0, 0};
+    r.where = nmv_where(bx, by);
     emb *m;
     if (by >= 0 && bx > 3) return r;
     if (bx >= 0 && bx <= 3 && by >= 0) {
@@ -669,6 +711,7 @@ static nmv get_nmv(enc *e, int bx, int by) {
     }
     r.ok = 1;
     if (IS_INTRA(m->type)) return r;
+    r.inter = 1;
     r.ref = m->ref[(by >> 1) * 2 + (bx >> 1)];
     r.x = m->mv[by * 4 + bx][0];
     r.y = m->mv[by * 4 + bx][1];
@@ -678,26 +721,36 @@ static int mid3(int a, int b, int c) { return a > b ? (b > c ? b : (a > c ? c : 
 /* shape: 0 median, 1/2 = 16x8 upper/lower, 3/4 = 8x16 left/right */
 static void mv_pred(enc *e, int bx, int by, int w, int ref, int shape, int out[2]) {
     nmv A = get_nmv(e, bx - 1, by), B = get_nmv(e, bx, by - 1), C = get_nmv(e, bx + w, by - 1);
-    if (!C.ok) C = get_nmv(e, bx - 1, by - 1);
-    if (shape == 1 && B.ref == ref) { out[0] = B.x, out[1] = B.y; return; }
-    if ((shape == 2 || shape == 3) && A.ref == ref) { out[0] = A.x, out[1] = A.y; return; }
-    if (shape == 4 && C.ref == ref) { out[0] = C.x, out[1] = C.y; return; }
-    if (!B.ok && !C.ok && A.ok) B = A, C = A;
+    int csrc = 0;
+    const int c_ok = C.ok;
+    if (!C.ok) C = get_nmv(e, bx - 1, by - 1), csrc = C.ok ? 1 : 2;
+    {
+        const nmv n[3] = {A, B, C};
+        mot_geo(e, bx, by, w, c_ok, csrc, n);
+    }
+    if (shape == 1 && B.ref == ref) { out[0] = B.x, out[1] = B.y, mot_pred(e, 0, shape, 0, csrc); return; }
+    if ((shape == 2 || shape == 3) && A.ref == ref) { out[0] = A.x, out[1] = A.y, mot_pred(e, 0, shape, 0, csrc); return; }
+    if (shape == 4 && C.ref == ref) { out[0] = C.x, out[1] = C.y, mot_pred(e, 0, shape, 0, csrc); return; }
+    const int only_a = !B.ok && !C.ok && A.ok;
+    if (only_a) B = A, C = A;
     int hits = (A.ref == ref) + (B.ref == ref) + (C.ref == ref);
     if (hits == 1) {
         nmv s = A.ref == ref ? A : (B.ref == ref ? B : C);
         out[0] = s.x, out[1] = s.y;
+        mot_pred(e, 0, shape, only_a ? 1 : (A.ref == ref ? 2 : (B.ref == ref ? 3 : 4)), csrc);
         return;
     }
+    mot_pred(e, 0, shape, only_a ? 1 : (hits == 0 ? 5 : (hits == 2 ? 6 : 7)), csrc);
     out[0] = mid3(A.x, B.x, C.x);
     out[1] = mid3(A.y, B.y, C.y);
 }
 static void skip_mv(enc *e, int out[2]) {
     nmv A = get_nmv(e, -1, 0), B = get_nmv(e, 0, -1);
     out[0] = out[1] = 0;
-    if (!A.ok || !B.ok) return;
-    if ((A.ref == 0 && !A.x && !A.y) || (B.ref == 0 && !B.x && !B.y)) return;
-    mv_pred(e, 0, 0, 4, 0, 0, out);
+    const int why = !A.ok ? 0 : (!B.ok ? 1 : ((A.ref == 0 && !A.x && !A.y) ? 2 : ((B.ref == 0 && !B.x && !B.y) ? 3 : 4)));
+    e->pred_h = 4;
+    if (why == 4) mv_pred(e, 0, 0, 4, 0, 0, out);
+    g_mot[SG_M_PSKIP + (why == 4 && !out[0] && !out[1] ? 5 : why)]++;
 }
 static void fill_part(enc *e, int bx, int by, int w, int h, const int mv[2], const int mvd[2]) {
     emb *m = CURMB(e);
@@ -1054,6 +1107,7 @@ static void begin_mb(enc *e, int addr) {
     memset(m->ref1, -1, sizeof(m->ref1));
     for (int i = 0; i < 4; i++) m->refid[i] = m->refid1[i] = -1;
     e->done_l[0] = e->done_l[1] = 0, e->cur_sub = 3;
+    if (e->mvmb) memset(&e->mvmb[addr], 0, sizeof(sg_mvmb));
     memset(e->i16dc, 0, sizeof(e->i16dc));
     memset(e->luma, 0, sizeof(e->luma));
     memset(e->luma8, 0, sizeof(e->luma8));
@@ -1097,6 +1151,18 @@ static void end_mb(enc *e) {
         t->kind = (uint8_t)(m->type == T_I4 ? 1 : (m->type == T_I8 ? 2 : (m->type == T_I16 ? 3 : (m->type == T_PCM ? 4 : 0))));
         t->i16mode = m->i16mode, t->chroma_mode = m->chroma_mode, t->slice_id = m->slice_id;
         memcpy(t->ipm, m->ipm, sizeof(t->ipm));
+    }
+    if (e->mvmb) { /* (the signed mvd were put there by the macroblock's coder) */
+        sg_mvmb *t = &e->mvmb[e->addr];
+        static const uint8_t kinds[12] = {0, 0, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7}; /* by T_* */
+        const int written = m->type >= T_P16 && m->type <= T_P8x8, ref0 = e->slice_type == 0 && e->raw_type == 4; /* P_8x8ref0: no ref_idx */
+        t->kind = kinds[m->type], t->raw = (int8_t)(written || m->type == T_BDIRECT ? e->raw_type : -1), t->direct8 = m->direct8, t->slice = m->slice_id;
+        memcpy(t->sub, m->sub, sizeof(t->sub));
+        memcpy(t->mv[0], m->mv, sizeof(m->mv)), memcpy(t->mv[1], m->mv1, sizeof(m->mv1));
+        for (int q = 0; q < 4; q++) {
+            t->ref[0][q] = IS_INTRA(m->type) ? -1 : m->ref[q], t->ref[1][q] = IS_INTRA(m->type) ? -1 : m->ref1[q];
+            for (int l = 0; l < 2; l++) t->ref_idx[l][q] = (int8_t)(written && !ref0 && !(m->direct8 >> q & 1) ? t->ref[l][q] : -1);
+        }
     }
 }
 
@@ -1453,6 +1519,7 @@ static void pick_mv(enc *e, int x, int y, int w, int h, sg_pic *ref, const int m
             if (s < bs) bs = s, best = i;
         }
     out[0] = cand[best][0], out[1] = cand[best][1];
+    if (e->force_mv) out[0] = e->forced[0], out[1] = e->forced[1], e->force_mv = 0; /* sg_params::motion_stim */
     /* keep the displaced block within 32 samples of the picture so that streams stay level-conformant */
     int minx = -4 * (x + margin), maxx = 4 * (e->W - x - w + margin), miny = -4 * (y + margin), maxy = 4 * (e->H - y - h + margin);
     out[0] = out[0] < minx ? minx : (out[0] > maxx ? maxx : out[0]);
@@ -1506,6 +1573,42 @@ typedef struct {
     int bx, by, w, h, shape, mvd[2];
 } part;
 
+/* sg_params::motion_stim, the least-visited choice: how often each candidate of a draw was taken in this sg_encode() call -- P macroblock kinds (mb_type 0..3,
+ * and 4 = P_8x8ref0 where it can be written), B mb_type 1..22, sub_mb_type of P and of B slices, ref_idx values per list.  Per thread. */
+static _Thread_local uint32_t g_mvis_ptype[5], g_mvis_btype[22], g_mvis_psub[4], g_mvis_bsub[13], g_mvis_ref[2][4];
+/* the allowed candidate (bit i of `allowed`) of 0 .. n - 1 that was taken least often; among equals the drawn one, then the next after it */
+static int least_visited(uint32_t *visits, int n, uint32_t allowed, int drawn) {
+    int best = -1;
+    for (int k = 0; k < n; k++) {
+        const int i = (drawn + k) % n;
+        if ((allowed >> i & 1) && (best < 0 || visits[i] < visits[best])) best = i;
+    }
+    if (best < 0) return drawn;
+    visits[best]++;
+    return best;
+}
+/* ref_idx of list l: the drawn value, or under motion_stim the least-visited index that the list's size and the reference barrier allow */
+static int stim_ref(enc *e, int l, int nref, int drawn) {
+    if (e->p.motion_stim != 1) return drawn;
+    return least_visited(g_mvis_ref[l], nref < 4 ? nref : 4, e->allow[l], drawn);
+}
+/* sg_params::motion_stim: one partition in four is told which vector to take (see sg.h).  n[3]: its neighbours A, B, C (D where C is not there) */
+static void stim_force_mv(enc *e, const nmv n[3], int ref) {
+    static const int8_t near0[5] = {-2, -1, 0, 1, 2};
+    e->force_mv = 0;
+    if (e->p.motion_stim != 1 || rnd(e) % 4) return;
+    const int r = (int)(rnd(e) % 5);
+    if (r < 3) {
+        if (n[r].ref < 0) return;
+        e->forced[0] = n[r].x, e->forced[1] = n[r].y;
+    } else if (r == 3) {
+        if (ref != 0) return;
+        e->forced[0] = e->forced[1] = 0;
+    } else
+        e->forced[0] = near0[rnd(e) % 5], e->forced[1] = near0[rnd(e) % 5];
+    e->force_mv = 1;
+}
+
 static void set_refids(enc *e, emb *m) {
     for (int i = 0; i < 4; i++) m->refid[i] = m->ref[i] >= 0 ? e->refs[m->ref[i]]->id : -1;
 }
@@ -1533,11 +1636,16 @@ static void encode_inter(enc *e, int kind) {
     sg_bw *w = &e->bw;
     int cabac = e->p.cabac, nref = e->nref_active;
     part parts[16];
-    int np = 0;
+    int np = 0, all_ref0 = 0;
+    if (e->p.motion_stim == 1) { /* the kind taken least often so far; P_8x8ref0 is a fifth kind where it can be written */
+        const int pick = least_visited(g_mvis_ptype, !cabac && nref > 1 && (e->allow[0] & 1) ? 5 : 4, ~0u, kind - T_P16);
+        all_ref0 = pick == 4, kind = pick == 4 ? T_P8x8 : T_P16 + pick;
+    }
     m->type = (uint8_t)kind;
     /* reference indices */
     int refs4[4];
-    for (int i = 0; i < 4; i++) refs4[i] = barrier_ref(e, 0, (nref > 1 && rnd(e) % 100 < 35) ? rnd_range(e, 0, nref - 1) : 0);
+    for (int i = 0; i < 4; i++) refs4[i] = stim_ref(e, 0, nref, barrier_ref(e, 0, (nref > 1 && rnd(e) % 100 < 35) ? rnd_range(e, 0, nref - 1) : 0));
+    if (all_ref0) refs4[0] = refs4[1] = refs4[2] = refs4[3] = 0;
     if (kind == T_P16)
         refs4[1] = refs4[2] = refs4[3] = refs4[0];
     else if (kind == T_P16x8)
@@ -1557,6 +1665,7 @@ static void encode_inter(enc *e, int kind) {
     } else
         for (int i = 0; i < 4; i++) {
             int bx = (i & 1) * 2, by = (i >> 1) * 2, st = rnd(e) % 100 < 55 ? 0 : rnd_range(e, 1, 3);
+            if (e->p.motion_stim == 1) st = least_visited(g_mvis_psub, 4, ~0u, st);
             m->sub[i] = (uint8_t)st;
             if (st == 0)
                 parts[np++] = (part){bx, by, 2, 2, 0, {0, 0}};
@@ -1578,10 +1687,17 @@ static void encode_inter(enc *e, int kind) {
     for (int i = 0; i < np; i++) {
         part *p = &parts[i];
         int mvp[2], mv[2], ref = m->ref[(p->by >> 1) * 2 + (p->bx >> 1)];
+        e->pred_h = p->h;
         mv_pred(e, p->bx, p->by, p->w, ref, p->shape, mvp);
+        if (e->p.motion_stim == 1) {
+            nmv n[3] = {get_nmv(e, p->bx - 1, p->by), get_nmv(e, p->bx, p->by - 1), get_nmv(e, p->bx + p->w, p->by - 1)};
+            if (!n[2].ok) n[2] = get_nmv(e, p->bx - 1, p->by - 1);
+            stim_force_mv(e, n, ref);
+        }
         pick_mv(e, e->mbx * 16 + p->bx * 4, e->mby * 16 + p->by * 4, p->w * 4, p->h * 4, e->refs[ref], mvp, mv);
         p->mvd[0] = mv[0] - mvp[0], p->mvd[1] = mv[1] - mvp[1];
         fill_part(e, p->bx, p->by, p->w, p->h, mv, p->mvd);
+        if (e->mvmb) e->mvmb[e->addr].mvd[0][p->by * 4 + p->bx][0] = (int16_t)p->mvd[0], e->mvmb[e->addr].mvd[0][p->by * 4 + p->bx][1] = (int16_t)p->mvd[1];
         mc_part(e, p->bx, p->by, p->w, p->h, py, pc);
     }
     int qp = want_qp(e);
@@ -1596,7 +1712,11 @@ static void encode_inter(enc *e, int kind) {
     code_chroma(e, 0, pc);
     /* ---- syntax ---- */
     int raw = kind == T_P16 ? 0 : (kind == T_P16x8 ? 1 : (kind == T_P8x16 ? 2 : 3));
+    /* sg_params::motion_stim: P_8x8ref0 (CAVLC only, Table 7-13): four indices of 0 that are not written */
+    const int ref0 = e->p.motion_stim == 1 && !cabac && nref > 1 && kind == T_P8x8 && !(m->ref[0] | m->ref[1] | m->ref[2] | m->ref[3]);
+    if (ref0) raw = 4;
     e->raw_type = raw;
+    g_mot[SG_M_MBTYPE_P] |= 1 << raw;
     if (cabac) {
         sg_cabac_bin(w, 14, 0);
         if (raw == 0 || raw == 3) {
@@ -1610,6 +1730,7 @@ static void encode_inter(enc *e, int kind) {
         sg_put_ue(w, (uint32_t)raw);
     if (kind == T_P8x8)
         for (int i = 0; i < 4; i++) {
+            g_mot[SG_M_SUBTYPE_P] |= 1 << m->sub[i];
             if (cabac) {
                 int st = m->sub[i];
                 sg_cabac_bin(w, 21, st == 0);
@@ -1620,7 +1741,7 @@ static void encode_inter(enc *e, int kind) {
             } else
                 sg_put_ue(w, m->sub[i]);
         }
-    if (nref > 1) {
+    if (nref > 1 && !ref0) {
         /* the CABAC ctxIdxInc for ref_idx looks at refs of neighbouring partitions in *this* MB too: they
          * are already final in m->ref[], but partitions that come later must read as "not yet known" =
          * they are never consulted (A/B neighbours always precede). */
@@ -1639,7 +1760,7 @@ static void encode_inter(enc *e, int kind) {
             if (cabac)
                 cabac_ref(e, bx, by, ref);
             else
-                sg_put_te(w, nref - 1, (uint32_t)ref);
+                mot_te(nref - 1, ref), sg_put_te(w, nref - 1, (uint32_t)ref);
         }
     }
     for (int i = 0; i < np; i++) {
@@ -1688,6 +1809,7 @@ static void encode_inter(enc *e, int kind) {
 
 static nmv get_nmv_l(enc *e, int l, int bx, int by) {
     nmv r = {0, -1, 0, 0};
+    r.where = nmv_where(bx, by);
     emb *m;
     if (by >= 0 && bx > 3) return r;
     if (bx >= 0 && bx <= 3 && by >= 0) {
@@ -1701,6 +1823,7 @@ static nmv get_nmv_l(enc *e, int l, int bx, int by) {
     }
     r.ok = 1;
     if (IS_INTRA(m->type)) return r;
+    r.inter = 1, r.direct = r.where == 0 && (m->direct8 >> ((by >> 1) * 2 + (bx >> 1)) & 1);
     r.ref = EREF(m, l)[(by >> 1) * 2 + (bx >> 1)];
     if (r.ref < 0) return r;
     r.x = EMV(m, l)[by * 4 + bx][0];
@@ -1709,17 +1832,26 @@ static nmv get_nmv_l(enc *e, int l, int bx, int by) {
 }
 static void mv_pred_l(enc *e, int l, int bx, int by, int w, int ref, int shape, int out[2]) {
     nmv A = get_nmv_l(e, l, bx - 1, by), B = get_nmv_l(e, l, bx, by - 1), C = get_nmv_l(e, l, bx + w, by - 1);
-    if (!C.ok) C = get_nmv_l(e, l, bx - 1, by - 1);
-    if (shape == 1 && B.ref == ref) { out[0] = B.x, out[1] = B.y; return; }
-    if ((shape == 2 || shape == 3) && A.ref == ref) { out[0] = A.x, out[1] = A.y; return; }
-    if (shape == 4 && C.ref == ref) { out[0] = C.x, out[1] = C.y; return; }
-    if (!B.ok && !C.ok && A.ok) B = A, C = A;
+    int csrc = 0;
+    const int c_ok = C.ok;
+    if (!C.ok) C = get_nmv_l(e, l, bx - 1, by - 1), csrc = C.ok ? 1 : 2;
+    {
+        const nmv n[3] = {A, B, C};
+        mot_geo(e, bx, by, w, c_ok, csrc, n);
+    }
+    if (shape == 1 && B.ref == ref) { out[0] = B.x, out[1] = B.y, mot_pred(e, l, shape, 0, csrc); return; }
+    if ((shape == 2 || shape == 3) && A.ref == ref) { out[0] = A.x, out[1] = A.y, mot_pred(e, l, shape, 0, csrc); return; }
+    if (shape == 4 && C.ref == ref) { out[0] = C.x, out[1] = C.y, mot_pred(e, l, shape, 0, csrc); return; }
+    const int only_a = !B.ok && !C.ok && A.ok;
+    if (only_a) B = A, C = A;
     int hits = (A.ref == ref) + (B.ref == ref) + (C.ref == ref);
     if (hits == 1) {
         nmv s = A.ref == ref ? A : (B.ref == ref ? B : C);
         out[0] = s.x, out[1] = s.y;
+        mot_pred(e, l, shape, only_a ? 1 : (A.ref == ref ? 2 : (B.ref == ref ? 3 : 4)), csrc);
         return;
     }
+    mot_pred(e, l, shape, only_a ? 1 : (hits == 0 ? 5 : (hits == 2 ? 6 : 7)), csrc);
     out[0] = mid3(A.x, B.x, C.x);
     out[1] = mid3(A.y, B.y, C.y);
 }
@@ -1738,6 +1870,7 @@ static void cabac_mvd_l(enc *e, int l, int comp, int bx, int by, int v) {
     emb *a = lnb(e, bx - 1, by, &ia), *b = lnb(e, bx, by - 1, &ib);
     int sum = (a ? EMVD(a, l)[ia][comp] : 0) + (b ? EMVD(b, l)[ib][comp] : 0), base = comp ? 47 : 40, m = abs(v);
     sg_cabac_bin(w, base + (sum > 2) + (sum > 32), m != 0);
+    g_mot[SG_M_MVD_BAND + 3 * comp + (sum > 2) + (sum > 32)]++, g_mot[SG_M_MVD_SUFFIX] += m >= 9;
     if (!m) return;
     int ctx = base + 3;
     for (int k = 1; k < (m < 9 ? m : 9); k++) {
@@ -1765,6 +1898,8 @@ static void cabac_ref_l(enc *e, int l, int bx, int by, int ref) {
     /* quadrants predicted in direct mode count as refIdx 0 here (9.3.3.1.1.6) */
     int ra = (a && !(a->direct8 >> qa & 1)) ? EREF(a, l)[qa] : 0, rb = (b && !(b->direct8 >> qb & 1)) ? EREF(b, l)[qb] : 0;
     int ctx = (ra > 0) + 2 * (rb > 0);
+    g_mot[SG_M_REF_INC] |= 1 << ctx, g_mot[SG_M_REF_GE3] += ref >= 3;
+    g_mot[SG_M_REF_DIRECT_NB] += (a && (a->direct8 >> qa & 1)) || (b && (b->direct8 >> qb & 1));
     for (int k = 0; k < ref; k++) {
         sg_cabac_bin(&e->bw, 54 + ctx, 1);
         ctx = (ctx >> 2) + 4;
@@ -1772,16 +1907,21 @@ static void cabac_ref_l(enc *e, int l, int bx, int by, int ref) {
     sg_cabac_bin(&e->bw, 54 + ctx, 0);
 }
 
-/* co-located block of (bx, by) in RefPicList1[0] (direct_8x8_inference_flag = 1: the corner block of the quadrant) */
+/* co-located block of (bx, by) in RefPicList1[0] (direct_8x8_inference_flag = 1: the corner block of the quadrant; 0, sg_params::direct_4x4: the block itself) */
 static int col_block(enc *e, int bx, int by, int mv[2], int *pic_id) {
     const sg_pic *col = e->refs1[0];
     const emb *cm = col && col->motion ? &((const emb *)col->motion)[e->addr] : NULL;
     mv[0] = mv[1] = 0, *pic_id = -1;
     if (!cm || !IS_INTER(cm->type)) return -1;
-    int cx = (bx >> 1) * 3, cy = (by >> 1) * 3, q = (cy >> 1) * 2 + (cx >> 1), l = cm->ref[q] >= 0 ? 0 : 1;
+    int cx = e->p.direct_4x4 ? bx : (bx >> 1) * 3, cy = e->p.direct_4x4 ? by : (by >> 1) * 3, q = (cy >> 1) * 2 + (cx >> 1), l = cm->ref[q] >= 0 ? 0 : 1;
     if (EREF(cm, l)[q] < 0) return -1;
     mv[0] = EMV(cm, l)[cy * 4 + cx][0], mv[1] = EMV(cm, l)[cy * 4 + cx][1];
+    if (!e->p.direct_4x4 && !e->quiet_pred) { /* the corner against the first block of the quadrant */
+        const int first = (by >> 1) * 8 + (bx >> 1) * 2;
+        g_mot[SG_M_COL_CORNER] += EMV(cm, l)[first][0] != mv[0] || EMV(cm, l)[first][1] != mv[1];
+    }
     *pic_id = EREFID(cm, l)[q];
+    e->col_list = 1 + l;
     return EREF(cm, l)[q];
 }
 static int poc_clip(int v) { return v < -128 ? -128 : (v > 127 ? 127 : v); }
@@ -1798,37 +1938,65 @@ static int dist_scale(int cur, int p0, int p1, int lt, int *dsf) {
 static void b_direct(enc *e, int mask8) {
     emb *m = CURMB(e);
     const int zero[2] = {0, 0};
+    if (e->p.direct_4x4) /* SG_M_COL_FOUR */
+        for (int q = 0; q < 4; q++) {
+            int v[4][2], id, unlike = 1;
+            if (!(mask8 >> q & 1)) continue;
+            for (int k = 0; k < 4; k++) col_block(e, (q & 1) * 2 + (k & 1), (q >> 1) * 2 + (k >> 1), v[k], &id);
+            for (int i = 0; i < 4; i++)
+                for (int j = i + 1; j < 4; j++) unlike &= v[i][0] != v[j][0] || v[i][1] != v[j][1];
+            g_mot[SG_M_COL_FOUR] += unlike;
+        }
+    if (e->p.direct_temporal) g_mot[m->type == T_P8x8 ? SG_M_TD_QUADRANT : SG_M_TD_MB16]++;
     if (!e->p.direct_temporal) { /* spatial: reference indices and vectors from the neighbours A, B, C of the macroblock */
         int ref[2], mvp[2][2] = {{0, 0}, {0, 0}};
         for (int l = 0; l < 2; l++) {
             nmv A = get_nmv_l(e, l, -1, 0), B = get_nmv_l(e, l, 0, -1), C = get_nmv_l(e, l, 4, -1);
             if (!C.ok) C = get_nmv_l(e, l, -1, -1);
-            int r = -1; /* the smallest non-negative one */
-            if (A.ref >= 0) r = A.ref;
-            if (B.ref >= 0 && (r < 0 || B.ref < r)) r = B.ref;
-            if (C.ref >= 0 && (r < 0 || C.ref < r)) r = C.ref;
+            int r = -1, src = 3; /* the smallest non-negative one */
+            if (A.ref >= 0) r = A.ref, src = 0;
+            if (B.ref >= 0 && (r < 0 || B.ref < r)) r = B.ref, src = 1;
+            if (C.ref >= 0 && (r < 0 || C.ref < r)) r = C.ref, src = 2;
             ref[l] = r;
+            g_mot[SG_M_SD_REF + 4 * l + src]++;
         }
-        if (ref[0] < 0 && ref[1] < 0)
-            ref[0] = ref[1] = 0;
+        const int bothneg = ref[0] < 0 && ref[1] < 0;
+        e->quiet_pred = 1;
+        if (bothneg)
+            ref[0] = ref[1] = 0, g_mot[SG_M_SD_BOTHNEG]++;
         else
             for (int l = 0; l < 2; l++)
                 if (ref[l] >= 0) mv_pred_l(e, l, 0, 0, 4, ref[l], 0, mvp[l]);
+        e->quiet_pred = 0;
         int col_is_short = e->refs1[0] && e->refs1[0]->is_ref == 1;
         for (int q = 0; q < 4; q++) {
             if (!(mask8 >> q & 1)) continue;
-            int cmv[2], cid, cref = col_block(e, (q & 1) * 2, (q >> 1) * 2, cmv, &cid);
-            int still = col_is_short && cref == 0 && abs(cmv[0]) <= 1 && abs(cmv[1]) <= 1; /* colZeroFlag */
-            for (int l = 0; l < 2; l++) {
-                EREF(m, l)[q] = (int8_t)ref[l];
-                fill_part_l(e, l, (q & 1) * 2, (q >> 1) * 2, 2, 2, (ref[l] < 0 || (ref[l] == 0 && still)) ? zero : mvp[l], zero);
+            for (int k = 0; k < (e->p.direct_4x4 ? 4 : 1); k++) { /* per quadrant, or per 4x4 block of it */
+                const int bx = (q & 1) * 2 + (k & 1), by = (q >> 1) * 2 + (k >> 1), n = e->p.direct_4x4 ? 1 : 2;
+                int cmv[2], cid, cref = col_block(e, bx, by, cmv, &cid);
+                int still = col_is_short && cref == 0 && abs(cmv[0]) <= 1 && abs(cmv[1]) <= 1; /* colZeroFlag */
+                g_mot[SG_M_COL + (cref < 0 ? 0 : e->col_list)] += n * n;
+                g_mot[SG_M_SD_COL + !col_is_short] += n * n;
+                if (cref >= 0) g_mot[SG_M_SD_REFCOL + (cref > 0)] += n * n;
+                for (int c = 0; c < 2 && col_is_short && cref == 0; c++)
+                    if (abs(cmv[c]) <= 2 && abs(cmv[1 - c]) <= 1) g_mot[SG_M_SD_MVCOL + 5 * c + cmv[c] + 2] += n * n;
+                for (int l = 0; l < 2; l++) {
+                    EREF(m, l)[q] = (int8_t)ref[l];
+                    fill_part_l(e, l, bx, by, n, n, (ref[l] < 0 || (ref[l] == 0 && still)) ? zero : mvp[l], zero);
+                    if (ref[l] < 0) g_mot[SG_M_SD_OUT + 4 * l] += n * n;
+                    else if (bothneg) continue;
+                    else if (ref[l] == 0) g_mot[SG_M_SD_OUT + 4 * l + (still ? 1 : 2)] += n * n;
+                    else if (still) g_mot[SG_M_SD_OUT + 4 * l + 3] += n * n;
+                }
             }
         }
         return;
     }
     for (int q = 0; q < 4; q++) { /* temporal: the co-located vector scaled by the POC distances */
         if (!(mask8 >> q & 1)) continue;
-        int cmv[2], cid, cref = col_block(e, (q & 1) * 2, (q >> 1) * 2, cmv, &cid), r0 = 0;
+      for (int k = 0; k < (e->p.direct_4x4 ? 4 : 1); k++) {
+        const int bx = (q & 1) * 2 + (k & 1), by = (q >> 1) * 2 + (k >> 1), n = e->p.direct_4x4 ? 1 : 2;
+        int cmv[2], cid, cref = col_block(e, bx, by, cmv, &cid), r0 = 0;
         if (cref >= 0) {
             r0 = -1;
             for (int i = 0; i < e->nref_active && r0 < 0; i++)
@@ -1839,13 +2007,17 @@ static void b_direct(enc *e, int mask8) {
             }
         }
         int dsf = 0, mv0[2], mv1[2];
+        g_mot[SG_M_COL + (cref < 0 ? 0 : e->col_list)] += n * n, g_mot[SG_M_TD_REF + (r0 > 0)] += n * n;
+        if (e->refs[r0]->is_ref == 2) g_mot[SG_M_TD_LONG] += n * n;
         if (dist_scale(e->cur_poc, e->refs[r0]->poc, e->refs1[0]->poc, e->refs[r0]->is_ref == 2, &dsf)) {
             for (int c = 0; c < 2; c++) mv0[c] = (dsf * cmv[c] + 128) >> 8, mv1[c] = mv0[c] - cmv[c];
+            if ((cmv[0] < 0 && ((dsf * cmv[0] + 128) & 255)) || (cmv[1] < 0 && ((dsf * cmv[1] + 128) & 255))) g_mot[SG_M_TD_NEG_REMAINDER] += n * n;
         } else
             mv0[0] = cmv[0], mv0[1] = cmv[1], mv1[0] = mv1[1] = 0;
         m->ref[q] = (int8_t)r0, m->ref1[q] = 0;
-        fill_part_l(e, 0, (q & 1) * 2, (q >> 1) * 2, 2, 2, mv0, zero);
-        fill_part_l(e, 1, (q & 1) * 2, (q >> 1) * 2, 2, 2, mv1, zero);
+        fill_part_l(e, 0, bx, by, n, n, mv0, zero);
+        fill_part_l(e, 1, bx, by, n, n, mv1, zero);
+      }
     }
 }
 
@@ -1928,7 +2100,20 @@ static void encode_b(enc *e, int kind) {
     sg_bw *w = &e->bw;
     const int cabac = e->p.cabac;
     bpart pt[16];
-    int np = 0, raw = 0;
+    int np = 0, raw = 0, sm0 = 0, sm1 = 0;
+    if (e->p.motion_stim == 1 && kind >= T_P16 && kind <= T_P8x8) { /* the mb_type 1 .. 22 taken least often so far: kind and prediction modes in one */
+        const int d0 = 1 + (int)(rnd(e) % 3), d1 = 1 + (int)(rnd(e) % 3);
+        int k = 0;
+        while (b_pair_modes[k][0] != d0 || b_pair_modes[k][1] != d1) k++;
+        const int drawn = kind == T_P16 ? d0 : (kind == T_P8x8 ? 22 : 4 + 2 * k + (kind == T_P8x16));
+        const int pick = 1 + least_visited(g_mvis_btype, 22, ~0u, drawn - 1);
+        if (pick <= 3)
+            kind = T_P16, sm0 = pick;
+        else if (pick == 22)
+            kind = T_P8x8;
+        else
+            kind = pick & 1 ? T_P8x16 : T_P16x8, sm0 = b_pair_modes[(pick - 4) / 2][0], sm1 = b_pair_modes[(pick - 4) / 2][1];
+    }
     m->type = (uint8_t)kind;
     if (kind == T_BSKIP || kind == T_BDIRECT) {
         m->direct8 = 15;
@@ -1937,6 +2122,7 @@ static void encode_b(enc *e, int kind) {
         raw = 22;
         for (int i = 0; i < 4; i++) {
             int st = (int)(rnd(e) % 13);
+            if (e->p.motion_stim == 1) st = least_visited(g_mvis_bsub, 13, ~0u, st);
             m->sub[i] = (uint8_t)st;
             if (b_sub_mode[st] == 0) m->direct8 |= (uint8_t)(1 << i);
         }
@@ -1957,6 +2143,7 @@ static void encode_b(enc *e, int kind) {
         }
     } else {
         int m0 = 1 + (int)(rnd(e) % 3), m1 = 1 + (int)(rnd(e) % 3);
+        if (sm0) m0 = sm0, m1 = sm1 ? sm1 : m1;
         if (kind == T_P16) {
             raw = m0;
             pt[np++] = (bpart){0, 0, 4, 4, 0, m0, 3, {{0, 0}, {0, 0}}};
@@ -1975,12 +2162,12 @@ static void encode_b(enc *e, int kind) {
     for (int l = 0; l < 2; l++) {
         if (kind == T_P8x8) { /* one index per non-direct quadrant that uses the list */
             for (int i = 0; i < 4; i++)
-                if (b_sub_mode[m->sub[i]] >> l & 1) EREF(m, l)[i] = (int8_t)barrier_ref(e, l, (nref[l] > 1 && rnd(e) % 100 < 35) ? rnd_range(e, 0, nref[l] - 1) : 0);
+                if (b_sub_mode[m->sub[i]] >> l & 1) EREF(m, l)[i] = (int8_t)stim_ref(e, l, nref[l], barrier_ref(e, l, (nref[l] > 1 && rnd(e) % 100 < 35) ? rnd_range(e, 0, nref[l] - 1) : 0));
             continue;
         }
         for (int i = 0; i < np; i++) {
             if (!(pt[i].mode >> l & 1)) continue;
-            int r = barrier_ref(e, l, (nref[l] > 1 && rnd(e) % 100 < 35) ? rnd_range(e, 0, nref[l] - 1) : 0);
+            int r = stim_ref(e, l, nref[l], barrier_ref(e, l, (nref[l] > 1 && rnd(e) % 100 < 35) ? rnd_range(e, 0, nref[l] - 1) : 0));
             for (int y = pt[i].by >> 1; y < (pt[i].by + pt[i].h + 1) >> 1; y++)
                 for (int x = pt[i].bx >> 1; x < (pt[i].bx + pt[i].w + 1) >> 1; x++) EREF(m, l)[y * 2 + x] = (int8_t)r;
         }
@@ -1997,10 +2184,17 @@ static void encode_b(enc *e, int kind) {
             }
             int mvp[2], mv[2], ref = EREF(m, l)[(p->by >> 1) * 2 + (p->bx >> 1)];
             e->cur_sub = p->sub;
+            e->pred_h = p->h;
             mv_pred_l(e, l, p->bx, p->by, p->w, ref, p->shape, mvp);
+            if (e->p.motion_stim == 1) {
+                nmv n[3] = {get_nmv_l(e, l, p->bx - 1, p->by), get_nmv_l(e, l, p->bx, p->by - 1), get_nmv_l(e, l, p->bx + p->w, p->by - 1)};
+                if (!n[2].ok) n[2] = get_nmv_l(e, l, p->bx - 1, p->by - 1);
+                stim_force_mv(e, n, ref);
+            }
             pick_mv(e, e->mbx * 16 + p->bx * 4, e->mby * 16 + p->by * 4, p->w * 4, p->h * 4, l ? e->refs1[ref] : e->refs[ref], mvp, mv);
             p->mvd[l][0] = mv[0] - mvp[0], p->mvd[l][1] = mv[1] - mvp[1];
             fill_part_l(e, l, p->bx, p->by, p->w, p->h, mv, p->mvd[l]);
+            if (e->mvmb) e->mvmb[e->addr].mvd[l][p->by * 4 + p->bx][0] = (int16_t)p->mvd[l][0], e->mvmb[e->addr].mvd[l][p->by * 4 + p->bx][1] = (int16_t)p->mvd[l][1];
         }
     e->cur_sub = 3;
     for (int i = 0; i < 4; i++) {
@@ -2020,22 +2214,25 @@ static void encode_b(enc *e, int kind) {
     }
     int qp = want_qp(e);
     set_qpc(e, m, qp);
-    int all8 = 1; /* no sub-partition smaller than 8x8 (direct quadrants count as 8x8: direct_8x8_inference_flag = 1) */
+    int all8 = 1; /* no sub-partition smaller than 8x8 (direct quadrants count as 8x8 with direct_8x8_inference_flag = 1, as 4x4 without it: 7.3.5) */
     if (kind == T_P8x8)
         for (int i = 0; i < 4; i++)
             if (b_sub_shape[m->sub[i]]) all8 = 0;
+    if (e->p.direct_4x4 && m->direct8) all8 = 0;
     m->t8x8 = (e->p.transform8x8 && all8 && rnd(e) % 2) ? 1 : 0;
     code_luma_inter(e, py);
     if (!m->cbp_luma) m->t8x8 = 0;
     code_chroma(e, 0, pc);
     /* ---- syntax ---- */
     e->raw_type = raw;
+    g_mot[SG_M_MBTYPE_B] |= 1 << raw;
     if (cabac)
         cabac_b_mb_type(e, raw);
     else
         sg_put_ue(w, (uint32_t)raw);
     if (kind == T_P8x8)
         for (int i = 0; i < 4; i++) {
+            g_mot[SG_M_SUBTYPE_B] |= 1 << m->sub[i];
             if (cabac)
                 cabac_b_sub_type(e, m->sub[i]);
             else
@@ -2049,7 +2246,7 @@ static void encode_b(enc *e, int kind) {
                 if (cabac)
                     cabac_ref_l(e, l, (i & 1) * 2, (i >> 1) * 2, EREF(m, l)[i]);
                 else
-                    sg_put_te(w, nref[l] - 1, (uint32_t)EREF(m, l)[i]);
+                    mot_te(nref[l] - 1, EREF(m, l)[i]), sg_put_te(w, nref[l] - 1, (uint32_t)EREF(m, l)[i]);
             }
             continue;
         }
@@ -2059,7 +2256,7 @@ static void encode_b(enc *e, int kind) {
             if (cabac)
                 cabac_ref_l(e, l, pt[i].bx, pt[i].by, ref);
             else
-                sg_put_te(w, nref[l] - 1, (uint32_t)ref);
+                mot_te(nref[l] - 1, ref), sg_put_te(w, nref[l] - 1, (uint32_t)ref);
         }
     }
     for (int l = 0; l < 2; l++)
@@ -2212,7 +2409,7 @@ static size_t write_sps(enc *e, uint8_t *dst, size_t cap) {
         sg_put_ue(&w, (uint32_t)(e->fH / 16 - 1));
         sg_put(&w, 1, 1); /* frame_mbs_only */
     }
-    sg_put(&w, 1, 1); /* direct_8x8_inference */
+    sg_put(&w, !p->direct_4x4, 1); /* direct_8x8_inference */
     /* CropUnitX x CropUnitY (7.4.2.1.1): SubWidthC x SubHeightC * (2 - frame_mbs_only_flag); monochrome: 1 x (2 - frame_mbs_only_flag) */
     int ux = p->mono ? 1 : 2, uy = (p->mono ? 1 : 2) * (p->interlace_sps ? 2 : 1);
     int cr = (e->W - p->width) / ux, cb = (e->fH - p->height) / uy;
@@ -2549,6 +2746,49 @@ int sg_last_intra_trace(int index, int32_t info[9], uint8_t *pred, int16_t *res,
     }
     return g_ntrace;
 }
+/* sg_params::trace_motion: per thread, like the counters */
+typedef struct {
+    int32_t info[8];
+    sg_mvmb *mbs;
+    sg_mvslice *slices;
+} mv_trace;
+static _Thread_local mv_trace *g_mtrace;
+static _Thread_local int g_nmtrace, g_mtrace_cap;
+static void motion_trace_clear(void) {
+    for (int i = 0; i < g_nmtrace; i++) free(g_mtrace[i].mbs), free(g_mtrace[i].slices);
+    g_nmtrace = 0;
+}
+static void trace_motion_picture(enc *e, int frame) {
+    const size_t msz = sizeof(sg_mvmb) * (size_t)e->wmb * e->hmb, ssz = sizeof(sg_mvslice) * (size_t)(e->n_mvsl ? e->n_mvsl : 1);
+    if (g_nmtrace == g_mtrace_cap) {
+        mv_trace *n = (mv_trace *)realloc(g_mtrace, sizeof(mv_trace) * (size_t)(g_mtrace_cap ? 2 * g_mtrace_cap : 16));
+        if (!n) return;
+        g_mtrace = n, g_mtrace_cap = g_mtrace_cap ? 2 * g_mtrace_cap : 16;
+    }
+    mv_trace *t = &g_mtrace[g_nmtrace];
+    t->mbs = (sg_mvmb *)malloc(msz), t->slices = (sg_mvslice *)malloc(ssz);
+    if (!t->mbs || !t->slices) {
+        free(t->mbs), free(t->slices);
+        return;
+    }
+    for (int s = 0; s < e->n_mvsl; s++) /* RefPicList1[0] among the pictures traced so far (the latest one of that identity) */
+        for (int i = g_nmtrace - 1; i >= 0 && e->mvsl[s].type == 1 && e->mvsl[s].col_index < 0; i--)
+            if (g_mtrace[i].info[4] == e->mvsl[s].pic[1][0]) e->mvsl[s].col_index = i;
+    const int32_t info[8] = {e->wmb, e->hmb, e->field ? 1 + e->bottom : 0, frame, e->cur->id, e->n_mvsl, (int32_t)sizeof(sg_mvmb), (int32_t)sizeof(sg_mvslice)};
+    memcpy(t->info, info, sizeof(info));
+    memcpy(t->mbs, e->mvmb, msz), memcpy(t->slices, e->mvsl, sizeof(sg_mvslice) * (size_t)e->n_mvsl);
+    g_nmtrace++;
+}
+int sg_last_motion_trace(int index, int32_t info[8], void *mbs, size_t mbs_cap, void *slices, size_t slices_cap) {
+    if (index >= 0 && index < g_nmtrace) {
+        const mv_trace *t = &g_mtrace[index];
+        const size_t msz = sizeof(sg_mvmb) * (size_t)t->info[0] * t->info[1], ssz = sizeof(sg_mvslice) * (size_t)t->info[5];
+        if (info) memcpy(info, t->info, sizeof(t->info));
+        if (mbs && mbs_cap >= msz) memcpy(mbs, t->mbs, msz);
+        if (slices && slices_cap >= ssz) memcpy(slices, t->slices, ssz);
+    }
+    return g_nmtrace;
+}
 int sg_last_pocs(int32_t *dst, int cap) {
     for (int i = 0; i < g_npocs && i < cap && dst; i++) dst[i] = g_pocs[i];
     return g_npocs;
@@ -2697,6 +2937,9 @@ static void plan_b_lists(enc *e) {
     n = 0;
     for (int i = 0; i < nf; i++) l1[n++] = future[i];
     for (int i = 0; i < np; i++) l1[n++] = past[i];
+    for (int idx = 0; idx < 6; idx++) /* long-term pictures close both lists, by LongTermPicNum (8.2.4.2.3) */
+        for (int i = 0; i < 6; i++)
+            if (&e->pics[i] != e->cur && e->pics[i].is_ref == 2 && e->pics[i].long_idx == idx && n < 12) l0[n] = &e->pics[i], l1[n++] = &e->pics[i];
     if (n > 1) { /* identical lists: the first two entries of list 1 trade places */
         int same = 1;
         for (int i = 0; i < n; i++) same &= l0[i] == l1[i];
@@ -3099,10 +3342,17 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
         return 0;
     }
     if (p->open_gop_period < 0) p->open_gop_period = 0;
+    if (p->direct_4x4 && (p->field_pics || p->interlace_sps)) {
+        snprintf(g_err, sizeof(g_err), "direct_4x4 (direct_8x8_inference_flag = 0) needs frame_mbs_only_flag = 1: not with field_pics or interlace_sps");
+        free(e);
+        return 0;
+    }
+    p->direct_4x4 = p->direct_4x4 != 0;
     if (p->profile_idc == 66) p->cabac = 0, p->weighted_pred = 0, p->bframes = 0;
     if (p->bframes > 0) { /* B pictures: two anchors must be referable, and the output order differs from the coding order */
         if (p->num_ref_frames < 2) p->num_ref_frames = 2;
-        p->poc_type = 0, p->nonref_period = 0, p->mmco = 0, p->idr_long_term = 0;
+        p->poc_type = 0, p->nonref_period = 0, p->mmco = 0;
+        if (p->b_pyramid) p->idr_long_term = 0;
         if (p->bframes > 3) p->bframes = 3;
         if (p->bframes < 2) p->b_pyramid = 0;
         /* the coding-order planner below puts an anchor every (bframes + 1) pictures: an IDR picture must be one of them */
@@ -3186,10 +3436,14 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
     int frame_num = 0, idr_id = 0, poc = 0, refs_since_reset = 0, since_idr = 0;
     static const int poc1_offsets[2] = {2, 6}; /* offset_for_ref_frame[] of write_sps() */
     g_feat = 0, g_npocs = 0;
-    memset(g_rng, 0, sizeof(g_rng));
+    memset(g_rng, 0, sizeof(g_rng)), memset(g_mot, 0, sizeof(g_mot));
+    memset(g_mvis_ptype, 0, sizeof(g_mvis_ptype)), memset(g_mvis_btype, 0, sizeof(g_mvis_btype)), memset(g_mvis_psub, 0, sizeof(g_mvis_psub));
+    memset(g_mvis_bsub, 0, sizeof(g_mvis_bsub)), memset(g_mvis_ref, 0, sizeof(g_mvis_ref));
     g_rng[SG_R_W_MIN] = g_rng[SG_R_O_MIN] = g_rng[SG_R_IMPLICIT_W1_MIN] = 1 << 20, g_rng[SG_R_W_MAX] = g_rng[SG_R_O_MAX] = g_rng[SG_R_IMPLICIT_W1_MAX] = -(1 << 20);
     g_rng[SG_R_DB_IA_MIN] = g_rng[SG_R_DB_IB_MIN] = 1 << 20, g_rng[SG_R_DB_IA_MAX] = g_rng[SG_R_DB_IB_MAX] = -(1 << 20);
     trace_clear();
+    motion_trace_clear();
+    if (p->trace_motion) e->mvmb = (sg_mvmb *)calloc((size_t)e->wmb * e->hmb, sizeof(sg_mvmb));
     memset(g_ip_visits, 0, sizeof(g_ip_visits));
     if (p->trace_intra) {
         e->ip_pred = (uint8_t *)calloc(fsz, 1), e->ip_res = (int16_t *)calloc(fsz, sizeof(int16_t));
@@ -3428,6 +3682,7 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
             for (int i = 0; i < 4; i++)
                 for (int c = 0; c < 2; c++) e->wp_cw[i][c] = e->wb_cw1[i][c] = 1 << e->wp_cd, e->wp_co[i][c] = e->wb_co1[i][c] = 0;
         for (int i = 0; i < e->wmb * e->hmb; i++) e->mb[i].type = T_NONE;
+        e->n_mvsl = 0;
         if (e->ip_pred) memset(e->ip_pred, 0, fsz), memset(e->ip_res, 0, fsz * sizeof(int16_t));
         e->pic_no++;
         /* the slices of this picture: (first macroblock, macroblock count), in the order they will be sent */
@@ -3480,6 +3735,17 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
                 e->dbf_alpha_div2 = e->dbf_idc == 1 ? 0 : rnd_range(e, -6, 6), e->dbf_beta_div2 = e->dbf_idc == 1 ? 0 : rnd_range(e, -6, 6);
             }
             write_slice_header(e, first, idr, frame_num, idr_id, pic_poc & (p->poc_step > 1 ? 65535 : 255));
+            if (e->mvmb && e->n_mvsl < 512) {
+                sg_mvslice *sl = &e->mvsl[e->n_mvsl++];
+                memset(sl, 0, sizeof(*sl));
+                sl->type = e->slice_type, sl->direct_spatial = bpic && !p->direct_temporal, sl->cur_poc = e->cur_poc, sl->first_mb = first, sl->count = sl_count[s];
+                sl->nref[0] = intra_pic ? 0 : e->nref_active, sl->nref[1] = bpic ? e->nref1_active : 0, sl->col_index = -1;
+                for (int l = 0; l < 2; l++)
+                    for (int i = 0; i < sl->nref[l] && i < 4; i++) {
+                        const sg_pic *r = l ? e->refs1[i] : e->refs[i];
+                        sl->pic[l][i] = r->id, sl->poc[l][i] = r->poc, sl->long_term[l][i] = r->is_ref == 2;
+                    }
+            }
             e->qp = e->slice_qp, e->prev_dqp_nz = 0, e->skip_run = 0;
             e->prev_kind = e->run_len = 0, e->sk_from = e->sk_to = -1, e->pcm_last = 0;
             int32_t syn_slice[SG_S_COUNT];
@@ -3504,8 +3770,8 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
                 const sg_bw bw0 = e->bw;
                 const int qp0 = e->qp, nz0 = e->prev_dqp_nz, run0 = e->skip_run, len0 = e->run_len, idx = sl_count[s] - left;
                 const int32_t zeroed0 = sg_guard_zeroed;
-                int32_t rng0[SG_R_COUNT], syn0[SG_S_COUNT];
-                memcpy(rng0, g_rng, sizeof(rng0)), memcpy(syn0, g_syn, sizeof(syn0));
+                int32_t rng0[SG_R_COUNT], syn0[SG_S_COUNT], mot0[SG_M_COUNT];
+                memcpy(rng0, g_rng, sizeof(rng0)), memcpy(syn0, g_syn, sizeof(syn0)), memcpy(mot0, g_mot, sizeof(mot0));
                 e->thin = 0;
               again:
                 begin_mb(e, addr);
@@ -3542,6 +3808,7 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
                     if (p->cabac) {
                         emb *a = MBA(e), *b = MBB(e);
                         sg_cabac_bin(&e->bw, 24 + (a && !IS_SKIPPED(a->type)) + (b && !IS_SKIPPED(b->type)), kind == T_BSKIP);
+                        g_mot[SG_M_SKIP_INC_B] |= 1 << ((a && !IS_SKIPPED(a->type)) + (b && !IS_SKIPPED(b->type)));
                     } else if (kind == T_BSKIP)
                         e->skip_run++;
                     else {
@@ -3568,6 +3835,7 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
                     if (p->cabac) {
                         emb *a = MBA(e), *b = MBB(e);
                         sg_cabac_bin(&e->bw, 11 + (a && a->type != T_SKIP) + (b && b->type != T_SKIP), kind == T_SKIP);
+                        g_mot[SG_M_SKIP_INC_P] |= 1 << ((a && a->type != T_SKIP) + (b && b->type != T_SKIP));
                     } else if (kind == T_SKIP)
                         e->skip_run++;
                     else {
@@ -3586,7 +3854,7 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
                     const int bits = (int)(e->bw.pos - bw0.pos) * 8 + e->bw.nacc - bw0.nacc + e->bw.outstanding - bw0.outstanding;
                     if (e->stim == 1 && bits > 3200 && e->thin < 3) {
                         e->bw = bw0, e->qp = qp0, e->prev_dqp_nz = nz0, e->skip_run = run0, e->run_len = len0, sg_guard_zeroed = zeroed0;
-                        memcpy(g_rng, rng0, sizeof(rng0)), memcpy(g_syn, syn0, sizeof(syn0));
+                        memcpy(g_rng, rng0, sizeof(rng0)), memcpy(g_syn, syn0, sizeof(syn0)), memcpy(g_mot, mot0, sizeof(mot0));
                         g_syn[SG_S_THINNED]++, memcpy(syn0, g_syn, sizeof(syn0));
                         e->thin++;
                         goto again;
@@ -3622,6 +3890,7 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
             out += n;
         }
         if (p->trace_deblock || p->trace_intra) trace_picture(e, t, 0);
+        if (e->mvmb) trace_motion_picture(e, t);
         sg_db_count = g_rng;
         sg_deblock(e->cur, e->db, e->wmb, e->hmb, p->mono);
         sg_db_count = NULL;
@@ -3679,7 +3948,7 @@ done:
     for (int i = 0; i < 6; i++) free(e->pics[i].pl[0]), free(e->pics[i].motion), free(e->fpics[i][0].pl[0]), free(e->fpics[i][1].pl[0]), free(e->fpics[i][0].motion), free(e->fpics[i][1].motion);
     free(e->mb);
     free(e->db);
-    free(e->ip_pred), free(e->ip_res), free(e->ipmb);
+    free(e->ip_pred), free(e->ip_res), free(e->ipmb), free(e->mvmb);
     free(e->src);
     free(frame_src);
     free(e->sgmap);

@@ -106,6 +106,31 @@ def entropy_syntax_vectors():
 entropy_syntax_vectors()
 
 
+def motion_vectors():
+    """tests/motionutil.py: the recipes whose motion derivations are counted cell by cell, and the geometries of the entropy kernels' P paths."""
+    import motionutil
+    out, lines = {}, []
+    for name in sorted(motionutil.RECIPES):
+        kw = motionutil.RECIPES[name]
+        s, rec, _ = streamgen.encode(**kw)
+        pics = motionutil.derive_stream(streamgen.last_motion_trace(), inference=not kw.get("direct_4x4"))
+        cells = motionutil.Counter()
+        for p in pics:
+            cells.update(p.cells)
+        lines.append(motionutil.cell_line(name, cells))
+        frames, _ = oracle.decode(s, crop=False)
+        assert (frames == rec).all(), name
+        out[name] = {"stream_md5": hashlib.md5(s).hexdigest(), "frames_md5": hashlib.md5(rec.tobytes()).hexdigest(), "stream_bytes": len(s)}
+    json.dump(out, open(os.path.join(HERE, "motion_md5.json"), "w"), indent=1, sort_keys=True)
+    open(os.path.join(HERE, "motion_counters.txt"), "w").write(
+        "The cells of 8.4.1 that the yardstick of tests/motionutil.py counts on the motion trace of each recipe there, at the seeds chosen there:\n"
+        "per family, distinct cells reached / derivations counted.\n" + "\n".join(lines) + "\n")
+    print("wrote", len(out), "motion vectors")
+
+
+motion_vectors()
+
+
 def intra_vectors():
     """tests/intrautil.py: the recipes whose intra-prediction cells are counted, and the geometries K3's schedules distinguish."""
     import intrautil

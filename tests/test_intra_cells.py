@@ -121,7 +121,10 @@ def test_new_knobs_at_zero_change_nothing(sg):
     trace is a record, not a knob"""
     kw = dict(width=64, height=48, frames=4, idr_period=0, profile_idc=100, cabac=1, transform8x8=1, slices=2, intra_in_p_permille=300, seed=5)
     a, rec, _ = sg.encode(**kw)
-    assert a == sg.encode(**dict(kw, intra_stim=0, trace_intra=0))[0] and sg.last_intra_trace() == []
+    assert a == sg.encode(**dict(kw, intra_stim=0, trace_intra=0, direct_4x4=0, trace_motion=0, motion_stim=0))[0] and sg.last_intra_trace() == []
+    assert sg.last_motion_trace() == []
+    m, rec_m, _ = sg.encode(**dict(kw, trace_motion=1))
+    assert a == m and np.array_equal(rec, rec_m) and len(sg.last_motion_trace()) == 4 and sg.last_intra_trace() == []
     b, rec_b, _ = sg.encode(**dict(kw, trace_intra=1))
     assert a == b and np.array_equal(rec, rec_b) and len(sg.last_intra_trace()) == 4 and "pred" in sg.last_intra_trace()[0]
     sg.encode(**dict(kw, trace_deblock=1))
