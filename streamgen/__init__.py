@@ -25,7 +25,8 @@ class Params(ctypes.Structure):
         ("wp_range", ctypes.c_int), ("poc_step", ctypes.c_int), ("mv_reach", ctypes.c_int), ("mv_margin", ctypes.c_int), ("contrast", ctypes.c_int),
         ("dbf_per_slice", ctypes.c_int), ("trace_deblock", ctypes.c_int), ("syntax_stim", ctypes.c_int),
         ("intra_stim", ctypes.c_int), ("trace_intra", ctypes.c_int),
-        ("direct_4x4", ctypes.c_int), ("trace_motion", ctypes.c_int), ("motion_stim", ctypes.c_int), ("open_gop_period", ctypes.c_int)]
+        ("direct_4x4", ctypes.c_int), ("trace_motion", ctypes.c_int), ("motion_stim", ctypes.c_int), ("open_gop_period", ctypes.c_int),
+        ("trace_residual", ctypes.c_int), ("residual_stim", ctypes.c_int)]
 
 
 def build(force=False):
@@ -58,6 +59,7 @@ def lib():
         _lib.sg_last_deblock_trace.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
         _lib.sg_last_intra_trace.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
         _lib.sg_last_motion.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        _lib.sg_last_residual_trace.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         _lib.sg_last_motion_trace.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
     return _lib
 
@@ -235,6 +237,37 @@ def last_intra_trace():
         def planes(a):
             return a[:w * h].reshape(h, w), a[w * h:w * h * 5 // 4].reshape(h // 2, w // 2), a[w * h * 5 // 4:].reshape(h // 2, w // 2)
         t.update(pred=planes(pred), res=planes(res), ipmbs=mbs, constrained_intra=int(info[8]))
+    return out
+
+
+# sg_rsmb (sg.h), one per macroblock: what 8.5 starts from
+RSMB = np.dtype(dict(names=["kind", "t8x8", "cbp", "qp", "slice", "slice_qp", "luma", "dc16", "cdc", "cac", "pcm"],
+                     formats=["u1", "u1", "u1", "u1", "u2", "u1", ("i4", (16, 16)), ("i4", 16), ("i4", (2, 4)), ("i4", (2, 4, 15)), ("u1", 384)],
+                     offsets=[0, 1, 2, 3, 4, 6, 8, 1032, 1096, 1128, 1608], itemsize=1992))
+RS_SKIPPED, RS_INTER, RS_I4, RS_I8, RS_I16, RS_PCM = range(6)
+
+
+def last_residual_trace():
+    """For every picture of the last encode(trace_residual=1, ...) of this thread, in coding order, what last_deblock_trace() gives (`planes` before
+    sg_deblock, `after`, `mbs`, `field`, `mono`, `frame`) and: `pred` = (Y, Cb, Cr) of the prediction sample of every sample (inter: after weighting; I_PCM:
+    0); `rsmbs` = the sg_rsmb table [rows, columns] (kind RS_*, t8x8, cbp = luma | chroma << 4, qp = QP_Y in force, slice, slice_qp, and the levels as written, in
+    scan order: luma [16 blocks in coding order][16] -- Intra16x16: positions 1..15; 8x8 transform: the same numbers as [4][64] --, dc16, cdc [plane][4],
+    cac [plane][block][15]; pcm = the 384 samples of an I_PCM macroblock); `chroma_qp_index_offset`, `second_chroma_qp_index_offset`; `lists4` [6][16] and
+    `lists8` [2][64] = the scaling lists in force, in the order of their syntax elements."""
+    out = last_deblock_trace()
+    for i, t in enumerate(out):
+        info = np.zeros(10, dtype=np.int32)
+        lib().sg_last_residual_trace(i, info.ctypes.data, None, 0, None, 0, None)
+        w, h, wmb, hmb, size = int(info[0]), int(info[1]), int(info[2]), int(info[3]), int(info[7])
+        if size == 0:  # a picture kept for another trace alone
+            continue
+        assert size == RSMB.itemsize, (size, RSMB.itemsize)
+        n = w * h * 3 // 2
+        pred, mbs, lists = np.zeros(n, dtype=np.uint8), np.zeros((hmb, wmb), dtype=RSMB), np.zeros(224, dtype=np.uint8)
+        lib().sg_last_residual_trace(i, None, pred.ctypes.data, n, mbs.ctypes.data, mbs.nbytes, lists.ctypes.data)
+        t.update(pred=(pred[:w * h].reshape(h, w), pred[w * h:w * h * 5 // 4].reshape(h // 2, w // 2), pred[w * h * 5 // 4:].reshape(h // 2, w // 2)),
+                 rsmbs=mbs, chroma_qp_index_offset=int(info[8]), second_chroma_qp_index_offset=int(info[9]),
+                 lists4=lists[:96].reshape(6, 16).copy(), lists8=lists[96:].reshape(2, 64).copy())
     return out
 
 

@@ -174,6 +174,19 @@ typedef struct {
      * where entry 0 is barred --; list sizes and orders are what the whole DPB gives.  Refused together with rplm, mmco, idr_long_term, fn_gap_period,
      * wp_range 2 (list modification) and direct_temporal (the index comes from the co-located block). */
     int open_gop_period;
+    /* residual decoding (8.5): both 0 = the streams of before, byte for byte, and not one more draw of the generator.
+     * trace_residual 1: sg_last_residual_trace() keeps, for every picture of this call, the prediction sample of every sample, the sg_rsmb table, the two
+     * chroma offsets and the eight scaling lists (and what trace_deblock keeps); changes nothing else */
+    int trace_residual;
+    /* residual stimulus: 1: the 16-bit range guard of sg_recon.c is on and QP_Y is drawn from the whole 0..51 as under syntax_stim (one macroblock in two
+     * takes the QP_Y its kind -- Intra4x4, Intra8x8, Intra16x16, inter -- had least often so far).  After every quantiser call (and after the pattern of
+     * syntax_stim, where both are set) and before the reconstruction is made from the levels: per macroblock a target (luma coded_block_pattern, chroma
+     * class) is the one its kind had least often so far in this sg_encode() call, blocks outside the target are emptied, blocks inside get levels -- what the
+     * quantiser left, or one level at the scan position used least often so far (small, or as large as the guard lets it pass alone), or a level at every scan
+     * position, or negative levels only; for chroma the planes that keep DC levels (class 1) or AC levels (class 2) are Cb, Cr or both in turn; in an 8x8
+     * block the raster row pairs (0-1, 2-3, 4-5, 6-7) that keep coefficients are the subset taken least often, every pair of it holding a coefficient.  The
+     * guard runs afterwards.  Heavy and thinned macroblocks of syntax_stim are left to it. */
+    int residual_stim;
 } sg_params;
 
 void sg_default_params(sg_params *p);
@@ -393,6 +406,25 @@ typedef struct {
     int32_t col_index;       /* B slices: the index (in this trace) of the picture that is RefPicList1[0]; -1: not traced */
 } sg_mvslice; /* (four entries per list and 512 slices per picture are the generator's own limits: it builds no longer list and sends no more slices) */
 int sg_last_motion_trace(int index, int32_t info[8], void *mbs, size_t mbs_cap, void *slices, size_t slices_cap);
+/* sg_params::trace_residual: the same pictures as sg_last_deblock_trace() (which serves them too): what 8.5 starts from.  info receives {width, height,
+ * macroblock columns, macroblock rows, field, mono, frame, sizeof(sg_rsmb), chroma_qp_index_offset, second_chroma_qp_index_offset}; pred the picture's I420
+ * planes of prediction samples (inter: after weighting; I_PCM: 0), planes_cap in bytes; mbs its sg_rsmb table; lists the scaling lists in force, in the
+ * order of their syntax elements after the fall-back rules: six of 16 entries, then two of 64 (224 bytes; sixteens without a matrix) */
+typedef struct {
+    uint8_t kind;        /* 0 skipped (P_Skip, B_Skip), 1 inter, 2 Intra4x4, 3 Intra8x8, 4 Intra16x16, 5 I_PCM */
+    uint8_t t8x8;        /* transform_size_8x8_flag */
+    uint8_t cbp;         /* coded_block_pattern: luma | chroma << 4 (Intra16x16: what mb_type implies; skipped and I_PCM: 0) */
+    uint8_t qp;          /* QP_Y in force (skipped, I_PCM and delta-less macroblocks: the value carried over) */
+    uint16_t slice;
+    uint8_t slice_qp, pad; /* SliceQP_Y of the macroblock's slice */
+    int32_t luma[16][16];   /* the levels as written, in scan order: per 4x4 block in coding order (luma4x4BlkIdx); Intra16x16: [..][0] is 0, 1..15 the AC
+                             * levels; with the 8x8 transform the same 256 numbers are four blocks of 64 */
+    int32_t dc16[16];       /* Intra16x16 DC */
+    int32_t cdc[2][4];      /* chroma DC */
+    int32_t cac[2][4][15];  /* chroma AC */
+    uint8_t pcm[384];       /* I_PCM: the samples as written (256 luma, 64 Cb, 64 Cr) */
+} sg_rsmb;
+int sg_last_residual_trace(int index, int32_t info[10], uint8_t *pred, size_t planes_cap, void *mbs, size_t mbs_cap, uint8_t lists[224]);
 
 #ifdef __cplusplus
 }

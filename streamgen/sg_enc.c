@@ -96,6 +96,12 @@ typedef struct {
     int quiet_pred; /* mot_pred() does not count */
     int pred_h;     /* height in blocks of the partition whose predictor comes next (mot_geo) */
     int col_list;   /* col_block(): 1 the co-located block used list 0, 2 list 1 only */
+    /* sg_params::trace_residual: prediction samples of the current picture (I420 planes of the picture's size), its sg_rsmb table */
+    uint8_t *rs_pred;
+    sg_rsmb *rsmb;
+    /* sg_params::residual_stim: the knob; per macroblock: whether rs_target() steers it, the kind its QP_Y is counted under (0 Intra4x4, 1 Intra8x8,
+     * 2 Intra16x16, 3 inter), the chroma planes (bit 0 Cb, bit 1 Cr) that keep DC / AC levels */
+    int rstim, rs_on, rs_qcls, rs_dcmask, rs_acmask;
 } enc;
 /* the entry of list l to predict from when `r` was drawn: `r` itself unless the barrier bars it, then the first entry that it lets through */
 static int barrier_ref(const enc *e, int l, int r) {
@@ -895,12 +901,98 @@ static void stim_pattern(enc *e, int16_t *out, int L, const int *cap, int maxmag
 }
 /* the levels of one block after its quantiser: n = 16 (first = 1: an AC block of 15), 64, 0 (the 16 luma DC levels; ls points at LevelScale(0, 0)) or
  * 4 (chroma DC, the same); kill: the block stays empty */
+/* sg_params::trace_residual: the prediction of the current macroblock, luma (16 x 16) and / or chroma (8 x 8 each); both NULL: zeros (I_PCM) */
+static void rs_keep_pred(enc *e, const uint8_t *py, const uint8_t pc[2][64]) {
+    if (!e->rs_pred) return;
+    const int W = e->W, W2 = W / 2, zero = !py && !pc;
+    if (py || zero)
+        for (int y = 0; y < 16; y++) {
+            uint8_t *d = e->rs_pred + (size_t)(e->mby * 16 + y) * W + e->mbx * 16;
+            if (zero) memset(d, 0, 16); else memcpy(d, py + 16 * y, 16);
+        }
+    if (pc || zero)
+        for (int c = 0; c < 2; c++)
+            for (int y = 0; y < 8; y++) {
+                uint8_t *d = e->rs_pred + (size_t)W * e->H + (size_t)c * (W * e->H / 4) + (size_t)(e->mby * 8 + y) * W2 + e->mbx * 8;
+                if (zero) memset(d, 0, 8); else memcpy(d, pc[c] + 8 * y, 8);
+            }
+}
+
+/* ------------------------------------------------------------------ residual stimulus (sg_params::residual_stim)
+ * How often each candidate of a draw was taken in this sg_encode() call: targets (coded_block_pattern luma + 16 * chroma class; Intra16x16: luma 0 / 1) per
+ * kind (0 Intra4x4 / Intra8x8, 1 inter, 2 Intra16x16); the planes of chroma class 1 and 2; the row-pair subsets of 8x8 blocks (intra / inter); scan
+ * positions (frame / field; 0 4x4, 1 8x8, 2 Intra16x16 DC, 3 AC blocks of 15, 4 chroma DC); QP_Y per kind.  Per thread. */
+static _Thread_local uint32_t g_rs_cbp[3][48], g_rs_planes[2][3], g_rs_rows[2][16], g_rs_scan[2][5][64], g_rs_qp[4][52];
+/* the candidate of lo .. n - 1 that was taken least often; among equals the drawn one, then the next after it */
+static int rs_least(uint32_t *visits, int lo, int n, int drawn) {
+    int best = -1;
+    for (int k = 0; k < n - lo; k++) {
+        const int i = lo + (drawn - lo + k) % (n - lo);
+        if (best < 0 || visits[i] < visits[best]) best = i;
+    }
+    visits[best]++;
+    return best;
+}
+/* the target of the macroblock that is about to quantise its blocks: kind 0 Intra4x4 / Intra8x8, 1 inter, 2 Intra16x16 */
+static void rs_target(enc *e, int kind) {
+    e->rs_on = 0, e->rs_dcmask = e->rs_acmask = 3;
+    if (!e->rstim || (e->stim && (e->heavy || e->thin))) return;
+    const int n = kind == 2 ? 6 : 48, t = rs_least(g_rs_cbp[kind], 0, n, (int)(rnd(e) % (uint32_t)n));
+    const int luma = kind == 2 ? t & 1 : t & 15, chroma = kind == 2 ? t >> 1 : t >> 4;
+    e->rs_on = 1;
+    e->kill8 = kind == 2 ? 0 : ~luma & 15, e->kill_ac16 = kind == 2 && !luma;
+    e->kill_c = chroma == 0, e->kill_cac = chroma != 2;
+    if (chroma == 1) e->rs_dcmask = 1 + rs_least(g_rs_planes[0], 0, 3, (int)(rnd(e) % 3));
+    if (chroma == 2) e->rs_acmask = 1 + rs_least(g_rs_planes[1], 0, 3, (int)(rnd(e) % 3)), e->rs_dcmask = (int)(rnd(e) % 4);
+}
+/* the levels of one block that the target keeps (n, first as for stim()) */
+static void rs_levels(enc *e, int16_t *lev, int n, int first, const int *ls, int qp) {
+    const int N = n ? n : 16, maxmag = e->p.cabac || e->p.profile_idc == 100 ? 32767 : 2063;
+    const int inter = !IS_INTRA(CURMB(e)->type), sc = n == 64 ? 1 : (n == 0 ? 2 : (n == 4 ? 4 : (first ? 3 : 0)));
+    uint32_t *vis = g_rs_scan[e->field != 0][sc];
+    int mode = (int)(rnd(e) % 8);
+    if (mode < 2 && !count_nz(lev + first, N - first)) mode = 2;
+    if (mode >= 2 && mode <= 4) { /* one level, at the scan position used least often: 1, small, what the guard lets pass alone, a part of that */
+        const int k = rs_least(vis, first, N, rnd_range(e, first, N - 1)), how = (int)(rnd(e) % 4), cap = sg_guard_cap(n, k, ls, qp, first);
+        int a = how == 0 ? 1 : (how == 1 ? 2 + (int)(rnd(e) % 6) : (how == 2 ? cap : cap * (1 + (int)(rnd(e) % 3)) / 4));
+        a = a > maxmag ? maxmag : (a < 1 ? 1 : a);
+        memset(lev, 0, sizeof(int16_t) * (size_t)N);
+        lev[k] = (int16_t)((rnd(e) & 1) ? -a : a);
+    } else if (mode == 5) /* a level at every scan position */
+        for (int k = first; k < N; k++) lev[k] = (int16_t)((rnd(e) & 1) ? -1 - (int)(rnd(e) % 2) : 1 + (int)(rnd(e) % 2));
+    else if (mode == 6) { /* one level of three quarters of that, and a few small ones */
+        const int k = rs_least(vis, first, N, rnd_range(e, first, N - 1)), cap = sg_guard_cap(n, k, ls, qp, first) * 3 / 4;
+        const int a = cap > maxmag ? maxmag : (cap < 1 ? 1 : cap);
+        memset(lev, 0, sizeof(int16_t) * (size_t)N);
+        for (int i = 0; i < 3; i++) lev[rnd_range(e, first, N - 1)] = (int16_t)rnd_range(e, -3, 3);
+        lev[k] = (int16_t)((rnd(e) & 1) ? -a : a);
+    } else if (mode == 7) { /* negative levels only */
+        memset(lev, 0, sizeof(int16_t) * (size_t)N);
+        for (int i = 0; i < 3; i++) lev[rnd_range(e, first, N - 1)] = (int16_t)rnd_range(e, -3, -1);
+    }
+    if (n == 64) { /* the raster row pairs that keep coefficients */
+        const int sub = rs_least(g_rs_rows[inter], 1, 16, rnd_range(e, 1, 15));
+        int have = 0;
+        for (int k = 0; k < 64; k++) {
+            const int pair = sg_scan_pos(64, k) >> 4;
+            if (!(sub >> pair & 1)) lev[k] = 0;
+            if (lev[k]) have |= 1 << pair;
+        }
+        for (int tries = 0; have != sub && tries < 400; tries++) {
+            const int k = (int)(rnd(e) % 64), pair = sg_scan_pos(64, k) >> 4;
+            if ((sub & ~have) >> pair & 1) lev[k] = (int16_t)((rnd(e) & 1) ? -1 : 1), have |= 1 << pair;
+        }
+    }
+}
+
 static void stim(enc *e, int16_t *lev, int n, int first, int kill, const int *ls, int qp) {
-    if (!e->stim) return;
+    if (!e->stim && !e->rstim) return;
     const int L = n == 0 ? 16 : n - first, maxmag = e->p.cabac || e->p.profile_idc == 100 ? 32767 : 2063;
     int cap[64];
     if (kill || e->thin >= 3)
         memset(lev, 0, sizeof(int16_t) * (size_t)(n ? n : 16));
+    else if (!e->stim)
+        ;
     else if (e->thin >= 2 || e->heavy || rnd(e) % 100 < 85) {
         for (int k = 0; k < L; k++) cap[k] = sg_guard_cap(n, k + first, ls, qp, first);
         if (n == 64 && !e->p.cabac) /* CAVLC: four interleaved blocks of 16 */
@@ -915,6 +1007,7 @@ static void stim(enc *e, int16_t *lev, int n, int first, int kill, const int *ls
             stim_pattern(e, lev + first, L, cap, maxmag);
     } else if (maxmag < 32767) /* (the quantisers stay below 2001) */
         for (int k = 0; k < (n ? n : 16); k++) lev[k] = (int16_t)(lev[k] > maxmag ? maxmag : (lev[k] < -maxmag ? -maxmag : lev[k]));
+    if (e->rs_on && !kill && e->thin < 3) rs_levels(e, lev, n, first, ls, qp);
     if (n == 16)
         sg_guard4(lev, ls, qp, first);
     else if (n == 64)
@@ -927,6 +1020,7 @@ static void stim(enc *e, int16_t *lev, int n, int first, int kill, const int *ls
 
 static void code_chroma(enc *e, int intra, const uint8_t pred[2][64]) {
     emb *m = CURMB(e);
+    if (!intra) rs_keep_pred(e, NULL, pred);
     int W2 = e->W / 2, any_dc = 0, any_ac = 0;
     for (int c = 0; c < 2; c++) {
         const uint8_t *src = e->src + e->W * e->H + c * (e->W * e->H / 4) + e->mby * 8 * W2 + e->mbx * 8;
@@ -944,12 +1038,12 @@ static void code_chroma(enc *e, int intra, const uint8_t pred[2][64]) {
             e->cac[c][b][0] = 0;
             int16_t lev[16];
             sg_quant4(res, ls, qp, deadzone(intra), 1, lev);
-            stim(e, lev, 16, 1, e->kill_cac || e->kill_c || e->p.mono, ls, qp);
+            stim(e, lev, 16, 1, e->kill_cac || e->kill_c || e->p.mono || !(e->rs_acmask >> c & 1), ls, qp);
             memcpy(e->cac[c][b], lev, sizeof(lev));
             if (count_nz(lev, 16)) any_ac = 1;
         }
         sg_quant_chroma_dc(sums, ls[0], qp, deadzone(intra), e->cdc[c]);
-        stim(e, e->cdc[c], 4, 0, e->kill_c || e->p.mono, ls, qp);
+        stim(e, e->cdc[c], 4, 0, e->kill_c || e->p.mono || !(e->rs_dcmask >> c & 1), ls, qp);
         if (count_nz(e->cdc[c], 4)) any_dc = 1;
     }
     m->cbp_chroma = any_ac ? 2 : (any_dc ? 1 : 0);
@@ -985,6 +1079,8 @@ static void code_luma_inter(enc *e, const uint8_t *pred /*16x16*/) {
     uint8_t *dst = e->cur->pl[0] + e->mby * 16 * e->W + e->mbx * 16;
     int qp = m->qp;
     m->cbp_luma = 0;
+    rs_keep_pred(e, pred, NULL);
+    rs_target(e, 1);
     for (int b8 = 0; b8 < 4; b8++) {
         int x8 = (b8 & 1) * 8, y8 = (b8 >> 1) * 8;
         if (m->t8x8) {
@@ -1114,8 +1210,11 @@ static void begin_mb(enc *e, int addr) {
     memset(e->cdc, 0, sizeof(e->cdc));
     memset(e->cac, 0, sizeof(e->cac));
 }
+static int second_chroma_offset(const enc *e) { /* second_chroma_qp_index_offset as write_pps() sends it (7.4.2.2: -12 .. 12); without it, the first */
+    return e->p.chroma_qp_offset + ((e->p.profile_idc == 100 && e->p.transform8x8 && e->p.chroma_qp_offset < 12) ? 1 : 0);
+}
 static void set_qpc(enc *e, emb *m, int qp) {
-    int second = e->p.chroma_qp_offset + ((e->p.profile_idc == 100 && e->p.transform8x8 && e->p.chroma_qp_offset < 12) ? 1 : 0); /* (7.4.2.2: -12 .. 12) */
+    int second = second_chroma_offset(e);
     m->qp = (uint8_t)qp;
     m->qpc[0] = (uint8_t)qpc_of(qp + e->p.chroma_qp_offset);
     m->qpc[1] = (uint8_t)qpc_of(qp + second);
@@ -1152,6 +1251,25 @@ static void end_mb(enc *e) {
         t->i16mode = m->i16mode, t->chroma_mode = m->chroma_mode, t->slice_id = m->slice_id;
         memcpy(t->ipm, m->ipm, sizeof(t->ipm));
     }
+    if (e->rsmb) {
+        sg_rsmb *t = &e->rsmb[e->addr];
+        const int coded = !IS_SKIPPED(m->type) && m->type != T_PCM;
+        memset(t, 0, sizeof(*t));
+        t->kind = (uint8_t)(IS_SKIPPED(m->type) ? 0 : (m->type == T_I4 ? 2 : (m->type == T_I8 ? 3 : (m->type == T_I16 ? 4 : (m->type == T_PCM ? 5 : 1)))));
+        t->t8x8 = m->t8x8, t->cbp = (uint8_t)(coded ? m->cbp_luma | m->cbp_chroma << 4 : 0), t->qp = m->qp, t->slice = m->slice_id, t->slice_qp = (uint8_t)e->slice_qp;
+        if (coded) {
+            for (int i = 0; i < 16; i++) {
+                t->dc16[i] = e->i16dc[i];
+                for (int k = 0; k < 16; k++) t->luma[i][k] = m->t8x8 ? e->luma8[i >> 2][16 * (i & 3) + k] : e->luma[i][k];
+            }
+            for (int c = 0; c < 2; c++)
+                for (int b = 0; b < 4; b++) {
+                    t->cdc[c][b] = e->cdc[c][b];
+                    for (int k = 0; k < 15; k++) t->cac[c][b][k] = e->cac[c][b][k + 1];
+                }
+        }
+        if (m->type == T_PCM) memcpy(t->pcm, e->pcm, sizeof(t->pcm));
+    }
     if (e->mvmb) { /* (the signed mvd were put there by the macroblock's coder) */
         sg_mvmb *t = &e->mvmb[e->addr];
         static const uint8_t kinds[12] = {0, 0, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7}; /* by T_* */
@@ -1168,7 +1286,8 @@ static void end_mb(enc *e) {
 
 /* choose the QP this MB would like to use */
 static int want_qp(enc *e) {
-    if (e->stim) { /* the whole 0..51: code_dqp() wraps where the straight difference is out of range */
+    if (e->rstim && (rnd(e) & 1)) return rs_least(g_rs_qp[e->rs_qcls], 0, 52, (int)(rnd(e) % 52));
+    if (e->stim || e->rstim) { /* the whole 0..51: code_dqp() wraps where the straight difference is out of range */
         int r = (int)(rnd(e) % 16), q;
         if (r < (e->prev_kind ? 2 : 7)) return e->qp;
         r = (int)(rnd(e) % 10);
@@ -1237,6 +1356,7 @@ static void put_intra(enc *e, int plane, int x, int y, const uint8_t *pred, int 
             const int v = pred[j * n + i] + (res ? res[j * n + i] : 0);
             g_rng[(plane ? SG_R_IP_REC_CHROMA_AT0 : SG_R_IP_REC_LUMA_AT0) + (v > 255)] += v < 0 || v > 255;
             if (e->ip_pred) e->ip_pred[off + (size_t)j * stride + i] = pred[j * n + i], e->ip_res[off + (size_t)j * stride + i] = (int16_t)(res ? res[j * n + i] : 0);
+            if (e->rs_pred) e->rs_pred[off + (size_t)j * stride + i] = pred[j * n + i];
         }
     put_block(e->cur->pl[plane] + (size_t)y * stride + x, stride, pred, n, res);
 }
@@ -1256,9 +1376,12 @@ static void encode_intra(enc *e, int islice) {
         kind = e->p.transform8x8 ? (k < 35 ? T_I16 : (k < 70 ? T_I4 : T_I8)) : (k < 50 ? T_I16 : T_I4);
     }
     m->type = (uint8_t)kind;
+    e->rs_qcls = kind == T_I16 ? 2 : (kind == T_I8 ? 1 : 0);
     int qp = want_qp(e);
     set_qpc(e, m, qp);
+    if (kind != T_PCM) rs_target(e, kind == T_I16 ? 2 : 0);
     if (kind == T_PCM) {
+        rs_keep_pred(e, NULL, NULL);
         /* raw samples */
         for (int y = 0; y < 16; y++) memcpy(e->pcm + 16 * y, src + y * W, 16);
         for (int c = 0; c < 2; c++)
@@ -1624,6 +1747,7 @@ static void encode_skip(enc *e) {
     set_refids(e, m);
     set_qpc(e, m, e->qp);
     mc_part(e, 0, 0, 4, 4, py, pc);
+    rs_keep_pred(e, py, pc);
     for (int y = 0; y < 16; y++) memcpy(e->cur->pl[0] + (e->mby * 16 + y) * e->W + e->mbx * 16, py + 16 * y, 16);
     for (int c = 0; c < 2; c++)
         for (int y = 0; y < 8; y++) memcpy(e->cur->pl[1 + c] + (e->mby * 8 + y) * (e->W / 2) + e->mbx * 8, pc[c] + 8 * y, 8);
@@ -2205,6 +2329,7 @@ static void encode_b(enc *e, int kind) {
     b_predict(e, py, pc);
     if (kind == T_BSKIP) {
         set_qpc(e, m, e->qp);
+        rs_keep_pred(e, py, pc);
         for (int y = 0; y < 16; y++) memcpy(e->cur->pl[0] + (e->mby * 16 + y) * e->W + e->mbx * 16, py + 16 * y, 16);
         for (int c = 0; c < 2; c++)
             for (int y = 0; y < 8; y++) memcpy(e->cur->pl[1 + c] + (e->mby * 8 + y) * (e->W / 2) + e->mbx * 8, pc[c] + 8 * y, 8);
@@ -2682,11 +2807,15 @@ typedef struct {
     uint8_t *pred;
     int16_t *res;
     sg_ipmb *ipmbs;
+    /* trace_residual */
+    int32_t cqo[2];
+    uint8_t *rs_pred, lists[224];
+    sg_rsmb *rsmbs;
 } db_trace;
 static _Thread_local db_trace *g_trace;
 static _Thread_local int g_ntrace, g_trace_cap;
 static void trace_clear(void) {
-    for (int i = 0; i < g_ntrace; i++) free(g_trace[i].before), free(g_trace[i].after), free(g_trace[i].mbs), free(g_trace[i].pred), free(g_trace[i].res), free(g_trace[i].ipmbs);
+    for (int i = 0; i < g_ntrace; i++) free(g_trace[i].before), free(g_trace[i].after), free(g_trace[i].mbs), free(g_trace[i].pred), free(g_trace[i].res), free(g_trace[i].ipmbs), free(g_trace[i].rs_pred), free(g_trace[i].rsmbs);
     g_ntrace = 0;
 }
 static void trace_planes(const sg_pic *p, uint8_t *dst) {
@@ -2709,13 +2838,20 @@ static void trace_picture(const enc *e, int frame, int after) {
     db_trace *t = &g_trace[g_ntrace];
     t->before = (uint8_t *)malloc(psz), t->after = (uint8_t *)malloc(psz), t->mbs = (sg_dbmb *)malloc(msz);
     t->pred = NULL, t->res = NULL, t->ipmbs = NULL, t->constrained = e->p.constrained_intra;
+    t->rs_pred = NULL, t->rsmbs = NULL;
+    if (e->rs_pred) {
+        t->rs_pred = (uint8_t *)malloc(psz), t->rsmbs = (sg_rsmb *)malloc(sizeof(sg_rsmb) * (size_t)e->wmb * e->hmb);
+        if (t->rs_pred && t->rsmbs) memcpy(t->rs_pred, e->rs_pred, psz), memcpy(t->rsmbs, e->rsmb, sizeof(sg_rsmb) * (size_t)e->wmb * e->hmb);
+        t->cqo[0] = e->p.chroma_qp_offset, t->cqo[1] = second_chroma_offset(e);
+        memcpy(t->lists, e->s4, 96), memcpy(t->lists + 96, e->s8, 128);
+    }
     if (e->ip_pred) {
         t->pred = (uint8_t *)malloc(psz), t->res = (int16_t *)malloc(psz * sizeof(int16_t)), t->ipmbs = (sg_ipmb *)malloc(sizeof(sg_ipmb) * (size_t)e->wmb * e->hmb);
         if (t->pred && t->res && t->ipmbs)
             memcpy(t->pred, e->ip_pred, psz), memcpy(t->res, e->ip_res, psz * sizeof(int16_t)), memcpy(t->ipmbs, e->ipmb, sizeof(sg_ipmb) * (size_t)e->wmb * e->hmb);
     }
-    if (!t->before || !t->after || !t->mbs || (e->ip_pred && (!t->pred || !t->res || !t->ipmbs))) {
-        free(t->before), free(t->after), free(t->mbs), free(t->pred), free(t->res), free(t->ipmbs);
+    if (!t->before || !t->after || !t->mbs || (e->ip_pred && (!t->pred || !t->res || !t->ipmbs)) || (e->rs_pred && (!t->rs_pred || !t->rsmbs))) {
+        free(t->before), free(t->after), free(t->mbs), free(t->pred), free(t->res), free(t->ipmbs), free(t->rs_pred), free(t->rsmbs);
         return;
     }
     const int32_t info[8] = {p->w, p->h, e->wmb, e->hmb, e->field ? 1 + e->bottom : 0, e->p.mono, frame, (int32_t)sizeof(sg_dbmb)};
@@ -2743,6 +2879,17 @@ int sg_last_intra_trace(int index, int32_t info[9], uint8_t *pred, int16_t *res,
         if (pred && planes_cap >= psz) memcpy(pred, t->pred, psz);
         if (res && planes_cap >= psz) memcpy(res, t->res, psz * sizeof(int16_t));
         if (mbs && mbs_cap >= msz) memcpy(mbs, t->ipmbs, msz);
+    }
+    return g_ntrace;
+}
+int sg_last_residual_trace(int index, int32_t info[10], uint8_t *pred, size_t planes_cap, void *mbs, size_t mbs_cap, uint8_t lists[224]) {
+    if (index >= 0 && index < g_ntrace && g_trace[index].rs_pred) {
+        const db_trace *t = &g_trace[index];
+        const size_t psz = (size_t)t->info[0] * t->info[1] * 3 / 2, msz = sizeof(sg_rsmb) * (size_t)t->info[2] * t->info[3];
+        if (info) memcpy(info, t->info, sizeof(t->info)), info[7] = (int32_t)sizeof(sg_rsmb), info[8] = t->cqo[0], info[9] = t->cqo[1];
+        if (pred && planes_cap >= psz) memcpy(pred, t->rs_pred, psz);
+        if (mbs && mbs_cap >= msz) memcpy(mbs, t->rsmbs, msz);
+        if (lists) memcpy(lists, t->lists, sizeof(t->lists));
     }
     return g_ntrace;
 }
@@ -3424,7 +3571,10 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
     if (p->scaling_matrix < 0 || p->scaling_matrix > 3) p->scaling_matrix = 1;
     e->t8_req = p->transform8x8;
     e->stim = p->syntax_stim < 0 || (p->syntax_stim & 3) == 3 ? 0 : p->syntax_stim & 3;
-    sg_set_range_guard(p->scaling_matrix >= 2 || e->stim);
+    e->rstim = p->residual_stim == 1;
+    sg_set_range_guard(p->scaling_matrix >= 2 || e->stim || e->rstim);
+    memset(g_rs_cbp, 0, sizeof(g_rs_cbp)), memset(g_rs_planes, 0, sizeof(g_rs_planes)), memset(g_rs_rows, 0, sizeof(g_rs_rows));
+    memset(g_rs_scan, 0, sizeof(g_rs_scan)), memset(g_rs_qp, 0, sizeof(g_rs_qp));
     memset(g_syn, 0, sizeof(g_syn));
     g_syn[SG_S_DQP_MIN] = g_syn[SG_S_QPY_MIN] = 1 << 20, g_syn[SG_S_DQP_MAX] = g_syn[SG_S_QPY_MAX] = -(1 << 20);
     if (p->scaling_matrix == 1) {
@@ -3445,6 +3595,7 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
     motion_trace_clear();
     if (p->trace_motion) e->mvmb = (sg_mvmb *)calloc((size_t)e->wmb * e->hmb, sizeof(sg_mvmb));
     memset(g_ip_visits, 0, sizeof(g_ip_visits));
+    if (p->trace_residual) e->rs_pred = (uint8_t *)calloc(fsz, 1), e->rsmb = (sg_rsmb *)calloc((size_t)e->wmb * e->hmb, sizeof(sg_rsmb));
     if (p->trace_intra) {
         e->ip_pred = (uint8_t *)calloc(fsz, 1), e->ip_res = (int16_t *)calloc(fsz, sizeof(int16_t));
         e->ipmb = (sg_ipmb *)calloc((size_t)e->wmb * e->hmb, sizeof(sg_ipmb));
@@ -3684,6 +3835,7 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
         for (int i = 0; i < e->wmb * e->hmb; i++) e->mb[i].type = T_NONE;
         e->n_mvsl = 0;
         if (e->ip_pred) memset(e->ip_pred, 0, fsz), memset(e->ip_res, 0, fsz * sizeof(int16_t));
+        if (e->rs_pred) memset(e->rs_pred, 0, fsz);
         e->pic_no++;
         /* the slices of this picture: (first macroblock, macroblock count), in the order they will be sent */
         int sl_first[512], sl_count[512], nsl = 0;
@@ -3776,6 +3928,7 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
               again:
                 begin_mb(e, addr);
                 e->had_dqp = 0, e->force_pcm = 0;
+                e->rs_on = 0, e->rs_dcmask = e->rs_acmask = 3, e->rs_qcls = 3;
                 const int force_skip = idx >= e->sk_from && idx < e->sk_to;
                 if (e->stim) {
                     const uint32_t h = hash32(p->seed ^ (uint32_t)((e->mbx >> 1) * 7919 + (e->mby >> 1) * 104729 + e->pic_no * 1299709));
@@ -3889,12 +4042,12 @@ size_t sg_encode(const sg_params *pp, uint8_t *stream, size_t cap, uint8_t *reco
             }
             out += n;
         }
-        if (p->trace_deblock || p->trace_intra) trace_picture(e, t, 0);
+        if (p->trace_deblock || p->trace_intra || p->trace_residual) trace_picture(e, t, 0);
         if (e->mvmb) trace_motion_picture(e, t);
         sg_db_count = g_rng;
         sg_deblock(e->cur, e->db, e->wmb, e->hmb, p->mono);
         sg_db_count = NULL;
-        if (p->trace_deblock || p->trace_intra) trace_picture(e, t, 1);
+        if (p->trace_deblock || p->trace_intra || p->trace_residual) trace_picture(e, t, 1);
         if (e->field) {
             e->cur->is_ref = e->nal_ref_idc ? 1 : 0; /* (short-term or not: what colZeroFlag asks of RefPicList1[0]; the window lives on the frames) */
             if (e->nal_ref_idc && p->bframes > 0) { /* a later B field may take this field as its co-located picture */
@@ -3948,7 +4101,7 @@ done:
     for (int i = 0; i < 6; i++) free(e->pics[i].pl[0]), free(e->pics[i].motion), free(e->fpics[i][0].pl[0]), free(e->fpics[i][1].pl[0]), free(e->fpics[i][0].motion), free(e->fpics[i][1].motion);
     free(e->mb);
     free(e->db);
-    free(e->ip_pred), free(e->ip_res), free(e->ipmb), free(e->mvmb);
+    free(e->ip_pred), free(e->ip_res), free(e->ipmb), free(e->mvmb), free(e->rs_pred), free(e->rsmb);
     free(e->src);
     free(frame_src);
     free(e->sgmap);

@@ -95,6 +95,8 @@ extern _Thread_local int32_t *sg_db_count;
 /* field pictures: coefficients in field scan order (8.5.6, 8.5.7); deblocking with the rules for field macroblocks (8.7.2.1:
  * horizontal edges of intra macroblocks get bS 3, vertical vector differences count from 4 quarter FRAME samples = 2 field ones) */
 void sg_set_field_mode(int on);
+/* the raster position (x + 4 * y, x + 8 * y) of scan index k of a block of n = 16 / 64 coefficients in the mode that is set */
+int sg_scan_pos(int n, int k);
 /* on: the quantisers drop levels that would take a scaled coefficient or a transform intermediate out of the 16-bit range of 8.5.12
  * (scaling lists with large entries); sg_guard_zeroed counts them since the call */
 void sg_set_range_guard(int on);

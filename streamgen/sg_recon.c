@@ -322,6 +322,7 @@ void sg_set_field_mode(int on) {
     g_scan4 = on ? field_scan4x4 : sg_zigzag4x4;
     g_scan8 = on ? field_scan8x8 : sg_zigzag8x8;
 }
+int sg_scan_pos(int n, int k) { return n == 64 ? g_scan8[k] : g_scan4[k]; }
 
 /* ------------------------------------------------------------------ scaling + inverse transforms */
 static void inv4(int *m) { /* m raster 4x4, in place: 8.5.12.2 */

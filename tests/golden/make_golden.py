@@ -151,6 +151,32 @@ def intra_vectors():
 
 intra_vectors()
 
+
+def residual_vectors():
+    """tests/residualutil.py: the recipes whose residual decoding (8.5) is counted cell by cell, and the largest dequantised coefficient per class."""
+    import residualutil
+    out, lines, max_d = {}, [], {}
+    for name in sorted(residualutil.RECIPES):
+        s, rec, _ = streamgen.encode(**residualutil.RECIPES[name])
+        cells = residualutil.Counter()
+        for p in residualutil.reconstruct_stream(streamgen.last_residual_trace()):
+            cells.update(p.cells)
+            for k, v in p.max_d.items():
+                max_d[k] = max(max_d.get(k, 0), v)
+        lines.append(residualutil.cell_line(name, cells))
+        frames, _ = oracle.decode(s, crop=False)
+        assert (frames == rec).all(), name
+        out[name] = {"stream_md5": hashlib.md5(s).hexdigest(), "frames_md5": hashlib.md5(rec.tobytes()).hexdigest(), "stream_bytes": len(s)}
+    json.dump(out, open(os.path.join(HERE, "residual_md5.json"), "w"), indent=1, sort_keys=True)
+    open(os.path.join(HERE, "residual_counters.txt"), "w").write(
+        "The cells of 8.5 that the yardstick of tests/residualutil.py counts on the residual trace of each recipe there, at the seeds chosen there:\n"
+        "per family, distinct cells reached / decisions counted.  T: per class the power of two of residualutil.T and the largest dequantised magnitude\n"
+        "the recipes reach together.\n" + "\n".join(lines) + "\n" + residualutil.max_line(max_d) + "\n")
+    print("wrote", len(out), "residual vectors")
+
+
+residual_vectors()
+
 # the characterisation trace of the product's picture management (tests/dpbtrace.py; CPU, null device): MD5 of the trace text of every case.  It
 # pins what the code DOES, so it is written once and not again for a change that is meant to keep behaviour.  Only with --dpb-trace.
 if "--dpb-trace" in sys.argv[1:]:

@@ -103,7 +103,8 @@ def test_generator_open_gop_off_and_refusals(sg):
     kw = dict(rautil.RECIPES["b"], frames=8)
     assert sg.encode(**dict(kw, open_gop_period=0))[0] == sg.encode(**{k: v for k, v in kw.items() if k != "open_gop_period"})[0]
     assert not sg.last_features() & sg.FEATURE_OPEN_GOP and sg.last_entries() == []
-    assert sg.Params._fields_[-1][0] == "open_gop_period"
+    # (appended to the struct; the two fields of the residual trace and stimulus were appended after it)
+    assert [f[0] for f in sg.Params._fields_[-3:]] == ["open_gop_period", "trace_residual", "residual_stim"]
     for extra in (dict(mmco=1), dict(rplm=1), dict(idr_long_term=1), dict(fn_gap_period=3), dict(wp_range=2, weighted_pred=1), dict(direct_temporal=1)):
         with pytest.raises(RuntimeError, match="open_gop_period"):
             sg.encode(**dict(rautil.RECIPES["a"], frames=8, **extra))
