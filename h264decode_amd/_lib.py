@@ -99,6 +99,14 @@ def load_hooks():
         # 1 while a K11 launch is recorded that the next execute's entropy stream waits for
         _hooks.h264mi_internal_side_pending.argtypes = [ctypes.c_void_p, ctypes.POINTER(I32)]
         _hooks.h264mi_internal_side_pending.restype = I32
+        # pass groups: the plan (level-0 slices, resident entropy wavefronts, pictures per reconstruction launch, B slices), the group size forced
+        # (0 / 2 / 3; -1: the plan), and the pass executed last with the pass whose reconstruction its entropy stage was gated on (-1: none)
+        _hooks.h264mi_internal_pass_group_plan.argtypes = [I32, I32, I32, I32]
+        _hooks.h264mi_internal_pass_group_plan.restype = I32
+        _hooks.h264mi_internal_set_pass_group.argtypes = [ctypes.c_void_p, I32]
+        _hooks.h264mi_internal_set_pass_group.restype = I32
+        _hooks.h264mi_internal_pass_waits.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+        _hooks.h264mi_internal_pass_waits.restype = I32
     return _hooks
 
 

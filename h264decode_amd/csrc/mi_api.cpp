@@ -329,6 +329,7 @@ extern "C" int32_t h264mi_decoder_create(const h264mi_config *cfg_, h264mi_decod
         hipDeviceProp_t prop;
         TRY_ALLOC(hipGetDeviceProperties(&prop, cfg->device));
         const int ncu = prop.multiProcessorCount;
+        d->n_cus = ncu;
         int ent_cus = 0;
         hook_create_entropy(d, &ent_cus);
         const int words = (ncu + 31) / 32;
@@ -395,6 +396,7 @@ extern "C" int32_t h264mi_decoder_create(const h264mi_config *cfg_, h264mi_decod
     // cross-workgroup hand-off state of the banded kernels; H264MI_X_WGS = 0 switches them off, n: up to n workgroups per launch
     if (const char *e = getenv("H264MI_X_WGS")) d->x_max_wgs = std::min(std::max(atoi(e), 0), d->x_cap);
     hook_create_k5(d);
+    hook_create_pass_group(d);
     DEV_ALLOC(d->d_xring, static_cast<size_t>(d->x_cap) * (d->Wmax / 16) * 24 * sizeof(unsigned long long));
     DEV_ALLOC(d->d_xdone, static_cast<size_t>(d->x_cap3) * (d->Wmax / 16) * sizeof(uint32_t));
     DEV_ALLOC(d->d_xctl, 8 * 128);

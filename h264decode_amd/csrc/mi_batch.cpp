@@ -483,6 +483,11 @@ extern "C" int32_t h264mi_batch_prepare(h264mi_decoder *d, int32_t n_streams, co
     if (d->conceal) concealment_tables(g);
     r = upload(d, g, launch_lists(d, g));
     if (r != H264MI_OK) return r;
+    {
+        int launches = 0, pics = 0; // pictures per reconstruction launch: the mean over the batch's waves
+        for (const Stage::Wave &W : g.waves) launches += W.all.n > 0, pics += static_cast<int>(W.all.n);
+        g.pass_group = mi_pass_group(g.levels.empty() ? 0 : g.levels[0].n, d->n_cus * 4 * mi_entropy_waves_per_simd(g.ent_kernel), launches ? pics / launches : 0, g.n_bext > 0);
+    }
     g.info.n_frames = 0; // frames that go out with this batch (a frame coded as two field pictures counts once, where its second field is)
     for (const auto &o : g.out) g.info.n_frames += static_cast<int32_t>(o.size());
     g.info.n_slices = g.n_slices, g.info.bitstream_bytes = static_cast<int64_t>(g.bits_used);
@@ -536,9 +541,24 @@ static int execute_stage(h264mi_decoder *d, int stage_idx, bool exclusive) {
     auto mark = [&](int kind) {
         if (prof) hipEventRecord(next_event(d, ei, kind), d->stream);
     };
-    // Pass n uses buffer set n&1.  Entropy runs on its own stream so that the entropy kernels of
-    // pass n+1 overlap the reconstruction kernels of pass n; set reuse is fenced by events.
+    // Pass n uses record set n % MI_SETS and entropy stream n & 1.  Entropy runs on a stream of its own so that the entropy kernels of
+    // passes n+1 and n+2 run ahead of the reconstruction kernels of pass n; set reuse is fenced by events.
     const int set = static_cast<int>(d->pass % MI_SETS);
+    // Pass groups (mi_pass_group): the entropy stages of G consecutive passes start together, behind the reconstruction of every pass before the
+    // group -- the gate, ev_rec of the last pass executed before the group opened.  EVERY pass of the group waits for it: the host enqueues far
+    // ahead, and a later pass of the group that waited for pass n - MI_SETS alone would start inside the previous group's reconstruction and keep
+    // its workgroups off the chip.  The gate only adds ordering behind strictly earlier passes.  G <= MI_SETS, so the gate's event is not
+    // recorded again before the group's last pass has enqueued its wait (its own ev_rec is the first of that set since).  A serialised pass
+    // (profiling, exclusive) and a pass whose plan says "ungrouped" close the open group.
+    int group = g.pass_group;
+    if (d->pass_group_force >= 0 && !g.n_bext) group = d->pass_group_force;
+    if (prof || group <= 0) d->group_left = 0;
+    else {
+        if (d->group_left <= 0) d->group_left = std::min(group, MI_SETS), d->group_gate = d->last_rec_pass >= 0 ? d->ev_rec[d->last_rec_pass % MI_SETS] : nullptr, d->group_gate_pass = d->last_rec_pass;
+        d->group_left--;
+    }
+    const bool gated = !prof && group > 0 && d->group_gate;
+    d->last_pass_gate = gated ? d->group_gate_pass : -1;
     hipStream_t es = d->ent_stream[d->pass & 1];
     MbRec *mbrec = d->d_mbrec[set];
     int16_t *coef = d->d_coef[set];
@@ -608,6 +628,7 @@ static int execute_stage(h264mi_decoder *d, int stage_idx, bool exclusive) {
             HIP_TRY(hipStreamWaitEvent(es, d->ev_rec[set], 0));
             HIP_TRY(hipStreamWaitEvent(es, d->ev_col[set], 0));
         }
+        if (gated) HIP_TRY(hipStreamWaitEvent(es, d->group_gate, 0));
         HIP_TRY(hipMemsetAsync(d->d_pool_head + set, 0, sizeof(uint32_t), es));
         launch_entropy(es, d->ent_lds_pad, (g.n_bext || d->last_pass_had_b) && d->pass > 0, d->ev_ent[set]);
         d->last_pass_had_b = g.n_bext > 0;
@@ -677,6 +698,7 @@ static int execute_stage(h264mi_decoder *d, int stage_idx, bool exclusive) {
         mark(3);
     }
     HIP_TRY(hipEventRecord(d->ev_rec[set], rs));
+    d->last_rec_pass = static_cast<int64_t>(d->pass);
     if (!prof) HIP_TRY(hipStreamWaitEvent(d->stream, d->ev_rec[set], 0)); // the caller's stream sees the finished pass
     d->pass++;
     HIP_TRY(hipGetLastError());

@@ -108,6 +108,7 @@ struct Stage {
     BSliceExt *d_bext = nullptr, *h_bext = nullptr; // one per B slice
     int n_bext = 0;
     int ent_kernel = MI_ENT_K_GENERAL;       // the I/P entropy kernel of level 0 (mi_entropy_kernel_choice), decided when the batch is prepared
+    int pass_group = 0;                      // passes over this batch whose entropy stages are released together (mi_pass_group; 0: ungrouped), decided with it
     int n_slices = 0, n_pics = 0, wmb_max = 0, hmb_max = 0, mbs_max = 0;
     uint64_t mb_used = 0;
     // ---- the batch's host-side facts: one record per picture, per slice, per reconstruction wave and per entropy level
@@ -232,6 +233,16 @@ struct h264mi_decoder {
     hipEvent_t ev_user = nullptr;
     hipEvent_t ev_ent[MI_SETS] = {}, ev_rec[MI_SETS] = {}, ev_col[MI_SETS] = {};
     uint64_t pass = 0; // execute() counter
+    // Pass groups (mi_pass_group): the entropy stages of up to Stage::pass_group consecutive passes are released together, behind the reconstruction
+    // of everything before the group.  group_left: passes that may still join the open group (0: none is open); group_gate: ev_rec of the last pass
+    // executed before the group opened (nullptr for the first group of a decoder), which every entropy launch of the group waits for besides its
+    // set's own fences; group_gate_pass: that pass (-1: none).  last_rec_pass: the pass that recorded an ev_rec last (-1: none yet).
+    int group_left = 0;
+    hipEvent_t group_gate = nullptr;
+    int64_t group_gate_pass = -1, last_rec_pass = -1;
+    int64_t last_pass_gate = -1;  // the gate of the pass executed last (-1: it waited for none), for the test hooks
+    int pass_group_force = -1;    // 0 / 2 / 3: instead of the plan for batches without B slices; -1: the plan (set by the hooks build only)
+    int n_cus = 0;                // compute units of the device
     int last_exec_stage = -1, last_exec_set = 0; // staging set and record set of the most recent execute (ensure_b_buffers)
     bool last_pass_had_b = false;
     int dbprep_launches[2] = {0, 0};     // launches of the last execute by kernel (MI_DBPREP_K_*), for the test hooks
@@ -331,6 +342,7 @@ int drain(h264mi_decoder *d); // both entropy streams, the reconstruction stream
 // ---- mi_hooks.cpp: the measurement switches of the hooks build, called where they act; in the product build they do nothing
 void hook_create_entropy(h264mi_decoder *d, int *ent_cus); // H264MI_ENT_LDS_PAD, H264MI_ENT_CUS
 void hook_create_k5(h264mi_decoder *d);                    // H264MI_K5_WAVES
+void hook_create_pass_group(h264mi_decoder *d);            // H264MI_PASS_GROUP
 int hook_entropy_kernel(int chosen);                       // H264MI_ENT_GENERIC
 int hook_dbprep_kernel(int chosen);                        // H264MI_DBPREP_GENERIC
 void hook_after_sync(const h264mi_decoder *d);             // H264MI_SLICE_STATS, H264MI_SLICE_TIMELINE

@@ -15,6 +15,7 @@
 #if !defined(H264MI_TEST_HOOKS)
 void hook_create_entropy(h264mi_decoder *, int *) {}
 void hook_create_k5(h264mi_decoder *) {}
+void hook_create_pass_group(h264mi_decoder *) {}
 int hook_entropy_kernel(int chosen) { return chosen; }
 int hook_dbprep_kernel(int chosen) { return chosen; }
 void hook_after_sync(const h264mi_decoder *) {}
@@ -26,6 +27,11 @@ void hook_create_entropy(h264mi_decoder *d, int *ent_cus) {
 }
 void hook_create_k5(h264mi_decoder *d) { // fewer wavefronts per picture in k_deblock
     if (const char *e = getenv("H264MI_K5_WAVES")) d->k5_max_waves = std::min(std::max(atoi(e), 1), MI_DEBLOCK8_MAX_WAVES);
+}
+void hook_create_pass_group(h264mi_decoder *d) { // 0 / 2 / 3 instead of the plan (mi_pass_group) for batches without B slices
+    const char *e = getenv("H264MI_PASS_GROUP");
+    const int v = e ? atoi(e) : -1;
+    if (v == 0 || v == 2 || v == 3) d->pass_group_force = v;
 }
 int hook_entropy_kernel(int chosen) { // 1: the general kernel for CABAC launches too, as before there was a CABAC-only build; 2: k_entropy_c for Main launches, as before there was a Main build
     const char *e = getenv("H264MI_ENT_GENERIC");
@@ -151,6 +157,26 @@ extern "C" int32_t h264mi_internal_set_dbprep_rows(h264mi_decoder *d, int32_t ro
 extern "C" int32_t h264mi_internal_set_k5_waves(h264mi_decoder *d, int32_t n) {
     if (!d) return H264MI_EINVAL;
     d->k5_max_waves = std::min(std::max(static_cast<int>(n), 1), MI_DEBLOCK8_MAX_WAVES);
+    return H264MI_OK;
+}
+
+// Not part of the public ABI: the pass-group plan (mi_pass_group) of a batch with n_slices0 level-0 slices on a chip that holds `capacity` entropy
+// wavefronts, pics_per_launch pictures per reconstruction launch, with or without B slices: 0 ungrouped, else the passes per group
+extern "C" int32_t h264mi_internal_pass_group_plan(int32_t n_slices0, int32_t capacity, int32_t pics_per_launch, int32_t has_b) {
+    return mi_pass_group(n_slices0, capacity, pics_per_launch, has_b != 0);
+}
+// Not part of the public ABI: passes per group for the executes to come, whatever the plan says -- 0, 2 or 3; -1: the plan again.  A batch with B slices
+// stays ungrouped.  (Short test streams never oversubscribe the chip.)
+extern "C" int32_t h264mi_internal_set_pass_group(h264mi_decoder *d, int32_t g) {
+    if (!d || !(g == -1 || g == 0 || g == 2 || g == 3)) return H264MI_EINVAL;
+    d->pass_group_force = g;
+    return H264MI_OK;
+}
+// Not part of the public ABI, reports only: the pass counter of the pass executed last, and the pass whose reconstruction (ev_rec) its entropy stage
+// was gated on as a member of a group (-1: none -- an ungrouped or serialised pass, or a pass of a decoder's first group)
+extern "C" int32_t h264mi_internal_pass_waits(h264mi_decoder *d, int64_t *pass, int64_t *gate_pass) {
+    if (!d || !pass || !gate_pass) return H264MI_EINVAL;
+    *pass = static_cast<int64_t>(d->pass) - 1, *gate_pass = d->last_pass_gate;
     return H264MI_OK;
 }
 

@@ -140,6 +140,22 @@ static inline int mi_entropy_kernel_choice(int n_cabac, int n_cavlc, bool slice_
     if (n_cavlc != 0 || n_cabac <= 0) return MI_ENT_K_GENERAL;
     return n_t8x8_mono == 0 ? MI_ENT_K_MAIN : MI_ENT_K_CABAC;
 }
+// Wavefronts of an I/P entropy build that a SIMD holds (amdgpu_waves_per_eu of the build: 512 VGPRs / 80, the slice-group build 512 / 102): with the
+// chip's CUs x 4 SIMDs the resident capacity that mi_pass_group compares a launch with.
+static inline int mi_entropy_waves_per_simd(int ent_kernel) { return ent_kernel == MI_ENT_K_FMO ? 5 : 6; }
+// Pass groups: how many consecutive passes over a batch release their entropy stages together (execute_stage: the gate), 0 = every pass on its own,
+// behind the reconstruction of pass n - MI_SETS only.  A level-0 launch of more slices than the chip holds wavefronts (capacity) runs a second,
+// underfilled round, and while it runs no reconstruction workgroup becomes resident ("Pass pipeline"): there the stages of
+// consecutive passes time-slice, and two entropy launches side by side fill each other's tail.  Not grouped: a launch that fits (its slice chains
+// already overlap across passes) and a batch with B slices (its levels are fenced between passes).  pics_per_launch (the batch's mean pictures per
+// reconstruction launch) decides nothing yet: no measurement has shown banded launches -- few pictures, each spread over several workgroups -- losing
+// behind a group.  The group may not be larger than MI_SETS: the gate is an event of a record set.
+#define MI_PASS_GROUP_DEFAULT 2
+static inline int mi_pass_group(int n_slices0, int capacity, int pics_per_launch, bool has_b) {
+    (void)pics_per_launch;
+    if (has_b || capacity <= 0 || n_slices0 <= capacity) return 0;
+    return MI_PASS_GROUP_DEFAULT;
+}
 // Which k_dbprep kernel runs on the pictures complete with a level: the one-lane-per-macroblock kernel if none of them has B slices (n_has_b) and none
 // leaves a ColRec array (n_save_col); else -- one such picture is enough -- the general one.
 enum { MI_DBPREP_K_GENERIC = 0, MI_DBPREP_K_IP = 1 };
